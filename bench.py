@@ -10,12 +10,17 @@ resident in HBM before the timed region.  One JSON line on stdout (rank 0).
          --master-port P bench.py --gpus N --steps K --warmup W
   python bench.py --gpus N            (no WORLD_SIZE in the environment: starts the line above as a child)
 
-Timed region (warm-up, then the median of 5 runs).  The engines fold their pivots
-into the stored representation once per `update_block` pivots (the "flush"), so a window that is not a
-whole number of blocks would leave amortised work outside the clock.  The timed region is therefore
-5 windows of `steps_per_window` = max(K, 4 * update_block) rounded UP to whole blocks, the first one
-starting right after a flush; `steps` in the JSON is that actual pivot count per window, `value` =
-steps / median window time.
+Timed region of the headline: W warm-up pivots, a flush, then exactly K pivots under one clock
+(`steps` = K, `ms_per_step` = that time / K, `value` = 1000 / ms_per_step).  The LP ends after a
+bounded number of pivots (SOLVE_PIVOTS); K beyond that is timed over fresh solves of the same LP, the
+clock stopped while the next one is set up.  --dump-outputs DIR writes the state the last timed pivot
+left (x_B, the basis, the objective) as .npy files.
+
+--full adds everything else the line used to carry: the kernel-event windows (SURVEY.md section 8d:
+the engines fold their pivots into the stored representation once per `update_block` pivots, so each of
+5 windows is max(K, 4 * update_block) pivots rounded UP to whole blocks, starting right after a flush,
+all of them on one solve of the LP -- window_plan() cuts them to what fits; `timing`, `roofline`,
+`kernels`), the revised engine, c1 / c2 / c4 / c5, the sparse path and the CPU baselines.
 
 Workloads (config.workload):
   dense10k  (default) m = 10,000 rows, n = 10,000 structural columns (+10,000 slacks), f64,
@@ -27,11 +32,11 @@ Engines (--engine):
             every K pivots.  Same pivots as the revised engine (parity-tested).
   revised   explicit dense inverse `Carry<_, BasisInverseRows<_>>`: PRICE streams A (8 m n bytes) and
             FTRAN streams B^-1 (8 m^2 bytes) at every pivot -- the FTRAN/PRICE HBM-roofline numbers.
-  At N = 1 the default run measures the tableau engine as `value` and adds the revised engine's
+  At N = 1 the --full run measures the tableau engine as `value` and adds the revised engine's
   numbers under "revised_engine" and inside "roofline".
 N > 1: the same LP (strong scaling); the stored tableau columns are split contiguously over the
 ranks, ONE all-gather of [key, j, d_j, alpha(m)] candidates per pivot over RCCL, everything else local.
-Every N also reports "c4" (10,000 x 50,000, the shape whose flush is large enough for sharding to pay).
+With --full every N also reports "c4" (10,000 x 50,000, the shape whose flush is large enough for sharding to pay).
 """
 import argparse
 import json
@@ -52,6 +57,13 @@ HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s
 F64_MFMA_PEAK_TF = 78.6    # FP64 matrix 78.6 TFLOP/s
 WINDOWS = 5                # median of 5 runs
 CPU_BUDGET_S = 20.0        # cpu_baseline: bounded sample (10-30 s of CPU work)
+# pivots a fresh solve of each workload is taken through, below the number it ends after (scripts/soak_dense10k.py:
+# dense10k 54,006, c4 91,579, c2 5,947): a solve that ended inside the timed region would leave no-op launches on the clock
+SOLVE_PIVOTS = {"dense10k": 50000, "c2": 5000, "c4": 85000}
+CPU_WARMUP_MAX = 20        # cpu_baseline: untimed oracle pivots before the sample (~6 per second at 10,000 x 10,000)
+STEPS_NOTE = ("exactly `steps` pivots under one clock, after `warmup` pivots and a flush; the update block still pending at the end "
+              "is not flushed on the clock.  More warm-up and timed pivots than one solve of the LP has (SOLVE_PIVOTS) run over "
+              "`solves` fresh solves of the same LP, the clock stopped while each is set up")
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -78,6 +90,31 @@ def window_steps(requested, block):
         return requested
     want = max(requested, 4 * block)
     return (want + block - 1) // block * block
+
+
+def solve_plan(steps, warmup, per_solve):
+    """(untimed warm-up pivots, timed pivots) per fresh solve of the LP: `warmup` pivots, then exactly `steps`, no solve taken
+    past `per_solve` pivots."""
+    steps, warmup = max(int(steps), 0), max(int(warmup), 0)
+    plan = []
+    while warmup > 0 or steps > 0:
+        warm = min(warmup, per_solve)
+        timed = min(steps, per_solve - warm)
+        plan.append((warm, timed))
+        warmup, steps = warmup - warm, steps - timed
+    return plan
+
+
+def window_plan(requested, warmup, block, per_solve):
+    """(warm-up, pivots per window) of the WINDOWS kernel-event windows, all on one solve of the LP: windows as window_steps()
+    makes them, but only as long as WINDOWS of them still fit into the `per_solve` pivots after the warm-up (rounded down to
+    whole blocks); the warm-up is cut where it would leave no room for windows of 4 blocks."""
+    shortest = 4 * block if block > 0 else 1
+    warm = max(0, min(int(warmup), per_solve - WINDOWS * shortest))
+    room = (per_solve - warm) // WINDOWS
+    if block > 0:
+        room = room // block * block
+    return warm, min(window_steps(requested, block), room)
 
 
 def algorithmic_bytes(kind, m, n, world, block):
@@ -175,7 +212,7 @@ def section(res, workload, m, n, world, kind):
     alg = algorithmic_bytes(kind, m, n, world, res["block"])
     kernels = kernel_table(res.get("prof"), alg["launch"], alg["flops"])
     roof = kernel_roofline(kind, workload, kernels, alg)
-    out = {"value": steps / med, "unit": "iterations/s", "steps": steps, "windows": len(res["window_s"]),
+    out = {"value": steps / med, "unit": "iterations/s", "steps": steps, "warmup": res.get("warmup"), "windows": len(res["window_s"]),
            "ms_per_step": ms_per_step, "window_ms": [round(w * 1e3, 4) for w in res["window_s"]],
            "update_block": res["block"], "kernels": kernels, "roofline": roof,
            "pivot_roofline": pivot_roofline(alg, ms_per_step), "objective_after_run": res.get("objective"),
@@ -183,11 +220,34 @@ def section(res, workload, m, n, world, kind):
     return out
 
 
-def assemble(args_ns, world, primary_kind, primary, secondary=None, c2=None, c4=None, sparse=None, cpu=None,
-             loop_kind=None):
-    """The ONE JSON line.  `primary` etc. are outputs of section(); any of the optional parts may be None, and no
-    kernel class is assumed to be present."""
+def line_config(args_ns, world, kind, block, loop_kind=None):
     m, n, seed = WORKLOADS[args_ns.workload]
+    cfg = {"workload": f"{args_ns.workload}: synthetic dense LP {m}x{n} f64 (+{m} slack columns), SteepestDescent, "
+                       + ("dense tableau with blocked f64-MFMA updates" if kind == "tableau" else "explicit dense basis inverse"),
+           "m": m, "n": n, "seed": seed, "engine": kind, "update_block": block, "steps_note": STEPS_NOTE,
+           "parallelism": "single GPU" if world == 1 else
+           (f"stored tableau columns sharded x{world}, one all-gather per pivot" if kind == "tableau"
+            else f"columns of A and rows of B^-1 sharded x{world}")}
+    if loop_kind:
+        cfg["shard_loop"] = loop_kind
+    return cfg
+
+
+def headline_line(args_ns, world, kind, head, loop_kind=None):
+    """The line of a plain run: `head` is what measure_steps() returned."""
+    cfg = dict(line_config(args_ns, world, kind, head["block"], loop_kind), solves=head["solves"])
+    return {"metric": "simplex iterations/sec", "value": head["steps"] / head["seconds"], "unit": "iterations/s", "n_gpus": world,
+            "steps": head["steps"], "steps_requested": args_ns.steps, "warmup": args_ns.warmup,
+            "ms_per_step": head["seconds"] * 1e3 / head["steps"], "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+            "dtype": "f64", "data": "synthetic", "config": cfg, "objective_after_run": head["objective"]}
+
+
+def assemble(args_ns, world, primary_kind, primary, secondary=None, c2=None, c4=None, sparse=None, cpu=None,
+             loop_kind=None, head=None):
+    """The ONE JSON line of --full.  `primary` etc. are outputs of section(); any of the optional parts may be None, and no
+    kernel class is assumed to be present.  `head` (measure_steps()) gives value, steps and ms_per_step; without it the
+    windows do."""
+    m, n, _ = WORKLOADS[args_ns.workload]
     roofline = dict(primary["roofline"]) if primary.get("roofline") else \
         {"kernel": None, "bound": "hbm", "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None, "traffic": None,
          "note": "no bracketed launch of a streaming kernel in the timed windows (kernel events off)"}
@@ -200,29 +260,27 @@ def assemble(args_ns, world, primary_kind, primary, secondary=None, c2=None, c4=
                    "traffic": load_traffic(args_ns.workload, TRAFFIC_KEY[name])}
             for name in ("ftran", "price", "update_inverse", "flush") if "GBps" in k2.get(name, {})}
         roofline["revised_engine"]["pivot"] = secondary["pivot_roofline"]
-    out = {
-        "metric": "simplex iterations/sec", "value": primary["value"], "unit": "iterations/s", "n_gpus": world,
-        "steps": primary["steps"], "steps_requested": args_ns.steps, "warmup": args_ns.warmup, "ms_per_step": primary["ms_per_step"],
-        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": f"{args_ns.workload}: synthetic dense LP {m}x{n} f64 (+{m} slack columns), SteepestDescent, "
-                               + ("dense tableau with blocked f64-MFMA updates" if primary_kind == "tableau"
-                                  else "explicit dense basis inverse"),
-                   "m": m, "n": n, "seed": seed, "engine": primary_kind, "update_block": primary["update_block"],
-                   "steps_note": "--steps is honoured as AT LEAST: a timed window is a whole number of update blocks (max(steps, 4 blocks) "
-                                 "rounded up to the block), because a window that ends inside a block would leave the block's one "
-                                 "O(m n) flush out of the time; `steps` is what was timed, `steps_requested` what was asked for",
-                   "parallelism": "single GPU" if world == 1 else
-                   (f"stored tableau columns sharded x{world}, one all-gather per pivot" if primary_kind == "tableau"
-                    else f"columns of A and rows of B^-1 sharded x{world}")},
-        "timing": {"steps_requested": args_ns.steps, "windows": primary["windows"], "window_ms": primary["window_ms"],
-                   "statistic": "median window; every window is a whole number of update blocks and starts right after a flush"},
+    if head is not None:
+        out = headline_line(args_ns, world, primary_kind, head, loop_kind)
+    else:
+        out = {"metric": "simplex iterations/sec", "value": primary["value"], "unit": "iterations/s", "n_gpus": world,
+               "steps": primary["steps"], "steps_requested": args_ns.steps, "warmup": args_ns.warmup,
+               "ms_per_step": primary["ms_per_step"], "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+               "dtype": "f64", "data": "synthetic", "config": line_config(args_ns, world, primary_kind, primary["update_block"], loop_kind),
+               "objective_after_run": primary.get("objective_after_run")}
+    out.update({
+        "timing": {"steps_requested": args_ns.steps, "steps_per_window": primary["steps"], "windows": primary["windows"],
+                   "window_ms": primary["window_ms"], "value": primary["value"], "ms_per_step": primary["ms_per_step"],
+                   "statistic": "median window; every window is a whole number of update blocks and starts right after a flush",
+                   "warmup": primary.get("warmup"),
+                   "window_note": "a window is max(steps, 4 blocks) pivots rounded up to the block, because a window that ends inside a "
+                                  "block would leave the block's one O(m n) flush out of the time; all windows and their warm-up on one "
+                                  "solve of the LP (window_plan: longer windows are cut to whole blocks that fit, a longer warm-up to what "
+                                  "leaves room); kernels bracketed by HIP events"},
         "roofline": roofline, "kernels": primary["kernels"],
         "kernel_event_stride": primary.get("kernel_event_stride"),
-        "objective_after_run": primary.get("objective_after_run"),
         "reference_iteration_algorithmic_bytes": 8.0 * m * n + 24.0 * m * m,
-    }
-    if loop_kind:
-        out["config"]["shard_loop"] = loop_kind
+    })
     if secondary is not None:
         out["revised_engine"] = dict(secondary, note="explicit dense inverse (Carry<_, BasisInverseRows<_>>): PRICE streams A, "
                                      "FTRAN streams B^-1 every pivot; GB/s = algorithmic bytes / HIP-event duration")
@@ -692,11 +750,16 @@ def spawn_ranks(n, argv):
     return proc.returncode
 
 
-def main():
+def parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=200, help="pivots timed for the headline (exactly this many)")
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: kernel-event windows and rooflines, the revised engine, c1 / c2 / c4 / c5, "
+                         "the sparse path, the CPU baselines (the --no-* options and --quick trim this)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed pivot left (x_B, basis, objective) to DIR/<name>.npy, float64")
     ap.add_argument("--workload", default="dense10k", choices=sorted(WORKLOADS))
     ap.add_argument("--engine", default="default", choices=["default", "revised", "tableau", "lu"],
                     help="default = tableau as the measured engine (+ the revised engine's numbers at N = 1); lu = the sparse path as "
@@ -713,9 +776,9 @@ def main():
     ap.add_argument("--no-scale", action="store_true", help="skip the 63,988-row multi-commodity section (LU engine, third kernel layout)")
     ap.add_argument("--no-c5", action="store_true", help="skip the configs[4] (MIPLIB relaxations, degenerate pivot counts) section")
     ap.add_argument("--quick", action="store_true",
-                    help="the line's schema in a fraction of the time (tests/test_bench_gpu.py): no c4 / c5 / sparse.large / "
-                         "sparse.scale / sparse.replicas, CPU samples of 3 s; the headline, roofline, cpu_baseline, c1, c2 and the 25FV47 "
-                         "section are measured as always")
+                    help="implies --full: the line's schema in a fraction of the time (tests/test_bench_gpu.py): no c4 / c5 / "
+                         "sparse.large / sparse.scale / sparse.replicas, CPU samples of 3 s; the headline, roofline, cpu_baseline, c1, c2 "
+                         "and the 25FV47 section are measured as always")
     ap.add_argument("--no-kernel-events", action="store_true", help="do not bracket kernels with HIP events")
     ap.add_argument("--event-stride", type=int, default=64,
                     help="bracket the kernels of every n-th pivot with HIP events (1 = every pivot)")
@@ -723,7 +786,20 @@ def main():
                     help="N > 1: pivot loop inside the library calling RCCL itself, or the Python loop over torch.distributed")
     ap.add_argument("--force-sharded", action="store_true",
                     help="run the multi-GPU loop (torch.distributed collectives) even at N = 1 (rehearsal)")
-    args = ap.parse_args()
+    return ap
+
+
+def write_outputs(directory, head):
+    """What a caller of the timed path holds after its last pivot, float64: x_B by basis row, the basic column of every row,
+    the objective."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, values in (("x_basic", head["b"]), ("basis", head["basis"]), ("objective", [head["objective"]])):
+        np.save(os.path.join(directory, name + ".npy"), np.asarray(values, dtype=np.float64))
+
+
+def main():
+    args = parser().parse_args()
 
     # R engines on R streams run side by side only as far as the HIP runtime has hardware queues for them: its default of 4 capped
     # eight replicas at 2.7 x one (profiles/r04_replicas.md); 16 queues: 7.5 x.  The variable is read when the runtime initialises,
@@ -740,6 +816,7 @@ def main():
     if args.quick:
         global CPU_BUDGET_S
         CPU_BUDGET_S = 3.0
+        args.full = True
         args.no_c4 = args.no_c5 = args.no_scale = args.no_replicas = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(args.gpus, sys.argv[1:]))
@@ -750,11 +827,6 @@ def main():
     json_fd = os.dup(1)
     os.dup2(2, 1)
 
-    import numpy as np
-    import torch
-    import rust_lp_amd  # noqa: F401
-    from rust_lp_amd import MatrixData, engine, synthetic
-
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -764,9 +836,19 @@ def main():
     if rehearse:
         local_rank = 0
     args.gpus = world
-    torch.cuda.set_device(local_rank)
-    dev = torch.device("cuda", local_rank)
     sharded = world > 1 or args.force_sharded
+
+    import ctypes as C
+    import numpy as np
+    # a plain single-GPU run needs no torch: the engine allocates, fills and times on its own.  Where torch is used it is imported
+    # before the engine's library, so that both run on torch's HIP runtime (tests/conftest.py)
+    if args.full or sharded or args.engine == "lu":
+        import torch
+        torch.cuda.set_device(local_rank)
+        dev = torch.device("cuda", local_rank)
+    import rust_lp_amd  # noqa: F401
+    from rust_lp_amd import MatrixData, engine, synthetic
+
     if sharded:
         import torch.distributed as dist
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -811,9 +893,11 @@ def main():
     primary_kind = "tableau" if args.engine in ("default", "tableau") else "revised"
     loop_kind = {}
 
-    def measure(kind, workload):
-        """Build the engine of `kind` on the synthetic LP (generated in HBM), warm up, flush, and time WINDOWS
-        windows of whole update blocks."""
+    device_sync = lib.hipDeviceSynchronize              # of the HIP runtime the engine runs on (found among the library's dependencies)
+    device_sync.restype, device_sync.argtypes = C.c_int, []
+
+    def synthetic_md(kind, workload):
+        """The host side of the synthetic LP (b, c, bounds) and the engine's config; A is generated in HBM by relp_synth_fill_dense."""
         m, n, seed = WORKLOADS[workload]
         nums_b = n * (1000 + (synthetic.splitmix64(seed, 1, np.arange(m, dtype=np.uint64)) % np.uint64(1000)).astype(np.int64))
         nums_c = -(1000 + (synthetic.splitmix64(seed, 2, np.arange(n, dtype=np.uint64)) % np.uint64(1000)).astype(np.int64))
@@ -822,6 +906,88 @@ def main():
         cfg = engine.default_config(device=local_rank, poll_interval=1 << 20, shard_rank=rank, shard_count=world,
                                     engine=engine.ENGINE_TABLEAU if kind == "tableau" else engine.ENGINE_REVISED,
                                     update_block=args.update_block)
+        return md, cfg
+
+    def start(t, kind):
+        """Phase 1 of the slack basis (empty: one PRICE proves it) -> the engine's (run, flush), through the sharded loop if sharded."""
+        if not sharded:
+            done, oc = t.run(1)
+            assert oc == engine.PHASE_ONE_DONE, engine.OUTCOME_NAMES.get(oc)
+            return t.run, t.flush
+        from rust_lp_amd.sharded import NativeShardedLoop, ShardedPivotLoop
+        loop = None
+        if not rehearse and args.shard_loop == "native":
+            # the loop inside the library, RCCL called from C++ on the engine's stream
+            try:
+                loop = NativeShardedLoop(t, dist, dev)
+                loop_kind[kind] = "native (relp_shard_run, RCCL from C++)"
+            except engine.RelpError as e:             # agreed on by all ranks (all-reduce MIN inside)
+                print(f"[bench] native sharded loop unavailable, using the Python loop: {e}", file=sys.stderr)
+        if loop is None:
+            loop = ShardedPivotLoop(t, dist, dev, poll_interval=1 << 20)
+            loop_kind[kind] = "python (torch.distributed collectives)"
+        assert loop.finish_phase_one() == engine.PHASE_ONE_DONE
+        return loop.run, loop.flush
+
+    def timed(run, steps):
+        """Seconds `steps` pivots take, every rank done (the slowest rank's time)."""
+        if sharded:
+            dist.barrier()
+        assert device_sync() == 0                      # (flush and set-up only enqueue: none of it on the clock)
+        t0 = time.perf_counter()
+        done, oc = run(steps)
+        assert device_sync() == 0
+        if sharded:
+            dist.barrier()
+        dt = time.perf_counter() - t0
+        if sharded:
+            tt = torch.tensor([dt], dtype=torch.float64, device=dev if not rehearse else "cpu")
+            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+            dt = float(tt.item())
+        assert done == steps and oc == engine.RUNNING, f"only {done} of {steps} pivots were possible ({engine.OUTCOME_NAMES.get(oc)})"
+        return dt
+
+    def measure_steps(kind, workload):
+        """The headline: a fresh solve of the synthetic LP on the engine of `kind`, W warm-up pivots, a flush, then exactly K
+        pivots on the clock -- over as many fresh solves as solve_plan() asks for, the clock stopped while each is set up."""
+        m, n, seed = WORKLOADS[workload]
+        plan = solve_plan(K, W, SOLVE_PIVOTS[workload])
+        head = {"steps": K, "seconds": 0.0, "solves": len(plan)}
+        flushed = False
+        for i, (warm, steps) in enumerate(plan):
+            md, cfg = synthetic_md(kind, workload)
+            col_lo, col_hi = engine.shard_plan(md, cfg)
+            n_local = col_hi - col_lo
+            A = C.c_void_p()                                   # column-major m x n_local
+            assert lib.relp_device_alloc(C.byref(A), 8 * m * max(n_local, 1)) == 0, "device allocation failed"
+            t = None
+            try:
+                assert lib.relp_synth_fill_dense(A, m, m, n_local, seed, col_lo, None) == 0, "synthetic fill failed"
+                t = engine.Tableau(md, config=cfg, device_dense_ptr=A.value, device_dense_ld=m)
+                run, flush = start(t, kind)
+                if warm > 0:
+                    done, oc = run(warm)
+                    assert done == warm and oc == engine.RUNNING, "LP ended inside the warm-up"
+                if steps > 0 and not flushed:
+                    flush()                            # the clock starts with an empty update block
+                    flushed = True
+                if steps > 0:
+                    head["seconds"] += timed(run, steps)
+                if i == len(plan) - 1:
+                    head.update(block=t.update_block(), objective=t.objective_function_value())
+                    if args.dump_outputs and rank == 0:
+                        head.update(b=t.b(), basis=t.basis_indices())
+            finally:
+                if t is not None:
+                    t.close()
+                lib.relp_device_free(A)
+        return head
+
+    def measure(kind, workload):
+        """Build the engine of `kind` on the synthetic LP (generated in HBM), warm up, flush, and time WINDOWS
+        windows of whole update blocks."""
+        m, n, seed = WORKLOADS[workload]
+        md, cfg = synthetic_md(kind, workload)
         col_lo, col_hi = engine.shard_plan(md, cfg)
         n_local = col_hi - col_lo
         A = torch.empty((max(n_local, 1), m), dtype=torch.float64, device=dev)      # column-major m x n_local
@@ -830,29 +996,11 @@ def main():
         t = engine.Tableau(md, config=cfg, device_dense_ptr=A.data_ptr(), device_dense_ld=m)
         torch.cuda.synchronize()
         block = t.update_block()
-        steps = window_steps(K, block)
-        if not sharded:
-            run, flush = t.run, t.flush
-            done, oc = t.run(1)                        # phase 1 is empty (slack basis): one PRICE proves it
-            assert oc == engine.PHASE_ONE_DONE, engine.OUTCOME_NAMES.get(oc)
-        else:
-            from rust_lp_amd.sharded import NativeShardedLoop, ShardedPivotLoop
-            loop = None
-            if not rehearse and args.shard_loop == "native":
-                # the loop inside the library, RCCL called from C++ on the engine's stream
-                try:
-                    loop = NativeShardedLoop(t, dist, dev)
-                    loop_kind[kind] = "native (relp_shard_run, RCCL from C++)"
-                except engine.RelpError as e:             # agreed on by all ranks (all-reduce MIN inside)
-                    print(f"[bench] native sharded loop unavailable, using the Python loop: {e}", file=sys.stderr)
-            if loop is None:
-                loop = ShardedPivotLoop(t, dist, dev, poll_interval=1 << 20)
-                loop_kind[kind] = "python (torch.distributed collectives)"
-            run, flush = loop.run, loop.flush
-            assert loop.finish_phase_one() == engine.PHASE_ONE_DONE
-        if W > 0:
-            done, oc = run(W)
-            assert done == W and oc == engine.RUNNING, "LP ended inside the warm-up"
+        warm, steps = window_plan(K, W, block, SOLVE_PIVOTS[workload])
+        run, flush = start(t, kind)
+        if warm > 0:
+            done, oc = run(warm)
+            assert done == warm and oc == engine.RUNNING, "LP ended inside the warm-up"
         flush()                                        # the first window starts with an empty update block
         if events:
             stride = coprime_stride(args.event_stride, block)
@@ -880,9 +1028,20 @@ def main():
         t.close()
         del A
         torch.cuda.empty_cache()
-        res = {"steps": steps, "window_s": windows, "prof": prof, "block": block, "objective": obj,
+        res = {"steps": steps, "warmup": warm, "window_s": windows, "prof": prof, "block": block, "objective": obj,
                "event_stride": stride if events else None}
         return section(res, workload, m, n, world, kind)
+
+    head = measure_steps(primary_kind, args.workload)
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, head)
+    if not args.full:
+        if rank == 0:
+            line = headline_line(args, world, primary_kind, head, loop_kind.get(primary_kind))
+            os.write(json_fd, (json.dumps(line) + "\n").encode())
+        if sharded:
+            dist.destroy_process_group()
+        return
 
     primary = measure(primary_kind, args.workload)
     solo = args.engine == "default" and not sharded and rank == 0
@@ -918,8 +1077,8 @@ def main():
         cpu = None
         if world == 1 and not args.no_cpu_baseline:
             m, n, seed = WORKLOADS[args.workload]
-            cpu = cpu_baseline(m, n, seed, W)
-        out = assemble(args, world, primary_kind, primary, secondary, c2, c4, sparse, cpu, loop_kind.get(primary_kind))
+            cpu = cpu_baseline(m, n, seed, min(W, CPU_WARMUP_MAX))
+        out = assemble(args, world, primary_kind, primary, secondary, c2, c4, sparse, cpu, loop_kind.get(primary_kind), head)
         if c1 is not None:
             out["c1"] = c1
         if c5 is not None:

@@ -1,28 +1,39 @@
 """The driver's benchmark command as a child process on the GPU box: one complete JSON line (round 1's run died with KeyError
-'GBps' and left BENCH_r01.json empty).  [r4] in its `--quick` form; the full line is checked on the recorded run of the round."""
+'GBps' and left BENCH_r01.json empty).  The plain command times exactly --steps pivots and nothing else; --full in its
+`--quick` form; the long sections are checked on the recorded run of round 4."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import bench  # noqa: E402
 
 
-def check_headline(out, quick):
+def check_headline(out, quick, recorded=False):
+    """`recorded`: a line of record from before --steps was timed exactly, when the kernel-event windows were the headline."""
     assert out["metric"] == "simplex iterations/sec" and out["unit"] == "iterations/s" and out["n_gpus"] == 1
     assert out["value"] > 1000 and out["higher_is_better"] is True and out["dtype"] == "f64" and out["vs_baseline"] is None
     block = out["config"]["update_block"]
-    assert block == 64 and out["steps"] % block == 0 and out["steps"] >= 4 * block
-    assert out["steps_requested"] == 20 and out["timing"]["steps_requested"] == 20 and "AT LEAST" in out["config"]["steps_note"]
+    window = out["steps"] if recorded else out["timing"]["steps_per_window"]
+    assert block == 64 and window % block == 0 and window >= 4 * block
+    assert out["steps_requested"] == 20 and out["timing"]["steps_requested"] == 20
+    if recorded:
+        assert "AT LEAST" in out["config"]["steps_note"]
+    else:
+        assert out["steps"] == 20 and out["config"]["solves"] == 1 and out["config"]["steps_note"] == bench.STEPS_NOTE
+        assert abs(out["timing"]["value"] - 1e3 / out["timing"]["ms_per_step"]) <= 1e-6 * out["timing"]["value"]
     assert out["timing"]["windows"] == 5 and len(out["timing"]["window_ms"]) == 5
     assert abs(out["value"] - 1e3 / out["ms_per_step"]) <= 1e-6 * out["value"]
     roof = out["roofline"]
     assert roof["kernel"] == "k_tab_flush_lds" and roof["bound"] == "hbm" and roof["unit"] == "GB/s" and roof["peak"] == 8000.0
     assert 0.2 < roof["frac"] < 1.0 and abs(roof["frac"] - roof["achieved"] / roof["peak"]) < 1e-3
-    assert roof["launches_timed"] == 5 * out["steps"] // block              # every flush of the timed windows is bracketed
+    assert roof["launches_timed"] == 5 * window // block                    # every flush of the timed windows is bracketed
     assert 0.0 < roof["pivot"]["frac"] < 1.0 and roof["pivot"]["algorithmic_bytes"] > 0
     assert 0.3 < roof["revised_engine"]["ftran"]["frac"] < 1.0 and 0.3 < roof["revised_engine"]["price"]["frac"] < 1.0
     cpu = out["cpu_baseline"]
@@ -86,15 +97,42 @@ def check_full_sections(out):
 
 
 def test_driver_command_quick_form_emits_one_complete_json_line():
-    """`--quick` (the full command took 130 of the tier's 372 s and the driver runs it anyway): the same
-    launcher, the same assembly, every key of the headline, `roofline` and `cpu_baseline`, the 25FV47 section and c1 / c2 measured
-    as always; the long sections are left to the driver's own run, whose recorded line tests/test_bench_json.py checks."""
-    cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--quick"]
+    """`--full --quick` (the full command took 130 of the tier's 372 s): the same launcher, the same
+    assembly, every key of the headline, `roofline` and `cpu_baseline`, the 25FV47 section and c1 / c2 measured as always; the
+    long sections are left to the recorded line tests/test_bench_json.py checks."""
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--quick"]
     p = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.strip()]
     assert len(lines) == 1, lines
     check_headline(json.loads(lines[0]), quick=True)
+
+
+def test_plain_command_times_exactly_the_requested_steps_and_dumps_its_outputs(tmp_path):
+    """The plain command times exactly --steps pivots and measures nothing else.  60,000 pivots are more than one solve of the LP
+    is taken through (bench.SOLVE_PIVOTS), so they run over two fresh solves.  --dump-outputs leaves the state of the last
+    timed pivot, and the same arguments give the same outputs."""
+    runs = {}
+    for tag, steps in (("long", 60000), ("a", 300), ("b", 300)):
+        d = tmp_path / tag
+        cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", str(steps), "--warmup", "5", "--dump-outputs", str(d)]
+        out = _one_line(subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600))
+        assert out["steps"] == out["steps_requested"] == steps and out["warmup"] == 5
+        assert out["config"]["solves"] == len(bench.solve_plan(steps, 5, bench.SOLVE_PIVOTS["dense10k"])) == (2 if tag == "long" else 1)
+        assert out["value"] > 1000 and abs(out["value"] * out["ms_per_step"] - 1e3) < 1e-9 * 1e3
+        for key in ("timing", "roofline", "kernels", "revised_engine", "c1", "c2", "c4", "c5", "sparse_engine", "cpu_baseline"):
+            assert key not in out, key
+        arrays = {name: np.load(d / f"{name}.npy") for name in ("x_basic", "basis", "objective")}
+        m, n = out["config"]["m"], out["config"]["n"]
+        assert all(a.dtype == np.float64 for a in arrays.values())
+        assert arrays["x_basic"].shape == (m,) and arrays["basis"].shape == (m,) and arrays["objective"].shape == (1,)
+        assert arrays["objective"][0] == out["objective_after_run"] and arrays["x_basic"].min() >= -1e-9 * max(1.0, arrays["x_basic"].max())
+        basis = arrays["basis"].astype(np.int64)
+        assert np.array_equal(basis, arrays["basis"]) and len(set(basis.tolist())) == m and 0 <= basis.min() and basis.max() < n + m
+        runs[tag] = arrays
+    np.testing.assert_array_equal(runs["a"]["basis"], runs["b"]["basis"])
+    for name in ("x_basic", "objective"):
+        np.testing.assert_allclose(runs["a"][name], runs["b"][name], rtol=1e-12, atol=1e-12)
 
 
 def test_sparse_path_as_replicas_is_what_gpus_n_engine_lu_runs():
@@ -119,7 +157,7 @@ def test_multi_rank_command_rehearsed_with_two_ranks_on_one_gpu():
     ranks on one device); launcher, rank wiring, sharded engines, barrier + max-over-ranks timing and the JSON assembly are the
     ones an 8-GPU node runs.  No scaling curve has been measured anywhere yet: this checks the path, not a speed."""
     env = dict(os.environ, RELP_BENCH_REHEARSE="1")
-    cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "20", "--warmup", "5"]
+    cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "20", "--warmup", "5", "--full"]
     out = _one_line(subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1500))
     assert out["n_gpus"] == 2 and out["scaling"] == "strong" and out["value"] > 10       # (gloo on the host carries every exchange)
     assert "sharded x2" in out["config"]["parallelism"] and "shard_loop" in out["config"]
@@ -142,7 +180,7 @@ def test_sparse_replicas_over_two_ranks_rehearsed_on_one_gpu():
 def test_sharded_loop_over_rccl_with_one_rank():
     """`--force-sharded` at N = 1: the native multi-GPU loop (relp_shard_run) with RCCL itself -- ncclCommInitRank from the id
     torch.distributed broadcasts, ncclAllGather between the kernels on the engine's stream -- on a communicator of one rank."""
-    cmd = [sys.executable, "bench.py", "--gpus", "1", "--force-sharded", "--steps", "20", "--warmup", "5", "--no-cpu-baseline"]
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--force-sharded", "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline"]
     out = _one_line(subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1500))
     assert out["n_gpus"] == 1 and out["value"] > 1000
     assert "native" in out["config"]["shard_loop"] and out["c4"]["value"] > 1000

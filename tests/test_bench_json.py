@@ -141,9 +141,10 @@ def test_event_stride_never_aliases_with_the_update_block(stride, block):
 
 
 def test_recorded_bench_line_of_the_round_is_complete():
-    """The driver's exact command (`python3 bench.py --gpus 1 --steps 20 --warmup 5`) run on an MI355X and recorded as
-    profiles/r04_bench.json: every section the GPU tier's `--quick` form leaves out (c4, c5, sparse.large, sparse.scale,
-    sparse.replicas) is checked here against the same assertions (tests/test_bench_gpu.py)."""
+    """The driver's command (`python3 bench.py --gpus 1 --steps 20 --warmup 5`, which carried every section before --full
+    did) run on an MI355X and recorded as profiles/r04_bench.json: every section the GPU tier's `--full --quick` form leaves
+    out (c4, c5, sparse.large, sparse.scale, sparse.replicas) is checked here against the same assertions
+    (tests/test_bench_gpu.py)."""
     path = os.path.join(ROOT, "profiles", "r04_bench.json")
     if not os.path.exists(path):
         pytest.skip("no recorded line yet")
@@ -151,5 +152,60 @@ def test_recorded_bench_line_of_the_round_is_complete():
     import test_bench_gpu
     with open(path) as f:
         out = json.load(f)
-    test_bench_gpu.check_headline(out, quick=False)
+    test_bench_gpu.check_headline(out, quick=False, recorded=True)
     test_bench_gpu.check_full_sections(out)
+
+
+@pytest.mark.parametrize("steps,warmup,per_solve,expect", [(200, 20, 50000, [(20, 200)]), (49980, 20, 50000, [(20, 49980)]),
+                                                         (49981, 20, 50000, [(20, 49980), (0, 1)]),
+                                                         (60000, 5, 50000, [(5, 49995), (0, 10005)]),
+                                                         (120000, 0, 50000, [(0, 50000), (0, 50000), (0, 20000)]), (1, 0, 5000, [(0, 1)]),
+                                                         (10, 5000, 5000, [(5000, 0), (0, 10)]), (300, 7000, 5000, [(5000, 0), (2000, 300)])])
+def test_solve_plan_times_exactly_the_steps_asked_for(steps, warmup, per_solve, expect):
+    """The headline: exactly `steps` timed pivots after exactly `warmup` untimed ones, whatever their size, no solve past `per_solve`."""
+    plan = bench.solve_plan(steps, warmup, per_solve)
+    assert plan == expect
+    assert sum(k for _, k in plan) == steps and sum(w for w, _ in plan) == warmup
+    assert all(0 < w + k <= per_solve for w, k in plan)
+
+
+@pytest.mark.parametrize("workload", sorted(bench.WORKLOADS))
+@pytest.mark.parametrize("block", [0, 32, 64, 96])
+@pytest.mark.parametrize("k,w", [(1, 0), (20, 5), (200, 20), (11776, 20), (11776, 1200), (60000, 5), (10 ** 7, 10 ** 7)])
+def test_kernel_event_windows_fit_into_one_solve_whatever_the_steps(workload, block, k, w):
+    """--full with the step count a plain run is timed at (11,776 pivots x 5 windows once ran the 10,000 x 10,000 LP to its optimum
+    inside the windows; c2 has 5,947 pivots in all): the windows and their warm-up stay inside one solve."""
+    per_solve = bench.SOLVE_PIVOTS[workload]
+    warm, steps = bench.window_plan(k, w, block, per_solve)
+    assert 0 <= warm <= w and warm + bench.WINDOWS * steps <= per_solve
+    assert steps <= bench.window_steps(k, block)
+    if block:
+        assert steps % block == 0 and steps >= 4 * block
+    if warm + bench.WINDOWS * bench.window_steps(k, block) <= per_solve and w == warm:
+        assert steps == bench.window_steps(k, block)                  # as before wherever the old windows fit
+
+
+def test_window_plan_leaves_short_runs_as_they_were():
+    for workload, block in (("dense10k", 64), ("c2", 64), ("c4", 96)):
+        assert bench.window_plan(20, 5, block, bench.SOLVE_PIVOTS[workload]) == (5, bench.window_steps(20, block))
+
+
+def test_plain_run_is_the_default_and_its_line_is_the_headline_alone():
+    args = bench.parser().parse_args(["--gpus", "1", "--steps", "300", "--warmup", "5"])
+    assert args.full is False and args.dump_outputs is None and args.quick is False
+    head = {"steps": 300, "seconds": 300 * 31e-6, "solves": 1, "block": 64, "objective": -2.5}
+    line = json.loads(json.dumps(bench.headline_line(args, 1, "tableau", head)))
+    assert line["steps"] == line["steps_requested"] == 300 and line["warmup"] == 5
+    assert line["ms_per_step"] == pytest.approx(0.031, rel=1e-12) and line["value"] == pytest.approx(1e3 / 0.031, rel=1e-12)
+    assert line["metric"] == "simplex iterations/sec" and line["unit"] == "iterations/s" and line["dtype"] == "f64"
+    assert line["higher_is_better"] is True and line["config"]["solves"] == 1 and line["config"]["update_block"] == 64
+    assert not {"timing", "roofline", "kernels", "cpu_baseline"} & set(line)
+    # --full: the same headline, the kernel-event windows under `timing`
+    steps = bench.window_steps(300, 64)
+    windows = [steps * 33e-6] * 5
+    res = {"steps": steps, "window_s": windows, "prof": tableau_prof(steps * 5, 64), "block": 64, "objective": -1.0}
+    m, n, _ = bench.WORKLOADS["dense10k"]
+    full = bench.assemble(args, 1, "tableau", bench.section(res, "dense10k", m, n, 1, "tableau"), head=head)
+    assert {k: full[k] for k in line} == line
+    assert full["timing"]["steps_per_window"] == 320 and full["timing"]["ms_per_step"] == pytest.approx(0.033)
+    assert full["roofline"]["kernel"] == "k_tab_flush_lds"
