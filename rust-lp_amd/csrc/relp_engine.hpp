@@ -23,6 +23,7 @@
 
 #include "../../include/relp_engine.h"
 #include "relp_kernels.h"
+#include "relp_layout.hpp"
 #include "relp_lu.hpp"
 
 namespace relp {
@@ -46,7 +47,7 @@ class Engine {
 
     // loops
     relp_status_t run(int64_t max_iters, int64_t* done, int32_t* outcome);
-    int32_t engine_kind() const { return cfg_.engine; }
+    int32_t engine_kind() const { return lay_.engine; }
     relp_status_t robust_stats(int64_t* out4) const;
     relp_status_t solve_relaxation(int64_t max_iters, int32_t* outcome);
     relp_status_t from_basis(const int32_t* basis_columns);
@@ -84,10 +85,10 @@ class Engine {
     relp_status_t shard_flush_end();
 
     // getters
-    int32_t nr_rows() const { return m_; }
-    int32_t nr_columns() const { return nr_artificial_ + n_provider_; }
+    int32_t nr_rows() const { return lay_.m; }
+    int32_t nr_columns() const { return lay_.nr_columns(); }
     int32_t phase() const { return phase_; }
-    int32_t nr_artificial() const { return nr_artificial_; }
+    int32_t nr_artificial() const { return lay_.nr_artificial; }
     relp_status_t get_objective(double* out);
     relp_status_t get_vector(int which, double* out);  // 0 b, 1 minus_pi, 2 alpha
     relp_status_t get_basis_indices(int32_t* out);
@@ -104,7 +105,7 @@ class Engine {
 
     // shards
     void shard_ranges(int32_t* col_lo, int32_t* col_hi, int32_t* row_lo, int32_t* row_hi, int32_t* stride) const;
-    int64_t candidate_len() const { return cand_len_; }
+    int64_t candidate_len() const { return lay_.candidate_len; }
     int64_t rho_len() const { return ld_b_; }
     relp_status_t shard_price(double* dev_candidate);
     relp_status_t shard_select_column(const double* dev_candidates, int32_t count);
@@ -121,23 +122,10 @@ class Engine {
     const char* last_error() const { return err_.c_str(); }
 
   private:
-    // ---- MatrixData (host mirror) ----
-    int32_t nr_normal_ = 0, nr_eq_ = 0, nr_range_ = 0, nr_le_ = 0, nr_ge_ = 0;
-    int32_t mc_ = 0;          // constraint rows of A
-    int32_t nr_bounds_ = 0;   // variables with an upper bound
-    int32_t m_ = 0;           // tableau rows
-    int32_t n_provider_ = 0;  // provider columns (structural + virtual)
-    int32_t nr_virtual_ = 0;
-    std::vector<double> cost_h_, upper_h_, rhs_h_;
-    std::vector<int32_t> bound_row_h_, vrow0_h_, vrow1_h_, vsign_h_;
+    // ---- MatrixData + Kind (host side: rows, columns, artificial columns, shards) ----
+    Layout lay_;
     relp_config_t cfg_{};
-
-    // ---- Kind ----
     int32_t phase_ = 1;
-    int32_t nr_artificial_ = 0;
-    std::vector<int32_t> column_to_row_;
-    double initial_phase1_objective_ = 0.0;
-    int32_t wrapped_na_ = 0;      // nr_artificial at the phase switch (decodes wrapped artificial indices)
 
     // ---- device state ----
     double* dA_ = nullptr; int64_t ld_a_ = 0; bool owns_A_ = false;
@@ -173,7 +161,6 @@ class Engine {
     double* d_rmin_ = nullptr;           // minimum ratio per block of 256 rows (k_tab_select_column -> k_ratio_blocks)
     int32_t n_store_ = 0;                // stored columns = original artificials + provider columns
     int32_t tab_na_ = 0;                 // original number of artificial columns (their block is kept)
-    int32_t sc_lo_ = 0, sc_hi_ = 0;      // storage columns owned by this rank (sharded tableau)
     bool tab_partials_valid_ = false;    // the PRICE partials describe the current d
     static constexpr int kRepriceEveryFlushes = 8;
     int32_t flushes_since_reprice_ = 0;
@@ -252,6 +239,10 @@ class Engine {
     // revised engine: B^-1 is re-inverted from the basis columns every `reinvert_interval_` pivots (0 = never)
     int64_t reinvert_interval_ = 0, since_reinvert_ = 0, reinversions_ = 0;
     DeviceCSC csc() const { return DeviceCSC{d_cptr_, d_cidx_, d_cval_}; }
+    // structural column p of the host CSC for Layout::for_each_entry
+    auto csc_column() const {
+        return [this](int32_t p, auto&& put) { for (int64_t e = hc_ptr_[p]; e < hc_ptr_[p + 1]; ++e) put(hc_idx_[e], hc_val_[e]); };
+    }
     relp_status_t lu_load_matrix(const relp_matrix_data_t& md);
     relp_status_t lu_refactor();
     relp_status_t lu_upload_factors();
@@ -300,13 +291,6 @@ class Engine {
     int32_t n_alloc_ = 0;     // allocated tableau columns (artificial + provider)
 
     // ---- shards ----
-    int32_t col_lo_ = 0, col_hi_ = 0, row_lo_ = 0, row_hi_ = 0, row_stride_ = 0;
-    // [key, j, d_j, column (m)] and, tableau engine, the minimum ratio of every block of 256 rows
-    int64_t candidate_len_for(int32_t m) const {
-        return round_up_even(3 + (int64_t)m + (cfg_.engine == RELP_ENGINE_TABLEAU ? (m + 255) / 256 : 0));
-    }
-    static int64_t round_up_even(int64_t v) { return (v + 1) & ~int64_t(1); }
-    int64_t cand_len_ = 0;
     // native multi-GPU loop: collective hooks and the message buffers they exchange
     relp_allgather_fn coll_allgather_ = nullptr;
     relp_allreduce_sum_fn coll_allreduce_ = nullptr;

@@ -12,12 +12,12 @@ namespace relp {
 
 // BasisInverse::basis_inverse_row (carry/mod.rs:145-150; lower_upper/mod.rs:204-222; basis_inverse_rows.rs:181-183)
 relp_status_t Engine::basis_inverse_row(int32_t row, double* out_m) {
-    if (row < 0 || row >= m_) return fail(RELP_E_ARG, "row out of range");
+    if (row < 0 || row >= lay_.m) return fail(RELP_E_ARG, "row out of range");
     if (cfg_.shard_count > 1) return fail(RELP_E_UNSUPPORTED, "B^-1 is sharded");
     if (lu_) {
         if (ft_) launch_ft_btran(dlu_, fts_, ft_problem(0), row, nullptr, d_rho_, stream_);
         else launch_lu_btran(dlu_, deferred(), nullptr, row, d_rho_, d_lu_scratch_, nullptr, stream_);
-        HIP_TRY(hipMemcpyAsync(out_m, d_rho_, sizeof(double) * m_, hipMemcpyDeviceToHost, stream_));
+        HIP_TRY(hipMemcpyAsync(out_m, d_rho_, sizeof(double) * lay_.m, hipMemcpyDeviceToHost, stream_));
         HIP_TRY(hipStreamSynchronize(stream_));
         return RELP_OK;
     }
@@ -27,11 +27,11 @@ relp_status_t Engine::basis_inverse_row(int32_t row, double* out_m) {
         std::vector<double> trow(n_store_);
         HIP_TRY(hipMemcpyAsync(trow.data(), d_aq_big(), sizeof(double) * n_store_, hipMemcpyDeviceToHost, stream_));
         HIP_TRY(hipStreamSynchronize(stream_));
-        for (int32_t k = 0; k < m_; ++k) out_m[k] = trow[idcol_h_[k]];
+        for (int32_t k = 0; k < lay_.m; ++k) out_m[k] = trow[idcol_h_[k]];
         return RELP_OK;
     }
     enqueue_flush();
-    HIP_TRY(hipMemcpyAsync(out_m, dBinv_ + (int64_t)row * ld_b_, sizeof(double) * m_, hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(hipMemcpyAsync(out_m, dBinv_ + (int64_t)row * ld_b_, sizeof(double) * lay_.m, hipMemcpyDeviceToHost, stream_));
     HIP_TRY(hipStreamSynchronize(stream_));
     return RELP_OK;
 }
@@ -60,23 +60,23 @@ relp_status_t Engine::generate_column_of(const int32_t* idx, const double* val, 
     if (cfg_.shard_count > 1) return fail(RELP_E_UNSUPPORTED, "generate_column_of in sharded mode");
     std::vector<double> a(ld_b_, 0.0);
     for (int32_t k = 0; k < nnz; ++k) {
-        if (idx[k] < 0 || idx[k] >= m_) return fail(RELP_E_ARG, "row index out of range");
+        if (idx[k] < 0 || idx[k] >= lay_.m) return fail(RELP_E_ARG, "row index out of range");
         a[idx[k]] = val[k];
     }
     if (tableau_) {
         // alpha = B^-1 a with B^-1 read off the tableau (host product: not a hot path of this engine)
-        std::vector<double> binv((size_t)m_ * m_);
+        std::vector<double> binv((size_t)lay_.m * lay_.m);
         relp_status_t st = get_basis_inverse(binv.data());
         if (st) return st;
-        std::vector<double> alpha(m_, 0.0);
-        for (int32_t i = 0; i < m_; ++i) {
+        std::vector<double> alpha(lay_.m, 0.0);
+        for (int32_t i = 0; i < lay_.m; ++i) {
             double s = 0.0;
-            for (int32_t k = 0; k < nnz; ++k) s = std::fma(binv[(size_t)i * m_ + idx[k]], val[k], s);
+            for (int32_t k = 0; k < nnz; ++k) s = std::fma(binv[(size_t)i * lay_.m + idx[k]], val[k], s);
             alpha[i] = s;
         }
-        HIP_TRY(hipMemcpyAsync(d_alpha_, alpha.data(), sizeof(double) * m_, hipMemcpyHostToDevice, stream_));
+        HIP_TRY(hipMemcpyAsync(d_alpha_, alpha.data(), sizeof(double) * lay_.m, hipMemcpyHostToDevice, stream_));
         HIP_TRY(hipStreamSynchronize(stream_));
-        if (out_m) std::memcpy(out_m, alpha.data(), sizeof(double) * m_);
+        if (out_m) std::memcpy(out_m, alpha.data(), sizeof(double) * lay_.m);
         return RELP_OK;
     }
     relp_status_t st = download_rec();
@@ -89,13 +89,13 @@ relp_status_t Engine::generate_column_of(const int32_t* idx, const double* val, 
         launch_ft_ftran(dlu_, fts_, ft_problem(0), -1, d_aq_, d_alpha_, stream_);
     } else if (lu_) {
         launch_lu_ftran(dlu_, d_aq_, d_v_, d_lu_scratch_, d_rec_, stream_);
-        launch_apply_w(deferred(), m_, d_v_, d_alpha_, d_rec_, stream_);
+        launch_apply_w(deferred(), lay_.m, d_v_, d_alpha_, d_rec_, stream_);
     } else {
         enqueue_flush();
-        double* Binv = dBinv_ - (int64_t)row_lo_ * ld_b_;
-        launch_ftran(Binv, ld_b_, m_, row_lo_, row_hi_, d_aq_, d_alpha_, 0, d_rec_, stream_);
+        double* Binv = dBinv_ - (int64_t)lay_.row_lo * ld_b_;
+        launch_ftran(Binv, ld_b_, lay_.m, lay_.row_lo, lay_.row_hi, d_aq_, d_alpha_, 0, d_rec_, stream_);
     }
-    if (out_m) HIP_TRY(hipMemcpyAsync(out_m, d_alpha_, sizeof(double) * m_, hipMemcpyDeviceToHost, stream_));
+    if (out_m) HIP_TRY(hipMemcpyAsync(out_m, d_alpha_, sizeof(double) * lay_.m, hipMemcpyDeviceToHost, stream_));
     HIP_TRY(hipStreamSynchronize(stream_));
     return RELP_OK;
 }
@@ -103,12 +103,12 @@ relp_status_t Engine::generate_column_of(const int32_t* idx, const double* val, 
 // InverseMaintener::cost_difference (carry/mod.rs:572-577): (-pi) . a for a column the caller supplies
 relp_status_t Engine::cost_difference_of(const int32_t* idx, const double* val, int32_t nnz, double* out) {
     if (nnz < 0 || (nnz > 0 && (!idx || !val)) || !out) return fail(RELP_E_ARG, "bad column");
-    std::vector<double> mp(m_);
+    std::vector<double> mp(lay_.m);
     relp_status_t st = get_vector(1, mp.data());
     if (st) return st;
     double s = 0.0;
     for (int32_t k = 0; k < nnz; ++k) {
-        if (idx[k] < 0 || idx[k] >= m_) return fail(RELP_E_ARG, "row index out of range");
+        if (idx[k] < 0 || idx[k] >= lay_.m) return fail(RELP_E_ARG, "row index out of range");
         s = std::fma(mp[idx[k]], val[k], s);              // vector/dense.rs:81-92, in the column's order
     }
     *out = s;
@@ -119,7 +119,7 @@ relp_status_t Engine::cost_difference_of(const int32_t* idx, const double* val, 
 // is the one of the last generate_column / generate_column_of, whose spike the engine kept (ColumnAndSpike, mod.rs:378-381)
 relp_status_t Engine::lu_change_basis(int32_t row) {
     if (!lu_ || !ft_) return fail(RELP_E_UNSUPPORTED, "change_basis on the inverse alone is the LU engine's (Forrest-Tomlin mode)");
-    if (row < 0 || row >= m_) return fail(RELP_E_ARG, "row out of range");
+    if (row < 0 || row >= lay_.m) return fail(RELP_E_ARG, "row out of range");
     relp_status_t st = ft_read_hdr();
     if (st) return st;
     if (h_ft_hdr_[0] >= ft_tcap_) return fail(RELP_E_STATE, "update file full: refactor first (relp_flush)");
@@ -138,13 +138,13 @@ relp_status_t Engine::lu_set_factors(const int64_t* l_ptr, const int32_t* l_idx,
                                      const int32_t* u_idx, const double* u_val) {
     if (!lu_) return fail(RELP_E_UNSUPPORTED, "relp_lu_set_factors is the LU engine's");
     if (!l_ptr || !u_ptr) return fail(RELP_E_ARG, "missing factors");
-    std::vector<std::vector<std::pair<int32_t, double>>> lc(m_), uc(m_);
-    for (int32_t j = 0; j < m_; ++j) {
+    std::vector<std::vector<std::pair<int32_t, double>>> lc(lay_.m), uc(lay_.m);
+    for (int32_t j = 0; j < lay_.m; ++j) {
         for (int64_t e = l_ptr[j]; e < l_ptr[j + 1]; ++e) lc[j].emplace_back(l_idx[e], l_val[e]);
         for (int64_t e = u_ptr[j]; e < u_ptr[j + 1]; ++e) uc[j].emplace_back(u_idx[e], u_val[e]);
     }
     std::string msg;
-    if (!lu_from_triangles(m_, lc, uc, &hlu_, &msg)) return fail(RELP_E_ARG, msg);
+    if (!lu_from_triangles(lay_.m, lc, uc, &hlu_, &msg)) return fail(RELP_E_ARG, msg);
     HIP_TRY(hipStreamSynchronize(stream_));
     relp_status_t st = lu_upload_factors();
     if (st) return st;
@@ -237,9 +237,9 @@ relp_status_t Engine::lu_get_upper(int64_t* col_ptr, int32_t* row_idx, double* v
     if (st) return st;
     if ((st = lu_host_factors())) return st;               // (after a device-resident factorisation the rows are fetched now)
     const std::vector<int32_t> pos = v.positions_before(v.t);
-    std::vector<std::vector<std::pair<int32_t, double>>> cols(m_);
+    std::vector<std::vector<std::pair<int32_t, double>>> cols(lay_.m);
     const int nwp = kFtWaves + 1;
-    for (int32_t l = 0; l < m_; ++l) {
+    for (int32_t l = 0; l < lay_.m; ++l) {
         if (v.tslot[l] >= 0) continue;                      // its column is a spike now
         auto& c = cols[pos[l]];
         for (int32_t e = hlu_.Ub.ptr[l]; e < hlu_.Ub.ptr[l + 1]; ++e) {
@@ -251,7 +251,7 @@ relp_status_t Engine::lu_get_upper(int64_t* col_ptr, int32_t* row_idx, double* v
     for (int32_t s = 0; s < v.t; ++s) {
         if (!v.slot_live[s]) continue;
         auto& c = cols[pos[v.slot_pivot[s]]];
-        const size_t base = (size_t)s * m_;
+        const size_t base = (size_t)s * lay_.m;
         for (int32_t e = v.spk_off[(size_t)s * nwp]; e < v.spk_off[(size_t)s * nwp + kFtWaves]; ++e) {
             const int32_t k = v.spk_idx[base + e];
             if (v.tslot[k] < 0 && v.spk_val[base + e] != 0.0) c.emplace_back(pos[k], v.spk_val[base + e]);
@@ -261,12 +261,12 @@ relp_status_t Engine::lu_get_upper(int64_t* col_ptr, int32_t* row_idx, double* v
         c.emplace_back(pos[v.slot_pivot[s]], v.TC[(size_t)s * v.ldt + s]);
     }
     int64_t at = 0;
-    for (int32_t j = 0; j < m_; ++j) {
+    for (int32_t j = 0; j < lay_.m; ++j) {
         std::sort(cols[j].begin(), cols[j].end());
         if (col_ptr) col_ptr[j] = at;
         for (auto& e : cols[j]) { if (at < cap) { if (row_idx) row_idx[at] = e.first; if (values) values[at] = e.second; } ++at; }
     }
-    if (col_ptr) col_ptr[m_] = at;
+    if (col_ptr) col_ptr[lay_.m] = at;
     if (nnz) *nnz = at;
     return RELP_OK;
 }

@@ -18,39 +18,39 @@ static_assert(sizeof(EllPassHost) == 16 && sizeof(EllPass) == 16, "the packed pa
 // Sparse LU engine: matrix in CSC, factors from the host (relp_lu.cpp), solves on the device
 // ------------------------------------------------------------------------------------------------
 relp_status_t Engine::lu_load_matrix(const relp_matrix_data_t& md) {
-    hc_ptr_.assign(nr_normal_ + 1, 0);
+    hc_ptr_.assign(lay_.nr_normal + 1, 0);
     hc_idx_.clear(); hc_val_.clear();
     if (md.format == RELP_FORMAT_CSC) {
         if (md.matrix_memory != RELP_MEM_HOST) return fail(RELP_E_UNSUPPORTED, "CSC input must be in host memory");
         if (!md.col_ptr) return fail(RELP_E_ARG, "col_ptr missing");
-        for (int32_t j = 0; j < nr_normal_; ++j) {
+        for (int32_t j = 0; j < lay_.nr_normal; ++j) {
             for (int64_t p = md.col_ptr[j]; p < md.col_ptr[j + 1]; ++p) {
                 const int32_t i = md.row_idx[p];
-                if (i < 0 || i >= mc_) return fail(RELP_E_ARG, "row index out of range");
+                if (i < 0 || i >= lay_.mc) return fail(RELP_E_ARG, "row index out of range");
                 if (md.values[p] == 0.0) continue;
                 hc_idx_.push_back(i); hc_val_.push_back(md.values[p]);
             }
             hc_ptr_[j + 1] = (int64_t)hc_idx_.size();
         }
     } else if (md.format == RELP_FORMAT_DENSE) {
-        if (nr_normal_ > 0 && mc_ > 0 && !md.dense) return fail(RELP_E_ARG, "dense matrix missing");
-        const int64_t src_ld = md.dense_ld > 0 ? md.dense_ld : mc_;
-        if (src_ld < mc_) return fail(RELP_E_ARG, "dense_ld < nr_constraints");
-        std::vector<double> col(std::max(mc_, 1));
-        for (int32_t j = 0; j < nr_normal_; ++j) {
+        if (lay_.nr_normal > 0 && lay_.mc > 0 && !md.dense) return fail(RELP_E_ARG, "dense matrix missing");
+        const int64_t src_ld = md.dense_ld > 0 ? md.dense_ld : lay_.mc;
+        if (src_ld < lay_.mc) return fail(RELP_E_ARG, "dense_ld < nr_constraints");
+        std::vector<double> col(std::max(lay_.mc, 1));
+        for (int32_t j = 0; j < lay_.nr_normal; ++j) {
             const double* src = md.dense + (int64_t)j * src_ld;
             if (md.matrix_memory == RELP_MEM_DEVICE) {
-                HIP_TRY(hipMemcpy(col.data(), src, sizeof(double) * mc_, hipMemcpyDeviceToHost));
+                HIP_TRY(hipMemcpy(col.data(), src, sizeof(double) * lay_.mc, hipMemcpyDeviceToHost));
                 src = col.data();
             }
-            for (int32_t i = 0; i < mc_; ++i)
+            for (int32_t i = 0; i < lay_.mc; ++i)
                 if (src[i] != 0.0) { hc_idx_.push_back(i); hc_val_.push_back(src[i]); }
             hc_ptr_[j + 1] = (int64_t)hc_idx_.size();
         }
     } else {
         return fail(RELP_E_ARG, "unknown matrix format");
     }
-    HIP_TRY(dev_alloc(&d_cptr_, nr_normal_ + 1));
+    HIP_TRY(dev_alloc(&d_cptr_, lay_.nr_normal + 1));
     HIP_TRY(dev_alloc(&d_cidx_, (int64_t)hc_idx_.size()));
     HIP_TRY(dev_alloc(&d_cval_, (int64_t)hc_val_.size()));
     HIP_TRY(hipMemcpy(d_cptr_, hc_ptr_.data(), sizeof(int64_t) * hc_ptr_.size(), hipMemcpyHostToDevice));
@@ -63,35 +63,20 @@ relp_status_t Engine::lu_load_matrix(const relp_matrix_data_t& md) {
 
 // The basis as it is on the device -> pinned host memory.  Synchronises the stream.
 relp_status_t Engine::lu_download_basis() {
-    if (!h_basis_) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_basis_), sizeof(int32_t) * (size_t)std::max(m_alloc_rows_, m_), hipHostMallocDefault));
-    HIP_TRY(hipMemcpyAsync(h_basis_, d_basis_, sizeof(int32_t) * m_, hipMemcpyDeviceToHost, stream_));
+    if (!h_basis_) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_basis_), sizeof(int32_t) * (size_t)std::max(m_alloc_rows_, lay_.m), hipHostMallocDefault));
+    HIP_TRY(hipMemcpyAsync(h_basis_, d_basis_, sizeof(int32_t) * lay_.m, hipMemcpyDeviceToHost, stream_));
     HIP_TRY(hipStreamSynchronize(stream_));
     return RELP_OK;
 }
 
 // the columns of the basis in h_basis_ from the host copy of the matrix (the LU engine never holds A densely)
 relp_status_t Engine::lu_basis_columns(std::vector<std::vector<std::pair<int32_t, double>>>& cols) {
-    const int32_t* const basis = h_basis_;
-    cols.resize(m_);
-    for (int32_t i = 0; i < m_; ++i) {
-        const int32_t j = basis[i];
+    cols.resize(lay_.m);
+    for (int32_t i = 0; i < lay_.m; ++i) {
         auto& c = cols[i];
         c.clear();
-        if (j < nr_artificial_) { c.emplace_back(column_to_row_[j], 1.0); continue; }
-        if (j >= kWrappedArtificialBase) {                      // artificial that survived phase 1: still e_row
-            c.emplace_back(column_to_row_[wrapped_na_ - 1 - (INT32_MAX - j)], 1.0);
-            continue;
-        }
-        const int32_t p = j - nr_artificial_;
-        if (p < nr_normal_) {
-            for (int64_t e = hc_ptr_[p]; e < hc_ptr_[p + 1]; ++e) c.emplace_back(hc_idx_[e], hc_val_[e]);
-            if (bound_row_h_[p] >= 0) c.emplace_back(bound_row_h_[p], 1.0);
-        } else {
-            const int32_t v = p - nr_normal_;
-            if (v >= nr_virtual_) return fail(RELP_E_STATE, "basis column out of range");
-            if (vrow0_h_[v] >= 0) c.emplace_back(vrow0_h_[v], (double)vsign_h_[v]);   // -1: its row was removed
-            if (vrow1_h_[v] >= 0) c.emplace_back(vrow1_h_[v], 1.0);
-        }
+        if (!lay_.for_each_entry(h_basis_[i], csc_column(), [&c](int32_t row, double v) { c.emplace_back(row, v); }))
+            return fail(RELP_E_STATE, "basis column out of range");
     }
     return RELP_OK;
 }
@@ -99,26 +84,11 @@ relp_status_t Engine::lu_basis_columns(std::vector<std::vector<std::pair<int32_t
 // The same columns as one flat copy (column i = entries [ptr[i], ptr[i + 1])): what lu_factor_csc wants -- at 64,000 rows the
 // vector per column was a cache miss per column and pass.
 relp_status_t Engine::lu_basis_flat(std::vector<int64_t>& ptr, std::vector<int32_t>& idx, std::vector<double>& val) {
-    const int32_t* const basis = h_basis_;
-    ptr.assign((size_t)m_ + 1, 0);
+    ptr.assign((size_t)lay_.m + 1, 0);
     idx.clear(); val.clear();
     auto put = [&](int32_t row, double v) { idx.push_back(row); val.push_back(v); };
-    for (int32_t i = 0; i < m_; ++i) {
-        const int32_t j = basis[i];
-        if (j < nr_artificial_) put(column_to_row_[j], 1.0);
-        else if (j >= kWrappedArtificialBase) put(column_to_row_[wrapped_na_ - 1 - (INT32_MAX - j)], 1.0);
-        else {
-            const int32_t p = j - nr_artificial_;
-            if (p < nr_normal_) {
-                for (int64_t e = hc_ptr_[p]; e < hc_ptr_[p + 1]; ++e) put(hc_idx_[e], hc_val_[e]);
-                if (bound_row_h_[p] >= 0) put(bound_row_h_[p], 1.0);
-            } else {
-                const int32_t v = p - nr_normal_;
-                if (v >= nr_virtual_) return fail(RELP_E_STATE, "basis column out of range");
-                if (vrow0_h_[v] >= 0) put(vrow0_h_[v], (double)vsign_h_[v]);
-                if (vrow1_h_[v] >= 0) put(vrow1_h_[v], 1.0);
-            }
-        }
+    for (int32_t i = 0; i < lay_.m; ++i) {
+        if (!lay_.for_each_entry(h_basis_[i], csc_column(), put)) return fail(RELP_E_STATE, "basis column out of range");
         ptr[(size_t)i + 1] = (int64_t)idx.size();
     }
     return RELP_OK;
@@ -130,7 +100,7 @@ relp_status_t Engine::lu_factor_downloaded_basis() {
         const relp_status_t fst = lu_basis_flat(basis_ptr_, basis_idx_, basis_val_);
         if (fst) return fst;
         std::string msg;
-        if (!lu_factor_csc(m_, basis_ptr_.data(), basis_idx_.data(), basis_val_.data(), &hlu_, &msg)) return fail(RELP_E_SINGULAR, msg);
+        if (!lu_factor_csc(lay_.m, basis_ptr_.data(), basis_idx_.data(), basis_val_.data(), &hlu_, &msg)) return fail(RELP_E_SINGULAR, msg);
         return RELP_OK;
     }
     std::vector<std::vector<std::pair<int32_t, double>>>& cols = basis_cols_;     // (kept: no 790 allocations per refactorisation)
@@ -139,14 +109,14 @@ relp_status_t Engine::lu_factor_downloaded_basis() {
     if (const char* dump = std::getenv("RELP_DUMP_BASIS")) {
         if (lu_refactors_ == 100) {                        // one mid-solve basis as text: m, then per column "n i v i v ..."
             if (FILE* f = std::fopen(dump, "w")) {
-                std::fprintf(f, "%d\n", m_);
+                std::fprintf(f, "%d\n", lay_.m);
                 for (auto& c : cols) { std::fprintf(f, "%zu", c.size()); for (auto& e : c) std::fprintf(f, " %d %.17g", e.first, e.second); std::fprintf(f, "\n"); }
                 std::fclose(f);
             }
         }
     }
     std::string msg;
-    if (!lu_factor(m_, cols, &hlu_, &msg)) return fail(RELP_E_SINGULAR, msg);
+    if (!lu_factor(lay_.m, cols, &hlu_, &msg)) return fail(RELP_E_SINGULAR, msg);
     return RELP_OK;
 }
 
@@ -273,15 +243,15 @@ relp_status_t Engine::lu_upload_factors() {
         buf_size = need;
         return o;
     };
-    const size_t o_rp = put(hlu_.rowperm.data(), sizeof(int32_t) * m_), o_cp = put(hlu_.colperm.data(), sizeof(int32_t) * m_);
+    const size_t o_rp = put(hlu_.rowperm.data(), sizeof(int32_t) * lay_.m), o_cp = put(hlu_.colperm.data(), sizeof(int32_t) * lay_.m);
     // Forrest-Tomlin kernels: original row -> pivot, basis position -> pivot, pivot -> its row in the U / U' schedules
-    std::vector<int32_t> inv_rp(m_), inv_cp(m_), task_uf(m_), task_ub(m_);
-    for (int32_t k = 0; k < m_; ++k) {
+    std::vector<int32_t> inv_rp(lay_.m), inv_cp(lay_.m), task_uf(lay_.m), task_ub(lay_.m);
+    for (int32_t k = 0; k < lay_.m; ++k) {
         inv_rp[hlu_.rowperm[k]] = k; inv_cp[hlu_.colperm[k]] = k;
         task_uf[hlu_.Uf.level_rows[k]] = k; task_ub[hlu_.Ub.level_rows[k]] = k;
     }
-    const size_t o_irp = put(inv_rp.data(), sizeof(int32_t) * m_), o_icp = put(inv_cp.data(), sizeof(int32_t) * m_);
-    const size_t o_tuf = put(task_uf.data(), sizeof(int32_t) * m_), o_tub = put(task_ub.data(), sizeof(int32_t) * m_);
+    const size_t o_irp = put(inv_rp.data(), sizeof(int32_t) * lay_.m), o_icp = put(inv_cp.data(), sizeof(int32_t) * lay_.m);
+    const size_t o_tuf = put(task_uf.data(), sizeof(int32_t) * lay_.m), o_tub = put(task_ub.data(), sizeof(int32_t) * lay_.m);
     // the four schedules once more for the persistent pivot kernel: consecutive levels fused into groups one pass solves
     // (relp_lu.hpp: fuse_levels), packed "ELL by pass", one contiguous image each (headers | lvl_pass | rdiag | sval | oval |
     // rovf | sidx | oidx); rows of U and U' without entries are kept, an update may mask them
@@ -290,7 +260,7 @@ relp_status_t Engine::lu_upload_factors() {
     size_t o_ell[4] = {0, 0, 0, 0}, o_via_ptr[4] = {0, 0, 0, 0}, o_via_pos[4] = {0, 0, 0, 0}, o_triv[4] = {0, 0, 0, 0},
            o_reach[4] = {0, 0, 0, 0}, o_rhs[4] = {0, 0, 0, 0};
     int32_t rhs_base[4] = {0, 0, 0, 0};
-    std::vector<int32_t> lev_ub(m_, 0);
+    std::vector<int32_t> lev_ub(lay_.m, 0);
     for (int32_t l = 0; l + 1 < (int32_t)hlu_.Ub.level_ptr.size(); ++l)
         for (int32_t t = hlu_.Ub.level_ptr[l]; t < hlu_.Ub.level_ptr[l + 1]; ++t) lev_ub[hlu_.Ub.level_rows[t]] = l;
     static_assert(kEllLgShift == kEllLg, "host packing and device decoding of sidx");
@@ -311,7 +281,7 @@ relp_status_t Engine::lu_upload_factors() {
             const int32_t triv_min = ft_big_ ? 512 : 0x7fffffff;
             fuse_levels(*sch[k], maskable, maskable, cap, &fs);
             ell_pack(fs, maskable, &ell[k], ft_big_, ft_big_, triv_min);
-            if (ft_big_ && ((int64_t)ell[k].rhs_src.size() > ft_rhs_cap_ || (int64_t)m_ + 1 + (int64_t)ell[k].rhs_src.size() > index_room)) {
+            if (ft_big_ && ((int64_t)ell[k].rhs_src.size() > ft_rhs_cap_ || (int64_t)lay_.m + 1 + (int64_t)ell[k].rhs_src.size() > index_room)) {
                 fuse_levels(*sch[k], maskable, maskable, 0, &fs);      // more copies than the layout has room for: level by level
                 ell_pack(fs, maskable, &ell[k], ft_big_, ft_big_, triv_min);
             }
@@ -320,7 +290,7 @@ relp_status_t Engine::lu_upload_factors() {
             if (k == 2) lev_ub = fs.start_after;
             if (uses_rhs[k]) rhs_base[k] = fs.rhs_base;
         };
-        if (m_ >= 256) {
+        if (lay_.m >= 256) {
             host_pool_.run(0, [&] { prepare(2); });
             host_pool_.run(1, [&] { prepare(0); prepare(3); });
             prepare(1);
@@ -349,9 +319,9 @@ relp_status_t Engine::lu_upload_factors() {
             o_rhs[k] = put(ell[k].rhs_src.data(), sizeof(int32_t) * ell[k].rhs_src.size());
             o_triv[k] = put(ell[k].triv.data(), sizeof(int32_t) * ell[k].triv.size());
             if (ft_tier_ >= 2) {                       // layout 2 walks the non-zeros of x: the inverse of rhs_src, `triv` as a bitmap
-                std::vector<int32_t> pos(m_, -1);
+                std::vector<int32_t> pos(lay_.m, -1);
                 for (size_t i = 0; i < ell[k].rhs_src.size(); ++i) pos[ell[k].rhs_src[i]] = (int32_t)i;
-                std::vector<uint32_t> tb((size_t)(m_ + 31) / 32 + 1, 0u);
+                std::vector<uint32_t> tb((size_t)(lay_.m + 31) / 32 + 1, 0u);
                 for (int32_t r : ell[k].triv) tb[(size_t)r >> 5] |= 1u << (r & 31);
                 o_rpos[k] = put(pos.data(), sizeof(int32_t) * pos.size());
                 o_tbits[k] = put(tb.data(), sizeof(uint32_t) * tb.size());
@@ -359,11 +329,11 @@ relp_status_t Engine::lu_upload_factors() {
             o_reach[k] = put(ell[k].reach.data(), sizeof(int32_t) * ell[k].reach.size());
         }
     }
-    const size_t o_lub = put(lev_ub.data(), sizeof(int32_t) * m_);
+    const size_t o_lub = put(lev_ub.data(), sizeof(int32_t) * lay_.m);
     size_t o_pinfo = 0;
     if (ft_) {
-        std::vector<FtPivotInfo> pinfo(m_);
-        for (int32_t p = 0; p < m_; ++p) {
+        std::vector<FtPivotInfo> pinfo(lay_.m);
+        for (int32_t p = 0; p < lay_.m; ++p) {
             FtPivotInfo& q = pinfo[p];
             q.u_e0 = hlu_.Uf.ptr[p]; q.u_e1 = hlu_.Uf.ptr[p + 1];
             const bool v1 = !ell[1].via_ptr.empty(), v2 = !ell[2].via_ptr.empty();
@@ -375,7 +345,7 @@ relp_status_t Engine::lu_upload_factors() {
     }
     size_t o_rows[4], o_idx[4], o_val[4], o_lp[4], o_seg[4];
     int32_t n_seg[4] = {0, 0, 0, 0};
-    std::vector<LuRow> rows(m_);
+    std::vector<LuRow> rows(lay_.m);
     for (int k = 0; k < 4; ++k) {
         const TriangularSchedule& t = *sch[k];
         o_rows[k] = o_idx[k] = o_val[k] = o_lp[k] = o_seg[k] = 0;
@@ -385,11 +355,11 @@ relp_status_t Engine::lu_upload_factors() {
             if (k == 1) { o_idx[k] = put(t.idx.data(), sizeof(int32_t) * t.idx.size()); o_val[k] = put(t.val.data(), sizeof(double) * t.val.size()); }
             continue;
         }
-        for (int32_t i = 0; i < m_; ++i) {
+        for (int32_t i = 0; i < lay_.m; ++i) {
             const int32_t r = t.level_rows[i];
             rows[i] = LuRow{r, t.ptr[r], t.ptr[r + 1], 0, 1.0 / t.diag[r]};
         }
-        o_rows[k] = put(rows.data(), sizeof(LuRow) * m_);
+        o_rows[k] = put(rows.data(), sizeof(LuRow) * lay_.m);
         o_idx[k] = put(t.idx.data(), sizeof(int32_t) * t.idx.size());
         o_val[k] = put(t.val.data(), sizeof(double) * t.val.size());
         o_lp[k] = put(t.level_ptr.data(), sizeof(int32_t) * t.level_ptr.size());
@@ -422,7 +392,7 @@ relp_status_t Engine::lu_upload_factors() {
         lu_cap_ = want;
     }
     HIP_TRY(hipMemcpyAsync(d_lu_buf_, h_lu_buf_, buf_size, hipMemcpyHostToDevice, stream_));
-    dlu_.m = m_; dlu_.pad_ = 0;
+    dlu_.m = lay_.m; dlu_.pad_ = 0;
     dlu_.rowperm = reinterpret_cast<const int32_t*>(d_lu_buf_ + o_rp);
     dlu_.colperm = reinterpret_cast<const int32_t*>(d_lu_buf_ + o_cp);
     DeviceSchedule* ds[4] = {&dlu_.Lf, &dlu_.Uf, &dlu_.Ub, &dlu_.Lb};
@@ -438,12 +408,12 @@ relp_status_t Engine::lu_upload_factors() {
     }
     HIP_TRY(hipStreamSynchronize(stream_));             // (the pinned buffer is rewritten by the next refactorisation)
     if (ft_) {
-        if (ft_tier_ >= 2 && fts_.m != m_) {           // rows were removed: the bitmaps saved between launches describe another m
+        if (ft_tier_ >= 2 && fts_.m != lay_.m) {           // rows were removed: the bitmaps saved between launches describe another m
             const int32_t reset[4] = {-1, -1, 0, 0};
             HIP_TRY(hipMemcpyAsync(fts_.nzc, reset, sizeof reset, hipMemcpyHostToDevice, stream_));
             HIP_TRY(hipStreamSynchronize(stream_));
         }
-        fts_.m = m_;
+        fts_.m = lay_.m;
         fts_.inv_rowperm = reinterpret_cast<const int32_t*>(d_lu_buf_ + o_irp);
         fts_.inv_colperm = reinterpret_cast<const int32_t*>(d_lu_buf_ + o_icp);
         fts_.task_uf = reinterpret_cast<const int32_t*>(d_lu_buf_ + o_tuf);
@@ -451,7 +421,7 @@ relp_status_t Engine::lu_upload_factors() {
         fts_.lev_ub = reinterpret_cast<const int32_t*>(d_lu_buf_ + o_lub);
         fts_.pinfo = reinterpret_cast<const FtPivotInfo*>(d_lu_buf_ + o_pinfo);
         // what is left of the CU's LDS after the work vectors stages one schedule image at a time
-        const int64_t base = (int64_t)ft_lds_base_bytes(m_, ft_tcap_, ft_eta_cap_, ft_tier_, ft_rhs_cap_);
+        const int64_t base = (int64_t)ft_lds_base_bytes(lay_.m, ft_tcap_, ft_eta_cap_, ft_tier_, ft_rhs_cap_);
         const int64_t idx_bytes = ft_big_ ? 4 : 2;
         fts_.stage_bytes = (int32_t)std::max<int64_t>(0, kFtLdsBudget - base);
         int64_t need = 0;
@@ -465,14 +435,14 @@ relp_status_t Engine::lu_upload_factors() {
             char* const q0 = q;
             d.passes = reinterpret_cast<const EllPass*>(q); q += up16(16 * (np + kEllPadHeaders));
             d.lvl_pass = reinterpret_cast<const int32_t*>(q); q += up16(4 * nlv);
-            d.rdiag = reinterpret_cast<double*>(q); q += up16(8 * ((int64_t)m_ + 1));
+            d.rdiag = reinterpret_cast<double*>(q); q += up16(8 * ((int64_t)lay_.m + 1));
             d.sval = reinterpret_cast<double*>(q); q += up16(8 * nln);
             d.oval = reinterpret_cast<const double*>(q); q += up16(8 * nov);
             d.rovf = reinterpret_cast<const int32_t*>(q); q += up16(4 * (int64_t)e.rovf.size());
             d.sidx = reinterpret_cast<const uint16_t*>(q); q += up16(idx_bytes * nln);      // (uint32_t when FtState::big)
             d.oidx = reinterpret_cast<const uint16_t*>(q); q += up16(idx_bytes * nov);
             const int64_t total = q - q0;
-            d.n_passes = (int32_t)np; d.n_levels = (int32_t)nlv - 1; d.m = m_; d.n_lanes = (int32_t)nln; d.n_ovf = (int32_t)nov;
+            d.n_passes = (int32_t)np; d.n_levels = (int32_t)nlv - 1; d.m = lay_.m; d.n_lanes = (int32_t)nln; d.n_ovf = (int32_t)nov;
             d.bytes = (int32_t)total;
             d.rhs_base = rhs_base[k];
             d.n_triv = (int32_t)e.triv.size();
@@ -508,7 +478,7 @@ relp_status_t Engine::lu_upload_factors() {
 // ------------------------------------------------------------------------------------------------
 relp_status_t Engine::ft_plan_and_alloc() {
     ft_ = false; ft_big_ = false; ft_tier_ = 0; ft_rhs_cap_ = 0;
-    if (m_ > kFtMaxRows) return RELP_OK;
+    if (lay_.m > kFtMaxRows) return RELP_OK;
     // The dense tail of U (tcap x tcap in LDS) is as large as the refactorisation interval asks for, not larger: what it does
     // not take stages the triangular factors, and an image that does not fit is solved from L2 at several times the cost.
     // Default interval 48: with a refactorisation at ~0.7 ms and ~1,100 clocks per pending update and pivot, the optimum is
@@ -522,7 +492,7 @@ relp_status_t Engine::ft_plan_and_alloc() {
     // slot indices of the images 32 bits wide.  The first is taken while it leaves the dense
     // tail the interval asks for AND >= kFtMinStage bytes to stage the factor images (an image that is not staged is solved
     // from L2 at several times the cost); RELP_FT_BIG = 0 / 1 forces one of them.
-    const int64_t eta_cap = std::max<int64_t>((int64_t)2 * m_ + 64, 1024);   // (one eta never exceeds m entries)
+    const int64_t eta_cap = std::max<int64_t>((int64_t)2 * lay_.m + 64, 1024);   // (one eta never exceeds m entries)
     constexpr int64_t kFtMinStage = 64 * 1024;
     (void)kFtMinStage;
     const char* big_env = std::getenv("RELP_FT_BIG");
@@ -532,7 +502,7 @@ relp_status_t Engine::ft_plan_and_alloc() {
             if (tcap != 16 && tcap - 16 >= want) continue;              // a smaller tail serves the interval
             if (tcap < std::min(want, min_tcap)) return false;          // (a refactorisation every 16 pivots is the last resort)
             if (tcap < want && min_stage > 4096) return false;          // (only the last resort shortens the interval)
-            if ((int64_t)ft_lds_base_bytes(m_, tcap, (int32_t)eta_cap, tier, rhs_cap) + min_stage <= kFtLdsBudget) {
+            if ((int64_t)ft_lds_base_bytes(lay_.m, tcap, (int32_t)eta_cap, tier, rhs_cap) + min_stage <= kFtLdsBudget) {
                 ft_tcap_ = tcap; ft_eta_cap_ = (int32_t)eta_cap; ft_tier_ = tier; ft_big_ = tier >= 1; ft_rhs_cap_ = rhs_cap; ft_ = true;
                 return true;
             }
@@ -540,28 +510,28 @@ relp_status_t Engine::ft_plan_and_alloc() {
         return false;
     };
     // (16-bit slot indices: m + 1 + copies < 8,192)
-    const int32_t small_rhs = (int32_t)std::max<int64_t>(0, std::min<int64_t>(m_, (int64_t(1) << kEllLgShift) - 2 - m_));
+    const int32_t small_rhs = (int32_t)std::max<int64_t>(0, std::min<int64_t>(lay_.m, (int64_t(1) << kEllLgShift) - 2 - lay_.m));
     // (measured on GREENBEB, m = 2,228: all-in-LDS with a 32-slot tail and nothing staged 209,000 clocks per pivot, big with a
     // 48-slot tail and 78 KB of staging 235,000 -- what the big layout reads from L2 costs more than staging saves; so the
     // all-in-LDS layout is taken whenever it fits at all)
     // Layout 2 (nothing per row in LDS, x and -pi in L2) takes whatever the other two cannot hold: any m, every right-hand-side
     // copy the fused schedules ask for, the whole LDS minus the dense tail as the staging area.  RELP_FT_BIG = 2 forces it.
     // (the 16-bit row indices of the PRICE copy end at 32,767; the slot indices of the images at 2^24)
-    const bool fits_tier1 = m_ < kPriceLongFlag;
-    const bool fits_tier2 = 2 * (int64_t)m_ + 2 <= (int64_t(1) << kEllLgShiftWide);
-    if (force_big < 1 && m_ < kPriceLongFlag && small_rhs > 0 && plan(0, small_rhs, 4096, force_big == 0 ? 16 : 32)) {}
+    const bool fits_tier1 = lay_.m < kPriceLongFlag;
+    const bool fits_tier2 = 2 * (int64_t)lay_.m + 2 <= (int64_t(1) << kEllLgShiftWide);
+    if (force_big < 1 && lay_.m < kPriceLongFlag && small_rhs > 0 && plan(0, small_rhs, 4096, force_big == 0 ? 16 : 32)) {}
     else if (force_big != 0 && force_big != 2 && fits_tier1 &&
-             (plan(1, m_, kFtMinStage) || plan(1, std::min(m_, 2048), 32 * 1024) || plan(1, std::min(m_, 1024), 8 * 1024) || plan(1, 0, 4096))) {}
+             (plan(1, lay_.m, kFtMinStage) || plan(1, std::min(lay_.m, 2048), 32 * 1024) || plan(1, std::min(lay_.m, 1024), 8 * 1024) || plan(1, 0, 4096))) {}
     // (layout 2 by default refactorises every 64 updates and lets the kernel make 16 of them while the host factorises: at
     // 64,000 rows a refactorisation is 5 ms of host time against 0.35 ms per pivot, and a pending update costs a pivot whose
     // per-row loops dominate next to nothing -- measured 2,670 it/s at 48 / 8, 2,870 at 64 / 8, 2,975 at 64 / 16)
-    else if (force_big != 0 && force_big != 1 && fits_tier2 && ((want = cfg_.update_block < 0 ? 64 : want), plan(2, m_, kFtMinStage))) {}
+    else if (force_big != 0 && force_big != 1 && fits_tier2 && ((want = cfg_.update_block < 0 ? 64 : want), plan(2, lay_.m, kFtMinStage))) {}
     if (!ft_) return RELP_OK;
     if (std::getenv("RELP_DEBUG"))
         std::fprintf(stderr, "[relp] persistent pivot kernel: m %d, layout %s, %d right-hand-side copies, dense tail %d, LDS base %zu bytes\n",
-                     m_, ft_tier_ >= 2 ? "nothing per row in LDS" : ft_big_ ? "big" : "all-in-LDS", ft_rhs_cap_, ft_tcap_,
-                     ft_lds_base_bytes(m_, ft_tcap_, ft_eta_cap_, ft_tier_, ft_rhs_cap_));
-    const int64_t tc = ft_tcap_, ldt = tc + 1, m = m_, nwp = kFtWaves + 1;
+                     lay_.m, ft_tier_ >= 2 ? "nothing per row in LDS" : ft_big_ ? "big" : "all-in-LDS", ft_rhs_cap_, ft_tcap_,
+                     ft_lds_base_bytes(lay_.m, ft_tcap_, ft_eta_cap_, ft_tier_, ft_rhs_cap_));
+    const int64_t tc = ft_tcap_, ldt = tc + 1, m = lay_.m, nwp = kFtWaves + 1;
     std::vector<char> dummy;
     int64_t o = 0;
     auto take = [&](int64_t bytes) { const int64_t at = o; o += round_up(bytes, 16); return at; };
@@ -580,7 +550,7 @@ relp_status_t Engine::ft_plan_and_alloc() {
     std::memset(h_ft_hdr_, 0, 4 * sizeof(int32_t));
     {   // the kernel's report in mapped host memory; without it (allocation refused) the copies below do the same job
         void* hp = nullptr; void* dp = nullptr;
-        if (hipHostMalloc(&hp, sizeof(FtMirror) + sizeof(int32_t) * (size_t)m_, hipHostMallocMapped) == hipSuccess &&
+        if (hipHostMalloc(&hp, sizeof(FtMirror) + sizeof(int32_t) * (size_t)lay_.m, hipHostMallocMapped) == hipSuccess &&
             hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) {
             h_mirror_ = static_cast<FtMirror*>(hp); d_mirror_ = static_cast<FtMirror*>(dp);
             std::memset(h_mirror_, 0, sizeof(FtMirror));
@@ -590,7 +560,7 @@ relp_status_t Engine::ft_plan_and_alloc() {
         }
     }
     fts_ = FtState{};
-    fts_.m = m_; fts_.tcap = ft_tcap_; fts_.ldt = (int32_t)ldt; fts_.eta_cap = ft_eta_cap_;
+    fts_.m = lay_.m; fts_.tcap = ft_tcap_; fts_.ldt = (int32_t)ldt; fts_.eta_cap = ft_eta_cap_;
     fts_.hdr = reinterpret_cast<int32_t*>(d_ft_buf_ + o_hdr);
     fts_.slot_pivot = reinterpret_cast<int32_t*>(d_ft_buf_ + o_sp);
     fts_.slot_prev = reinterpret_cast<int32_t*>(d_ft_buf_ + o_pv);
@@ -637,11 +607,11 @@ relp_status_t Engine::ft_plan_and_alloc() {
 
 // k-major PRICE copy of the structural columns (relp_kernels.h: PriceEll; rebuilt when rows are removed)
 relp_status_t Engine::ft_build_price_ell() {
-    const int64_t ns = std::max(nr_normal_, 1);
+    const int64_t ns = std::max(lay_.nr_normal, 1);
     std::vector<uint16_t> idx((size_t)kPriceSlots * ns, 0);
     std::vector<double> val((size_t)kPriceSlots * ns, 0.0);
     std::vector<int32_t> longs, very_long;
-    for (int32_t p = 0; p < nr_normal_; ++p) {
+    for (int32_t p = 0; p < lay_.nr_normal; ++p) {
         const int64_t n = hc_ptr_[p + 1] - hc_ptr_[p];
         for (int64_t k = 0; k < std::min<int64_t>(n, kPriceSlots); ++k) {
             idx[(size_t)k * ns + p] = (uint16_t)hc_idx_[hc_ptr_[p] + k]; val[(size_t)k * ns + p] = hc_val_[hc_ptr_[p] + k];
@@ -676,7 +646,7 @@ relp_status_t Engine::ft_build_price_ell() {
     size_t o_idx32 = 0, o_lidx32 = 0;
     if (ft_tier_ >= 2) {                                   // the same two tables with 32-bit row indices (bit 31 = long column)
         std::vector<uint32_t> w(idx.size(), 0), lw(lidx.size(), 0);
-        for (int32_t p = 0; p < nr_normal_; ++p) {
+        for (int32_t p = 0; p < lay_.nr_normal; ++p) {
             const int64_t n = hc_ptr_[p + 1] - hc_ptr_[p];
             for (int64_t k = 0; k < std::min<int64_t>(n, kPriceSlots); ++k) w[(size_t)k * ns + p] = (uint32_t)hc_idx_[hc_ptr_[p] + k];
             if (n > kPriceSlots) w[p] |= kPriceLongFlag32;
@@ -745,8 +715,8 @@ relp_status_t Engine::ft_read_report(bool* have_basis) {
     since_flush_ = h_ft_hdr_[0];
     ft_need_refactor_ = h_ft_hdr_[2] != 0;
     if (have_basis) {
-        if (!h_basis_) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_basis_), sizeof(int32_t) * (size_t)std::max(m_alloc_rows_, m_), hipHostMallocDefault));
-        std::memcpy(h_basis_, h_mirror_->basis, sizeof(int32_t) * (size_t)m_);     // (the next launch rewrites the mirror)
+        if (!h_basis_) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_basis_), sizeof(int32_t) * (size_t)std::max(m_alloc_rows_, lay_.m), hipHostMallocDefault));
+        std::memcpy(h_basis_, h_mirror_->basis, sizeof(int32_t) * (size_t)lay_.m);     // (the next launch rewrites the mirror)
         *have_basis = true;
     }
     return RELP_OK;
@@ -770,18 +740,18 @@ void Engine::ft_enqueue_pivots(const FtState& go, int rule, int64_t left) {
     const ColumnTable ct = table();
     SelectPartials sp;
     sp.k1 = d_part_k1_; sp.j = d_part_j_; sp.in_basis = d_in_basis_; sp.tol_cost = cfg_.tol_cost; sp.rule = rule;
-    const int nb_struct = price_csc_blocks(0, nr_normal_), nb_virt = price_virtual_blocks(ct);
+    const int nb_struct = price_csc_blocks(0, lay_.nr_normal), nb_virt = price_virtual_blocks(ct);
     sp.n = nr_columns(); sp.offset = 0; sp.nb_struct = nb_struct; sp.tol_tie = cfg_.tol_tie; sp.p_lo = 0; sp.cols_per_slot = 256;
     for (int64_t k = 0; k < batch; ++k) {
         if (nb_struct > 0 && nb_virt > 0) {
-            launch_price_csc_all(csc(), ct, d_minus_pi_, d_d_, nr_normal_, phase_, sp, nb_virt, d_rec_, stream_);
+            launch_price_csc_all(csc(), ct, d_minus_pi_, d_d_, lay_.nr_normal, phase_, sp, nb_virt, d_rec_, stream_);
         } else {
-            launch_price_csc(csc(), ct, d_minus_pi_, d_d_, 0, nr_normal_, phase_, sp, d_rec_, stream_);
+            launch_price_csc(csc(), ct, d_minus_pi_, d_d_, 0, lay_.nr_normal, phase_, sp, d_rec_, stream_);
             SelectPartials spv = sp;
             spv.offset = nb_struct;
             launch_price_virtual_sel(ct, d_minus_pi_, d_d_, phase_, spv, d_rec_, stream_);
         }
-        launch_select_partials_csc(sp, nb_struct + nb_virt, d_d_, csc(), ct, m_, nullptr, d_rec_, stream_);
+        launch_select_partials_csc(sp, nb_struct + nb_virt, d_d_, csc(), ct, lay_.m, nullptr, d_rec_, stream_);
         pb.mirror = k + 1 == batch ? d_mirror_ : nullptr;
         launch_ft_run(dlu_, go, pb, 1, stream_);
     }
@@ -911,37 +881,37 @@ void Engine::enqueue_iteration_lu(int rule) {
     const DeferredUpdate du = deferred();
     SelectPartials sp;
     sp.k1 = d_part_k1_; sp.j = d_part_j_; sp.in_basis = d_in_basis_; sp.tol_cost = cfg_.tol_cost; sp.rule = rule;
-    const int nb_struct = price_csc_blocks(0, nr_normal_);
+    const int nb_struct = price_csc_blocks(0, lay_.nr_normal);
     sp.n = nr_columns(); sp.offset = 0; sp.nb_struct = nb_struct; sp.tol_tie = cfg_.tol_tie; sp.p_lo = 0; sp.cols_per_slot = 256;
     const int nb_virt = price_virtual_blocks(ct);
     prof_begin(RELP_K_PRICE);
     if (nb_struct > 0 && nb_virt > 0) {
-        launch_price_csc_all(csc(), ct, d_minus_pi_, d_d_, nr_normal_, phase_, sp, nb_virt, d_rec_, stream_);
+        launch_price_csc_all(csc(), ct, d_minus_pi_, d_d_, lay_.nr_normal, phase_, sp, nb_virt, d_rec_, stream_);
     } else {
-        launch_price_csc(csc(), ct, d_minus_pi_, d_d_, 0, nr_normal_, phase_, sp, d_rec_, stream_);
+        launch_price_csc(csc(), ct, d_minus_pi_, d_d_, 0, lay_.nr_normal, phase_, sp, d_rec_, stream_);
         SelectPartials spv = sp;
         spv.offset = nb_struct;
         launch_price_virtual_sel(ct, d_minus_pi_, d_d_, phase_, spv, d_rec_, stream_);
     }
     prof_end();
     prof_begin(RELP_K_SELECT_COLUMN);
-    launch_select_partials_csc(sp, nb_struct + nb_virt, d_d_, csc(), ct, m_, d_aq_, d_rec_, stream_);
+    launch_select_partials_csc(sp, nb_struct + nb_virt, d_d_, csc(), ct, lay_.m, d_aq_, d_rec_, stream_);
     prof_end();
     prof_begin(RELP_K_FTRAN);
     launch_lu_ftran(dlu_, d_aq_, d_v_, d_lu_scratch_, d_rec_, stream_);
     prof_end();
     prof_begin(RELP_K_APPLY_W);
-    launch_apply_w_rmin(du, m_, d_v_, d_alpha_, d_b_, tolerances(), d_rmin_, d_rec_, stream_);
+    launch_apply_w_rmin(du, lay_.m, d_v_, d_alpha_, d_b_, tolerances(), d_rmin_, d_rec_, stream_);
     prof_end();
     prof_begin(RELP_K_RATIO);
-    launch_ratio_rows(d_alpha_, d_b_, d_basis_, m_, tolerances(), du, d_rmin_, 256, d_rec_, stream_);
+    launch_ratio_rows(d_alpha_, d_b_, d_basis_, lay_.m, tolerances(), du, d_rmin_, 256, d_rec_, stream_);
     prof_end();
     prof_begin(RELP_K_UPDATE_W);
-    launch_update_w(du, m_, d_alpha_, d_rec_, stream_);
+    launch_update_w(du, lay_.m, d_alpha_, d_rec_, stream_);
     prof_end();
     prof_begin(RELP_K_UPDATE_VECTORS);
     launch_lu_btran(dlu_, du, nullptr, -1, d_rho_, d_lu_scratch_, d_rec_, stream_);
-    launch_update_vectors(m_, d_alpha_, d_rho_, d_b_, d_minus_pi_, d_basis_, d_in_basis_, d_trace_, trace_cap_, d_rec_,
+    launch_update_vectors(lay_.m, d_alpha_, d_rho_, d_b_, d_minus_pi_, d_basis_, d_in_basis_, d_trace_, trace_cap_, d_rec_,
                           stream_);
     prof_end();
     if (++since_flush_ >= block_) enqueue_flush();

@@ -35,18 +35,11 @@ relp_status_t Engine::luf_prepare() {
     if (!luf_) luf_ = new LufState();
     LufState& S = *luf_;
     if (S.d_buf) { HIP_TRY(hipFree(S.d_buf)); S.d_buf = nullptr; }
-    const int32_t m = m_, nprov = nr_normal_ + nr_virtual_, na = nr_artificial_;
+    const int32_t m = lay_.m, nprov = lay_.n_provider, na = lay_.nr_artificial;
     // row-major copy of the provider columns (structural incl. bound rows, virtual), in column order
     std::vector<int32_t> rcount(m + 1, 0);
     auto each = [&](auto f) {
-        for (int32_t p = 0; p < nr_normal_; ++p) {
-            for (int64_t e = hc_ptr_[p]; e < hc_ptr_[p + 1]; ++e) f(hc_idx_[e], p, hc_val_[e]);
-            if (bound_row_h_[p] >= 0) f(bound_row_h_[p], p, 1.0);
-        }
-        for (int32_t v = 0; v < nr_virtual_; ++v) {
-            if (vrow0_h_[v] >= 0) f(vrow0_h_[v], nr_normal_ + v, (double)vsign_h_[v]);
-            if (vrow1_h_[v] >= 0) f(vrow1_h_[v], nr_normal_ + v, 1.0);
-        }
+        for (int32_t p = 0; p < nprov; ++p) lay_.for_each_provider_entry(p, csc_column(), [&](int32_t i, double v) { f(i, p, v); });
     };
     int64_t nnz = 0;
     each([&](int32_t i, int32_t, double) { ++rcount[i + 1]; ++nnz; });
@@ -54,20 +47,20 @@ relp_status_t Engine::luf_prepare() {
     std::vector<int32_t> rcol((size_t)nnz), fill(rcount.begin(), rcount.end() - 1), art_of_row(m, -1);
     std::vector<double> rval((size_t)nnz);
     each([&](int32_t i, int32_t p, double v) { const int32_t o = fill[i]++; rcol[o] = p; rval[o] = v; });
-    for (int32_t a = 0; a < na; ++a) art_of_row[column_to_row_[a]] = a;
+    for (int32_t a = 0; a < na; ++a) art_of_row[lay_.column_to_row[a]] = a;
     // sizes: the bump is eliminated on sparse rows in an arena; RELP_LUF_BUMP_CAP bounds its rows (default: any), a bump or a
     // fill-in beyond the arrays falls back to the host
     const char* cap_env = std::getenv("RELP_LUF_BUMP_CAP");
     S.nb_cap = std::min<int32_t>(m, cap_env ? std::max(16, std::atoi(cap_env)) : m);
     // (a small dense bump may fill in completely)
-    const int64_t arena_cap = std::min<int64_t>(INT32_MAX / 4, 3 * (nnz + (int64_t)wrapped_na_ + na + m) + 64 * (int64_t)S.nb_cap + 1024 +
+    const int64_t arena_cap = std::min<int64_t>(INT32_MAX / 4, 3 * (nnz + (int64_t)lay_.wrapped_na + na + m) + 64 * (int64_t)S.nb_cap + 1024 +
                                                                   4 * std::min<int64_t>((int64_t)S.nb_cap * S.nb_cap, int64_t(1) << 21));
     S.cap = (int32_t)arena_cap;
     const int32_t nt = luf_threads();
     int64_t o = 0;
     auto take = [&](int64_t bytes) { const int64_t at = o; o += round_up(std::max<int64_t>(bytes, 16), 16); return at; };
     const int64_t o_rptr = take(4 * ((int64_t)m + 1)), o_rcol = take(4 * nnz), o_rval = take(8 * nnz), o_art = take(4 * (int64_t)m),
-                  o_wr = take(4 * (int64_t)std::max<int32_t>(wrapped_na_, 1));
+                  o_wr = take(4 * (int64_t)std::max<int32_t>(lay_.wrapped_na, 1));
     const int64_t o_posp = take(4 * ((int64_t)nprov + 1)), o_posa = take(4 * ((int64_t)na + 1));
     int64_t o_m[13];
     for (auto& v : o_m) v = take(4 * (int64_t)m);       // wrow_pos rcount ccount claim claim2 list list2 piv brow bcol lrow lcol (+1 spare)
@@ -118,14 +111,14 @@ relp_status_t Engine::luf_prepare() {
         HIP_TRY(hipMemcpy(B + o_rval, rval.data(), 8 * (size_t)nnz, hipMemcpyHostToDevice));
     }
     HIP_TRY(hipMemcpy(B + o_art, art_of_row.data(), 4 * (size_t)m, hipMemcpyHostToDevice));
-    if (wrapped_na_ > 0) HIP_TRY(hipMemcpy(B + o_wr, column_to_row_.data(), 4 * (size_t)wrapped_na_, hipMemcpyHostToDevice));
+    if (lay_.wrapped_na > 0) HIP_TRY(hipMemcpy(B + o_wr, lay_.column_to_row.data(), 4 * (size_t)lay_.wrapped_na, hipMemcpyHostToDevice));
     auto I32 = [&](int64_t at) { return reinterpret_cast<int32_t*>(B + at); };
     auto F64 = [&](int64_t at) { return reinterpret_cast<double*>(B + at); };
     S.M = LufMatrix{};
     S.M.m = m; S.M.na = na; S.M.n_provider = nprov;
     S.M.csc = csc(); S.M.ct = table();
     S.M.rptr = I32(o_rptr); S.M.rcol = I32(o_rcol); S.M.rval = F64(o_rval); S.M.art_of_row = I32(o_art);
-    S.M.wrapped_na = wrapped_na_; S.M.wrapped_row = I32(o_wr);
+    S.M.wrapped_na = lay_.wrapped_na; S.M.wrapped_row = I32(o_wr);
     LufWork& W = S.W;
     W.pos_p = I32(o_posp); W.pos_a = I32(o_posa);
     W.wrow_pos = I32(o_m[0]); W.rcount = I32(o_m[1]); W.ccount = I32(o_m[2]); W.claim = I32(o_m[3]); W.claim2 = I32(o_m[4]);
@@ -173,7 +166,7 @@ relp_status_t Engine::luf_prepare() {
     }
     S.pinfo = reinterpret_cast<FtPivotInfo*>(B + o_pinfo);
     S.dirty = false;
-    S.key[0] = m_; S.key[1] = nr_artificial_; S.key[2] = phase_; S.key[3] = wrapped_na_;
+    S.key[0] = lay_.m; S.key[1] = lay_.nr_artificial; S.key[2] = phase_; S.key[3] = lay_.wrapped_na;
     return RELP_OK;
 }
 
@@ -185,7 +178,7 @@ relp_status_t Engine::lu_factor_on_device(int32_t* device_status) {
     // (the device factorisation packs its images for layouts 0 and 1 and keeps its working sets in one workgroup's LDS:
     // beyond their row range the host factorises)
     if (ft_tier_ >= 2) return RELP_E_UNSUPPORTED;
-    if (!luf_ || luf_->dirty || luf_->key[0] != m_ || luf_->key[1] != nr_artificial_ || luf_->key[2] != phase_ || luf_->key[3] != wrapped_na_) {
+    if (!luf_ || luf_->dirty || luf_->key[0] != lay_.m || luf_->key[1] != lay_.nr_artificial || luf_->key[2] != phase_ || luf_->key[3] != lay_.wrapped_na) {
         const relp_status_t st = luf_prepare();            // (a row removal or the phase switch renumbers rows / columns)
         if (st) return st;
     }
@@ -233,7 +226,7 @@ relp_status_t Engine::lu_factor_on_device(int32_t* device_status) {
     if (status[0] == LUF_SINGULAR) return fail(RELP_E_SINGULAR, "singular basis (device factorisation)");
     if (status[0] != LUF_OK) return RELP_E_UNSUPPORTED;      // bump too large / no room: not an error, the host takes over
     if (resident) for (int q = 0; q < 4; ++q) if (desc[q][LUF_D_STATUS] != LUF_OK) return RELP_E_UNSUPPORTED;
-    const int32_t m = m_, nl = status[3], nu = status[4];
+    const int32_t m = lay_.m, nl = status[3], nu = status[4];
     hlu_ = LUFactors{};
     hlu_.m = m; hlu_.nnz_l = nl; hlu_.nnz_u = (int64_t)nu + m;
     S.resident = resident;
@@ -279,7 +272,7 @@ relp_status_t Engine::lu_factor_on_device(int32_t* device_status) {
 // the factors of the last device factorisation -> hlu_ with level schedules, like after lu_factor (relp_lu.cpp)
 relp_status_t Engine::luf_download_factors() {
     LufState& S = *luf_;
-    const int32_t m = m_, nl = (int32_t)hlu_.nnz_l, nu = (int32_t)(hlu_.nnz_u - m);
+    const int32_t m = lay_.m, nl = (int32_t)hlu_.nnz_l, nu = (int32_t)(hlu_.nnz_u - m);
     hlu_.rowperm.resize(m); hlu_.colperm.resize(m);
     std::vector<double> diag(m), ones(m, 1.0);
     HIP_TRY(hipMemcpyAsync(hlu_.rowperm.data(), S.O.rowperm, 4 * (size_t)m, hipMemcpyDeviceToHost, stream_));
@@ -336,7 +329,7 @@ namespace relp {
 relp_status_t Engine::lu_factor_residual(double* out) {
     if (!lu_) return fail(RELP_E_UNSUPPORTED, "the LU engine's factors");
     *out = -1.0;
-    const int32_t m = m_;
+    const int32_t m = lay_.m;
     if (m > 1024 || hlu_.m != m) return RELP_OK;
     if (ft_) {                                             // updates pending: the factors are those of an earlier basis
         relp_status_t hs = ft_read_hdr();

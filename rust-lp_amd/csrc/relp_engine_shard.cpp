@@ -8,11 +8,11 @@ namespace relp {
 // RCCL collectives on the same stream, so there is no host sync inside a pivot.
 // ------------------------------------------------------------------------------------------------
 void Engine::shard_ranges(int32_t* col_lo, int32_t* col_hi, int32_t* row_lo, int32_t* row_hi, int32_t* stride) const {
-    if (col_lo) *col_lo = col_lo_;
-    if (col_hi) *col_hi = col_hi_;
-    if (row_lo) *row_lo = row_lo_;
-    if (row_hi) *row_hi = row_hi_;
-    if (stride) *stride = row_stride_;
+    if (col_lo) *col_lo = lay_.col_lo;
+    if (col_hi) *col_hi = lay_.col_hi;
+    if (row_lo) *row_lo = lay_.row_lo;
+    if (row_hi) *row_hi = lay_.row_hi;
+    if (stride) *stride = lay_.row_stride;
 }
 
 // Tableau engine, one pivot after the candidates were exchanged: ratio test (replicated), row update
@@ -27,7 +27,7 @@ relp_status_t Engine::shard_pivot() {
     // the ratio test ran in relp_shard_select_column; tableau row / reduced costs / PRICE partials of the
     // owned columns and W, b, basis (replicated) in one launch
     prof_begin(RELP_K_PRICE);
-    launch_tab_update_all(tv, du, sp, m_, d_alpha_, d_b_, d_basis_, d_in_basis_, d_trace_, trace_cap_, d_rec_, stream_);
+    launch_tab_update_all(tv, du, sp, lay_.m, d_alpha_, d_b_, d_basis_, d_in_basis_, d_trace_, trace_cap_, d_rec_, stream_);
     prof_end();
     tab_partials_valid_ = true;
     if (++since_flush_ >= block_) enqueue_flush();
@@ -47,21 +47,21 @@ relp_status_t Engine::shard_price(double* dev_candidate) {
         // PRICE's final reduction over the local partials + the local winner's tableau column, written
         // straight into the candidate message
         prof_begin(RELP_K_FTRAN);
-        launch_tab_select_column_msg(tv, deferred(), sp, tab_scan_blocks(sc_hi_ - sc_lo_), dev_candidate, d_b_, tolerances(), d_rec_,
+        launch_tab_select_column_msg(tv, deferred(), sp, tab_scan_blocks(lay_.sc_hi - lay_.sc_lo), dev_candidate, d_b_, tolerances(), d_rec_,
                                      stream_);
         prof_end();
         return RELP_OK;
     }
-    const double* A = dA_ - (int64_t)col_lo_ * ld_a_;
+    const double* A = dA_ - (int64_t)lay_.col_lo * ld_a_;
     prof_begin(RELP_K_PRICE);
-    enqueue_price(phase_, d_minus_pi_, d_rec_, col_lo_, col_hi_);
+    enqueue_price(phase_, d_minus_pi_, d_rec_, lay_.col_lo, lay_.col_hi);
     prof_end();
     prof_begin(RELP_K_SELECT_COLUMN);
     launch_select_column(d_d_, d_in_basis_, nr_columns(), rule, cfg_.tol_cost, cfg_.tol_tie, d_rec_, stream_);
     prof_end();
     prof_begin(RELP_K_BUILD_COLUMN);
-    launch_build_column(A, ld_a_, table(), m_, d_aq_, d_rec_, stream_);
-    launch_pack_candidate(d_aq_, m_, dev_candidate, d_rec_, stream_);
+    launch_build_column(A, ld_a_, table(), lay_.m, d_aq_, d_rec_, stream_);
+    launch_pack_candidate(d_aq_, lay_.m, dev_candidate, d_rec_, stream_);
     prof_end();
     return RELP_OK;
 }
@@ -73,33 +73,33 @@ relp_status_t Engine::shard_select_column(const double* dev_candidates, int32_t 
         // the winner's payload is the entering tableau column (alpha) itself: pick it and run the ratio test
         if (count > 64) return fail(RELP_E_UNSUPPORTED, "at most 64 shards");
         prof_begin(RELP_K_RATIO);
-        launch_tab_select_candidate_ratio(dev_candidates, count, cand_len_, m_, d_alpha_, d_b_, d_basis_, rule, tolerances(),
+        launch_tab_select_candidate_ratio(dev_candidates, count, lay_.candidate_len, lay_.m, d_alpha_, d_b_, d_basis_, rule, tolerances(),
                                           deferred(), -1, d_rec_, stream_);
         prof_end();
         return RELP_OK;
     }
-    launch_select_candidate(dev_candidates, count, cand_len_, m_, d_aq_, rule, cfg_.tol_tie, d_rec_, stream_);
+    launch_select_candidate(dev_candidates, count, lay_.candidate_len, lay_.m, d_aq_, rule, cfg_.tol_tie, d_rec_, stream_);
     return RELP_OK;
 }
 
 relp_status_t Engine::shard_ftran(double* dev_alpha_slice) {
     if (lu_) return fail(RELP_E_UNSUPPORTED, "the LU engine is not sharded");
-    double* Binv = dBinv_ - (int64_t)row_lo_ * ld_b_;
+    double* Binv = dBinv_ - (int64_t)lay_.row_lo * ld_b_;
     prof_begin(RELP_K_FTRAN);
-    launch_ftran(Binv, ld_b_, m_, row_lo_, row_hi_, d_aq_, dev_alpha_slice, row_lo_, d_rec_, stream_);
-    launch_pad_slice(dev_alpha_slice, row_hi_ - row_lo_, row_stride_, stream_);
+    launch_ftran(Binv, ld_b_, lay_.m, lay_.row_lo, lay_.row_hi, d_aq_, dev_alpha_slice, lay_.row_lo, d_rec_, stream_);
+    launch_pad_slice(dev_alpha_slice, lay_.row_hi - lay_.row_lo, lay_.row_stride, stream_);
     prof_end();
     return RELP_OK;
 }
 
 relp_status_t Engine::shard_ratio(const double* dev_alpha_slices, int32_t count, double* dev_rho) {
     if (lu_) return fail(RELP_E_UNSUPPORTED, "the LU engine is not sharded");
-    double* Binv = dBinv_ - (int64_t)row_lo_ * ld_b_;
+    double* Binv = dBinv_ - (int64_t)lay_.row_lo * ld_b_;
     if (block_ == 0) {
         prof_begin(RELP_K_RATIO);
-        launch_gather_alpha(dev_alpha_slices, count, row_stride_, m_, d_alpha_, d_rec_, stream_);
-        launch_ratio(d_alpha_, d_b_, d_basis_, m_, tolerances(), d_rec_, stream_);
-        launch_compute_rho(Binv, ld_b_, m_, row_lo_, row_hi_, dev_rho, d_rec_, stream_);
+        launch_gather_alpha(dev_alpha_slices, count, lay_.row_stride, lay_.m, d_alpha_, d_rec_, stream_);
+        launch_ratio(d_alpha_, d_b_, d_basis_, lay_.m, tolerances(), d_rec_, stream_);
+        launch_compute_rho(Binv, ld_b_, lay_.m, lay_.row_lo, lay_.row_hi, dev_rho, d_rec_, stream_);
         prof_end();
         return RELP_OK;
     }
@@ -107,16 +107,16 @@ relp_status_t Engine::shard_ratio(const double* dev_alpha_slices, int32_t count,
     // updates its copy of W and contributes the rows of B0inv it owns to rho (SUM over ranks).
     const DeferredUpdate du = deferred();
     prof_begin(RELP_K_APPLY_W);
-    launch_gather_alpha(dev_alpha_slices, count, row_stride_, m_, d_v_, d_rec_, stream_);
-    launch_apply_w(du, m_, d_v_, d_alpha_, d_rec_, stream_);
+    launch_gather_alpha(dev_alpha_slices, count, lay_.row_stride, lay_.m, d_v_, d_rec_, stream_);
+    launch_apply_w(du, lay_.m, d_v_, d_alpha_, d_rec_, stream_);
     prof_end();
     prof_begin(RELP_K_RATIO);
-    launch_ratio(d_alpha_, d_b_, d_basis_, m_, tolerances(), d_rec_, stream_);
+    launch_ratio(d_alpha_, d_b_, d_basis_, lay_.m, tolerances(), d_rec_, stream_);
     prof_end();
     prof_begin(RELP_K_UPDATE_W);
     launch_eta_prepare(du, d_rec_, stream_);
-    launch_update_w(du, m_, d_alpha_, d_rec_, stream_);
-    launch_rho_deferred(du, Binv, ld_b_, m_, row_lo_, row_hi_, dev_rho, d_rec_, stream_);
+    launch_update_w(du, lay_.m, d_alpha_, d_rec_, stream_);
+    launch_rho_deferred(du, Binv, ld_b_, lay_.m, lay_.row_lo, lay_.row_hi, dev_rho, d_rec_, stream_);
     prof_end();
     return RELP_OK;
 }
@@ -125,9 +125,9 @@ relp_status_t Engine::shard_flush_begin(double** dev_snapshot, int64_t* len) {
     if (lu_) return fail(RELP_E_UNSUPPORTED, "the LU engine is not sharded");
     if (len) *len = 0;
     if (block_ == 0) return RELP_OK;
-    double* Binv = dBinv_ - (int64_t)row_lo_ * ld_b_;
+    double* Binv = dBinv_ - (int64_t)lay_.row_lo * ld_b_;
     prof_begin(RELP_K_FLUSH);
-    launch_flush_snapshot(deferred(), Binv, ld_b_, row_lo_, row_hi_, d_rec_, stream_);
+    launch_flush_snapshot(deferred(), Binv, ld_b_, lay_.row_lo, lay_.row_hi, d_rec_, stream_);
     prof_end();
     if (dev_snapshot) *dev_snapshot = d_R_;
     if (len) *len = ld_b_ * block_;
@@ -138,9 +138,9 @@ relp_status_t Engine::shard_flush_end() {
     if (lu_) return fail(RELP_E_UNSUPPORTED, "the LU engine is not sharded");
     if (block_ == 0) return RELP_OK;
     const DeferredUpdate du = deferred();
-    double* Binv = dBinv_ - (int64_t)row_lo_ * ld_b_;
+    double* Binv = dBinv_ - (int64_t)lay_.row_lo * ld_b_;
     prof_begin(RELP_K_FLUSH);
-    launch_flush_apply(du, Binv, ld_b_, m_, row_lo_, row_hi_, d_rec_, stream_);
+    launch_flush_apply(du, Binv, ld_b_, lay_.m, lay_.row_lo, lay_.row_hi, d_rec_, stream_);
     launch_flush_reset(du, d_rec_, stream_);
     prof_end();
     since_flush_ = 0;
@@ -149,14 +149,14 @@ relp_status_t Engine::shard_flush_end() {
 
 relp_status_t Engine::shard_update(const double* dev_rho) {
     if (lu_) return fail(RELP_E_UNSUPPORTED, "the LU engine is not sharded");
-    double* Binv = dBinv_ - (int64_t)row_lo_ * ld_b_;
+    double* Binv = dBinv_ - (int64_t)lay_.row_lo * ld_b_;
     prof_begin(RELP_K_UPDATE_VECTORS);
-    launch_update_vectors(m_, d_alpha_, dev_rho, d_b_, d_minus_pi_, d_basis_, d_in_basis_, d_trace_, trace_cap_, d_rec_,
+    launch_update_vectors(lay_.m, d_alpha_, dev_rho, d_b_, d_minus_pi_, d_basis_, d_in_basis_, d_trace_, trace_cap_, d_rec_,
                           stream_);
     prof_end();
     if (block_ == 0) {
         prof_begin(RELP_K_UPDATE_INVERSE);
-        launch_update_inverse(Binv, ld_b_, m_, row_lo_, row_hi_, d_alpha_, dev_rho, d_rec_, stream_);
+        launch_update_inverse(Binv, ld_b_, lay_.m, lay_.row_lo, lay_.row_hi, d_alpha_, dev_rho, d_rec_, stream_);
         prof_end();
     } else {
         ++since_flush_;
@@ -173,10 +173,10 @@ relp_status_t Engine::shard_update(const double* dev_rho) {
 // every rank and enters in that row at zero level.  No eligible column anywhere: the row is redundant.
 relp_status_t Engine::remove_artificial_basis_variables_sharded(std::vector<int32_t>& rows_to_remove) {
     HIP_TRY(hipStreamSynchronize(stream_));
-    std::vector<int32_t> basis(m_);
-    HIP_TRY(hipMemcpy(basis.data(), d_basis_, sizeof(int32_t) * m_, hipMemcpyDeviceToHost));
+    std::vector<int32_t> basis(lay_.m);
+    HIP_TRY(hipMemcpy(basis.data(), d_basis_, sizeof(int32_t) * lay_.m, hipMemcpyDeviceToHost));
     std::vector<int32_t> arts;
-    for (int32_t v : basis) if (v < nr_artificial_) arts.push_back(v);
+    for (int32_t v : basis) if (v < lay_.nr_artificial) arts.push_back(v);
     if (arts.empty()) return RELP_OK;
     if (!coll_allgather_)
         return fail(RELP_E_STATE, "artificial variables are still basic after phase 1: the sharded engine pivots them out "
@@ -186,7 +186,7 @@ relp_status_t Engine::remove_artificial_basis_variables_sharded(std::vector<int3
     const int32_t g = std::max(cfg_.shard_count, 1);
     const bool textbook = cfg_.artificial_removal == RELP_ARTIFICIAL_TEXTBOOK;
     for (int32_t a : arts) {
-        int32_t pivot_row = column_to_row_[a];             // phase_one.rs:236: the row the artificial STARTED in
+        int32_t pivot_row = lay_.column_to_row[a];             // phase_one.rs:236: the row the artificial STARTED in
         if (textbook) pivot_row = (int32_t)(std::find(basis.begin(), basis.end(), a) - basis.begin());   // the row it is basic in
         if ((st = download_rec())) return st;
         h_rec_->outcome = DEV_RUNNING;
@@ -196,20 +196,20 @@ relp_status_t Engine::remove_artificial_basis_variables_sharded(std::vector<int3
         const SelectPartials sp = tab_partials(RELP_RULE_FIRST_PROFITABLE);        // key = column index
         Tolerances zt = tolerances();
         if (textbook) zt.cost = INFINITY;               // any reduced cost will do: the pivot is at zero level
-        launch_tab_zero_level_scan(tv, du, sp, pivot_row, nr_artificial_, zt, d_rec_, stream_);
-        launch_tab_select_column_msg(tv, du, sp, tab_scan_blocks(sc_hi_ - sc_lo_), d_msg_cand_, d_b_, tolerances(), d_rec_, stream_);
-        if (coll_allgather_(coll_ctx_, d_msg_cand_, d_msg_cands_, cand_len_ * (int64_t)sizeof(double), stream_))
+        launch_tab_zero_level_scan(tv, du, sp, pivot_row, lay_.nr_artificial, zt, d_rec_, stream_);
+        launch_tab_select_column_msg(tv, du, sp, tab_scan_blocks(lay_.sc_hi - lay_.sc_lo), d_msg_cand_, d_b_, tolerances(), d_rec_, stream_);
+        if (coll_allgather_(coll_ctx_, d_msg_cand_, d_msg_cands_, lay_.candidate_len * (int64_t)sizeof(double), stream_))
             return fail(RELP_E_HIP, "all-gather of the zero-level candidates failed");
-        launch_tab_select_candidate_ratio(d_msg_cands_, g, cand_len_, m_, d_alpha_, d_b_, d_basis_, RELP_RULE_FIRST_PROFITABLE,
+        launch_tab_select_candidate_ratio(d_msg_cands_, g, lay_.candidate_len, lay_.m, d_alpha_, d_b_, d_basis_, RELP_RULE_FIRST_PROFITABLE,
                                           tolerances(), du, pivot_row, d_rec_, stream_);
         if ((st = download_rec())) return st;
         if (h_rec_->outcome == DEV_NO_CANDIDATE) {      // (textbook: the artificial's own row; remove_rows moves it there first)
-            if (textbook) { stuck_artificials_.push_back(a); rows_to_remove.push_back(column_to_row_[a]); }
+            if (textbook) { stuck_artificials_.push_back(a); rows_to_remove.push_back(lay_.column_to_row[a]); }
             else rows_to_remove.push_back(a);
             continue;
         }
         if (h_rec_->alpha_r == 0.0) return fail(RELP_E_ZERO_PIVOT, "Pivot value can't be zero.");
-        launch_tab_update_all(tv, du, sp, m_, d_alpha_, d_b_, d_basis_, d_in_basis_, d_trace_, trace_cap_, d_rec_, stream_);
+        launch_tab_update_all(tv, du, sp, lay_.m, d_alpha_, d_b_, d_basis_, d_in_basis_, d_trace_, trace_cap_, d_rec_, stream_);
         tab_partials_valid_ = false;
         basis[pivot_row] = h_rec_->q;
         if (++since_flush_ >= block_) enqueue_flush();
@@ -225,11 +225,11 @@ relp_status_t Engine::shard_set_collectives(relp_allgather_fn ag, relp_allreduce
     if (!d_msg_cand_) {
         HIP_TRY(dev_alloc(&d_msg_status_, 2));
         HIP_TRY(dev_alloc(&d_msg_statuses_, 2 * g));
-        HIP_TRY(dev_alloc(&d_msg_cand_, cand_len_));
-        HIP_TRY(dev_alloc(&d_msg_cands_, cand_len_ * g));
+        HIP_TRY(dev_alloc(&d_msg_cand_, lay_.candidate_len));
+        HIP_TRY(dev_alloc(&d_msg_cands_, lay_.candidate_len * g));
         if (!tableau_) {
-            HIP_TRY(dev_alloc(&d_msg_slice_, row_stride_));
-            HIP_TRY(dev_alloc(&d_msg_slices_, (int64_t)row_stride_ * g));
+            HIP_TRY(dev_alloc(&d_msg_slice_, lay_.row_stride));
+            HIP_TRY(dev_alloc(&d_msg_slices_, (int64_t)lay_.row_stride * g));
             HIP_TRY(dev_alloc(&d_msg_rho_, rho_len()));
         }
     }
@@ -255,16 +255,16 @@ relp_status_t Engine::shard_iteration() {
         const SelectPartials sp = tab_partials(rule);
         if (!tab_partials_valid_) { launch_tab_scan(tv, sp, d_rec_, stream_); tab_partials_valid_ = true; }
         prof_begin(RELP_K_FTRAN);
-        launch_tab_select_column_msg(tv, du, sp, tab_scan_blocks(sc_hi_ - sc_lo_), d_msg_cand_, d_b_, tolerances(), d_rec_, stream_,
+        launch_tab_select_column_msg(tv, du, sp, tab_scan_blocks(lay_.sc_hi - lay_.sc_lo), d_msg_cand_, d_b_, tolerances(), d_rec_, stream_,
                                      d_shadow_, d_shadow_meta_);
         prof_end();
-        if (coll_allgather_(coll_ctx_, d_msg_cand_, d_msg_cands_, cand_len_ * (int64_t)sizeof(double), stream_))
+        if (coll_allgather_(coll_ctx_, d_msg_cand_, d_msg_cands_, lay_.candidate_len * (int64_t)sizeof(double), stream_))
             return broken("all-gather of the PRICE candidates failed");
         ++coll_step_;
         prof_begin(RELP_K_PRICE);
-        launch_tab_ratio_update_all(tv, du, sp, m_, nullptr, d_b_, d_b_alt_, d_basis_, d_basis_alt_, d_in_basis_, d_trace_,
+        launch_tab_ratio_update_all(tv, du, sp, lay_.m, nullptr, d_b_, d_b_alt_, d_basis_, d_basis_alt_, d_in_basis_, d_trace_,
                                     trace_cap_, tolerances(), nullptr, d_shadow_, d_shadow_meta_, d_rec_, stream_, d_msg_cands_, g,
-                                    cand_len_, rule);
+                                    lay_.candidate_len, rule);
         prof_end();
         std::swap(d_b_, d_b_alt_);
         std::swap(d_basis_, d_basis_alt_);
@@ -274,13 +274,13 @@ relp_status_t Engine::shard_iteration() {
         return RELP_OK;
     }
     if ((st = shard_price(d_msg_cand_))) return st;
-    if (coll_allgather_(coll_ctx_, d_msg_cand_, d_msg_cands_, cand_len_ * (int64_t)sizeof(double), stream_))
+    if (coll_allgather_(coll_ctx_, d_msg_cand_, d_msg_cands_, lay_.candidate_len * (int64_t)sizeof(double), stream_))
         return broken("all-gather of the PRICE candidates failed");
     ++coll_step_;
     if ((st = shard_select_column(d_msg_cands_, g))) return st;
     if (tableau_) return shard_pivot();
     if ((st = shard_ftran(d_msg_slice_))) return st;
-    if (coll_allgather_(coll_ctx_, d_msg_slice_, d_msg_slices_, row_stride_ * (int64_t)sizeof(double), stream_))
+    if (coll_allgather_(coll_ctx_, d_msg_slice_, d_msg_slices_, lay_.row_stride * (int64_t)sizeof(double), stream_))
         return broken("all-gather of the FTRAN slices failed");
     ++coll_step_;
     if ((st = shard_ratio(d_msg_slices_, g, d_msg_rho_))) return st;
@@ -306,9 +306,9 @@ relp_status_t Engine::shard_iteration() {
 // `from_step`: the collectives of this pivot with a lower index have happened already (the pivot that failed).
 relp_status_t Engine::shard_iteration_comm_only(int from_step) {
     auto broken = [&](const char* what) { coll_broken_ = true; return fail(RELP_E_HIP, what); };
-    if (from_step <= 0 && coll_allgather_(coll_ctx_, d_msg_cand_, d_msg_cands_, cand_len_ * (int64_t)sizeof(double), stream_)) return broken("all-gather failed");
+    if (from_step <= 0 && coll_allgather_(coll_ctx_, d_msg_cand_, d_msg_cands_, lay_.candidate_len * (int64_t)sizeof(double), stream_)) return broken("all-gather failed");
     if (tableau_) return RELP_OK;                          // (its flush is local)
-    if (from_step <= 1 && coll_allgather_(coll_ctx_, d_msg_slice_, d_msg_slices_, row_stride_ * (int64_t)sizeof(double), stream_)) return broken("all-gather failed");
+    if (from_step <= 1 && coll_allgather_(coll_ctx_, d_msg_slice_, d_msg_slices_, lay_.row_stride * (int64_t)sizeof(double), stream_)) return broken("all-gather failed");
     if (from_step <= 2 && coll_allreduce_(coll_ctx_, d_msg_rho_, rho_len(), stream_)) return broken("all-reduce failed");
     ++shadow_flush_;
     if (block_ > 0 && shadow_flush_ >= block_) {

@@ -11,6 +11,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "relp_layout.hpp"   // kWrappedArtificialBase
+
 namespace relp {
 
 enum DeviceOutcome : int32_t { DEV_RUNNING = 0, DEV_NO_CANDIDATE = 1, DEV_NO_ROW = 2 };
@@ -139,9 +141,6 @@ struct EllSchedule {
     const int32_t* rhs_pos;      // m: i with rhs_src[i] == pivot, or -1 (the inverse of rhs_src)
     const uint32_t* triv_bits;   // m bits: pivot is in `triv`
 };
-// Column indices at or above this value are artificial variables that survived phase 1 (see
-// Engine::switch_to_phase_two): INT32_MAX - (na - 1 - a).  They have no flag, no cost and no column.
-static constexpr int32_t kWrappedArtificialBase = 0x40000000;
 
 struct DeviceCSC { const int64_t* col_ptr; const int32_t* row_idx; const double* values; };
 

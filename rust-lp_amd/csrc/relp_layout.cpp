@@ -1,0 +1,154 @@
+// relp_layout.cpp -- the standard form of a relp_matrix_data_t.  See relp_layout.hpp.
+#include "relp_layout.hpp"
+
+#include <algorithm>
+#include <cmath>
+
+namespace relp {
+
+static relp_status_t fail(std::string* err, relp_status_t code, const char* msg) {
+    if (err) *err = msg;
+    return code;
+}
+
+static int64_t round_up_even(int64_t v) { return (v + 1) & ~int64_t(1); }
+
+void shard_column_range(int32_t n, int32_t rank, int32_t count, int32_t* lo, int32_t* hi) {
+    if (count < 1) count = 1;
+    const int32_t per = (n + count - 1) / count;
+    const int32_t a = std::min(n, rank * per);
+    if (lo) *lo = a;
+    if (hi) *hi = std::min(n, a + per);
+}
+
+relp_status_t Layout::plan(const relp_matrix_data_t& md, const relp_config_t& cfg, std::string* err) {
+    if (md.nr_normal < 0 || md.nr_eq < 0 || md.nr_range < 0 || md.nr_le < 0 || md.nr_ge < 0)
+        return fail(err, RELP_E_ARG, "negative size");
+    const int32_t G = std::max(cfg.shard_count, 1), g = cfg.shard_rank;
+    if (g < 0 || g >= G) return fail(err, RELP_E_ARG, "bad shard rank");
+
+    nr_normal = md.nr_normal; nr_eq = md.nr_eq; nr_range = md.nr_range; nr_le = md.nr_le; nr_ge = md.nr_ge;
+    mc = nr_eq + nr_range + nr_le + nr_ge;
+    bound_row.assign(nr_normal, -1);
+    nr_bounds = 0;
+    for (int32_t j = 0; j < nr_normal; ++j)
+        if (md.upper_bound && std::isfinite(md.upper_bound[j])) bound_row[j] = mc + nr_bounds++;
+    m = mc + nr_bounds + nr_range;
+    engine = cfg.engine;
+    if (engine == RELP_ENGINE_AUTO) {
+        // INTEGRATION.md "which engine for which LP": the dense tableau while it fits comfortably, the LU engine beyond
+        const double n_all = (double)nr_normal + nr_range + nr_le + nr_ge + nr_bounds + nr_range + m;       // (+ m: identity / artificial block)
+        const bool fits = 8.0 * (double)m * n_all <= 64e9 && m <= 50000;
+        engine = (G > 1 || fits) ? RELP_ENGINE_TABLEAU : RELP_ENGINE_LU;
+    }
+    if (m < 1) return fail(err, RELP_E_ARG, "empty problem");
+    const int32_t row_start[7] = {0, nr_eq, nr_eq + nr_range, nr_eq + nr_range + nr_le, mc, mc + nr_bounds, m};
+    nr_virtual = nr_range + nr_le + nr_ge + nr_bounds + nr_range;
+    n_provider = nr_normal + nr_virtual;
+    vrow0.clear(); vrow1.clear(); vsign.clear();
+    auto slacks = [&](int32_t count, int32_t row, int32_t row1, int32_t sign) {
+        for (int32_t k = 0; k < count; ++k) { vrow0.push_back(row + k); vrow1.push_back(row1 < 0 ? -1 : row1 + k); vsign.push_back(sign); }
+    };
+    slacks(nr_range, row_start[1], row_start[5], 1);      // range slack: its row and its range-bound row
+    slacks(nr_le, row_start[2], -1, 1);
+    slacks(nr_ge, row_start[3], -1, -1);
+    slacks(nr_bounds, row_start[4], -1, 1);
+    slacks(nr_range, row_start[5], -1, 1);                // range-bound slack
+
+    // initial basis: <=-slacks, bound slacks, range-bound slacks are real pivots (matrix_data.rs:432-452);
+    // every other row gets an artificial, numbered before all provider columns (partially.rs:72-80)
+    std::vector<int32_t> real_row, real_col;
+    const int32_t col_start2 = nr_normal + nr_range;                    // <= slacks
+    const int32_t col_start4 = nr_normal + nr_range + nr_le + nr_ge;    // bound slacks
+    const int32_t col_start5 = col_start4 + nr_bounds;                  // range-bound slacks
+    for (int32_t k = 0; k < nr_le; ++k) { real_row.push_back(row_start[2] + k); real_col.push_back(col_start2 + k); }
+    for (int32_t k = 0; k < nr_bounds; ++k) { real_row.push_back(row_start[4] + k); real_col.push_back(col_start4 + k); }
+    for (int32_t k = 0; k < nr_range; ++k) { real_row.push_back(row_start[5] + k); real_col.push_back(col_start5 + k); }
+    const int32_t nr_real = (int32_t)real_row.size();
+    nr_artificial = m - nr_real;
+    wrapped_na = 0;
+    if (G > 1 && nr_artificial > 0 && engine != RELP_ENGINE_TABLEAU)
+        return fail(err, RELP_E_UNSUPPORTED, "the sharded revised engine needs a full slack basis (no artificial variables); "
+                                             "the sharded tableau engine runs both phases");
+    column_to_row.assign(nr_artificial, 0);
+    for (int32_t ith = 0, i = 0; ith < nr_artificial; ++ith) {
+        while (i < nr_real && ith + i == real_row[i]) ++i;
+        column_to_row[ith] = ith + i;
+    }
+    basis.assign(m, 0);
+    for (int32_t row = 0, ac = 0; row < m; ++row) {
+        const bool can_a = ac < nr_artificial, can_r = (row - ac) < nr_real;
+        if (can_a && (!can_r || column_to_row[ac] < real_row[row - ac])) basis[row] = ac++;
+        else basis[row] = nr_artificial + real_col[row - ac];
+    }
+    plan_shards(G, g);
+    return RELP_OK;
+}
+
+relp_status_t Layout::build(const relp_matrix_data_t& md, const relp_config_t& cfg, std::string* err) {
+    if (md.nr_normal < 0 || md.nr_eq < 0 || md.nr_range < 0 || md.nr_le < 0 || md.nr_ge < 0)
+        return fail(err, RELP_E_ARG, "negative size");
+    if (cfg.shard_rank < 0 || cfg.shard_rank >= std::max(cfg.shard_count, 1)) return fail(err, RELP_E_ARG, "bad shard rank");
+    const int32_t mc_in = md.nr_eq + md.nr_range + md.nr_le + md.nr_ge;
+    if ((mc_in > 0 && !md.b) || (md.nr_normal > 0 && (!md.cost || !md.upper_bound)) || (md.nr_range > 0 && !md.ranges))
+        return fail(err, RELP_E_ARG, "missing b / cost / upper_bound / ranges");
+    const relp_status_t st = plan(md, cfg, err);
+    if (st) return st;
+
+    cost.assign(md.cost, md.cost + nr_normal);
+    rhs.assign(m, 0.0);
+    for (int32_t i = 0; i < mc; ++i) rhs[i] = md.b[i];
+    for (int32_t j = 0; j < nr_normal; ++j) if (bound_row[j] >= 0) rhs[bound_row[j]] = md.upper_bound[j];
+    for (int32_t k = 0; k < nr_range; ++k) rhs[mc + nr_bounds + k] = md.ranges[k];
+    // Carry::create_for_partially_artificial, carry/mod.rs:381-426
+    minus_pi.assign(m, 0.0);
+    phase1_objective = 0.0;
+    for (int32_t k = 0; k < nr_artificial; ++k) { phase1_objective += rhs[column_to_row[k]]; minus_pi[column_to_row[k]] = -1.0; }
+    return RELP_OK;
+}
+
+int64_t Layout::candidate_len_for(int32_t rows) const {
+    return round_up_even(3 + (int64_t)rows + (engine == RELP_ENGINE_TABLEAU ? (rows + 255) / 256 : 0));
+}
+
+void Layout::plan_shards(int32_t G, int32_t g) {
+    // structural columns and rows of B^-1
+    shard_column_range(nr_normal, g, G, &col_lo, &col_hi);
+    row_stride = (int32_t)round_up_even((m + G - 1) / G);
+    row_lo = std::min(m, g * row_stride);
+    row_hi = std::min(m, row_lo + row_stride);
+    candidate_len = candidate_len_for(m);
+    sc_lo = sc_hi = 0;
+    if (engine == RELP_ENGINE_TABLEAU) {
+        // the tableau shards its STORED columns [artificial | structural | virtual] contiguously; the
+        // structural part of the owned range is what the caller supplies in `dense`
+        const int32_t n_store = nr_columns();
+        const int32_t per = (int32_t)round_up_even((n_store + G - 1) / G);
+        sc_lo = std::min(n_store, g * per);
+        sc_hi = std::min(n_store, sc_lo + per);
+        col_lo = std::min(nr_normal, std::max(0, sc_lo - nr_artificial));
+        col_hi = std::min(nr_normal, std::max(0, sc_hi - nr_artificial));
+        if (col_hi < col_lo) col_hi = col_lo;
+    }
+}
+
+void Layout::remove_rows(const std::vector<int32_t>& map) {
+    auto remap = [&](std::vector<int32_t>& v) { for (auto& x : v) if (x >= 0) x = map[x]; };
+    remap(bound_row); remap(vrow0); remap(vrow1);
+    // a slack whose row disappears keeps its column index and becomes an empty column (vrow0 = -1), as
+    // Column::into_filtered does (matrix_data.rs:592-614)
+    for (auto& x : column_to_row) x = map[x] >= 0 ? map[x] : 0;
+    int32_t kept = 0, kept_constraints = 0;
+    for (int32_t i = 0; i < m; ++i) {
+        if (map[i] < 0) continue;
+        rhs[kept++] = rhs[i];
+        if (i < mc) ++kept_constraints;
+    }
+    rhs.resize(kept);
+    m = kept; mc = kept_constraints;
+    row_lo = 0; row_hi = m;
+    row_stride = (int32_t)round_up_even(m);
+    candidate_len = candidate_len_for(m);
+}
+
+}  // namespace relp

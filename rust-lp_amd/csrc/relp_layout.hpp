@@ -1,0 +1,104 @@
+// relp_layout.hpp -- the standard form of a relp_matrix_data_t, decided once on the host (plain C++17, no HIP).
+//
+// `Layout` is what the reference's `MatrixData` provider and the partially artificial start describe (file:line under the
+// reference's src/algorithm/two_phase/):
+//   rows, columns, right-hand side     matrix_provider/matrix_data.rs:198-268, 359-371, 432-452
+//   artificial columns, initial basis  tableau/kind/artificial/partially.rs:72-80, 125-206
+//   phase-1 -pi and objective          tableau/inverse_maintenance/carry/mod.rs:381-426
+// plus the engine kind (RELP_ENGINE_AUTO resolved) and the split of the columns over shards.  The engine keeps one and
+// uploads its arrays; relp_shard_plan asks the same code which columns a rank must supply.
+#pragma once
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/relp_engine.h"
+
+namespace relp {
+
+// Column indices at or above this value are artificial variables that survived phase 1 (see
+// Engine::switch_to_phase_two): INT32_MAX - (na - 1 - a).  They have no flag, no cost and no column.
+static constexpr int32_t kWrappedArtificialBase = 0x40000000;
+
+// Structural columns [lo, hi) of `rank` when `count` ranks split `n` columns contiguously (relp_shard_column_range)
+void shard_column_range(int32_t n, int32_t rank, int32_t count, int32_t* lo, int32_t* hi);
+
+struct Layout {
+    // rows: == | range | <= | >= (the mc constraints) | bound rows | range-bound rows  (m in all)
+    int32_t nr_normal = 0, nr_eq = 0, nr_range = 0, nr_le = 0, nr_ge = 0;
+    int32_t mc = 0;           // constraint rows of A
+    int32_t nr_bounds = 0;    // variables with an upper bound
+    int32_t m = 0;            // tableau rows
+    // provider columns: structural | range slack | <= slack | >= slack | bound slack | range-bound slack
+    int32_t nr_virtual = 0;
+    int32_t n_provider = 0;   // structural + virtual
+    std::vector<double> cost;                 // per structural column
+    std::vector<double> rhs;                  // (b, upper bounds, ranges), matrix_data.rs:359-371
+    std::vector<int32_t> bound_row;           // per structural column: its bound row, -1 = none
+    std::vector<int32_t> vrow0, vrow1, vsign; // per virtual column: its row (-1: removed), the second row or -1, the sign
+    int32_t engine = RELP_ENGINE_AUTO;        // relp_engine_kind_t, AUTO resolved
+
+    // Kind: the artificial columns are numbered before all provider columns
+    int32_t nr_artificial = 0;                // 0 from phase 2 on
+    int32_t wrapped_na = 0;                   // nr_artificial at the phase switch (decodes wrapped artificial indices)
+    std::vector<int32_t> column_to_row;       // row of artificial column k
+    std::vector<int32_t> basis;               // initial basis (tableau column indices)
+    std::vector<double> minus_pi;             // initial -pi of phase 1
+    double phase1_objective = 0.0;            // initial objective of phase 1 (the sum of the artificial rows' rhs)
+
+    // shards: structural columns [col_lo, col_hi) and rows of B^-1 [row_lo, row_hi) (revised engine); the tableau engine
+    // stores the columns [sc_lo, sc_hi) of [artificial | structural | virtual] and supplies the structural ones among them
+    int32_t col_lo = 0, col_hi = 0, row_lo = 0, row_hi = 0, row_stride = 0;
+    int32_t sc_lo = 0, sc_hi = 0;
+    int64_t candidate_len = 0;                // [key, j, d_j, column (m)] (+ the tableau's block minima of the ratio test)
+
+    // Counts, descriptors, engine kind, artificial columns, initial basis and shards from md's sizes and upper bounds
+    // alone (b, cost and ranges are not read).  A status other than RELP_OK comes with a message in *err.
+    relp_status_t plan(const relp_matrix_data_t& md, const relp_config_t& cfg, std::string* err);
+    // The whole standard form: plan() plus cost, rhs, -pi and the phase-1 objective.
+    relp_status_t build(const relp_matrix_data_t& md, const relp_config_t& cfg, std::string* err);
+    // Rows deleted (map: old row -> new row, -1 = removed; only constraint rows go): every remaining row index shifts
+    // down (Column::into_filtered, matrix_data.rs:592-614), rhs loses the rows, the shards own all rows.
+    void remove_rows(const std::vector<int32_t>& map);
+
+    int32_t nr_columns() const { return nr_artificial + n_provider; }
+
+    // the row of an artificial column: j < nr_artificial, or a wrapped index after the phase switch
+    int32_t artificial_row(int32_t j) const {
+        return column_to_row[j >= kWrappedArtificialBase ? wrapped_na - 1 - (INT32_MAX - j) : j];
+    }
+
+    // The entries (row, value) of tableau column j, in order: an artificial column is e_row; a structural column is what
+    // `structural(p, put)` supplies for it, then its bound row; a virtual column its descriptor rows.  False if j is no column.
+    // It runs for every basis column of every LU refactorisation: forced inline (left to itself the compiler calls it per
+    // column, 20 % slower at 64,000 rows); the unsigned compares also reject j < 0.
+    template <class S, class P>
+    __attribute__((always_inline)) bool for_each_entry(int32_t j, S&& structural, P&& put) const {
+        if ((uint32_t)j < (uint32_t)nr_artificial || j >= kWrappedArtificialBase) {
+            put(artificial_row(j), 1.0);
+            return true;
+        }
+        const int32_t p = j - nr_artificial;
+        if ((uint32_t)p < (uint32_t)nr_normal) {
+            structural(p, put);
+            if (bound_row[p] >= 0) put(bound_row[p], 1.0);
+            return true;
+        }
+        const uint32_t v = (uint32_t)(p - nr_normal);
+        if (v >= (uint32_t)nr_virtual) return false;
+        if (vrow0[v] >= 0) put(vrow0[v], (double)vsign[v]);     // -1: its row was removed
+        if (vrow1[v] >= 0) put(vrow1[v], 1.0);
+        return true;
+    }
+    // the same for provider column p (no artificial columns in front)
+    template <class S, class P>
+    bool for_each_provider_entry(int32_t p, S&& structural, P&& put) const {
+        return p >= 0 && for_each_entry(nr_artificial + p, structural, put);
+    }
+
+  private:
+    void plan_shards(int32_t count, int32_t rank);
+    int64_t candidate_len_for(int32_t rows) const;
+};
+
+}  // namespace relp

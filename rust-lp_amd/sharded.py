@@ -48,7 +48,7 @@ class HipShardOps:
         self.h = tableau.handle
         self.refresh_lengths()
         self.update_block = self.lib.relp_update_block(self.h)
-        self.tableau = int(tableau.config.engine) == _engine.ENGINE_TABLEAU
+        self.tableau = tableau.engine_kind() == _engine.ENGINE_TABLEAU
 
     def refresh_lengths(self):
         lo, hi, rlo, rhi, stride = (C.c_int32() for _ in range(5))

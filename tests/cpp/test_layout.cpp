@@ -1,0 +1,296 @@
+// test_layout.cpp -- the standard form of a relp_matrix_data_t without a GPU (rust-lp_amd/csrc/relp_layout.{hpp,cpp}).
+//
+// Pins:
+//   * the reference's own known answer for problem_1 (matrix_data.rs:680-755: columns, right-hand side, bound rows, sizes)
+//     and its partially artificial start (src/tests/problem_1.rs:376-399: artificials, basis, -pi, -objective);
+//   * the initial basis, rhs, -pi and phase-1 objective against the C oracle (oracle/relp_f64.c) on seeded LPs with every
+//     row kind and some bounded variables, and B = I for that basis through the column walker;
+//   * row removal against a layout built afresh without those rows;
+//   * the shard plans: for 1..4 ranks and every engine kind the structural columns (and the rows / stored columns) tile
+//     their range contiguously, and RELP_ENGINE_AUTO with more than one rank plans the tableau engine.
+#include "relp_layout.hpp"
+
+extern "C" {
+#include "relp_oracle.h"
+}
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstdio>
+#include <limits>
+#include <random>
+#include <string>
+#include <utility>
+#include <vector>
+
+using namespace relp;
+using Entries = std::vector<std::pair<int32_t, double>>;
+
+static int g_failed = 0, g_checks = 0;
+#define CHECK(cond, ...) do { ++g_checks; if (!(cond)) { ++g_failed; std::printf("FAILED %s:%d: ", __FILE__, __LINE__); std::printf(__VA_ARGS__); std::printf("\n"); } } while (0)
+
+static const double kInf = std::numeric_limits<double>::infinity();
+
+// an LP in the C ABI's CSC form, owning its arrays
+struct Lp {
+    int32_t nr_normal = 0, nr_eq = 0, nr_range = 0, nr_le = 0, nr_ge = 0;
+    std::vector<int64_t> col_ptr{0};
+    std::vector<int32_t> row_idx;
+    std::vector<double> values, b, ranges, cost, upper;
+    int32_t mc() const { return nr_eq + nr_range + nr_le + nr_ge; }
+    relp_matrix_data_t md() const {
+        relp_matrix_data_t d{};
+        d.nr_normal = nr_normal; d.nr_eq = nr_eq; d.nr_range = nr_range; d.nr_le = nr_le; d.nr_ge = nr_ge;
+        d.format = RELP_FORMAT_CSC; d.matrix_memory = RELP_MEM_HOST;
+        d.col_ptr = col_ptr.data(); d.row_idx = row_idx.data(); d.values = values.data();
+        d.b = b.data(); d.ranges = ranges.data(); d.cost = cost.data(); d.upper_bound = upper.data();
+        return d;
+    }
+};
+
+static relp_config_t config(int32_t engine, int32_t count = 1, int32_t rank = 0) {
+    relp_config_t c{};
+    c.engine = engine; c.shard_count = count; c.shard_rank = rank;
+    return c;
+}
+
+static Entries column(const Layout& L, const Lp& lp, int32_t j) {
+    Entries out;
+    auto csc = [&](int32_t p, auto&& put) { for (int64_t e = lp.col_ptr[p]; e < lp.col_ptr[p + 1]; ++e) put(lp.row_idx[e], lp.values[e]); };
+    if (!L.for_each_entry(j, csc, [&](int32_t r, double v) { out.emplace_back(r, v); })) out.emplace_back(-99, 0.0);
+    return out;
+}
+
+// src/tests/problem_1.rs:317-374 as MatrixData: one == row, one >= row, the first two variables bounded
+static Lp problem_1() {
+    Lp lp;
+    lp.nr_normal = 3; lp.nr_eq = 1; lp.nr_ge = 1;
+    lp.col_ptr = {0, 1, 2, 4};
+    lp.row_idx = {1, 0, 0, 1};
+    lp.values = {1.0, -1.0, 1.0, 1.0};
+    lp.b = {6.0, 10.0};
+    lp.cost = {1.0, 4.0, 9.0};
+    lp.upper = {4.0, 2.0, kInf};
+    return lp;
+}
+
+static void test_problem_1() {
+    const Lp lp = problem_1();
+    Layout L;
+    std::string err;
+    CHECK(L.build(lp.md(), config(RELP_ENGINE_REVISED), &err) == RELP_OK, "build: %s", err.c_str());
+    // matrix_data.rs:680-755 (provider columns: no artificial columns in front)
+    auto prov = [&](int32_t p) { return column(L, lp, L.nr_artificial + p); };
+    CHECK(L.nr_normal == 3, "nr_normal %d", L.nr_normal);
+    CHECK(prov(0) == (Entries{{1, 1.0}, {2, 1.0}}), "column 0");
+    CHECK(prov(1) == (Entries{{0, -1.0}, {3, 1.0}}), "column 1");
+    CHECK(prov(2) == (Entries{{0, 1.0}, {1, 1.0}}), "column 2");
+    CHECK(prov(3) == (Entries{{1, -1.0}}), "column 3");
+    CHECK(prov(4) == (Entries{{2, 1.0}}), "column 4");
+    CHECK(prov(5) == (Entries{{3, 1.0}}), "column 5");
+    CHECK(L.rhs == (std::vector<double>{6, 10, 4, 2}), "right-hand side");
+    CHECK(L.bound_row == (std::vector<int32_t>{2, 3, -1}), "bound rows");
+    CHECK(L.mc == 2 && L.nr_bounds == 2 && L.m == 4 && L.n_provider == 6, "mc %d bounds %d m %d n %d", L.mc, L.nr_bounds, L.m, L.n_provider);
+    // src/tests/problem_1.rs:376-399: artificials for rows 0 and 1, basis [0, 1, 2 + 4, 2 + 5], -pi (-1, -1, 0, 0), -obj -16
+    CHECK(L.nr_artificial == 2 && L.column_to_row == (std::vector<int32_t>{0, 1}), "artificial columns");
+    CHECK(L.basis == (std::vector<int32_t>{0, 1, 6, 7}), "initial basis");
+    CHECK(L.minus_pi == (std::vector<double>{-1, -1, 0, 0}), "-pi");
+    CHECK(L.phase1_objective == 16.0, "phase-1 objective %g", L.phase1_objective);
+    CHECK(column(L, lp, 0) == (Entries{{0, 1.0}}) && column(L, lp, 1) == (Entries{{1, 1.0}}), "artificial columns are unit columns");
+    CHECK(column(L, lp, L.nr_columns()) == (Entries{{-99, 0.0}}), "no column beyond the last");
+    // after the phase switch (Engine::switch_to_phase_two) an artificial that stayed basic has a wrapped index
+    L.wrapped_na = L.nr_artificial; L.nr_artificial = 0;
+    CHECK(L.artificial_row(INT32_MAX - (2 - 1 - 1)) == 1 && L.artificial_row(INT32_MAX - (2 - 1 - 0)) == 0, "wrapped decode");
+    CHECK(column(L, lp, INT32_MAX) == (Entries{{1, 1.0}}) && column(L, lp, 0) == (Entries{{1, 1.0}, {2, 1.0}}), "phase-2 columns");
+}
+
+// seeded LP with every row kind; columns sorted by row, some variables bounded
+static Lp random_lp(uint64_t seed, int32_t n, int32_t neq, int32_t nrange, int32_t nle, int32_t nge) {
+    std::mt19937_64 rng(seed);
+    std::uniform_real_distribution<double> u(0.0, 1.0);
+    Lp lp;
+    lp.nr_normal = n; lp.nr_eq = neq; lp.nr_range = nrange; lp.nr_le = nle; lp.nr_ge = nge;
+    const int32_t mc = lp.mc();
+    for (int32_t j = 0; j < n; ++j) {
+        for (int32_t i = 0; i < mc; ++i)
+            if (u(rng) < 0.4) { lp.row_idx.push_back(i); lp.values.push_back(std::round(u(rng) * 18.0 - 9.0) + 0.5); }
+        lp.col_ptr.push_back((int64_t)lp.row_idx.size());
+        lp.cost.push_back(std::round(u(rng) * 10.0 - 3.0));
+        lp.upper.push_back(u(rng) < 0.35 ? 1.0 + std::round(u(rng) * 8.0) : kInf);
+    }
+    for (int32_t i = 0; i < mc; ++i) lp.b.push_back(std::round(u(rng) * 20.0));
+    for (int32_t k = 0; k < nrange; ++k) lp.ranges.push_back(1.0 + std::round(u(rng) * 5.0));
+    return lp;
+}
+
+static void test_against_oracle() {
+    for (uint64_t seed = 1; seed <= 40; ++seed) {
+        std::mt19937_64 rng(seed * 7919);
+        auto pick = [&](int lo, int hi) { return lo + (int)(rng() % (uint64_t)(hi - lo + 1)); };
+        const Lp lp = random_lp(seed, pick(1, 12), pick(0, 4), pick(0, 3), pick(0, 4), pick(0, 4));
+        Layout L;
+        std::string err;
+        const relp_status_t st = L.build(lp.md(), config(RELP_ENGINE_REVISED), &err);
+        if (lp.mc() == 0 && L.nr_bounds == 0) { CHECK(st == RELP_E_ARG && err == "empty problem", "seed %llu: %s", (unsigned long long)seed, err.c_str()); continue; }
+        CHECK(st == RELP_OK, "seed %llu: %s", (unsigned long long)seed, err.c_str());
+        if (st) continue;
+        oracle_matrix_data_t omd{};
+        omd.nr_normal = lp.nr_normal; omd.nr_eq = lp.nr_eq; omd.nr_range = lp.nr_range; omd.nr_le = lp.nr_le; omd.nr_ge = lp.nr_ge;
+        omd.col_ptr = lp.col_ptr.data(); omd.row_idx = lp.row_idx.data(); omd.values = lp.values.data();
+        omd.b = lp.b.data(); omd.ranges = lp.ranges.data(); omd.cost = lp.cost.data(); omd.upper_bound = lp.upper.data();
+        oracle_config_t ocfg{};
+        oracle_engine_t* o = oracle_create(&omd, &ocfg);
+        const int32_t m = oracle_m(o);
+        CHECK(m == L.m && oracle_n(o) == L.nr_columns() && oracle_nr_artificial(o) == L.nr_artificial,
+              "seed %llu: sizes m %d/%d n %d/%d", (unsigned long long)seed, m, L.m, oracle_n(o), L.nr_columns());
+        if (m == L.m) {
+            std::vector<int32_t> basis(m);
+            std::vector<double> b(m), mpi(m);
+            oracle_get_basis(o, basis.data());
+            oracle_get_b(o, b.data());
+            oracle_get_minus_pi(o, mpi.data());
+            CHECK(basis == L.basis, "seed %llu: initial basis", (unsigned long long)seed);
+            CHECK(b == L.rhs, "seed %llu: rhs", (unsigned long long)seed);
+            CHECK(mpi == L.minus_pi, "seed %llu: -pi", (unsigned long long)seed);
+            CHECK(oracle_objective(o) == L.phase1_objective, "seed %llu: objective %g / %g", (unsigned long long)seed,
+                  oracle_objective(o), L.phase1_objective);
+            // the initial basis is the identity: column basis[r] is e_r
+            for (int32_t r = 0; r < m; ++r)
+                CHECK(column(L, lp, L.basis[r]) == (Entries{{r, 1.0}}), "seed %llu: basis column of row %d", (unsigned long long)seed, r);
+        }
+        oracle_destroy(o);
+    }
+}
+
+// lp without the constraint rows in `drop` (ascending)
+static Lp without_rows(const Lp& lp, const std::vector<int32_t>& drop) {
+    const int32_t mc = lp.mc();
+    std::vector<int32_t> map(mc);
+    for (int32_t i = 0, f = 0, out = 0; i < mc; ++i) map[i] = (f < (int32_t)drop.size() && drop[f] == i) ? (++f, -1) : out++;
+    const int32_t starts[4] = {0, lp.nr_eq, lp.nr_eq + lp.nr_range, lp.nr_eq + lp.nr_range + lp.nr_le};
+    Lp r = lp;
+    int32_t* counts[4] = {&r.nr_eq, &r.nr_range, &r.nr_le, &r.nr_ge};
+    for (int32_t i : drop) { int k = 3; while (i < starts[k]) --k; --*counts[k]; }
+    r.col_ptr = {0}; r.row_idx.clear(); r.values.clear(); r.b.clear(); r.ranges.clear();
+    for (int32_t j = 0; j < lp.nr_normal; ++j) {
+        for (int64_t e = lp.col_ptr[j]; e < lp.col_ptr[j + 1]; ++e)
+            if (map[lp.row_idx[e]] >= 0) { r.row_idx.push_back(map[lp.row_idx[e]]); r.values.push_back(lp.values[e]); }
+        r.col_ptr.push_back((int64_t)r.row_idx.size());
+    }
+    for (int32_t i = 0; i < mc; ++i) if (map[i] >= 0) r.b.push_back(lp.b[i]);
+    for (int32_t k = 0; k < lp.nr_range; ++k) if (map[lp.nr_eq + k] >= 0) r.ranges.push_back(lp.ranges[k]);
+    return r;
+}
+
+static void test_remove_rows() {
+    for (uint64_t seed = 100; seed < 130; ++seed) {
+        const Lp lp = random_lp(seed, 9, 4, 0, 3, 2);
+        std::vector<int32_t> drop;
+        for (int32_t i = 0; i < lp.nr_eq; ++i) if ((seed >> i) & 1) drop.push_back(i);
+        Layout L, F;
+        std::string err;
+        CHECK(L.build(lp.md(), config(RELP_ENGINE_TABLEAU), &err) == RELP_OK, "build: %s", err.c_str());
+        const Lp lp_f = without_rows(lp, drop);
+        CHECK(F.build(lp_f.md(), config(RELP_ENGINE_TABLEAU), &err) == RELP_OK, "build: %s", err.c_str());
+        std::vector<int32_t> map(L.m);
+        for (int32_t i = 0, f = 0, out = 0; i < L.m; ++i) map[i] = (f < (int32_t)drop.size() && drop[f] == i) ? (++f, -1) : out++;
+        L.remove_rows(map);
+        // (== rows have no slack: the provider columns are the same columns)
+        CHECK(L.m == F.m && L.mc == F.mc && L.n_provider == F.n_provider, "seed %llu: sizes", (unsigned long long)seed);
+        CHECK(L.rhs == F.rhs && L.bound_row == F.bound_row, "seed %llu: rhs / bound rows", (unsigned long long)seed);
+        CHECK(L.vrow0 == F.vrow0 && L.vrow1 == F.vrow1 && L.vsign == F.vsign, "seed %llu: virtual columns", (unsigned long long)seed);
+        CHECK(L.row_lo == 0 && L.row_hi == F.m && L.row_stride == F.row_stride && L.candidate_len == F.candidate_len,
+              "seed %llu: shard fields", (unsigned long long)seed);
+        for (int32_t p = 0; p < L.n_provider; ++p)
+            CHECK(column(L, lp_f, L.nr_artificial + p) == column(F, lp_f, F.nr_artificial + p), "seed %llu: column %d", (unsigned long long)seed, p);
+        // the artificial columns of the rows that stay keep their (shifted) rows
+        for (int32_t a = 0, fa = 0; a < L.nr_artificial; ++a) {
+            if (std::find(drop.begin(), drop.end(), a) != drop.end()) continue;      // (artificial a < nr_eq started in == row a)
+            CHECK(fa < F.nr_artificial && L.column_to_row[a] == F.column_to_row[fa], "seed %llu: artificial %d", (unsigned long long)seed, a);
+            ++fa;
+        }
+    }
+    // a >= row that goes: its slack keeps its column index and becomes empty (Column::into_filtered)
+    const Lp lp = random_lp(7, 5, 1, 1, 1, 2);
+    Layout L;
+    std::string err;
+    CHECK(L.build(lp.md(), config(RELP_ENGINE_TABLEAU), &err) == RELP_OK, "build: %s", err.c_str());
+    std::vector<int32_t> map(L.m);
+    const int32_t gone = lp.nr_eq + lp.nr_range + lp.nr_le;            // the first >= row
+    for (int32_t i = 0, out = 0; i < L.m; ++i) map[i] = i == gone ? -1 : out++;
+    const int32_t slack = L.nr_normal + lp.nr_range + lp.nr_le;         // its slack column
+    L.remove_rows(map);
+    CHECK(column(L, lp, L.nr_artificial + slack).empty(), "the slack of a removed row is an empty column");
+    CHECK(column(L, lp, L.nr_artificial + slack + 1) == (Entries{{gone, -1.0}}), "the next >= slack moves up a row");
+}
+
+static void test_shard_plans() {
+    const Lp slack_basis = random_lp(11, 23, 0, 0, 9, 0);                 // only <= rows: no artificial columns
+    const Lp general = random_lp(12, 23, 3, 2, 4, 3);
+    const int32_t kinds[4] = {RELP_ENGINE_REVISED, RELP_ENGINE_TABLEAU, RELP_ENGINE_LU, RELP_ENGINE_AUTO};
+    for (const Lp* lp : {&slack_basis, &general}) {
+        for (int32_t G = 1; G <= 4; ++G) {
+            for (int32_t kind : kinds) {
+                int32_t next_col = 0, next_row = 0, next_store = 0;
+                for (int32_t g = 0; g < G; ++g) {
+                    Layout L;
+                    std::string err;
+                    const relp_status_t st = L.plan(lp->md(), config(kind, G, g), &err);
+                    if ((kind == RELP_ENGINE_REVISED || kind == RELP_ENGINE_LU) && G > 1 && lp == &general) {
+                        CHECK(st == RELP_E_UNSUPPORTED, "a sharded engine other than the tableau needs a slack basis");
+                        break;
+                    }
+                    CHECK(st == RELP_OK, "G %d kind %d rank %d: %s", G, kind, g, err.c_str());
+                    const int32_t resolved = L.engine;
+                    CHECK(kind != RELP_ENGINE_AUTO || resolved == RELP_ENGINE_TABLEAU, "AUTO on a small LP is the tableau engine");
+                    CHECK(L.col_lo == next_col && L.col_hi >= L.col_lo, "G %d kind %d rank %d: columns [%d, %d) after %d", G, kind, g,
+                          L.col_lo, L.col_hi, next_col);
+                    next_col = L.col_hi;
+                    if (resolved == RELP_ENGINE_TABLEAU) {
+                        CHECK(L.sc_lo == next_store && L.sc_hi >= L.sc_lo, "stored columns");
+                        next_store = L.sc_hi;
+                    } else {
+                        CHECK(L.row_lo == next_row && L.row_hi >= L.row_lo && L.row_hi - L.row_lo <= L.row_stride, "rows of B^-1");
+                        next_row = L.row_hi;
+                    }
+                    if (kind == RELP_ENGINE_AUTO) {
+                        Layout T;
+                        CHECK(T.plan(lp->md(), config(RELP_ENGINE_TABLEAU, G, g), &err) == RELP_OK, "tableau plan");
+                        CHECK(T.col_lo == L.col_lo && T.col_hi == L.col_hi && T.sc_lo == L.sc_lo && T.sc_hi == L.sc_hi &&
+                              T.candidate_len == L.candidate_len, "AUTO plans the tableau engine (G %d rank %d)", G, g);
+                    }
+                    if (g == G - 1) {
+                        CHECK(next_col == L.nr_normal, "G %d kind %d: the columns end at %d of %d", G, kind, next_col, L.nr_normal);
+                        if (resolved == RELP_ENGINE_TABLEAU) CHECK(next_store == L.nr_columns(), "the stored columns are covered");
+                        else CHECK(next_row == L.m, "the rows are covered");
+                    }
+                }
+            }
+        }
+    }
+    // an upper bound beyond 1e300 is a bound (std::isfinite), in the plan as in the engine
+    Lp big = random_lp(13, 6, 2, 0, 0, 1);
+    big.upper[2] = 1e301;
+    Layout L;
+    std::string err;
+    CHECK(L.plan(big.md(), config(RELP_ENGINE_TABLEAU), &err) == RELP_OK && L.bound_row[2] >= 0, "1e301 is a bound");
+    // the argument checks of relp_create
+    relp_matrix_data_t md = big.md();
+    md.nr_ge = -1;
+    CHECK(L.build(md, config(RELP_ENGINE_TABLEAU), &err) == RELP_E_ARG && err == "negative size", "negative size");
+    CHECK(L.build(big.md(), config(RELP_ENGINE_TABLEAU, 2, 2), &err) == RELP_E_ARG && err == "bad shard rank", "bad shard rank");
+    md = big.md();
+    md.b = nullptr;
+    CHECK(L.build(md, config(RELP_ENGINE_TABLEAU), &err) == RELP_E_ARG && err == "missing b / cost / upper_bound / ranges", "missing b");
+    CHECK(L.plan(md, config(RELP_ENGINE_TABLEAU), &err) == RELP_OK, "the plan reads no b");
+}
+
+int main() {
+    test_problem_1();
+    test_against_oracle();
+    test_remove_rows();
+    test_shard_plans();
+    std::printf("test_layout: %d checks, %d failed\n", g_checks, g_failed);
+    return g_failed ? 1 : 0;
+}

@@ -44,6 +44,16 @@ def test_device_lu_factorisation_as_a_host_model():
     assert " 0 failed" in res.stdout
 
 
+def test_standard_form_layout():
+    """tests/cpp/test_layout.cpp (no GPU): the standard form the engine builds (rust-lp_amd/csrc/relp_layout.cpp) -- the
+    reference's known answer for problem_1 (matrix_data.rs:680-755), the initial basis, rhs, -pi and phase-1 objective
+    against the C oracle, row removal against a fresh layout, and the shard plans of every engine kind."""
+    subprocess.check_call(["make", "-C", CPP, "test_layout"], stdout=subprocess.DEVNULL)
+    res = subprocess.run([os.path.join(CPP, "test_layout")], capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-1000:]
+    assert " 0 failed" in res.stdout
+
+
 @pytest.mark.gpu
 def test_cpp_host_tests_pass_on_the_gpu():
     if not os.access(BINARY, os.X_OK):

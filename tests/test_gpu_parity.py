@@ -1016,6 +1016,61 @@ def test_c4_full_size_column_sharded_over_eight_ranks_on_one_gpu():
     assert first[2].min() >= -1e-8
 
 
+@pytest.mark.parametrize("seed", [9000, 9002, 9009])
+def test_robust_config_on_two_sharded_ranks_reaches_the_unsharded_optimum(seed):
+    """relp_robust_config (RELP_ENGINE_AUTO) with two ranks: relp_shard_plan hands every rank the structural columns the
+    engine relp_create resolves to (the sharded tableau) stores, the Python driver sees the tableau protocol, and the native
+    loop on two thread ranks ends in the optimum of the unsharded robust solve (every row kind, bounded variables; seed 9009
+    removes a redundant row at the phase switch)."""
+    import ctypes as C
+    import torch
+    from rust_lp_amd.sharded import HipShardOps
+    from shard_threads import ThreadRank, ThreadWorld, run_ranks
+    lib = engine.load_library()
+    dev = torch.device("cuda", 0)
+    torch.zeros(1, device=dev)
+    torch.cuda.synchronize()
+    m, n, world = 40, 60, 2
+    d = synthetic.mixed_lp(m, n, seed, nnz_per_col=4, frac_negative_cost=0.1, infeasible=False)
+    full = MatrixData.from_sparse_dict(d)
+    single = engine.Tableau(full, config=engine.robust_config())
+    assert single.solve_relaxation() == engine.OPTIMAL
+    optimum = single.objective_function_value()
+    single.close()
+    dense = np.zeros((m, n))
+    for j in range(n):
+        for e in range(d["col_ptr"][j], d["col_ptr"][j + 1]):
+            dense[d["row_idx"][e], j] = d["values"][e]
+    shared = ThreadWorld(world)
+    tabs, ranks = [], []
+    for r in range(world):
+        cfg = engine.robust_config(shard_rank=r, shard_count=world)
+        md = MatrixData(nr_normal=n, nr_eq=d["nr_eq"], nr_range=d["nr_range"], nr_le=d["nr_le"], nr_ge=d["nr_ge"], b=d["b"],
+                        cost=d["c"], upper_bound=d["ub"], ranges=d["ranges"])
+        lo, hi = engine.shard_plan(md, cfg)
+        assert (lo, hi) == engine.shard_plan(md, engine.robust_config(shard_rank=r, shard_count=world, engine=engine.ENGINE_TABLEAU))
+        md.dense = np.asfortranarray(dense[:, lo:hi]) if hi > lo else np.zeros((m, 1), order="F")
+        t = engine.Tableau(md, config=cfg)
+        assert t.engine_kind() == engine.ENGINE_TABLEAU and HipShardOps(t).tableau
+        tabs.append(t)
+        ranks.append(ThreadRank(shared, r, lib, t.handle, torch, dev))
+
+    def body(r):
+        t = tabs[r]
+        done, oc = C.c_int64(), C.c_int32()
+        assert lib.relp_shard_run(t.handle, 1 << 20, C.byref(done), C.byref(oc)) == 0, lib.relp_last_error(t.handle).decode()
+        if oc.value == engine.PHASE_ONE_DONE:
+            assert lib.relp_shard_run(t.handle, 1 << 20, C.byref(done), C.byref(oc)) == 0, lib.relp_last_error(t.handle).decode()
+        return oc.value, t.objective_function_value()
+    out = run_ranks(world, body)
+    assert not shared.errors, shared.errors
+    for t in tabs:
+        t.close()
+    for oc, obj in out:
+        assert oc == engine.OPTIMAL
+        assert abs(obj - optimum) <= OBJ_RTOL * max(1.0, abs(optimum)), (obj, optimum)
+
+
 def _c4_sharded_run(lib, make_md, pivots, world=8):
     import ctypes as C
     import torch

@@ -73,3 +73,21 @@ def test_shard_column_range_partition():
         assert spans[0][0] == 0 and spans[-1][1] == n
         for a, b in zip(spans, spans[1:]):
             assert a[1] == b[0]
+
+
+def test_shard_plan_under_auto_is_the_tableau_plan():
+    """relp_shard_plan resolves RELP_ENGINE_AUTO as relp_create does: with more than one rank the tableau engine, whose ranks
+    supply the structural part of their stored columns (not the revised engine's even split of the structural columns)."""
+    import rust_lp_amd  # noqa: F401
+    from rust_lp_amd import MatrixData, engine
+    m, n = 30, 50
+    md = MatrixData(nr_normal=n, nr_eq=4, nr_range=0, nr_le=m - 10, nr_ge=6, b=np.ones(m), cost=np.ones(n),
+                    upper_bound=np.where(np.arange(n) % 3 == 0, 5.0, np.inf))
+    for world in (2, 3):
+        plans = []
+        for r in range(world):
+            plan = engine.shard_plan(md, engine.robust_config(shard_rank=r, shard_count=world))
+            assert plan == engine.shard_plan(md, engine.robust_config(shard_rank=r, shard_count=world, engine=engine.ENGINE_TABLEAU))
+            plans.append(plan)
+        assert plans[0][0] == 0 and plans[-1][1] == n and all(a[1] == b[0] for a, b in zip(plans, plans[1:]))
+        assert plans != [engine.shard_column_range(n, r, world) for r in range(world)]
