@@ -232,6 +232,10 @@ int64_t       relp_reinversions(const relp_engine_t *h);
 /* Fold every pending deferred update into the stored representation: B0^-1 += W (S' B0^-1) (revised), T0 += W R0
  * (tableau), refactorisation (LU).  No-op when update_block = 0. */
 relp_status_t relp_flush(relp_engine_t *h);
+/* Tableau engine: out2 = { flushes that folded pending pivots, columns they rewrote } since create.  A flush rewrites the
+ * owned columns with a nonzero entry among the pending rows R0 (the others have T0 + W R0 = T0), or every owned column
+ * when RELP_TAB_FLUSH_ALL=1 was set at create.  Other engines: { 0, 0 }. */
+relp_status_t relp_tab_flush_stats(relp_engine_t *h, int64_t *out2);
 /* The block size K in effect (0 = explicit rank-1 updates; LU engine: pivots between refactorisations). */
 int32_t       relp_update_block(const relp_engine_t *h);
 /* RELP_ENGINE_LU only: statistics of the current factorisation, out[8] = { refactorisations so far, m,

@@ -26,6 +26,7 @@ void Engine::free_all() {
     fr(d_basis_); fr(d_column_to_row_); fr(d_bound_row_); fr(d_vrow0_); fr(d_vrow1_); fr(d_vsign_); fr(d_trace_);
     fr(d_in_basis_); fr(d_rec_);
     fr(d_part_k1_); fr(d_part_j_);
+    fr(d_fcols_); fr(d_fcount_); fr(d_fmask_); fr(d_fstats_); fr(d_R0c_);
     fr(dT0_); fr(dR0_); fr(d_b_alt_); fr(d_basis_alt_); fr(d_shadow_); fr(d_shadow_meta_);
     if (h_lu_buf_) { (void)hipHostFree(h_lu_buf_); h_lu_buf_ = nullptr; h_lu_cap_ = 0; }
     if (h_basis_) { (void)hipHostFree(h_basis_); h_basis_ = nullptr; }
@@ -71,6 +72,12 @@ TableauView Engine::tview() const {
     tv.n = nr_columns();
     tv.c_lo = lay_.sc_lo; tv.c_hi = lay_.sc_hi;
     return tv;
+}
+
+FlushList Engine::flush_list() const {
+    FlushList fl;
+    fl.cols = d_fcols_; fl.count = d_fcount_; fl.mask = d_fmask_; fl.R0c = d_R0c_; fl.ld = ld_r_; fl.stats = d_fstats_;
+    return fl;
 }
 
 SelectPartials Engine::tab_partials(int rule) const {
@@ -239,6 +246,17 @@ relp_status_t Engine::create(const relp_matrix_data_t& md, const relp_config_t& 
         ld_r_ = round_up(n_owned, 2);
         HIP_TRY(dev_alloc(&dT0_, ld_t_ * n_owned));
         HIP_TRY(dev_alloc(&dR0_, ld_r_ * (block_ + 1)));        // + one scratch row (d_aq_big)
+        {   // the flush rewrites only the columns with a nonzero R0 entry unless RELP_TAB_FLUSH_ALL=1
+            const char* e = std::getenv("RELP_TAB_FLUSH_ALL");
+            flush_all_ = e && std::atoi(e) != 0;
+            HIP_TRY(dev_alloc(&d_fstats_, 2));
+            if (!flush_all_) {
+                HIP_TRY(dev_alloc(&d_fcols_, n_owned));
+                HIP_TRY(dev_alloc(&d_fcount_, 1));
+                HIP_TRY(dev_alloc(&d_fmask_, (n_owned + 63) / 64));
+                HIP_TRY(dev_alloc(&d_R0c_, ld_r_ * block_));
+            }
+        }
         {   // two launches per pivot instead of three in the single-GPU loop (RELP_FUSED_UPDATE=0: k_ratio_blocks + k_tab_update_all)
             const char* e = std::getenv("RELP_FUSED_UPDATE");
             fused_update_ = !(e && std::atoi(e) == 0);      // (also the native sharded loop, relp_shard_run)
@@ -525,7 +543,7 @@ void Engine::enqueue_flush() {
         // T0 += W R0 on the f64 matrix cores
         const DeferredUpdate dut = deferred();
         prof_begin(RELP_K_FLUSH);
-        launch_tab_flush(tview(), dut, d_rec_, stream_);
+        launch_tab_flush(tview(), dut, d_rec_, flush_list(), stream_);
         launch_flush_reset(dut, d_rec_, stream_);
         prof_end();
         since_flush_ = 0;
@@ -1568,6 +1586,16 @@ relp_status_t Engine::get_degenerate_pivots(int64_t* out) {
     relp_status_t st = download_rec();
     if (st) return st;
     *out = h_rec_->degenerate;
+    return RELP_OK;
+}
+
+relp_status_t Engine::tab_flush_stats(int64_t* out2) {
+    unsigned long long h[2] = {0, 0};
+    if (d_fstats_) {
+        HIP_TRY(hipMemcpyAsync(h, d_fstats_, sizeof h, hipMemcpyDeviceToHost, stream_));
+        HIP_TRY(hipStreamSynchronize(stream_));
+    }
+    out2[0] = (int64_t)h[0]; out2[1] = (int64_t)h[1];
     return RELP_OK;
 }
 

@@ -96,6 +96,7 @@ class Engine {
     relp_status_t current_bfs(int32_t* cols, double* vals, int32_t cap, int32_t* count);
     relp_status_t get_iterations(int64_t* out);
     relp_status_t get_degenerate_pivots(int64_t* out);
+    relp_status_t tab_flush_stats(int64_t* out2);
     relp_status_t get_trace(int32_t* phase, int32_t* entering, int32_t* row, int32_t* leaving, int64_t cap,
                             int64_t* count);
     relp_status_t check_basis(double* max_identity_error, double* max_basic_cost, double* min_b);
@@ -151,6 +152,12 @@ class Engine {
     bool tableau_ = false;
     double* dT0_ = nullptr; int64_t ld_t_ = 0;
     double* dR0_ = nullptr; int64_t ld_r_ = 0;
+    // flush over the columns with a nonzero R0 entry (relp_kernels.h: FlushList); RELP_TAB_FLUSH_ALL=1: every owned column
+    bool flush_all_ = false;
+    int32_t *d_fcols_ = nullptr, *d_fcount_ = nullptr;
+    unsigned long long *d_fmask_ = nullptr, *d_fstats_ = nullptr;   // d_fstats_: {flushes, columns flushed} since create
+    double* d_R0c_ = nullptr;
+    FlushList flush_list() const;
     double* d_cost_store_ = nullptr;     // cost per stored column in the current phase
     int32_t* d_idcol_ = nullptr;         // stored column that was e_k originally, per row k
     // Ratio test + update in one launch (single-GPU loop, relp_kernels.h: launch_tab_ratio_update_all): the second copies of b

@@ -431,8 +431,20 @@ void launch_select_candidate_ratio(const double* msgs, int32_t count, int64_t ms
 void launch_tab_update_all(const TableauView& tv, const DeferredUpdate& du, SelectPartials sp, int32_t m,
                            const double* alpha, double* b, int32_t* basis_indices, uint8_t* in_basis, int32_t* trace,
                            int64_t trace_cap, PivotRecord* rec, hipStream_t s);
+// Columns of a flush.  Column c of T0 + W R0 differs from T0 only if R0[j][c] != 0 for a pending row j < p (a NaN counts
+// as nonzero): for every other column the flush adds sum 0 * w.  With `cols` set the flush first lists those columns and
+// copies their R0 columns, then rewrites only them; `cols` = nullptr: every owned column (RELP_TAB_FLUSH_ALL=1).
+struct FlushList {
+    int32_t*            cols;    // storage columns to flush, ascending (n_owned)
+    int32_t*            count;   // how many (one device int)
+    unsigned long long* mask;    // per 64 owned columns from c_lo: which of them have a nonzero R0 entry
+    double*             R0c;     // R0[:, cols]: kmax rows, position x at R0c[j * ld + x]
+    int64_t             ld;      // even, >= n_owned
+    unsigned long long* stats;   // {flushes with p > 0, columns rewritten} since create
+};
 // flush: T0 += W R0 with v_mfma_f64_16x16x4_f64 tiles
-void launch_tab_flush(const TableauView& tv, const DeferredUpdate& du, const PivotRecord* rec, hipStream_t s);
+void launch_tab_flush(const TableauView& tv, const DeferredUpdate& du, const PivotRecord* rec, const FlushList& fl,
+                      hipStream_t s);
 // Ratio test + update in ONE launch (single-GPU loop): every workgroup repeats the ratio test from the block minima the column
 // kernel left (same code, same answer), then does its share of the update.  What one workgroup rewrites while another may
 // still read it is double-buffered: b and the basis array (in -> out, the caller swaps them), row r of W (its new values go

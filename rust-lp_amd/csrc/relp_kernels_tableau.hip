@@ -685,10 +685,12 @@ __global__ void k_tab_update_vectors(int m, const double* __restrict__ alpha, do
 // Wavefront tile 64 columns x 64 rows (4 x 4 MFMA tiles, 8 operand loads per 16 MFMAs), workgroup
 // 128 x 128.
 template <int MT, int NT>
-__global__ __launch_bounds__(kThreads) void k_tab_flush(TableauView tv, DeferredUpdate du, const int32_t* p_dev) {
+__global__ __launch_bounds__(kThreads) void k_tab_flush(TableauView tv, DeferredUpdate du, const int32_t* p_dev,
+                                                        unsigned long long* stats) {
     constexpr int kFlushMT = MT, kFlushNT = NT;
     const int p = *p_dev;
     if (p == 0) return;
+    if (stats && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) { stats[0] += 1; stats[1] += tv.c_hi - tv.c_lo; }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c_wave = tv.c_lo + blockIdx.x * (2 * 16 * MT) + (wave & 1) * (16 * MT);   // first T0 column of this wavefront
     const int i_wave = blockIdx.y * (2 * 16 * NT) + (wave >> 1) * (16 * NT);            // first T0 row
@@ -754,32 +756,48 @@ __global__ __launch_bounds__(kThreads) void k_tab_flush(TableauView tv, Deferred
 // loads issued one chunk ahead) and every wavefront takes its MFMA fragments from there.  Without this
 // each wavefront fetches its own operands from L2 / Infinity Cache: 48 KB per 32 KB of T0 traffic
 // (4.7 GB per flush at 10k x 20k against 3.2 GB of HBM traffic); with a 256 x 128 tile it is 12 KB.
-template <int WC, int WR, int KC>
-__global__ __launch_bounds__(WC * WR * 64) void k_tab_flush_lds(TableauView tv, DeferredUpdate du, const int32_t* p_dev) {
+// Column tiles walk positions x: the owned column c_lo + x (kList = false), or the x-th column of the
+// FlushList with its compacted R0 (kList = true; the grid covers every owned column and the tiles past
+// the list's count return at once).  Each column gets the same k order, so the same bits, either way.
+template <int WC, int WR, int KC, bool kList>
+__global__ __launch_bounds__(WC * WR * 64) void k_tab_flush_lds(TableauView tv, DeferredUpdate du, const int32_t* p_dev,
+                                                                FlushList fl) {
     constexpr int MT = 4, NT = 2;                     // wavefront tile: 64 columns x 32 rows
     constexpr int TC = WC * 16 * MT, TR = WR * 16 * NT, NTHR = WC * WR * 64;
     constexpr int RA = KC * TC / 2 / NTHR, RB = KC * TR / 2 / NTHR;
     static_assert(RA * NTHR * 2 == KC * TC && RB * NTHR * 2 == KC * TR, "staging must divide evenly");
     const int p = *p_dev;
+    const int n_cols = kList ? *fl.count : tv.c_hi - tv.c_lo;
     if (p == 0) return;
+    if (kList && (int)blockIdx.y * TC >= n_cols) return;
+    if (!kList && fl.stats && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) { fl.stats[0] += 1; fl.stats[1] += n_cols; }
     __shared__ __align__(16) double As[2][KC][TC];
     __shared__ __align__(16) double Bs[2][KC][TR];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wc = wave % WC, wr = wave / WC;
     // consecutive workgroups walk down the rows of the same 256 columns: T0 is column-major, so the
     // workgroups in flight stream whole columns (sequential DRAM pages) and share one R0 chunk in L2
-    const int c_blk = tv.c_lo + blockIdx.y * TC, i_blk = blockIdx.x * TR;
-    const int c_wave = c_blk + wc * 16 * MT, i_wave = i_blk + wr * 16 * NT;
-    const bool active = c_wave < tv.c_hi && i_wave < tv.m;
+    const int x_blk = blockIdx.y * TC, i_blk = blockIdx.x * TR;
+    const int x_wave = x_blk + wc * 16 * MT, i_wave = i_blk + wr * 16 * NT;
+    const bool active = x_wave < n_cols && i_wave < tv.m;
     const int lm = lane & 15, lk = lane >> 4;
-    const int c_end = tv.c_lo + (int)tv.ld_r;         // R0 rows are readable up to their (even) pitch
+    // A operand rows: position x at a_src[k * a_ld + x], readable up to the (even) pitch
+    const double* a_src = kList ? fl.R0c : tv.R0 + tv.c_lo;
+    const int64_t a_ld = kList ? fl.ld : tv.ld_r;
+    // kList: lane l holds the storage column at position x_wave + l; accumulator (a, g) belongs to lane a * 16 + lk + 4 g
+    const int col_lane = kList && active && x_wave + lane < n_cols ? fl.cols[x_wave + lane] : -1;
+    auto column = [&](int a, int g) -> int {           // storage column of accumulator (a, g), -1 past the end
+        const int x = a * 16 + lk + 4 * g;
+        if (kList) return __shfl(col_lane, x, 64);
+        return x_wave + x < n_cols ? tv.c_lo + x_wave + x : -1;
+    };
     double2 ra[RA], rb[RB];
     auto gload = [&](int kc) {
 #pragma unroll
         for (int u = 0; u < RA; ++u) {
-            const int idx = tid + NTHR * u, k = idx / (TC / 2), c = c_blk + 2 * (idx % (TC / 2));
-            ra[u] = (kc + k < p && c < c_end) ? *reinterpret_cast<const double2*>(tv.R0 + (int64_t)(kc + k) * tv.ld_r + c)
-                                              : make_double2(0.0, 0.0);
+            const int idx = tid + NTHR * u, k = idx / (TC / 2), x = x_blk + 2 * (idx % (TC / 2));
+            ra[u] = (kc + k < p && x < a_ld) ? *reinterpret_cast<const double2*>(a_src + (int64_t)(kc + k) * a_ld + x)
+                                             : make_double2(0.0, 0.0);
         }
 #pragma unroll
         for (int u = 0; u < RB; ++u) {
@@ -809,9 +827,9 @@ __global__ __launch_bounds__(WC * WR * 64) void k_tab_flush_lds(TableauView tv, 
         for (int b = 0; b < NT; ++b)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                const int c = c_wave + a * 16 + lk + 4 * g;
+                const int c = column(a, g);
                 const int i = i_wave + b * 16 + lm;
-                acc[a][b][g] = (active && c < tv.c_hi && i < tv.m) ? tv.T0[(int64_t)c * tv.ld_t + i] : 0.0;
+                acc[a][b][g] = (active && c >= 0 && i < tv.m) ? tv.T0[(int64_t)c * tv.ld_t + i] : 0.0;
             }
     lstore(0);
     __syncthreads();
@@ -844,10 +862,71 @@ __global__ __launch_bounds__(WC * WR * 64) void k_tab_flush_lds(TableauView tv, 
         for (int b = 0; b < NT; ++b)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                const int c = c_wave + a * 16 + lk + 4 * g;
+                const int c = column(a, g);
                 const int i = i_wave + b * 16 + lm;
-                if (c < tv.c_hi && i < tv.m) tv.T0[(int64_t)c * tv.ld_t + i] = acc[a][b][g];
+                if (c >= 0 && i < tv.m) tv.T0[(int64_t)c * tv.ld_t + i] = acc[a][b][g];
             }
+}
+
+// The FlushList of a flush, in two launches over groups of 64 owned columns (one workgroup each, its four wavefronts on
+// every fourth pending row).  Mark: bit l of mask[b] = column c_lo + 64 b + l has a nonzero R0 entry.
+__global__ __launch_bounds__(kThreads) void k_tab_flush_mark(TableauView tv, FlushList fl, const int32_t* p_dev) {
+    const int p = *p_dev;
+    if (p == 0) return;
+    __shared__ unsigned long long s_mask[kThreads / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c = tv.c_lo + blockIdx.x * 64 + lane;
+    bool nz = false;
+    if (c < tv.c_hi) {
+        // eight independent loads in flight per step (p <= kMaxEta: at most four steps)
+        for (int j0 = wave; j0 < p; j0 += 4 * 8) {
+            double v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v[u] = j0 + 4 * u < p ? tv.R0[(int64_t)(j0 + 4 * u) * tv.ld_r + c] : 0.0;
+#pragma unroll
+            for (int u = 0; u < 8; ++u) nz |= !(v[u] == 0.0);          // NaN != 0
+        }
+    }
+    const unsigned long long m = __ballot(nz);
+    if (lane == 0) s_mask[wave] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) fl.mask[blockIdx.x] = s_mask[0] | s_mask[1] | s_mask[2] | s_mask[3];
+}
+
+// Compact: group b's marked columns go after those of groups 0 .. b-1 (ascending storage column, the same list every run):
+// their indices to cols, their R0 columns to R0c.  The last group stores the count and adds the flush to the statistics.
+__global__ __launch_bounds__(kThreads) void k_tab_flush_compact(TableauView tv, FlushList fl, const int32_t* p_dev, int nb) {
+    const int p = *p_dev;
+    if (p == 0) return;
+    __shared__ int s_before[kThreads / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int before = 0;
+    for (int b = threadIdx.x; b < (int)blockIdx.x; b += kThreads) before += __popcll(fl.mask[b]);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) before += __shfl_down(before, off, 64);
+    if (lane == 0) s_before[wave] = before;
+    __syncthreads();
+    before = s_before[0] + s_before[1] + s_before[2] + s_before[3];
+    const unsigned long long mask = fl.mask[blockIdx.x];
+    if ((mask >> lane) & 1ull) {
+        const int c = tv.c_lo + blockIdx.x * 64 + lane;
+        const int x = before + __popcll(mask & ((1ull << lane) - 1ull));
+        if (wave == 0) fl.cols[x] = c;
+        for (int j0 = wave; j0 < p; j0 += 4 * 8) {
+            double v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v[u] = j0 + 4 * u < p ? tv.R0[(int64_t)(j0 + 4 * u) * tv.ld_r + c] : 0.0;
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+                if (j0 + 4 * u < p) fl.R0c[(int64_t)(j0 + 4 * u) * fl.ld + x] = v[u];
+        }
+    }
+    if ((int)blockIdx.x == nb - 1 && threadIdx.x == 0) {
+        const int count = before + __popcll(mask);
+        *fl.count = count;
+        fl.stats[0] += 1;
+        fl.stats[1] += count;
+    }
 }
 
 __global__ void k_tab_gather_columns(TableauView tv, const int32_t* __restrict__ cols, double* __restrict__ out) {
@@ -1013,7 +1092,8 @@ void launch_tab_update_all(const TableauView& tv, const DeferredUpdate& du, Sele
                        basis_indices, in_basis, trace, trace_cap, rec);
 }
 
-void launch_tab_flush(const TableauView& tv, const DeferredUpdate& du, const PivotRecord* rec, hipStream_t s) {
+void launch_tab_flush(const TableauView& tv, const DeferredUpdate& du, const PivotRecord* rec, const FlushList& fl,
+                      hipStream_t s) {
     if (tv.c_hi <= tv.c_lo) return;
     const int ncols = tv.c_hi - tv.c_lo;
     const int32_t* p_dev = &rec->n_eta;
@@ -1023,12 +1103,20 @@ void launch_tab_flush(const TableauView& tv, const DeferredUpdate& du, const Piv
         // other one is in its MFMA loop)
         constexpr int WC = 2, WR = 4, KC = 16;
         dim3 grid(cdiv(tv.m, WR * 32), cdiv(ncols, WC * 64));
-        hipLaunchKernelGGL((k_tab_flush_lds<WC, WR, KC>), grid, dim3(WC * WR * 64), 0, s, tv, du, p_dev);
+        if (fl.cols) {
+            // only the listed columns; the host reads nothing back, the grid stays sized for all of them
+            const int nb = cdiv(ncols, 64);
+            hipLaunchKernelGGL(k_tab_flush_mark, dim3(nb), dim3(kThreads), 0, s, tv, fl, p_dev);
+            hipLaunchKernelGGL(k_tab_flush_compact, dim3(nb), dim3(kThreads), 0, s, tv, fl, p_dev, nb);
+            hipLaunchKernelGGL((k_tab_flush_lds<WC, WR, KC, true>), grid, dim3(WC * WR * 64), 0, s, tv, du, p_dev, fl);
+        } else {
+            hipLaunchKernelGGL((k_tab_flush_lds<WC, WR, KC, false>), grid, dim3(WC * WR * 64), 0, s, tv, du, p_dev, fl);
+        }
         return;
     }
-    constexpr int MT = 4, NT = 2;      // wavefront tile 64 columns x 32 rows, workgroup 128 x 64
+    constexpr int MT = 4, NT = 2;      // wavefront tile 64 columns x 32 rows, workgroup 128 x 64 (every owned column)
     dim3 grid(cdiv(ncols, 2 * 16 * MT), cdiv(tv.m, 2 * 16 * NT));
-    hipLaunchKernelGGL((k_tab_flush<MT, NT>), grid, dim3(kThreads), 0, s, tv, du, p_dev);
+    hipLaunchKernelGGL((k_tab_flush<MT, NT>), grid, dim3(kThreads), 0, s, tv, du, p_dev, fl.stats);
 }
 
 void launch_tab_gather_columns(const TableauView& tv, const int32_t* cols, double* out, hipStream_t s) {

@@ -92,6 +92,7 @@ _SIGNATURES = {
     "relp_from_basis": (C.c_int, [C.c_void_p, C.c_void_p]),
     "relp_flush": (C.c_int, [C.c_void_p]),
     "relp_update_block": (C.c_int32, [C.c_void_p]),
+    "relp_tab_flush_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "relp_lu_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "relp_lu_lookahead_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "relp_lu_kernel_layout": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
@@ -373,6 +374,12 @@ class Tableau:
 
     def update_block(self) -> int:
         return self._lib.relp_update_block(self._h)
+
+    def flush_stats(self) -> Tuple[int, int]:
+        """Tableau engine: (flushes, columns those flushes rewrote) since create."""
+        out = (C.c_int64 * 2)()
+        self._ck(self._lib.relp_tab_flush_stats(self._h, out))
+        return int(out[0]), int(out[1])
 
     def engine_kind(self) -> int:
         """The engine in use (RELP_ENGINE_AUTO resolved at create)."""
