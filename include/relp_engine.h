@@ -236,6 +236,9 @@ relp_status_t relp_flush(relp_engine_t *h);
  * owned columns with a nonzero entry among the pending rows R0 (the others have T0 + W R0 = T0), or every owned column
  * when RELP_TAB_FLUSH_ALL=1 was set at create.  Other engines: { 0, 0 }. */
 relp_status_t relp_tab_flush_stats(relp_engine_t *h, int64_t *out2);
+/* Tableau engine: how many of the p pending rows of an update block the per-pivot kernels load per memory round trip:
+ * RELP_TAB_LOAD_BATCH at create if it was 1 (one by one), 8, 16 or 32, else the default.  Other engines: 0. */
+int32_t       relp_tab_load_batch(const relp_engine_t *h);
 /* The block size K in effect (0 = explicit rank-1 updates; LU engine: pivots between refactorisations). */
 int32_t       relp_update_block(const relp_engine_t *h);
 /* RELP_ENGINE_LU only: statistics of the current factorisation, out[8] = { refactorisations so far, m,

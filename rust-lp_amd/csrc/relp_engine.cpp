@@ -90,6 +90,7 @@ SelectPartials Engine::tab_partials(int rule) const {
 DeferredUpdate Engine::deferred() const {
     DeferredUpdate du;
     du.W = d_W_; du.ld = ld_b_; du.kmax = block_; du.S = d_S_; du.pos_of_row = d_pos_of_row_; du.wr = d_wr_; du.R = d_R_;
+    du.batch = load_batch_; du.w_split = w_split_;
     return du;
 }
 
@@ -256,6 +257,13 @@ relp_status_t Engine::create(const relp_matrix_data_t& md, const relp_config_t& 
                 HIP_TRY(dev_alloc(&d_fmask_, (n_owned + 63) / 64));
                 HIP_TRY(dev_alloc(&d_R0c_, ld_r_ * block_));
             }
+        }
+        {   // pending rows loaded per round trip in the per-pivot kernels (1 = one by one, the control), and the workgroups per 256
+            // rows that share W <- E W in the fused update; both read once, here
+            const char* e = std::getenv("RELP_TAB_LOAD_BATCH");
+            load_batch_ = tab_load_batch(e ? std::atoi(e) : 0);
+            const char* w = std::getenv("RELP_TAB_W_SPLIT");
+            w_split_ = w && std::atoi(w) >= 1 ? std::min(std::atoi(w), 16) : kTabSplitDefault;
         }
         {   // two launches per pivot instead of three in the single-GPU loop (RELP_FUSED_UPDATE=0: k_ratio_blocks + k_tab_update_all)
             const char* e = std::getenv("RELP_FUSED_UPDATE");

@@ -97,6 +97,7 @@ class Engine {
     relp_status_t get_iterations(int64_t* out);
     relp_status_t get_degenerate_pivots(int64_t* out);
     relp_status_t tab_flush_stats(int64_t* out2);
+    int32_t tab_load_batch_size() const { return tableau_ ? load_batch_ : 0; }
     relp_status_t get_trace(int32_t* phase, int32_t* entering, int32_t* row, int32_t* leaving, int64_t cap,
                             int64_t* count);
     relp_status_t check_basis(double* max_identity_error, double* max_basic_cost, double* min_b);
@@ -158,6 +159,8 @@ class Engine {
     unsigned long long *d_fmask_ = nullptr, *d_fstats_ = nullptr;   // d_fstats_: {flushes, columns flushed} since create
     double* d_R0c_ = nullptr;
     FlushList flush_list() const;
+    // RELP_TAB_LOAD_BATCH / RELP_TAB_W_SPLIT (relp_kernels.h: tab_load_batch, launch_tab_ratio_update_all)
+    int32_t load_batch_ = 0, w_split_ = 0;
     double* d_cost_store_ = nullptr;     // cost per stored column in the current phase
     int32_t* d_idcol_ = nullptr;         // stored column that was e_k originally, per row k
     // Ratio test + update in one launch (single-GPU loop, relp_kernels.h: launch_tab_ratio_update_all): the second copies of b

@@ -54,6 +54,8 @@ struct DeferredUpdate {
     int32_t* pos_of_row;    // row -> column of W, or -1                          (m)
     double*  wr;            // row r of W before this pivot's update              (kmax)
     double*  R;             // flush snapshot S' B0inv, kmax x ld (row j contiguous)
+    int32_t  batch;         // tableau kernels: pending rows loaded per round trip (tab_load_batch; 0 = the default)
+    int32_t  w_split;       // tableau fused update: workgroups per 256 rows of W <- E W, at most (0 or 1 = one)
 };
 
 // Read-only description of the tableau's columns (Kind + MatrixData, partially.rs:72-80,
@@ -442,6 +444,13 @@ struct FlushList {
     int64_t             ld;      // even, >= n_owned
     unsigned long long* stats;   // {flushes with p > 0, columns rewritten} since create
 };
+// RELP_TAB_LOAD_BATCH: the tableau kernels walk the p pending rows of W and R0 `batch` loads at a time.  tab_load_batch maps
+// a wanted value to one the kernels are instantiated for: 1 (one load per round trip, the control), 8, 16, 32; anything else
+// to the default.  kTabSplitDefault / kTabSplitCUs: see launch_tab_ratio_update_all.
+static constexpr int32_t kTabLoadBatchDefault = 8;
+static constexpr int32_t kTabSplitDefault = 2;
+static constexpr int32_t kTabSplitCUs = 256;
+int32_t tab_load_batch(int32_t wanted);
 // flush: T0 += W R0 with v_mfma_f64_16x16x4_f64 tiles
 void launch_tab_flush(const TableauView& tv, const DeferredUpdate& du, const PivotRecord* rec, const FlushList& fl,
                       hipStream_t s);
@@ -449,7 +458,9 @@ void launch_tab_flush(const TableauView& tv, const DeferredUpdate& du, const Piv
 // kernel left (same code, same answer), then does its share of the update.  What one workgroup rewrites while another may
 // still read it is double-buffered: b and the basis array (in -> out, the caller swaps them), row r of W (its new values go
 // to `shadow`, {row, length} to `shadow_meta`; the next column kernel or launch_tab_apply_shadow folds them into W), n_eta
-// (read as PivotRecord::p_now).
+// (read as PivotRecord::p_now).  With du.batch > 1 the rows of W get up to du.w_split workgroups per 256 rows, each with an
+// equal share of the p pending columns of W <- E W (one of them keeps b, the basis, the shadow row and the record), as long as
+// the grid stays within one workgroup per CU (kTabSplitCUs); under batch 1 the grid is the unsplit one.
 void launch_tab_ratio_update_all(const TableauView& tv, const DeferredUpdate& du, SelectPartials sp, int32_t m,
                                  const double* alpha, const double* b_in, double* b_out, const int32_t* basis_in,
                                  int32_t* basis_out, uint8_t* in_basis, int32_t* trace, int64_t trace_cap, Tolerances tol,

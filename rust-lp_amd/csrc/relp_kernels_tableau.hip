@@ -1,6 +1,7 @@
 // relp_kernels_tableau.hip -- kernels of the dense-tableau engine (RELP_ENGINE_TABLEAU), including the
 // f64-MFMA flush T0 += W R0.
 #include "relp_device_common.h"
+#include <type_traits>
 
 namespace relp {
 
@@ -11,6 +12,45 @@ namespace relp {
 //   UPDATE = W <- E W per pivot; T0 += W R0 once per K pivots on the f64 matrix cores
 // ------------------------------------------------------------------------------------------------
 typedef double double4_t __attribute__((ext_vector_type(4)));
+
+// The walk over the p pending rows of an update block: use(j, base[j * stride + x]) for j = 0 .. n-1 in ascending order, the
+// loads B at a time.  The B elements of a batch are loaded into registers before any of them is used or stored, so the
+// loads leave back to back and one descending vmcnt ladder follows: a thread makes ceil(n / B) serial round trips to
+// L2 / Infinity Cache instead of n (a store in `use`, or a load the compiler cannot prove independent of it, otherwise
+// closes every round trip before the next one opens).  The tail batch is masked: nothing at or past row n is read.
+// `use` may store to the element it was given and to nothing else of the walked range (j * stride + x is a different
+// address for every j when stride > 0).  B = 1 is the plain loop.
+template <int B, class Use>
+__device__ __forceinline__ void for_pending(const double* base, int64_t stride, int64_t x, int n, Use&& use) {
+    int j0 = 0;
+    for (; j0 + B <= n; j0 += B) {
+        double v[B];
+#pragma unroll
+        for (int t = 0; t < B; ++t) v[t] = base[(int64_t)(j0 + t) * stride + x];
+#pragma unroll
+        for (int t = 0; t < B; ++t) use(j0 + t, v[t]);
+    }
+    if (B > 1 && j0 < n) {
+        double v[B];
+#pragma unroll
+        for (int t = 0; t < B; ++t) v[t] = j0 + t < n ? base[(int64_t)(j0 + t) * stride + x] : 0.0;
+#pragma unroll
+        for (int t = 0; t < B; ++t)
+            if (j0 + t < n) use(j0 + t, v[t]);
+    }
+}
+
+// W <- E W for row i: W[j][i] = fma(u, w_r[j], W[j][i]) for the pending rows j0 <= j < j1, where neither factor is zero
+// (fma(u, 0.0, -0.0) is +0.0: an entry a zero factor would leave alone keeps its bits).
+template <int B>
+__device__ __forceinline__ void tab_update_w_row(const DeferredUpdate& du, int i, double u, const double* s_wr, int j0, int j1) {
+    if (u == 0.0 || j1 <= j0) return;
+    double* col = du.W + (int64_t)j0 * du.ld;
+    for_pending<B>(col, du.ld, i, j1 - j0, [&](int j, double old) {
+        const double w = s_wr[j0 + j];
+        if (w != 0.0) col[(int64_t)j * du.ld + i] = fma(u, w, old);
+    });
+}
 
 __global__ void k_tab_build(TableauView tv, const double* __restrict__ A, int64_t ld_a, ColumnTable ct) {
     const int64_t total = (int64_t)tv.m * (tv.c_hi - tv.c_lo);
@@ -141,6 +181,7 @@ __global__ __launch_bounds__(kSingleBlock) void k_tab_select(TableauView tv, Sel
 }
 
 // alpha = T[:,q] = T0[:,q] + W (R0[:,q])
+template <int B>
 __global__ __launch_bounds__(kThreads) void k_tab_column(TableauView tv, DeferredUpdate du, double* __restrict__ alpha,
                                                          const PivotRecord* rec) {
     if (rec->outcome != DEV_RUNNING) return;
@@ -152,7 +193,7 @@ __global__ __launch_bounds__(kThreads) void k_tab_column(TableauView tv, Deferre
     const int i = blockIdx.x * kThreads + threadIdx.x;
     if (i >= tv.m) return;
     double a = tv.T0[(int64_t)cq * tv.ld_t + i];
-    for (int j = 0; j < p; ++j) a = fma(du.W[(int64_t)j * du.ld + i], s_vs[j], a);
+    for_pending<B>(du.W, du.ld, i, p, [&](int j, double w) { a = fma(w, s_vs[j], a); });
     alpha[i] = a;
 }
 
@@ -163,6 +204,7 @@ __global__ __launch_bounds__(kThreads) void k_tab_column(TableauView tv, Deferre
 // it field by field between stores costs a dependent memory round trip each time).
 // `wr` (shared memory) = row r of W before this pivot; the pivot itself as plain arguments (the fused launch computes them
 // per workgroup, the others take them from the record).  `R` is only read for the selection key's rule memory.
+template <int B>
 __device__ __forceinline__ void tab_row_update_core(const TableauView& tv, const DeferredUpdate& du, const SelectPartials& sp,
                                                     const PivotRecord& R, int block, const double* s_wr, int p_old, int jt, int r,
                                                     int q, int leaving, double d_q, double alpha_r) {
@@ -181,7 +223,7 @@ __device__ __forceinline__ void tab_row_update_core(const TableauView& tv, const
             tv.R0[(int64_t)jt * tv.ld_r + c] = base;
         }
         double row = base;
-        for (int j = 0; j < p_old; ++j) row = fma(s_wr[j], tv.R0[(int64_t)j * tv.ld_r + c], row);
+        for_pending<B>(tv.R0, tv.ld_r, c, p_old, [&](int j, double r0) { row = fma(s_wr[j], r0, row); });
         const double theta = d_q / alpha_r;
         const int j = c - tv.col_off;
         double dn = fma(-theta, row, d_old);
@@ -196,22 +238,25 @@ __device__ __forceinline__ void tab_row_update_core(const TableauView& tv, const
     block_partial_min(key, kj, sp, block);
 }
 
+template <int B>
 __device__ __forceinline__ void tab_row_update_body(const TableauView& tv, const DeferredUpdate& du,
                                                     const SelectPartials& sp, const PivotRecord& R, int block) {
     __shared__ double s_wr[kMaxEta];
     // fetched without waiting for p_old (entries beyond it are never used)
     if ((int)threadIdx.x < du.kmax) s_wr[threadIdx.x] = du.wr[threadIdx.x];
-    tab_row_update_core(tv, du, sp, R, block, s_wr, R.n_eta_old, R.eta_target, R.r, R.q, R.leaving, R.d_q, R.alpha_r);
+    tab_row_update_core<B>(tv, du, sp, R, block, s_wr, R.n_eta_old, R.eta_target, R.r, R.q, R.leaving, R.d_q, R.alpha_r);
 }
 
+template <int B>
 __global__ __launch_bounds__(kThreads) void k_tab_row_update(TableauView tv, DeferredUpdate du, SelectPartials sp,
                                                              PivotRecord* rec) {
     const PivotRecord R = *rec;
     if (R.outcome != DEV_RUNNING) return;
-    tab_row_update_body(tv, du, sp, R, blockIdx.x);
+    tab_row_update_body<B>(tv, du, sp, R, blockIdx.x);
 }
 
 // W <- E W  and  b, -obj, basis, flags, trace (both walk the m rows)
+template <int B>
 __device__ __forceinline__ void tab_update_w_vectors_body(const DeferredUpdate& du, int m, const double* __restrict__ alpha,
                                                           double* __restrict__ b, int32_t* __restrict__ basis_indices,
                                                           uint8_t* __restrict__ in_basis, int32_t* __restrict__ trace,
@@ -229,12 +274,7 @@ __device__ __forceinline__ void tab_update_w_vectors_body(const DeferredUpdate& 
     if (i < m) {
         const double a = a_i;
         const double u = (i == r) ? (1.0 / ar - 1.0) : (-a / ar);
-        if (u != 0.0) {
-            for (int j = 0; j < p_old; ++j) {
-                const double w = s_wr2[j];
-                if (w != 0.0) du.W[(int64_t)j * du.ld + i] = fma(u, w, du.W[(int64_t)j * du.ld + i]);
-            }
-        }
+        tab_update_w_row<B>(du, i, u, s_wr2, 0, p_old);
         double* tgt = du.W + (int64_t)jt * du.ld + i;
         if (jt < p_old) *tgt += u; else *tgt = u;
         if (i == r) b[i] = br;
@@ -258,6 +298,7 @@ __device__ __forceinline__ void tab_update_w_vectors_body(const DeferredUpdate& 
     }
 }
 
+template <int B>
 __global__ __launch_bounds__(kThreads) void k_tab_update_w_vectors(DeferredUpdate du, int m,
                                                                    const double* __restrict__ alpha,
                                                                    double* __restrict__ b,
@@ -267,13 +308,14 @@ __global__ __launch_bounds__(kThreads) void k_tab_update_w_vectors(DeferredUpdat
                                                                    PivotRecord* rec) {
     const PivotRecord R = *rec;
     if (R.outcome != DEV_RUNNING) return;
-    tab_update_w_vectors_body(du, m, alpha, b, basis_indices, in_basis, trace, trace_cap, R, rec, blockIdx.x);
+    tab_update_w_vectors_body<B>(du, m, alpha, b, basis_indices, in_basis, trace, trace_cap, R, rec, blockIdx.x);
 }
 
 // Both halves of the update in ONE launch: workgroups [0, nb_row) update the tableau row / reduced
 // costs / PRICE partials of their columns, workgroups [nb_row, ..) update W, b and the bookkeeping.
 // The halves touch disjoint data; the basis flags flipped by the second half are read by the first
 // through an expression that is the same for the old and the new flags.
+template <int B>
 __global__ __launch_bounds__(kThreads) void k_tab_update_all(TableauView tv, DeferredUpdate du, SelectPartials sp,
                                                              int nb_row, int m, const double* __restrict__ alpha,
                                                              double* __restrict__ b, int32_t* __restrict__ basis_indices,
@@ -281,8 +323,8 @@ __global__ __launch_bounds__(kThreads) void k_tab_update_all(TableauView tv, Def
                                                              int64_t trace_cap, PivotRecord* rec) {
     const PivotRecord R = *rec;
     if (R.outcome != DEV_RUNNING) return;
-    if ((int)blockIdx.x < nb_row) tab_row_update_body(tv, du, sp, R, blockIdx.x);
-    else tab_update_w_vectors_body(du, m, alpha, b, basis_indices, in_basis, trace, trace_cap, R, rec, blockIdx.x - nb_row);
+    if ((int)blockIdx.x < nb_row) tab_row_update_body<B>(tv, du, sp, R, blockIdx.x);
+    else tab_update_w_vectors_body<B>(du, m, alpha, b, basis_indices, in_basis, trace, trace_cap, R, rec, blockIdx.x - nb_row);
 }
 
 // Ratio test + both halves of the update in ONE launch (relp_kernels.h: launch_tab_ratio_update_all).  Workgroups
@@ -292,6 +334,10 @@ __global__ __launch_bounds__(kThreads) void k_tab_update_all(TableauView tv, Def
 // the new row r of W goes to `shadow`, n_eta is read as p_now; the basis flags are read through the expression that is
 // the same for old and new flags; pos_of_row[r] reads as -1 or as the value it is about to get.  Same arithmetic as
 // k_ratio_blocks + k_tab_update_all, bit for bit.
+// `split` > 1: the W half has split * nblk workgroups, and workgroup part * nblk + wblock updates the rows of block wblock in
+// its share of the pending columns of W (the m x p entries are independent of each other).  Part 0 alone keeps b, the
+// basis array, the shadow row and the record; column jt gets its u from the part that holds it.
+template <int B>
 __global__ __launch_bounds__(kThreads) void k_tab_ratio_update_all(TableauView tv, DeferredUpdate du, SelectPartials sp, int nb_row,
                                                                    int m, const double* alpha,
                                                                    const double* __restrict__ b_in, double* __restrict__ b_out,
@@ -301,14 +347,16 @@ __global__ __launch_bounds__(kThreads) void k_tab_ratio_update_all(TableauView t
                                                                    const double* rmin, int nblk,
                                                                    double* __restrict__ shadow, int32_t* __restrict__ shadow_meta,
                                                                    PivotRecord* rec, const double* __restrict__ msgs, int count,
-                                                                   int64_t msg_len, int rule) {
+                                                                   int64_t msg_len, int rule, int split) {
     const double first = (!msgs && (int)threadIdx.x < nblk) ? rmin[threadIdx.x] : INFINITY;      // in flight with the record
     PivotRecord R = *rec;
     const bool w_half = (int)blockIdx.x >= nb_row;
-    const int wblock = (int)blockIdx.x - nb_row;
+    const int part = w_half ? ((int)blockIdx.x - nb_row) / nblk : 0;
+    const int wblock = (int)blockIdx.x - nb_row - part * nblk;
     const int i = wblock * kThreads + threadIdx.x;
     // the loop has ended (or ends here): the double buffers still advance, because the host keeps swapping them
-    const bool mine = w_half && i < m;
+    const bool lead = w_half && part == 0;
+    const bool mine = lead && i < m;
     if (R.outcome != DEV_RUNNING) {
         if (mine) { b_out[i] = b_in[i]; basis_out[i] = basis_in[i]; }
         return;
@@ -340,7 +388,7 @@ __global__ __launch_bounds__(kThreads) void k_tab_ratio_update_all(TableauView t
         const int win = s_win;
         if (win < 0) {
             if (mine) { b_out[i] = b_in[i]; basis_out[i] = basis_in[i]; }
-            if (wblock == 0 && threadIdx.x == 0) {
+            if (lead && wblock == 0 && threadIdx.x == 0) {
                 rec->outcome = DEV_NO_CANDIDATE;
                 if (rule == 1) rec->last_selected = -1;
             }
@@ -356,7 +404,7 @@ __global__ __launch_bounds__(kThreads) void k_tab_ratio_update_all(TableauView t
     ratio_blocks_pick<kThreads>(alpha, b_in, basis_in, m, tol, rmin, nblk, &r, &leaving, first, !msgs);
     if (r < 0) {
         if (mine) { b_out[i] = b_in[i]; basis_out[i] = basis_in[i]; }
-        if (wblock == 0 && threadIdx.x == 0) rec->outcome = DEV_NO_ROW;
+        if (lead && wblock == 0 && threadIdx.x == 0) rec->outcome = DEV_NO_ROW;
         return;
     }
     __shared__ double s_wr[kMaxEta];
@@ -373,22 +421,29 @@ __global__ __launch_bounds__(kThreads) void k_tab_ratio_update_all(TableauView t
     const double alpha_r = s_ab[0], b_r = s_ab[1];
     const int jt = s_jt, q = R.q;
     if (!w_half) {
-        tab_row_update_core(tv, du, sp, R, blockIdx.x, s_wr, p_old, jt, r, q, leaving, R.d_q, alpha_r);
+        tab_row_update_core<B>(tv, du, sp, R, blockIdx.x, s_wr, p_old, jt, r, q, leaving, R.d_q, alpha_r);
         return;
     }
     const double br = b_r / alpha_r;
+    // this part's pending columns [j_lo, j_hi): equal shares, so every part makes the same number of round trips
+    const int share = (p_old + split - 1) / split;
+    const int j_lo = min(part * share, p_old), j_hi = min(j_lo + share, p_old);
+    if (!lead) {
+        if (i < m && i != r) {
+            const double u = -alpha[i] / alpha_r;
+            tab_update_w_row<B>(du, i, u, s_wr, j_lo, j_hi);
+            if (jt >= j_lo && jt < j_hi) du.W[(int64_t)jt * du.ld + i] += u;
+        }
+        return;
+    }
     if (i < m) {
         const double a = alpha[i], b_i = b_in[i];
         const double u = (i == r) ? (1.0 / alpha_r - 1.0) : (-a / alpha_r);
         if (i != r) {
-            if (u != 0.0) {
-                for (int j = 0; j < p_old; ++j) {
-                    const double w = s_wr[j];
-                    if (w != 0.0) du.W[(int64_t)j * du.ld + i] = fma(u, w, du.W[(int64_t)j * du.ld + i]);
-                }
-            }
+            tab_update_w_row<B>(du, i, u, s_wr, j_lo, j_hi);
             double* tgt = du.W + (int64_t)jt * du.ld + i;
-            if (jt < p_old) *tgt += u; else *tgt = u;
+            if (jt >= p_old) *tgt = u;
+            else if (jt < j_hi) *tgt += u;
         } else {
             // row r itself: other workgroups are reading its old values right now, the new ones go to the shadow row
             for (int j = 0; j < p_old; ++j) {
@@ -437,11 +492,12 @@ __global__ void k_tab_apply_shadow(DeferredUpdate du, double* __restrict__ shado
 // of the record; a rank without a candidate sends key = +inf and stays RUNNING (another rank may have one).
 // `rmin` (single-GPU loop): the minimum ratio b_i / alpha_i over this workgroup's 256 rows, for
 // k_ratio_blocks.
+template <int B>
 __global__ __launch_bounds__(kThreads) void k_tab_select_column(TableauView tv, DeferredUpdate du, SelectPartials sp,
                                                                 int count, double* alpha, double* msg,
                                                                 const double* b, Tolerances tol,
                                                                 double* rmin, PivotRecord* rec,
-                                                                const double* shadow = nullptr, int32_t* shadow_meta = nullptr) {
+                                                                const double* shadow, int32_t* shadow_meta) {
     const int outcome = rec->outcome, p = rec->n_eta;          // one round trip for both ...
     // ... and for the shadow row of the previous pivot's fused update: the workgroup that owns the row folds it into W before
     // it reads the row (no other workgroup reads it)
@@ -547,7 +603,7 @@ __global__ __launch_bounds__(kThreads) void k_tab_select_column(TableauView tv, 
     double ratio = INFINITY;
     if (i < tv.m) {
         double a = t0;
-        for (int j = 0; j < p; ++j) a = fma(du.W[(int64_t)j * du.ld + i], s_vs[j], a);
+        for_pending<B>(du.W, du.ld, i, p, [&](int j, double w) { a = fma(w, s_vs[j], a); });
         alpha[i] = a;
         // the same expression as the ratio test's first pass (ratio_body), so min over the block minima is
         // bit for bit the minimum over all rows
@@ -937,6 +993,7 @@ __global__ void k_tab_gather_columns(TableauView tv, const int32_t* __restrict__
     }
 }
 
+template <int B>
 __global__ __launch_bounds__(kThreads) void k_tab_row(TableauView tv, DeferredUpdate du, int row, double* __restrict__ out,
                                                       const PivotRecord* rec) {
     __shared__ double s_w[kMaxEta];
@@ -946,13 +1003,14 @@ __global__ __launch_bounds__(kThreads) void k_tab_row(TableauView tv, DeferredUp
     const int c = tv.c_lo + blockIdx.x * kThreads + threadIdx.x;
     if (c >= tv.c_hi) return;
     double v = tv.T0[(int64_t)c * tv.ld_t + row];
-    for (int j = 0; j < p; ++j) v = fma(s_w[j], tv.R0[(int64_t)j * tv.ld_r + c], v);
+    for_pending<B>(tv.R0, tv.ld_r, c, p, [&](int j, double r0) { v = fma(s_w[j], r0, v); });
     out[c - tv.c_lo] = v;
 }
 
 // phase_one.rs:236-244 for the sharded engine: among the owned columns, the candidates to replace a basic
 // artificial variable at zero level in tableau row `row` -- non-basic, not artificial, reduced cost 0, tableau
 // entry != 0 -- as PRICE partials with key = column index (the first one wins, like FirstProfitable).
+template <int B>
 __global__ __launch_bounds__(kThreads) void k_tab_zero_level_scan(TableauView tv, DeferredUpdate du, SelectPartials sp, int row,
                                                                   int nr_artificial, Tolerances tol, const PivotRecord* rec) {
     const int outcome = rec->outcome, p = rec->n_eta;
@@ -966,13 +1024,31 @@ __global__ __launch_bounds__(kThreads) void k_tab_zero_level_scan(TableauView tv
     int kj = 0x7fffffff;
     if (c < tv.c_hi && j >= nr_artificial && j < tv.n && !sp.in_basis[j] && fabs(tv.d[c]) <= tol.cost) {
         double v = tv.T0[(int64_t)c * tv.ld_t + row];
-        for (int k = 0; k < p; ++k) v = fma(s_w[k], tv.R0[(int64_t)k * tv.ld_r + c], v);
+        for_pending<B>(tv.R0, tv.ld_r, c, p, [&](int k, double r0) { v = fma(s_w[k], r0, v); });
         if (fabs(v) > tol.pivot) { key = (double)j; kj = j; }
     }
     block_partial_min(key, kj, sp, blockIdx.x);
 }
 
 int32_t tab_scan_blocks(int32_t n_owned_columns) { return cdiv(n_owned_columns, kThreads); }
+
+// The batch sizes of for_pending the kernels are instantiated for (DeferredUpdate::batch, RELP_TAB_LOAD_BATCH).  1 is the
+// serial loop, the control; the default measured best on dense10k (profiles/r06_tab_load_batch.md).
+int32_t tab_load_batch(int32_t wanted) {
+    return (wanted == 1 || wanted == 8 || wanted == 16 || wanted == 32) ? wanted : kTabLoadBatchDefault;
+}
+
+// launch(std::integral_constant<int, B>) for B = tab_load_batch(batch)
+template <class Launch>
+static void with_load_batch(int32_t batch, Launch&& launch) {
+    switch (tab_load_batch(batch)) {
+    case 1:  launch(std::integral_constant<int, 1>{}); break;
+    case 16: launch(std::integral_constant<int, 16>{}); break;
+    case 32: launch(std::integral_constant<int, 32>{}); break;
+    default: launch(std::integral_constant<int, 8>{}); break;
+    }
+    static_assert(kTabLoadBatchDefault == 8, "the default of tab_load_batch is the switch's default case");
+}
 
 void launch_tab_build(const TableauView& tv, const double* A, int64_t ld_a, const ColumnTable& ct, hipStream_t s) {
     const int64_t total = (int64_t)tv.m * (tv.c_hi - tv.c_lo);
@@ -1003,14 +1079,18 @@ void launch_tab_select(const TableauView& tv, SelectPartials sp, int32_t count, 
 
 void launch_tab_column(const TableauView& tv, const DeferredUpdate& du, double* alpha, const PivotRecord* rec,
                        hipStream_t s) {
-    hipLaunchKernelGGL(k_tab_column, dim3(cdiv(tv.m, kThreads)), dim3(kThreads), 0, s, tv, du, alpha, rec);
+    with_load_batch(du.batch, [&](auto B) {
+        hipLaunchKernelGGL((k_tab_column<decltype(B)::value>), dim3(cdiv(tv.m, kThreads)), dim3(kThreads), 0, s, tv, du, alpha, rec);
+    });
 }
 
 void launch_tab_row_update(const TableauView& tv, const DeferredUpdate& du, SelectPartials sp, PivotRecord* rec,
                            hipStream_t s) {
     if (tv.c_hi <= tv.c_lo) return;
-    hipLaunchKernelGGL(k_tab_row_update, dim3(tab_scan_blocks(tv.c_hi - tv.c_lo)), dim3(kThreads), 0, s, tv, du, sp,
-                       rec);
+    with_load_batch(du.batch, [&](auto B) {
+        hipLaunchKernelGGL((k_tab_row_update<decltype(B)::value>), dim3(tab_scan_blocks(tv.c_hi - tv.c_lo)), dim3(kThreads), 0, s, tv, du, sp,
+                           rec);
+    });
 }
 
 void launch_tab_update_vectors(int32_t m, const double* alpha, double* b, int32_t* basis_indices, uint8_t* in_basis,
@@ -1022,22 +1102,28 @@ void launch_tab_update_vectors(int32_t m, const double* alpha, double* b, int32_
 void launch_tab_update_w_vectors(const DeferredUpdate& du, int32_t m, const double* alpha, double* b,
                                  int32_t* basis_indices, uint8_t* in_basis, int32_t* trace, int64_t trace_cap,
                                  PivotRecord* rec, hipStream_t s) {
-    hipLaunchKernelGGL(k_tab_update_w_vectors, dim3(cdiv(m, kThreads)), dim3(kThreads), 0, s, du, m, alpha, b,
-                       basis_indices, in_basis, trace, trace_cap, rec);
+    with_load_batch(du.batch, [&](auto B) {
+        hipLaunchKernelGGL((k_tab_update_w_vectors<decltype(B)::value>), dim3(cdiv(m, kThreads)), dim3(kThreads), 0, s, du, m, alpha, b,
+                           basis_indices, in_basis, trace, trace_cap, rec);
+    });
 }
 
 void launch_tab_select_column(const TableauView& tv, const DeferredUpdate& du, SelectPartials sp, int32_t count,
                               double* alpha, PivotRecord* rec, hipStream_t s) {
-    hipLaunchKernelGGL(k_tab_select_column, dim3(cdiv(tv.m, kThreads)), dim3(kThreads), 0, s, tv, du, sp, count, alpha,
-                       (double*)nullptr, (const double*)nullptr, Tolerances{}, (double*)nullptr, rec, (const double*)nullptr,
-                       (int32_t*)nullptr);
+    with_load_batch(du.batch, [&](auto B) {
+        hipLaunchKernelGGL((k_tab_select_column<decltype(B)::value>), dim3(cdiv(tv.m, kThreads)), dim3(kThreads), 0, s, tv, du, sp, count, alpha,
+                           (double*)nullptr, (const double*)nullptr, Tolerances{}, (double*)nullptr, rec, (const double*)nullptr,
+                           (int32_t*)nullptr);
+    });
 }
 
 void launch_tab_select_column_rmin(const TableauView& tv, const DeferredUpdate& du, SelectPartials sp, int32_t count,
                                    double* alpha, const double* b, Tolerances tol, double* rmin, PivotRecord* rec,
                                    hipStream_t s, const double* shadow, int32_t* shadow_meta) {
-    hipLaunchKernelGGL(k_tab_select_column, dim3(cdiv(tv.m, kThreads)), dim3(kThreads), 0, s, tv, du, sp, count, alpha,
-                       (double*)nullptr, b, tol, rmin, rec, shadow, shadow_meta);
+    with_load_batch(du.batch, [&](auto B) {
+        hipLaunchKernelGGL((k_tab_select_column<decltype(B)::value>), dim3(cdiv(tv.m, kThreads)), dim3(kThreads), 0, s, tv, du, sp, count, alpha,
+                           (double*)nullptr, b, tol, rmin, rec, shadow, shadow_meta);
+    });
 }
 
 void launch_tab_ratio_update_all(const TableauView& tv, const DeferredUpdate& du, SelectPartials sp, int32_t m,
@@ -1047,9 +1133,14 @@ void launch_tab_ratio_update_all(const TableauView& tv, const DeferredUpdate& du
                                  const double* msgs, int32_t count, int64_t msg_len, int32_t rule) {
     const int nb_row = tv.c_hi > tv.c_lo ? tab_scan_blocks(tv.c_hi - tv.c_lo) : 0;
     const int nb_w = cdiv(m, kThreads);
-    hipLaunchKernelGGL(k_tab_ratio_update_all, dim3(nb_row + nb_w), dim3(kThreads), 0, s, tv, du, sp, nb_row, m, alpha, b_in,
-                       b_out, basis_in, basis_out, in_basis, trace, trace_cap, tol, rmin, nb_w, shadow, shadow_meta, rec, msgs,
-                       (int)count, msg_len, (int)rule);
+    // the W half over `split` workgroups per 256 rows, as far as the whole grid still fits one workgroup per CU (past that
+    // the extra workgroups queue behind the others and only repeat the ratio test); never under batch 1, the control
+    int split = tab_load_batch(du.batch) == 1 ? 1 : std::max(1, std::min({(int)du.w_split, (int)du.kmax, (kTabSplitCUs - nb_row) / nb_w}));
+    with_load_batch(du.batch, [&](auto B) {
+        hipLaunchKernelGGL((k_tab_ratio_update_all<decltype(B)::value>), dim3(nb_row + split * nb_w), dim3(kThreads), 0, s, tv, du, sp, nb_row, m,
+                           alpha, b_in, b_out, basis_in, basis_out, in_basis, trace, trace_cap, tol, rmin, nb_w, shadow,
+                           shadow_meta, rec, msgs, (int)count, msg_len, (int)rule, split);
+    });
 }
 
 void launch_tab_apply_shadow(const DeferredUpdate& du, double* shadow, int32_t* shadow_meta, hipStream_t s) {
@@ -1065,8 +1156,10 @@ void launch_ratio_blocks(const double* alpha, const double* b, const int32_t* ba
 void launch_tab_select_column_msg(const TableauView& tv, const DeferredUpdate& du, SelectPartials sp, int32_t count,
                                   double* msg, const double* b, Tolerances tol, PivotRecord* rec, hipStream_t s,
                                   const double* shadow, int32_t* shadow_meta) {
-    hipLaunchKernelGGL(k_tab_select_column, dim3(cdiv(tv.m, kThreads)), dim3(kThreads), 0, s, tv, du, sp, count, msg + 3,
-                       msg, b, tol, msg + 3 + tv.m, rec, shadow, shadow_meta);
+    with_load_batch(du.batch, [&](auto B) {
+        hipLaunchKernelGGL((k_tab_select_column<decltype(B)::value>), dim3(cdiv(tv.m, kThreads)), dim3(kThreads), 0, s, tv, du, sp, count, msg + 3,
+                           msg, b, tol, msg + 3 + tv.m, rec, shadow, shadow_meta);
+    });
 }
 
 void launch_tab_select_candidate_ratio(const double* msgs, int32_t count, int64_t msg_len, int32_t m, double* alpha,
@@ -1079,8 +1172,10 @@ void launch_tab_select_candidate_ratio(const double* msgs, int32_t count, int64_
 void launch_tab_zero_level_scan(const TableauView& tv, const DeferredUpdate& du, SelectPartials sp, int32_t row,
                                 int32_t nr_artificial, Tolerances tol, const PivotRecord* rec, hipStream_t s) {
     if (tv.c_hi <= tv.c_lo) return;
-    hipLaunchKernelGGL(k_tab_zero_level_scan, dim3(tab_scan_blocks(tv.c_hi - tv.c_lo)), dim3(kThreads), 0, s, tv, du, sp, row,
-                       nr_artificial, tol, rec);
+    with_load_batch(du.batch, [&](auto B) {
+        hipLaunchKernelGGL((k_tab_zero_level_scan<decltype(B)::value>), dim3(tab_scan_blocks(tv.c_hi - tv.c_lo)), dim3(kThreads), 0, s, tv, du, sp,
+                           row, nr_artificial, tol, rec);
+    });
 }
 
 void launch_tab_update_all(const TableauView& tv, const DeferredUpdate& du, SelectPartials sp, int32_t m,
@@ -1088,8 +1183,10 @@ void launch_tab_update_all(const TableauView& tv, const DeferredUpdate& du, Sele
                            int64_t trace_cap, PivotRecord* rec, hipStream_t s) {
     const int nb_row = tv.c_hi > tv.c_lo ? tab_scan_blocks(tv.c_hi - tv.c_lo) : 0;
     const int nb_w = cdiv(m, kThreads);
-    hipLaunchKernelGGL(k_tab_update_all, dim3(nb_row + nb_w), dim3(kThreads), 0, s, tv, du, sp, nb_row, m, alpha, b,
-                       basis_indices, in_basis, trace, trace_cap, rec);
+    with_load_batch(du.batch, [&](auto B) {
+        hipLaunchKernelGGL((k_tab_update_all<decltype(B)::value>), dim3(nb_row + nb_w), dim3(kThreads), 0, s, tv, du, sp, nb_row, m, alpha, b,
+                           basis_indices, in_basis, trace, trace_cap, rec);
+    });
 }
 
 void launch_tab_flush(const TableauView& tv, const DeferredUpdate& du, const PivotRecord* rec, const FlushList& fl,
@@ -1127,7 +1224,9 @@ void launch_tab_gather_columns(const TableauView& tv, const int32_t* cols, doubl
 void launch_tab_row(const TableauView& tv, const DeferredUpdate& du, int32_t row, double* out, const PivotRecord* rec,
                     hipStream_t s) {
     if (tv.c_hi <= tv.c_lo) return;
-    hipLaunchKernelGGL(k_tab_row, dim3(tab_scan_blocks(tv.c_hi - tv.c_lo)), dim3(kThreads), 0, s, tv, du, row, out, rec);
+    with_load_batch(du.batch, [&](auto B) {
+        hipLaunchKernelGGL((k_tab_row<decltype(B)::value>), dim3(tab_scan_blocks(tv.c_hi - tv.c_lo)), dim3(kThreads), 0, s, tv, du, row, out, rec);
+    });
 }
 
 

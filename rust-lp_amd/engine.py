@@ -92,6 +92,7 @@ _SIGNATURES = {
     "relp_from_basis": (C.c_int, [C.c_void_p, C.c_void_p]),
     "relp_flush": (C.c_int, [C.c_void_p]),
     "relp_update_block": (C.c_int32, [C.c_void_p]),
+    "relp_tab_load_batch": (C.c_int32, [C.c_void_p]),
     "relp_tab_flush_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "relp_lu_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "relp_lu_lookahead_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
@@ -374,6 +375,10 @@ class Tableau:
 
     def update_block(self) -> int:
         return self._lib.relp_update_block(self._h)
+
+    def load_batch(self) -> int:
+        """Tableau engine: pending rows the per-pivot kernels load per round trip (RELP_TAB_LOAD_BATCH at create)."""
+        return self._lib.relp_tab_load_batch(self._h)
 
     def flush_stats(self) -> Tuple[int, int]:
         """Tableau engine: (flushes, columns those flushes rewrote) since create."""
