@@ -1,5 +1,7 @@
 // relp_device_common.h -- device helpers shared by the three kernel files (constants, wavefront and
-// workgroup reductions, the PRICE key, the ratio-test body).  Included by relp_kernels_*.hip only.
+// workgroup reductions, and the steps of a pivot every engine's kernels share: the PRICE key and (key, column) minimum, the
+// entering-column choice, the winner among shard candidates, the ratio test, the bookkeeping of a completed pivot).
+// Included by relp_kernels_*.hip only.
 #pragma once
 #include <algorithm>
 #include "relp_kernels.h"
@@ -78,10 +80,13 @@ __device__ __forceinline__ double select_key(int rule, int n, const PivotRecord*
 
 // ------------------------------------------------------------------------------------------------
 // PRICE
-// Workgroup-level (key, j) minimum of one candidate per thread -> partial slot `slot`.
-__device__ __forceinline__ void block_partial_min(double key, int kj, SelectPartials sp, int slot) {
-    __shared__ double s_k[kThreads / 64];
-    __shared__ int s_j[kThreads / 64];
+// Workgroup minimum of (key, column) over BS threads, result in every thread: smaller key wins, ties go to the lower column.
+// One barrier; every thread finishes from the BS / 64 LDS words itself.  The order is total, so the result does not depend
+// on how the candidates are spread over the threads.  A kernel that calls it twice puts a barrier between the calls.
+template <int BS>
+__device__ __forceinline__ void block_min_key(double& key, int& kj) {
+    __shared__ double s_k[BS / 64];
+    __shared__ int s_j[BS / 64];
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         const double ok = __shfl_down(key, off, 64);
@@ -91,12 +96,16 @@ __device__ __forceinline__ void block_partial_min(double key, int kj, SelectPart
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0) { s_k[wave] = key; s_j[wave] = kj; }
     __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < kThreads / 64; ++w)
-            if (s_k[w] < key || (s_k[w] == key && s_j[w] < kj)) { key = s_k[w]; kj = s_j[w]; }
-        sp.k1[slot] = key;
-        sp.j[slot] = kj;
-    }
+    key = s_k[0]; kj = s_j[0];
+#pragma unroll
+    for (int w = 1; w < BS / 64; ++w)
+        if (s_k[w] < key || (s_k[w] == key && s_j[w] < kj)) { key = s_k[w]; kj = s_j[w]; }
+}
+
+// Workgroup-level (key, j) minimum of one candidate per thread -> partial slot `slot`.
+__device__ __forceinline__ void block_partial_min(double key, int kj, SelectPartials sp, int slot) {
+    block_min_key<kThreads>(key, kj);
+    if (threadIdx.x == 0) { sp.k1[slot] = key; sp.j[slot] = kj; }
 }
 
 // PRICE of 256 virtual columns (artificial, slack, bound slack; no matrix data: d_j = cost + (+-)(-pi)_row) and their
@@ -124,26 +133,143 @@ __device__ __forceinline__ void price_virtual_body(const ColumnTable& ct, const 
     }
     if (j >= 0) d[j] = val;
     if (!sp.k1) return;
-    __shared__ double s_k[kThreads / 64];
-    __shared__ int s_j[kThreads / 64];
     double key = INFINITY;
     int kj = 0x7fffffff;
     if (j >= 0 && !sp.in_basis[j] && val < -sp.tol_cost) { key = select_key(sp.rule, sp.n, rec, j, val); kj = j; }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double ok = __shfl_down(key, off, 64);
-        const int oj = __shfl_down(kj, off, 64);
-        if (ok < key || (ok == key && oj < kj)) { key = ok; kj = oj; }
+    block_partial_min(key, kj, sp, sp.offset + block);
+}
+
+// Entering column of the tableau engine from the `count` PRICE partials (slot t = the kThreads storage columns from
+// tv.c_lo + t * kThreads), by a workgroup of BS threads.  On entry (k1, bj) is the thread's first partial -- slot threadIdx.x,
+// (+inf, 0x7fffffff) past the end -- which the caller loads together with whatever else it has to wait for; on return every
+// thread holds the winner's key and column, bj = 0x7fffffff when there is none.
+// Dantzig ties (pivot_rule.rs:118): the lowest index with d_j <= k1 + tol_tie * max(1, |k1|).  Only a slot whose own minimum
+// is inside the band can hold such a column: those slots (normally one or two) are listed first, then re-read one column per
+// thread, so the scan does not walk all `count` slots one dependent load after the other.
+template <int BS>
+__device__ __forceinline__ void tab_select_entering(const TableauView& tv, const SelectPartials& sp, int count, double& k1,
+                                                    int& bj) {
+    constexpr int kListMax = 32, kGroups = BS / kThreads;
+    __shared__ int s_list[kListMax];
+    __shared__ int s_cnt;
+    __shared__ int s_low[BS / 64];
+    for (int t = threadIdx.x + BS; t < count; t += BS) {
+        const double key = sp.k1[t];
+        const int j = sp.j[t];
+        if (key < k1 || (key == k1 && j < bj)) { k1 = key; bj = j; }
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) { s_k[wave] = key; s_j[wave] = kj; }
+    if (threadIdx.x == 0) s_cnt = 0;                   // (visible after the barrier of the reduction)
+    block_min_key<BS>(k1, bj);
+    if (!(bj != 0x7fffffff && sp.rule == 2 && sp.tol_tie > 0.0)) return;
+    const double bound = k1 + sp.tol_tie * fmax(1.0, fabs(k1));
+    for (int t = threadIdx.x; t < count; t += BS) {
+        if (!(sp.k1[t] <= bound)) continue;
+        const int pos = atomicAdd(&s_cnt, 1);
+        if (pos < kListMax) s_list[pos] = t;
+    }
     __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < kThreads / 64; ++w)
-            if (s_k[w] < key || (s_k[w] == key && s_j[w] < kj)) { key = s_k[w]; kj = s_j[w]; }
-        sp.k1[sp.offset + block] = key;
-        sp.j[sp.offset + block] = kj;
+    const int listed = s_cnt;
+    // kGroups groups of kThreads threads, each on every kGroups-th slot
+    const int grp = threadIdx.x / kThreads, u = threadIdx.x % kThreads;
+    int lowest = 0x7fffffff;
+    auto scan_slot = [&](int t) {
+        const int c = tv.c_lo + t * kThreads + u;
+        const int j = c - tv.col_off;
+        if (c < tv.c_hi && j >= 0 && j < tv.n) {
+            const double v = tv.d[c];
+            if (!sp.in_basis[j] && v < -sp.tol_cost && v <= bound && j < lowest) lowest = j;
+        }
+    };
+    if (listed <= kListMax) {
+        for (int i = grp; i < listed; i += kGroups) scan_slot(s_list[i]);
+    } else {
+        for (int t = grp; t < count; t += kGroups)
+            if (sp.k1[t] <= bound) scan_slot(t);
     }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) lowest = min(lowest, __shfl_down(lowest, off, 64));
+    if ((threadIdx.x & 63) == 0) s_low[threadIdx.x >> 6] = lowest;
+    __syncthreads();
+    bj = s_low[0];                                     // the minimum itself is inside the band: there is one
+#pragma unroll
+    for (int w = 1; w < BS / 64; ++w) bj = min(bj, s_low[w]);
+}
+
+// Sharded PRICE: the winner among `count` gathered candidates, candidate g with key key[g * stride] (+inf = the rank has
+// none) and column idx[g * stride] -- the heads of the messages themselves or a copy of them in LDS.  Smallest key, ties to
+// the lower column; Dantzig ties across ranks: every rank sent (its minimum, its lowest index within the band of that
+// minimum), and the lowest index among the ranks inside the global band wins.  Returns the rank, -1 when no rank has a
+// candidate.  Serial: for ONE thread, which hands the answer to the others.
+__device__ __forceinline__ int candidate_winner(const double* key, const double* idx, int64_t stride, int count, int rule,
+                                                double tol_tie) {
+    int win = -1; double k1 = INFINITY; double kj = 0.0;
+    for (int g = 0; g < count; ++g) {
+        const double a = key[g * stride], j = idx[g * stride];
+        if (a < k1 || (a == k1 && win >= 0 && j < kj)) { k1 = a; kj = j; win = g; }
+    }
+    if (win >= 0 && rule == 2 && tol_tie > 0.0) {
+        const double bound = k1 + tol_tie * fmax(1.0, fabs(k1));
+        for (int g = 0; g < count; ++g)
+            if (key[g * stride] <= bound && idx[g * stride] < kj) { kj = idx[g * stride]; win = g; }
+    }
+    return win;
+}
+
+// The same for a whole workgroup (of blockDim.x threads) with the heads [key, j, d_j] of the messages staged in LDS, so that
+// they arrive in one round trip: the winner's rank in every thread, with its column and reduced cost.
+static constexpr int kMaxRanks = 64;
+__device__ __forceinline__ int candidate_winner_staged(const double* __restrict__ msgs, int count, int64_t msg_len, int rule,
+                                                       double tol_tie, int* q, double* d_q) {
+    __shared__ double s_key[kMaxRanks], s_idx[kMaxRanks], s_dq[kMaxRanks];
+    __shared__ int s_win;
+    for (int g = threadIdx.x; g < count && g < kMaxRanks; g += blockDim.x) {
+        s_key[g] = msgs[g * msg_len + 0]; s_idx[g] = msgs[g * msg_len + 1]; s_dq[g] = msgs[g * msg_len + 2];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) s_win = candidate_winner(s_key, s_idx, 1, count, rule, tol_tie);
+    __syncthreads();
+    const int win = s_win;
+    if (win >= 0) { *q = (int)s_idx[win]; *d_q = s_dq[win]; }
+    return win;
+}
+
+// What the sharded PRICE leaves in the record, by one thread: the entering column, or the end of the loop (win < 0)
+__device__ __forceinline__ void record_candidate(PivotRecord* rec, int rule, int win, int q, double d_q) {
+    if (win < 0) {
+        rec->outcome = DEV_NO_CANDIDATE;
+        if (rule == 1) rec->last_selected = -1;
+    } else {
+        rec->q = q;
+        rec->d_q = d_q;
+        if (rule == 1) rec->last_selected = q;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// UPDATE: what every engine does to b and to the scalars of a completed pivot (carry/mod.rs:283-333, tableau/mod.rs:72-84)
+// ------------------------------------------------------------------------------------------------
+// b_i after the pivot, br = b_r / alpha_r: row r gets br, a row with alpha_i = 0 keeps its bits
+__device__ __forceinline__ double pivot_b(double a, double b_i, double br, bool is_r) {
+    return is_r ? br : (a != 0.0 ? fma(-a, br, b_i) : b_i);
+}
+
+// -obj, the basis flags, the trace row, the degenerate and the iteration counter, by ONE thread.  The pivot comes by value, so
+// from the record and from a register snapshot of it alike; basis_indices[r] = q stays with the caller (the fused launch writes
+// it to its output copy of the array).
+__device__ __forceinline__ void pivot_bookkeeping(int phase, long long iterations, double minus_objective, double d_q, double br,
+                                                  int q, int r, int leaving, uint8_t* in_basis, int32_t* trace, int64_t trace_cap,
+                                                  PivotRecord* rec) {
+    rec->minus_objective = fma(-d_q, br, minus_objective);
+    if (leaving < kWrappedArtificialBase) in_basis[leaving] = 0;   // a wrapped artificial has no flag
+    in_basis[q] = 1;
+    if (trace && iterations < trace_cap) {
+        trace[0 * trace_cap + iterations] = phase;
+        trace[1 * trace_cap + iterations] = q;
+        trace[2 * trace_cap + iterations] = r;
+        trace[3 * trace_cap + iterations] = leaving;
+    }
+    if (br == 0.0) rec->degenerate += 1;               // ratio 0: the basis changes, the vertex does not
+    rec->iterations = iterations + 1;
 }
 
 static constexpr int kMaxEta = 128;
@@ -195,19 +321,13 @@ __device__ __forceinline__ void tie_reduce(tie_key_t& key, int& row, tie_key_t* 
         if (s_k[w] < key) { key = s_k[w]; row = s_r[w]; }
 }
 
-// Last step of the ratio test: every thread brings its best (tie key, row) among the rows inside the
-// tie band; the workgroup's minimum wins (Bland on the leaving column, tableau/mod.rs:229-239), the record is
-// written and the block bookkeeping of the deferred update (row r of W saved, slot of W chosen) is done.
+// Last step of the ratio test, once the workgroup agrees on the pivot row r and its leaving column (tie_reduce: Bland on the
+// leaving column among the rows inside the tie band, tableau/mod.rs:229-239): the pivot guard, then the record is written and
+// the block bookkeeping of the deferred update (row r of W saved, slot of W chosen) is done.
+// (everything this reads from memory -- alpha_r, b_r, row r of W, the slot of row r -- goes out in ONE round trip)
 template <int BS>
-__device__ __forceinline__ void ratio_commit(tie_key_t best_key, int best_row, const double* alpha, const double* b,
-                                             const DeferredUpdate& du, int p, PivotRecord* rec, bool wide = false, int guard_m = 0,
-                                             double guard_rel = 0.0) {
-    __shared__ tie_key_t s_cl[BS / 64];
-    __shared__ int s_cr[BS / 64];
-    // (everything the epilogue reads from memory -- alpha_r, b_r, row r of W, the slot of row r -- goes out in ONE round trip)
-    tie_reduce<BS>(best_key, best_row, s_cl, s_cr, wide);
-    const int best_leave = tie_key_leaving(best_key);
-    const int r = best_row;
+__device__ __forceinline__ void ratio_commit_row(int r, int leaving, const double* alpha, const double* b, const DeferredUpdate& du,
+                                                 int p, PivotRecord* rec, int guard_m = 0, double guard_rel = 0.0) {
     if (guard_m > 0) {
         // Tolerances::pivot_guard: the chosen element against the largest |entry| of the column (one pass of the workgroup
         // over alpha; nothing has been written yet)
@@ -240,7 +360,7 @@ __device__ __forceinline__ void ratio_commit(tie_key_t best_key, int best_row, c
         for (int j = threadIdx.x; j < p; j += BS) du.wr[j] = du.W[(int64_t)j * du.ld + r];
     if (threadIdx.x == 0) {
         rec->r = r;
-        rec->leaving = best_leave;
+        rec->leaving = leaving;
         rec->alpha_r = a_r;
         rec->b_r = b_r;
         if (deferred) {
@@ -331,79 +451,24 @@ __device__ __forceinline__ void ratio_body(const double* alpha, const double* b,
             }
         }
     }
-    ratio_commit<BS>(best_key, best_row, alpha, b, du, p, rec, tol.ratio_rule != 0, tol.pivot_guard ? m : 0, tol.guard_rel);
+    __shared__ tie_key_t s_cl[BS / 64];
+    __shared__ int s_cr[BS / 64];
+    tie_reduce<BS>(best_key, best_row, s_cl, s_cr, tol.ratio_rule != 0);
+    ratio_commit_row<BS>(best_row, tie_key_leaving(best_key), alpha, b, du, p, rec, tol.pivot_guard ? m : 0, tol.guard_rel);
 }
 
-// Ratio test of a workgroup of BS threads from the minimum ratio of every block of `rpb` rows (`rmin`, nblk
-// entries, written by the kernel that formed alpha): the global minimum is the minimum of the block minima, and
-// a row inside the tie band lives in a block whose own minimum is inside the band, so only those blocks' rows
-// (usually one or two blocks) are read again.  Same result as ratio_body.  `p` = rec->n_eta read by the caller.
 // b_i / alpha_i as the ratio test's first pass forms it (ratio_body), +inf when the row does not qualify
 __device__ __forceinline__ double row_ratio(double a, double bi, const Tolerances& tol) {
     if (bi <= tol.zero) bi = 0.0;   // also clamps a b_i that rounding pushed below 0: no negative step
     return a > tol.pivot ? bi / a : INFINITY;
 }
 
-template <int BS>
-__device__ __forceinline__ void ratio_blocks_body(const double* __restrict__ alpha, const double* __restrict__ b,
-                                                  const int32_t* __restrict__ basis_indices, int m, const Tolerances& tol,
-                                                  const DeferredUpdate& du, const double* __restrict__ rmin, int nblk, int p,
-                                                  PivotRecord* rec, double first = INFINITY, bool have_first = false,
-                                                  int rpb = kThreads) {
-    __shared__ double s_min[BS / 64];
-    __shared__ double s_bcast;
-    constexpr int kListMax = 64;
-    __shared__ int s_list[kListMax];
-    __shared__ int s_cnt;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    // `first` = rmin[threadIdx.x] when the caller loaded it together with the record (have_first)
-    double mn = have_first ? first : INFINITY;
-    for (int t = threadIdx.x + (have_first ? BS : 0); t < nblk; t += BS) mn = fmin(mn, rmin[t]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mn = fmin(mn, __shfl_down(mn, off, 64));
-    if (lane == 0) s_min[wave] = mn;
-    if (threadIdx.x == 0) s_cnt = 0;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double g = s_min[0];
-        for (int w = 1; w < BS / 64; ++w) g = fmin(g, s_min[w]);
-        s_bcast = g;
-    }
-    __syncthreads();
-    const double gmin = s_bcast;
-    if (gmin == INFINITY) {
-        if (threadIdx.x == 0) rec->outcome = DEV_NO_ROW;
-        return;
-    }
-    const double bound = gmin + tol.tie * fmax(1.0, fabs(gmin));
-    for (int t = threadIdx.x; t < nblk; t += BS) {
-        if (!(rmin[t] <= bound)) continue;
-        const int pos = atomicAdd(&s_cnt, 1);
-        if (pos < kListMax) s_list[pos] = t;
-    }
-    __syncthreads();
-    const int listed = s_cnt;
-    const bool use_list = listed <= kListMax;
-    const int total = (use_list ? listed : nblk) * rpb;
-    tie_key_t best_key = kNoTieKey;
-    int best_row = -1;
-    for (int idx = threadIdx.x; idx < total; idx += BS) {
-        const int t = use_list ? s_list[idx / rpb] : idx / rpb;
-        const int i = t * rpb + idx % rpb;
-        if (i >= m) continue;
-        const double a = alpha[i];
-        double bi = b[i];
-        if (bi <= tol.zero) bi = 0.0;   // also clamps a b_i that rounding pushed below 0: no negative step
-        if (a > tol.pivot && bi / a <= bound) {
-            const tie_key_t key = tie_key(a, basis_indices[i], tol.ratio_rule);
-            if (key < best_key) { best_key = key; best_row = i; }
-        }
-    }
-    ratio_commit<BS>(best_key, best_row, alpha, b, du, p, rec, tol.ratio_rule != 0, tol.pivot_guard ? m : 0, tol.guard_rel);
-}
-
-// The same choice without the bookkeeping: every thread of the workgroup returns with (row, leaving column), row = -1 when
-// no row qualifies.  For launches in which every workgroup needs the pivot row (k_tab_ratio_update_all).
+// Ratio test of a workgroup of BS threads from the minimum ratio of every block of `rpb` rows (`rmin`, nblk
+// entries, written by the kernel that formed alpha): the global minimum is the minimum of the block minima, and
+// a row inside the tie band lives in a block whose own minimum is inside the band, so only those blocks' rows
+// (usually one or two blocks) are read again.  Same choice as ratio_body.  Every thread of the workgroup returns with
+// (row, leaving column), row = -1 when no row qualifies; nothing is written.
+// `first` = rmin[threadIdx.x] when the caller loaded it together with the record (have_first)
 template <int BS>
 __device__ __forceinline__ void ratio_blocks_pick(const double* alpha, const double* b, const int32_t* basis_indices, int m,
                                                   const Tolerances& tol, const double* rmin, int nblk, int* row_out, int* leave_out,
@@ -416,7 +481,6 @@ __device__ __forceinline__ void ratio_blocks_pick(const double* alpha, const dou
     __shared__ tie_key_t s_cl[BS / 64];
     __shared__ int s_cr[BS / 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    // `first` = rmin[threadIdx.x] when the caller loaded it together with the record (have_first)
     double mn = have_first ? first : INFINITY;
     for (int t = threadIdx.x + (have_first ? BS : 0); t < nblk; t += BS) mn = fmin(mn, rmin[t]);
 #pragma unroll
@@ -452,7 +516,7 @@ __device__ __forceinline__ void ratio_blocks_pick(const double* alpha, const dou
         double bi = b[i];
         int lv = basis_indices[i];                     // with alpha and b: one round trip, not two
         asm volatile("" : "+v"(lv));
-        if (bi <= tol.zero) bi = 0.0;
+        if (bi <= tol.zero) bi = 0.0;   // also clamps a b_i that rounding pushed below 0: no negative step
         if (a > tol.pivot && bi / a <= bound) {
             const tie_key_t key = tie_key(a, lv, tol.ratio_rule);
             if (key < best_key) { best_key = key; best_row = i; }
@@ -460,6 +524,22 @@ __device__ __forceinline__ void ratio_blocks_pick(const double* alpha, const dou
     }
     tie_reduce<BS>(best_key, best_row, s_cl, s_cr, tol.ratio_rule != 0);
     *row_out = best_row; *leave_out = tie_key_leaving(best_key);
+}
+
+// The same as one whole step of a single-workgroup launch: the choice, then "no row" or the record and the block bookkeeping.
+// `p` = rec->n_eta read by the caller.
+template <int BS>
+__device__ __forceinline__ void ratio_blocks_body(const double* alpha, const double* b, const int32_t* basis_indices, int m,
+                                                  const Tolerances& tol, const DeferredUpdate& du, const double* rmin, int nblk,
+                                                  int p, PivotRecord* rec, double first = INFINITY, bool have_first = false,
+                                                  int rpb = kThreads) {
+    int r, leaving;
+    ratio_blocks_pick<BS>(alpha, b, basis_indices, m, tol, rmin, nblk, &r, &leaving, first, have_first, rpb);
+    if (r < 0) {
+        if (threadIdx.x == 0) rec->outcome = DEV_NO_ROW;
+        return;
+    }
+    ratio_commit_row<BS>(r, leaving, alpha, b, du, p, rec, tol.pivot_guard ? m : 0, tol.guard_rel);
 }
 
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }

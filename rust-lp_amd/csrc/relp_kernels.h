@@ -286,9 +286,6 @@ int32_t price_virtual_blocks(const ColumnTable& ct);
 // reduce `count` partials, record q / d_q, and build aq (= k_select_column + k_build_column)
 void launch_select_partials(SelectPartials sp, int32_t count, const double* d, const double* A, int64_t ld_a,
                             const ColumnTable& ct, int32_t m, double* aq, PivotRecord* rec, hipStream_t s);
-// ratio test followed by the deferred-update bookkeeping of k_eta_prepare (du.kmax = 0: ratio only)
-void launch_ratio_eta(const double* alpha, const double* b, const int32_t* basis_indices, int32_t m, Tolerances tol,
-                      const DeferredUpdate& du, PivotRecord* rec, hipStream_t s);
 // PRICE, artificial + virtual columns
 void launch_price_virtual(const ColumnTable& ct, const double* minus_pi, double* d, int32_t cost_mode,
                           const PivotRecord* rec, hipStream_t s);
@@ -335,7 +332,8 @@ void launch_apply_w(const DeferredUpdate& du, int32_t m, const double* v, double
                     hipStream_t s);
 // FTRAN / alpha = v + W (S'v) that also leave the minimum ratio b_i / alpha_i of every block of rows (8 rows per
 // k_ftran workgroup, 256 per k_apply_w workgroup), and the ratio test that starts from those minima (same result
-// as launch_ratio / launch_ratio_eta; re-reads only the blocks inside the tie band).  Unsharded engines.
+// as launch_ratio, followed by the bookkeeping of launch_eta_prepare when du.kmax > 0; re-reads only the blocks inside the tie
+// band).  Unsharded engines.
 int32_t ftran_rows_per_block();
 void launch_ftran_rmin(const double* Binv, int64_t ld_b, int32_t m, const double* aq, double* out, const double* b,
                        Tolerances tol, double* rmin, const PivotRecord* rec, hipStream_t s);
@@ -397,23 +395,17 @@ void launch_tab_row_update(const TableauView& tv, const DeferredUpdate& du, Sele
 // b, -obj, basis_indices, in_basis, trace, iteration counter (no -pi: it is read off d)
 void launch_tab_update_vectors(int32_t m, const double* alpha, double* b, int32_t* basis_indices, uint8_t* in_basis,
                                int32_t* trace, int64_t trace_cap, PivotRecord* rec, hipStream_t s);
-// launch_update_w + launch_tab_update_vectors in one launch
-void launch_tab_update_w_vectors(const DeferredUpdate& du, int32_t m, const double* alpha, double* b,
-                                 int32_t* basis_indices, uint8_t* in_basis, int32_t* trace, int64_t trace_cap,
-                                 PivotRecord* rec, hipStream_t s);
-// launch_tab_select + launch_tab_column in one launch (every workgroup reduces the partials itself)
-void launch_tab_select_column(const TableauView& tv, const DeferredUpdate& du, SelectPartials sp, int32_t count,
-                              double* alpha, PivotRecord* rec, hipStream_t s);
-// single-GPU loop: also leaves the minimum ratio of every block of 256 rows in `rmin`, and the ratio test that
-// starts from those minima (re-reads only the row blocks inside the tie band)
+// launch_tab_select + launch_tab_column in one launch (every workgroup reduces the partials itself) that also leaves the
+// minimum ratio of every block of 256 rows in `rmin` (single-GPU loop), and the ratio test that starts from those minima
+// (re-reads only the row blocks inside the tie band)
 void launch_tab_select_column_rmin(const TableauView& tv, const DeferredUpdate& du, SelectPartials sp, int32_t count,
                                    double* alpha, const double* b, Tolerances tol, double* rmin, PivotRecord* rec,
                                    hipStream_t s, const double* shadow = nullptr, int32_t* shadow_meta = nullptr);
 void launch_ratio_blocks(const double* alpha, const double* b, const int32_t* basis_indices, int32_t m, Tolerances tol,
                          const DeferredUpdate& du, const double* rmin, PivotRecord* rec, hipStream_t s);
-// sharded engines: this rank's candidate message [key, j, d_j, alpha (m), minimum ratio per block of 256 rows
-// (cdiv(m, 256))] instead of the record, and the choice among the gathered messages + ratio test from the
-// winner's block minima
+// sharded engines: the same launch with this rank's candidate message [key, j, d_j, alpha (m), minimum ratio per block of
+// 256 rows (cdiv(m, 256))] written instead of the record, and the choice among the gathered messages + ratio test from the
+// winner's block minima + block bookkeeping in one launch
 void launch_tab_select_column_msg(const TableauView& tv, const DeferredUpdate& du, SelectPartials sp, int32_t count,
                                   double* msg, const double* b, Tolerances tol, PivotRecord* rec, hipStream_t s,
                                   const double* shadow = nullptr, int32_t* shadow_meta = nullptr);
@@ -425,11 +417,7 @@ void launch_tab_select_candidate_ratio(const double* msgs, int32_t count, int64_
 // replace the variable basic in `row` at zero level
 void launch_tab_zero_level_scan(const TableauView& tv, const DeferredUpdate& du, SelectPartials sp, int32_t row,
                                 int32_t nr_artificial, Tolerances tol, const PivotRecord* rec, hipStream_t s);
-// winner among the gathered candidates + ratio test + block bookkeeping in one launch (tableau engine)
-void launch_select_candidate_ratio(const double* msgs, int32_t count, int64_t msg_len, int32_t m, double* alpha,
-                                   const double* b, const int32_t* basis_indices, int32_t rule, Tolerances tol,
-                                   const DeferredUpdate& du, PivotRecord* rec, hipStream_t s);
-// launch_tab_row_update + launch_tab_update_w_vectors in one launch (disjoint workgroup ranges)
+// launch_tab_row_update, and launch_update_w + launch_tab_update_vectors for the rows, in one launch (disjoint workgroup ranges)
 void launch_tab_update_all(const TableauView& tv, const DeferredUpdate& du, SelectPartials sp, int32_t m,
                            const double* alpha, double* b, int32_t* basis_indices, uint8_t* in_basis, int32_t* trace,
                            int64_t trace_cap, PivotRecord* rec, hipStream_t s);

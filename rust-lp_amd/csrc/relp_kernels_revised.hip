@@ -96,7 +96,6 @@ __global__ __launch_bounds__(kSingleBlock) void k_select_partials(SelectPartials
                                                                   DeviceCSC csc, ColumnTable ct, int m,
                                                                   double* __restrict__ aq, PivotRecord* rec) {
     if (rec->outcome != DEV_RUNNING) return;
-    __shared__ double s_k1[kSingleBlock / 64];
     __shared__ int s_j[kSingleBlock / 64];
     __shared__ int s_q;
     double k1 = INFINITY;
@@ -106,25 +105,8 @@ __global__ __launch_bounds__(kSingleBlock) void k_select_partials(SelectPartials
         const int j = sp.j[t];
         if (key < k1 || (key == k1 && j < bj)) { k1 = key; bj = j; }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double ok = __shfl_down(k1, off, 64);
-        const int oj = __shfl_down(bj, off, 64);
-        if (ok < k1 || (ok == k1 && oj < bj)) { k1 = ok; bj = oj; }
-    }
+    block_min_key<kSingleBlock>(k1, bj);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) { s_k1[wave] = k1; s_j[wave] = bj; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < kSingleBlock / 64; ++w)
-            if (s_k1[w] < k1 || (s_k1[w] == k1 && s_j[w] < bj)) { k1 = s_k1[w]; bj = s_j[w]; }
-        s_k1[0] = k1;
-        s_j[0] = bj;
-    }
-    __syncthreads();
-    k1 = s_k1[0];
-    bj = s_j[0];
-    __syncthreads();
     if (bj != 0x7fffffff && sp.rule == 2 && sp.tol_tie > 0.0) {
         // Dantzig ties: lowest index among the columns within the tie band of the minimum.  A column
         // inside the band lives in a workgroup whose own minimum is inside the band, so only those
@@ -291,7 +273,6 @@ __global__ __launch_bounds__(kSingleBlock) void k_select_column(
     const double* __restrict__ d, const uint8_t* __restrict__ in_basis, int n, int rule, double tol_cost,
     double tol_tie, PivotRecord* rec) {
     if (rec->outcome != DEV_RUNNING) return;
-    __shared__ double s_k1[kSingleBlock / 64];
     __shared__ int s_j[kSingleBlock / 64];
     const int last = (rule == 1) ? rec->last_selected : -1;
     double k1 = INFINITY;
@@ -307,25 +288,8 @@ __global__ __launch_bounds__(kSingleBlock) void k_select_column(
             if (key < k1 || (key == k1 && j < bj)) { k1 = key; bj = j; }
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double ok = __shfl_down(k1, off, 64);
-        const int oj = __shfl_down(bj, off, 64);
-        if (ok < k1 || (ok == k1 && oj < bj)) { k1 = ok; bj = oj; }
-    }
+    block_min_key<kSingleBlock>(k1, bj);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) { s_k1[wave] = k1; s_j[wave] = bj; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < kSingleBlock / 64; ++w) {
-            if (s_k1[w] < k1 || (s_k1[w] == k1 && s_j[w] < bj)) { k1 = s_k1[w]; bj = s_j[w]; }
-        }
-        s_j[0] = bj;
-        s_k1[0] = k1;
-    }
-    __syncthreads();
-    bj = s_j[0];
-    k1 = s_k1[0];
     if (bj != 0x7fffffff && rule == 2 && tol_tie > 0.0) {
         // Dantzig ties: lowest index among the columns within the tie band of the minimum
         const double bound = k1 + tol_tie * fmax(1.0, fabs(k1));
@@ -461,27 +425,12 @@ __global__ void k_update_vectors(int m, const double* __restrict__ alpha, const 
     const double br = rec->b_r / rec->alpha_r;
     if (i < m) {
         minus_pi[i] = fma(-d_q, rho[i], minus_pi[i]);
-        if (i == r) b[i] = br;
-        else {
-            const double a = alpha[i];
-            if (a != 0.0) b[i] = fma(-a, br, b[i]);
-        }
+        b[i] = pivot_b(alpha[i], b[i], br, i == r);
     }
     if (i == 0) {
-        const int q = rec->q, leaving = rec->leaving;
-        rec->minus_objective = fma(-d_q, br, rec->minus_objective);
-        basis_indices[r] = q;
-        if (leaving < kWrappedArtificialBase) in_basis[leaving] = 0;   // a wrapped artificial has no flag
-        in_basis[q] = 1;
-        const long long it = rec->iterations;
-        if (trace && it < trace_cap) {
-            trace[0 * trace_cap + it] = rec->phase;
-            trace[1 * trace_cap + it] = q;
-            trace[2 * trace_cap + it] = r;
-            trace[3 * trace_cap + it] = leaving;
-        }
-        if (br == 0.0) rec->degenerate += 1;            // ratio 0: the basis changes, the vertex does not
-        rec->iterations = it + 1;
+        basis_indices[r] = rec->q;
+        pivot_bookkeeping(rec->phase, rec->iterations, rec->minus_objective, d_q, br, rec->q, r, rec->leaving, in_basis, trace,
+                          trace_cap, rec);
     }
 }
 
@@ -542,27 +491,11 @@ __global__ __launch_bounds__(kThreads) void k_update_inverse_vectors(double* __r
     const int r = R.r;
     for (int i = blockIdx.x * kThreads + threadIdx.x; i < m; i += gridDim.x * kThreads) {
         minus_pi[i] = fma(-d_q, rho[i], minus_pi[i]);
-        if (i == r) b[i] = br;
-        else {
-            const double a = alpha[i];
-            if (a != 0.0) b[i] = fma(-a, br, b[i]);
-        }
+        b[i] = pivot_b(alpha[i], b[i], br, i == r);
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-        const int q = R.q, leaving = R.leaving;
-        rec->minus_objective = fma(-d_q, br, R.minus_objective);
-        basis_indices[r] = q;
-        if (leaving < kWrappedArtificialBase) in_basis[leaving] = 0;   // a wrapped artificial has no flag
-        in_basis[q] = 1;
-        const long long it = R.iterations;
-        if (trace && it < trace_cap) {
-            trace[0 * trace_cap + it] = R.phase;
-            trace[1 * trace_cap + it] = q;
-            trace[2 * trace_cap + it] = r;
-            trace[3 * trace_cap + it] = leaving;
-        }
-        if (br == 0.0) rec->degenerate += 1;            // ratio 0: the basis changes, the vertex does not
-        rec->iterations = it + 1;
+        basis_indices[r] = R.q;
+        pivot_bookkeeping(R.phase, R.iterations, R.minus_objective, d_q, br, R.q, r, R.leaving, in_basis, trace, trace_cap, rec);
     }
 }
 
@@ -845,75 +778,14 @@ __global__ __launch_bounds__(kSingleBlock) void k_select_candidate(const double*
     if (rec->outcome != DEV_RUNNING) return;
     __shared__ int s_win;
     if (threadIdx.x == 0) {
-        int win = -1; double k1 = INFINITY; double kj = 0.0;
-        for (int g = 0; g < count; ++g) {
-            const double a = msgs[g * msg_len + 0], j = msgs[g * msg_len + 1];
-            if (a < k1 || (a == k1 && win >= 0 && j < kj)) { k1 = a; kj = j; win = g; }
-        }
-        if (win >= 0 && rule == 2 && tol_tie > 0.0) {
-            // Dantzig ties across ranks: every rank sent (its minimum, its lowest index within the band
-            // of that minimum); the lowest index among the ranks inside the global band wins
-            const double bound = k1 + tol_tie * fmax(1.0, fabs(k1));
-            for (int g = 0; g < count; ++g) {
-                const double a = msgs[g * msg_len + 0], j = msgs[g * msg_len + 1];
-                if (a <= bound && j < kj) { kj = j; win = g; }
-            }
-        }
+        const int win = candidate_winner(msgs, msgs + 1, msg_len, count, rule, tol_tie);
         s_win = win;
-        if (win < 0) {
-            rec->outcome = DEV_NO_CANDIDATE;
-            if (rule == 1) rec->last_selected = -1;
-        } else {
-            rec->q = (int)msgs[win * msg_len + 1];
-            rec->d_q = msgs[win * msg_len + 2];
-            if (rule == 1) rec->last_selected = rec->q;
-        }
+        record_candidate(rec, rule, win, win < 0 ? 0 : (int)msgs[win * msg_len + 1], win < 0 ? 0.0 : msgs[win * msg_len + 2]);
     }
     __syncthreads();
     const int win = s_win;
     if (win < 0) return;
     for (int i = threadIdx.x; i < m; i += kSingleBlock) aq[i] = msgs[win * msg_len + 3 + i];
-}
-
-// The winner among the gathered candidates, its tableau column, and the ratio test on it in one
-// single-workgroup launch (tableau engine: the candidate's payload IS alpha).
-__global__ __launch_bounds__(kSingleBlock) void k_select_candidate_ratio(const double* __restrict__ msgs, int count,
-                                                                         int64_t msg_len, int m, double* alpha,
-                                                                         const double* b, const int32_t* basis_indices,
-                                                                         int rule, Tolerances tol, DeferredUpdate du,
-                                                                         PivotRecord* rec) {
-    const int outcome = rec->outcome, p = rec->n_eta;
-    if (outcome != DEV_RUNNING) return;
-    __shared__ int s_win;
-    if (threadIdx.x == 0) {
-        int win = -1; double k1 = INFINITY; double kj = 0.0;
-        for (int g = 0; g < count; ++g) {
-            const double a = msgs[g * msg_len + 0], j = msgs[g * msg_len + 1];
-            if (a < k1 || (a == k1 && win >= 0 && j < kj)) { k1 = a; kj = j; win = g; }
-        }
-        if (win >= 0 && rule == 2 && tol.tie > 0.0) {
-            const double bound = k1 + tol.tie * fmax(1.0, fabs(k1));
-            for (int g = 0; g < count; ++g) {
-                const double a = msgs[g * msg_len + 0], j = msgs[g * msg_len + 1];
-                if (a <= bound && j < kj) { kj = j; win = g; }
-            }
-        }
-        s_win = win;
-        if (win < 0) {
-            rec->outcome = DEV_NO_CANDIDATE;
-            if (rule == 1) rec->last_selected = -1;
-        } else {
-            rec->q = (int)msgs[win * msg_len + 1];
-            rec->d_q = msgs[win * msg_len + 2];
-            if (rule == 1) rec->last_selected = rec->q;
-        }
-    }
-    __syncthreads();
-    const int win = s_win;
-    if (win < 0) return;
-    for (int i = threadIdx.x; i < m; i += kSingleBlock) alpha[i] = msgs[win * msg_len + 3 + i];
-    __syncthreads();                                   // alpha was written by this workgroup: visible to it
-    ratio_body<kSingleBlock, 16>(alpha, b, basis_indices, m, tol, du, p, rec);
 }
 
 __global__ void k_gather_alpha(const double* __restrict__ slices, int count, int stride, int m,
@@ -992,11 +864,6 @@ void launch_select_partials(SelectPartials sp, int32_t count, const double* d, c
                             const ColumnTable& ct, int32_t m, double* aq, PivotRecord* rec, hipStream_t s) {
     hipLaunchKernelGGL(k_select_partials, dim3(1), dim3(kSingleBlock), 0, s, sp, count, d, A, ld_a, DeviceCSC{}, ct, m, aq,
                        rec);
-}
-
-void launch_ratio_eta(const double* alpha, const double* b, const int32_t* basis_indices, int32_t m, Tolerances tol,
-                      const DeferredUpdate& du, PivotRecord* rec, hipStream_t s) {
-    hipLaunchKernelGGL(k_ratio, dim3(1), dim3(kSingleBlock), 0, s, alpha, b, basis_indices, m, tol, du, rec);
 }
 
 void launch_select_column(const double* d, const uint8_t* in_basis, int32_t n, int32_t rule, double tol_cost,
@@ -1152,13 +1019,6 @@ void launch_build_column_csc(const DeviceCSC& csc, const ColumnTable& ct, int32_
 void launch_pack_candidate(const double* aq, int32_t m, double* msg, PivotRecord* rec, hipStream_t s) {
     hipLaunchKernelGGL(k_pack_candidate, dim3(cdiv(m, 256)), dim3(256), 0, s, aq, m, msg, rec);
     hipLaunchKernelGGL(k_clear_no_candidate, dim3(1), dim3(1), 0, s, rec);
-}
-
-void launch_select_candidate_ratio(const double* msgs, int32_t count, int64_t msg_len, int32_t m, double* alpha,
-                                   const double* b, const int32_t* basis_indices, int32_t rule, Tolerances tol,
-                                   const DeferredUpdate& du, PivotRecord* rec, hipStream_t s) {
-    hipLaunchKernelGGL(k_select_candidate_ratio, dim3(1), dim3(kSingleBlock), 0, s, msgs, count, msg_len, m, alpha, b,
-                       basis_indices, rule, tol, du, rec);
 }
 
 void launch_select_candidate(const double* msgs, int32_t count, int64_t msg_len, int32_t m, double* aq,

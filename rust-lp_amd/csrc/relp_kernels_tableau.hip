@@ -112,61 +112,10 @@ __global__ __launch_bounds__(kThreads) void k_tab_scan(TableauView tv, SelectPar
 __global__ __launch_bounds__(kSingleBlock) void k_tab_select(TableauView tv, SelectPartials sp, int count,
                                                              PivotRecord* rec) {
     if (rec->outcome != DEV_RUNNING) return;
-    __shared__ double s_k1[kSingleBlock / 64];
-    __shared__ int s_j[kSingleBlock / 64];
     double k1 = INFINITY;
     int bj = 0x7fffffff;
-    for (int t = threadIdx.x; t < count; t += kSingleBlock) {
-        const double key = sp.k1[t];
-        const int j = sp.j[t];
-        if (key < k1 || (key == k1 && j < bj)) { k1 = key; bj = j; }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double ok = __shfl_down(k1, off, 64);
-        const int oj = __shfl_down(bj, off, 64);
-        if (ok < k1 || (ok == k1 && oj < bj)) { k1 = ok; bj = oj; }
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) { s_k1[wave] = k1; s_j[wave] = bj; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < kSingleBlock / 64; ++w)
-            if (s_k1[w] < k1 || (s_k1[w] == k1 && s_j[w] < bj)) { k1 = s_k1[w]; bj = s_j[w]; }
-        s_k1[0] = k1;
-        s_j[0] = bj;
-    }
-    __syncthreads();
-    k1 = s_k1[0];
-    bj = s_j[0];
-    __syncthreads();
-    if (bj != 0x7fffffff && sp.rule == 2 && sp.tol_tie > 0.0) {
-        // Dantzig ties (pivot_rule.rs:118): lowest index inside the band; only slots whose minimum is
-        // inside the band can hold such a column
-        const double bound = k1 + sp.tol_tie * fmax(1.0, fabs(k1));
-        int lowest = 0x7fffffff;
-        // four groups of 256 threads walk the slots; a slot inside the band is re-read by its group,
-        // one column per thread
-        const int grp = threadIdx.x >> 8, u = threadIdx.x & 255;
-        for (int t = grp; t < count; t += kSingleBlock / kThreads) {
-            if (!(sp.k1[t] <= bound)) continue;
-            const int c = tv.c_lo + t * kThreads + u;
-            const int j = c - tv.col_off;
-            if (c < tv.c_hi && j >= 0 && j < tv.n) {
-                const double v = tv.d[c];
-                if (!sp.in_basis[j] && v < -sp.tol_cost && v <= bound && j < lowest) lowest = j;
-            }
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) lowest = min(lowest, __shfl_down(lowest, off, 64));
-        if (lane == 0) s_j[wave] = lowest;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            int low = 0x7fffffff;
-            for (int w = 0; w < kSingleBlock / 64; ++w) low = min(low, s_j[w]);
-            bj = low;
-        }
-    }
+    if ((int)threadIdx.x < count) { k1 = sp.k1[threadIdx.x]; bj = sp.j[threadIdx.x]; }
+    tab_select_entering<kSingleBlock>(tv, sp, count, k1, bj);
     if (threadIdx.x == 0) {
         if (bj == 0x7fffffff) {
             rec->outcome = DEV_NO_CANDIDATE;
@@ -277,38 +226,12 @@ __device__ __forceinline__ void tab_update_w_vectors_body(const DeferredUpdate& 
         tab_update_w_row<B>(du, i, u, s_wr2, 0, p_old);
         double* tgt = du.W + (int64_t)jt * du.ld + i;
         if (jt < p_old) *tgt += u; else *tgt = u;
-        if (i == r) b[i] = br;
-        else if (a != 0.0) b[i] = fma(-a, br, b_i);
+        b[i] = pivot_b(a, b_i, br, i == r);
     }
     if (i == 0) {
-        const int q = R.q, leaving = R.leaving;
-        rec->minus_objective = fma(-R.d_q, br, R.minus_objective);
-        basis_indices[r] = q;
-        if (leaving < kWrappedArtificialBase) in_basis[leaving] = 0;   // a wrapped artificial has no flag
-        in_basis[q] = 1;
-        const long long it = R.iterations;
-        if (trace && it < trace_cap) {
-            trace[0 * trace_cap + it] = R.phase;
-            trace[1 * trace_cap + it] = q;
-            trace[2 * trace_cap + it] = r;
-            trace[3 * trace_cap + it] = leaving;
-        }
-        if (br == 0.0) rec->degenerate += 1;            // ratio 0: the basis changes, the vertex does not
-        rec->iterations = it + 1;
+        basis_indices[r] = R.q;
+        pivot_bookkeeping(R.phase, R.iterations, R.minus_objective, R.d_q, br, R.q, r, R.leaving, in_basis, trace, trace_cap, rec);
     }
-}
-
-template <int B>
-__global__ __launch_bounds__(kThreads) void k_tab_update_w_vectors(DeferredUpdate du, int m,
-                                                                   const double* __restrict__ alpha,
-                                                                   double* __restrict__ b,
-                                                                   int32_t* __restrict__ basis_indices,
-                                                                   uint8_t* __restrict__ in_basis,
-                                                                   int32_t* __restrict__ trace, int64_t trace_cap,
-                                                                   PivotRecord* rec) {
-    const PivotRecord R = *rec;
-    if (R.outcome != DEV_RUNNING) return;
-    tab_update_w_vectors_body<B>(du, m, alpha, b, basis_indices, in_basis, trace, trace_cap, R, rec, blockIdx.x);
 }
 
 // Both halves of the update in ONE launch: workgroups [0, nb_row) update the tableau row / reduced
@@ -364,38 +287,16 @@ __global__ __launch_bounds__(kThreads) void k_tab_ratio_update_all(TableauView t
     if (msgs) {
         // sharded loop: the entering column is the winner among the gathered candidates [key, j, d_j, alpha (m), block
         // minima of the ratios]; every workgroup picks it with the rules of k_tab_select_candidate_ratio
-        constexpr int kMaxRanks = 64;
-        __shared__ double s_key[kMaxRanks], s_idx[kMaxRanks], s_dq[kMaxRanks];
-        __shared__ int s_win;
-        for (int g = threadIdx.x; g < count && g < kMaxRanks; g += kThreads) {
-            s_key[g] = msgs[g * msg_len + 0]; s_idx[g] = msgs[g * msg_len + 1]; s_dq[g] = msgs[g * msg_len + 2];
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            int win = -1; double k1 = INFINITY; double kj = 0.0;
-            for (int g = 0; g < count; ++g) {
-                const double a = s_key[g], j = s_idx[g];
-                if (a < k1 || (a == k1 && win >= 0 && j < kj)) { k1 = a; kj = j; win = g; }
-            }
-            if (win >= 0 && rule == 2 && tol.tie > 0.0) {
-                const double bound = k1 + tol.tie * fmax(1.0, fabs(k1));
-                for (int g = 0; g < count; ++g)
-                    if (s_key[g] <= bound && s_idx[g] < kj) { kj = s_idx[g]; win = g; }
-            }
-            s_win = win;
-        }
-        __syncthreads();
-        const int win = s_win;
+        int q_win = 0;
+        double d_win = 0.0;
+        const int win = candidate_winner_staged(msgs, count, msg_len, rule, tol.tie, &q_win, &d_win);
         if (win < 0) {
             if (mine) { b_out[i] = b_in[i]; basis_out[i] = basis_in[i]; }
-            if (lead && wblock == 0 && threadIdx.x == 0) {
-                rec->outcome = DEV_NO_CANDIDATE;
-                if (rule == 1) rec->last_selected = -1;
-            }
+            if (lead && wblock == 0 && threadIdx.x == 0) record_candidate(rec, rule, -1, 0, 0.0);
             return;
         }
-        R.q = (int)s_idx[win];
-        R.d_q = s_dq[win];
+        R.q = q_win;
+        R.d_q = d_win;
         if (rule == 1) R.last_selected = R.q;                      // (what the row update's selection keys start from)
         alpha = msgs + win * msg_len + 3;
         rmin = alpha + m;
@@ -454,26 +355,15 @@ __global__ __launch_bounds__(kThreads) void k_tab_ratio_update_all(TableauView t
             shadow_meta[0] = r;
             shadow_meta[1] = jt < p_old ? p_old : p_old + 1;
         }
-        b_out[i] = (i == r) ? br : (a != 0.0 ? fma(-a, br, b_i) : b_i);
+        b_out[i] = pivot_b(a, b_i, br, i == r);
         basis_out[i] = (i == r) ? q : basis_in[i];
     }
     if (i == 0) {
-        if (msgs) { rec->q = q; rec->d_q = R.d_q; if (rule == 1) rec->last_selected = q; }
+        if (msgs) record_candidate(rec, rule, 0, q, R.d_q);
         rec->r = r; rec->leaving = leaving; rec->alpha_r = alpha_r; rec->b_r = b_r;
         rec->n_eta_old = p_old; rec->eta_target = jt;
         if (jt >= p_old) { du.S[p_old] = r; du.pos_of_row[r] = p_old; rec->n_eta = p_old + 1; }
-        rec->minus_objective = fma(-R.d_q, br, R.minus_objective);
-        if (leaving < kWrappedArtificialBase) in_basis[leaving] = 0;   // a wrapped artificial has no flag
-        in_basis[q] = 1;
-        const long long it = R.iterations;
-        if (trace && it < trace_cap) {
-            trace[0 * trace_cap + it] = R.phase;
-            trace[1 * trace_cap + it] = q;
-            trace[2 * trace_cap + it] = r;
-            trace[3 * trace_cap + it] = leaving;
-        }
-        if (br == 0.0) rec->degenerate += 1;
-        rec->iterations = it + 1;
+        pivot_bookkeeping(R.phase, R.iterations, R.minus_objective, R.d_q, br, q, r, leaving, in_basis, trace, trace_cap, rec);
     }
 }
 
@@ -517,66 +407,9 @@ __global__ __launch_bounds__(kThreads) void k_tab_select_column(TableauView tv, 
     const int i = blockIdx.x * kThreads + threadIdx.x;
     const double b_i = (rmin && i < tv.m) ? b[i] : 0.0;
     if (outcome != DEV_RUNNING) return;
-    __shared__ double s_k1[kThreads / 64];
-    __shared__ int s_j[kThreads / 64];
     __shared__ double s_vs[kMaxEta];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int t = threadIdx.x + kThreads; t < count; t += kThreads) {
-        const double key = sp.k1[t];
-        const int j = sp.j[t];
-        if (key < k1 || (key == k1 && j < bj)) { k1 = key; bj = j; }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double ok = __shfl_down(k1, off, 64);
-        const int oj = __shfl_down(bj, off, 64);
-        if (ok < k1 || (ok == k1 && oj < bj)) { k1 = ok; bj = oj; }
-    }
-    if (lane == 0) { s_k1[wave] = k1; s_j[wave] = bj; }
-    __syncthreads();
-    k1 = s_k1[0]; bj = s_j[0];
-    for (int w = 1; w < kThreads / 64; ++w)
-        if (s_k1[w] < k1 || (s_k1[w] == k1 && s_j[w] < bj)) { k1 = s_k1[w]; bj = s_j[w]; }
-    __syncthreads();
-    if (bj != 0x7fffffff && sp.rule == 2 && sp.tol_tie > 0.0) {
-        // Dantzig tie band (see k_tab_select): slots inside the band are re-read, one column per thread
-        const double bound = k1 + sp.tol_tie * fmax(1.0, fabs(k1));
-        int lowest = 0x7fffffff;
-        // the slots whose own minimum is inside the band (normally one or two) are listed first, so the
-        // scan does not walk all `count` slots one dependent load after the other
-        constexpr int kListMax = 32;
-        __shared__ int s_list[kListMax];
-        __shared__ int s_cnt;
-        if (threadIdx.x == 0) s_cnt = 0;
-        __syncthreads();
-        for (int t = threadIdx.x; t < count; t += kThreads) {
-            if (!(sp.k1[t] <= bound)) continue;
-            const int pos = atomicAdd(&s_cnt, 1);
-            if (pos < kListMax) s_list[pos] = t;
-        }
-        __syncthreads();
-        const int listed = s_cnt;
-        auto scan_slot = [&](int t) {
-            const int c = tv.c_lo + t * kThreads + threadIdx.x;
-            const int j = c - tv.col_off;
-            if (c < tv.c_hi && j >= 0 && j < tv.n) {
-                const double v = tv.d[c];
-                if (!sp.in_basis[j] && v < -sp.tol_cost && v <= bound && j < lowest) lowest = j;
-            }
-        };
-        if (listed <= kListMax) {
-            for (int i = 0; i < listed; ++i) scan_slot(s_list[i]);
-        } else {
-            for (int t = 0; t < count; ++t)
-                if (sp.k1[t] <= bound) scan_slot(t);
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) lowest = min(lowest, __shfl_down(lowest, off, 64));
-        if (lane == 0) s_j[wave] = lowest;
-        __syncthreads();
-        bj = s_j[0];
-        for (int w = 1; w < kThreads / 64; ++w) bj = min(bj, s_j[w]);
-    }
+    __shared__ double s_min[kThreads / 64];
+    tab_select_entering<kThreads>(tv, sp, count, k1, bj);
     if (bj == 0x7fffffff) {
         if (msg) {
             if (i < tv.m) alpha[i] = 0.0;
@@ -613,9 +446,9 @@ __global__ __launch_bounds__(kThreads) void k_tab_select_column(TableauView tv, 
     if (!rmin) return;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) ratio = fmin(ratio, __shfl_down(ratio, off, 64));
-    if (lane == 0) s_k1[wave] = ratio;
+    if ((threadIdx.x & 63) == 0) s_min[threadIdx.x >> 6] = ratio;
     __syncthreads();
-    if (threadIdx.x == 0) rmin[blockIdx.x] = fmin(fmin(s_k1[0], s_k1[1]), fmin(s_k1[2], s_k1[3]));
+    if (threadIdx.x == 0) rmin[blockIdx.x] = fmin(fmin(s_min[0], s_min[1]), fmin(s_min[2], s_min[3]));
 }
 
 // Ratio test from the per-block minima of k_tab_select_column (ratio_blocks_body): one workgroup.
@@ -640,38 +473,10 @@ __global__ __launch_bounds__(kSingleBlock) void k_tab_select_candidate_ratio(con
                                                                              int forced_row, PivotRecord* rec) {
     const int outcome = rec->outcome, p = rec->n_eta;
     if (outcome != DEV_RUNNING) return;
-    constexpr int kMaxRanks = 64;
-    __shared__ double s_key[kMaxRanks], s_idx[kMaxRanks], s_dq[kMaxRanks];
-    __shared__ int s_win;
-    for (int g = threadIdx.x; g < count && g < kMaxRanks; g += kSingleBlock) {       // all heads in one round trip
-        s_key[g] = msgs[g * msg_len + 0];
-        s_idx[g] = msgs[g * msg_len + 1];
-        s_dq[g] = msgs[g * msg_len + 2];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int win = -1; double k1 = INFINITY; double kj = 0.0;
-        for (int g = 0; g < count; ++g) {
-            const double a = s_key[g], j = s_idx[g];
-            if (a < k1 || (a == k1 && win >= 0 && j < kj)) { k1 = a; kj = j; win = g; }
-        }
-        if (win >= 0 && rule == 2 && tol.tie > 0.0) {
-            const double bound = k1 + tol.tie * fmax(1.0, fabs(k1));
-            for (int g = 0; g < count; ++g)
-                if (s_key[g] <= bound && s_idx[g] < kj) { kj = s_idx[g]; win = g; }
-        }
-        s_win = win;
-        if (win < 0) {
-            rec->outcome = DEV_NO_CANDIDATE;
-            if (rule == 1) rec->last_selected = -1;
-        } else {
-            rec->q = (int)s_idx[win];
-            rec->d_q = s_dq[win];
-            if (rule == 1) rec->last_selected = (int)s_idx[win];
-        }
-    }
-    __syncthreads();
-    const int win = s_win;
+    int q = 0;
+    double d_q = 0.0;
+    const int win = candidate_winner_staged(msgs, count, msg_len, rule, tol.tie, &q, &d_q);      // all heads in one round trip
+    if (threadIdx.x == 0) record_candidate(rec, rule, win, q, d_q);
     if (win < 0) return;
     const double* __restrict__ col = msgs + win * msg_len + 3;
     // the winner's block minima and its column (copied for the update launch) leave in the same round trip; the
@@ -680,7 +485,7 @@ __global__ __launch_bounds__(kSingleBlock) void k_tab_select_candidate_ratio(con
     if (forced_row >= 0) {
         // zero-level pivot in a given row (phase_one.rs:246-250): no ratio test, the variable basic there leaves
         for (int i = threadIdx.x; i < m; i += kSingleBlock) alpha[i] = col[i];
-        ratio_commit<kSingleBlock>(basis_indices[forced_row], forced_row, col, b, du, p, rec);
+        ratio_commit_row<kSingleBlock>(forced_row, basis_indices[forced_row], col, b, du, p, rec);
         return;
     }
     const double first = (int)threadIdx.x < nblk ? col[m + threadIdx.x] : INFINITY;
@@ -707,28 +512,11 @@ __global__ void k_tab_update_vectors(int m, const double* __restrict__ alpha, do
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const int r = rec->r;
     const double br = rec->b_r / rec->alpha_r;
-    if (i < m) {
-        if (i == r) b[i] = br;
-        else {
-            const double a = alpha[i];
-            if (a != 0.0) b[i] = fma(-a, br, b[i]);
-        }
-    }
+    if (i < m) b[i] = pivot_b(alpha[i], b[i], br, i == r);
     if (i == 0) {
-        const int q = rec->q, leaving = rec->leaving;
-        rec->minus_objective = fma(-rec->d_q, br, rec->minus_objective);
-        basis_indices[r] = q;
-        if (leaving < kWrappedArtificialBase) in_basis[leaving] = 0;   // a wrapped artificial has no flag
-        in_basis[q] = 1;
-        const long long it = rec->iterations;
-        if (trace && it < trace_cap) {
-            trace[0 * trace_cap + it] = rec->phase;
-            trace[1 * trace_cap + it] = q;
-            trace[2 * trace_cap + it] = r;
-            trace[3 * trace_cap + it] = leaving;
-        }
-        if (br == 0.0) rec->degenerate += 1;            // ratio 0: the basis changes, the vertex does not
-        rec->iterations = it + 1;
+        basis_indices[r] = rec->q;
+        pivot_bookkeeping(rec->phase, rec->iterations, rec->minus_objective, rec->d_q, br, rec->q, r, rec->leaving, in_basis, trace,
+                          trace_cap, rec);
     }
 }
 
@@ -1097,24 +885,6 @@ void launch_tab_update_vectors(int32_t m, const double* alpha, double* b, int32_
                                int32_t* trace, int64_t trace_cap, PivotRecord* rec, hipStream_t s) {
     hipLaunchKernelGGL(k_tab_update_vectors, dim3(cdiv(m, 256)), dim3(256), 0, s, m, alpha, b, basis_indices, in_basis,
                        trace, trace_cap, rec);
-}
-
-void launch_tab_update_w_vectors(const DeferredUpdate& du, int32_t m, const double* alpha, double* b,
-                                 int32_t* basis_indices, uint8_t* in_basis, int32_t* trace, int64_t trace_cap,
-                                 PivotRecord* rec, hipStream_t s) {
-    with_load_batch(du.batch, [&](auto B) {
-        hipLaunchKernelGGL((k_tab_update_w_vectors<decltype(B)::value>), dim3(cdiv(m, kThreads)), dim3(kThreads), 0, s, du, m, alpha, b,
-                           basis_indices, in_basis, trace, trace_cap, rec);
-    });
-}
-
-void launch_tab_select_column(const TableauView& tv, const DeferredUpdate& du, SelectPartials sp, int32_t count,
-                              double* alpha, PivotRecord* rec, hipStream_t s) {
-    with_load_batch(du.batch, [&](auto B) {
-        hipLaunchKernelGGL((k_tab_select_column<decltype(B)::value>), dim3(cdiv(tv.m, kThreads)), dim3(kThreads), 0, s, tv, du, sp, count, alpha,
-                           (double*)nullptr, (const double*)nullptr, Tolerances{}, (double*)nullptr, rec, (const double*)nullptr,
-                           (int32_t*)nullptr);
-    });
 }
 
 void launch_tab_select_column_rmin(const TableauView& tv, const DeferredUpdate& du, SelectPartials sp, int32_t count,
