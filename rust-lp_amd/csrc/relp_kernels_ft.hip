@@ -327,9 +327,64 @@ __device__ __forceinline__ double tc_chain(const double* TC, int ldt, int t, int
 // lanes per update slot when all t slots are worked on at once: 64, 32, 16 or 8 (as a shift)
 __device__ __forceinline__ int slot_lanes_shift(int t) { return t <= NT / 64 ? 6 : t <= NT / 32 ? 5 : t <= NT / 16 ? 4 : 3; }
 
-// `which`: 0 L, 1 U, 2 U', 3 L'.  first_level: levels below it hold zeros only (0 = everything).
-template <class Ctx> __device__ __forceinline__ int block_min_int(Ctx& c, int v);
+// ---- workgroup minima ------------------------------------------------------------------------------------------------------
+// Minimum over the wavefront, valid in lane 0.  double and int: lane swaps and DPP row shifts, register to register (the same
+// tree as group_sum; __shfl_down goes through the LDS crossbar, ~100 clocks a step, and a pivot has six block reductions).
+__device__ __forceinline__ double wave_min(double v) {
+    v = fmin(v, lane_plus_32(v));
+    v = fmin(v, lane_plus_16(v));
+    v = fmin(v, dpp_row_shl<0x108>(v));
+    v = fmin(v, dpp_row_shl<0x104>(v));
+    v = fmin(v, dpp_row_shl<0x102>(v));
+    v = fmin(v, dpp_row_shl<0x101>(v));
+    return v;
+}
+template <int kCtrl>
+__device__ __forceinline__ int dpp_row_shl_i32(int v) { return __builtin_amdgcn_update_dpp(0, v, kCtrl, 0xf, 0xf, true); }
+__device__ __forceinline__ int wave_min(int v) {
+    { const auto a = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false); v = min(v, (int)a[1]); }
+    { const auto a = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false); v = min(v, (int)a[1]); }
+    v = min(v, dpp_row_shl_i32<0x108>(v));
+    v = min(v, dpp_row_shl_i32<0x104>(v));
+    v = min(v, dpp_row_shl_i32<0x102>(v));
+    v = min(v, dpp_row_shl_i32<0x101>(v));
+    return v;
+}
+// 64-bit tie keys (relp_device_common.h: tie_key): only the RELP_RATIO_LARGEST_PIVOT rule comes here, the reference's rule
+// reduces 32-bit leaving columns
+__device__ __forceinline__ tie_key_t wave_min(tie_key_t v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { const tie_key_t o = __shfl_down(v, off, 64); v = o < v ? o : v; }
+    return v;
+}
+__device__ __forceinline__ double lesser(double a, double b) { return fmin(a, b); }
+__device__ __forceinline__ int lesser(int a, int b) { return min(a, b); }
+__device__ __forceinline__ tie_key_t lesser(tie_key_t a, tie_key_t b) { return b < a ? b : a; }
 
+// Workgroup minimum of one int, double or tie key per thread; result in every thread.  Through red_i (int) or red_d, with a
+// barrier before the words are written and one after.
+template <class Ctx, class T>
+__device__ __forceinline__ T block_min(Ctx& c, T v) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    T* red;
+    if constexpr (sizeof(T) == sizeof(int)) red = reinterpret_cast<T*>(c.red_i); else red = reinterpret_cast<T*>(c.red_d);
+    v = wave_min(v);
+    __syncthreads();
+    if (lane == 0) red[wave] = v;
+    __syncthreads();
+    v = red[0];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) v = lesser(v, red[w]);
+    return v;
+}
+
+// lexicographic minimum of (key, j) over the workgroup: the smallest key, then the lowest j among the threads that hold it
+template <class Ctx>
+__device__ __forceinline__ void block_min_key(Ctx& c, double& key, int& kj) {
+    const double kmin = block_min(c, key);
+    kj = block_min(c, key == kmin ? kj : 0x7fffffff);
+    key = kmin;
+}
 // Hyper-sparse start of a sweep (the reference's solves only touch what they reach: lower_upper/mod.rs:236-271, 359-374 walk a
 // BTreeMap of non-zeros): the first group of the schedule in which a non-zero of x matters (EllSchedule::reach).  One
 // coalesced pass over reach (its loads do not depend on x), one block reduction.  x must be complete (behind a barrier).
@@ -338,7 +393,7 @@ __device__ __forceinline__ int ft_first_group(Ctx& c, const int32_t* __restrict_
     int g = 0x7fffffff;
     if constexpr (Ctx::huge) {
         hs_for_each(c.bx, c.gs, 0, c.m, [&](int k) { if (c.x[k] != 0.0) g = min(g, reach[k]); });
-        return block_min_int(c, g);
+        return block_min(c, g);
     }
     for (int k0 = threadIdx.x; k0 < c.m; k0 += 4 * NT) {
         int r[4];
@@ -348,7 +403,7 @@ __device__ __forceinline__ int ft_first_group(Ctx& c, const int32_t* __restrict_
 #pragma unroll
         for (int u = 0; u < 4; ++u) if (k0 + u * NT < c.m && c.x[k0 + u * NT] != 0.0) g = min(g, r[u]);
     }
-    return block_min_int(c, g);
+    return block_min(c, g);
 }
 
 // `hyper`: derive the first level from the non-zeros of x (st.hyper selects the schedules for which that pays)
@@ -882,101 +937,464 @@ __device__ __forceinline__ void ft_scatter_column(const FtState& st, const FtPro
     __syncthreads();
 }
 
-// workgroup minimum of (key, j), lexicographic; result in every thread
-// Minimum over the wavefront, valid in lane 0: lane swaps and DPP row shifts, register to register (the same tree as
-// group_sum; __shfl_down goes through the LDS crossbar, ~100 clocks a step, and a pivot has six block reductions).
-__device__ __forceinline__ double wave_min_f64(double v) {
-    v = fmin(v, lane_plus_32(v));
-    v = fmin(v, lane_plus_16(v));
-    v = fmin(v, dpp_row_shl<0x108>(v));
-    v = fmin(v, dpp_row_shl<0x104>(v));
-    v = fmin(v, dpp_row_shl<0x102>(v));
-    v = fmin(v, dpp_row_shl<0x101>(v));
-    return v;
-}
-template <int kCtrl>
-__device__ __forceinline__ int dpp_row_shl_i32(int v) { return __builtin_amdgcn_update_dpp(0, v, kCtrl, 0xf, 0xf, true); }
-__device__ __forceinline__ int wave_min_i32(int v) {
-    { const auto a = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false); v = min(v, (int)a[1]); }
-    { const auto a = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false); v = min(v, (int)a[1]); }
-    v = min(v, dpp_row_shl_i32<0x108>(v));
-    v = min(v, dpp_row_shl_i32<0x104>(v));
-    v = min(v, dpp_row_shl_i32<0x102>(v));
-    v = min(v, dpp_row_shl_i32<0x101>(v));
-    return v;
-}
+// ---- The persistent pivot kernel: its steps, one helper each, then the kernel ------------------------------------------------
+// The pivot under way and the running totals, in registers: the fields of the record this kernel owns (read at entry, stored
+// by ft_report), and the step length br = b_r / alpha_r
+struct FtPivot { PivotRecord rec; double br; };
 
-template <class Ctx>
-__device__ __forceinline__ int block_min_int(Ctx& c, int v) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    v = wave_min_i32(v);
-    __syncthreads();
-    if (lane == 0) c.red_i[wave] = v;
-    __syncthreads();
-    v = c.red_i[0];
+// ---- PRICE (pivot_rule.rs:38-126 over tableau/mod.rs:102-108): d_j = c_j + (-pi) . a_j, a thread per column ------------------
+// One tier of the PRICE copy (PriceEll), slot u of column `col` at [u * stride + col].  Tier A: the first kPriceSlots entries
+// of every structural column, the flag bit of slot 0's index = "the column has more".  Tier B: the long columns, complete.
+// (row indices: 16 bits, bit 15 the flag; 32 bits with bit 31 in layout 2)
+template <int kTier, bool kTierB>
+struct PeSlots {
+    static constexpr int kFlag = kTierB ? 0 : kTier >= 2 ? (int)kPriceLongFlag32 : kPriceLongFlag;
+    static constexpr int kMask = kTier >= 2 ? 0x7fffffff : kPriceLongFlag - 1;
+    const PriceEll& pe; int stride, col;
+    __device__ __forceinline__ int idx(int u) const {
+        if constexpr (kTier >= 2) return (int)(kTierB ? pe.lidx32 : pe.idx32)[u * stride + col];
+        else return (kTierB ? pe.lidx : pe.idx)[u * stride + col];
+    }
+    __device__ __forceinline__ double val(int u) const { return (kTierB ? pe.lval : pe.val)[u * stride + col]; }
+};
+
+// What the reduced cost of a structural column has besides the dot product: (-pi) of its bound row and its cost.  The two
+// loads go out with the column's entries, the gather with the entries' own (price_slots).
+struct PriceTail {
+    int br; double cp, pi_br; bool with_cost;
+    __device__ __forceinline__ PriceTail(const ColumnTable& ct, const double* costs, int p)
+        : br(ct.bound_row[p]), cp(costs ? costs[p] : 0.0), pi_br(0.0), with_cost(costs != nullptr) {}
+    __device__ __forceinline__ void gather(const double* pi) { pi_br = pi[br >= 0 ? br : 0]; }
+    __device__ __forceinline__ double finish(double v) const { if (br >= 0) v += pi_br; if (with_cost) v += cp; return v; }
+};
+
+// v + (-pi) . a over slots [kFirst, kFirst + kCount) of one column, summed in the column's own order like k_price_csc: every
+// (row, value) pair is loaded, then every -pi is gathered (the bound row's with them), then the chain runs.  `more`: tier A
+// from slot 0 on, the flag of slot 0 (taken off its index either way).
+template <int kFirst, int kCount, class Slots>
+__device__ __forceinline__ double price_slots(const Slots& s, const double* pi, double v, PriceTail* tail = nullptr, bool* more = nullptr) {
+    int ri[kCount];
+    double va[kCount], px[kCount];
 #pragma unroll
-    for (int w = 1; w < NW; ++w) v = min(v, c.red_i[w]);
+    for (int u = 0; u < kCount; ++u) { ri[u] = s.idx(kFirst + u); va[u] = s.val(kFirst + u); }
+    if constexpr (Slots::kFlag != 0 && kFirst == 0) { if (more) *more = (ri[0] & Slots::kFlag) != 0; ri[0] &= Slots::kMask; }
+#pragma unroll
+    for (int u = 0; u < kCount; ++u) px[u] = pi[ri[u]];
+    if (tail) tail->gather(pi);
+#pragma unroll
+    for (int u = 0; u < kCount; ++u) v = fma(px[u], va[u], v);
+    return v;
+}
+// the same for a column beyond the second tier: the whole column from the CSC arrays
+__device__ __forceinline__ double price_csc(const DeviceCSC& csc, const double* pi, int p) {
+    double v = 0.0;
+    for (int64_t e = csc.col_ptr[p]; e < csc.col_ptr[p + 1]; ++e) v = fma(pi[csc.row_idx[e]], csc.values[e], v);
+    return v;
+}
+// Artificial column j and virtual column vv (slack, bound slack): no matrix data.  (price_virtual_body of relp_device_common.h
+// wraps the same two expressions in a 256-thread block's store of d and partial minimum into SelectPartials: it does not fit.)
+__device__ __forceinline__ double price_artificial(const ColumnTable& ct, const double* pi, int cost_mode, int j) { return (cost_mode == 1 ? 1.0 : 0.0) + pi[ct.column_to_row[j]]; }
+__device__ __forceinline__ double price_virtual(const ColumnTable& ct, const double* pi, int vv) {
+    const int r0 = ct.vrow0[vv], r1 = ct.vrow1[vv];
+    double v = r0 >= 0 ? (double)ct.vsign[vv] * pi[r0] : 0.0;
+    if (r1 >= 0) v += pi[r1];
     return v;
 }
 
+// The winner of PRICE: its key and column in every thread (kj = 0x7fffffff: none); my_j == kj in the thread that priced it,
+// which holds its reduced cost in my_v
+struct PriceChoice { double key = INFINITY, my_v = 0.0; int kj = 0x7fffffff, my_j = 0x7fffffff; };
+
+// FirstProfitable / FirstProfitableWithMemory (pivot_rule.rs:38-95) take the first profitable column of a fixed search order
+// (from `start` on, wrapping): the columns are priced NT at a time along that order and the scan stops at the first chunk
+// that holds one -- the same column as a full scan would choose, for a fraction of the loads.  (d is not refreshed here;
+// nothing reads it under these rules.)
 template <class Ctx>
-__device__ __forceinline__ double block_min_double(Ctx& c, double v) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    v = wave_min_f64(v);
-    __syncthreads();
-    if (lane == 0) c.red_d[wave] = v;
-    __syncthreads();
-    v = c.red_d[0];
-#pragma unroll
-    for (int w = 1; w < NW; ++w) v = fmin(v, c.red_d[w]);
-    return v;
+__device__ __forceinline__ PriceChoice ft_price_first(Ctx& c, const FtProblem& pb, int start) {
+    typedef PeSlots<Ctx::tier, false> TierA;
+    typedef PeSlots<Ctx::tier, true> TierB;
+    const ColumnTable& ct = pb.ct;
+    const int tid = threadIdx.x, n = pb.n, cost_mode = pb.phase, na = ct.nr_artificial, nstr = ct.nr_normal;
+    const double* costs = cost_mode == 2 ? ct.cost : nullptr;
+    PriceChoice pc;
+    for (int base = 0; base < n; base += NT) {
+        const int k = base + tid;
+        int my_k = 0x7fffffff;
+        if (k < n) {
+            int j = start + k;
+            if (j >= n) j -= n;
+            const int basic = pb.in_basis[j];
+            double v;
+            if (j < na) {
+                v = price_artificial(ct, c.pi, cost_mode, j);
+            } else if (j < na + nstr) {
+                const int p = j - na;
+                PriceTail tail(ct, costs, p);
+                const int li = pb.pe.long_of[p];
+                bool is_long;
+                v = price_slots<0, kPriceSlots>(TierA{pb.pe, nstr, p}, c.pi, 0.0, &tail, &is_long);
+                if (is_long && li != 0xFFFF)                    // its entries 8.. from the second tier, same order
+                    v = price_slots<kPriceSlots, kPriceLongSlots - kPriceSlots>(TierB{pb.pe, pb.pe.n_long, li}, c.pi, v);
+                else if (is_long) v = price_csc(pb.csc, c.pi, p);
+                v = tail.finish(v);
+            } else {
+                v = price_virtual(ct, c.pi, j - na - nstr);
+            }
+            if (!basic && v < -pb.tol.cost) { my_k = k; pc.my_v = v; }
+        }
+        const int kmin = block_min(c, my_k);
+        if (kmin != 0x7fffffff) {
+            pc.key = (double)kmin;                              // (= select_key: the position in the search order)
+            pc.kj = start + kmin;
+            if (pc.kj >= n) pc.kj -= n;
+            if (my_k == kmin) pc.my_j = pc.kj;
+            break;
+        }
+    }
+    return pc;
 }
 
-// minimum of 64-bit tie keys (relp_device_common.h: tie_key) over the workgroup; only the RELP_RATIO_LARGEST_PIVOT rule
-// comes here, the reference's rule reduces 32-bit leaving columns (block_min_int)
+// Dantzig ties (pivot_rule.rs:118): the lowest index within the tie band of the minimum `key` (every thread re-reads a stripe
+// of d, eight columns per round so that the loads of a round are in flight together)
 template <class Ctx>
-__device__ __forceinline__ tie_key_t block_min_key64(Ctx& c, tie_key_t v) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+__device__ __forceinline__ void ft_price_tie_band(Ctx& c, const FtProblem& pb, PriceChoice& pc) {
+    const int tid = threadIdx.x, n = pb.n;
+    const double bound = pc.key + pb.tol.tie * fmax(1.0, fabs(pc.key));
+    pc.my_j = 0x7fffffff;
+    for (int j0 = tid; j0 < n; j0 += 8 * NT) {
+        double dv[8];
+        int ib[8];
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { const tie_key_t o = __shfl_down(v, off, 64); v = o < v ? o : v; }
-    tie_key_t* red = reinterpret_cast<tie_key_t*>(c.red_d);
-    __syncthreads();
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    v = red[0];
+        for (int u = 0; u < 8; ++u) { const int j = min(j0 + u * NT, n - 1); dv[u] = pb.d[j]; ib[u] = pb.in_basis[j]; }
 #pragma unroll
-    for (int w = 1; w < NW; ++w) v = red[w] < v ? red[w] : v;
-    return v;
+        for (int u = 0; u < 8; ++u) {
+            const int j = j0 + u * NT;
+            if (j < n && !ib[u] && dv[u] < -pb.tol.cost && dv[u] <= bound && j < pc.my_j) { pc.my_j = j; pc.my_v = dv[u]; }
+        }
+    }
+    pc.kj = block_min(c, pc.my_j);
 }
 
-// lexicographic minimum of (key, j) over the workgroup: the smallest key, then the lowest j among the threads that hold it
+// SteepestDescent (pivot_rule.rs:97-126; rule 2, whose selection key is d_j itself): every column is priced and d refreshed.  Structural columns from the k-major PRICE
+// copy, tier A, then the long columns from tier B, then the few beyond it: every load of a column is issued before the first
+// is used, incl. its basis flag, bound row and cost.
 template <class Ctx>
-__device__ __forceinline__ void block_min_key(Ctx& c, double& key, int& kj) {
-    const double kmin = block_min_double(c, key);
-    kj = block_min_int(c, key == kmin ? kj : 0x7fffffff);
-    key = kmin;
+__device__ __forceinline__ PriceChoice ft_price_dantzig(Ctx& c, const FtProblem& pb) {
+    typedef PeSlots<Ctx::tier, false> TierA;
+    typedef PeSlots<Ctx::tier, true> TierB;
+    const ColumnTable& ct = pb.ct;
+    const int tid = threadIdx.x, cost_mode = pb.phase, na = ct.nr_artificial, nstr = ct.nr_normal;
+    const double* costs = cost_mode == 2 ? ct.cost : nullptr;
+    PriceChoice pc;
+    auto consider = [&](int j, double v, int basic) {
+        pb.d[j] = v;
+        if (!basic && v < -pb.tol.cost) {
+            if (v < pc.key || (v == pc.key && j < pc.my_j)) { pc.key = v; pc.my_j = j; pc.my_v = v; }    // (key = select_key: d_j)
+        }
+    };
+    for (int j = tid; j < na; j += NT) consider(j, price_artificial(ct, c.pi, cost_mode, j), pb.in_basis[j]);
+    for (int p = tid; p < nstr; p += NT) {
+        PriceTail tail(ct, costs, p);
+        const int basic = pb.in_basis[na + p];
+        bool is_long;                                           // more than kPriceSlots entries: priced below
+        const double v = tail.finish(price_slots<0, kPriceSlots>(TierA{pb.pe, nstr, p}, c.pi, 0.0, &tail, &is_long));
+        if (!is_long) consider(na + p, v, basic);
+    }
+    for (int i = tid; i < pb.pe.n_long; i += NT) {                 // columns of kPriceSlots + 1 .. kPriceLongSlots entries
+        const int p = pb.pe.long_cols[i];
+        PriceTail tail(ct, costs, p);
+        const int basic = pb.in_basis[na + p];
+        consider(na + p, tail.finish(price_slots<0, kPriceLongSlots>(TierB{pb.pe, pb.pe.n_long, i}, c.pi, 0.0, &tail)), basic);
+    }
+    for (int i = tid; i < pb.pe.n_very_long; i += NT) {            // the few columns beyond that
+        const int p = pb.pe.very_long[i];
+        const double v = price_csc(pb.csc, c.pi, p);
+        PriceTail tail(ct, costs, p);
+        tail.gather(c.pi);
+        consider(na + p, tail.finish(v), pb.in_basis[na + p]);
+    }
+    for (int vv = tid; vv < ct.nr_virtual; vv += NT) consider(na + nstr + vv, price_virtual(ct, c.pi, vv), pb.in_basis[na + nstr + vv]);
+#ifdef PRICE_DIAG
+    c.clk.lap(FT_PRICE);
+#endif
+    pc.kj = pc.my_j;
+    block_min_key(c, pc.key, pc.kj);
+#ifdef PRICE_DIAG
+    c.clk.lap(FT_LOAD_STORE);
+#endif
+    if (pc.kj != 0x7fffffff && pb.tol.tie > 0.0) ft_price_tie_band(c, pb, pc);
+    return pc;
 }
 
-// ------------------------------------------------------------------------------------------------------------------
-// The persistent pivot kernel
-// ------------------------------------------------------------------------------------------------------------------
+// The entering column into pv.rec (q, d_q, key1, the rule's memory); false, with the outcome set, when no column is profitable
+template <class Ctx>
+__device__ __forceinline__ bool ft_price(Ctx& c, const FtProblem& pb, FtPivot& pv) {
+    const int rule = pb.rule;
+    const PriceChoice pc = rule != 2 ? ft_price_first(c, pb, (rule == 1 && pv.rec.last_selected >= 0) ? pv.rec.last_selected : 0)
+                                     : ft_price_dantzig(c, pb);
+    if (pc.kj == 0x7fffffff) {
+        pv.rec.outcome = DEV_NO_CANDIDATE;
+        if (rule == 1) pv.rec.last_selected = -1;
+        return false;
+    }
+#ifdef PRICE_DIAG
+    c.clk.lap(FT_B);
+#endif
+    if (pc.my_j == pc.kj) c.red_d[NW] = pc.my_v;                    // the owner publishes d_q
+    __syncthreads();
+    pv.rec.q = pc.kj; pv.rec.key1 = pc.key; pv.rec.d_q = c.red_d[NW];
+    if (rule == 1) pv.rec.last_selected = pc.kj;
+    return true;
+}
+
+// ---- RATIO TEST and b (tableau/mod.rs:221-247, carry/mod.rs:283-313; two passes as relp_device_common.h ratio_body) ----------
+// A row walker hands every row of this thread that can matter to f(i, alpha_i, b_i, basis_of), basis_of() = the column basic
+// in row i, fetched only when asked for.  alpha_of(r): the pivot element, for the thread that owns row r.
+//
+// Layout 0: alpha = x through the column permutation, every row.  Rows tid and tid + NT of this thread stay in registers
+// through the passes and the update of b (one round of global loads for m <= 2 NT); rows beyond that are re-read.
+// pb.alpha (dense, for whoever reads it after the launch) is written here.
+template <class Ctx>
+struct FtDenseRows {
+    const Ctx& c; const FtProblem& pb;
+    int i0, i1, s0, s1; bool h0, h1; double a0, a1, b0, b1;
+    __device__ __forceinline__ FtDenseRows(const Ctx& c_, const FtProblem& pb_) : c(c_), pb(pb_) {
+        const int m = c.m;
+        i0 = threadIdx.x;
+        asm volatile("" : "+v"(i0));                   // (formed per pivot: no address made of it is kept across the whole loop)
+        i1 = i0 + NT; h0 = i0 < m; h1 = i1 < m;
+        const int p0 = c.icp[h0 ? i0 : 0], p1 = c.icp[h1 ? i1 : 0];
+        b0 = pb.b[h0 ? i0 : 0]; b1 = pb.b[h1 ? i1 : 0];
+        s0 = pb.basis[h0 ? i0 : 0]; s1 = pb.basis[h1 ? i1 : 0];
+        a0 = c.x[p0]; a1 = c.x[p1];
+        if (h0) pb.alpha[i0] = a0;
+        if (h1) pb.alpha[i1] = a1;
+        for (int i = i1 + NT; i < m; i += NT) pb.alpha[i] = c.x[c.icp[i]];
+    }
+    template <class F>
+    __device__ __forceinline__ void each(F f) const {
+        if (h0) f(i0, a0, b0, [&]() { return s0; });
+        if (h1) f(i1, a1, b1, [&]() { return s1; });
+        for (int i = i1 + NT; i < c.m; i += NT) f(i, c.x[c.icp[i]], pb.b[i], [&]() { return pb.basis[i]; });
+    }
+    __device__ __forceinline__ double alpha_of(int r) const { return c.x[c.icp[r]]; }
+};
+
+// Layouts 1 and 2: the solve leaves x pivot-indexed and mostly zero.  One coalesced pass over x scatters alpha (dense, for
+// whoever reads it after the launch) and appends the non-zeros as (row, alpha) pairs to a list; the ratio test, the tie band,
+// the leaving row and the update of b then touch the list only (tableau/mod.rs:221-247 walks the stored non-zeros of the
+// column just the same).  Every reduction is order-free (minima), so the list's order does not matter.  Returns the length
+// of the list, which is also `alpha_nnz` (layout 2: the entries of nz_idx that describe pb.alpha) from here on.
+template <class Ctx>
+__device__ __forceinline__ int ft_list_alpha(Ctx& c, const DeviceLU& lu, const FtState& st, const FtProblem& pb, int& alpha_nnz) {
+    const int tid = threadIdx.x, m = c.m;
+    if constexpr (Ctx::huge) {
+        // pb.alpha is zeroed where the previous column was not -- its list is still there -- then the non-zeros of x, found
+        // through the bitmap, are scattered and listed
+        if (alpha_nnz < 0) { for (int i = tid; i < m; i += NT) pb.alpha[i] = 0.0; }
+        else for (int e = tid; e < alpha_nnz; e += NT) pb.alpha[st.nz_idx[e]] = 0.0;
+        if (tid == 0) c.red_i[2 * NW] = 0;
+        __syncthreads();
+        hs_for_each(c.bx, c.gs, 0, m, [&](int k) {
+            const double v = c.x[k];
+            if (v != 0.0) {
+                const int i = lu.colperm[k];
+                pb.alpha[i] = v;
+                const int e = atomicAdd(&c.red_i[2 * NW], 1);
+                st.nz_idx[e] = i; st.nz_val[e] = v;
+            }
+        });
+    } else {
+        // (layout 1: x in LDS, no bitmap -- one pass over x with the permutation coalesced from L2 beside it: alpha written
+        // everywhere, the non-zeros listed.  The three passes this replaces each went x[icp[i]], b[i], basis[i] through L2
+        // for every row.)
+        if (tid == 0) c.red_i[2 * NW] = 0;
+        __syncthreads();
+        for (int k0 = tid; k0 < m; k0 += 4 * NT) {
+            int cp[4];
+            double xv[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) { const int k = min(k0 + u * NT, m - 1); xv[u] = c.x[k]; cp[u] = lu.colperm[k]; }
+            asm volatile("" : "+v"(cp[0]), "+v"(cp[1]), "+v"(cp[2]), "+v"(cp[3]));
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (k0 + u * NT < m) {
+                    pb.alpha[cp[u]] = xv[u];
+                    if (xv[u] != 0.0) { const int e = atomicAdd(&c.red_i[2 * NW], 1); st.nz_idx[e] = cp[u]; st.nz_val[e] = xv[u]; }
+                }
+            }
+        }
+    }
+    __syncthreads();
+    const int nnz = c.red_i[2 * NW];
+    alpha_nnz = nnz;
+    if constexpr (Ctx::huge) if (c.clk.on) { c.clk.nnz[0] += nnz; c.clk.nnz[3] += 1; }
+    return nnz;
+}
+
+// The rows of that list.  The first entry of every thread stays in registers: a column rarely has more than NT non-zeros.
+struct FtListRows {
+    const FtState& st; const FtProblem& pb;
+    int nnz, i0; bool h0; double a0, b0;
+    __device__ __forceinline__ FtListRows(const FtState& st_, const FtProblem& pb_, int nnz_) : st(st_), pb(pb_), nnz(nnz_) {
+        const int tid = threadIdx.x;
+        h0 = tid < nnz; i0 = h0 ? st.nz_idx[tid] : 0; a0 = h0 ? st.nz_val[tid] : 0.0; b0 = h0 ? pb.b[i0] : 0.0;
+    }
+    template <class F>
+    __device__ __forceinline__ void each(F f) const {
+        if (h0) f(i0, a0, b0, [&]() { return pb.basis[i0]; });
+        for (int e = (int)threadIdx.x + NT; e < nnz; e += NT) { const int i = st.nz_idx[e]; f(i, st.nz_val[e], pb.b[i], [&]() { return pb.basis[i]; }); }
+    }
+    __device__ __forceinline__ double alpha_of(int r) const { return pb.alpha[r]; }
+};
+
+// The ratio test over the rows of `rows`, then b while alpha is still at hand: minimum ratio, tie band, leaving column (the
+// reference: the lowest inside the band; RELP_RATIO_LARGEST_PIVOT: pivot size first, through tie_key), its row, alpha_r and b_r
+// from the thread that owns the row, the pivot guard, b.  False, with the outcome set, when no row qualifies.  Ends with a
+// barrier.
+template <class Ctx, class Rows>
+__device__ __forceinline__ bool ft_ratio_and_b(Ctx& c, const FtProblem& pb, const Rows& rows, FtPivot& pv) {
+    const Tolerances& tol = pb.tol;
+    double mn = INFINITY;
+    rows.each([&](int, double a, double bi, auto) { mn = fmin(mn, row_ratio(a, bi, tol)); });
+    const double gmin = block_min(c, mn);
+    if (gmin == INFINITY) { pv.rec.outcome = DEV_NO_ROW; return false; }
+    const double bound = gmin + tol.tie * fmax(1.0, fabs(gmin));
+    // this thread's best row inside the band (a column is basic in one row: the keys of two rows differ)
+    int best_leave = 0x7fffffff, rr = 0x7fffffff;
+    tie_key_t best = kNoTieKey;
+    const bool by_column = tol.ratio_rule == 0;
+    rows.each([&](int i, double a, double bi, auto basis_of) {
+        if (row_ratio(a, bi, tol) <= bound) {
+            const int sc = basis_of();
+            if (by_column) { if (sc < best_leave || (sc == best_leave && i < rr)) { best_leave = sc; rr = i; } }
+            else { const tie_key_t k = tie_key(a, sc, 1); if (k < best || (k == best && i < rr)) { best = k; best_leave = sc; rr = i; } }
+        }
+    });
+    int leaving;
+    if (by_column) leaving = block_min(c, best_leave);
+    else {
+        const tie_key_t kmin = block_min(c, best);
+        leaving = tie_key_leaving(kmin);
+        if (best != kmin) best_leave = 0x7fffffff;
+    }
+    const int r = block_min(c, best_leave == leaving ? rr : 0x7fffffff);
+    if (best_leave == leaving && rr == r) { c.red_d[NW] = rows.alpha_of(r); c.red_d[NW + 1] = pb.b[r]; }    // the owner publishes
+    __syncthreads();
+    const double alpha_r = c.red_d[NW], b_r = c.red_d[NW + 1];
+    pv.rec.leaving = leaving; pv.rec.r = r; pv.rec.alpha_r = alpha_r; pv.rec.b_r = b_r;
+    if (tol.pivot_guard) {                             // (Tolerances::pivot_guard: too small beside the column's largest entry)
+        double mx = 0.0;
+        rows.each([&](int, double a, double, auto) { mx = fmax(mx, fabs(a)); });
+        const double amax = -block_min(c, -mx);
+        if (alpha_r < tol.guard_rel * amax) { pv.rec.outcome = DEV_NO_ROW; return false; }
+    }
+    c.clk.lap(FT_RATIO);
+    const double br = b_r / alpha_r;
+    pv.br = br;
+    rows.each([&](int i, double a, double bi, auto) { pb.b[i] = pivot_b(a, bi, br, i == r); });
+    __syncthreads();
+    return true;
+}
+
+// ---- rho = row r of the new inverse (x, pivot-indexed, times rho_scale) into pb.rho, and -pi -= d_q rho
+// (carry/mod.rs:326-333, 549-570) -------------------------------------------------------------------------------------------
+// Layout 2: pb.rho as pb.alpha in ft_list_alpha (rho_nnz: the entries of rho_idx that describe it); -pi changes where rho is
+// not zero only.  Layout 1: the permutation comes from L2, four rows requested at a time.
+template <class Ctx>
+__device__ __forceinline__ void ft_rho_and_pi(Ctx& c, const FtState& st, const FtProblem& pb, double d_q, double rho_scale, int& rho_nnz) {
+    const int tid = threadIdx.x, m = c.m;
+    auto row = [&](int i, double rho) { pb.rho[i] = rho; c.pi[i] = fma(-d_q, rho, c.pi[i]); };
+    if constexpr (Ctx::huge) {
+        if (rho_nnz < 0) { for (int i = tid; i < m; i += NT) pb.rho[i] = 0.0; }
+        else for (int e = tid; e < rho_nnz; e += NT) pb.rho[st.rho_idx[e]] = 0.0;
+        if (tid == 0) c.red_i[2 * NW + 1] = 0;
+        __syncthreads();
+        hs_for_each(c.bx, c.gs, 0, m, [&](int k) {
+            const double rho = c.x[k] * rho_scale;
+            if (rho != 0.0) {
+                const int i = c.rp[k];
+                row(i, rho);
+                st.rho_idx[atomicAdd(&c.red_i[2 * NW + 1], 1)] = i;
+            }
+        });
+        __syncthreads();
+        rho_nnz = c.red_i[2 * NW + 1];
+    } else if constexpr (Ctx::big) {
+        for (int k0 = tid; k0 < m; k0 += 4 * NT) {
+            int ii[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) ii[u] = c.rp[min(k0 + u * NT, m - 1)];
+            asm volatile("" : "+v"(ii[0]), "+v"(ii[1]), "+v"(ii[2]), "+v"(ii[3]));
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (k0 + u * NT < m) row(ii[u], c.x[k0 + u * NT] * rho_scale);
+        }
+    } else {
+        for (int k = tid; k < m; k += NT) row(c.rp[k], c.x[k] * rho_scale);
+    }
+}
+
+// ---- basis, basis flags and trace row by thread 0; -obj, the degenerate and the iteration counter in every thread's copy of
+// the record, in the field order of pivot_bookkeeping (relp_device_common.h: that one is for ONE thread and counts in memory;
+// here every thread counts for itself, so that the counters stay uniform) -------------------------------------------------------
+__device__ __forceinline__ void ft_bookkeeping(const FtProblem& pb, FtPivot& pv) {
+    PivotRecord& rec = pv.rec;
+    if (threadIdx.x == 0) {
+        pb.basis[rec.r] = rec.q;
+        if (rec.leaving < kWrappedArtificialBase) pb.in_basis[rec.leaving] = 0;
+        pb.in_basis[rec.q] = 1;
+        if (pb.trace && rec.iterations < pb.trace_cap) {
+            pb.trace[0 * pb.trace_cap + rec.iterations] = pb.phase;
+            pb.trace[1 * pb.trace_cap + rec.iterations] = rec.q;
+            pb.trace[2 * pb.trace_cap + rec.iterations] = rec.r;
+            pb.trace[3 * pb.trace_cap + rec.iterations] = rec.leaving;
+        }
+    }
+    rec.minus_objective = fma(-rec.d_q, pv.br, rec.minus_objective);
+    if (pv.br == 0.0) rec.degenerate += 1;
+    rec.iterations += 1;
+}
+
+// ---- the report to the host, by every exit of the kernel: the record (`now`: the register snapshot of this launch, stored
+// first; null: the record as it stands), and into the mirror the record, the header of the update file, what the sweeps
+// walked (kWalks; clk null: nothing) and the basis -- the host reads the mirror after synchronising the stream ---------------
+template <bool kWalks>
+__device__ __forceinline__ void ft_report(const FtProblem& pb, int m, const PivotRecord* now, int t, int eta_used, int need_refactor,
+                                          int journal_n, const FtClock* clk) {
+    const int tid = threadIdx.x;
+    PivotRecord* rec = pb.rec;
+    if (now && tid == 0) {
+        rec->outcome = now->outcome; rec->q = now->q; rec->d_q = now->d_q; rec->r = now->r; rec->leaving = now->leaving;
+        rec->alpha_r = now->alpha_r; rec->b_r = now->b_r; rec->minus_objective = now->minus_objective; rec->iterations = now->iterations;
+        rec->last_selected = now->last_selected; rec->key1 = now->key1; rec->degenerate = now->degenerate;
+    }
+    if (!pb.mirror) return;
+    if (tid == 0) {
+        pb.mirror->rec = *rec;
+        pb.mirror->hdr[0] = t; pb.mirror->hdr[1] = eta_used; pb.mirror->hdr[2] = need_refactor; pb.mirror->hdr[3] = journal_n;
+        if constexpr (kWalks) {
+            for (int k = 0; k < 4; ++k) {
+                pb.mirror->walked[k] = clk ? (int32_t)clk->passes[k] : 0; pb.mirror->whole[k] = clk ? (int32_t)clk->total[k] : 0;
+                pb.mirror->sweeps[k] = clk ? (int32_t)clk->sweeps[k] : 0;
+            }
+        }
+    }
+    for (int i = tid; i < m; i += NT) pb.mirror->basis[i] = pb.basis[i];
+}
+
 template <int kTier>
 __global__ __launch_bounds__(NT) void k_ft_run(DeviceLU lu, FtState st, FtProblem pb, long long max_pivots) {
     extern __shared__ __align__(16) char lds[];
-    PivotRecord* rec = pb.rec;
+    const int tid = threadIdx.x;
+    const PivotRecord* rec = pb.rec;
     if (rec->outcome != DEV_RUNNING) {
         // nothing to do; the report is still this launch's own (no basis change in the journal), never the previous one's
-        if (pb.mirror) {
-            if (threadIdx.x == 0) {
-                pb.mirror->rec = *rec;
-                pb.mirror->hdr[0] = st.hdr[0]; pb.mirror->hdr[1] = st.hdr[1]; pb.mirror->hdr[2] = st.hdr[2]; pb.mirror->hdr[3] = 0;
-                for (int k = 0; k < 4; ++k) { pb.mirror->walked[k] = 0; pb.mirror->whole[k] = 0; pb.mirror->sweeps[k] = 0; }
-            }
-            for (int i = threadIdx.x; i < st.m; i += NT) pb.mirror->basis[i] = pb.basis[i];
-        }
-        if (threadIdx.x == 0) st.hdr[3] = 0;
+        ft_report<true>(pb, st.m, nullptr, st.hdr[0], st.hdr[1], st.hdr[2], 0, nullptr);
+        if (tid == 0) st.hdr[3] = 0;
         return;
     }
+    // ---- prologue: the update file into LDS, the record into registers ------------------------------------------------------
     FtCtxT<kTier> c;
     ft_bind(c, lds, lu, st);
     c.clk.start(st.prof);
@@ -985,396 +1403,37 @@ __global__ __launch_bounds__(NT) void k_ft_run(DeviceLU lu, FtState st, FtProble
     int alpha_nnz = 0, rho_nnz = 0;                    // (layout 2) entries of nz_idx / rho_idx that describe pb.alpha / pb.rho
     if constexpr (kTier >= 2) { alpha_nnz = st.nzc[0]; rho_nnz = st.nzc[1]; }
     c.clk.lap(FT_LOAD_STORE);
-    const int tid = threadIdx.x;
-    const ColumnTable& ct = pb.ct;
-    const int m = c.m, n = pb.n, rule = pb.rule, cost_mode = pb.phase;
-    int last_selected = rec->last_selected;
-    double minus_objective = rec->minus_objective;
-    long long iterations = rec->iterations;
-    int degenerate = rec->degenerate;
-    int outcome = DEV_RUNNING, need_refactor = st.hdr[2] >= 2 ? 2 : 0;       // (2: a replay failed, the factors are unusable)
+    FtPivot pv;
+    pv.rec = *rec;
+    int need_refactor = st.hdr[2] >= 2 ? 2 : 0;       // (2: a replay failed, the factors are unusable)
     // (a launch of the one-pivot-per-launch loop must not pivot on factors an earlier launch of its batch declared due: the host
     // looks at the header after the batch only.  The persistent loop is relaunched on purpose with hdr[2] == 1: look-ahead.)
     if (pb.external_price && st.hdr[2]) need_refactor = st.hdr[2];
     if (pb.external_price) c.journal_n = st.hdr[3];                     // (one journal per batch)
-    int q = rec->q, r = rec->r, leaving = rec->leaving;
-    double d_q = rec->d_q, alpha_r = rec->alpha_r, b_r = rec->b_r, key1 = rec->key1;
-    PivotRecord fake;                                  // select_key reads rule memory through a record
-    fake.last_selected = last_selected;
-    // (row indices of the PRICE copy: 16 bits, bit 15 = "long column"; 32 bits with bit 31 in layout 2)
-    constexpr int kLongFlag = kTier >= 2 ? (int)kPriceLongFlag32 : kPriceLongFlag, kLongMask = kTier >= 2 ? 0x7fffffff : kPriceLongFlag - 1;
-    auto pe_idx = [&](int i) -> int { if constexpr (kTier >= 2) return (int)pb.pe.idx32[i]; else return pb.pe.idx[i]; };
-    auto pe_lidx = [&](int i) -> int { if constexpr (kTier >= 2) return (int)pb.pe.lidx32[i]; else return pb.pe.lidx[i]; };
 
     for (long long it = 0; it < max_pivots; ++it) {
         if (need_refactor || c.t >= st.max_updates || c.t >= c.tcap) { if (!need_refactor) need_refactor = 1; break; }
-        // ---- PRICE (pivot_rule.rs:38-126 over tableau/mod.rs:102-108): d_j = c_j + (-pi) . a_j, thread per column ----------
+        // ---- PRICE ----------------------------------------------------------------------------------------------------------
         // (external_price: this launch makes one pivot with the column a grid-wide PRICE chose -- Engine::run_ft, Dantzig's rule
         // over very many columns, where one workgroup pricing all of them was 70 % of the pivot)
-        if (!pb.external_price) {
-        fake.last_selected = last_selected;
-        double key = INFINITY, kv = 0.0;
-        int kj = 0x7fffffff;
-        // (structural columns from the k-major PRICE copy: every load of a column is issued before the first is used, incl.
-        // its basis flag, bound row and cost; summation in the column's own order like k_price_csc)
-        const int na = ct.nr_artificial, nstr = ct.nr_normal;
-        auto consider = [&](int j, double v, int basic) {
-            pb.d[j] = v;
-            if (!basic && v < -pb.tol.cost) {
-                const double k = select_key(rule, n, &fake, j, v);
-                if (k < key || (k == key && j < kj)) { key = k; kj = j; kv = v; }
-            }
-        };
-        const double* costs = cost_mode == 2 ? ct.cost : nullptr;
-        int my_j = 0x7fffffff;                                      // this thread's own candidate and its reduced cost
-        double my_v = 0.0;
-        if (rule != 2) {
-            // FirstProfitable / FirstProfitableWithMemory (pivot_rule.rs:38-95) take the first profitable column of a fixed
-            // search order: the columns are priced NT at a time along that order and the scan stops at the first chunk that
-            // holds one -- the same column as a full scan would choose, for a fraction of the loads.  (d is not refreshed
-            // here; nothing reads it under these rules.)
-            const int start = (rule == 1 && last_selected >= 0) ? last_selected : 0;
-            for (int base = 0; base < n; base += NT) {
-                const int k = base + tid;
-                int my_k = 0x7fffffff;
-                if (k < n) {
-                    int j = start + k;
-                    if (j >= n) j -= n;
-                    const int basic = pb.in_basis[j];
-                    double v;
-                    if (j < na) {
-                        v = (cost_mode == 1 ? 1.0 : 0.0) + c.pi[ct.column_to_row[j]];
-                    } else if (j < na + nstr) {
-                        const int p = j - na;
-                        int ri[kPriceSlots];
-                        double va[kPriceSlots], px[kPriceSlots];
-#pragma unroll
-                        for (int u = 0; u < kPriceSlots; ++u) { ri[u] = pe_idx(u * nstr + p); va[u] = pb.pe.val[u * nstr + p]; }
-                        const int br = ct.bound_row[p];
-                        const int li = pb.pe.long_of[p];
-                        const double cp = costs ? costs[p] : 0.0;
-                        const bool is_long = (ri[0] & kLongFlag) != 0;
-                        ri[0] &= kLongMask;
-#pragma unroll
-                        for (int u = 0; u < kPriceSlots; ++u) px[u] = c.pi[ri[u]];
-                        const double pb_r = c.pi[br >= 0 ? br : 0];
-                        v = 0.0;
-#pragma unroll
-                        for (int u = 0; u < kPriceSlots; ++u) v = fma(px[u], va[u], v);
-                        if (is_long && li != 0xFFFF) {              // its entries 8.. from the second tier, same order
-                            const int nl = pb.pe.n_long;
-                            constexpr int kRest = kPriceLongSlots - kPriceSlots;
-                            int rj[kRest];
-                            double vb[kRest], py[kRest];
-#pragma unroll
-                            for (int u = 0; u < kRest; ++u) { rj[u] = pe_lidx((kPriceSlots + u) * nl + li); vb[u] = pb.pe.lval[(kPriceSlots + u) * nl + li]; }
-#pragma unroll
-                            for (int u = 0; u < kRest; ++u) py[u] = c.pi[rj[u]];
-#pragma unroll
-                            for (int u = 0; u < kRest; ++u) v = fma(py[u], vb[u], v);
-                        } else if (is_long) {                       // beyond the second tier: the whole column from the CSC arrays
-                            v = 0.0;
-                            for (int64_t e = pb.csc.col_ptr[p]; e < pb.csc.col_ptr[p + 1]; ++e) v = fma(c.pi[pb.csc.row_idx[e]], pb.csc.values[e], v);
-                        }
-                        if (br >= 0) v += pb_r;
-                        if (costs) v += cp;
-                    } else {
-                        const int vv = j - na - nstr;
-                        const int r0 = ct.vrow0[vv], r1 = ct.vrow1[vv];
-                        v = r0 >= 0 ? (double)ct.vsign[vv] * c.pi[r0] : 0.0;
-                        if (r1 >= 0) v += c.pi[r1];
-                    }
-                    if (!basic && v < -pb.tol.cost) { my_k = k; my_v = v; }
-                }
-                const int kmin = block_min_int(c, my_k);
-                if (kmin != 0x7fffffff) {
-                    key = (double)kmin;                             // (= select_key: the position in the search order)
-                    kj = start + kmin;
-                    if (kj >= n) kj -= n;
-                    if (my_k == kmin) my_j = kj;
-                    break;
-                }
-            }
-        } else {
-        for (int j = tid; j < na; j += NT) consider(j, (cost_mode == 1 ? 1.0 : 0.0) + c.pi[ct.column_to_row[j]], pb.in_basis[j]);
-        for (int p = tid; p < nstr; p += NT) {
-            int ri[kPriceSlots];
-            double va[kPriceSlots], px[kPriceSlots];
-#pragma unroll
-            for (int u = 0; u < kPriceSlots; ++u) { ri[u] = pe_idx(u * nstr + p); va[u] = pb.pe.val[u * nstr + p]; }
-            const int br = ct.bound_row[p];
-            const int basic = pb.in_basis[na + p];
-            const double cp = costs ? costs[p] : 0.0;
-            const bool is_long = (ri[0] & kLongFlag) != 0;    // more than kPriceSlots entries: priced below
-            ri[0] &= kLongMask;
-#pragma unroll
-            for (int u = 0; u < kPriceSlots; ++u) px[u] = c.pi[ri[u]];
-            const double pb_r = c.pi[br >= 0 ? br : 0];
-            double v = 0.0;
-#pragma unroll
-            for (int u = 0; u < kPriceSlots; ++u) v = fma(px[u], va[u], v);
-            if (br >= 0) v += pb_r;
-            if (costs) v += cp;
-            if (!is_long) consider(na + p, v, basic);
-        }
-        for (int i = tid; i < pb.pe.n_long; i += NT) {             // columns of kPriceSlots + 1 .. kPriceLongSlots entries
-            const int nl = pb.pe.n_long;
-            const int p = pb.pe.long_cols[i];
-            int ri[kPriceLongSlots];
-            double va[kPriceLongSlots], px[kPriceLongSlots];
-#pragma unroll
-            for (int u = 0; u < kPriceLongSlots; ++u) { ri[u] = pe_lidx(u * nl + i); va[u] = pb.pe.lval[u * nl + i]; }
-            const int br = ct.bound_row[p];
-            const int basic = pb.in_basis[na + p];
-            const double cp = costs ? costs[p] : 0.0;
-#pragma unroll
-            for (int u = 0; u < kPriceLongSlots; ++u) px[u] = c.pi[ri[u]];
-            const double pb_r = c.pi[br >= 0 ? br : 0];
-            double v = 0.0;
-#pragma unroll
-            for (int u = 0; u < kPriceLongSlots; ++u) v = fma(px[u], va[u], v);
-            if (br >= 0) v += pb_r;
-            if (costs) v += cp;
-            consider(na + p, v, basic);
-        }
-        for (int i = tid; i < pb.pe.n_very_long; i += NT) {        // the few columns beyond that
-            const int p = pb.pe.very_long[i];
-            double v = 0.0;
-            for (int64_t e = pb.csc.col_ptr[p]; e < pb.csc.col_ptr[p + 1]; ++e) v = fma(c.pi[pb.csc.row_idx[e]], pb.csc.values[e], v);
-            const int br = ct.bound_row[p];
-            if (br >= 0) v += c.pi[br];
-            if (cost_mode == 2) v += ct.cost[p];
-            consider(na + p, v, pb.in_basis[na + p]);
-        }
-        for (int vv = tid; vv < ct.nr_virtual; vv += NT) {
-            const int r0 = ct.vrow0[vv], r1 = ct.vrow1[vv];
-            double v = r0 >= 0 ? (double)ct.vsign[vv] * c.pi[r0] : 0.0;
-            if (r1 >= 0) v += c.pi[r1];
-            consider(na + nstr + vv, v, pb.in_basis[na + nstr + vv]);
-        }
-#ifdef PRICE_DIAG
-        c.clk.lap(FT_PRICE);
-#endif
-        my_j = kj;
-        my_v = kv;
-        block_min_key(c, key, kj);
-#ifdef PRICE_DIAG
-        c.clk.lap(FT_LOAD_STORE);
-#endif
-        if (kj != 0x7fffffff && rule == 2 && pb.tol.tie > 0.0) {
-            // Dantzig ties: lowest index within the tie band of the minimum (every thread re-reads a stripe of d, eight
-            // columns per round so that the loads of a round are in flight together)
-            const double bound = key + pb.tol.tie * fmax(1.0, fabs(key));
-            my_j = 0x7fffffff;
-            for (int j0 = tid; j0 < n; j0 += 8 * NT) {
-                double dv[8];
-                int ib[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) { const int j = min(j0 + u * NT, n - 1); dv[u] = pb.d[j]; ib[u] = pb.in_basis[j]; }
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const int j = j0 + u * NT;
-                    if (j < n && !ib[u] && dv[u] < -pb.tol.cost && dv[u] <= bound && j < my_j) { my_j = j; my_v = dv[u]; }
-                }
-            }
-            kj = block_min_int(c, my_j);
-        }
-        }
-        if (kj == 0x7fffffff) {
-            outcome = DEV_NO_CANDIDATE;
-            if (rule == 1) last_selected = -1;
-            break;
-        }
-#ifdef PRICE_DIAG
-        c.clk.lap(FT_B);
-#endif
-        if (my_j == kj) c.red_d[NW] = my_v;                         // the owner publishes d_q
-        __syncthreads();
-        q = kj; key1 = key; d_q = c.red_d[NW];
-        if (rule == 1) last_selected = q;
-        }
+        if (!pb.external_price && !ft_price(c, pb, pv)) break;
 #ifdef PRICE_DIAG
         c.clk.lap(FT_SCATTER);
 #else
         c.clk.lap(FT_PRICE);
 #endif
-
         // ---- FTRAN (mod.rs:157-190) ------------------------------------------------------------------------------------
-        ft_scatter_column(st, pb, c, q);
+        ft_scatter_column(st, pb, c, pv.rec.q);
         c.clk.lap(FT_SCATTER);
         ft_ftran(lu, st, c);
-
-        // ---- RATIO TEST (tableau/mod.rs:221-247; two passes as relp_device_common.h ratio_body) ------------------------
-        double br;
-        if constexpr (kTier >= 1) {
-        // Layouts 1 and 2: the solve leaves x pivot-indexed and mostly zero.  One coalesced pass over x scatters alpha (dense, for
-        // whoever reads it after the launch) and appends the non-zeros as (row, alpha) pairs to a list; the ratio test, the tie
-        // band, the leaving row and the update of b then touch the list only (tableau/mod.rs:221-247 walks the stored
-        // non-zeros of the column just the same).  Every reduction is order-free (minima), so the list's order does not matter.
-        // pb.alpha (dense, for whoever reads it after the launch): zeroed where the previous column was not -- its list is
-        // still there -- then the non-zeros of x, found through the bitmap, are scattered and listed
-        if constexpr (kTier >= 2) {
-            if (alpha_nnz < 0) { for (int i = tid; i < m; i += NT) pb.alpha[i] = 0.0; }
-            else for (int e = tid; e < alpha_nnz; e += NT) pb.alpha[st.nz_idx[e]] = 0.0;
-            if (tid == 0) c.red_i[2 * NW] = 0;
-            __syncthreads();
-            hs_for_each(c.bx, c.gs, 0, m, [&](int k) {
-                const double v = c.x[k];
-                if (v != 0.0) {
-                    const int i = lu.colperm[k];
-                    pb.alpha[i] = v;
-                    const int e = atomicAdd(&c.red_i[2 * NW], 1);
-                    st.nz_idx[e] = i; st.nz_val[e] = v;
-                }
-            });
-        } else {
-            // (layout 1: x in LDS, no bitmap -- one pass over x with the permutation coalesced from L2 beside it: alpha written
-            // everywhere, the non-zeros listed.  The three passes this replaces each went x[icp[i]], b[i], basis[i] through L2
-            // for every row.)
-            if (tid == 0) c.red_i[2 * NW] = 0;
-            __syncthreads();
-            for (int k0 = tid; k0 < m; k0 += 4 * NT) {
-                int cp[4];
-                double xv[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) { const int k = min(k0 + u * NT, m - 1); xv[u] = c.x[k]; cp[u] = lu.colperm[k]; }
-                asm volatile("" : "+v"(cp[0]), "+v"(cp[1]), "+v"(cp[2]), "+v"(cp[3]));
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    if (k0 + u * NT < m) {
-                        pb.alpha[cp[u]] = xv[u];
-                        if (xv[u] != 0.0) { const int e = atomicAdd(&c.red_i[2 * NW], 1); st.nz_idx[e] = cp[u]; st.nz_val[e] = xv[u]; }
-                    }
-                }
-            }
-        }
-        __syncthreads();
-        const int nnz = c.red_i[2 * NW];
-        alpha_nnz = nnz;
-        if constexpr (kTier >= 2) if (c.clk.on) { c.clk.nnz[0] += nnz; c.clk.nnz[3] += 1; }
-        // (the first entry of every thread stays in registers: a column rarely has more than NT non-zeros)
-        const bool h0 = tid < nnz;
-        const int i0 = h0 ? st.nz_idx[tid] : 0;
-        const double a0 = h0 ? st.nz_val[tid] : 0.0;
-        const double b0 = h0 ? pb.b[i0] : 0.0;
-        double mn = h0 ? row_ratio(a0, b0, pb.tol) : INFINITY;
-        for (int e = tid + NT; e < nnz; e += NT) mn = fmin(mn, row_ratio(st.nz_val[e], pb.b[st.nz_idx[e]], pb.tol));
-        const double gmin = block_min_double(c, mn);
-        if (gmin == INFINITY) { outcome = DEV_NO_ROW; break; }
-        const double bound = gmin + pb.tol.tie * fmax(1.0, fabs(gmin));
-        int best_leave = 0x7fffffff, rr = 0x7fffffff;
-        tie_key_t best = kNoTieKey;
-        const bool by_column = pb.tol.ratio_rule == 0;
-        auto candidate = [&](int i, double a, double bi) {
-            if (row_ratio(a, bi, pb.tol) <= bound) {
-                const int sc = pb.basis[i];
-                if (by_column) { if (sc < best_leave || (sc == best_leave && i < rr)) { best_leave = sc; rr = i; } }
-                else { const tie_key_t k = tie_key(a, sc, 1); if (k < best || (k == best && i < rr)) { best = k; best_leave = sc; rr = i; } }
-            }
-        };
-        if (h0) candidate(i0, a0, b0);
-        for (int e = tid + NT; e < nnz; e += NT) { const int i = st.nz_idx[e]; candidate(i, st.nz_val[e], pb.b[i]); }
-        if (by_column) leaving = block_min_int(c, best_leave);
-        else {
-            const tie_key_t kmin = block_min_key64(c, best);
-            leaving = tie_key_leaving(kmin);
-            if (best != kmin) best_leave = 0x7fffffff;
-        }
-        r = block_min_int(c, best_leave == leaving ? rr : 0x7fffffff);       // (a column is basic in one row)
-        if (best_leave == leaving && rr == r) { c.red_d[NW] = pb.alpha[r]; c.red_d[NW + 1] = pb.b[r]; }
-        __syncthreads();
-        alpha_r = c.red_d[NW];
-        b_r = c.red_d[NW + 1];
-        if (pb.tol.pivot_guard) {                      // (Tolerances::pivot_guard: too small beside the column's largest entry)
-            double mx = h0 ? fabs(a0) : 0.0;
-            for (int e = tid + NT; e < nnz; e += NT) mx = fmax(mx, fabs(st.nz_val[e]));
-            const double amax = -block_min_double(c, -mx);
-            if (alpha_r < pb.tol.guard_rel * amax) { outcome = DEV_NO_ROW; break; }
-        }
-        c.clk.lap(FT_RATIO);
-        br = b_r / alpha_r;
-        if (h0) pb.b[i0] = i0 == r ? br : fma(-a0, br, b0);
-        for (int e = tid + NT; e < nnz; e += NT) {
-            const int i = st.nz_idx[e];
-            pb.b[i] = i == r ? br : fma(-st.nz_val[e], br, pb.b[i]);
-        }
-        __syncthreads();
-        } else {
-        // Rows tid and tid + NT of this thread stay in registers through the three passes and the update of b (one round of
-        // global loads for m <= 2 NT); rows beyond that take the generic loops.
-        const int i0 = tid, i1 = tid + NT;
-        const bool h0 = i0 < m, h1 = i1 < m;
-        const int p0 = c.icp[h0 ? i0 : 0], p1 = c.icp[h1 ? i1 : 0];
-        double b0 = pb.b[h0 ? i0 : 0], b1 = pb.b[h1 ? i1 : 0];
-        const int s0 = pb.basis[h0 ? i0 : 0], s1 = pb.basis[h1 ? i1 : 0];
-        const double a0 = c.x[p0], a1 = c.x[p1];
-        if (h0) pb.alpha[i0] = a0;
-        if (h1) pb.alpha[i1] = a1;
-        const double t0 = h0 ? row_ratio(a0, b0, pb.tol) : INFINITY, t1 = h1 ? row_ratio(a1, b1, pb.tol) : INFINITY;
-        double mn = fmin(t0, t1);
-        for (int i = tid + 2 * NT; i < m; i += NT) {
-            const double a = c.x[c.icp[i]];
-            pb.alpha[i] = a;
-            mn = fmin(mn, row_ratio(a, pb.b[i], pb.tol));
-        }
-        const double gmin = block_min_double(c, mn);
-        if (gmin == INFINITY) { outcome = DEV_NO_ROW; break; }
-        const double bound = gmin + pb.tol.tie * fmax(1.0, fabs(gmin));
-        if (pb.tol.ratio_rule == 0) {                  // the reference: lowest leaving column inside the band
-            int best_leave = 0x7fffffff;
-            if (t0 <= bound) best_leave = s0;
-            if (t1 <= bound) best_leave = min(best_leave, s1);
-            for (int i = tid + 2 * NT; i < m; i += NT) {
-                const double a = c.x[c.icp[i]];
-                if (row_ratio(a, pb.b[i], pb.tol) <= bound) best_leave = min(best_leave, pb.basis[i]);
-            }
-            leaving = block_min_int(c, best_leave);
-        } else {                                       // RELP_RATIO_LARGEST_PIVOT: pivot size first, then the column
-            tie_key_t best = kNoTieKey;
-            if (t0 <= bound) best = tie_key(a0, s0, 1);
-            if (t1 <= bound) { const tie_key_t k1 = tie_key(a1, s1, 1); best = k1 < best ? k1 : best; }
-            for (int i = tid + 2 * NT; i < m; i += NT) {
-                const double a = c.x[c.icp[i]];
-                if (row_ratio(a, pb.b[i], pb.tol) <= bound) { const tie_key_t k = tie_key(a, pb.basis[i], 1); best = k < best ? k : best; }
-            }
-            leaving = tie_key_leaving(block_min_key64(c, best));
-        }
-        // the row of the leaving column
-        int rr = 0x7fffffff;
-        if (h0 && s0 == leaving && t0 <= bound) rr = i0;
-        if (h1 && s1 == leaving && t1 <= bound) rr = i1;             // (a column is basic in one row)
-        for (int i = tid + 2 * NT; i < m; i += NT)
-            if (pb.basis[i] == leaving && row_ratio(c.x[c.icp[i]], pb.b[i], pb.tol) <= bound) rr = i;
-        r = block_min_int(c, rr);
-        // alpha_r and b_r from their owner
-        if (rr == r) { c.red_d[NW] = c.x[c.icp[r]]; c.red_d[NW + 1] = pb.b[r]; }
-        __syncthreads();
-        alpha_r = c.red_d[NW];
-        b_r = c.red_d[NW + 1];
-        if (pb.tol.pivot_guard) {                      // (Tolerances::pivot_guard: too small beside the column's largest entry)
-            double mx = fmax(h0 ? fabs(a0) : 0.0, h1 ? fabs(a1) : 0.0);
-            for (int i = tid + 2 * NT; i < m; i += NT) mx = fmax(mx, fabs(c.x[c.icp[i]]));
-            const double amax = -block_min_double(c, -mx);
-            if (alpha_r < pb.tol.guard_rel * amax) { outcome = DEV_NO_ROW; break; }
-        }
-        c.clk.lap(FT_RATIO);
-
-        // ---- b (carry/mod.rs:283-313) while alpha is still in x -----------------------------------------------------
-        br = b_r / alpha_r;
-        if (h0) { if (i0 == r) pb.b[i0] = br; else if (a0 != 0.0) pb.b[i0] = fma(-a0, br, b0); }
-        if (h1) { if (i1 == r) pb.b[i1] = br; else if (a1 != 0.0) pb.b[i1] = fma(-a1, br, b1); }
-        for (int i = tid + 2 * NT; i < m; i += NT) {
-            if (i == r) pb.b[i] = br;
-            else {
-                const double a = c.x[c.icp[i]];
-                if (a != 0.0) pb.b[i] = fma(-a, br, pb.b[i]);
-            }
-        }
-        __syncthreads();
-        }
-
+        // ---- RATIO TEST, b ------------------------------------------------------------------------------------------------
+        bool row_found;
+        if constexpr (kTier >= 1) row_found = ft_ratio_and_b(c, pb, FtListRows(st, pb, ft_list_alpha(c, lu, st, pb, alpha_nnz)), pv);
+        else row_found = ft_ratio_and_b(c, pb, FtDenseRows<FtCtxT<kTier>>(c, pb), pv);
+        if (!row_found) break;
         c.clk.lap(FT_B);
         // ---- basis inverse: the Forrest-Tomlin update, then row r of the new inverse (mod.rs:92-155, 204-222) --------------
+        const int q = pv.rec.q, r = pv.rec.r;
         const bool updated = ft_update(lu, st, c, r);
         if (tid == 0 && c.journal_n < c.tcap) { st.journal[2 * c.journal_n] = r; st.journal[2 * c.journal_n + 1] = q; }
         c.journal_n += 1;
@@ -1389,93 +1448,27 @@ __global__ __launch_bounds__(NT) void k_ft_run(DeviceLU lu, FtState st, FtProble
             // the eta pool is full: row r of the new inverse = row r of the old one / alpha_r (basis_inverse_rows.rs:42-51
             // states the same division); the factors are rebuilt before the next pivot
             ft_btran(lu, st, c, c.tslot[pl] < 0, st.lev_ub[pl]);
-            rho_scale = 1.0 / alpha_r;
+            rho_scale = 1.0 / pv.rec.alpha_r;
             need_refactor = 1;
         }
-        // ---- -pi, -obj, basis (carry/mod.rs:326-333, 549-570) ----------------------------------------------------------
-        if constexpr (kTier >= 2) {                     // (pb.rho as pb.alpha above; -pi changes where rho is not zero only)
-            if (rho_nnz < 0) { for (int i = tid; i < m; i += NT) pb.rho[i] = 0.0; }
-            else for (int e = tid; e < rho_nnz; e += NT) pb.rho[st.rho_idx[e]] = 0.0;
-            if (tid == 0) c.red_i[2 * NW + 1] = 0;
-            __syncthreads();
-            hs_for_each(c.bx, c.gs, 0, m, [&](int k) {
-                const double rho = c.x[k] * rho_scale;
-                if (rho != 0.0) {
-                    const int i = c.rp[k];
-                    pb.rho[i] = rho;
-                    c.pi[i] = fma(-d_q, rho, c.pi[i]);
-                    st.rho_idx[atomicAdd(&c.red_i[2 * NW + 1], 1)] = i;
-                }
-            });
-            __syncthreads();
-            rho_nnz = c.red_i[2 * NW + 1];
-        } else if constexpr (kTier == 1) {             // (the permutation comes from L2: four rows requested at a time)
-            for (int k0 = tid; k0 < m; k0 += 4 * NT) {
-                int ii[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) ii[u] = c.rp[min(k0 + u * NT, m - 1)];
-                asm volatile("" : "+v"(ii[0]), "+v"(ii[1]), "+v"(ii[2]), "+v"(ii[3]));
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    if (k0 + u * NT < m) {
-                        const double rho = c.x[k0 + u * NT] * rho_scale;
-                        pb.rho[ii[u]] = rho;
-                        c.pi[ii[u]] = fma(-d_q, rho, c.pi[ii[u]]);
-                    }
-                }
-            }
-        } else
-        for (int k = tid; k < m; k += NT) {
-            const int i = c.rp[k];
-            const double rho = c.x[k] * rho_scale;
-            pb.rho[i] = rho;
-            c.pi[i] = fma(-d_q, rho, c.pi[i]);
-        }
-        if (tid == 0) {
-            pb.basis[r] = q;
-            if (leaving < kWrappedArtificialBase) pb.in_basis[leaving] = 0;
-            pb.in_basis[q] = 1;
-            if (pb.trace && iterations < pb.trace_cap) {
-                pb.trace[0 * pb.trace_cap + iterations] = pb.phase;
-                pb.trace[1 * pb.trace_cap + iterations] = q;
-                pb.trace[2 * pb.trace_cap + iterations] = r;
-                pb.trace[3 * pb.trace_cap + iterations] = leaving;
-            }
-        }
-        minus_objective = fma(-d_q, br, minus_objective);
-        if (br == 0.0) degenerate += 1;
-        iterations += 1;
+        // ---- rho, -pi; basis, -obj and the counters (carry/mod.rs:326-333, 549-570) -----------------------------------------
+        ft_rho_and_pi(c, st, pb, pv.rec.d_q, rho_scale, rho_nnz);
+        ft_bookkeeping(pb, pv);
         __syncthreads();
         c.clk.lap(FT_VECTORS);
     }
+    // ---- epilogue ---------------------------------------------------------------------------------------------------------
     ft_store(c, st, pb.minus_pi, need_refactor);
     hs_leave(c, st, true);
     if constexpr (kTier >= 2) if (tid == 0) { st.nzc[0] = alpha_nnz; st.nzc[1] = rho_nnz; }
     c.clk.lap(FT_LOAD_STORE);
     c.clk.flush(st.prof, kTier >= 2);
 #ifdef PASS_DIAG
-    if (tid == 0 && outcome != DEV_RUNNING)
+    if (tid == 0 && pv.rec.outcome != DEV_RUNNING)
         printf("pass_diag: own-pass clocks %llu / %llu over %llu / %llu passes; barrier clocks %llu / %llu over %llu / %llu; fetch clocks %llu / %llu; other set's passes %llu / %llu\n",
                pass_diag[0], pass_diag[1], pass_diag[2], pass_diag[3], pass_diag[4], pass_diag[5], pass_diag[6], pass_diag[7], pass_diag[8], pass_diag[9], pass_diag[10], pass_diag[11]);
 #endif
-    if (tid == 0) {
-        rec->outcome = outcome; rec->q = q; rec->d_q = d_q; rec->r = r; rec->leaving = leaving; rec->alpha_r = alpha_r;
-        rec->b_r = b_r; rec->minus_objective = minus_objective; rec->iterations = iterations;
-        rec->last_selected = last_selected; rec->key1 = key1; rec->degenerate = degenerate;
-    }
-    if (pb.mirror) {                                   // (the host reads these after synchronising the stream)
-        if (tid == 0) {
-            pb.mirror->rec = *rec;
-            pb.mirror->hdr[0] = c.t; pb.mirror->hdr[1] = c.eta_used; pb.mirror->hdr[2] = need_refactor; pb.mirror->hdr[3] = c.journal_n;
-            if constexpr (kTier >= 1) {
-                for (int k = 0; k < 4; ++k) {
-                    pb.mirror->walked[k] = (int32_t)c.clk.passes[k]; pb.mirror->whole[k] = (int32_t)c.clk.total[k];
-                    pb.mirror->sweeps[k] = (int32_t)c.clk.sweeps[k];
-                }
-            }
-        }
-        for (int i = tid; i < m; i += NT) pb.mirror->basis[i] = pb.basis[i];
-    }
+    ft_report<(kTier >= 1)>(pb, c.m, &pv.rec, c.t, c.eta_used, need_refactor, c.journal_n, &c.clk);
 }
 
 // ---- single steps (step-wise API, phase boundaries) ------------------------------------------------------------------
