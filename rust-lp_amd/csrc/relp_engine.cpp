@@ -17,33 +17,8 @@ bool Engine::hip_ok(hipError_t e, const char* what) {
     return false;
 }
 
-void Engine::free_all() {
-    luf_release();
-    auto fr = [](auto*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
-    if (owns_A_) fr(dA_);
-    dA_ = nullptr;
-    fr(dBinv_); fr(d_minus_pi_); fr(d_b_); fr(d_alpha_); fr(d_aq_); fr(d_rho_); fr(d_d_); fr(d_w_); fr(d_cost_);
-    fr(d_basis_); fr(d_column_to_row_); fr(d_bound_row_); fr(d_vrow0_); fr(d_vrow1_); fr(d_vsign_); fr(d_trace_);
-    fr(d_in_basis_); fr(d_rec_);
-    fr(d_part_k1_); fr(d_part_j_);
-    fr(d_fcols_); fr(d_fcount_); fr(d_fmask_); fr(d_fstats_); fr(d_R0c_);
-    fr(dT0_); fr(dR0_); fr(d_b_alt_); fr(d_basis_alt_); fr(d_shadow_); fr(d_shadow_meta_);
-    if (h_lu_buf_) { (void)hipHostFree(h_lu_buf_); h_lu_buf_ = nullptr; h_lu_cap_ = 0; }
-    if (h_basis_) { (void)hipHostFree(h_basis_); h_basis_ = nullptr; }
-    if (h_mirror_) { (void)hipHostFree(h_mirror_); h_mirror_ = nullptr; d_mirror_ = nullptr; }
-    fr(d_cost_store_); fr(d_idcol_); fr(d_rmin_);
-    fr(d_msg_cand_); fr(d_msg_cands_); fr(d_msg_slice_); fr(d_msg_slices_); fr(d_msg_rho_); fr(d_msg_status_); fr(d_msg_statuses_);
-    fr(d_v_); fr(d_W_); fr(d_wr_); fr(d_R_); fr(d_S_); fr(d_pos_of_row_);
-    fr(d_cptr_); fr(d_cidx_); fr(d_cval_); fr(d_lu_buf_); fr(d_lu_buf_alt_); fr(d_lu_scratch_); fr(d_ft_buf_); fr(d_pe_buf_);
-    if (h_ft_hdr_) { (void)hipHostFree(h_ft_hdr_); h_ft_hdr_ = nullptr; }
-    if (h_rec_) { (void)hipHostFree(h_rec_); h_rec_ = nullptr; }
-    for (auto e : prof_ev_) (void)hipEventDestroy(e);
-    prof_ev_.clear();
-    if (owns_stream_ && stream_) { (void)hipStreamDestroy(stream_); }
-    stream_ = nullptr;
-}
-
-Engine::~Engine() { rccl_release(); free_all(); }
+// the buffers free themselves (members), the events and the stream go last (EngineQueue)
+Engine::~Engine() { rccl_release(); luf_release(); }
 
 ColumnTable Engine::table() const {
     ColumnTable ct;
@@ -94,11 +69,14 @@ DeferredUpdate Engine::deferred() const {
     return du;
 }
 
-relp_status_t Engine::download_rec() {
-    HIP_TRY(hipMemcpyAsync(h_rec_, d_rec_, sizeof(PivotRecord), hipMemcpyDeviceToHost, stream_));
+// device -> host on the engine's stream, and wait for it
+relp_status_t Engine::fetch(void* dst, const void* src, size_t bytes) {
+    HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream_));
     HIP_TRY(hipStreamSynchronize(stream_));
     return RELP_OK;
 }
+
+relp_status_t Engine::download_rec() { return fetch(h_rec_, d_rec_, sizeof(PivotRecord)); }
 
 relp_status_t Engine::upload_rec() {
     HIP_TRY(hipMemcpyAsync(d_rec_, h_rec_, sizeof(PivotRecord), hipMemcpyHostToDevice, stream_));
@@ -114,6 +92,33 @@ relp_status_t Engine::set_stream(hipStream_t s) {
     return RELP_OK;
 }
 
+Switches Switches::read() {
+    Switches s;
+    auto given = [](const char* name) { return std::getenv(name) != nullptr; };
+    auto num = [](const char* name, int unset) { const char* e = std::getenv(name); return e ? std::atoi(e) : unset; };
+    s.debug = given("RELP_DEBUG");
+    s.pivot_guard_set = given("RELP_PIVOT_GUARD");
+    if (s.pivot_guard_set) s.pivot_guard = std::atof(std::getenv("RELP_PIVOT_GUARD"));
+    s.tab_flush_all = num("RELP_TAB_FLUSH_ALL", 0) != 0;
+    s.tab_load_batch = num("RELP_TAB_LOAD_BATCH", 0);
+    s.tab_w_split = num("RELP_TAB_W_SPLIT", 0);
+    s.fused_update = num("RELP_FUSED_UPDATE", 1) != 0;
+    s.lu_lookahead_set = given("RELP_LU_LOOKAHEAD");
+    s.lu_lookahead = num("RELP_LU_LOOKAHEAD", 8);
+    s.fuse_lanes = num("RELP_FUSE_LANES", 256);
+    s.lu_device_factor = num("RELP_LU_DEVICE_FACTOR", 0);
+    s.lu_pipeline_short = num("RELP_LU_PIPELINE_SHORT", 0) != 0;
+    s.ft_big = num("RELP_FT_BIG", -1);
+    s.ft_hyper_set = given("RELP_FT_HYPER");
+    s.ft_hyper = num("RELP_FT_HYPER", 0x9);
+    s.ft_grid_price = given("RELP_FT_GRID_PRICE") ? (num("RELP_FT_GRID_PRICE", 0) != 0 ? 1 : 0) : -1;
+    if (given("RELP_LUF_BUMP_CAP")) s.luf_bump_cap = std::max(16, num("RELP_LUF_BUMP_CAP", 0));
+    s.luf_dense = std::max(0, std::min(64, num("RELP_LUF_DENSE", 64)));
+    s.dump_basis_set = given("RELP_DUMP_BASIS");
+    if (s.dump_basis_set) s.dump_basis = std::getenv("RELP_DUMP_BASIS");
+    return s;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Construction: MatrixData layout (matrix_data.rs:198-268, 308-371, 432-452) and the partially
 // artificial start (partially.rs:125-206, carry/mod.rs:381-426)
@@ -121,6 +126,9 @@ relp_status_t Engine::set_stream(hipStream_t s) {
 relp_status_t Engine::create(const relp_matrix_data_t& md, const relp_config_t& cfg) {
     (void)hipGetLastError();                               // (the launch check at the end must only see this create's launches)
     cfg_ = cfg;
+    sw_ = Switches::read();
+    // (measurement aid: the relative threshold of the guard that relp_run's pivot rescue switches on)
+    if (sw_.pivot_guard_set && cfg_.pivot_rescue && cfg_.shard_count <= 1) guard_rel_ = sw_.pivot_guard;
     if (cfg_.shard_count < 1) cfg_.shard_count = 1;
     if (cfg_.poll_interval < 1) cfg_.poll_interval = 64;
     if (const relp_status_t lst = lay_.build(md, cfg_, &err_)) return lst;
@@ -144,11 +152,10 @@ relp_status_t Engine::create(const relp_matrix_data_t& md, const relp_config_t& 
         if (src_ld < lay_.mc) return fail(RELP_E_ARG, "dense_ld < nr_constraints");
         // In sharded mode `dense` holds only the owned columns [col_lo, col_hi).
         if (md.matrix_memory == RELP_MEM_DEVICE && (src_ld % 2) == 0) {
-            dA_ = const_cast<double*>(md.dense); ld_a_ = src_ld; owns_A_ = false;          // zero-copy adoption
+            dA_.adopt(const_cast<double*>(md.dense)); ld_a_ = src_ld;                      // zero-copy adoption
         } else {
             ld_a_ = round_up(std::max<int64_t>(lay_.mc, 1), 2);
-            HIP_TRY(dev_alloc(&dA_, ld_a_ * std::max(n_local, 1)));
-            owns_A_ = true;
+            HIP_TRY(dA_.alloc(ld_a_ * std::max(n_local, 1)));
             if (n_local > 0 && lay_.mc > 0)
                 HIP_TRY(hipMemcpy2D(dA_, ld_a_ * sizeof(double), md.dense, src_ld * sizeof(double), lay_.mc * sizeof(double),
                                     n_local, md.matrix_memory == RELP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
@@ -162,18 +169,14 @@ relp_status_t Engine::create(const relp_matrix_data_t& md, const relp_config_t& 
         for (int64_t p = e0; p < e1; ++p)
             if (md.row_idx[p] < 0 || md.row_idx[p] >= lay_.mc) return fail(RELP_E_ARG, "row index out of range");
         const int64_t cells = ld_a_ * std::max(n_local, 1);
-        HIP_TRY(dev_alloc(&dA_, cells));
-        owns_A_ = true;
+        HIP_TRY(dA_.alloc(cells));
         HIP_TRY(hipMemset(dA_, 0, (size_t)cells * sizeof(double)));
         if (e1 > e0) {
-            int64_t* t_ptr = nullptr; int32_t* t_idx = nullptr; double* t_val = nullptr;
-            auto drop = [&]() { if (t_ptr) (void)hipFree(t_ptr); if (t_idx) (void)hipFree(t_idx); if (t_val) (void)hipFree(t_val); };
-            if (hipMalloc(reinterpret_cast<void**>(&t_ptr), sizeof(int64_t) * (size_t)(n_local + 1)) != hipSuccess ||
-                hipMalloc(reinterpret_cast<void**>(&t_idx), sizeof(int32_t) * (size_t)(e1 - e0)) != hipSuccess ||
-                hipMalloc(reinterpret_cast<void**>(&t_val), sizeof(double) * (size_t)(e1 - e0)) != hipSuccess) {
-                drop();
+            DeviceBuf<int64_t> t_ptr; DeviceBuf<int32_t> t_idx; DeviceBuf<double> t_val;       // staging: freed on every way out
+            if (t_ptr.alloc_raw(sizeof(int64_t) * (size_t)(n_local + 1)) != hipSuccess ||
+                t_idx.alloc_raw(sizeof(int32_t) * (size_t)(e1 - e0)) != hipSuccess ||
+                t_val.alloc_raw(sizeof(double) * (size_t)(e1 - e0)) != hipSuccess)
                 return fail(RELP_E_ALLOC, "staging the CSC arrays");
-            }
             hipError_t err = hipMemcpy(t_ptr, md.col_ptr + lay_.col_lo, sizeof(int64_t) * (size_t)(n_local + 1), hipMemcpyHostToDevice);
             if (err == hipSuccess) err = hipMemcpy(t_idx, md.row_idx + e0, sizeof(int32_t) * (size_t)(e1 - e0), hipMemcpyHostToDevice);
             if (err == hipSuccess) err = hipMemcpy(t_val, md.values + e0, sizeof(double) * (size_t)(e1 - e0), hipMemcpyHostToDevice);
@@ -181,7 +184,6 @@ relp_status_t Engine::create(const relp_matrix_data_t& md, const relp_config_t& 
                 launch_csc_to_dense(t_ptr, t_idx, t_val, n_local, dA_, ld_a_, nullptr);
                 err = hipDeviceSynchronize();
             }
-            drop();
             if (err != hipSuccess) return fail(RELP_E_HIP, "dense copy of the CSC input");
         }
     } else {
@@ -191,45 +193,38 @@ relp_status_t Engine::create(const relp_matrix_data_t& md, const relp_config_t& 
     ld_b_ = round_up(lay_.m, 16);
     const int64_t rows_local = std::max(lay_.row_hi - lay_.row_lo, 1);
     // the tableau engine reads B^-1 off the identity columns of T; the explicit inverse is not stored
-    HIP_TRY(dev_alloc(&dBinv_, (tableau_ || lu_) ? 16 : rows_local * ld_b_));
-    HIP_TRY(dev_alloc(&d_minus_pi_, ld_b_));
-    HIP_TRY(dev_alloc(&d_b_, ld_b_));
-    HIP_TRY(dev_alloc(&d_alpha_, ld_b_));
-    HIP_TRY(dev_alloc(&d_aq_, ld_b_));
-    HIP_TRY(dev_alloc(&d_rho_, ld_b_));
-    HIP_TRY(dev_alloc(&d_w_, ld_b_));
-    HIP_TRY(dev_alloc(&d_d_, n_alloc_));
-    HIP_TRY(dev_alloc(&d_cost_, lay_.nr_normal));
-    HIP_TRY(dev_alloc(&d_basis_, lay_.m));
-    HIP_TRY(dev_alloc(&d_column_to_row_, lay_.nr_artificial));
-    HIP_TRY(dev_alloc(&d_bound_row_, lay_.nr_normal));
-    HIP_TRY(dev_alloc(&d_vrow0_, lay_.nr_virtual));
-    HIP_TRY(dev_alloc(&d_vrow1_, lay_.nr_virtual));
-    HIP_TRY(dev_alloc(&d_vsign_, lay_.nr_virtual));
-    HIP_TRY(dev_alloc(&d_in_basis_, n_alloc_));
-    HIP_TRY(dev_alloc(&d_rec_, 1));
+    HIP_TRY(dBinv_.alloc((tableau_ || lu_) ? 16 : rows_local * ld_b_));
+    HIP_TRY(d_minus_pi_.alloc(ld_b_));
+    HIP_TRY(d_b_.alloc(ld_b_));
+    HIP_TRY(d_alpha_.alloc(ld_b_));
+    HIP_TRY(d_aq_.alloc(ld_b_));
+    HIP_TRY(d_rho_.alloc(ld_b_));
+    HIP_TRY(d_w_.alloc(ld_b_));
+    HIP_TRY(d_d_.alloc(n_alloc_));
+    HIP_TRY(d_cost_.alloc(lay_.nr_normal));
+    HIP_TRY(d_basis_.alloc(lay_.m));
+    HIP_TRY(d_column_to_row_.alloc(lay_.nr_artificial));
+    HIP_TRY(d_bound_row_.alloc(lay_.nr_normal));
+    HIP_TRY(d_vrow0_.alloc(lay_.nr_virtual));
+    HIP_TRY(d_vrow1_.alloc(lay_.nr_virtual));
+    HIP_TRY(d_vsign_.alloc(lay_.nr_virtual));
+    HIP_TRY(d_in_basis_.alloc(n_alloc_));
+    HIP_TRY(d_rec_.alloc(1));
     {
         const int64_t slots = price_structural_blocks(lay_.col_lo, lay_.col_hi) + (lay_.nr_artificial + lay_.nr_virtual + 255) / 256 + 8 +
                               tab_scan_blocks(n_alloc_) + price_csc_blocks(0, lay_.nr_normal);
-        HIP_TRY(dev_alloc(&d_part_k1_, slots));
-        HIP_TRY(dev_alloc(&d_part_j_, slots));
+        HIP_TRY(d_part_k1_.alloc(slots));
+        HIP_TRY(d_part_j_.alloc(slots));
     }
     block_ = cfg_.update_block < 0 ? (lay_.m >= 4096 ? 64 : 0) : std::min(cfg_.update_block, 128);
     if (lu_) {
         // pivots between refactorisations (the reference refactors after 10 updates, lower_upper/mod.rs:199;
         // here an update is one column of W, so longer blocks are cheap)
         block_ = cfg_.update_block < 0 ? 128 : std::max(1, std::min(cfg_.update_block, 128));
-        HIP_TRY(dev_alloc(&d_lu_scratch_, ld_b_));
-        {   // environment switches of the LU engine, read once per engine
-            const char* la = std::getenv("RELP_LU_LOOKAHEAD");
-            const char* fl = std::getenv("RELP_FUSE_LANES");
-            const char* df = std::getenv("RELP_LU_DEVICE_FACTOR");
-            luf_enabled_ = df && std::atoi(df) != 0;
-            luf_download_ = df && std::atoi(df) == 2;
-            lu_lookahead_env_ = la ? std::atoi(la) : 8;
-            lu_lookahead_set_ = la != nullptr;
-            lu_fuse_lanes_env_ = fl ? std::atoi(fl) : 256;
-        }
+        HIP_TRY(d_lu_scratch_.alloc(ld_b_));
+        HIP_TRY(h_basis_.alloc(sizeof(int32_t) * (size_t)std::max(lay_.m, 1)));      // (rows are only ever removed)
+        luf_enabled_ = sw_.lu_device_factor != 0;
+        luf_download_ = sw_.lu_device_factor == 2;
         relp_status_t fst = ft_plan_and_alloc();           // Forrest-Tomlin on the device when the LDS budget allows
         if (fst) return fst;
     }
@@ -245,57 +240,51 @@ relp_status_t Engine::create(const relp_matrix_data_t& md, const relp_config_t& 
         const int64_t n_owned = std::max(lay_.sc_hi - lay_.sc_lo, 1);
         ld_t_ = round_up(lay_.m, 2);
         ld_r_ = round_up(n_owned, 2);
-        HIP_TRY(dev_alloc(&dT0_, ld_t_ * n_owned));
-        HIP_TRY(dev_alloc(&dR0_, ld_r_ * (block_ + 1)));        // + one scratch row (d_aq_big)
+        HIP_TRY(dT0_.alloc(ld_t_ * n_owned));
+        HIP_TRY(dR0_.alloc(ld_r_ * (block_ + 1)));        // + one scratch row (d_aq_big)
         {   // the flush rewrites only the columns with a nonzero R0 entry unless RELP_TAB_FLUSH_ALL=1
-            const char* e = std::getenv("RELP_TAB_FLUSH_ALL");
-            flush_all_ = e && std::atoi(e) != 0;
-            HIP_TRY(dev_alloc(&d_fstats_, 2));
+            flush_all_ = sw_.tab_flush_all;
+            HIP_TRY(d_fstats_.alloc(2));
             if (!flush_all_) {
-                HIP_TRY(dev_alloc(&d_fcols_, n_owned));
-                HIP_TRY(dev_alloc(&d_fcount_, 1));
-                HIP_TRY(dev_alloc(&d_fmask_, (n_owned + 63) / 64));
-                HIP_TRY(dev_alloc(&d_R0c_, ld_r_ * block_));
+                HIP_TRY(d_fcols_.alloc(n_owned));
+                HIP_TRY(d_fcount_.alloc(1));
+                HIP_TRY(d_fmask_.alloc((n_owned + 63) / 64));
+                HIP_TRY(d_R0c_.alloc(ld_r_ * block_));
             }
         }
         {   // pending rows loaded per round trip in the per-pivot kernels (1 = one by one, the control), and the workgroups per 256
-            // rows that share W <- E W in the fused update; both read once, here
-            const char* e = std::getenv("RELP_TAB_LOAD_BATCH");
-            load_batch_ = tab_load_batch(e ? std::atoi(e) : 0);
-            const char* w = std::getenv("RELP_TAB_W_SPLIT");
-            w_split_ = w && std::atoi(w) >= 1 ? std::min(std::atoi(w), 16) : kTabSplitDefault;
+            // rows that share W <- E W in the fused update: RELP_TAB_LOAD_BATCH, RELP_TAB_W_SPLIT
+            load_batch_ = tab_load_batch(sw_.tab_load_batch);
+            w_split_ = sw_.tab_w_split >= 1 ? std::min(sw_.tab_w_split, 16) : kTabSplitDefault;
         }
         {   // two launches per pivot instead of three in the single-GPU loop (RELP_FUSED_UPDATE=0: k_ratio_blocks + k_tab_update_all)
-            const char* e = std::getenv("RELP_FUSED_UPDATE");
-            fused_update_ = !(e && std::atoi(e) == 0);      // (also the native sharded loop, relp_shard_run)
+            fused_update_ = sw_.fused_update;               // (also the native sharded loop, relp_shard_run)
             if (cfg_.pivot_rescue && cfg_.shard_count == 1) fused_update_ = false;       // (the pivot guard lives in the shared ratio epilogue)
             if (fused_update_) {
-                HIP_TRY(dev_alloc(&d_b_alt_, ld_b_));
-                HIP_TRY(dev_alloc(&d_basis_alt_, lay_.m));
-                HIP_TRY(dev_alloc(&d_shadow_, std::max(block_, 1) + 1));
-                HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_shadow_meta_), 2 * sizeof(int32_t)));
+                HIP_TRY(d_b_alt_.alloc(ld_b_));
+                HIP_TRY(d_basis_alt_.alloc(lay_.m));
+                HIP_TRY(d_shadow_.alloc(std::max(block_, 1) + 1));
+                HIP_TRY(d_shadow_meta_.alloc_raw(2 * sizeof(int32_t)));
                 const int32_t none[2] = {-1, 0};
                 HIP_TRY(hipMemcpy(d_shadow_meta_, none, sizeof none, hipMemcpyHostToDevice));
             }
         }
-        HIP_TRY(dev_alloc(&d_cost_store_, n_store_));
-        HIP_TRY(dev_alloc(&d_idcol_, lay_.m));
+        HIP_TRY(d_cost_store_.alloc(n_store_));
+        HIP_TRY(d_idcol_.alloc(lay_.m));
     }
-    if (block_ > 0 && ft_) {
-        HIP_TRY(dev_alloc(&d_v_, ld_b_));                  // (no W: the update file lives in FtState)
-    } else if (block_ > 0) {
-        HIP_TRY(dev_alloc(&d_v_, ld_b_));
-        HIP_TRY(dev_alloc(&d_W_, ld_b_ * block_));
-        if (!tableau_) HIP_TRY(dev_alloc(&d_R_, ld_b_ * block_));
-        HIP_TRY(dev_alloc(&d_wr_, block_));
-        HIP_TRY(dev_alloc(&d_S_, block_));
-        HIP_TRY(dev_alloc(&d_pos_of_row_, lay_.m));
+    if (block_ > 0) HIP_TRY(d_v_.alloc(ld_b_));
+    if (block_ > 0 && !ft_) {                              // (Forrest-Tomlin: no W, the update file lives in FtState)
+        HIP_TRY(d_W_.alloc(ld_b_ * block_));
+        if (!tableau_) HIP_TRY(d_R_.alloc(ld_b_ * block_));
+        HIP_TRY(d_wr_.alloc(block_));
+        HIP_TRY(d_S_.alloc(block_));
+        HIP_TRY(d_pos_of_row_.alloc(lay_.m));
         HIP_TRY(hipMemset(d_pos_of_row_, 0xFF, sizeof(int32_t) * lay_.m));      // -1 everywhere
     }
-    HIP_TRY(dev_alloc(&d_rmin_, lay_.m / 8 + 2));          // block minima of the ratio test (8 or 256 rows per block)
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_rec_), sizeof(PivotRecord), hipHostMallocDefault));
+    HIP_TRY(d_rmin_.alloc(lay_.m / 8 + 2));          // block minima of the ratio test (8 or 256 rows per block)
+    HIP_TRY(h_rec_.alloc(sizeof(PivotRecord)));
     trace_cap_ = std::max(cfg_.trace_capacity, 0);
-    if (trace_cap_ > 0) HIP_TRY(dev_alloc(&d_trace_, 4 * trace_cap_));
+    if (trace_cap_ > 0) HIP_TRY(d_trace_.alloc(4 * trace_cap_));
 
     auto up = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
         return bytes ? hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) : hipSuccess;
@@ -318,8 +307,7 @@ relp_status_t Engine::create(const relp_matrix_data_t& md, const relp_config_t& 
         // T0 = the original matrix in row space (B = I), d = c - c_B' T0 with the phase-1 costs
         idcol_h_ = lay_.basis;                               // the initial basis column of row k is e_k
         HIP_TRY(up(d_idcol_, idcol_h_.data(), sizeof(int32_t) * lay_.m));
-        const double* A = dA_ - (int64_t)lay_.col_lo * ld_a_;
-        launch_tab_build(tview(), A, ld_a_, table(), stream_);
+        launch_tab_build(tview(), A_base(), ld_a_, table(), stream_);
         cost_store_h_.assign(n_store_, 0.0);
         for (int32_t k = 0; k < lay_.nr_artificial; ++k) cost_store_h_[k] = 1.0;
         std::vector<double> w(ld_b_, 0.0);
@@ -411,9 +399,7 @@ void Engine::enqueue_price(int cost_mode, const double* vec, const PivotRecord* 
         launch_price_virtual(ct, vec, d_d_, cost_mode, rec, stream_);
         return;
     }
-    // dA_ holds the owned columns only: shift the base so that global column p indexes correctly
-    const double* A = dA_ - (int64_t)lay_.col_lo * ld_a_;
-    launch_price_structural(A, ld_a_, ct, vec, d_d_, p_lo, p_hi, cost_mode, rec, stream_);
+    launch_price_structural(A_base(), ld_a_, ct, vec, d_d_, p_lo, p_hi, cost_mode, rec, stream_);
     if (p_lo > 0 || p_hi < lay_.nr_normal) launch_price_mask_unowned(ct, d_d_, p_lo, p_hi, rec, stream_);
     launch_price_virtual(ct, vec, d_d_, cost_mode, rec, stream_);
 }
@@ -436,8 +422,8 @@ void Engine::enqueue_iteration_tableau(int rule) {
         launch_tab_ratio_update_all(tv, du, sp, lay_.m, d_alpha_, d_b_, d_b_alt_, d_basis_, d_basis_alt_, d_in_basis_, d_trace_,
                                     trace_cap_, tolerances(), d_rmin_, d_shadow_, d_shadow_meta_, d_rec_, stream_);
         prof_end();
-        std::swap(d_b_, d_b_alt_);
-        std::swap(d_basis_, d_basis_alt_);
+        d_b_.swap(d_b_alt_);
+        d_basis_.swap(d_basis_alt_);
         shadow_pending_ = true;
         if (++since_flush_ >= block_) enqueue_flush();
         return;
@@ -461,15 +447,13 @@ void Engine::enqueue_iteration(int rule) {
     if (tableau_) { enqueue_iteration_tableau(rule); return; }
     if (lu_) { enqueue_iteration_lu(rule); return; }
     const ColumnTable ct = table();
-    const double* A = dA_ - (int64_t)lay_.col_lo * ld_a_;
-    double* Binv = dBinv_ - (int64_t)lay_.row_lo * ld_b_;
-    const int n = nr_columns();
+    const double* A = A_base();
+    double* Binv = Binv_base();
     // PRICE with the partial argmin fused in, then one single-workgroup launch that picks the
     // entering column and builds it in row space
-    SelectPartials sp;
-    sp.k1 = d_part_k1_; sp.j = d_part_j_; sp.in_basis = d_in_basis_; sp.tol_cost = cfg_.tol_cost; sp.rule = rule;
     const int nb_struct = price_structural_blocks(lay_.col_lo, lay_.col_hi);
-    sp.n = n; sp.offset = 0; sp.nb_struct = nb_struct; sp.tol_tie = cfg_.tol_tie; sp.p_lo = lay_.col_lo; sp.cols_per_slot = 8;
+    SelectPartials sp = tab_partials(rule);
+    sp.nb_struct = nb_struct; sp.p_lo = lay_.col_lo;
     const int nb_virt = price_virtual_blocks(ct);
     prof_begin(RELP_K_PRICE);
     if (lay_.col_lo > 0 || lay_.col_hi < lay_.nr_normal) {
@@ -559,23 +543,27 @@ void Engine::enqueue_flush() {
         // from the flushed tableau, d = c - c_B' T0, so that rounding does not pile up over thousands of
         // pivots (one extra pass over T0 per kRepriceEveryFlushes * K pivots).
         if (++flushes_since_reprice_ >= kRepriceEveryFlushes) {
-            flushes_since_reprice_ = 0;
-            const TableauView tv = tview();
-            const int rule = phase_ == 1 ? cfg_.phase_one_rule : cfg_.phase_two_rule;
-            launch_tab_basis_costs(tv, d_basis_, d_cost_store_, d_w_, stream_);
-            launch_tab_price_init(tv, d_w_, d_cost_store_, stream_);
-            launch_tab_scan(tv, tab_partials(rule), d_rec_, stream_);
+            tableau_reprice();
         }
         return;
     }
     const DeferredUpdate du = deferred();
-    double* Binv = dBinv_ - (int64_t)lay_.row_lo * ld_b_;
+    double* Binv = Binv_base();
     prof_begin(RELP_K_FLUSH);
     launch_flush_snapshot(du, Binv, ld_b_, lay_.row_lo, lay_.row_hi, d_rec_, stream_);
     launch_flush_apply(du, Binv, ld_b_, lay_.m, lay_.row_lo, lay_.row_hi, d_rec_, stream_);
     launch_flush_reset(du, d_rec_, stream_);
     prof_end();
     since_flush_ = 0;
+}
+
+// d = c - c_B' T0 from the tableau as it is, and the PRICE partials of the new d
+void Engine::tableau_reprice() {
+    const TableauView tv = tview();
+    flushes_since_reprice_ = 0;
+    launch_tab_basis_costs(tv, d_basis_, d_cost_store_, d_w_, stream_);
+    launch_tab_price_init(tv, d_w_, d_cost_store_, stream_);
+    launch_tab_scan(tv, tab_partials(current_rule()), d_rec_, stream_);
 }
 
 relp_status_t Engine::flush() {
@@ -601,14 +589,10 @@ relp_status_t Engine::flush() {
 
 // ---- step-wise API ------------------------------------------------------------------------------
 relp_status_t Engine::select_primal_pivot_column(int rule, int32_t* found, int32_t* column, double* cost) {
-    relp_status_t st = download_rec();
+    relp_status_t st = edit_rec();
     if (st) return st;
-    h_rec_->outcome = DEV_RUNNING;
-    if ((st = upload_rec())) return st;
     if (tableau_) {
-        SelectPartials sp;
-        sp.k1 = d_part_k1_; sp.j = d_part_j_; sp.in_basis = d_in_basis_; sp.tol_cost = cfg_.tol_cost; sp.rule = rule;
-        sp.n = nr_columns(); sp.offset = 0; sp.nb_struct = 0; sp.tol_tie = cfg_.tol_tie; sp.p_lo = 0; sp.cols_per_slot = 8;
+        const SelectPartials sp = tab_partials(rule);
         launch_tab_scan(tview(), sp, d_rec_, stream_);
         launch_tab_select(tview(), sp, tab_scan_blocks(lay_.sc_hi - lay_.sc_lo), d_rec_, stream_);
     } else {
@@ -626,18 +610,13 @@ relp_status_t Engine::select_primal_pivot_column(int rule, int32_t* found, int32
 relp_status_t Engine::relative_costs(double* out_n) {
     if (!tableau_) enqueue_price(phase_, d_minus_pi_, nullptr, lay_.col_lo, lay_.col_hi);
     const double* src = tableau_ ? d_d_ + (phase_ == 1 ? 0 : tab_na_) : d_d_;     // the tableau keeps d up to date
-    HIP_TRY(hipMemcpyAsync(out_n, src, sizeof(double) * nr_columns(), hipMemcpyDeviceToHost, stream_));
-    HIP_TRY(hipStreamSynchronize(stream_));
-    return RELP_OK;
+    return fetch(out_n, src, sizeof(double) * nr_columns());
 }
 
 relp_status_t Engine::generate_column(int32_t column, double* out_m) {
     if (column < 0 || column >= nr_columns()) return fail(RELP_E_ARG, "column out of range");
-    relp_status_t st = download_rec();
+    const relp_status_t st = edit_rec([&](PivotRecord& r) { r.q = column; });
     if (st) return st;
-    h_rec_->outcome = DEV_RUNNING;
-    h_rec_->q = column;
-    if ((st = upload_rec())) return st;
     if (tableau_) {
         launch_tab_column(tview(), deferred(), d_alpha_, d_rec_, stream_);
     } else if (lu_ && ft_) {
@@ -648,10 +627,8 @@ relp_status_t Engine::generate_column(int32_t column, double* out_m) {
         launch_apply_w(deferred(), lay_.m, d_v_, d_alpha_, d_rec_, stream_);
     } else {
         enqueue_flush();                               // the step-wise calls work on the explicit inverse
-        const double* A = dA_ - (int64_t)lay_.col_lo * ld_a_;
-        double* Binv = dBinv_ - (int64_t)lay_.row_lo * ld_b_;
-        launch_build_column(A, ld_a_, table(), lay_.m, d_aq_, d_rec_, stream_);
-        launch_ftran(Binv, ld_b_, lay_.m, lay_.row_lo, lay_.row_hi, d_aq_, d_alpha_, 0, d_rec_, stream_);
+        launch_build_column(A_base(), ld_a_, table(), lay_.m, d_aq_, d_rec_, stream_);
+        launch_ftran(Binv_base(), ld_b_, lay_.m, lay_.row_lo, lay_.row_hi, d_aq_, d_alpha_, 0, d_rec_, stream_);
     }
     if (out_m) HIP_TRY(hipMemcpyAsync(out_m, d_alpha_, sizeof(double) * lay_.m, hipMemcpyDeviceToHost, stream_));
     HIP_TRY(hipStreamSynchronize(stream_));
@@ -667,9 +644,9 @@ relp_status_t Engine::generate_element(int32_t row, int32_t column, double* out)
     return RELP_OK;
 }
 
-relp_status_t Engine::select_primal_pivot_row(int32_t* found, int32_t* row) {
-    launch_ratio(d_alpha_, d_b_, d_basis_, lay_.m, tolerances(), d_rec_, stream_);
-    relp_status_t st = download_rec();
+// what the ratio test just enqueued decided; the record is re-armed after it has been read
+relp_status_t Engine::read_pivot_row(int32_t* found, int32_t* row) {
+    const relp_status_t st = download_rec();
     if (st) return st;
     const bool ok = h_rec_->outcome == DEV_RUNNING;
     if (found) *found = ok ? 1 : 0;
@@ -678,16 +655,15 @@ relp_status_t Engine::select_primal_pivot_row(int32_t* found, int32_t* row) {
     return upload_rec();
 }
 
+relp_status_t Engine::select_primal_pivot_row(int32_t* found, int32_t* row) {
+    launch_ratio(d_alpha_, d_b_, d_basis_, lay_.m, tolerances(), d_rec_, stream_);
+    return read_pivot_row(found, row);
+}
+
 relp_status_t Engine::select_primal_pivot_row_of(const double* column, int32_t* found, int32_t* row) {
     HIP_TRY(hipMemcpyAsync(d_aq_, column, sizeof(double) * lay_.m, hipMemcpyHostToDevice, stream_));
     launch_ratio(d_aq_, d_b_, d_basis_, lay_.m, tolerances(), d_rec_, stream_);
-    relp_status_t st = download_rec();
-    if (st) return st;
-    const bool ok = h_rec_->outcome == DEV_RUNNING;
-    if (found) *found = ok ? 1 : 0;
-    if (ok && row) *row = h_rec_->r;
-    h_rec_->outcome = DEV_RUNNING;
-    return upload_rec();
+    return read_pivot_row(found, row);
 }
 
 relp_status_t Engine::bring_into_basis(int32_t column, int32_t row, double cost, int32_t* leaving) {
@@ -700,17 +676,14 @@ relp_status_t Engine::bring_into_basis(int32_t column, int32_t row, double cost,
     HIP_TRY(hipMemcpy(&lv, d_basis_ + row, sizeof(int32_t), hipMemcpyDeviceToHost));
     if (alpha_r == 0.0) return fail(RELP_E_ZERO_PIVOT, "Pivot value can't be zero.");
     if (!tableau_ && !lu_) enqueue_flush();
-    if ((st = download_rec())) return st;               // the flush may have reset the block counters
-    h_rec_->outcome = DEV_RUNNING;
-    h_rec_->q = column; h_rec_->d_q = cost; h_rec_->r = row; h_rec_->leaving = lv; h_rec_->alpha_r = alpha_r; h_rec_->b_r = b_r;
-    if ((st = upload_rec())) return st;
+    st = edit_rec([&](PivotRecord& r) {                 // (a download of its own: the flush may have reset the block counters)
+        r.q = column; r.d_q = cost; r.r = row; r.leaving = lv; r.alpha_r = alpha_r; r.b_r = b_r;
+    });
+    if (st) return st;
     if (tableau_) {
         const TableauView tv = tview();
         const DeferredUpdate du = deferred();
-        SelectPartials sp;
-        sp.k1 = d_part_k1_; sp.j = d_part_j_; sp.in_basis = d_in_basis_; sp.tol_cost = cfg_.tol_cost;
-        sp.rule = phase_ == 1 ? cfg_.phase_one_rule : cfg_.phase_two_rule;
-        sp.n = tv.n; sp.offset = 0; sp.nb_struct = 0; sp.tol_tie = cfg_.tol_tie; sp.p_lo = 0; sp.cols_per_slot = 8;
+        const SelectPartials sp = tab_partials(current_rule());
         launch_eta_prepare(du, d_rec_, stream_);
         launch_tab_row_update(tv, du, sp, d_rec_, stream_);
         launch_update_w(du, lay_.m, d_alpha_, d_rec_, stream_);
@@ -755,10 +728,9 @@ relp_status_t Engine::bring_into_basis(int32_t column, int32_t row, double cost,
         if (++since_flush_ >= block_) enqueue_flush();
         HIP_TRY(hipStreamSynchronize(stream_));
         if (leaving) *leaving = lv;
-        if (lu_status_) { const relp_status_t e = lu_status_; lu_status_ = RELP_OK; return e; }
-        return RELP_OK;
+        return take_lu_status();
     }
-    double* Binv = dBinv_ - (int64_t)lay_.row_lo * ld_b_;
+    double* Binv = Binv_base();
     launch_compute_rho(Binv, ld_b_, lay_.m, lay_.row_lo, lay_.row_hi, d_rho_, d_rec_, stream_);
     launch_update_vectors(lay_.m, d_alpha_, d_rho_, d_b_, d_minus_pi_, d_basis_, d_in_basis_, d_trace_, trace_cap_, d_rec_,
                           stream_);
@@ -792,7 +764,6 @@ relp_status_t Engine::rescue_unbar_all() {
 // entry worth pivoting on.
 relp_status_t Engine::run(int64_t max_iters, int64_t* done, int32_t* outcome) {
     if (!cfg_.pivot_rescue || cfg_.shard_count > 1) return run_loop(max_iters, done, outcome);
-    if (const char* e = std::getenv("RELP_PIVOT_GUARD")) guard_rel_ = std::atof(e);          // (measurement aid: the guard's relative threshold)
     struct GuardScope { bool& g; GuardScope(bool& x) : g(x) { g = true; } ~GuardScope() { g = false; } } guard_scope(pivot_guard_on_);
     int64_t total = 0;
     int32_t oc = RELP_RUNNING;
@@ -832,9 +803,7 @@ relp_status_t Engine::run(int64_t max_iters, int64_t* done, int32_t* outcome) {
                 if (st) return st;
                 if (found) {
                     ++rescue_small_pivots_; ++total;
-                    if ((st = download_rec())) return st;
-                    h_rec_->outcome = DEV_RUNNING;                          // (the update kernels have counted and traced the pivot)
-                    if ((st = upload_rec())) return st;
+                    if ((st = edit_rec())) return st;                        // (the update kernels have counted and traced the pivot)
                     if (total >= max_iters) { oc = RELP_RUNNING; break; }
                     continue;
                 }
@@ -847,9 +816,7 @@ relp_status_t Engine::run(int64_t max_iters, int64_t* done, int32_t* outcome) {
                 HIP_TRY(hipMemcpy(d_in_basis_ + q, &two, 1, hipMemcpyHostToDevice));
                 barred_.push_back(q);
                 ++rescue_barred_;
-                if ((st = download_rec())) return st;
-                h_rec_->outcome = DEV_RUNNING;
-                if ((st = upload_rec())) return st;
+                if ((st = edit_rec())) return st;
                 continue;
             }
             break;
@@ -860,9 +827,7 @@ relp_status_t Engine::run(int64_t max_iters, int64_t* done, int32_t* outcome) {
                 if ((st = rescue_unbar_all())) return st;
                 confirming = true;
                 ++rescue_confirmations_;
-                if ((st = download_rec())) return st;
-                h_rec_->outcome = DEV_RUNNING;
-                if ((st = upload_rec())) return st;
+                if ((st = edit_rec())) return st;
                 continue;
             }
             // barred again without a pivot in between: they stay out, the phase ends
@@ -880,12 +845,25 @@ relp_status_t Engine::run(int64_t max_iters, int64_t* done, int32_t* outcome) {
     return RELP_OK;
 }
 
+// What the downloaded record says about the phase: no candidate ends it (phase 1: the phase boundary runs here, unless the
+// pivot rescue holds it back), no pivot row is unbounded / the reference's panic; anything else leaves RELP_RUNNING.
+relp_status_t Engine::outcome_of_record(int32_t* oc) {
+    if (h_rec_->outcome == DEV_NO_CANDIDATE) {
+        if (hold_phase_end_) *oc = kHeldNoCandidate;
+        else if (phase_ == 2) *oc = RELP_OPTIMAL;
+        else return finish_phase_one(oc);
+    } else if (h_rec_->outcome == DEV_NO_ROW) {
+        *oc = phase_ == 2 ? RELP_UNBOUNDED : RELP_NO_ROW_PHASE_ONE;
+    }
+    return RELP_OK;
+}
+
 relp_status_t Engine::run_loop(int64_t max_iters, int64_t* done, int32_t* outcome) {
     if (ft_) return run_ft(max_iters, done, outcome);
     relp_status_t st = download_rec();
     if (st) return st;
     const long long start = h_rec_->iterations;
-    const int rule = phase_ == 1 ? cfg_.phase_one_rule : cfg_.phase_two_rule;
+    const int rule = current_rule();
     // Phase 1 often ends after very few pivots (none at all with a full slack basis): poll at 1, 2, 4, ...
     // there so that an early end does not leave a long tail of no-op launches queued.
     if (tableau_) {
@@ -901,7 +879,7 @@ relp_status_t Engine::run_loop(int64_t max_iters, int64_t* done, int32_t* outcom
     for (int64_t it = 0; it < max_iters && h_rec_->outcome == DEV_RUNNING; ++it) {
         enqueue_iteration(rule);
         ++enqueued;
-        if (lu_status_) { const relp_status_t e = lu_status_; lu_status_ = RELP_OK; return e; }
+        if (lu_status_) return take_lu_status();
         if (reinvert_interval_ > 0 && ++since_reinvert_ >= reinvert_interval_) {
             if ((st = download_rec())) return st;
             if (h_rec_->outcome != DEV_RUNNING) break;
@@ -914,19 +892,13 @@ relp_status_t Engine::run_loop(int64_t max_iters, int64_t* done, int32_t* outcom
         }
     }
     }
-    if (std::getenv("RELP_DEBUG") && enqueued >= 64)
+    if (sw_.debug && enqueued >= 64)
         std::fprintf(stderr, "[relp] run: %lld pivots enqueued in %.1f us of host time each\n", (long long)enqueued,
                      std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_enq0).count() / enqueued);
     if ((st = download_rec())) return st;
     if (hipGetLastError() != hipSuccess) return fail(RELP_E_HIP, "kernel launch failed");
     int32_t oc = RELP_RUNNING;
-    if (h_rec_->outcome == DEV_NO_CANDIDATE) {
-        if (hold_phase_end_) oc = kHeldNoCandidate;
-        else if (phase_ == 2) oc = RELP_OPTIMAL;
-        else if ((st = finish_phase_one(&oc))) return st;
-    } else if (h_rec_->outcome == DEV_NO_ROW) {
-        oc = phase_ == 2 ? RELP_UNBOUNDED : RELP_NO_ROW_PHASE_ONE;
-    }
+    if ((st = outcome_of_record(&oc))) return st;
     if (done) *done = h_rec_->iterations - start;          // includes the zero-level pivots of the phase boundary
     if (outcome) *outcome = oc;
     return RELP_OK;
@@ -960,19 +932,33 @@ relp_status_t Engine::finish_phase_one(int32_t* outcome) {
     return RELP_OK;
 }
 
+// The head the two zero-level removers share: the basis on the host and the basic artificial variables, ascending.
+relp_status_t Engine::basic_artificials(std::vector<int32_t>* basis, std::vector<int32_t>* arts) {
+    HIP_TRY(hipStreamSynchronize(stream_));            // null-stream copy below vs. kernels on stream_
+    basis->resize(lay_.m);
+    HIP_TRY(hipMemcpy(basis->data(), d_basis_, sizeof(int32_t) * lay_.m, hipMemcpyDeviceToHost));
+    arts->clear();
+    for (int32_t v : *basis) if (v < lay_.nr_artificial) arts->push_back(v);
+    std::sort(arts->begin(), arts->end());
+    return RELP_OK;
+}
+
+// No eligible column: phase_one.rs:252 pushes the artificial's index; RELP_ARTIFICIAL_TEXTBOOK its own row, and remove_rows
+// moves the artificial into that position first (relp_engine.h)
+void Engine::keep_artificial_row(int32_t a, std::vector<int32_t>& rows_to_remove) {
+    if (cfg_.artificial_removal == RELP_ARTIFICIAL_TEXTBOOK) { stuck_artificials_.push_back(a); rows_to_remove.push_back(lay_.column_to_row[a]); }
+    else rows_to_remove.push_back(a);
+}
+
 // phase_one.rs:223-260 (pivots "at zero level"; pushes the artificial index like the reference)
 relp_status_t Engine::remove_artificial_basis_variables(std::vector<int32_t>& rows_to_remove) {
-    HIP_TRY(hipStreamSynchronize(stream_));            // null-stream copies below vs. kernels on stream_
-    std::vector<int32_t> basis(lay_.m);
-    HIP_TRY(hipMemcpy(basis.data(), d_basis_, sizeof(int32_t) * lay_.m, hipMemcpyDeviceToHost));
-    std::vector<int32_t> arts;
-    for (int32_t v : basis) if (v < lay_.nr_artificial) arts.push_back(v);
+    std::vector<int32_t> basis, arts;
+    relp_status_t st = basic_artificials(&basis, &arts);
+    if (st) return st;
     if (arts.empty()) return RELP_OK;
-    std::sort(arts.begin(), arts.end());
     const int n = nr_columns();
     std::vector<double> d(n), tau(n);
     std::vector<uint8_t> inb(n);
-    relp_status_t st;
     const bool textbook = cfg_.artificial_removal == RELP_ARTIFICIAL_TEXTBOOK;
     for (int32_t a : arts) {
         int32_t pivot_row = lay_.column_to_row[a];             // phase_one.rs:236: the row the artificial STARTED in
@@ -981,17 +967,13 @@ relp_status_t Engine::remove_artificial_basis_variables(std::vector<int32_t>& ro
         // tableau row pivot_row over every column: (row of B^-1) . a_j, no cost term
         if (tableau_) {
             launch_tab_row(tview(), deferred(), pivot_row, d_aq_big(), d_rec_, stream_);        // single GPU: all columns
-            HIP_TRY(hipMemcpyAsync(tau.data(), d_aq_big(), sizeof(double) * n, hipMemcpyDeviceToHost, stream_));
         } else if (lu_) {
-            if (ft_) launch_ft_btran(dlu_, fts_, ft_problem(0), pivot_row, nullptr, d_rho_, stream_);
-            else launch_lu_btran(dlu_, deferred(), nullptr, pivot_row, d_rho_, d_lu_scratch_, nullptr, stream_);
+            lu_btran(pivot_row, nullptr, d_rho_);
             enqueue_price(0, d_rho_, nullptr, 0, lay_.nr_normal);
-            HIP_TRY(hipMemcpyAsync(tau.data(), d_d_, sizeof(double) * n, hipMemcpyDeviceToHost, stream_));
         } else {
-            double* Binv = dBinv_ - (int64_t)lay_.row_lo * ld_b_;
-            enqueue_price(0, Binv + (int64_t)pivot_row * ld_b_, nullptr, lay_.col_lo, lay_.col_hi);
-            HIP_TRY(hipMemcpyAsync(tau.data(), d_d_, sizeof(double) * n, hipMemcpyDeviceToHost, stream_));
+            enqueue_price(0, Binv_base() + (int64_t)pivot_row * ld_b_, nullptr, lay_.col_lo, lay_.col_hi);
         }
+        HIP_TRY(hipMemcpyAsync(tau.data(), tableau_ ? d_aq_big() : (double*)d_d_, sizeof(double) * n, hipMemcpyDeviceToHost, stream_));
         HIP_TRY(hipMemcpyAsync(inb.data(), d_in_basis_, n, hipMemcpyDeviceToHost, stream_));
         HIP_TRY(hipStreamSynchronize(stream_));
         int32_t q = -1;
@@ -1000,13 +982,7 @@ relp_status_t Engine::remove_artificial_basis_variables(std::vector<int32_t>& ro
             if (!textbook && std::fabs(d[j]) > cfg_.tol_cost) continue;        // phase_one.rs:241: cost.is_zero()
             if (std::fabs(tau[j]) > cfg_.tol_pivot) { q = j; break; }
         }
-        // phase_one.rs:252 pushes the artificial's index; RELP_ARTIFICIAL_TEXTBOOK its own row, and remove_rows moves the
-        // artificial into that position first (relp_engine.h)
-        if (q < 0) {
-            if (textbook) { stuck_artificials_.push_back(a); rows_to_remove.push_back(lay_.column_to_row[a]); }
-            else rows_to_remove.push_back(a);
-            continue;
-        }
+        if (q < 0) { keep_artificial_row(a, rows_to_remove); continue; }
         if ((st = generate_column(q, nullptr))) return st;
         if ((st = bring_into_basis(q, pivot_row, d[q], nullptr))) return st;
         basis[pivot_row] = q;
@@ -1051,16 +1027,14 @@ relp_status_t Engine::switch_to_phase_two(const std::vector<int32_t>& rows_to_re
     }
     HIP_TRY(hipMemcpy(d_in_basis_, flags.data(), flags.size(), hipMemcpyHostToDevice));
     // -pi = -(c_B' B^-1) (create_minus_pi_from_artificial, carry/mod.rs:214-248), accumulated over rows in order
-    std::vector<double> w(lay_.m, 0.0), b(lay_.m);
-    for (int32_t i = 0; i < lay_.m; ++i) if (basis[i] < lay_.nr_normal) w[i] = lay_.cost[basis[i]];
+    std::vector<double> w = basic_costs(basis, 2, 1.0), b(lay_.m);
     if (cfg_.shard_count > 1 && !tableau_)
         for (double v : w) if (v != 0.0) return fail(RELP_E_UNSUPPORTED, "sharded phase switch needs an all-slack basis");
     if (lu_) for (auto& v : w) v = -v;                 // BTRAN with rhs -c_B gives -pi directly
     HIP_TRY(hipMemcpy(d_w_, w.data(), sizeof(double) * lay_.m, hipMemcpyHostToDevice));
     if (lu_) {
-        if (lu_status_) { const relp_status_t e = lu_status_; lu_status_ = RELP_OK; return e; }
-        if (ft_) launch_ft_btran(dlu_, fts_, ft_problem(0), -1, d_w_, d_minus_pi_, stream_);
-        else launch_lu_btran(dlu_, deferred(), d_w_, -1, d_minus_pi_, d_lu_scratch_, nullptr, stream_);
+        if (lu_status_) return take_lu_status();
+        lu_btran(-1, d_w_, d_minus_pi_);
     } else if (tableau_) {
         // phase-2 reduced costs of every stored column: d = c - c_B' T (the artificial block keeps cost 0)
         cost_store_h_.assign(n_store_, 0.0);
@@ -1069,19 +1043,37 @@ relp_status_t Engine::switch_to_phase_two(const std::vector<int32_t>& rows_to_re
         launch_tab_price_init(tview(), d_w_, d_cost_store_, stream_);
         tab_partials_valid_ = false;
     } else {
-        double* Binv = dBinv_ - (int64_t)lay_.row_lo * ld_b_;
-        launch_weighted_column_sums(Binv, ld_b_, lay_.m, d_w_, d_minus_pi_, stream_);
+        launch_weighted_column_sums(Binv_base(), ld_b_, lay_.m, d_w_, d_minus_pi_, stream_);
     }
-    // -obj = -sum_i b_i c_B(i) (create_minus_obj_from_artificial, carry/mod.rs:258-271)
+    // -obj = -sum_i b_i c_B(i) (create_minus_obj_from_artificial, carry/mod.rs:258-271); b has arrived once the record has
     HIP_TRY(hipMemcpyAsync(b.data(), d_b_, sizeof(double) * lay_.m, hipMemcpyDeviceToHost, stream_));
-    if ((st = download_rec())) return st;
+    return edit_rec([&](PivotRecord& r) { r.minus_objective = -objective_of(basis, b); r.last_selected = -1; r.phase = 2; });
+}
+
+// Costs of the basic columns by row, times `sign`: Cost::One on artificial columns in phase 1 (tableau column indices), the
+// variable costs in phase 2 (provider indices); a wrapped artificial index has none.  ld_b_ long, zero elsewhere.
+std::vector<double> Engine::basic_costs(const std::vector<int32_t>& basis, int phase, double sign) const {
+    std::vector<double> w(ld_b_, 0.0);
+    for (int32_t i = 0; i < lay_.m; ++i) {
+        const int32_t j = basis[i];
+        if (j >= kWrappedArtificialBase) continue;
+        if (phase == 1) w[i] = j < lay_.nr_artificial ? sign : 0.0;
+        else if (j < lay_.nr_normal) w[i] = sign * lay_.cost[j];
+    }
+    return w;
+}
+
+// Objective of the basis with values b in the current phase: the artificial variables in phase 1, c_B' b in phase 2
+// (summed over the rows in order)
+double Engine::objective_of(const std::vector<int32_t>& basis, const std::vector<double>& b) const {
     double objective = 0.0;
-    for (int32_t i = 0; i < lay_.m; ++i) if (basis[i] < lay_.nr_normal) objective += b[i] * lay_.cost[basis[i]];
-    h_rec_->minus_objective = -objective;
-    h_rec_->outcome = DEV_RUNNING;
-    h_rec_->last_selected = -1;
-    h_rec_->phase = 2;
-    return upload_rec();
+    for (int32_t i = 0; i < lay_.m; ++i) {
+        const int32_t j = basis[i];
+        if (j >= kWrappedArtificialBase) continue;
+        if (phase_ == 1) { if (j < lay_.nr_artificial) objective += b[i]; }
+        else if (j < lay_.nr_normal) objective += lay_.cost[j] * b[i];
+    }
+    return objective;
 }
 
 // Rank-deficient problems (filter/generic_wrapper.rs:51, carry/mod.rs:650-689, basis_inverse_rows.rs:190-204):
@@ -1176,13 +1168,12 @@ relp_status_t Engine::remove_rows(const std::vector<int32_t>& rows) {
                 if (perm[i] != i) std::copy(B0.begin() + (size_t)perm[i] * ld_b_, B0.begin() + (size_t)(perm[i] + 1) * ld_b_, Bh.begin() + (size_t)i * ld_b_);
         }
     }
-    const int64_t ld_new = ld_b_;
-    std::vector<double> Bn(no_inv ? 1 : (size_t)lay_.m * ld_new, 0.0), bn(lay_.m, 0.0);
+    std::vector<double> Bn(no_inv ? 1 : (size_t)lay_.m * ld_b_, 0.0), bn(lay_.m, 0.0);
     std::vector<int32_t> basisn(lay_.m, 0);
     for (int32_t i = 0; i < lay_.m; ++i) {
         if (map[i] < 0) continue;
         if (!no_inv)
-            for (int32_t j = 0; j < lay_.m; ++j) if (map[j] >= 0) Bn[(size_t)map[i] * ld_new + map[j]] = Bh[(size_t)i * ld_b_ + j];
+            for (int32_t j = 0; j < lay_.m; ++j) if (map[j] >= 0) Bn[(size_t)map[i] * ld_b_ + map[j]] = Bh[(size_t)i * ld_b_ + j];
         bn[map[i]] = b[i];
         basisn[map[i]] = basis[i];
     }
@@ -1197,7 +1188,7 @@ relp_status_t Engine::remove_rows(const std::vector<int32_t>& rows) {
         std::vector<double> An((size_t)ld_a_ * lay_.nr_normal, 0.0);
         for (int32_t j = 0; j < lay_.nr_normal; ++j)
             for (int32_t i = 0; i < lay_.mc; ++i) if (map[i] >= 0) An[(size_t)j * ld_a_ + map[i]] = Ah[(size_t)j * ld_a_ + i];
-        if (!owns_A_) { HIP_TRY(dev_alloc(&dA_, (int64_t)An.size())); owns_A_ = true; }
+        if (!dA_.owned()) HIP_TRY(dA_.alloc((int64_t)An.size()));      // (the caller's matrix was adopted: it stays as it is)
         HIP_TRY(hipMemcpy(dA_, An.data(), An.size() * sizeof(double), hipMemcpyHostToDevice));
     }
     lay_.remove_rows(map);
@@ -1255,52 +1246,83 @@ relp_status_t Engine::build_basis_columns(const std::vector<int32_t>& basis,
 // The dense tableau's counterpart: T0 = B^-1 [artificial | A + bound rows | virtual] recomputed column by column from
 // a fresh factorisation of the basis (one launch: workgroup c solves stored column c), b = B^-1 rhs, d re-priced
 // from the new T0, -obj from b.  T0 is otherwise only ever updated (every flush adds W R0 to it).
-relp_status_t Engine::retabulate() {
-    SettledScope settled(*this);
+//
+// The shared start of both rebuilds: pending updates folded in, b kept for relp_config_t.auto_reinversion, the basis on the
+// host, its columns factorised (hlu_) and the factors on the device.  `factored` false: lu_factor declined (numerically
+// singular for the LU) and the caller keeps the updated state.
+relp_status_t Engine::refactor_current_basis(std::vector<int32_t>* basis, std::vector<double>* b_before, bool* factored) {
+    *factored = false;
     since_reinvert_ = 0;
-    retab_done_ = false;
     enqueue_flush();
     HIP_TRY(hipStreamSynchronize(stream_));
-    std::vector<double> b_before;
-    if (cfg_.auto_reinversion) { b_before.resize(lay_.m); HIP_TRY(hipMemcpy(b_before.data(), d_b_, sizeof(double) * lay_.m, hipMemcpyDeviceToHost)); }
-    std::vector<int32_t> basis(lay_.m);
-    HIP_TRY(hipMemcpy(basis.data(), d_basis_, sizeof(int32_t) * lay_.m, hipMemcpyDeviceToHost));
+    if (cfg_.auto_reinversion) { b_before->resize(lay_.m); HIP_TRY(hipMemcpy(b_before->data(), d_b_, sizeof(double) * lay_.m, hipMemcpyDeviceToHost)); }
+    basis->resize(lay_.m);
+    HIP_TRY(hipMemcpy(basis->data(), d_basis_, sizeof(int32_t) * lay_.m, hipMemcpyDeviceToHost));
     std::vector<std::vector<std::pair<int32_t, double>>> cols;
-    relp_status_t st = build_basis_columns(basis, &cols);
+    relp_status_t st = build_basis_columns(*basis, &cols);
     if (st) return st;
     std::string msg;
-    if (!lu_factor(lay_.m, cols, &hlu_, &msg)) return RELP_OK;        // keep the updated tableau
+    if (!lu_factor(lay_.m, cols, &hlu_, &msg)) return RELP_OK;
     if ((st = lu_upload_factors())) return st;
-    if (!d_lu_scratch_) HIP_TRY(dev_alloc(&d_lu_scratch_, ld_b_));
+    if ((st = ensure_lu_scratch())) return st;
+    *factored = true;
+    return RELP_OK;
+}
+
+relp_status_t Engine::ensure_lu_scratch() {
+    if (!d_lu_scratch_) HIP_TRY(d_lu_scratch_.alloc(ld_b_));
+    return RELP_OK;
+}
+
+// With the factors of the basis on the device: the rows of B^-1 by m unit BTRANs written in place (the one-off
+// `BasisInverseRows::invert`, basis_inverse_rows.rs:103-129), -pi = -(w' B^-1) (carry/mod.rs:214-248) and b = B^-1 rhs, whose
+// download into `b` is enqueued, not awaited.  `rearm`: the record is re-armed before the FTRAN (a warm start may find it decided).
+relp_status_t Engine::inverse_from_factors(const std::vector<double>& w, bool rearm, std::vector<double>* b) {
+    HIP_TRY(hipMemsetAsync(dBinv_, 0, sizeof(double) * (size_t)lay_.m * ld_b_, stream_));
+    DeferredUpdate none = deferred();
+    none.kmax = 0;
+    launch_lu_btran_rows(dlu_, none, dBinv_, ld_b_, d_lu_scratch_, stream_);
+    HIP_TRY(hipMemcpyAsync(d_w_, w.data(), sizeof(double) * ld_b_, hipMemcpyHostToDevice, stream_));
+    HIP_TRY(hipMemcpyAsync(d_aq_, lay_.rhs.data(), sizeof(double) * lay_.m, hipMemcpyHostToDevice, stream_));
+    HIP_TRY(hipStreamSynchronize(stream_));             // w, lay_.rhs are host buffers
+    launch_weighted_column_sums(dBinv_, ld_b_, lay_.m, d_w_, d_minus_pi_, stream_);
+    if (rearm) { const relp_status_t st = edit_rec(); if (st) return st; }
+    launch_ftran(dBinv_, ld_b_, lay_.m, 0, lay_.m, d_aq_, d_b_, 0, d_rec_, stream_);
+    b->resize(lay_.m);
+    HIP_TRY(hipMemcpyAsync(b->data(), d_b_, sizeof(double) * lay_.m, hipMemcpyDeviceToHost, stream_));
+    return RELP_OK;
+}
+
+static double weighted_sum(const std::vector<double>& w, const std::vector<double>& b) {     // over the rows in order
+    double s = 0.0;
+    for (size_t i = 0; i < b.size(); ++i) s += w[i] * b[i];
+    return s;
+}
+
+relp_status_t Engine::retabulate() {
+    SettledScope settled(*this);
+    retab_done_ = false;
+    std::vector<double> b_before;
+    std::vector<int32_t> basis;
+    bool factored = false;
+    relp_status_t st = refactor_current_basis(&basis, &b_before, &factored);
+    if (st || !factored) return st;                     // (not factored: keep the updated tableau)
     const TableauView tv = tview();
-    const double* A = dA_ - (int64_t)lay_.col_lo * ld_a_;
     // every stored column, the artificial block included: phase 2 never prices it, but B^-1 and -pi are read off the
     // columns that were the identity originally (relp_get_basis_inverse, relp_basis_inverse_row, relp_get_minus_pi)
     const int32_t c_first = lay_.sc_lo;
     ColumnTable storage = table();
     storage.nr_artificial = tab_na_;                    // storage columns keep the artificial block in front
-    if (!launch_lu_ftran_cols(dlu_, tv, A, ld_a_, storage, c_first, lay_.sc_hi - c_first, stream_)) return RELP_OK;
+    if (!launch_lu_ftran_cols(dlu_, tv, A_base(), ld_a_, storage, c_first, lay_.sc_hi - c_first, stream_)) return RELP_OK;
     HIP_TRY(hipMemcpyAsync(d_aq_, lay_.rhs.data(), sizeof(double) * lay_.m, hipMemcpyHostToDevice, stream_));
     HIP_TRY(hipStreamSynchronize(stream_));
     launch_lu_ftran(dlu_, d_aq_, d_b_, d_lu_scratch_, nullptr, stream_);                 // b = B^-1 rhs
-    // d = c - c_B' T0 and the PRICE partials, as after every few flushes
-    const int rule = phase_ == 1 ? cfg_.phase_one_rule : cfg_.phase_two_rule;
-    launch_tab_basis_costs(tv, d_basis_, d_cost_store_, d_w_, stream_);
-    launch_tab_price_init(tv, d_w_, d_cost_store_, stream_);
-    launch_tab_scan(tv, tab_partials(rule), d_rec_, stream_);
+    tableau_reprice();                                  // as after every few flushes
     tab_partials_valid_ = true;
-    flushes_since_reprice_ = 0;
     std::vector<double> b(lay_.m);
     HIP_TRY(hipMemcpyAsync(b.data(), d_b_, sizeof(double) * lay_.m, hipMemcpyDeviceToHost, stream_));
     if ((st = download_rec())) return st;
-    double objective = 0.0;
-    for (int32_t i = 0; i < lay_.m; ++i) {
-        const int32_t j = basis[i];
-        if (j >= kWrappedArtificialBase) continue;
-        if (phase_ == 1) { if (j < lay_.nr_artificial) objective += b[i]; }
-        else if (j < lay_.nr_normal) objective += lay_.cost[j] * b[i];
-    }
-    h_rec_->minus_objective = -objective;
+    h_rec_->minus_objective = -objective_of(basis, b);
     ++reinversions_;
     retab_done_ = true;
     if (cfg_.auto_reinversion) auto_reinversion_adapt(b_before, b);
@@ -1311,42 +1333,15 @@ relp_status_t Engine::reinvert() {
     SettledScope settled(*this);
     if (lu_ || cfg_.shard_count > 1) return fail(RELP_E_UNSUPPORTED, "re-inversion is for the unsharded revised and tableau engines");
     if (tableau_) return retabulate();
-    since_reinvert_ = 0;
-    enqueue_flush();
-    HIP_TRY(hipStreamSynchronize(stream_));
-    std::vector<double> b_before;
-    if (cfg_.auto_reinversion) { b_before.resize(lay_.m); HIP_TRY(hipMemcpy(b_before.data(), d_b_, sizeof(double) * lay_.m, hipMemcpyDeviceToHost)); }
-    std::vector<int32_t> basis(lay_.m);
-    HIP_TRY(hipMemcpy(basis.data(), d_basis_, sizeof(int32_t) * lay_.m, hipMemcpyDeviceToHost));
-    std::vector<std::vector<std::pair<int32_t, double>>> cols;
-    relp_status_t st = build_basis_columns(basis, &cols);
-    if (st) return st;
-    std::string msg;
-    if (!lu_factor(lay_.m, cols, &hlu_, &msg)) return RELP_OK;        // numerically singular for the LU: keep the updated inverse
-    if ((st = lu_upload_factors())) return st;
-    if (!d_lu_scratch_) HIP_TRY(dev_alloc(&d_lu_scratch_, ld_b_));
-    HIP_TRY(hipMemsetAsync(dBinv_, 0, sizeof(double) * (size_t)lay_.m * ld_b_, stream_));
-    DeferredUpdate none = deferred();
-    none.kmax = 0;
-    launch_lu_btran_rows(dlu_, none, dBinv_, ld_b_, d_lu_scratch_, stream_);
-    // costs of the phase: Cost::One on artificial columns in phase 1, the variable costs in phase 2
-    std::vector<double> w(ld_b_, 0.0), b(lay_.m);
-    for (int32_t i = 0; i < lay_.m; ++i) {
-        const int32_t j = basis[i];
-        if (j >= kWrappedArtificialBase) continue;
-        if (phase_ == 1) w[i] = j < lay_.nr_artificial ? 1.0 : 0.0;
-        else if (j < lay_.nr_normal) w[i] = lay_.cost[j];
-    }
-    HIP_TRY(hipMemcpyAsync(d_w_, w.data(), sizeof(double) * ld_b_, hipMemcpyHostToDevice, stream_));
-    HIP_TRY(hipMemcpyAsync(d_aq_, lay_.rhs.data(), sizeof(double) * lay_.m, hipMemcpyHostToDevice, stream_));
-    HIP_TRY(hipStreamSynchronize(stream_));
-    launch_weighted_column_sums(dBinv_, ld_b_, lay_.m, d_w_, d_minus_pi_, stream_);
-    launch_ftran(dBinv_, ld_b_, lay_.m, 0, lay_.m, d_aq_, d_b_, 0, d_rec_, stream_);
-    HIP_TRY(hipMemcpyAsync(b.data(), d_b_, sizeof(double) * lay_.m, hipMemcpyDeviceToHost, stream_));
+    std::vector<double> b_before, b;
+    std::vector<int32_t> basis;
+    bool factored = false;
+    relp_status_t st = refactor_current_basis(&basis, &b_before, &factored);
+    if (st || !factored) return st;                     // (not factored: keep the updated inverse)
+    const std::vector<double> w = basic_costs(basis, phase_, 1.0);
+    if ((st = inverse_from_factors(w, false, &b))) return st;
     if ((st = download_rec())) return st;
-    double objective = 0.0;
-    for (int32_t i = 0; i < lay_.m; ++i) objective += w[i] * b[i];
-    h_rec_->minus_objective = -objective;
+    h_rec_->minus_objective = -weighted_sum(w, b);
     ++reinversions_;
     if (cfg_.auto_reinversion) auto_reinversion_adapt(b_before, b);
     return upload_rec();
@@ -1361,90 +1356,78 @@ void Engine::auto_reinversion_adapt(const std::vector<double>& before, const std
     last_reinvert_drift_ = diff / scale;
     if (last_reinvert_drift_ > 1e-7) reinvert_interval_ = std::max<int64_t>(32, reinvert_interval_ / 2);
     else if (last_reinvert_drift_ < 1e-10) reinvert_interval_ = std::min<int64_t>(1024, reinvert_interval_ * 2);
-    if (std::getenv("RELP_DEBUG")) std::fprintf(stderr, "[relp] rebuild %lld: b moved by %.2e (relative), interval now %lld\n", (long long)reinversions_, last_reinvert_drift_, (long long)reinvert_interval_);
+    if (sw_.debug) std::fprintf(stderr, "[relp] rebuild %lld: b moved by %.2e (relative), interval now %lld\n", (long long)reinversions_, last_reinvert_drift_, (long long)reinvert_interval_);
+}
+
+// from_basis: every column a provider column, none twice.  `flags`: the in_basis flags of the basis.
+relp_status_t Engine::check_basis_columns(const std::vector<int32_t>& basis, std::vector<uint8_t>* flags) {
+    flags->assign(n_alloc_, 0);
+    for (int32_t v : basis) {
+        if (v < 0 || v >= lay_.n_provider) return fail(RELP_E_ARG, "from_basis: column out of range");
+        if ((*flags)[v]) return fail(RELP_E_SINGULAR, "from_basis: duplicate column");
+        (*flags)[v] = 1;
+    }
+    return RELP_OK;
 }
 
 relp_status_t Engine::from_basis(const int32_t* basis_columns) {
     // InverseMaintener::from_basis (carry/mod.rs:428-463): any basis on the LU and the revised engine (the
     // latter factorises on the host and runs the m unit solves on the device; slack bases are a signed permutation and take a shortcut).
     if (cfg_.shard_count > 1) return fail(RELP_E_UNSUPPORTED, "from_basis in sharded mode");
+    const std::vector<int32_t> basis(basis_columns, basis_columns + lay_.m);
+    std::vector<uint8_t> flags;
+    relp_status_t st;
+    auto phase_two = [](PivotRecord& r) { r.last_selected = -1; r.phase = 2; };
     if (tableau_) {
         // T = B^-1 [A | I] for the given basis: factorise it (host, like every refactorisation), then every stored column
         // by one FTRAN each in a single launch (re-tabulation), b = B^-1 rhs, d = c - c_B' T
         enqueue_flush();
         HIP_TRY(hipStreamSynchronize(stream_));
-        std::vector<int32_t> basis(basis_columns, basis_columns + lay_.m);
-        std::vector<uint8_t> flags(n_alloc_, 0);
-        for (int32_t v : basis) {
-            if (v < 0 || v >= lay_.n_provider) return fail(RELP_E_ARG, "from_basis: column out of range");
-            if (flags[v]) return fail(RELP_E_SINGULAR, "from_basis: duplicate column");
-            flags[v] = 1;
-        }
+        if ((st = check_basis_columns(basis, &flags))) return st;
         const int32_t keep_na = lay_.nr_artificial, keep_phase = phase_;
         lay_.nr_artificial = 0; phase_ = 2;
         HIP_TRY(hipMemcpy(d_basis_, basis.data(), sizeof(int32_t) * lay_.m, hipMemcpyHostToDevice));
         cost_store_h_.assign(n_store_, 0.0);
         for (int32_t p = 0; p < lay_.nr_normal; ++p) cost_store_h_[tab_na_ + p] = lay_.cost[p];
         HIP_TRY(hipMemcpy(d_cost_store_, cost_store_h_.data(), sizeof(double) * n_store_, hipMemcpyHostToDevice));
-        relp_status_t st = retabulate();
+        st = retabulate();
         if (st || !retab_done_) {
             lay_.nr_artificial = keep_na; phase_ = keep_phase;
             return st ? st : fail(RELP_E_SINGULAR, "from_basis: the basis could not be factorised (or m is too large for the "
                                                     "LDS-resident solves of the re-tabulation)");
         }
         HIP_TRY(hipMemcpy(d_in_basis_, flags.data(), flags.size(), hipMemcpyHostToDevice));
-        if ((st = download_rec())) return st;
-        h_rec_->outcome = DEV_RUNNING; h_rec_->last_selected = -1; h_rec_->phase = 2;
         tab_partials_valid_ = false;
-        return upload_rec();
+        return edit_rec(phase_two);
     }
     if (lu_) {
         // any basis: factorise it, b = B^-1 rhs (FTRAN), -pi = -c_B' B^-1 (BTRAN), carry/mod.rs:428-463
         HIP_TRY(hipStreamSynchronize(stream_));
-        std::vector<int32_t> basis(basis_columns, basis_columns + lay_.m);
-        std::vector<uint8_t> flags(n_alloc_, 0);
-        for (int32_t v : basis) {
-            if (v < 0 || v >= lay_.n_provider) return fail(RELP_E_ARG, "from_basis: column out of range");
-            if (flags[v]) return fail(RELP_E_SINGULAR, "from_basis: duplicate column");
-            flags[v] = 1;
-        }
+        if ((st = check_basis_columns(basis, &flags))) return st;
         lay_.nr_artificial = 0; phase_ = 2;
         HIP_TRY(hipMemcpy(d_basis_, basis.data(), sizeof(int32_t) * lay_.m, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(d_in_basis_, flags.data(), flags.size(), hipMemcpyHostToDevice));
         since_flush_ = 1;                              // force: the factors are stale
-        relp_status_t st = lu_refactor();
-        if (st) return st;
-        std::vector<double> w(ld_b_, 0.0), b(lay_.m);
-        for (int32_t i = 0; i < lay_.m; ++i) if (basis[i] < lay_.nr_normal) w[i] = -lay_.cost[basis[i]];
+        if ((st = lu_refactor())) return st;
+        const std::vector<double> w = basic_costs(basis, 2, -1.0);        // BTRAN with rhs -c_B gives -pi directly
+        std::vector<double> b(lay_.m);
         HIP_TRY(hipMemcpy(d_w_, w.data(), sizeof(double) * lay_.m, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(d_aq_, lay_.rhs.data(), sizeof(double) * lay_.m, hipMemcpyHostToDevice));
-        if (ft_) {
-            launch_ft_ftran(dlu_, fts_, ft_problem(0), -1, d_aq_, d_b_, stream_);
-            launch_ft_btran(dlu_, fts_, ft_problem(0), -1, d_w_, d_minus_pi_, stream_);
-        } else {
-            launch_lu_ftran(dlu_, d_aq_, d_b_, d_lu_scratch_, nullptr, stream_);
-            launch_lu_btran(dlu_, deferred(), d_w_, -1, d_minus_pi_, d_lu_scratch_, nullptr, stream_);
-        }
+        lu_ftran(d_aq_, d_b_, nullptr);
+        lu_btran(-1, d_w_, d_minus_pi_);
         HIP_TRY(hipMemcpyAsync(b.data(), d_b_, sizeof(double) * lay_.m, hipMemcpyDeviceToHost, stream_));
-        if ((st = download_rec())) return st;
-        double objective = 0.0;
-        for (int32_t i = 0; i < lay_.m; ++i) if (basis[i] < lay_.nr_normal) objective += b[i] * lay_.cost[basis[i]];
-        h_rec_->minus_objective = -objective; h_rec_->outcome = DEV_RUNNING; h_rec_->last_selected = -1; h_rec_->phase = 2;
-        return upload_rec();
+        return edit_rec([&](PivotRecord& r) { r.minus_objective = -objective_of(basis, b); phase_two(r); });
     }
     enqueue_flush();                                   // leaves the deferred state empty
     HIP_TRY(hipStreamSynchronize(stream_));
-    std::vector<int32_t> basis(basis_columns, basis_columns + lay_.m);
-    std::vector<double> Bn((size_t)lay_.m * ld_b_, 0.0), b(lay_.m, 0.0), minus_pi(ld_b_, 0.0);
+    if ((st = check_basis_columns(basis, &flags))) return st;
     double objective = 0.0;
-    bool unit_basis = true, on_device = false;
-    for (int32_t i = 0; i < lay_.m; ++i) {
-        const int32_t p = basis[i];
-        if (p < 0 || p >= lay_.n_provider) return fail(RELP_E_ARG, "from_basis: column out of range");
+    bool unit_basis = true;
+    for (int32_t p : basis)
         if (p < lay_.nr_normal || lay_.vrow1[p - lay_.nr_normal] >= 0) unit_basis = false;
-    }
     if (unit_basis) {
         // slack basis (two_phase/mod.rs:103-111 `FullInitialBasis`): the inverse is a signed permutation
+        std::vector<double> Bn((size_t)lay_.m * ld_b_, 0.0), b(lay_.m, 0.0), minus_pi(ld_b_, 0.0);
         std::vector<uint8_t> seen(lay_.m, 0);
         for (int32_t i = 0; i < lay_.m; ++i) {
             const int32_t v = basis[i] - lay_.nr_normal;
@@ -1456,54 +1439,29 @@ relp_status_t Engine::from_basis(const int32_t* basis_columns) {
             Bn[(size_t)i * ld_b_ + row] = (double)lay_.vsign[v];
             b[i] = (double)lay_.vsign[v] * lay_.rhs[row];
         }
-    } else {
-        // any basis: factorise it on the host (relp_lu.cpp) and form the rows of B^-1 by unit BTRANs,
-        // O(m (m + nnz(L) + nnz(U))) - the one-off `BasisInverseRows::invert` of the reference
-        // (basis_inverse_rows.rs:103-129: LU-invert, then m unit solves)
-        std::vector<int32_t> columns(basis);               // tableau column indices of the current kind
-        for (auto& j : columns) j += lay_.nr_artificial;
-        std::vector<std::vector<std::pair<int32_t, double>>> cols;
-        relp_status_t st = build_basis_columns(columns, &cols);
-        if (st) return st;
-        std::string msg;
-        if (!lu_factor(lay_.m, cols, &hlu_, &msg)) return fail(RELP_E_SINGULAR, "from_basis: " + msg);
-        // the factorisation is host work (like every refactorisation); the m unit solves, b = B^-1 rhs and
-        // -pi = -(c_B' B^-1) run on the device: row i of B^-1 is the BTRAN of e_i, written in place
-        if ((st = lu_upload_factors())) return st;
-        if (!d_lu_scratch_) HIP_TRY(dev_alloc(&d_lu_scratch_, ld_b_));
-        HIP_TRY(hipMemsetAsync(dBinv_, 0, sizeof(double) * (size_t)lay_.m * ld_b_, stream_));
-        DeferredUpdate none = deferred();
-        none.kmax = 0;
-        launch_lu_btran_rows(dlu_, none, dBinv_, ld_b_, d_lu_scratch_, stream_);
-        std::vector<double> w(ld_b_, 0.0);
-        for (int32_t i = 0; i < lay_.m; ++i) if (basis[i] < lay_.nr_normal) w[i] = lay_.cost[basis[i]];
-        HIP_TRY(hipMemcpyAsync(d_w_, w.data(), sizeof(double) * ld_b_, hipMemcpyHostToDevice, stream_));
-        HIP_TRY(hipMemcpyAsync(d_aq_, lay_.rhs.data(), sizeof(double) * lay_.m, hipMemcpyHostToDevice, stream_));
-        HIP_TRY(hipStreamSynchronize(stream_));                     // w, lay_.rhs are host buffers
-        launch_weighted_column_sums(dBinv_, ld_b_, lay_.m, d_w_, d_minus_pi_, stream_);          // -pi, carry/mod.rs:214-248
-        if ((st = download_rec())) return st;
-        h_rec_->outcome = DEV_RUNNING;
-        if ((st = upload_rec())) return st;
-        launch_ftran(dBinv_, ld_b_, lay_.m, 0, lay_.m, d_aq_, d_b_, 0, d_rec_, stream_);            // b = B^-1 rhs
-        HIP_TRY(hipMemcpyAsync(b.data(), d_b_, sizeof(double) * lay_.m, hipMemcpyDeviceToHost, stream_));
-        HIP_TRY(hipStreamSynchronize(stream_));
-        for (int32_t i = 0; i < lay_.m; ++i) objective += w[i] * b[i];
-        on_device = true;
-    }
-    if (!on_device) {
         HIP_TRY(hipMemcpy(dBinv_, Bn.data(), Bn.size() * sizeof(double), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(d_b_, b.data(), sizeof(double) * lay_.m, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(d_minus_pi_, minus_pi.data(), sizeof(double) * ld_b_, hipMemcpyHostToDevice));
+    } else {
+        // any basis: factorise it on the host (relp_lu.cpp, like every refactorisation); the rows of B^-1, -pi and b on the device
+        std::vector<int32_t> columns(basis);               // tableau column indices of the current kind
+        for (auto& j : columns) j += lay_.nr_artificial;
+        std::vector<std::vector<std::pair<int32_t, double>>> cols;
+        if ((st = build_basis_columns(columns, &cols))) return st;
+        std::string msg;
+        if (!lu_factor(lay_.m, cols, &hlu_, &msg)) return fail(RELP_E_SINGULAR, "from_basis: " + msg);
+        if ((st = lu_upload_factors())) return st;
+        if ((st = ensure_lu_scratch())) return st;
+        const std::vector<double> w = basic_costs(basis, 2, 1.0);
+        std::vector<double> b;
+        if ((st = inverse_from_factors(w, true, &b))) return st;
+        HIP_TRY(hipStreamSynchronize(stream_));
+        objective = weighted_sum(w, b);
     }
     HIP_TRY(hipMemcpy(d_basis_, basis.data(), sizeof(int32_t) * lay_.m, hipMemcpyHostToDevice));
-    std::vector<uint8_t> flags(n_alloc_, 0);
-    for (int32_t v : basis) flags[v] = 1;
     HIP_TRY(hipMemcpy(d_in_basis_, flags.data(), flags.size(), hipMemcpyHostToDevice));
     lay_.nr_artificial = 0; phase_ = 2;
-    relp_status_t st = download_rec();
-    if (st) return st;
-    h_rec_->minus_objective = -objective; h_rec_->outcome = DEV_RUNNING; h_rec_->last_selected = -1; h_rec_->phase = 2;
-    return upload_rec();
+    return edit_rec([&](PivotRecord& r) { r.minus_objective = -objective; phase_two(r); });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1521,48 +1479,27 @@ relp_status_t Engine::get_vector(int which, double* out) {
         if (cfg_.shard_count > 1) return fail(RELP_E_UNSUPPORTED, "-pi of the sharded tableau: d is column-sharded");
         // -pi_k = d_j - c_j for the stored column j that was e_k originally
         std::vector<double> d(n_store_);
-        HIP_TRY(hipMemcpyAsync(d.data(), d_d_, sizeof(double) * n_store_, hipMemcpyDeviceToHost, stream_));
-        HIP_TRY(hipStreamSynchronize(stream_));
+        if (const relp_status_t st = fetch(d.data(), d_d_, sizeof(double) * n_store_)) return st;
         for (int32_t k = 0; k < lay_.m; ++k) out[k] = d[idcol_h_[k]] - cost_store_h_[idcol_h_[k]];
         return RELP_OK;
     }
     const double* src = which == 0 ? d_b_ : which == 1 ? d_minus_pi_ : d_alpha_;
-    HIP_TRY(hipMemcpyAsync(out, src, sizeof(double) * lay_.m, hipMemcpyDeviceToHost, stream_));
-    HIP_TRY(hipStreamSynchronize(stream_));
-    return RELP_OK;
+    return fetch(out, src, sizeof(double) * lay_.m);
 }
 
-relp_status_t Engine::get_basis_indices(int32_t* out) {
-    HIP_TRY(hipMemcpyAsync(out, d_basis_, sizeof(int32_t) * lay_.m, hipMemcpyDeviceToHost, stream_));
-    HIP_TRY(hipStreamSynchronize(stream_));
-    return RELP_OK;
-}
+relp_status_t Engine::get_basis_indices(int32_t* out) { return fetch(out, d_basis_, sizeof(int32_t) * lay_.m); }
 
 relp_status_t Engine::get_basis_inverse(double* out) {
     if (cfg_.shard_count > 1) return fail(RELP_E_UNSUPPORTED, "B^-1 is row-sharded");
-    if (lu_) {
-        // row i of B^-1 = BTRAN of e_i (with the pending W); test / debugging path
-        double* tmp = nullptr;
-        HIP_TRY(dev_alloc(&tmp, (int64_t)lay_.m * lay_.m));
-        for (int32_t i = 0; i < lay_.m; ++i) {
-            if (ft_) launch_ft_btran(dlu_, fts_, ft_problem(0), i, nullptr, tmp + (int64_t)i * lay_.m, stream_);
-            else launch_lu_btran(dlu_, deferred(), nullptr, i, tmp + (int64_t)i * lay_.m, d_lu_scratch_, nullptr, stream_);
-        }
-        HIP_TRY(hipMemcpyAsync(out, tmp, sizeof(double) * lay_.m * lay_.m, hipMemcpyDeviceToHost, stream_));
-        HIP_TRY(hipStreamSynchronize(stream_));
-        HIP_TRY(hipFree(tmp));
-        return RELP_OK;
-    }
-    enqueue_flush();
-    if (tableau_) {
-        // B^-1 = the tableau columns of the original identity columns
-        double* tmp = nullptr;
-        HIP_TRY(dev_alloc(&tmp, (int64_t)lay_.m * lay_.m));
-        launch_tab_gather_columns(tview(), d_idcol_, tmp, stream_);
-        HIP_TRY(hipMemcpyAsync(out, tmp, sizeof(double) * lay_.m * lay_.m, hipMemcpyDeviceToHost, stream_));
-        HIP_TRY(hipStreamSynchronize(stream_));
-        HIP_TRY(hipFree(tmp));
-        return RELP_OK;
+    if (!lu_) enqueue_flush();
+    if (lu_ || tableau_) {
+        DeviceBuf<double> tmp;                             // (freed on every way out)
+        HIP_TRY(tmp.alloc((int64_t)lay_.m * lay_.m));
+        // LU: row i of B^-1 = BTRAN of e_i (with the pending updates); test / debugging path.  Tableau: B^-1 = the tableau
+        // columns of the original identity columns
+        if (lu_) for (int32_t i = 0; i < lay_.m; ++i) lu_btran(i, nullptr, tmp + (int64_t)i * lay_.m);
+        else launch_tab_gather_columns(tview(), d_idcol_, tmp, stream_);
+        return fetch(out, tmp, sizeof(double) * lay_.m * lay_.m);
     }
     HIP_TRY(hipStreamSynchronize(stream_));
     HIP_TRY(hipMemcpy2D(out, sizeof(double) * lay_.m, dBinv_, sizeof(double) * ld_b_, sizeof(double) * lay_.m, lay_.m, hipMemcpyDeviceToHost));
@@ -1599,10 +1536,7 @@ relp_status_t Engine::get_degenerate_pivots(int64_t* out) {
 
 relp_status_t Engine::tab_flush_stats(int64_t* out2) {
     unsigned long long h[2] = {0, 0};
-    if (d_fstats_) {
-        HIP_TRY(hipMemcpyAsync(h, d_fstats_, sizeof h, hipMemcpyDeviceToHost, stream_));
-        HIP_TRY(hipStreamSynchronize(stream_));
-    }
+    if (d_fstats_) { const relp_status_t st = fetch(h, d_fstats_, sizeof h); if (st) return st; }
     out2[0] = (int64_t)h[0]; out2[1] = (int64_t)h[1];
     return RELP_OK;
 }

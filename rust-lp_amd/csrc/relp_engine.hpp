@@ -1,4 +1,5 @@
-// relp_engine.hpp -- host driver of the explicit-inverse pivot engine.
+// relp_engine.hpp -- host driver of the three pivot engines: revised (explicit B^-1, deferred updates), dense tableau
+// (T = B^-1 [A | I] in blocks) and sparse LU (product form, or Forrest-Tomlin in one persistent workgroup).
 //
 // `Engine` plays the role of the reference's `Tableau<Carry<f64, BasisInverseRows<f64>>, K>` plus
 // the `PivotRule` state and the `MatrixData` provider (file:line under
@@ -22,16 +23,80 @@
 #include <vector>
 
 #include "../../include/relp_engine.h"
+#include "relp_buffers.hpp"
 #include "relp_kernels.h"
 #include "relp_layout.hpp"
 #include "relp_lu.hpp"
 
 namespace relp {
 
-class Engine {
+// two helper threads for the host side of a refactorisation (created at first use, joined with their owner)
+struct HostPool {
+    struct Slot { std::thread th; std::mutex mu; std::condition_variable cv; std::function<void()> job; bool busy = false, stop = false; };
+    Slot slot[2];
+    void run(int i, std::function<void()> f) {
+        Slot& s = slot[i];
+        if (!s.th.joinable())
+            s.th = std::thread([&s] {
+                std::unique_lock<std::mutex> lk(s.mu);
+                for (;;) {
+                    s.cv.wait(lk, [&s] { return s.busy || s.stop; });
+                    if (s.stop) return;
+                    lk.unlock(); s.job(); lk.lock();
+                    s.busy = false;
+                    s.cv.notify_all();
+                }
+            });
+        { std::lock_guard<std::mutex> lk(s.mu); s.job = std::move(f); s.busy = true; }
+        s.cv.notify_all();
+    }
+    void wait() {
+        for (Slot& s : slot) { std::unique_lock<std::mutex> lk(s.mu); s.cv.wait(lk, [&s] { return !s.busy; }); }
+    }
+    ~HostPool() {
+        for (Slot& s : slot) {
+            if (!s.th.joinable()) continue;
+            { std::lock_guard<std::mutex> lk(s.mu); s.stop = true; }
+            s.cv.notify_all();
+            s.th.join();
+        }
+    }
+};
+
+// The environment switches, read once per engine in Engine::create.  `*_set`: the variable was given.
+struct Switches {
+    bool debug = false;                                   // RELP_DEBUG
+    bool pivot_guard_set = false; double pivot_guard = 0.0;   // RELP_PIVOT_GUARD
+    bool tab_flush_all = false;                           // RELP_TAB_FLUSH_ALL
+    int tab_load_batch = 0, tab_w_split = 0;              // RELP_TAB_LOAD_BATCH, RELP_TAB_W_SPLIT (0: the default)
+    bool fused_update = true;                             // RELP_FUSED_UPDATE
+    bool lu_lookahead_set = false; int lu_lookahead = 8;  // RELP_LU_LOOKAHEAD
+    int fuse_lanes = 256;                                 // RELP_FUSE_LANES
+    int lu_device_factor = 0;                             // RELP_LU_DEVICE_FACTOR
+    bool lu_pipeline_short = false;                       // RELP_LU_PIPELINE_SHORT
+    int ft_big = -1;                                      // RELP_FT_BIG (-1: not given)
+    bool ft_hyper_set = false; int ft_hyper = 0x9;        // RELP_FT_HYPER
+    int ft_grid_price = -1;                               // RELP_FT_GRID_PRICE (-1: not given)
+    int luf_bump_cap = INT32_MAX;                         // RELP_LUF_BUMP_CAP (at least 16 when given)
+    int luf_dense = 64;                                   // RELP_LUF_DENSE
+    bool dump_basis_set = false; std::string dump_basis;  // RELP_DUMP_BASIS
+    static Switches read();
+};
+
+// The stream and the profiling events.  A base of Engine: destroyed after every member, i.e. after all memory is freed.
+struct EngineQueue {
+    hipStream_t stream_ = nullptr; bool owns_stream_ = false;
+    std::vector<hipEvent_t> prof_ev_;
+    ~EngineQueue() {
+        for (auto e : prof_ev_) (void)hipEventDestroy(e);
+        if (owns_stream_ && stream_) (void)hipStreamDestroy(stream_);
+    }
+};
+
+class Engine : private EngineQueue {
   public:
     Engine() = default;
-    ~Engine();
+    ~Engine();                                            // rccl_release() first, then the members, then EngineQueue
 
     relp_status_t create(const relp_matrix_data_t& md, const relp_config_t& cfg);
     relp_status_t set_stream(hipStream_t s);
@@ -130,45 +195,43 @@ class Engine {
     int32_t phase_ = 1;
 
     // ---- device state ----
-    double* dA_ = nullptr; int64_t ld_a_ = 0; bool owns_A_ = false;
-    double* dBinv_ = nullptr; int64_t ld_b_ = 0;
-    double *d_minus_pi_ = nullptr, *d_b_ = nullptr, *d_alpha_ = nullptr, *d_aq_ = nullptr, *d_rho_ = nullptr,
-           *d_d_ = nullptr, *d_w_ = nullptr, *d_cost_ = nullptr;
-    int32_t *d_basis_ = nullptr, *d_column_to_row_ = nullptr, *d_bound_row_ = nullptr, *d_vrow0_ = nullptr,
-            *d_vrow1_ = nullptr, *d_vsign_ = nullptr, *d_trace_ = nullptr;
-    uint8_t* d_in_basis_ = nullptr;
-    PivotRecord* d_rec_ = nullptr;
-    PivotRecord* h_rec_ = nullptr;  // pinned
-    hipStream_t stream_ = nullptr; bool owns_stream_ = false;
+    Switches sw_;
+    DeviceBuf<double> dA_; int64_t ld_a_ = 0;             // (a view when the caller's device matrix was adopted)
+    DeviceBuf<double> dBinv_; int64_t ld_b_ = 0;
+    DeviceBuf<double> d_minus_pi_, d_b_, d_alpha_, d_aq_, d_rho_, d_d_, d_w_, d_cost_;
+    DeviceBuf<int32_t> d_basis_, d_column_to_row_, d_bound_row_, d_vrow0_, d_vrow1_, d_vsign_, d_trace_;
+    DeviceBuf<uint8_t> d_in_basis_;
+    DeviceBuf<PivotRecord> d_rec_;
+    PinnedBuf<PivotRecord> h_rec_;
     int64_t trace_cap_ = 0;
     // deferred update (B^-1 = (I + W S') B0inv), see relp_kernels.h
     int32_t block_ = 0;            // K, 0 = explicit rank-1 updates
     int64_t since_flush_ = 0;      // pivots enqueued since the last flush
-    double* d_v_ = nullptr;        // B0inv a_q before the W correction
-    double *d_W_ = nullptr, *d_wr_ = nullptr, *d_R_ = nullptr;
-    int32_t *d_S_ = nullptr, *d_pos_of_row_ = nullptr;
-    double* d_part_k1_ = nullptr;  // PRICE workgroups' partial argmin (SelectPartials)
-    int32_t* d_part_j_ = nullptr;
+    DeviceBuf<double> d_v_;        // B0inv a_q before the W correction
+    DeviceBuf<double> d_W_, d_wr_, d_R_;
+    DeviceBuf<int32_t> d_S_, d_pos_of_row_;
+    DeviceBuf<double> d_part_k1_;  // PRICE workgroups' partial argmin (SelectPartials)
+    DeviceBuf<int32_t> d_part_j_;
     // dense-tableau engine (cfg.engine == RELP_ENGINE_TABLEAU)
     bool tableau_ = false;
-    double* dT0_ = nullptr; int64_t ld_t_ = 0;
-    double* dR0_ = nullptr; int64_t ld_r_ = 0;
+    DeviceBuf<double> dT0_; int64_t ld_t_ = 0;
+    DeviceBuf<double> dR0_; int64_t ld_r_ = 0;
     // flush over the columns with a nonzero R0 entry (relp_kernels.h: FlushList); RELP_TAB_FLUSH_ALL=1: every owned column
     bool flush_all_ = false;
-    int32_t *d_fcols_ = nullptr, *d_fcount_ = nullptr;
-    unsigned long long *d_fmask_ = nullptr, *d_fstats_ = nullptr;   // d_fstats_: {flushes, columns flushed} since create
-    double* d_R0c_ = nullptr;
+    DeviceBuf<int32_t> d_fcols_, d_fcount_;
+    DeviceBuf<unsigned long long> d_fmask_, d_fstats_;              // d_fstats_: {flushes, columns flushed} since create
+    DeviceBuf<double> d_R0c_;
     FlushList flush_list() const;
     // RELP_TAB_LOAD_BATCH / RELP_TAB_W_SPLIT (relp_kernels.h: tab_load_batch, launch_tab_ratio_update_all)
     int32_t load_batch_ = 0, w_split_ = 0;
-    double* d_cost_store_ = nullptr;     // cost per stored column in the current phase
-    int32_t* d_idcol_ = nullptr;         // stored column that was e_k originally, per row k
+    DeviceBuf<double> d_cost_store_;     // cost per stored column in the current phase
+    DeviceBuf<int32_t> d_idcol_;         // stored column that was e_k originally, per row k
     // Ratio test + update in one launch (single-GPU loop, relp_kernels.h: launch_tab_ratio_update_all): the second copies of b
     // and the basis array it writes (swapped with d_b_ / d_basis_ after every pivot), the shadow row of W and its {row, length}
     bool fused_update_ = false, shadow_pending_ = false;
-    double *d_b_alt_ = nullptr, *d_shadow_ = nullptr;
-    int32_t *d_basis_alt_ = nullptr, *d_shadow_meta_ = nullptr;
-    double* d_rmin_ = nullptr;           // minimum ratio per block of 256 rows (k_tab_select_column -> k_ratio_blocks)
+    DeviceBuf<double> d_b_alt_, d_shadow_;
+    DeviceBuf<int32_t> d_basis_alt_, d_shadow_meta_;
+    DeviceBuf<double> d_rmin_;           // minimum ratio per block of 256 rows (k_tab_select_column -> k_ratio_blocks)
     int32_t n_store_ = 0;                // stored columns = original artificials + provider columns
     int32_t tab_na_ = 0;                 // original number of artificial columns (their block is kept)
     bool tab_partials_valid_ = false;    // the PRICE partials describe the current d
@@ -191,59 +254,28 @@ class Engine {
     TableauView tview() const;
     double* d_aq_big() { return dR0_ + (int64_t)block_ * ld_r_; }         // scratch row behind R0 (owned columns)
     SelectPartials tab_partials(int rule) const;
+    SelectPartials lu_partials(int rule) const;
     void enqueue_iteration_tableau(int rule);
-    relp_status_t tableau_reprice();
+    void tableau_reprice();
     // sparse LU engine (cfg.engine == RELP_ENGINE_LU): B^-1 = (I + W S') (L U)^-1, refactor every block_ pivots
     bool lu_ = false;
     std::vector<int64_t> hc_ptr_; std::vector<int32_t> hc_idx_; std::vector<double> hc_val_;   // host CSC of A
-    int64_t* d_cptr_ = nullptr; int32_t* d_cidx_ = nullptr; double* d_cval_ = nullptr;         // device CSC of A
+    DeviceBuf<int64_t> d_cptr_; DeviceBuf<int32_t> d_cidx_; DeviceBuf<double> d_cval_;         // device CSC of A
     LUFactors hlu_;
-    char* d_lu_buf_ = nullptr; int64_t lu_cap_ = 0;       // packed factors (permutations, rows, entries, levels)
+    DeviceBuf<char> d_lu_buf_; int64_t lu_cap_ = 0;      // packed factors (permutations, rows, entries, levels)
     std::vector<std::vector<std::pair<int32_t, double>>> basis_cols_;      // the basis columns handed to lu_factor
     std::vector<int64_t> basis_ptr_; std::vector<int32_t> basis_idx_; std::vector<double> basis_val_;   // ... as one flat copy (lu_factor_csc)
-    // two helper threads for the host side of a refactorisation (created at first use, joined with the engine)
-    struct HostPool {
-        struct Slot { std::thread th; std::mutex mu; std::condition_variable cv; std::function<void()> job; bool busy = false, stop = false; };
-        Slot slot[2];
-        void run(int i, std::function<void()> f) {
-            Slot& s = slot[i];
-            if (!s.th.joinable())
-                s.th = std::thread([&s] {
-                    std::unique_lock<std::mutex> lk(s.mu);
-                    for (;;) {
-                        s.cv.wait(lk, [&s] { return s.busy || s.stop; });
-                        if (s.stop) return;
-                        lk.unlock(); s.job(); lk.lock();
-                        s.busy = false;
-                        s.cv.notify_all();
-                    }
-                });
-            { std::lock_guard<std::mutex> lk(s.mu); s.job = std::move(f); s.busy = true; }
-            s.cv.notify_all();
-        }
-        void wait() {
-            for (Slot& s : slot) { std::unique_lock<std::mutex> lk(s.mu); s.cv.wait(lk, [&s] { return !s.busy; }); }
-        }
-        ~HostPool() {
-            for (Slot& s : slot) {
-                if (!s.th.joinable()) continue;
-                { std::lock_guard<std::mutex> lk(s.mu); s.stop = true; }
-                s.cv.notify_all();
-                s.th.join();
-            }
-        }
-    } host_pool_;
-    char* h_lu_buf_ = nullptr; size_t h_lu_cap_ = 0;      // the same, assembled in pinned host memory
-    char* d_lu_buf_alt_ = nullptr; int64_t lu_cap_alt_ = 0;   // second device buffer: the factors the host prepares while the kernel runs
-    int32_t* h_basis_ = nullptr; int32_t m_alloc_rows_ = 0;   // pinned: the basis a refactorisation downloads
-    FtMirror* h_mirror_ = nullptr; FtMirror* d_mirror_ = nullptr;   // pinned + mapped: what k_ft_run reports (relp_kernels.h)
-    double* d_lu_scratch_ = nullptr;
+    HostPool host_pool_;                                  // the host side of a refactorisation (created at first use, joined with the engine)
+    PinnedBuf<char> h_lu_buf_; size_t h_lu_cap_ = 0;      // the same, assembled in pinned host memory
+    DeviceBuf<char> d_lu_buf_alt_; int64_t lu_cap_alt_ = 0;   // second device buffer: the factors the host prepares while the kernel runs
+    PinnedBuf<int32_t> h_basis_;                          // the basis a refactorisation downloads
+    PinnedBuf<FtMirror> h_mirror_;                        // mapped: what k_ft_run reports (relp_kernels.h); .device() is its address there
+    DeviceBuf<double> d_lu_scratch_;
+    relp_status_t ensure_lu_scratch();
     DeviceLU dlu_{};
     relp_status_t lu_status_ = RELP_OK;                   // a failed refactorisation inside the loop
     int64_t lu_refactors_ = 0;
     int64_t lu_lookahead_installs_ = 0, lu_replayed_changes_ = 0;     // look-ahead refactorisations installed, journal entries replayed
-    int32_t lu_lookahead_env_ = 8, lu_fuse_lanes_env_ = 256;          // RELP_LU_LOOKAHEAD, RELP_FUSE_LANES (read at create)
-    bool lu_lookahead_set_ = false;                      // RELP_LU_LOOKAHEAD given (else layout 2 takes 16)
     int32_t lu_pipeline_cap_ = 0;                        // RELP_LU_PIPELINE_SHORT: the update file's cap while the host factorises (run_ft)
     double refactor_us_[3] = {0.0, 0.0, 0.0};            // host time: basis + columns, factorisation, schedules + upload
     // revised engine: B^-1 is re-inverted from the basis columns every `reinvert_interval_` pivots (0 = never)
@@ -265,8 +297,8 @@ class Engine {
     // create when the work vectors, the eta pool and the dense tail of U fit one CU's LDS (m <= kFtMaxRows)
     bool ft_ = false;
     FtState fts_{};
-    char* d_ft_buf_ = nullptr;
-    int32_t* h_ft_hdr_ = nullptr;                         // pinned copy of fts_.hdr
+    DeviceBuf<char> d_ft_buf_;
+    PinnedBuf<int32_t> h_ft_hdr_;                         // copy of fts_.hdr
     int32_t ft_tcap_ = 0, ft_eta_cap_ = 0;
     // the refactorisation on the device (relp_engine_luf.cpp, relp_lu_factor_core.h): RELP_LU_DEVICE_FACTOR=1 or
     // relp_lu_set_device_factorisation; a bump beyond the dense working copy falls back to lu_factor on the host
@@ -281,7 +313,6 @@ class Engine {
     bool luf_is_resident() const;
     bool luf_download_ = false;                          // RELP_LU_DEVICE_FACTOR=2: download the factors, schedule on the host
     void luf_release();
-    void luf_mark_dirty();
     bool hyper_forced_ = false; int32_t hyper_probe_in_[4] = {0, 0, 0, 0};    // adaptive hyper-sparse starts (ft_read_report)
     bool ft_big_ = false; int32_t ft_rhs_cap_ = 0;        // layout of the persistent kernel (relp_kernels_ft.hip: ft_layout)
     bool ft_grid_price_ = false;                          // Dantzig PRICE as a grid launch per pivot (run_ft): layout 2 with very many columns
@@ -293,7 +324,7 @@ class Engine {
     relp_status_t ft_read_hdr();
     FtProblem ft_problem(int rule) const;
     void ft_enqueue_pivots(const FtState& go, int rule, int64_t left);
-    char* d_pe_buf_ = nullptr; PriceEll pe_{};            // PRICE copy of the structural columns (relp_kernels.h: PriceEll)
+    DeviceBuf<char> d_pe_buf_; PriceEll pe_{};            // PRICE copy of the structural columns (relp_kernels.h: PriceEll)
     relp_status_t ft_build_price_ell();
     relp_status_t run_ft(int64_t max_iters, int64_t* done, int32_t* outcome);
     DeferredUpdate deferred() const;
@@ -306,18 +337,14 @@ class Engine {
     relp_allreduce_sum_fn coll_allreduce_ = nullptr;
     void* coll_ctx_ = nullptr;
     void* rccl_comm_ = nullptr;          // ncclComm_t owned by this engine (relp_rccl_attach)
-    double* d_msg_cand_ = nullptr;       // this rank's candidate / all ranks' candidates
-    double* d_msg_cands_ = nullptr;
-    double* d_msg_slice_ = nullptr;      // revised engine: alpha slice / all slices, rho
-    double* d_msg_slices_ = nullptr;
-    double* d_msg_rho_ = nullptr;
+    DeviceBuf<double> d_msg_cand_, d_msg_cands_;                 // this rank's candidate / all ranks' candidates
+    DeviceBuf<double> d_msg_slice_, d_msg_slices_, d_msg_rho_;   // revised engine: alpha slice / all slices, rho
     relp_status_t shard_iteration();
     relp_status_t shard_iteration_comm_only(int from_step);
     int coll_step_ = 0;                  // collectives of the current pivot already done (a failed pivot is completed from here)
     int64_t shadow_flush_ = 0;           // pivots since the last flush as every rank counts them
     relp_status_t shard_agree_on_status(relp_status_t local);
-    double* d_msg_status_ = nullptr;     // this rank's status / all ranks' statuses (agreed on at every poll of relp_shard_run)
-    double* d_msg_statuses_ = nullptr;
+    DeviceBuf<double> d_msg_status_, d_msg_statuses_;   // this rank's status / all ranks' statuses (agreed on at every poll of relp_shard_run)
     int64_t inject_failure_after_ = -1;  // test hook (relp_shard_inject_failure)
     bool coll_broken_ = false;           // a collective hook itself failed: nothing can be agreed on any more
     relp_status_t remove_artificial_basis_variables_sharded(std::vector<int32_t>& rows_to_remove);
@@ -325,7 +352,6 @@ class Engine {
 
     // ---- profiling ----
     bool prof_on_ = false;
-    std::vector<hipEvent_t> prof_ev_;
     std::vector<int> prof_kid_;
     bool prof_open_ = false;
     int32_t prof_stride_ = 1;      // bracket the kernels of every prof_stride_-th pivot only
@@ -338,8 +364,34 @@ class Engine {
     Tolerances tolerances() const;
     bool hip_ok(hipError_t e, const char* what);
     relp_status_t fail(relp_status_t code, const std::string& msg) { err_ = msg; return code; }
+    relp_status_t fetch(void* dst, const void* src, size_t bytes);
     relp_status_t download_rec();
     relp_status_t upload_rec();
+    // re-arm the pivot record: download it, outcome = DEV_RUNNING, whatever else `f` sets, upload it
+    template <class F> relp_status_t edit_rec(F&& f) {
+        const relp_status_t st = download_rec();
+        if (st) return st;
+        h_rec_->outcome = DEV_RUNNING;
+        f(*h_rec_);
+        return upload_rec();
+    }
+    relp_status_t edit_rec() { return edit_rec([](PivotRecord&) {}); }
+    int current_rule() const { return phase_ == 1 ? cfg_.phase_one_rule : cfg_.phase_two_rule; }
+    // dA_ / dBinv_ hold the owned columns / rows only: shifted so that kernels index globally
+    double* A_base() const { return dA_ - (int64_t)lay_.col_lo * ld_a_; }
+    double* Binv_base() const { return dBinv_ - (int64_t)lay_.row_lo * ld_b_; }
+    relp_status_t take_lu_status() { const relp_status_t e = lu_status_; lu_status_ = RELP_OK; return e; }   // a refactorisation that failed inside a launch sequence
+    // LU engine, Forrest-Tomlin or product form: row `row` of B^-1 (rhs null) or rhs' B^-1 (row -1); B^-1 rhs
+    void lu_btran(int32_t row, const double* rhs, double* out);
+    void lu_ftran(const double* rhs, double* out, const PivotRecord* rec);
+    relp_status_t read_pivot_row(int32_t* found, int32_t* row);
+    std::vector<double> basic_costs(const std::vector<int32_t>& basis, int phase, double sign) const;
+    double objective_of(const std::vector<int32_t>& basis, const std::vector<double>& b) const;
+    relp_status_t check_basis_columns(const std::vector<int32_t>& basis, std::vector<uint8_t>* flags);
+    relp_status_t refactor_current_basis(std::vector<int32_t>* basis, std::vector<double>* b_before, bool* factored);
+    relp_status_t inverse_from_factors(const std::vector<double>& w, bool rearm, std::vector<double>* b);
+    relp_status_t basic_artificials(std::vector<int32_t>* basis, std::vector<int32_t>* arts);
+    void keep_artificial_row(int32_t a, std::vector<int32_t>& rows_to_remove);
     void prof_begin(int kid, hipStream_t on = nullptr);
     void prof_end(hipStream_t on = nullptr);
     void enqueue_price(int cost_mode, const double* vec, const PivotRecord* rec, int32_t p_lo, int32_t p_hi);
@@ -352,6 +404,7 @@ class Engine {
     std::vector<int32_t> stuck_artificials_;
     // relp_config_t.pivot_rescue (relp_engine.h): the loop of run_loop() behind a look at every exit without a pivot row
     relp_status_t run_loop(int64_t max_iters, int64_t* done, int32_t* outcome);
+    relp_status_t outcome_of_record(int32_t* oc);
     relp_status_t rescue_unbar_all();
     void auto_reinversion_adapt(const std::vector<double>& before, const std::vector<double>& after);
     std::vector<int32_t> barred_;                  // columns barred from pricing (in_basis flag 2) until the basis changes
@@ -364,7 +417,6 @@ class Engine {
     int64_t rescue_small_pivots_ = 0, rescue_barred_ = 0, rescue_confirmations_ = 0;
     double last_reinvert_drift_ = -1.0;            // relp_config_t.auto_reinversion: what the last rebuild moved b by (relative)
     relp_status_t remove_rows(const std::vector<int32_t>& rows);
-    void free_all();
 };
 
 }  // namespace relp

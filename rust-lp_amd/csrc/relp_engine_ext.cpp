@@ -15,25 +15,19 @@ relp_status_t Engine::basis_inverse_row(int32_t row, double* out_m) {
     if (row < 0 || row >= lay_.m) return fail(RELP_E_ARG, "row out of range");
     if (cfg_.shard_count > 1) return fail(RELP_E_UNSUPPORTED, "B^-1 is sharded");
     if (lu_) {
-        if (ft_) launch_ft_btran(dlu_, fts_, ft_problem(0), row, nullptr, d_rho_, stream_);
-        else launch_lu_btran(dlu_, deferred(), nullptr, row, d_rho_, d_lu_scratch_, nullptr, stream_);
-        HIP_TRY(hipMemcpyAsync(out_m, d_rho_, sizeof(double) * lay_.m, hipMemcpyDeviceToHost, stream_));
-        HIP_TRY(hipStreamSynchronize(stream_));
-        return RELP_OK;
+        lu_btran(row, nullptr, d_rho_);
+        return fetch(out_m, d_rho_, sizeof(double) * lay_.m);
     }
     if (tableau_) {
         // B^-1 = the tableau columns that were the identity originally: row r of T over those columns
         launch_tab_row(tview(), deferred(), row, d_aq_big(), d_rec_, stream_);
         std::vector<double> trow(n_store_);
-        HIP_TRY(hipMemcpyAsync(trow.data(), d_aq_big(), sizeof(double) * n_store_, hipMemcpyDeviceToHost, stream_));
-        HIP_TRY(hipStreamSynchronize(stream_));
+        if (const relp_status_t st = fetch(trow.data(), d_aq_big(), sizeof(double) * n_store_)) return st;
         for (int32_t k = 0; k < lay_.m; ++k) out_m[k] = trow[idcol_h_[k]];
         return RELP_OK;
     }
     enqueue_flush();
-    HIP_TRY(hipMemcpyAsync(out_m, dBinv_ + (int64_t)row * ld_b_, sizeof(double) * lay_.m, hipMemcpyDeviceToHost, stream_));
-    HIP_TRY(hipStreamSynchronize(stream_));
-    return RELP_OK;
+    return fetch(out_m, dBinv_ + (int64_t)row * ld_b_, sizeof(double) * lay_.m);
 }
 
 // BasisInverse::should_refactor: lower_upper/mod.rs:199-202 (`updates.len() > 10`; here: the configured number of
@@ -79,21 +73,16 @@ relp_status_t Engine::generate_column_of(const int32_t* idx, const double* val, 
         if (out_m) std::memcpy(out_m, alpha.data(), sizeof(double) * lay_.m);
         return RELP_OK;
     }
-    relp_status_t st = download_rec();
+    const relp_status_t st = edit_rec();
     if (st) return st;
-    h_rec_->outcome = DEV_RUNNING;
-    if ((st = upload_rec())) return st;
     HIP_TRY(hipMemcpyAsync(d_aq_, a.data(), sizeof(double) * ld_b_, hipMemcpyHostToDevice, stream_));
     HIP_TRY(hipStreamSynchronize(stream_));              // `a` is stack-owned
-    if (lu_ && ft_) {
-        launch_ft_ftran(dlu_, fts_, ft_problem(0), -1, d_aq_, d_alpha_, stream_);
-    } else if (lu_) {
-        launch_lu_ftran(dlu_, d_aq_, d_v_, d_lu_scratch_, d_rec_, stream_);
-        launch_apply_w(deferred(), lay_.m, d_v_, d_alpha_, d_rec_, stream_);
+    if (lu_) {
+        lu_ftran(d_aq_, ft_ ? d_alpha_ : d_v_, d_rec_);
+        if (!ft_) launch_apply_w(deferred(), lay_.m, d_v_, d_alpha_, d_rec_, stream_);      // the product form's pending W
     } else {
         enqueue_flush();
-        double* Binv = dBinv_ - (int64_t)lay_.row_lo * ld_b_;
-        launch_ftran(Binv, ld_b_, lay_.m, lay_.row_lo, lay_.row_hi, d_aq_, d_alpha_, 0, d_rec_, stream_);
+        launch_ftran(Binv_base(), ld_b_, lay_.m, lay_.row_lo, lay_.row_hi, d_aq_, d_alpha_, 0, d_rec_, stream_);
     }
     if (out_m) HIP_TRY(hipMemcpyAsync(out_m, d_alpha_, sizeof(double) * lay_.m, hipMemcpyDeviceToHost, stream_));
     HIP_TRY(hipStreamSynchronize(stream_));
@@ -123,10 +112,7 @@ relp_status_t Engine::lu_change_basis(int32_t row) {
     relp_status_t st = ft_read_hdr();
     if (st) return st;
     if (h_ft_hdr_[0] >= ft_tcap_) return fail(RELP_E_STATE, "update file full: refactor first (relp_flush)");
-    if ((st = download_rec())) return st;
-    h_rec_->outcome = DEV_RUNNING;
-    h_rec_->r = row;
-    if ((st = upload_rec())) return st;
+    if ((st = edit_rec([&](PivotRecord& r) { r.r = row; }))) return st;
     launch_ft_update(dlu_, fts_, ft_problem(0), stream_);
     if ((st = ft_read_hdr())) return st;
     if (h_ft_hdr_[2] == 2) return fail(RELP_E_STATE, "the eta pool is full: refactor first (relp_flush), then generate the column again");

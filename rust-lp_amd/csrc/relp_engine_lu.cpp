@@ -50,9 +50,9 @@ relp_status_t Engine::lu_load_matrix(const relp_matrix_data_t& md) {
     } else {
         return fail(RELP_E_ARG, "unknown matrix format");
     }
-    HIP_TRY(dev_alloc(&d_cptr_, lay_.nr_normal + 1));
-    HIP_TRY(dev_alloc(&d_cidx_, (int64_t)hc_idx_.size()));
-    HIP_TRY(dev_alloc(&d_cval_, (int64_t)hc_val_.size()));
+    HIP_TRY(d_cptr_.alloc(lay_.nr_normal + 1));
+    HIP_TRY(d_cidx_.alloc((int64_t)hc_idx_.size()));
+    HIP_TRY(d_cval_.alloc((int64_t)hc_val_.size()));
     HIP_TRY(hipMemcpy(d_cptr_, hc_ptr_.data(), sizeof(int64_t) * hc_ptr_.size(), hipMemcpyHostToDevice));
     if (!hc_idx_.empty()) {
         HIP_TRY(hipMemcpy(d_cidx_, hc_idx_.data(), sizeof(int32_t) * hc_idx_.size(), hipMemcpyHostToDevice));
@@ -62,12 +62,7 @@ relp_status_t Engine::lu_load_matrix(const relp_matrix_data_t& md) {
 }
 
 // The basis as it is on the device -> pinned host memory.  Synchronises the stream.
-relp_status_t Engine::lu_download_basis() {
-    if (!h_basis_) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_basis_), sizeof(int32_t) * (size_t)std::max(m_alloc_rows_, lay_.m), hipHostMallocDefault));
-    HIP_TRY(hipMemcpyAsync(h_basis_, d_basis_, sizeof(int32_t) * lay_.m, hipMemcpyDeviceToHost, stream_));
-    HIP_TRY(hipStreamSynchronize(stream_));
-    return RELP_OK;
-}
+relp_status_t Engine::lu_download_basis() { return fetch(h_basis_, d_basis_, sizeof(int32_t) * lay_.m); }
 
 // the columns of the basis in h_basis_ from the host copy of the matrix (the LU engine never holds A densely)
 relp_status_t Engine::lu_basis_columns(std::vector<std::vector<std::pair<int32_t, double>>>& cols) {
@@ -96,7 +91,7 @@ relp_status_t Engine::lu_basis_flat(std::vector<int64_t>& ptr, std::vector<int32
 
 // P B Q = L U on the host for the basis in h_basis_ (hlu_ is overwritten)
 relp_status_t Engine::lu_factor_downloaded_basis() {
-    if (!std::getenv("RELP_DUMP_BASIS")) {
+    if (!sw_.dump_basis_set) {
         const relp_status_t fst = lu_basis_flat(basis_ptr_, basis_idx_, basis_val_);
         if (fst) return fst;
         std::string msg;
@@ -106,13 +101,11 @@ relp_status_t Engine::lu_factor_downloaded_basis() {
     std::vector<std::vector<std::pair<int32_t, double>>>& cols = basis_cols_;     // (kept: no 790 allocations per refactorisation)
     const relp_status_t cst = lu_basis_columns(cols);
     if (cst) return cst;
-    if (const char* dump = std::getenv("RELP_DUMP_BASIS")) {
-        if (lu_refactors_ == 100) {                        // one mid-solve basis as text: m, then per column "n i v i v ..."
-            if (FILE* f = std::fopen(dump, "w")) {
-                std::fprintf(f, "%d\n", lay_.m);
-                for (auto& c : cols) { std::fprintf(f, "%zu", c.size()); for (auto& e : c) std::fprintf(f, " %d %.17g", e.first, e.second); std::fprintf(f, "\n"); }
-                std::fclose(f);
-            }
+    if (lu_refactors_ == 100) {                            // one mid-solve basis as text: m, then per column "n i v i v ..."
+        if (FILE* f = std::fopen(sw_.dump_basis.c_str(), "w")) {
+            std::fprintf(f, "%d\n", lay_.m);
+            for (auto& c : cols) { std::fprintf(f, "%zu", c.size()); for (auto& e : c) std::fprintf(f, " %d %.17g", e.first, e.second); std::fprintf(f, "\n"); }
+            std::fclose(f);
         }
     }
     std::string msg;
@@ -125,7 +118,7 @@ void Engine::lu_refactor_clock(std::chrono::steady_clock::time_point tb, std::ch
     refactor_us_[0] += std::chrono::duration<double, std::micro>(t0 - tb).count();
     refactor_us_[1] += std::chrono::duration<double, std::micro>(t1 - t0).count();
     refactor_us_[2] += std::chrono::duration<double, std::micro>(t2 - t1).count();
-    if (std::getenv("RELP_DEBUG") && lu_refactors_ % 60 == 59)
+    if (sw_.debug && lu_refactors_ % 60 == 59)
         std::fprintf(stderr, "[relp] refactorisations so far %lld: basis download + columns %.0f us, lu_factor %.0f us, schedules + upload %.0f us (averages)\n",
                      (long long)lu_refactors_ + 1, refactor_us_[0] / (lu_refactors_ + 1), refactor_us_[1] / (lu_refactors_ + 1),
                      refactor_us_[2] / (lu_refactors_ + 1));
@@ -182,13 +175,12 @@ relp_status_t Engine::lu_refactor_lookahead(int rule, int64_t budget, bool have_
     LUFactors old_h = std::move(hlu_);
     const DeviceLU old_d = dlu_;
     const FtState old_f = fts_;
-    char* const old_buf = d_lu_buf_;
-    const int64_t old_cap = lu_cap_;
-    d_lu_buf_ = d_lu_buf_alt_; lu_cap_ = lu_cap_alt_;
+    auto swap_buffers = [&]() { d_lu_buf_.swap(d_lu_buf_alt_); std::swap(lu_cap_, lu_cap_alt_); };
+    swap_buffers();                                        // the new factors go into the other buffer, the old one stays in use
     hlu_ = LUFactors{};
     auto restore = [&]() {
-        d_lu_buf_alt_ = d_lu_buf_; lu_cap_alt_ = d_lu_buf_ ? lu_cap_ : 0;      // (null after a failed re-allocation)
-        hlu_ = std::move(old_h); dlu_ = old_d; fts_ = old_f; d_lu_buf_ = old_buf; lu_cap_ = old_cap;
+        swap_buffers();                                    // (the other buffer may be null, capacity 0, after a failed re-allocation)
+        hlu_ = std::move(old_h); dlu_ = old_d; fts_ = old_f;
     };
     st = lu_factor_downloaded_basis();
     const auto t1 = std::chrono::steady_clock::now();
@@ -206,7 +198,6 @@ relp_status_t Engine::lu_refactor_lookahead(int rule, int64_t budget, bool have_
         if (h_ft_hdr_[2] == 2 || changes > ft_tcap_) ft_need_refactor_ = true;
         return RELP_OK;
     }
-    d_lu_buf_alt_ = old_buf; lu_cap_alt_ = old_cap;
     if ((st = ft_reset())) return st;
     prof_begin(RELP_K_FLUSH);
     launch_ft_replay(dlu_, fts_, ft_problem(rule), changes, stream_);
@@ -233,11 +224,10 @@ relp_status_t Engine::lu_upload_factors() {
         const size_t o = buf_size, need = o + (bytes + 15) / 16 * 16;
         if (need > h_lu_cap_) {
             const size_t cap = std::max<size_t>(need * 2, size_t(1) << 20);
-            char* grown = nullptr;
-            if (hipHostMalloc(reinterpret_cast<void**>(&grown), cap, hipHostMallocDefault) != hipSuccess) { buf_failed = true; return o; }
+            PinnedBuf<char> grown;
+            if (grown.alloc(cap) != hipSuccess) { buf_failed = true; return o; }
             if (buf_size) std::memcpy(grown, h_lu_buf_, buf_size);
-            if (h_lu_buf_) (void)hipHostFree(h_lu_buf_);
-            h_lu_buf_ = grown; h_lu_cap_ = cap;
+            h_lu_buf_ = std::move(grown); h_lu_cap_ = cap;
         }
         if (bytes) std::memcpy(h_lu_buf_ + o, src, bytes);
         buf_size = need;
@@ -265,7 +255,7 @@ relp_status_t Engine::lu_upload_factors() {
         for (int32_t t = hlu_.Ub.level_ptr[l]; t < hlu_.Ub.level_ptr[l + 1]; ++t) lev_ub[hlu_.Ub.level_rows[t]] = l;
     static_assert(kEllLgShift == kEllLg, "host packing and device decoding of sidx");
     if (ft_) {
-        const int32_t fuse_cap = lu_fuse_lanes_env_;       // (RELP_FUSE_LANES, read at create)
+        const int32_t fuse_cap = sw_.fuse_lanes;       // (RELP_FUSE_LANES, read at create)
         // (fused schedules read copies of some right-hand sides behind x: ft_rhs_cap_ words of LDS, and of index space)
         const int32_t cap = ft_rhs_cap_ > 0 ? fuse_cap : 0;
         const int64_t index_room = ft_big_ ? (int64_t(1) << kEllLgShiftWide) : (int64_t(1) << kEllLgShift);
@@ -384,11 +374,9 @@ relp_status_t Engine::lu_upload_factors() {
     if ((int64_t)buf_size > lu_cap_) {
         // (pointer and capacity are cleared before the new allocation: if it fails nothing dangles, and the look-ahead's
         // restore() below skips an empty buffer)
-        char* const stale = d_lu_buf_;
-        d_lu_buf_ = nullptr; lu_cap_ = 0;
-        if (stale) HIP_TRY(hipFree(stale));
+        lu_cap_ = 0;
         const int64_t want = (int64_t)buf_size * 3 / 2 + 256;
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_lu_buf_), (size_t)want));
+        HIP_TRY(d_lu_buf_.alloc_raw((size_t)want));         // (frees the old buffer first; null if the new one is refused)
         lu_cap_ = want;
     }
     HIP_TRY(hipMemcpyAsync(d_lu_buf_, h_lu_buf_, buf_size, hipMemcpyHostToDevice, stream_));
@@ -464,7 +452,7 @@ relp_status_t Engine::lu_upload_factors() {
                 if (!fts_.stage[k] && hb <= fts_.stage_bytes) need = std::max(need, hb);
             }
         fts_.lds_bytes = (int32_t)(base + need);
-        if (std::getenv("RELP_DEBUG") && lu_refactors_ % 60 == 59)
+        if (sw_.debug && lu_refactors_ % 60 == 59)
             for (int k = 0; k < 4; ++k)
                 std::fprintf(stderr, "[relp] schedule %d: %d levels, %d passes, %d lanes (%d entries), image %d bytes, staged %d (stage area %d, base %lld)\n",
                              k, fts_.ell[k].n_levels, fts_.ell[k].n_passes, fts_.ell[k].n_lanes, (int)sch[k]->idx.size(),
@@ -485,7 +473,7 @@ relp_status_t Engine::ft_plan_and_alloc() {
     // flat between 40 and 64, and 48 x 49 doubles leave 14 KB more for the images than 64 x 65.
     int32_t want = cfg_.update_block < 0 ? 48 : std::max(1, std::min(cfg_.update_block, kFtMaxSlots));
     // (RELP_LU_PIPELINE_SHORT, run_ft: a short interval pivots on into a tail twice as long while the host factorises)
-    if (std::getenv("RELP_LU_PIPELINE_SHORT") && std::atoi(std::getenv("RELP_LU_PIPELINE_SHORT")) != 0 && want < 24) want = 2 * want;
+    if (sw_.lu_pipeline_short && want < 24) want = 2 * want;
     // Two layouts (relp_kernels_ft.hip: ft_layout).  "All in LDS": x with m right-hand-side copies, spike, -pi, permutations,
     // eta pool -- 63 bytes per row.  "big": x, -pi and the slot tables only (17 bytes per row + 8 per right-hand-side copy the
     // fused schedules may use: as many as fit, a schedule that needs more is packed level by level), the rest read from L2;
@@ -494,9 +482,7 @@ relp_status_t Engine::ft_plan_and_alloc() {
     // from L2 at several times the cost); RELP_FT_BIG = 0 / 1 forces one of them.
     const int64_t eta_cap = std::max<int64_t>((int64_t)2 * lay_.m + 64, 1024);   // (one eta never exceeds m entries)
     constexpr int64_t kFtMinStage = 64 * 1024;
-    (void)kFtMinStage;
-    const char* big_env = std::getenv("RELP_FT_BIG");
-    const int force_big = big_env ? std::atoi(big_env) : -1;
+    const int force_big = sw_.ft_big;
     auto plan = [&](int32_t tier, int32_t rhs_cap, int64_t min_stage, int32_t min_tcap = 16) {
         for (int32_t tcap : {64, 48, 32, 16}) {
             if (tcap != 16 && tcap - 16 >= want) continue;              // a smaller tail serves the interval
@@ -527,12 +513,11 @@ relp_status_t Engine::ft_plan_and_alloc() {
     // per-row loops dominate next to nothing -- measured 2,670 it/s at 48 / 8, 2,870 at 64 / 8, 2,975 at 64 / 16)
     else if (force_big != 0 && force_big != 1 && fits_tier2 && ((want = cfg_.update_block < 0 ? 64 : want), plan(2, lay_.m, kFtMinStage))) {}
     if (!ft_) return RELP_OK;
-    if (std::getenv("RELP_DEBUG"))
+    if (sw_.debug)
         std::fprintf(stderr, "[relp] persistent pivot kernel: m %d, layout %s, %d right-hand-side copies, dense tail %d, LDS base %zu bytes\n",
                      lay_.m, ft_tier_ >= 2 ? "nothing per row in LDS" : ft_big_ ? "big" : "all-in-LDS", ft_rhs_cap_, ft_tcap_,
                      ft_lds_base_bytes(lay_.m, ft_tcap_, ft_eta_cap_, ft_tier_, ft_rhs_cap_));
     const int64_t tc = ft_tcap_, ldt = tc + 1, m = lay_.m, nwp = kFtWaves + 1;
-    std::vector<char> dummy;
     int64_t o = 0;
     auto take = [&](int64_t bytes) { const int64_t at = o; o += round_up(bytes, 16); return at; };
     // (what a refactorisation clears to 0 first, then what it clears to -1, then the rest: two memsets per reset)
@@ -544,20 +529,13 @@ relp_status_t Engine::ft_plan_and_alloc() {
                   o_nzv = take(ft_tier_ >= 1 ? 8 * m : 0), o_rhoi = take(ft_tier_ >= 2 ? 4 * m : 0), o_nzc = take(16),
                   o_bits = take(ft_tier_ >= 2 ? kFtBitmapBytes + 1024 : 0);
     ft_zero_bytes_ = o_pv - o_hdr; ft_ones_bytes_ = o_ei - o_pv;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_ft_buf_), (size_t)o));
+    HIP_TRY(d_ft_buf_.alloc_raw((size_t)o));
     HIP_TRY(hipMemset(d_ft_buf_, 0, (size_t)o));
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_ft_hdr_), 4 * sizeof(int32_t), hipHostMallocDefault));
+    HIP_TRY(h_ft_hdr_.alloc(4 * sizeof(int32_t)));
     std::memset(h_ft_hdr_, 0, 4 * sizeof(int32_t));
     {   // the kernel's report in mapped host memory; without it (allocation refused) the copies below do the same job
-        void* hp = nullptr; void* dp = nullptr;
-        if (hipHostMalloc(&hp, sizeof(FtMirror) + sizeof(int32_t) * (size_t)lay_.m, hipHostMallocMapped) == hipSuccess &&
-            hipHostGetDevicePointer(&dp, hp, 0) == hipSuccess) {
-            h_mirror_ = static_cast<FtMirror*>(hp); d_mirror_ = static_cast<FtMirror*>(dp);
-            std::memset(h_mirror_, 0, sizeof(FtMirror));
-        } else {
-            if (hp) (void)hipHostFree(hp);
-            (void)hipGetLastError();
-        }
+        if (h_mirror_.alloc(sizeof(FtMirror) + sizeof(int32_t) * (size_t)lay_.m, true) == hipSuccess) std::memset(h_mirror_, 0, sizeof(FtMirror));
+        else (void)hipGetLastError();
     }
     fts_ = FtState{};
     fts_.m = lay_.m; fts_.tcap = ft_tcap_; fts_.ldt = (int32_t)ldt; fts_.eta_cap = ft_eta_cap_;
@@ -588,9 +566,8 @@ relp_status_t Engine::ft_plan_and_alloc() {
     }
     fts_.big = ft_tier_; fts_.rhs_cap = ft_rhs_cap_;
     {   // hyper-sparse starts: L and L' by default (U' starts from the leaving pivot's level anyway; on U the spike reaches the first groups: measured 31.4 of 31.4 passes on 25FV47, not worth the reduction); RELP_FT_HYPER = bit mask
-        const char* e = std::getenv("RELP_FT_HYPER");
-        fts_.hyper = e ? std::atoi(e) : 0x9;
-        hyper_forced_ = e != nullptr;
+        fts_.hyper = sw_.ft_hyper;
+        hyper_forced_ = sw_.ft_hyper_set;
     }
     fts_.prof = reinterpret_cast<long long*>(d_ft_buf_ + o_prof);
     fts_.journal = reinterpret_cast<int32_t*>(d_ft_buf_ + o_journal);
@@ -599,8 +576,7 @@ relp_status_t Engine::ft_plan_and_alloc() {
     fts_.max_updates = cfg_.update_block < 0 ? ft_tcap_ : std::max(1, std::min(cfg_.update_block, ft_tcap_));
     block_ = fts_.max_updates;
     {   // RELP_FT_GRID_PRICE = 0 / 1 forces the choice (any layout: -pi is current in global memory between launches)
-        const char* e = std::getenv("RELP_FT_GRID_PRICE");
-        ft_grid_price_ = e ? std::atoi(e) != 0 : (ft_tier_ >= 2 && nr_columns() >= 32768);
+        ft_grid_price_ = sw_.ft_grid_price >= 0 ? sw_.ft_grid_price != 0 : (ft_tier_ >= 2 && nr_columns() >= 32768);
     }
     return ft_build_price_ell();
 }
@@ -657,8 +633,7 @@ relp_status_t Engine::ft_build_price_ell() {
         }
         o_idx32 = put(w.data(), w.size() * 4); o_lidx32 = put(lw.data(), lw.size() * 4);
     }
-    if (d_pe_buf_) { HIP_TRY(hipFree(d_pe_buf_)); d_pe_buf_ = nullptr; }
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_pe_buf_), buf.size()));
+    HIP_TRY(d_pe_buf_.alloc_raw(buf.size()));              // (frees the copy of before a row removal)
     HIP_TRY(hipMemcpy(d_pe_buf_, buf.data(), buf.size(), hipMemcpyHostToDevice));
     pe_.val = reinterpret_cast<const double*>(d_pe_buf_ + o_val);
     pe_.lval = reinterpret_cast<const double*>(d_pe_buf_ + o_lval);
@@ -715,7 +690,6 @@ relp_status_t Engine::ft_read_report(bool* have_basis) {
     since_flush_ = h_ft_hdr_[0];
     ft_need_refactor_ = h_ft_hdr_[2] != 0;
     if (have_basis) {
-        if (!h_basis_) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_basis_), sizeof(int32_t) * (size_t)std::max(m_alloc_rows_, lay_.m), hipHostMallocDefault));
         std::memcpy(h_basis_, h_mirror_->basis, sizeof(int32_t) * (size_t)lay_.m);     // (the next launch rewrites the mirror)
         *have_basis = true;
     }
@@ -738,10 +712,8 @@ void Engine::ft_enqueue_pivots(const FtState& go, int rule, int64_t left) {
     FtProblem pb = ft_problem(rule);
     pb.external_price = 1;
     const ColumnTable ct = table();
-    SelectPartials sp;
-    sp.k1 = d_part_k1_; sp.j = d_part_j_; sp.in_basis = d_in_basis_; sp.tol_cost = cfg_.tol_cost; sp.rule = rule;
-    const int nb_struct = price_csc_blocks(0, lay_.nr_normal), nb_virt = price_virtual_blocks(ct);
-    sp.n = nr_columns(); sp.offset = 0; sp.nb_struct = nb_struct; sp.tol_tie = cfg_.tol_tie; sp.p_lo = 0; sp.cols_per_slot = 256;
+    const SelectPartials sp = lu_partials(rule);
+    const int nb_struct = sp.nb_struct, nb_virt = price_virtual_blocks(ct);
     for (int64_t k = 0; k < batch; ++k) {
         if (nb_struct > 0 && nb_virt > 0) {
             launch_price_csc_all(csc(), ct, d_minus_pi_, d_d_, lay_.nr_normal, phase_, sp, nb_virt, d_rec_, stream_);
@@ -752,7 +724,7 @@ void Engine::ft_enqueue_pivots(const FtState& go, int rule, int64_t left) {
             launch_price_virtual_sel(ct, d_minus_pi_, d_d_, phase_, spv, d_rec_, stream_);
         }
         launch_select_partials_csc(sp, nb_struct + nb_virt, d_d_, csc(), ct, lay_.m, nullptr, d_rec_, stream_);
-        pb.mirror = k + 1 == batch ? d_mirror_ : nullptr;
+        pb.mirror = k + 1 == batch ? h_mirror_.device() : nullptr;
         launch_ft_run(dlu_, go, pb, 1, stream_);
     }
 }
@@ -763,7 +735,7 @@ FtProblem Engine::ft_problem(int rule) const {
     pb.minus_pi = d_minus_pi_; pb.b = d_b_; pb.alpha = d_alpha_; pb.rho = d_rho_; pb.d = d_d_;
     pb.basis = d_basis_; pb.in_basis = d_in_basis_; pb.trace = d_trace_; pb.trace_cap = trace_cap_;
     pb.rec = d_rec_;
-    pb.mirror = d_mirror_;
+    pb.mirror = h_mirror_.device();
     pb.tol = tolerances();
     pb.rule = rule; pb.n = nr_columns(); pb.phase = phase_;
     return pb;
@@ -778,20 +750,18 @@ relp_status_t Engine::run_ft(int64_t max_iters, int64_t* done, int32_t* outcome)
     // step-wise API, phase switch, warm start -- may have written the two vectors: the first pivot rewrites them densely)
     if (ft_tier_ >= 2) HIP_TRY(hipMemsetAsync(fts_.nzc, 0xFF, 2 * sizeof(int32_t), stream_));
     const long long start = h_rec_->iterations;
-    const int rule = phase_ == 1 ? cfg_.phase_one_rule : cfg_.phase_two_rule;
+    const int rule = current_rule();
     struct Tick { int64_t& t; ~Tick() { ++t; } };
     // Look-ahead refactorisation (lu_refactor_lookahead): the kernel returns `la` updates before the file is full, and fills
     // the rest while the host factorises.  On for refactorisation intervals from 24 on; RELP_LU_LOOKAHEAD = 0 switches it off.
-    const int32_t la_env = luf_enabled_ ? 0 : (ft_tier_ >= 2 && !lu_lookahead_set_) ? 16 : lu_lookahead_env_;     // (RELP_LU_LOOKAHEAD, read at create; the device
+    const int32_t la_env = luf_enabled_ ? 0 : (ft_tier_ >= 2 && !sw_.lu_lookahead_set) ? 16 : sw_.lu_lookahead;     // (RELP_LU_LOOKAHEAD, read at create; the device
                                                                      // factorisation is synchronous on the engine's stream)
     const int32_t la = (fts_.max_updates >= 24 && la_env > 0) ? std::min(la_env, fts_.max_updates / 3) : 0;
     // Short intervals (the reference's cadence of 11: too short for the look-ahead above, which needs its updates inside the interval):
     // RELP_LU_PIPELINE_SHORT=1 lets the kernel return at the interval, pivot on into the REST of the dense tail (up to twice the
     // interval) while the host factorises, and replays those pivots onto the new factors -- the factors lag one interval behind, the
     // pivots are the same, the device never waits for a whole factorisation.  Opt-in: a measurement (bench: reference cadence).
-    const char* pipeline_s = std::getenv("RELP_LU_PIPELINE_SHORT");
-    const bool pipeline_env = pipeline_s && std::atoi(pipeline_s) != 0;
-    const bool pipeline_short = pipeline_env && la == 0 && !luf_enabled_ && la_env > 0 && fts_.max_updates < 24 && 2 * fts_.max_updates <= ft_tcap_;
+    const bool pipeline_short = sw_.lu_pipeline_short && la == 0 && !luf_enabled_ && la_env > 0 && fts_.max_updates < 24 && 2 * fts_.max_updates <= ft_tcap_;
     bool have_basis = false;                               // h_basis_ holds the basis as the last launch left it
     while (h_rec_->outcome == DEV_RUNNING && h_rec_->iterations - start < max_iters) {
         if (ft_need_refactor_) {
@@ -824,13 +794,7 @@ relp_status_t Engine::run_ft(int64_t max_iters, int64_t* done, int32_t* outcome)
     }
     if (hipGetLastError() != hipSuccess) return fail(RELP_E_HIP, "kernel launch failed");
     int32_t oc = RELP_RUNNING;
-    if (h_rec_->outcome == DEV_NO_CANDIDATE) {
-        if (hold_phase_end_) oc = 100;                     // (kHeldNoCandidate, relp_engine.cpp: columns are barred by the pivot rescue)
-        else if (phase_ == 2) oc = RELP_OPTIMAL;
-        else if ((st = finish_phase_one(&oc))) return st;
-    } else if (h_rec_->outcome == DEV_NO_ROW) {
-        oc = phase_ == 2 ? RELP_UNBOUNDED : RELP_NO_ROW_PHASE_ONE;
-    }
+    if ((st = outcome_of_record(&oc))) return st;
     if (done) *done = h_rec_->iterations - start;
     if (outcome) *outcome = oc;
     return RELP_OK;
@@ -841,7 +805,7 @@ relp_status_t Engine::lu_phase_cycles(int64_t* out16) {
     if (!lu_ || !ft_) return fail(RELP_E_UNSUPPORTED, "phase clocks are the persistent pivot kernel's");
     HIP_TRY(hipStreamSynchronize(stream_));
     HIP_TRY(hipMemcpy(out16, fts_.prof, 16 * sizeof(int64_t), hipMemcpyDeviceToHost));
-    if (std::getenv("RELP_DEBUG")) {                       // passes walked per sweep of L, U, U', L' against the whole schedule
+    if (sw_.debug) {                       // passes walked per sweep of L, U, U', L' against the whole schedule
         int64_t ex[16];
         HIP_TRY(hipMemcpy(ex, fts_.prof + 16, sizeof ex, hipMemcpyDeviceToHost));
         if (ex[15]) std::fprintf(stderr, "[relp] non-zeros per pivot (layout 2): entering column %.1f, eta row %.1f, spike %.1f\n",
@@ -870,8 +834,26 @@ relp_status_t Engine::lu_kernel_layout(int32_t* out4) const {
 
 relp_status_t Engine::lu_lookahead_stats(int64_t* out4) const {
     if (!lu_) return RELP_E_STATE;
-    out4[0] = lu_lookahead_installs_; out4[1] = lu_replayed_changes_; out4[2] = (ft_tier_ >= 2 && !lu_lookahead_set_) ? 16 : lu_lookahead_env_; out4[3] = lu_fuse_lanes_env_;
+    out4[0] = lu_lookahead_installs_; out4[1] = lu_replayed_changes_; out4[2] = (ft_tier_ >= 2 && !sw_.lu_lookahead_set) ? 16 : sw_.lu_lookahead; out4[3] = sw_.fuse_lanes;
     return RELP_OK;
+}
+
+// the PRICE partials of the CSC kernels: 256 columns per slot, the structural blocks in front of the virtual ones
+SelectPartials Engine::lu_partials(int rule) const {
+    SelectPartials sp = tab_partials(rule);
+    sp.nb_struct = price_csc_blocks(0, lay_.nr_normal); sp.cols_per_slot = 256;
+    return sp;
+}
+
+void Engine::lu_btran(int32_t row, const double* rhs, double* out) {
+    if (ft_) launch_ft_btran(dlu_, fts_, ft_problem(0), row, rhs, out, stream_);
+    else launch_lu_btran(dlu_, deferred(), rhs, row, out, d_lu_scratch_, nullptr, stream_);
+}
+
+// (the product form's FTRAN leaves the pending W to the caller: launch_apply_w; `rec` is its alone)
+void Engine::lu_ftran(const double* rhs, double* out, const PivotRecord* rec) {
+    if (ft_) launch_ft_ftran(dlu_, fts_, ft_problem(0), -1, rhs, out, stream_);
+    else launch_lu_ftran(dlu_, rhs, out, d_lu_scratch_, rec, stream_);
 }
 
 // One pivot of the LU engine: CSC PRICE -> select + scatter a_q -> FTRAN (L, U solves) -> W correction
@@ -879,11 +861,8 @@ relp_status_t Engine::lu_lookahead_stats(int64_t* out4) const {
 void Engine::enqueue_iteration_lu(int rule) {
     const ColumnTable ct = table();
     const DeferredUpdate du = deferred();
-    SelectPartials sp;
-    sp.k1 = d_part_k1_; sp.j = d_part_j_; sp.in_basis = d_in_basis_; sp.tol_cost = cfg_.tol_cost; sp.rule = rule;
-    const int nb_struct = price_csc_blocks(0, lay_.nr_normal);
-    sp.n = nr_columns(); sp.offset = 0; sp.nb_struct = nb_struct; sp.tol_tie = cfg_.tol_tie; sp.p_lo = 0; sp.cols_per_slot = 256;
-    const int nb_virt = price_virtual_blocks(ct);
+    const SelectPartials sp = lu_partials(rule);
+    const int nb_struct = sp.nb_struct, nb_virt = price_virtual_blocks(ct);
     prof_begin(RELP_K_PRICE);
     if (nb_struct > 0 && nb_virt > 0) {
         launch_price_csc_all(csc(), ct, d_minus_pi_, d_d_, lay_.nr_normal, phase_, sp, nb_virt, d_rec_, stream_);

@@ -14,7 +14,7 @@
 namespace relp {
 
 struct Engine::LufState {
-    char* d_buf = nullptr;
+    DeviceBuf<char> d_buf;
     LufMatrix M{}; LufWork W{}; LufOut O{};
     int32_t cap = 0, nb_cap = 0;
     bool dirty = true;
@@ -24,17 +24,15 @@ struct Engine::LufState {
     FtPivotInfo* pinfo = nullptr;
     int64_t img_cap = 0;
     bool resident = false;                                       // hlu_ does not hold the rows of the factors in use (they are on the device)
-    ~LufState() { if (d_buf) (void)hipFree(d_buf); }
 };
 
 void Engine::luf_release() { delete luf_; luf_ = nullptr; }
-void Engine::luf_mark_dirty() { if (luf_) luf_->dirty = true; }
 
 // static tables + workspace for the current shape of the problem (rows may have been removed, the phase may have changed)
 relp_status_t Engine::luf_prepare() {
     if (!luf_) luf_ = new LufState();
     LufState& S = *luf_;
-    if (S.d_buf) { HIP_TRY(hipFree(S.d_buf)); S.d_buf = nullptr; }
+    S.d_buf.reset();
     const int32_t m = lay_.m, nprov = lay_.n_provider, na = lay_.nr_artificial;
     // row-major copy of the provider columns (structural incl. bound rows, virtual), in column order
     std::vector<int32_t> rcount(m + 1, 0);
@@ -50,8 +48,7 @@ relp_status_t Engine::luf_prepare() {
     for (int32_t a = 0; a < na; ++a) art_of_row[lay_.column_to_row[a]] = a;
     // sizes: the bump is eliminated on sparse rows in an arena; RELP_LUF_BUMP_CAP bounds its rows (default: any), a bump or a
     // fill-in beyond the arrays falls back to the host
-    const char* cap_env = std::getenv("RELP_LUF_BUMP_CAP");
-    S.nb_cap = std::min<int32_t>(m, cap_env ? std::max(16, std::atoi(cap_env)) : m);
+    S.nb_cap = std::min<int32_t>(m, sw_.luf_bump_cap);
     // (a small dense bump may fill in completely)
     const int64_t arena_cap = std::min<int64_t>(INT32_MAX / 4, 3 * (nnz + (int64_t)lay_.wrapped_na + na + m) + 64 * (int64_t)S.nb_cap + 1024 +
                                                                   4 * std::min<int64_t>((int64_t)S.nb_cap * S.nb_cap, int64_t(1) << 21));
@@ -73,8 +70,7 @@ relp_status_t Engine::luf_prepare() {
     const int64_t o_ltr = take(4 * arena_cap), o_lts = take(4 * arena_cap), o_ltv = take(8 * arena_cap), o_ltp = take(4 * ((int64_t)S.nb_cap + 1)),
                   o_lto = take(4 * arena_cap), o_cnt = take(512);
     const int64_t o_red = take(8 * 8), o_sc = take(64);
-    const char* dense_env = std::getenv("RELP_LUF_DENSE");                   // rows of the dense finish (<= 64; 0 = off)
-    const int32_t dense_cap = dense_env ? std::max(0, std::min(64, std::atoi(dense_env))) : 64;
+    const int32_t dense_cap = sw_.luf_dense;                                // RELP_LUF_DENSE: rows of the dense finish (<= 64; 0 = off)
     const int64_t o_dense = take(8 * (int64_t)64 * 64), o_dint = take(4 * 8 * 64);
     const int64_t o_utr = take(4 * arena_cap), o_utc = take(4 * arena_cap), o_utv = take(8 * arena_cap), o_vw = take(4 * ((int64_t)m + 2)),
                   o_vtmp = take(4 * arena_cap);
@@ -102,7 +98,7 @@ relp_status_t Engine::luf_prepare() {
         f.tbits = take(4 * n_words);
     }
     const int64_t o_pinfo = take((int64_t)sizeof(FtPivotInfo) * m);
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&S.d_buf), (size_t)o));
+    HIP_TRY(S.d_buf.alloc_raw((size_t)o));
     HIP_TRY(hipMemset(S.d_buf, 0, (size_t)o));
     char* const B = S.d_buf;
     HIP_TRY(hipMemcpy(B + o_rptr, rcount.data(), 4 * ((size_t)m + 1), hipMemcpyHostToDevice));
@@ -146,7 +142,7 @@ relp_status_t Engine::luf_prepare() {
         const LufTriangle* tri4[4] = {&O.Lf, &O.Uf, &O.Ub, &O.Lb};
         const LufTriangle* trt4[4] = {&O.Lb, &O.Ub, &O.Uf, &O.Lf};     // the transposed pattern of each
         // (fused schedules read copies of some right-hand sides behind x: ft_rhs_cap_ words of the layout; RELP_FUSE_LANES, read at create)
-        const int32_t fuse = ft_rhs_cap_ > 0 ? lu_fuse_lanes_env_ : 0;
+        const int32_t fuse = ft_rhs_cap_ > 0 ? sw_.fuse_lanes : 0;
         for (int q = 0; q < 4; ++q) {
             const SchedOff& f = so[q];
             const bool maskable = q == 1 || q == 2;
@@ -200,7 +196,7 @@ relp_status_t Engine::lu_factor_on_device(int32_t* device_status) {
     }
     luf_kernel_us_ += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
     ++luf_runs_;
-    if (std::getenv("RELP_DEBUG") && luf_runs_ % 200 == 0) {          // phase clocks of the factorisation kernel (relp_lu_factor_core.h: LUF_LAP)
+    if (sw_.debug && luf_runs_ % 200 == 0) {          // phase clocks of the factorisation kernel (relp_lu_factor_core.h: LUF_LAP)
         int32_t cnt[128] = {0};
         HIP_TRY(hipMemcpy(cnt, S.W.counters, sizeof cnt, hipMemcpyDeviceToHost));
         const unsigned long long* ph = reinterpret_cast<const unsigned long long*>(cnt + 8);

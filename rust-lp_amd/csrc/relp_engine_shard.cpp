@@ -20,7 +20,7 @@ void Engine::shard_ranges(int32_t* col_lo, int32_t* col_hi, int32_t* row_lo, int
 relp_status_t Engine::shard_pivot() {
     if (lu_) return fail(RELP_E_UNSUPPORTED, "the LU engine is not sharded");
     if (!tableau_) return fail(RELP_E_STATE, "relp_shard_pivot is the tableau engine's step");
-    const int rule = phase_ == 1 ? cfg_.phase_one_rule : cfg_.phase_two_rule;
+    const int rule = current_rule();
     const TableauView tv = tview();
     const DeferredUpdate du = deferred();
     const SelectPartials sp = tab_partials(rule);
@@ -37,7 +37,7 @@ relp_status_t Engine::shard_pivot() {
 
 relp_status_t Engine::shard_price(double* dev_candidate) {
     if (lu_) return fail(RELP_E_UNSUPPORTED, "the LU engine is not sharded");
-    const int rule = phase_ == 1 ? cfg_.phase_one_rule : cfg_.phase_two_rule;
+    const int rule = current_rule();
     if (tableau_) {
         // local PRICE result = the partial argmin the last row update left behind (or a scan of d);
         // the candidate message carries the tableau column alpha itself
@@ -52,7 +52,6 @@ relp_status_t Engine::shard_price(double* dev_candidate) {
         prof_end();
         return RELP_OK;
     }
-    const double* A = dA_ - (int64_t)lay_.col_lo * ld_a_;
     prof_begin(RELP_K_PRICE);
     enqueue_price(phase_, d_minus_pi_, d_rec_, lay_.col_lo, lay_.col_hi);
     prof_end();
@@ -60,7 +59,7 @@ relp_status_t Engine::shard_price(double* dev_candidate) {
     launch_select_column(d_d_, d_in_basis_, nr_columns(), rule, cfg_.tol_cost, cfg_.tol_tie, d_rec_, stream_);
     prof_end();
     prof_begin(RELP_K_BUILD_COLUMN);
-    launch_build_column(A, ld_a_, table(), lay_.m, d_aq_, d_rec_, stream_);
+    launch_build_column(A_base(), ld_a_, table(), lay_.m, d_aq_, d_rec_, stream_);
     launch_pack_candidate(d_aq_, lay_.m, dev_candidate, d_rec_, stream_);
     prof_end();
     return RELP_OK;
@@ -68,7 +67,7 @@ relp_status_t Engine::shard_price(double* dev_candidate) {
 
 relp_status_t Engine::shard_select_column(const double* dev_candidates, int32_t count) {
     if (lu_) return fail(RELP_E_UNSUPPORTED, "the LU engine is not sharded");
-    const int rule = phase_ == 1 ? cfg_.phase_one_rule : cfg_.phase_two_rule;
+    const int rule = current_rule();
     if (tableau_) {
         // the winner's payload is the entering tableau column (alpha) itself: pick it and run the ratio test
         if (count > 64) return fail(RELP_E_UNSUPPORTED, "at most 64 shards");
@@ -84,7 +83,7 @@ relp_status_t Engine::shard_select_column(const double* dev_candidates, int32_t 
 
 relp_status_t Engine::shard_ftran(double* dev_alpha_slice) {
     if (lu_) return fail(RELP_E_UNSUPPORTED, "the LU engine is not sharded");
-    double* Binv = dBinv_ - (int64_t)lay_.row_lo * ld_b_;
+    double* Binv = Binv_base();
     prof_begin(RELP_K_FTRAN);
     launch_ftran(Binv, ld_b_, lay_.m, lay_.row_lo, lay_.row_hi, d_aq_, dev_alpha_slice, lay_.row_lo, d_rec_, stream_);
     launch_pad_slice(dev_alpha_slice, lay_.row_hi - lay_.row_lo, lay_.row_stride, stream_);
@@ -94,7 +93,7 @@ relp_status_t Engine::shard_ftran(double* dev_alpha_slice) {
 
 relp_status_t Engine::shard_ratio(const double* dev_alpha_slices, int32_t count, double* dev_rho) {
     if (lu_) return fail(RELP_E_UNSUPPORTED, "the LU engine is not sharded");
-    double* Binv = dBinv_ - (int64_t)lay_.row_lo * ld_b_;
+    double* Binv = Binv_base();
     if (block_ == 0) {
         prof_begin(RELP_K_RATIO);
         launch_gather_alpha(dev_alpha_slices, count, lay_.row_stride, lay_.m, d_alpha_, d_rec_, stream_);
@@ -125,7 +124,7 @@ relp_status_t Engine::shard_flush_begin(double** dev_snapshot, int64_t* len) {
     if (lu_) return fail(RELP_E_UNSUPPORTED, "the LU engine is not sharded");
     if (len) *len = 0;
     if (block_ == 0) return RELP_OK;
-    double* Binv = dBinv_ - (int64_t)lay_.row_lo * ld_b_;
+    double* Binv = Binv_base();
     prof_begin(RELP_K_FLUSH);
     launch_flush_snapshot(deferred(), Binv, ld_b_, lay_.row_lo, lay_.row_hi, d_rec_, stream_);
     prof_end();
@@ -138,7 +137,7 @@ relp_status_t Engine::shard_flush_end() {
     if (lu_) return fail(RELP_E_UNSUPPORTED, "the LU engine is not sharded");
     if (block_ == 0) return RELP_OK;
     const DeferredUpdate du = deferred();
-    double* Binv = dBinv_ - (int64_t)lay_.row_lo * ld_b_;
+    double* Binv = Binv_base();
     prof_begin(RELP_K_FLUSH);
     launch_flush_apply(du, Binv, ld_b_, lay_.m, lay_.row_lo, lay_.row_hi, d_rec_, stream_);
     launch_flush_reset(du, d_rec_, stream_);
@@ -149,7 +148,7 @@ relp_status_t Engine::shard_flush_end() {
 
 relp_status_t Engine::shard_update(const double* dev_rho) {
     if (lu_) return fail(RELP_E_UNSUPPORTED, "the LU engine is not sharded");
-    double* Binv = dBinv_ - (int64_t)lay_.row_lo * ld_b_;
+    double* Binv = Binv_base();
     prof_begin(RELP_K_UPDATE_VECTORS);
     launch_update_vectors(lay_.m, d_alpha_, dev_rho, d_b_, d_minus_pi_, d_basis_, d_in_basis_, d_trace_, trace_cap_, d_rec_,
                           stream_);
@@ -172,25 +171,19 @@ relp_status_t Engine::shard_update(const double* dev_rho) {
 // artificial's row through the same candidate message and all-gather as a PRICE step, the lowest column wins on
 // every rank and enters in that row at zero level.  No eligible column anywhere: the row is redundant.
 relp_status_t Engine::remove_artificial_basis_variables_sharded(std::vector<int32_t>& rows_to_remove) {
-    HIP_TRY(hipStreamSynchronize(stream_));
-    std::vector<int32_t> basis(lay_.m);
-    HIP_TRY(hipMemcpy(basis.data(), d_basis_, sizeof(int32_t) * lay_.m, hipMemcpyDeviceToHost));
-    std::vector<int32_t> arts;
-    for (int32_t v : basis) if (v < lay_.nr_artificial) arts.push_back(v);
+    std::vector<int32_t> basis, arts;
+    relp_status_t st = basic_artificials(&basis, &arts);
+    if (st) return st;
     if (arts.empty()) return RELP_OK;
     if (!coll_allgather_)
         return fail(RELP_E_STATE, "artificial variables are still basic after phase 1: the sharded engine pivots them out "
                                   "through the collective hooks (relp_shard_set_collectives / relp_rccl_attach)");
-    std::sort(arts.begin(), arts.end());
-    relp_status_t st;
     const int32_t g = std::max(cfg_.shard_count, 1);
     const bool textbook = cfg_.artificial_removal == RELP_ARTIFICIAL_TEXTBOOK;
     for (int32_t a : arts) {
         int32_t pivot_row = lay_.column_to_row[a];             // phase_one.rs:236: the row the artificial STARTED in
         if (textbook) pivot_row = (int32_t)(std::find(basis.begin(), basis.end(), a) - basis.begin());   // the row it is basic in
-        if ((st = download_rec())) return st;
-        h_rec_->outcome = DEV_RUNNING;
-        if ((st = upload_rec())) return st;
+        if ((st = edit_rec())) return st;
         const TableauView tv = tview();
         const DeferredUpdate du = deferred();
         const SelectPartials sp = tab_partials(RELP_RULE_FIRST_PROFITABLE);        // key = column index
@@ -203,11 +196,7 @@ relp_status_t Engine::remove_artificial_basis_variables_sharded(std::vector<int3
         launch_tab_select_candidate_ratio(d_msg_cands_, g, lay_.candidate_len, lay_.m, d_alpha_, d_b_, d_basis_, RELP_RULE_FIRST_PROFITABLE,
                                           tolerances(), du, pivot_row, d_rec_, stream_);
         if ((st = download_rec())) return st;
-        if (h_rec_->outcome == DEV_NO_CANDIDATE) {      // (textbook: the artificial's own row; remove_rows moves it there first)
-            if (textbook) { stuck_artificials_.push_back(a); rows_to_remove.push_back(lay_.column_to_row[a]); }
-            else rows_to_remove.push_back(a);
-            continue;
-        }
+        if (h_rec_->outcome == DEV_NO_CANDIDATE) { keep_artificial_row(a, rows_to_remove); continue; }
         if (h_rec_->alpha_r == 0.0) return fail(RELP_E_ZERO_PIVOT, "Pivot value can't be zero.");
         launch_tab_update_all(tv, du, sp, lay_.m, d_alpha_, d_b_, d_basis_, d_in_basis_, d_trace_, trace_cap_, d_rec_, stream_);
         tab_partials_valid_ = false;
@@ -223,14 +212,14 @@ relp_status_t Engine::shard_set_collectives(relp_allgather_fn ag, relp_allreduce
     coll_allgather_ = ag; coll_allreduce_ = ar; coll_ctx_ = ctx;
     const int64_t g = std::max(cfg_.shard_count, 1);
     if (!d_msg_cand_) {
-        HIP_TRY(dev_alloc(&d_msg_status_, 2));
-        HIP_TRY(dev_alloc(&d_msg_statuses_, 2 * g));
-        HIP_TRY(dev_alloc(&d_msg_cand_, lay_.candidate_len));
-        HIP_TRY(dev_alloc(&d_msg_cands_, lay_.candidate_len * g));
+        HIP_TRY(d_msg_status_.alloc(2));
+        HIP_TRY(d_msg_statuses_.alloc(2 * g));
+        HIP_TRY(d_msg_cand_.alloc(lay_.candidate_len));
+        HIP_TRY(d_msg_cands_.alloc(lay_.candidate_len * g));
         if (!tableau_) {
-            HIP_TRY(dev_alloc(&d_msg_slice_, lay_.row_stride));
-            HIP_TRY(dev_alloc(&d_msg_slices_, (int64_t)lay_.row_stride * g));
-            HIP_TRY(dev_alloc(&d_msg_rho_, rho_len()));
+            HIP_TRY(d_msg_slice_.alloc(lay_.row_stride));
+            HIP_TRY(d_msg_slices_.alloc((int64_t)lay_.row_stride * g));
+            HIP_TRY(d_msg_rho_.alloc(rho_len()));
         }
     }
     return RELP_OK;
@@ -249,7 +238,7 @@ relp_status_t Engine::shard_iteration() {
         // two launches around the all-gather: [local PRICE winner + its tableau column into the message] -> gather ->
         // [winner among the messages + ratio test in every workgroup + the update] (relp_kernels.h: launch_tab_ratio_update_all)
         if (g > 64) return fail(RELP_E_UNSUPPORTED, "at most 64 shards");
-        const int rule = phase_ == 1 ? cfg_.phase_one_rule : cfg_.phase_two_rule;
+        const int rule = current_rule();
         const TableauView tv = tview();
         const DeferredUpdate du = deferred();
         const SelectPartials sp = tab_partials(rule);
@@ -266,8 +255,8 @@ relp_status_t Engine::shard_iteration() {
                                     trace_cap_, tolerances(), nullptr, d_shadow_, d_shadow_meta_, d_rec_, stream_, d_msg_cands_, g,
                                     lay_.candidate_len, rule);
         prof_end();
-        std::swap(d_b_, d_b_alt_);
-        std::swap(d_basis_, d_basis_alt_);
+        d_b_.swap(d_b_alt_);
+        d_basis_.swap(d_basis_alt_);
         shadow_pending_ = true;
         if (++since_flush_ >= block_) enqueue_flush();
         ++prof_tick_;
@@ -380,10 +369,7 @@ relp_status_t Engine::poll(int32_t* outcome, int64_t* iterations) {
     relp_status_t st = download_rec();
     if (st) return st;
     int32_t oc = RELP_RUNNING;
-    if (h_rec_->outcome == DEV_NO_CANDIDATE) {
-        if (phase_ == 2) oc = RELP_OPTIMAL;
-        else if ((st = finish_phase_one(&oc))) return st;
-    } else if (h_rec_->outcome == DEV_NO_ROW) oc = phase_ == 2 ? RELP_UNBOUNDED : RELP_NO_ROW_PHASE_ONE;
+    if ((st = outcome_of_record(&oc))) return st;         // (nothing is held back here: the pivot rescue is unsharded)
     if (iterations) *iterations = h_rec_->iterations;      // after the phase boundary: it may have pivoted at zero level
     if (outcome) *outcome = oc;
     return RELP_OK;
