@@ -15,6 +15,7 @@
 // reference carry the tolerances of relp_config_t.
 #pragma once
 
+#include <array>
 #include <cmath>
 #include <cstdint>
 #include <limits>
@@ -301,6 +302,9 @@ class Tableau {
     // every `pivots` basis changes; revised and tableau engines, default 1,000 for sparse input below 4,097 rows, 0 = never
     void set_reinversion_interval(int64_t pivots) { ck(relp_set_reinversion_interval(h_, pivots)); }
     int64_t reinversions() const { return relp_reinversions(h_); }
+    // relp_retab_stats: {batch solves of the rebuilds with x in LDS, with x in global slabs, workgroups of the last launch
+    // of the second kind, bytes of the slab buffer}
+    std::array<int64_t, 4> retab_stats() { std::array<int64_t, 4> out{}; ck(relp_retab_stats(h_, out.data())); return out; }
 
     // ---- loops ---------------------------------------------------------------------------------------------
     // phase_one::primal (phase_one.rs:125-170) / phase_two::primal (phase_two.rs:22-51): up to max_iters basis

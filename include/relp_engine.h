@@ -218,14 +218,19 @@ relp_status_t relp_solve_relaxation(relp_engine_t *h, int64_t max_iters, int32_t
  * RELP_ENGINE_REVISED: any basis (basis_inverse_rows.rs:103-129: LU - factorised on the host like every
  * refactorisation - then m unit solves, b and -pi on the device; slack bases are a signed permutation and take a
  * shortcut); RELP_ENGINE_TABLEAU (unsharded): any basis -- the tableau B^-1 [A | I] is re-tabulated column by column from the
- * factors, then b, the reduced costs and -obj (tests/cpp/test_tableau.cpp, tests/test_gpu_parity.py::test_from_basis_*). */
+ * factors, then b, the reduced costs and -obj (tests/cpp/test_tableau.cpp, tests/test_gpu_parity.py::test_from_basis_*).
+ * "Any basis" holds at any m on both dense engines: the m unit solves / the solves of the stored columns keep their work
+ * vector in LDS up to m = 9,984 and in a slab of global memory per workgroup beyond (relp_retab_stats;
+ * tests/test_gpu_retab_any_m.py).  RELP_E_SINGULAR: a column twice, or a basis the factorisation declines. */
 relp_status_t relp_from_basis(relp_engine_t *h, const int32_t *basis_columns_m);
 /* RELP_ENGINE_REVISED and RELP_ENGINE_TABLEAU (unsharded), an f64 matter (the exact reference never needs it,
  * `should_refactor() = false`, basis_inverse_rows.rs:175-179): every `pivots` basis changes inside relp_run the state is
  * rebuilt from the columns of the current basis -- host LU, then on the device B^-1 row by row (revised) or the tableau
  * B^-1 [A | I] column by column (tableau), b = B^-1 rhs, -pi / the reduced costs and -obj -- which bounds the error of a
  * representation that is otherwise only ever updated.  Default: 1,000 for sparse input (CSC, at most 10 % nonzeros)
- * with at most 4,096 rows -- where the host factorisation of a basis is cheap -- else 0 = never.
+ * with at most 4,096 rows -- where the host factorisation of a basis is cheap -- else 0 = never.  An interval set by hand
+ * (and relp_config_t.auto_reinversion) works at any m: beyond m = 9,984 the solves of a rebuild keep their work vector in
+ * global memory instead of LDS (relp_retab_stats).
  * relp_reinversions: how many have been done. */
 relp_status_t relp_set_reinversion_interval(relp_engine_t *h, int64_t pivots);
 int64_t       relp_reinversions(const relp_engine_t *h);
@@ -236,6 +241,12 @@ relp_status_t relp_flush(relp_engine_t *h);
  * owned columns with a nonzero entry among the pending rows R0 (the others have T0 + W R0 = T0), or every owned column
  * when RELP_TAB_FLUSH_ALL=1 was set at create.  Other engines: { 0, 0 }. */
 relp_status_t relp_tab_flush_stats(relp_engine_t *h, int64_t *out2);
+/* Revised and tableau engines: the batch solves of the rebuilds so far (relp_from_basis, re-inversion, re-tabulation: all m
+ * rows of B^-1, or every stored column of the tableau, in one launch).  out4 = { batch solves with the work vector in LDS (one
+ * workgroup per right-hand side, m <= 9,984), batch solves with it in a slab of global memory per workgroup (larger m, or
+ * RELP_RETAB_GLOBAL=1 at create), workgroups of the last launch of the second kind (at most two per CU, at most 256 MiB of
+ * slabs, at most RELP_RETAB_GROUPS when that was set at create), bytes of the slab buffer }.  Other engines: zeros. */
+relp_status_t relp_retab_stats(const relp_engine_t *h, int64_t *out4);
 /* Tableau engine: how many of the p pending rows of an update block the per-pivot kernels load per memory round trip:
  * RELP_TAB_LOAD_BATCH at create if it was 1 (one by one), 8, 16 or 32, else the default.  Other engines: 0. */
 int32_t       relp_tab_load_batch(const relp_engine_t *h);

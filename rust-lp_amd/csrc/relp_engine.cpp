@@ -116,6 +116,8 @@ Switches Switches::read() {
     s.luf_dense = std::max(0, std::min(64, num("RELP_LUF_DENSE", 64)));
     s.dump_basis_set = given("RELP_DUMP_BASIS");
     if (s.dump_basis_set) s.dump_basis = std::getenv("RELP_DUMP_BASIS");
+    s.retab_global = num("RELP_RETAB_GLOBAL", 0) != 0;
+    s.retab_groups = std::max(0, num("RELP_RETAB_GROUPS", 0));
     return s;
 }
 
@@ -1274,14 +1276,48 @@ relp_status_t Engine::ensure_lu_scratch() {
     return RELP_OK;
 }
 
+// Where the batch solve over `rhs_count` right-hand sides keeps x.  In LDS while it fits (groups = 0).  Otherwise, or with
+// RELP_RETAB_GLOBAL=1, in slabs of global memory: G = min(right-hand sides, 2 workgroups per CU, the slabs that fit into
+// 256 MiB, RELP_RETAB_GROUPS) workgroups with ld_b_ doubles each (profiles/r10_retab_any_m.md).
+relp_status_t Engine::batch_solve_slabs(int32_t rhs_count, LuSlabs* slabs) {
+    *slabs = LuSlabs{nullptr, ld_b_, 0};
+    if (rhs_count <= 0) return RELP_OK;
+    if (!sw_.retab_global && lu_batch_fits_lds(lay_.m)) { ++batch_solves_lds_; return RELP_OK; }
+    int dev = 0, cus = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    int64_t groups = std::min<int64_t>(rhs_count, 2 * (int64_t)std::max(cus, 1));
+    groups = std::min<int64_t>(groups, (int64_t(256) << 20) / ((int64_t)sizeof(double) * ld_b_));
+    if (sw_.retab_groups > 0) groups = std::min<int64_t>(groups, sw_.retab_groups);
+    groups = std::max<int64_t>(groups, 1);
+    if (lu_slab_cap_ < groups * ld_b_) {
+        lu_slab_cap_ = 0;
+        HIP_TRY(d_lu_slabs_.alloc(groups * ld_b_));
+        lu_slab_cap_ = groups * ld_b_;
+    }
+    slabs->x = d_lu_slabs_;
+    slabs->groups = (int32_t)groups;
+    slab_groups_last_ = slabs->groups;
+    ++batch_solves_slab_;
+    return RELP_OK;
+}
+
+relp_status_t Engine::retab_stats(int64_t* out4) const {
+    out4[0] = batch_solves_lds_; out4[1] = batch_solves_slab_; out4[2] = slab_groups_last_;
+    out4[3] = lu_slab_cap_ * (int64_t)sizeof(double);
+    return RELP_OK;
+}
+
 // With the factors of the basis on the device: the rows of B^-1 by m unit BTRANs written in place (the one-off
 // `BasisInverseRows::invert`, basis_inverse_rows.rs:103-129), -pi = -(w' B^-1) (carry/mod.rs:214-248) and b = B^-1 rhs, whose
 // download into `b` is enqueued, not awaited.  `rearm`: the record is re-armed before the FTRAN (a warm start may find it decided).
 relp_status_t Engine::inverse_from_factors(const std::vector<double>& w, bool rearm, std::vector<double>* b) {
+    LuSlabs slabs;
+    if (const relp_status_t st = batch_solve_slabs(lay_.m, &slabs)) return st;
     HIP_TRY(hipMemsetAsync(dBinv_, 0, sizeof(double) * (size_t)lay_.m * ld_b_, stream_));
     DeferredUpdate none = deferred();
     none.kmax = 0;
-    launch_lu_btran_rows(dlu_, none, dBinv_, ld_b_, d_lu_scratch_, stream_);
+    launch_lu_btran_rows(dlu_, none, dBinv_, ld_b_, slabs, stream_);
     HIP_TRY(hipMemcpyAsync(d_w_, w.data(), sizeof(double) * ld_b_, hipMemcpyHostToDevice, stream_));
     HIP_TRY(hipMemcpyAsync(d_aq_, lay_.rhs.data(), sizeof(double) * lay_.m, hipMemcpyHostToDevice, stream_));
     HIP_TRY(hipStreamSynchronize(stream_));             // w, lay_.rhs are host buffers
@@ -1313,7 +1349,9 @@ relp_status_t Engine::retabulate() {
     const int32_t c_first = lay_.sc_lo;
     ColumnTable storage = table();
     storage.nr_artificial = tab_na_;                    // storage columns keep the artificial block in front
-    if (!launch_lu_ftran_cols(dlu_, tv, A_base(), ld_a_, storage, c_first, lay_.sc_hi - c_first, stream_)) return RELP_OK;
+    LuSlabs slabs;
+    if ((st = batch_solve_slabs(lay_.sc_hi - c_first, &slabs))) return st;
+    launch_lu_ftran_cols(dlu_, tv, A_base(), ld_a_, storage, c_first, lay_.sc_hi - c_first, slabs, stream_);
     HIP_TRY(hipMemcpyAsync(d_aq_, lay_.rhs.data(), sizeof(double) * lay_.m, hipMemcpyHostToDevice, stream_));
     HIP_TRY(hipStreamSynchronize(stream_));
     launch_lu_ftran(dlu_, d_aq_, d_b_, d_lu_scratch_, nullptr, stream_);                 // b = B^-1 rhs
@@ -1393,8 +1431,7 @@ relp_status_t Engine::from_basis(const int32_t* basis_columns) {
         st = retabulate();
         if (st || !retab_done_) {
             lay_.nr_artificial = keep_na; phase_ = keep_phase;
-            return st ? st : fail(RELP_E_SINGULAR, "from_basis: the basis could not be factorised (or m is too large for the "
-                                                    "LDS-resident solves of the re-tabulation)");
+            return st ? st : fail(RELP_E_SINGULAR, "from_basis: the basis could not be factorised");
         }
         HIP_TRY(hipMemcpy(d_in_basis_, flags.data(), flags.size(), hipMemcpyHostToDevice));
         tab_partials_valid_ = false;

@@ -80,6 +80,8 @@ struct Switches {
     int luf_bump_cap = INT32_MAX;                         // RELP_LUF_BUMP_CAP (at least 16 when given)
     int luf_dense = 64;                                   // RELP_LUF_DENSE
     bool dump_basis_set = false; std::string dump_basis;  // RELP_DUMP_BASIS
+    bool retab_global = false;                            // RELP_RETAB_GLOBAL
+    int retab_groups = 0;                                 // RELP_RETAB_GROUPS (0: not given)
     static Switches read();
 };
 
@@ -162,6 +164,7 @@ class Engine : private EngineQueue {
     relp_status_t get_iterations(int64_t* out);
     relp_status_t get_degenerate_pivots(int64_t* out);
     relp_status_t tab_flush_stats(int64_t* out2);
+    relp_status_t retab_stats(int64_t* out4) const;
     int32_t tab_load_batch_size() const { return tableau_ ? load_batch_ : 0; }
     relp_status_t get_trace(int32_t* phase, int32_t* entering, int32_t* row, int32_t* leaving, int64_t cap,
                             int64_t* count);
@@ -272,6 +275,12 @@ class Engine : private EngineQueue {
     PinnedBuf<FtMirror> h_mirror_;                        // mapped: what k_ft_run reports (relp_kernels.h); .device() is its address there
     DeviceBuf<double> d_lu_scratch_;
     relp_status_t ensure_lu_scratch();
+    // the batch solves of a rebuild (re-inversion, re-tabulation, warm start) with x in global memory (relp_kernels.h: LuSlabs):
+    // one slab of ld_b_ doubles per workgroup, allocated at first use and kept; what relp_retab_stats reports
+    DeviceBuf<double> d_lu_slabs_; int64_t lu_slab_cap_ = 0;
+    int64_t batch_solves_lds_ = 0, batch_solves_slab_ = 0;
+    int32_t slab_groups_last_ = 0;
+    relp_status_t batch_solve_slabs(int32_t rhs_count, LuSlabs* slabs);
     DeviceLU dlu_{};
     relp_status_t lu_status_ = RELP_OK;                   // a failed refactorisation inside the loop
     int64_t lu_refactors_ = 0;

@@ -380,10 +380,16 @@ void launch_tab_basis_costs(const TableauView& tv, const int32_t* basis_indices,
                             hipStream_t s);
 void launch_tab_scan(const TableauView& tv, SelectPartials sp, const PivotRecord* rec, hipStream_t s);
 int32_t tab_scan_blocks(int32_t n_owned_columns);
+// The two batch solves (launch_lu_ftran_cols, launch_lu_btran_rows) keep the work vector x in LDS, one workgroup per
+// right-hand side, while lu_batch_fits_lds(m) (m <= 9,984).  Beyond that -- or when the caller asks for it -- `groups`
+// workgroups each own a slab of `ld` doubles (ld >= m, even) in `x` (groups * ld doubles) and walk the right-hand sides in
+// a grid-stride loop.  groups == 0: the LDS path.
+struct LuSlabs { double* x; int64_t ld; int32_t groups; };
+bool lu_batch_fits_lds(int32_t m);
 // re-tabulation: T0[:, c] = (LU)^-1 a_c for the stored columns [c_first, c_first + c_count) in one launch (a_c as in
-// launch_tab_build); false when the solve vector does not fit into LDS
-bool launch_lu_ftran_cols(const DeviceLU& lu, const TableauView& tv, const double* A, int64_t ld_a, const ColumnTable& ct,
-                          int32_t c_first, int32_t c_count, hipStream_t s);
+// launch_tab_build)
+void launch_lu_ftran_cols(const DeviceLU& lu, const TableauView& tv, const double* A, int64_t ld_a, const ColumnTable& ct,
+                          int32_t c_first, int32_t c_count, const LuSlabs& slabs, hipStream_t s);
 // entering column from the partials (no column build: the tableau column is read directly)
 void launch_tab_select(const TableauView& tv, SelectPartials sp, int32_t count, PivotRecord* rec, hipStream_t s);
 // alpha = T[:,q] = T0[:,q] + W R0[:,q]
@@ -484,7 +490,7 @@ void launch_lu_ftran(const DeviceLU& lu, const double* aq, double* v, double* sc
 void launch_lu_btran(const DeviceLU& lu, const DeferredUpdate& du, const double* rhs, int32_t row, double* rho,
                      double* scratch, const PivotRecord* rec, hipStream_t s);
 // every row of B^-1 = (LU)^-1 in one launch (workgroup i: e_i' B^-1 -> out + i * ld); `none`: a DeferredUpdate with kmax = 0
-void launch_lu_btran_rows(const DeviceLU& lu, const DeferredUpdate& none, double* out, int64_t ld, double* scratch,
+void launch_lu_btran_rows(const DeviceLU& lu, const DeferredUpdate& none, double* out, int64_t ld, const LuSlabs& slabs,
                           hipStream_t s);
 
 // ---- Forrest-Tomlin engine (relp_kernels_ft.hip) ---------------------------------------------------------------

@@ -94,7 +94,7 @@ __global__ __launch_bounds__(kLuThreads) void k_lu_btran(DeviceLU lu, DeferredUp
 }
 
 // All m rows of B^-1 at once (re-inversion, warm start): workgroup i solves e_i' B^-1 and writes row i of `out`.
-// x lives in each workgroup's LDS (the launcher falls back to one launch per row otherwise).
+// x lives in each workgroup's LDS (k_lu_btran_rows_slab otherwise).
 template <bool kStage1, bool kStage2>
 __global__ __launch_bounds__(kLuThreads) void k_lu_btran_rows(DeviceLU lu, DeferredUpdate none, double* __restrict__ out,
                                                                 int64_t ld) {
@@ -164,8 +164,23 @@ void launch_lu_ftran(const DeviceLU& lu, const double* aq, double* v, double* sc
     hipLaunchKernelGGL(fn, dim3(1), dim3(kLuThreads), p.bytes, s, lu, aq, v, scratch, rec);
 }
 
-// Re-tabulation of the dense tableau: workgroup c solves B^-1 a_c for stored column c (artificial unit column,
-// structural column of A + its bound row, virtual unit column -- the same definition as k_tab_build) and writes
+// Entry i of stored column c of the dense tableau in row space: artificial unit column, structural column of A + its
+// bound row, virtual unit column -- the same definition as k_tab_build.
+__device__ __forceinline__ double stored_column_entry(const ColumnTable& ct, const double* __restrict__ A, int64_t ld_a,
+                                                      int c, int i) {
+    if (c < ct.nr_artificial) return (i == ct.column_to_row[c]) ? 1.0 : 0.0;
+    const int p = c - ct.nr_artificial;
+    if (p < ct.nr_normal) {
+        if (i < ct.nr_constraints) return A[(int64_t)p * ld_a + i];
+        return (i == ct.bound_row[p]) ? 1.0 : 0.0;
+    }
+    const int vv = p - ct.nr_normal;
+    if (i == ct.vrow0[vv]) return (double)ct.vsign[vv];
+    if (i == ct.vrow1[vv]) return 1.0;
+    return 0.0;
+}
+
+// Re-tabulation of the dense tableau: workgroup c solves B^-1 a_c for stored column c (stored_column_entry) and writes
 // column c of T0.  x lives in LDS.
 template <bool kStage1, bool kStage2>
 __global__ __launch_bounds__(kLuThreads) void k_lu_ftran_cols(DeviceLU lu, TableauView tv, const double* __restrict__ A,
@@ -174,24 +189,7 @@ __global__ __launch_bounds__(kLuThreads) void k_lu_ftran_cols(DeviceLU lu, Table
     double* x = reinterpret_cast<double*>(lds);
     char* base = lds + lu_up16((int64_t)lu.m * 8);
     const int c = c_first + blockIdx.x;
-    for (int k = threadIdx.x; k < lu.m; k += blockDim.x) {
-        const int i = lu.rowperm[k];
-        double v = 0.0;
-        if (c < ct.nr_artificial) {
-            v = (i == ct.column_to_row[c]) ? 1.0 : 0.0;
-        } else {
-            const int p = c - ct.nr_artificial;
-            if (p < ct.nr_normal) {
-                if (i < ct.nr_constraints) v = A[(int64_t)p * ld_a + i];
-                else v = (i == ct.bound_row[p]) ? 1.0 : 0.0;
-            } else {
-                const int vv = p - ct.nr_normal;
-                if (i == ct.vrow0[vv]) v = (double)ct.vsign[vv];
-                else if (i == ct.vrow1[vv]) v = 1.0;
-            }
-        }
-        x[k] = v;
-    }
+    for (int k = threadIdx.x; k < lu.m; k += blockDim.x) x[k] = stored_column_entry(ct, A, ld_a, c, lu.rowperm[k]);
     __syncthreads();
     solve_schedule<kStage1>(lu.Lf, lu.m, base, x);
     solve_schedule<kStage2>(lu.Uf, lu.m, base, x);
@@ -199,26 +197,93 @@ __global__ __launch_bounds__(kLuThreads) void k_lu_ftran_cols(DeviceLU lu, Table
     for (int k = threadIdx.x; k < lu.m; k += blockDim.x) out[lu.colperm[k]] = x[k];
 }
 
-// returns false when x does not fit into LDS (the caller then leaves the tableau as it is)
-bool launch_lu_ftran_cols(const DeviceLU& lu, const TableauView& tv, const double* A, int64_t ld_a, const ColumnTable& ct,
-                          int32_t c_first, int32_t c_count, hipStream_t s) {
+// ---- the two batch solves with x in global memory (m beyond the LDS-resident work vector) ----------------------------
+// gridDim.x workgroups, each with a private slab of `ld` doubles in `slabs`; workgroup g walks the right-hand sides
+// first + g, first + g + gridDim.x, ...  The arithmetic is solve_levels' in its order, as on the LDS path: the results are
+// the same bit for bit.  kStage: both schedules fit into LDS together and are copied there once per workgroup
+// (dynamic LDS: [first schedule][second schedule]); otherwise they are read from global memory.
+// Per trip: every entry of the slab is written by the initialisation (nothing of the previous right-hand side is ever
+// read), and a barrier separates reading the slab out from re-initialising it.
+template <bool kStage>
+__device__ __forceinline__ void slab_schedules(const DeviceSchedule& a, const DeviceSchedule& b, int m, ScheduleView* va,
+                                               ScheduleView* vb) {
+    extern __shared__ __align__(16) char lds[];
+    *va = kStage ? stage_schedule(a, m, lds) : schedule_view(a);
+    *vb = kStage ? stage_schedule(b, m, lds + schedule_lds_bytes(m, a.nnz, a.n_levels)) : schedule_view(b);
+}
+
+template <bool kStage>
+__global__ __launch_bounds__(kLuThreads) void k_lu_ftran_cols_slab(DeviceLU lu, TableauView tv, const double* __restrict__ A,
+                                                                     int64_t ld_a, ColumnTable ct, int c_first, int c_count,
+                                                                     double* slabs, int64_t ld) {
+    double* x = slabs + (int64_t)blockIdx.x * ld;
+    ScheduleView lower, upper;
+    slab_schedules<kStage>(lu.Lf, lu.Uf, lu.m, &lower, &upper);
+    for (int c = c_first + blockIdx.x; c < c_first + c_count; c += gridDim.x) {
+        for (int k = threadIdx.x; k < lu.m; k += blockDim.x) x[k] = stored_column_entry(ct, A, ld_a, c, lu.rowperm[k]);
+        __syncthreads();
+        solve_levels(lower, x);
+        solve_levels(upper, x);
+        double* out = tv.T0 + (int64_t)c * tv.ld_t;
+        for (int k = threadIdx.x; k < lu.m; k += blockDim.x) out[lu.colperm[k]] = x[k];
+        __syncthreads();
+    }
+}
+
+template <bool kStage>
+__global__ __launch_bounds__(kLuThreads) void k_lu_btran_rows_slab(DeviceLU lu, double* __restrict__ out, int64_t ld_out,
+                                                                     double* slabs, int64_t ld) {
+    double* x = slabs + (int64_t)blockIdx.x * ld;
+    ScheduleView upper, lower;
+    slab_schedules<kStage>(lu.Ub, lu.Lb, lu.m, &upper, &lower);
+    for (int i = blockIdx.x; i < lu.m; i += gridDim.x) {
+        for (int k = threadIdx.x; k < lu.m; k += blockDim.x) x[k] = (lu.colperm[k] == i) ? 1.0 : 0.0;
+        __syncthreads();
+        solve_levels(upper, x);
+        solve_levels(lower, x);
+        double* rho = out + (int64_t)i * ld_out;
+        for (int k = threadIdx.x; k < lu.m; k += blockDim.x) rho[lu.rowperm[k]] = x[k];
+        __syncthreads();
+    }
+}
+
+bool lu_batch_fits_lds(int32_t m) { return lu_up16((int64_t)m * 8) <= kLuLdsBytes / 2; }
+
+// dynamic LDS of the slab kernels: both schedules when they fit together, else none
+static size_t slab_stage_bytes(int m, const DeviceSchedule& a, const DeviceSchedule& b) {
+    const int64_t n = schedule_lds_bytes(m, a.nnz, a.n_levels) + schedule_lds_bytes(m, b.nnz, b.n_levels);
+    return n <= kLuLdsBytes ? (size_t)n : 0;
+}
+
+void launch_lu_ftran_cols(const DeviceLU& lu, const TableauView& tv, const double* A, int64_t ld_a, const ColumnTable& ct,
+                          int32_t c_first, int32_t c_count, const LuSlabs& slabs, hipStream_t s) {
+    if (c_count <= 0) return;
+    if (slabs.groups > 0) {
+        const size_t bytes = slab_stage_bytes(lu.m, lu.Lf, lu.Uf);
+        auto fn = bytes ? k_lu_ftran_cols_slab<true> : k_lu_ftran_cols_slab<false>;
+        allow_big_lds(reinterpret_cast<const void*>(fn));
+        hipLaunchKernelGGL(fn, dim3(std::min(slabs.groups, c_count)), dim3(kLuThreads), bytes, s, lu, tv, A, ld_a, ct, c_first,
+                           c_count, slabs.x, slabs.ld);
+        return;
+    }
     const LuLdsPlan p = plan_lu_lds(lu.m, lu.Lf, lu.Uf);
-    if (!p.x_in_lds) return false;
-    if (c_count <= 0) return true;
     auto fn = p.stage_first ? (p.stage_second ? k_lu_ftran_cols<true, true> : k_lu_ftran_cols<true, false>)
                             : (p.stage_second ? k_lu_ftran_cols<false, true> : k_lu_ftran_cols<false, false>);
     allow_big_lds(reinterpret_cast<const void*>(fn));
     hipLaunchKernelGGL(fn, dim3(c_count), dim3(kLuThreads), p.bytes, s, lu, tv, A, ld_a, ct, c_first);
-    return true;
 }
 
-void launch_lu_btran_rows(const DeviceLU& lu, const DeferredUpdate& none, double* out, int64_t ld, double* scratch,
+void launch_lu_btran_rows(const DeviceLU& lu, const DeferredUpdate& none, double* out, int64_t ld, const LuSlabs& slabs,
                           hipStream_t s) {
-    const LuLdsPlan p = plan_lu_lds(lu.m, lu.Ub, lu.Lb);
-    if (!p.x_in_lds) {                                   // x in global scratch: one solve at a time
-        for (int32_t i = 0; i < lu.m; ++i) launch_lu_btran(lu, none, nullptr, i, out + (int64_t)i * ld, scratch, nullptr, s);
+    if (lu.m <= 0) return;
+    if (slabs.groups > 0) {
+        const size_t bytes = slab_stage_bytes(lu.m, lu.Ub, lu.Lb);
+        auto fn = bytes ? k_lu_btran_rows_slab<true> : k_lu_btran_rows_slab<false>;
+        allow_big_lds(reinterpret_cast<const void*>(fn));
+        hipLaunchKernelGGL(fn, dim3(std::min(slabs.groups, lu.m)), dim3(kLuThreads), bytes, s, lu, out, ld, slabs.x, slabs.ld);
         return;
     }
+    const LuLdsPlan p = plan_lu_lds(lu.m, lu.Ub, lu.Lb);
     auto fn = p.stage_first ? (p.stage_second ? k_lu_btran_rows<true, true> : k_lu_btran_rows<true, false>)
                             : (p.stage_second ? k_lu_btran_rows<false, true> : k_lu_btran_rows<false, false>);
     allow_big_lds(reinterpret_cast<const void*>(fn));

@@ -70,23 +70,30 @@ __device__ __forceinline__ int group_shift(int rows) {
     return rows <= NT / 64 ? 6 : rows <= NT / 32 ? 5 : rows <= NT / 16 ? 4 : 3;
 }
 
-// kStage: copy the schedule into LDS at `base` and solve from there; otherwise solve from global memory.
-// NT = threads of the workgroup.
-template <bool kStage, int NT = kLuThreads>
-__device__ __forceinline__ void solve_schedule(const DeviceSchedule& s, int m, char* base, double* x) {
-    const LuRow* rows = s.rows; const int32_t* idx = s.idx; const double* val = s.val; const int32_t* level_ptr = s.level_ptr;
-    if (kStage) {
-        LuRow* l_rows = reinterpret_cast<LuRow*>(base); base += lu_up16((int64_t)sizeof(LuRow) * m);
-        double* l_val = reinterpret_cast<double*>(base); base += lu_up16(8 * (int64_t)s.nnz);
-        int32_t* l_idx = reinterpret_cast<int32_t*>(base); base += lu_up16(4 * (int64_t)s.nnz);
-        int32_t* l_lp = reinterpret_cast<int32_t*>(base);
-        for (int e = threadIdx.x; e < s.nnz; e += blockDim.x) { l_val[e] = s.val[e]; l_idx[e] = s.idx[e]; }
-        for (int k = threadIdx.x; k < m; k += blockDim.x) l_rows[k] = s.rows[k];
-        for (int k = threadIdx.x; k <= s.n_levels; k += blockDim.x) l_lp[k] = s.level_ptr[k];
-        __syncthreads();
-        rows = l_rows; idx = l_idx; val = l_val; level_ptr = l_lp;
-    }
-    const int n_levels = s.n_levels;
+// The arrays a solve reads: the schedule's own in global memory, or its copy in LDS.
+struct ScheduleView { const LuRow* rows; const int32_t* idx; const double* val; const int32_t* level_ptr; int n_levels; };
+__device__ __forceinline__ ScheduleView schedule_view(const DeviceSchedule& s) {
+    return ScheduleView{s.rows, s.idx, s.val, s.level_ptr, s.n_levels};
+}
+// Copy the schedule into LDS at `base` (schedule_lds_bytes(m, s.nnz, s.n_levels) bytes) and wait for the copy.
+__device__ __forceinline__ ScheduleView stage_schedule(const DeviceSchedule& s, int m, char* base) {
+    LuRow* l_rows = reinterpret_cast<LuRow*>(base); base += lu_up16((int64_t)sizeof(LuRow) * m);
+    double* l_val = reinterpret_cast<double*>(base); base += lu_up16(8 * (int64_t)s.nnz);
+    int32_t* l_idx = reinterpret_cast<int32_t*>(base); base += lu_up16(4 * (int64_t)s.nnz);
+    int32_t* l_lp = reinterpret_cast<int32_t*>(base);
+    for (int e = threadIdx.x; e < s.nnz; e += blockDim.x) { l_val[e] = s.val[e]; l_idx[e] = s.idx[e]; }
+    for (int k = threadIdx.x; k < m; k += blockDim.x) l_rows[k] = s.rows[k];
+    for (int k = threadIdx.x; k <= s.n_levels; k += blockDim.x) l_lp[k] = s.level_ptr[k];
+    __syncthreads();
+    return ScheduleView{l_rows, l_idx, l_val, l_lp, s.n_levels};
+}
+
+// The level-by-level solve: x in LDS or in global memory (the barrier after every level orders both).  NT = threads of
+// the workgroup.
+template <int NT = kLuThreads>
+__device__ __forceinline__ void solve_levels(const ScheduleView& v, double* x) {
+    const LuRow* rows = v.rows; const int32_t* idx = v.idx; const double* val = v.val; const int32_t* level_ptr = v.level_ptr;
+    const int n_levels = v.n_levels;
     const int tid = threadIdx.x;
     // prefetched first row of the level about to be solved
     int t0 = level_ptr[0], t1 = level_ptr[1];
@@ -128,6 +135,12 @@ __device__ __forceinline__ void solve_schedule(const DeviceSchedule& s, int m, c
         }
         __syncthreads();
     }
+}
+
+// kStage: copy the schedule into LDS at `base` and solve from there; otherwise solve from global memory.
+template <bool kStage, int NT = kLuThreads>
+__device__ __forceinline__ void solve_schedule(const DeviceSchedule& s, int m, char* base, double* x) {
+    solve_levels<NT>(kStage ? stage_schedule(s, m, base) : schedule_view(s), x);
 }
 
 // ---- the solve as a software pipeline over segments of levels (the persistent pivot kernel) -----------------------------

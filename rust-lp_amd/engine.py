@@ -94,6 +94,7 @@ _SIGNATURES = {
     "relp_update_block": (C.c_int32, [C.c_void_p]),
     "relp_tab_load_batch": (C.c_int32, [C.c_void_p]),
     "relp_tab_flush_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "relp_retab_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "relp_lu_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "relp_lu_lookahead_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "relp_lu_kernel_layout": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
@@ -332,7 +333,9 @@ class Tableau:
         return v.value
 
     def set_reinversion_interval(self, pivots: int) -> None:
-        """Revised engine: rebuild B^-1, b, -pi from the basis columns every `pivots` basis changes (0 = never)."""
+        """Revised and tableau engines (unsharded), any number of rows: rebuild B^-1 (revised) or the tableau B^-1 [A | I]
+        (tableau), b, -pi / the reduced costs and the objective from the columns of the current basis every `pivots` basis
+        changes (0 = never)."""
         self._ck(self._lib.relp_set_reinversion_interval(self._h, int(pivots)))
 
     def reinversions(self) -> int:
@@ -385,6 +388,13 @@ class Tableau:
         out = (C.c_int64 * 2)()
         self._ck(self._lib.relp_tab_flush_stats(self._h, out))
         return int(out[0]), int(out[1])
+
+    def retab_stats(self) -> Tuple[int, int, int, int]:
+        """Revised and tableau engines: (batch solves of the rebuilds with the work vector in LDS, batch solves with it in
+        global slabs, workgroups of the last launch of the second kind, bytes of the slab buffer); relp_retab_stats."""
+        out = (C.c_int64 * 4)()
+        self._ck(self._lib.relp_retab_stats(self._h, out))
+        return tuple(int(v) for v in out)
 
     def engine_kind(self) -> int:
         """The engine in use (RELP_ENGINE_AUTO resolved at create)."""
