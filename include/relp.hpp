@@ -327,6 +327,31 @@ class Tableau {
             default: throw Error(RELP_E_STATE, "iteration limit reached");
         }
     }
+    // ---- dual simplex (no counterpart in the reference: its primal_dual module is empty) ------------------------------
+    // tableau engine, phase 2, from a dual feasible basis: RELP_OPTIMAL, RELP_INFEASIBLE or RELP_RUNNING at the limit
+    relp_outcome_t run_dual(int64_t max_iters = std::numeric_limits<int64_t>::max(), int64_t* done = nullptr) {
+        int32_t oc = 0; int64_t n = 0;
+        ck(relp_run_dual(h_, max_iters, &n, &oc));
+        if (done) *done = n;
+        return (relp_outcome_t)oc;
+    }
+    // the leaving row (the most negative b_i), None when no row is infeasible
+    std::optional<int32_t> select_dual_pivot_row() {
+        int32_t found = 0, row = -1;
+        ck(relp_select_dual_pivot_row(h_, &found, &row));
+        return found ? std::optional<int32_t>(row) : std::nullopt;
+    }
+    // the entering column of tableau row `row`, None when the row has no candidate
+    std::optional<int32_t> select_dual_pivot_column(int32_t row) {
+        int32_t found = 0, column = -1;
+        ck(relp_select_dual_pivot_column(h_, row, &found, &column));
+        return found ? std::optional<int32_t>(column) : std::nullopt;
+    }
+    // a new right-hand side (engine row order, any sign) for the current basis; run_dual re-solves from there
+    void set_right_hand_side(const std::vector<double>& rhs) {
+        if ((int32_t)rhs.size() != nr_rows()) throw Error(RELP_E_ARG, "one right-hand side per row");
+        ck(relp_set_right_hand_side(h_, rhs.data()));
+    }
     // ---- one LP on several GPUs (no counterpart in the reference, which is single-threaded) ---------------------
     // Options::shard(rank, count) at construction, the owned structural columns in `MatrixData` (relp_shard_plan);
     // rank 0 makes the RCCL id, the host program hands it to every rank, every rank attaches, then the loop runs

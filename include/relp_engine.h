@@ -213,6 +213,39 @@ relp_status_t relp_run(relp_engine_t *h, int64_t max_iters, int64_t *iterations_
 /* SolveRelaxation::solve_relaxation (two_phase/mod.rs:30-76): phase 1, artificial removal
  * (phase_one.rs:223-260), phase switch (kind/non_artificial.rs:151-220), phase 2. */
 relp_status_t relp_solve_relaxation(relp_engine_t *h, int64_t max_iters, int32_t *outcome);
+/* ---- dual simplex (RELP_ENGINE_TABLEAU, unsharded, phase 2) --------------------------------------------------------
+ * No counterpart in the reference: its `primal_dual` and `criss_cross` modules are empty placeholders.  Like the f64 field this
+ * is the build's extension, for the bases the primal loops cannot use: reduced costs d >= 0 but b = B^-1 rhs with negative
+ * entries -- the all-surplus basis of a covering LP (min c'x, A x >= b, c > 0) after relp_from_basis, or an optimal basis
+ * after relp_set_right_hand_side.  Rules, with the absolute tolerances of relp_config_t:
+ *   leaving row      row i is infeasible iff b_i < -tol_feas; the minimum b_i over the infeasible rows; among the infeasible
+ *                    rows with b_i <= min + tol_tie*max(1,|min|) the smallest leaving column wins (the tie order of the primal
+ *                    ratio test); no infeasible row: the basis is optimal
+ *   entering column  over tableau row r, the non-basic columns j (a column barred by the pivot rescue is not one) with
+ *                    T[r,j] < -tol_pivot; ratio dz_j / (-T[r,j]) with dz_j = 0 when d_j <= tol_zero, else d_j; the minimum
+ *                    ratio; among ratios <= min + tol_tie*max(1,|min|) the lowest j wins; no candidate: the LP is infeasible
+ *   pivot            on T[r,q] < 0, by the update of the primal loop
+ * relp_config_t.ratio_rule and pivot_rescue are IGNORED by the dual loop (no largest-pivot tie-break, no rescue of a small
+ * pivot); update_block and the flush schedule, relp_set_reinversion_interval, auto_reinversion, trace_capacity (phase field 2)
+ * and poll_interval are honoured exactly as by relp_run.
+ * relp_run_dual: up to max_iters dual pivots with no per-pivot host sync.  *outcome: RELP_OPTIMAL, RELP_INFEASIBLE, or
+ * RELP_RUNNING at the iteration limit.  RELP_E_UNSUPPORTED on another engine or a sharded one; RELP_E_STATE in phase 1, and when
+ * the basis is not dual feasible (a non-basic column with d_j < -tol_cost: relp_last_error names it) -- the handle stays usable,
+ * and relp_run may follow on it in every case. */
+relp_status_t relp_run_dual(relp_engine_t *h, int64_t max_iters, int64_t *iterations_done, int32_t *outcome);
+/* The two selections of one dual pivot, step by step like relp_select_primal_pivot_row (no counterpart in the reference): the
+ * leaving row by the rule above (*found = 0: no row is infeasible), and the entering column for tableau row `row` (*found = 0:
+ * no candidate).  One pivot is then relp_select_dual_pivot_row, relp_select_dual_pivot_column, relp_generate_column(column),
+ * relp_bring_into_basis(column, row, d_column). */
+relp_status_t relp_select_dual_pivot_row(relp_engine_t *h, int32_t *found, int32_t *row);
+relp_status_t relp_select_dual_pivot_column(relp_engine_t *h, int32_t row, int32_t *found, int32_t *column);
+/* A new right-hand side for the current basis (no counterpart in the reference, which borrows an immutable provider):
+ * `rhs_m` has relp_nr_rows entries in the engine's current row order (b, upper bounds, ranges), of any sign.  The tableau is
+ * re-tabulated on the current basis -- b = B^-1 rhs, the reduced costs, -obj -- at the cost of relp_from_basis.  The reduced
+ * costs do not depend on rhs: an optimal basis stays dual feasible, and relp_run_dual re-solves from it.  The rebuild counts in
+ * relp_reinversions but does not adapt the auto_reinversion interval (b moved with rhs, not by drift).  RELP_ENGINE_TABLEAU,
+ * unsharded, phase 2. */
+relp_status_t relp_set_right_hand_side(relp_engine_t *h, const double *rhs_m);
 /* InverseMaintener::from_basis (carry/mod.rs:428-463): warm start from provider column indices,
  * one per row; switches to phase 2.  RELP_ENGINE_LU: any basis (factorise, b = FTRAN(rhs), -pi = BTRAN(-c_B));
  * RELP_ENGINE_REVISED: any basis (basis_inverse_rows.rs:103-129: LU - factorised on the host like every

@@ -72,6 +72,18 @@ relp_status_t relp_bring_into_basis(relp_engine_t* h, int32_t column, int32_t ro
 relp_status_t relp_run(relp_engine_t* h, int64_t max_iters, int64_t* done, int32_t* outcome) {
     return h ? H(h).run(max_iters, done, outcome) : RELP_E_ARG;
 }
+relp_status_t relp_run_dual(relp_engine_t* h, int64_t max_iters, int64_t* done, int32_t* outcome) {
+    return h ? H(h).run_dual(max_iters, done, outcome) : RELP_E_ARG;
+}
+relp_status_t relp_select_dual_pivot_row(relp_engine_t* h, int32_t* found, int32_t* row) {
+    return h ? H(h).select_dual_pivot_row(found, row) : RELP_E_ARG;
+}
+relp_status_t relp_select_dual_pivot_column(relp_engine_t* h, int32_t row, int32_t* found, int32_t* column) {
+    return h ? H(h).select_dual_pivot_column(row, found, column) : RELP_E_ARG;
+}
+relp_status_t relp_set_right_hand_side(relp_engine_t* h, const double* rhs_m) {
+    return (h && rhs_m) ? H(h).set_right_hand_side(rhs_m) : RELP_E_ARG;
+}
 relp_status_t relp_solve_relaxation(relp_engine_t* h, int64_t max_iters, int32_t* outcome) {
     return h ? H(h).solve_relaxation(max_iters, outcome) : RELP_E_ARG;
 }

@@ -919,6 +919,144 @@ relp_status_t Engine::solve_relaxation(int64_t max_iters, int32_t* outcome) {
     return RELP_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Dual simplex on the tableau (the reference's primal_dual module is an empty placeholder): from a basis whose reduced costs
+// are non-negative, pivot until b = B^-1 rhs is.  Selection by the dual kernels (relp_kernels.h), the pivot itself by the
+// update of the primal loop; ratio_rule and pivot_rescue do not apply.
+// ------------------------------------------------------------------------------------------------
+relp_status_t Engine::dual_ready(const char* what) {
+    if (!tableau_ || cfg_.shard_count > 1) return fail(RELP_E_UNSUPPORTED, std::string(what) + " is for the unsharded tableau engine");
+    if (phase_ != 2) return fail(RELP_E_STATE, std::string(what) + " needs a phase-2 tableau (relp_from_basis, or phase 1 done)");
+    return RELP_OK;
+}
+
+// One dual pivot: 5 launches.  [block minima of the infeasible b_i] -> [row r of T + partial minima of the dual ratios] ->
+// [entering column + tableau column] -> [alpha_r, b_r, block bookkeeping] -> [the update of the primal loop]
+void Engine::enqueue_iteration_dual() {
+    struct Tick { int64_t& t; ~Tick() { ++t; } } tick{prof_tick_};
+    const TableauView tv = tview();
+    const DeferredUpdate du = deferred();
+    const SelectPartials sp = tab_partials(current_rule());
+    const Tolerances tol = tolerances();
+    // relp_profile_read has the primal loop's classes only: RATIO = block minima + commit (the row choice), PRICE = row r of T +
+    // the update (as in the primal loop, whose update carries the next PRICE), FTRAN = entering column + tableau column
+    prof_begin(RELP_K_RATIO);
+    launch_dual_bmin(d_b_, lay_.m, cfg_.tol_feas, d_rmin_, d_rec_, stream_);
+    prof_end();
+    prof_begin(RELP_K_PRICE);
+    launch_dual_row(tv, du, sp, d_b_, d_basis_, tol, cfg_.tol_feas, d_rmin_, -1, d_aq_big(), d_rec_, stream_);
+    prof_end();
+    prof_begin(RELP_K_FTRAN);
+    launch_dual_select_column(tv, du, sp, d_b_, d_basis_, tol, cfg_.tol_feas, d_rmin_, -1, d_aq_big(), d_alpha_, d_rec_, stream_);
+    prof_end();
+    prof_begin(RELP_K_RATIO);
+    launch_dual_commit(d_alpha_, d_b_, du, d_rec_, stream_);
+    prof_end();
+    prof_begin(RELP_K_PRICE);
+    launch_tab_update_all(tv, du, sp, lay_.m, d_alpha_, d_b_, d_basis_, d_in_basis_, d_trace_, trace_cap_, d_rec_, stream_);
+    prof_end();
+    if (++since_flush_ >= block_) enqueue_flush();
+}
+
+relp_status_t Engine::run_dual(int64_t max_iters, int64_t* done, int32_t* outcome) {
+    relp_status_t st = dual_ready("relp_run_dual");
+    if (st) return st;
+    tab_settle();
+    if ((st = edit_rec())) return st;
+    const long long start = h_rec_->iterations;
+    {   // dual feasibility: PRICE finds no candidate among the non-basic columns
+        const SelectPartials sp = tab_partials(RELP_RULE_STEEPEST_DESCENT);
+        launch_tab_scan(tview(), sp, d_rec_, stream_);
+        launch_tab_select(tview(), sp, tab_scan_blocks(lay_.sc_hi - lay_.sc_lo), d_rec_, stream_);
+        if ((st = download_rec())) return st;
+        const bool dual_feasible = h_rec_->outcome == DEV_NO_CANDIDATE;
+        const int32_t q = h_rec_->q;
+        const double d_q = h_rec_->d_q;
+        h_rec_->outcome = DEV_RUNNING;
+        if ((st = upload_rec())) return st;
+        if (!dual_feasible) {
+            char msg[160];
+            std::snprintf(msg, sizeof msg, "relp_run_dual: the basis is not dual feasible (column %d has reduced cost %.3e)", (int)q, d_q);
+            return fail(RELP_E_STATE, msg);
+        }
+    }
+    tab_partials_valid_ = false;
+    int64_t next_poll = cfg_.poll_interval;
+    {
+    LoopScope loop(*this);
+    for (int64_t it = 0; it < max_iters && h_rec_->outcome == DEV_RUNNING; ++it) {
+        enqueue_iteration_dual();
+        if (reinvert_interval_ > 0 && ++since_reinvert_ >= reinvert_interval_) {
+            if ((st = download_rec())) return st;
+            if (h_rec_->outcome != DEV_RUNNING) break;
+            if ((st = reinvert())) return st;
+        }
+        if (it + 1 == next_poll) {
+            next_poll += cfg_.poll_interval;
+            if ((st = download_rec())) return st;
+            if (h_rec_->outcome != DEV_RUNNING) break;
+        }
+    }
+    }
+    if ((st = download_rec())) return st;
+    if (hipGetLastError() != hipSuccess) return fail(RELP_E_HIP, "kernel launch failed");
+    int32_t oc = RELP_RUNNING;
+    if (h_rec_->outcome == DEV_NO_ROW) oc = RELP_OPTIMAL;                  // no infeasible row left
+    else if (h_rec_->outcome == DEV_NO_CANDIDATE) oc = RELP_INFEASIBLE;    // an infeasible row without an entry to pivot on
+    if (done) *done = h_rec_->iterations - start;
+    if (outcome) *outcome = oc;
+    h_rec_->outcome = DEV_RUNNING;                                          // (a primal loop may follow on this handle)
+    return upload_rec();
+}
+
+relp_status_t Engine::select_dual_pivot_row(int32_t* found, int32_t* row) {
+    relp_status_t st = dual_ready("relp_select_dual_pivot_row");
+    if (st) return st;
+    if ((st = edit_rec())) return st;
+    launch_dual_bmin(d_b_, lay_.m, cfg_.tol_feas, d_rmin_, d_rec_, stream_);
+    launch_dual_select_row(d_b_, d_basis_, lay_.m, cfg_.tol_feas, cfg_.tol_tie, d_rmin_, d_rec_, stream_);
+    return read_pivot_row(found, row);
+}
+
+relp_status_t Engine::select_dual_pivot_column(int32_t row, int32_t* found, int32_t* column) {
+    relp_status_t st = dual_ready("relp_select_dual_pivot_column");
+    if (st) return st;
+    if (row < 0 || row >= lay_.m) return fail(RELP_E_ARG, "row out of range");
+    if ((st = edit_rec())) return st;
+    const TableauView tv = tview();
+    const DeferredUpdate du = deferred();
+    const SelectPartials sp = tab_partials(current_rule());
+    launch_dual_row(tv, du, sp, d_b_, d_basis_, tolerances(), cfg_.tol_feas, d_rmin_, row, d_aq_big(), d_rec_, stream_);
+    launch_dual_select_column(tv, du, sp, d_b_, d_basis_, tolerances(), cfg_.tol_feas, d_rmin_, row, d_aq_big(), d_alpha_, d_rec_,
+                              stream_);
+    tab_partials_valid_ = false;                       // (the partial slots now hold dual ratios)
+    if ((st = download_rec())) return st;
+    const bool ok = h_rec_->outcome == DEV_RUNNING;
+    if (found) *found = ok ? 1 : 0;
+    if (ok && column) *column = h_rec_->q;
+    h_rec_->outcome = DEV_RUNNING;
+    return upload_rec();
+}
+
+// A new right-hand side for the current basis: b = B^-1 rhs, the reduced costs and -obj by a re-tabulation (the reduced costs
+// do not depend on rhs: a basis that was optimal stays dual feasible, and relp_run_dual takes it from there).
+relp_status_t Engine::set_right_hand_side(const double* rhs_m) {
+    relp_status_t st = dual_ready("relp_set_right_hand_side");
+    if (st) return st;
+    if ((st = edit_rec())) return st;
+    std::vector<double> keep(rhs_m, rhs_m + lay_.m);
+    keep.swap(lay_.rhs);
+    st = retabulate(false);                            // (b moves with rhs: nothing the re-inversion interval should adapt to)
+    if (st || !retab_done_) {
+        // a basis the factorisation declines leaves the old tableau and the old rhs in place; after a HIP error (st) the handle
+        // is not guaranteed consistent, as everywhere else: b on the device may already belong to the new rhs
+        keep.swap(lay_.rhs);
+        return st ? st : fail(RELP_E_SINGULAR, "relp_set_right_hand_side: the basis could not be factorised");
+    }
+    tab_partials_valid_ = false;
+    return RELP_OK;
+}
+
 // phase_one.rs:146-166: objective == 0 -> feasible (remove artificials, switch) else infeasible
 relp_status_t Engine::finish_phase_one(int32_t* outcome) {
     tab_settle();
@@ -1335,7 +1473,7 @@ static double weighted_sum(const std::vector<double>& w, const std::vector<doubl
     return s;
 }
 
-relp_status_t Engine::retabulate() {
+relp_status_t Engine::retabulate(bool adapt_interval) {
     SettledScope settled(*this);
     retab_done_ = false;
     std::vector<double> b_before;
@@ -1363,7 +1501,7 @@ relp_status_t Engine::retabulate() {
     h_rec_->minus_objective = -objective_of(basis, b);
     ++reinversions_;
     retab_done_ = true;
-    if (cfg_.auto_reinversion) auto_reinversion_adapt(b_before, b);
+    if (cfg_.auto_reinversion && adapt_interval) auto_reinversion_adapt(b_before, b);
     return upload_rec();
 }
 

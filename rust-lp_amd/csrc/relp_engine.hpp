@@ -114,6 +114,12 @@ class Engine : private EngineQueue {
 
     // loops
     relp_status_t run(int64_t max_iters, int64_t* done, int32_t* outcome);
+    // dual simplex on the unsharded tableau engine (no counterpart in the reference): the loop, its two step-wise selectors and
+    // a new right-hand side for the current basis
+    relp_status_t run_dual(int64_t max_iters, int64_t* done, int32_t* outcome);
+    relp_status_t select_dual_pivot_row(int32_t* found, int32_t* row);
+    relp_status_t select_dual_pivot_column(int32_t row, int32_t* found, int32_t* column);
+    relp_status_t set_right_hand_side(const double* rhs_m);
     int32_t engine_kind() const { return lay_.engine; }
     relp_status_t robust_stats(int64_t* out4) const;
     relp_status_t solve_relaxation(int64_t max_iters, int32_t* outcome);
@@ -259,6 +265,8 @@ class Engine : private EngineQueue {
     SelectPartials tab_partials(int rule) const;
     SelectPartials lu_partials(int rule) const;
     void enqueue_iteration_tableau(int rule);
+    void enqueue_iteration_dual();
+    relp_status_t dual_ready(const char* what);        // phase 2 on the unsharded tableau engine, or the error
     void tableau_reprice();
     // sparse LU engine (cfg.engine == RELP_ENGINE_LU): B^-1 = (I + W S') (L U)^-1, refactor every block_ pivots
     bool lu_ = false;
@@ -298,7 +306,7 @@ class Engine : private EngineQueue {
     relp_status_t lu_refactor();
     relp_status_t lu_upload_factors();
     relp_status_t reinvert();
-    relp_status_t retabulate();
+    relp_status_t retabulate(bool adapt_interval = true);   // false: b moves because rhs did (relp_set_right_hand_side), not by drift
     bool retab_done_ = false;                             // the last retabulate() rebuilt the tableau (it keeps the old one otherwise)
     relp_status_t build_basis_columns(const std::vector<int32_t>& basis, std::vector<std::vector<std::pair<int32_t, double>>>* cols);
     void enqueue_iteration_lu(int rule);

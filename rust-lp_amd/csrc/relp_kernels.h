@@ -468,6 +468,26 @@ void launch_tab_gather_columns(const TableauView& tv, const int32_t* cols, doubl
 // tableau row `row` of the CURRENT T into out[0..n_store) (remove_artificial_basis_variables)
 void launch_tab_row(const TableauView& tv, const DeferredUpdate& du, int32_t row, double* out, const PivotRecord* rec,
                     hipStream_t s);
+// Dual simplex on the tableau (relp_run_dual; the reference has no dual loop).  One pivot: launch_dual_bmin, launch_dual_row,
+// launch_dual_select_column, launch_dual_commit, launch_tab_update_all -- the update takes the pivot from the record and does
+// not care that alpha_r and b_r are negative.  `tol`: pivot, zero and tie are read (ratio_rule and the pivot guard are not).
+// bmin[k] = the minimum b_i over the rows of block k (256 rows) with b_i < -tol_feas, +inf when there is none
+void launch_dual_bmin(const double* b, int32_t m, double tol_feas, double* bmin, const PivotRecord* rec, hipStream_t s);
+// step-wise call: the leaving row from the block minima into the record (DEV_NO_ROW: no row is infeasible)
+void launch_dual_select_row(const double* b, const int32_t* basis_indices, int32_t m, double tol_feas, double tol_tie,
+                            const double* bmin, PivotRecord* rec, hipStream_t s);
+// row r of T over the owned stored columns into `row` (indexed from tv.c_lo) and the partial (ratio, column) minima of the dual
+// ratio test, one slot per 256 columns; r = forced_row, or the leaving row picked from bmin (forced_row < 0)
+void launch_dual_row(const TableauView& tv, const DeferredUpdate& du, SelectPartials sp, const double* b,
+                     const int32_t* basis_indices, Tolerances tol, double tol_feas, const double* bmin, int32_t forced_row,
+                     double* row, const PivotRecord* rec, hipStream_t s);
+// q from those partials, (q, d_q, r, leaving) into the record and alpha = T[:,q]; DEV_NO_ROW: the basis is optimal,
+// DEV_NO_CANDIDATE: row r has no entry to pivot on (the LP is infeasible)
+void launch_dual_select_column(const TableauView& tv, const DeferredUpdate& du, SelectPartials sp, const double* b,
+                               const int32_t* basis_indices, Tolerances tol, double tol_feas, const double* bmin,
+                               int32_t forced_row, const double* row, double* alpha, PivotRecord* rec, hipStream_t s);
+// alpha_r, b_r and the block bookkeeping of the deferred update for the (r, leaving) of the record: ratio_commit_row, no guard
+void launch_dual_commit(const double* alpha, const double* b, const DeferredUpdate& du, PivotRecord* rec, hipStream_t s);
 
 // ---- sparse LU engine ------------------------------------------------------------------------------
 // PRICE over CSC columns (thread per column), partial argmin per 256 columns

@@ -818,6 +818,248 @@ __global__ __launch_bounds__(kThreads) void k_tab_zero_level_scan(TableauView tv
     block_partial_min(key, kj, sp, blockIdx.x);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Dual simplex on the tableau (relp_run_dual; no counterpart in the reference, whose primal_dual module is empty).  The
+// selection is new, the pivot itself is k_tab_update_all:
+//   leaving row      the minimum b_i over the infeasible rows (b_i < -tol_feas), ties to the smallest leaving column
+//   entering column  over row r of T: the minimum d_j / (-T[r,j]) over the non-basic columns with T[r,j] < -tol_pivot, ties to
+//                    the lowest column
+// ------------------------------------------------------------------------------------------------
+// The minimum b_i over the infeasible rows of every block of 256 rows (+inf: the block has none).
+__global__ __launch_bounds__(kThreads) void k_dual_bmin(const double* __restrict__ b, int m, double tol_feas,
+                                                        double* __restrict__ bmin, const PivotRecord* rec) {
+    if (rec->outcome != DEV_RUNNING) return;
+    __shared__ double s_min[kThreads / 64];
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    double v = INFINITY;
+    if (i < m) {
+        const double bi = b[i];
+        if (bi < -tol_feas) v = bi;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_down(v, off, 64));
+    if ((threadIdx.x & 63) == 0) s_min[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) bmin[blockIdx.x] = fmin(fmin(s_min[0], s_min[1]), fmin(s_min[2], s_min[3]));
+}
+
+// The leaving row from the block minima, by a workgroup of BS threads, the way ratio_blocks_pick picks from rmin: the minimum
+// of the minima, then only the blocks whose own minimum is inside the tie band are read again; Bland on the leaving column
+// among their infeasible rows inside the band.  Every thread returns with (row, leaving column), row = -1 when no row is
+// infeasible; nothing is written.
+template <int BS>
+__device__ __forceinline__ void dual_row_pick(const double* b, const int32_t* basis_indices, int m, double tol_feas, double tol_tie,
+                                              const double* bmin, int nblk, int* row_out, int* leave_out) {
+    __shared__ double s_min[BS / 64];
+    __shared__ double s_bcast;
+    constexpr int kListMax = 64;
+    __shared__ int s_list[kListMax];
+    __shared__ int s_cnt;
+    __shared__ tie_key_t s_cl[BS / 64];
+    __shared__ int s_cr[BS / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double mn = INFINITY;
+    for (int t = threadIdx.x; t < nblk; t += BS) mn = fmin(mn, bmin[t]);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) mn = fmin(mn, __shfl_down(mn, off, 64));
+    if (lane == 0) s_min[wave] = mn;
+    if (threadIdx.x == 0) s_cnt = 0;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double g = s_min[0];
+        for (int w = 1; w < BS / 64; ++w) g = fmin(g, s_min[w]);
+        s_bcast = g;
+    }
+    __syncthreads();
+    const double gmin = s_bcast;
+    if (gmin == INFINITY) { *row_out = -1; *leave_out = 0x7fffffff; return; }
+    const double bound = gmin + tol_tie * fmax(1.0, fabs(gmin));
+    for (int t = threadIdx.x; t < nblk; t += BS) {
+        if (!(bmin[t] <= bound)) continue;
+        const int pos = atomicAdd(&s_cnt, 1);
+        if (pos < kListMax) s_list[pos] = t;
+    }
+    __syncthreads();
+    const int listed = s_cnt;
+    const bool use_list = listed <= kListMax;
+    const int total = (use_list ? listed : nblk) * kThreads;
+    tie_key_t best_key = kNoTieKey;
+    int best_row = -1;
+    for (int idx = threadIdx.x; idx < total; idx += BS) {
+        const int t = use_list ? s_list[idx / kThreads] : idx / kThreads;
+        const int i = t * kThreads + idx % kThreads;
+        if (i >= m) continue;
+        const double bi = b[i];
+        const int lv = basis_indices[i];
+        if (bi < -tol_feas && bi <= bound) {
+            const tie_key_t key = tie_key(0.0, lv, 0);
+            if (key < best_key) { best_key = key; best_row = i; }
+        }
+    }
+    tie_reduce<BS>(best_key, best_row, s_cl, s_cr, false);
+    *row_out = best_row; *leave_out = tie_key_leaving(best_key);
+}
+
+// The pivot row of a dual kernel: the given one (step-wise call) or the pick from the block minima.
+template <int BS>
+__device__ __forceinline__ void dual_pivot_row(const double* b, const int32_t* basis_indices, int m, double tol_feas, double tol_tie,
+                                               const double* bmin, int nblk, int forced_row, int* r, int* leaving) {
+    if (forced_row >= 0) { *r = forced_row; *leaving = basis_indices[forced_row]; return; }
+    dual_row_pick<BS>(b, basis_indices, m, tol_feas, tol_tie, bmin, nblk, r, leaving);
+}
+
+// d_j / (-row_j) of a candidate of the dual ratio test (row_j < -tol_pivot), with a d_j that rounding left at or below tol_zero
+// read as 0: no negative step
+__device__ __forceinline__ double dual_ratio(double d_j, double row_j, double tol_zero) {
+    const double dz = d_j <= tol_zero ? 0.0 : d_j;
+    return dz / (-row_j);
+}
+
+// Row r of T over the stored columns, one column per thread, into `row` (indexed from tv.c_lo), and the minimum (ratio, column)
+// of the workgroup's 256 columns into partial slot blockIdx.x.  Every workgroup determines the same r.  Reads T0 and R0 only:
+// a row that is new in the block is appended to R0 by the update (tab_row_update_core), not here.
+template <int B>
+__global__ __launch_bounds__(kThreads) void k_dual_row(TableauView tv, DeferredUpdate du, SelectPartials sp,
+                                                       const double* __restrict__ b, const int32_t* __restrict__ basis_indices,
+                                                       Tolerances tol, double tol_feas, const double* __restrict__ bmin, int nblk,
+                                                       int forced_row, double* __restrict__ row, const PivotRecord* rec) {
+    const int outcome = rec->outcome, p = rec->n_eta;
+    if (outcome != DEV_RUNNING) return;
+    int r, leaving;
+    dual_pivot_row<kThreads>(b, basis_indices, tv.m, tol_feas, tol.tie, bmin, nblk, forced_row, &r, &leaving);
+    if (r < 0) return;                                 // (k_dual_select_column ends the loop)
+    __shared__ double s_w[kMaxEta];
+    if ((int)threadIdx.x < p) s_w[threadIdx.x] = du.W[(int64_t)threadIdx.x * du.ld + r];
+    __syncthreads();
+    const int c = tv.c_lo + blockIdx.x * kThreads + threadIdx.x;
+    const int j = c - tv.col_off;
+    double key = INFINITY;
+    int kj = 0x7fffffff;
+    if (c < tv.c_hi) {
+        const double d_c = tv.d[c];
+        double v = tv.T0[(int64_t)c * tv.ld_t + r];
+        for_pending<B>(tv.R0, tv.ld_r, c, p, [&](int k, double r0) { v = fma(s_w[k], r0, v); });
+        row[c - tv.c_lo] = v;
+        if (j >= 0 && j < tv.n && sp.in_basis[j] == 0 && v < -tol.pivot) { key = dual_ratio(d_c, v, tol.zero); kj = j; }
+    }
+    block_partial_min(key, kj, sp, blockIdx.x);
+}
+
+// The entering column from the `count` partials of k_dual_row, by a workgroup of BS threads (the tab_select_entering pattern): the
+// minimum ratio, then the lowest column with a ratio <= min + tol_tie * max(1, |min|) -- only a slot whose own minimum is inside
+// that band can hold one, so only those slots are read again, from the row k_dual_row left and d.  On return every thread holds
+// the winner's ratio and column, bj = 0x7fffffff when there is no candidate.
+template <int BS>
+__device__ __forceinline__ void dual_select_entering(const TableauView& tv, const SelectPartials& sp, const Tolerances& tol,
+                                                     const double* row, int count, double& k1, int& bj) {
+    constexpr int kListMax = 32;
+    __shared__ int s_list[kListMax];
+    __shared__ int s_cnt;
+    __shared__ int s_low[BS / 64];
+    k1 = INFINITY; bj = 0x7fffffff;
+    for (int t = threadIdx.x; t < count; t += BS) {
+        const double key = sp.k1[t];
+        const int j = sp.j[t];
+        if (key < k1 || (key == k1 && j < bj)) { k1 = key; bj = j; }
+    }
+    if (threadIdx.x == 0) s_cnt = 0;                   // (visible after the barrier of the reduction)
+    block_min_key<BS>(k1, bj);
+    if (bj == 0x7fffffff || !(tol.tie > 0.0)) return;
+    const double bound = k1 + tol.tie * fmax(1.0, fabs(k1));
+    for (int t = threadIdx.x; t < count; t += BS) {
+        if (!(sp.k1[t] <= bound)) continue;
+        const int pos = atomicAdd(&s_cnt, 1);
+        if (pos < kListMax) s_list[pos] = t;
+    }
+    __syncthreads();
+    const int listed = s_cnt;
+    int lowest = 0x7fffffff;
+    auto scan_slot = [&](int t) {
+        const int c = tv.c_lo + t * kThreads + (int)(threadIdx.x % kThreads);
+        const int j = c - tv.col_off;
+        if (c < tv.c_hi && j >= 0 && j < tv.n) {
+            const double v = row[c - tv.c_lo];
+            const double d_c = tv.d[c];
+            if (sp.in_basis[j] == 0 && v < -tol.pivot && dual_ratio(d_c, v, tol.zero) <= bound && j < lowest) lowest = j;
+        }
+    };
+    constexpr int kGroups = BS / kThreads;
+    const int grp = threadIdx.x / kThreads;
+    if (listed <= kListMax) {
+        for (int i = grp; i < listed; i += kGroups) scan_slot(s_list[i]);
+    } else {
+        for (int t = grp; t < count; t += kGroups)
+            if (sp.k1[t] <= bound) scan_slot(t);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) lowest = min(lowest, __shfl_down(lowest, off, 64));
+    if ((threadIdx.x & 63) == 0) s_low[threadIdx.x >> 6] = lowest;
+    __syncthreads();
+    bj = s_low[0];                                     // the minimum itself is inside the band: there is one
+#pragma unroll
+    for (int w = 1; w < BS / 64; ++w) bj = min(bj, s_low[w]);
+}
+
+// Leaving row, entering column and the tableau column alpha = T0[:,q] + W R0[:,q] (the code of k_tab_column) in one launch over
+// the rows: every workgroup determines the same r and q, the first one writes them to the record -- or ends the loop: no
+// infeasible row is DEV_NO_ROW (the basis is optimal), no candidate in row r is DEV_NO_CANDIDATE (the LP is infeasible).
+template <int B>
+__global__ __launch_bounds__(kThreads) void k_dual_select_column(TableauView tv, DeferredUpdate du, SelectPartials sp, int count,
+                                                                 const double* __restrict__ b,
+                                                                 const int32_t* __restrict__ basis_indices, Tolerances tol,
+                                                                 double tol_feas, const double* __restrict__ bmin, int nblk,
+                                                                 int forced_row, const double* __restrict__ row,
+                                                                 double* __restrict__ alpha, PivotRecord* rec) {
+    const int outcome = rec->outcome, p = rec->n_eta;
+    if (outcome != DEV_RUNNING) return;
+    const bool first = blockIdx.x == 0 && threadIdx.x == 0;
+    int r, leaving;
+    dual_pivot_row<kThreads>(b, basis_indices, tv.m, tol_feas, tol.tie, bmin, nblk, forced_row, &r, &leaving);
+    if (r < 0) {
+        if (first) rec->outcome = DEV_NO_ROW;
+        return;
+    }
+    double k1;
+    int bj;
+    dual_select_entering<kThreads>(tv, sp, tol, row, count, k1, bj);
+    if (bj == 0x7fffffff) {
+        if (first) { rec->r = r; rec->leaving = leaving; rec->outcome = DEV_NO_CANDIDATE; }
+        return;
+    }
+    const int cq = bj + tv.col_off;
+    if (first) { rec->q = bj; rec->d_q = tv.d[cq]; rec->key1 = k1; rec->r = r; rec->leaving = leaving; }
+    __shared__ double s_vs[kMaxEta];
+    if ((int)threadIdx.x < p) s_vs[threadIdx.x] = tv.R0[(int64_t)threadIdx.x * tv.ld_r + cq];
+    __syncthreads();
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= tv.m) return;
+    double a = tv.T0[(int64_t)cq * tv.ld_t + i];
+    for_pending<B>(du.W, du.ld, i, p, [&](int j, double w) { a = fma(w, s_vs[j], a); });
+    alpha[i] = a;
+}
+
+// Step-wise call: the leaving row alone, into the record (or DEV_NO_ROW).
+__global__ __launch_bounds__(kSingleBlock) void k_dual_select_row(const double* __restrict__ b,
+                                                                  const int32_t* __restrict__ basis_indices, int m, double tol_feas,
+                                                                  double tol_tie, const double* __restrict__ bmin, int nblk,
+                                                                  PivotRecord* rec) {
+    if (rec->outcome != DEV_RUNNING) return;
+    int r, leaving;
+    dual_row_pick<kSingleBlock>(b, basis_indices, m, tol_feas, tol_tie, bmin, nblk, &r, &leaving);
+    if (threadIdx.x != 0) return;
+    if (r < 0) rec->outcome = DEV_NO_ROW;
+    else { rec->r = r; rec->leaving = leaving; }
+}
+
+// The pivot (r, q) of k_dual_select_column committed: alpha_r (negative here), b_r and the block bookkeeping of the deferred
+// update, as after a ratio test but without its pivot guard.  One workgroup.
+__global__ __launch_bounds__(kSingleBlock) void k_dual_commit(const double* __restrict__ alpha, const double* __restrict__ b,
+                                                              DeferredUpdate du, PivotRecord* rec) {
+    const int outcome = rec->outcome, p = rec->n_eta, r = rec->r, leaving = rec->leaving;
+    if (outcome != DEV_RUNNING) return;
+    ratio_commit_row<kSingleBlock>(r, leaving, alpha, b, du, p, rec);
+}
+
 int32_t tab_scan_blocks(int32_t n_owned_columns) { return cdiv(n_owned_columns, kThreads); }
 
 // The batch sizes of for_pending the kernels are instantiated for (DeferredUpdate::batch, RELP_TAB_LOAD_BATCH).  1 is the
@@ -999,5 +1241,38 @@ void launch_tab_row(const TableauView& tv, const DeferredUpdate& du, int32_t row
     });
 }
 
+void launch_dual_bmin(const double* b, int32_t m, double tol_feas, double* bmin, const PivotRecord* rec, hipStream_t s) {
+    hipLaunchKernelGGL(k_dual_bmin, dim3(cdiv(m, kThreads)), dim3(kThreads), 0, s, b, m, tol_feas, bmin, rec);
+}
+
+void launch_dual_select_row(const double* b, const int32_t* basis_indices, int32_t m, double tol_feas, double tol_tie,
+                            const double* bmin, PivotRecord* rec, hipStream_t s) {
+    hipLaunchKernelGGL(k_dual_select_row, dim3(1), dim3(kSingleBlock), 0, s, b, basis_indices, m, tol_feas, tol_tie, bmin,
+                       cdiv(m, kThreads), rec);
+}
+
+void launch_dual_row(const TableauView& tv, const DeferredUpdate& du, SelectPartials sp, const double* b,
+                     const int32_t* basis_indices, Tolerances tol, double tol_feas, const double* bmin, int32_t forced_row,
+                     double* row, const PivotRecord* rec, hipStream_t s) {
+    if (tv.c_hi <= tv.c_lo) return;
+    with_load_batch(du.batch, [&](auto B) {
+        hipLaunchKernelGGL((k_dual_row<decltype(B)::value>), dim3(tab_scan_blocks(tv.c_hi - tv.c_lo)), dim3(kThreads), 0, s, tv, du, sp, b,
+                           basis_indices, tol, tol_feas, bmin, cdiv(tv.m, kThreads), (int)forced_row, row, rec);
+    });
+}
+
+void launch_dual_select_column(const TableauView& tv, const DeferredUpdate& du, SelectPartials sp, const double* b,
+                               const int32_t* basis_indices, Tolerances tol, double tol_feas, const double* bmin,
+                               int32_t forced_row, const double* row, double* alpha, PivotRecord* rec, hipStream_t s) {
+    const int count = tv.c_hi > tv.c_lo ? tab_scan_blocks(tv.c_hi - tv.c_lo) : 0;
+    with_load_batch(du.batch, [&](auto B) {
+        hipLaunchKernelGGL((k_dual_select_column<decltype(B)::value>), dim3(cdiv(tv.m, kThreads)), dim3(kThreads), 0, s, tv, du, sp, count, b,
+                           basis_indices, tol, tol_feas, bmin, cdiv(tv.m, kThreads), (int)forced_row, row, alpha, rec);
+    });
+}
+
+void launch_dual_commit(const double* alpha, const double* b, const DeferredUpdate& du, PivotRecord* rec, hipStream_t s) {
+    hipLaunchKernelGGL(k_dual_commit, dim3(1), dim3(kSingleBlock), 0, s, alpha, b, du, rec);
+}
 
 }  // namespace relp

@@ -88,6 +88,10 @@ _SIGNATURES = {
     "relp_select_primal_pivot_row_of": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "relp_bring_into_basis": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.POINTER(C.c_int32)]),
     "relp_run": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    "relp_run_dual": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    "relp_select_dual_pivot_row": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "relp_select_dual_pivot_column": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "relp_set_right_hand_side": (C.c_int, [C.c_void_p, C.c_void_p]),
     "relp_solve_relaxation": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]),
     "relp_from_basis": (C.c_int, [C.c_void_p, C.c_void_p]),
     "relp_flush": (C.c_int, [C.c_void_p]),
@@ -367,6 +371,34 @@ class Tableau:
         self._ck(self._lib.relp_run(self._h, max_iters, C.byref(done), C.byref(oc)))
         return done.value, oc.value
 
+    # -- dual simplex (tableau engine, phase 2; beyond the reference) ---------------------------
+    def run_dual(self, max_iters: int) -> Tuple[int, int]:
+        """Up to ``max_iters`` dual pivots from a dual feasible basis; returns (iterations, outcome) with outcome OPTIMAL,
+        INFEASIBLE or RUNNING (relp_run_dual)."""
+        done, oc = C.c_int64(), C.c_int32()
+        self._ck(self._lib.relp_run_dual(self._h, max_iters, C.byref(done), C.byref(oc)))
+        return done.value, oc.value
+
+    def select_dual_pivot_row(self) -> Optional[int]:
+        """The leaving row of a dual pivot: the most negative b_i; None when no row is infeasible."""
+        found, row = C.c_int32(), C.c_int32()
+        self._ck(self._lib.relp_select_dual_pivot_row(self._h, C.byref(found), C.byref(row)))
+        return row.value if found.value else None
+
+    def select_dual_pivot_column(self, row: int) -> Optional[int]:
+        """The entering column of a dual pivot in tableau row ``row``; None when the row has no candidate."""
+        found, col = C.c_int32(), C.c_int32()
+        self._ck(self._lib.relp_select_dual_pivot_column(self._h, int(row), C.byref(found), C.byref(col)))
+        return col.value if found.value else None
+
+    def set_right_hand_side(self, rhs) -> None:
+        """A new right-hand side (nr_rows() entries in the engine's row order, any sign) for the current basis: the tableau is
+        re-tabulated, ``run_dual`` re-solves from there."""
+        arr = np.ascontiguousarray(rhs, dtype=np.float64)
+        if arr.shape != (self.nr_rows(),):
+            raise ValueError("rhs must have nr_rows() entries")
+        self._ck(self._lib.relp_set_right_hand_side(self._h, arr.ctypes.data))
+
     def solve_relaxation(self, max_iters: int = 1 << 40) -> int:
         oc = C.c_int32()
         self._ck(self._lib.relp_solve_relaxation(self._h, max_iters, C.byref(oc)))
@@ -606,6 +638,13 @@ def phase_two_primal(tableau: Tableau, max_iters: int = 1 << 40) -> int:
     if tableau.phase != 2:
         raise RelpError("tableau still has artificial variables")
     return tableau.run(max_iters)[1]
+
+
+def phase_two_dual(tableau: Tableau, max_iters: int = 1 << 40) -> int:
+    """The dual simplex loop from a dual feasible basis (relp_run_dual; the reference has none)."""
+    if tableau.phase != 2:
+        raise RelpError("tableau still has artificial variables")
+    return tableau.run_dual(max_iters)[1]
 
 
 def solve_relaxation(provider: MatrixData, **config_overrides):
