@@ -23,6 +23,34 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
+// Workgroup minimum (block_max_value: maximum) of one value per thread over BS threads, result in every thread.  One barrier;
+// every thread finishes from the BS / 64 LDS words itself, in ascending order.  Exact, so the result does not depend on how the
+// values are spread over the threads.  One set of LDS words per (BS, type, min or max): a kernel that makes the same call twice
+// puts a barrier between the calls.
+struct MinOp {
+    __device__ double operator()(double a, double b) const { return fmin(a, b); }
+    __device__ int operator()(int a, int b) const { return min(a, b); }
+};
+struct MaxOp {
+    __device__ double operator()(double a, double b) const { return fmax(a, b); }
+};
+template <int BS, class T, class Op>
+__device__ __forceinline__ T block_reduce_value(T v, Op op) {
+    __shared__ T s_v[BS / 64];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = op(v, __shfl_down(v, off, 64));
+    if ((threadIdx.x & 63) == 0) s_v[threadIdx.x >> 6] = v;
+    __syncthreads();
+    v = s_v[0];
+#pragma unroll
+    for (int w = 1; w < BS / 64; ++w) v = op(v, s_v[w]);
+    return v;
+}
+template <int BS, class T>
+__device__ __forceinline__ T block_min_value(T v) { return block_reduce_value<BS>(v, MinOp{}); }
+template <int BS>
+__device__ __forceinline__ double block_max_value(double v) { return block_reduce_value<BS>(v, MaxOp{}); }
+
 // Dot products of kVecPerBlock contiguous vectors (stride ld) with one shared vector x.
 // Thread t streams 16-byte pairs k = 2t, 2t + 512, ...; all 8 loads of one step are independent.
 // Vectors beyond `v_hi` are clamped (duplicate loads, results discarded) so there is no branch in
@@ -139,46 +167,51 @@ __device__ __forceinline__ void price_virtual_body(const ColumnTable& ct, const 
     block_partial_min(key, kj, sp, sp.offset + block);
 }
 
-// Entering column of the tableau engine from the `count` PRICE partials (slot t = the kThreads storage columns from
+// The slots t < count whose own minimum is inside a tie band (minima[t] <= bound), listed in s_list by a workgroup of BS threads;
+// returns their number in every thread (one barrier).  More than kListMax: the list is incomplete and the caller walks all
+// slots instead.  One thread of the caller sets s_cnt = 0 ahead of a barrier the caller already has.
+template <int BS, int kListMax>
+__device__ __forceinline__ int band_slots(const double* minima, int count, double bound, int* s_list, int& s_cnt) {
+    for (int t = threadIdx.x; t < count; t += BS) {
+        if (!(minima[t] <= bound)) continue;
+        const int pos = atomicAdd(&s_cnt, 1);
+        if (pos < kListMax) s_list[pos] = t;
+    }
+    __syncthreads();
+    return s_cnt;
+}
+
+// Entering column of the tableau engine from the `count` partials of a PRICE (slot t = the kThreads storage columns from
 // tv.c_lo + t * kThreads), by a workgroup of BS threads.  On entry (k1, bj) is the thread's first partial -- slot threadIdx.x,
-// (+inf, 0x7fffffff) past the end -- which the caller loads together with whatever else it has to wait for; on return every
-// thread holds the winner's key and column, bj = 0x7fffffff when there is none.
-// Dantzig ties (pivot_rule.rs:118): the lowest index with d_j <= k1 + tol_tie * max(1, |k1|).  Only a slot whose own minimum
-// is inside the band can hold such a column: those slots (normally one or two) are listed first, then re-read one column per
-// thread, so the scan does not walk all `count` slots one dependent load after the other.
-template <int BS>
-__device__ __forceinline__ void tab_select_entering(const TableauView& tv, const SelectPartials& sp, int count, double& k1,
-                                                    int& bj) {
+// (+inf, 0x7fffffff) past the end -- when the caller loaded it together with whatever else it has to wait for (have_first),
+// (+inf, 0x7fffffff) otherwise; on return every thread holds the winner's key and column, bj = 0x7fffffff when there is none.
+// Ties (band_on): the lowest index among the columns inside the band k1 + tol_tie * max(1, |k1|), in_band(c, j, bound) = storage
+// column c (index j) is a candidate inside it.  Only a slot whose own minimum is inside the band can hold such a column: those
+// slots (normally one or two) are listed first, then re-read one column per thread, so the scan does not walk all `count`
+// slots one dependent load after the other.
+template <int BS, class InBand>
+__device__ __forceinline__ void select_entering(const TableauView& tv, const SelectPartials& sp, int count, double tol_tie,
+                                                bool band_on, bool have_first, double& k1, int& bj, InBand&& in_band) {
     constexpr int kListMax = 32, kGroups = BS / kThreads;
     __shared__ int s_list[kListMax];
     __shared__ int s_cnt;
-    __shared__ int s_low[BS / 64];
-    for (int t = threadIdx.x + BS; t < count; t += BS) {
+    for (int t = threadIdx.x + (have_first ? BS : 0); t < count; t += BS) {
         const double key = sp.k1[t];
         const int j = sp.j[t];
         if (key < k1 || (key == k1 && j < bj)) { k1 = key; bj = j; }
     }
     if (threadIdx.x == 0) s_cnt = 0;                   // (visible after the barrier of the reduction)
     block_min_key<BS>(k1, bj);
-    if (!(bj != 0x7fffffff && sp.rule == 2 && sp.tol_tie > 0.0)) return;
-    const double bound = k1 + sp.tol_tie * fmax(1.0, fabs(k1));
-    for (int t = threadIdx.x; t < count; t += BS) {
-        if (!(sp.k1[t] <= bound)) continue;
-        const int pos = atomicAdd(&s_cnt, 1);
-        if (pos < kListMax) s_list[pos] = t;
-    }
-    __syncthreads();
-    const int listed = s_cnt;
+    if (bj == 0x7fffffff || !band_on) return;
+    const double bound = k1 + tol_tie * fmax(1.0, fabs(k1));
+    const int listed = band_slots<BS, kListMax>(sp.k1, count, bound, s_list, s_cnt);
     // kGroups groups of kThreads threads, each on every kGroups-th slot
     const int grp = threadIdx.x / kThreads, u = threadIdx.x % kThreads;
     int lowest = 0x7fffffff;
     auto scan_slot = [&](int t) {
         const int c = tv.c_lo + t * kThreads + u;
         const int j = c - tv.col_off;
-        if (c < tv.c_hi && j >= 0 && j < tv.n) {
-            const double v = tv.d[c];
-            if (!sp.in_basis[j] && v < -sp.tol_cost && v <= bound && j < lowest) lowest = j;
-        }
+        if (c < tv.c_hi && j >= 0 && j < tv.n && in_band(c, j, bound) && j < lowest) lowest = j;
     };
     if (listed <= kListMax) {
         for (int i = grp; i < listed; i += kGroups) scan_slot(s_list[i]);
@@ -186,13 +219,19 @@ __device__ __forceinline__ void tab_select_entering(const TableauView& tv, const
         for (int t = grp; t < count; t += kGroups)
             if (sp.k1[t] <= bound) scan_slot(t);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) lowest = min(lowest, __shfl_down(lowest, off, 64));
-    if ((threadIdx.x & 63) == 0) s_low[threadIdx.x >> 6] = lowest;
-    __syncthreads();
-    bj = s_low[0];                                     // the minimum itself is inside the band: there is one
-#pragma unroll
-    for (int w = 1; w < BS / 64; ++w) bj = min(bj, s_low[w]);
+    bj = block_min_value<BS>(lowest);                  // the minimum itself is inside the band: there is one
+}
+
+// The primal pick: Dantzig ties (pivot_rule.rs:118), the lowest index with d_j <= k1 + tol_tie * max(1, |k1|).  (k1, bj) = the
+// thread's first partial, loaded by the caller.
+template <int BS>
+__device__ __forceinline__ void tab_select_entering(const TableauView& tv, const SelectPartials& sp, int count, double& k1,
+                                                    int& bj) {
+    select_entering<BS>(tv, sp, count, sp.tol_tie, sp.rule == 2 && sp.tol_tie > 0.0, true, k1, bj, [&](int c, int j, double bound) {
+        const double v = tv.d[c];
+        const bool basic = sp.in_basis[j];             // with d: one round trip, not two (no short circuit between the loads)
+        return !basic & (v < -sp.tol_cost && v <= bound);
+    });
 }
 
 // Sharded PRICE: the winner among `count` gathered candidates, candidate g with key key[g * stride] (+inf = the rank has
@@ -331,18 +370,9 @@ __device__ __forceinline__ void ratio_commit_row(int r, int leaving, const doubl
     if (guard_m > 0) {
         // Tolerances::pivot_guard: the chosen element against the largest |entry| of the column (one pass of the workgroup
         // over alpha; nothing has been written yet)
-        __shared__ double s_gm[BS / 64];
         double mx = 0.0;
         for (int i = threadIdx.x; i < guard_m; i += BS) mx = fmax(mx, fabs(alpha[i]));
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) mx = fmax(mx, __shfl_down(mx, off, 64));
-        __syncthreads();
-        if ((threadIdx.x & 63) == 0) s_gm[threadIdx.x >> 6] = mx;
-        __syncthreads();
-        double amax = s_gm[0];
-#pragma unroll
-        for (int w = 1; w < BS / 64; ++w) amax = fmax(amax, s_gm[w]);
-        if (alpha[r] < guard_rel * amax) {
+        if (alpha[r] < guard_rel * block_max_value<BS>(mx)) {
             if (threadIdx.x == 0) rec->outcome = DEV_NO_ROW;
             return;
         }
@@ -377,10 +407,6 @@ __device__ __forceinline__ void ratio_commit_row(int r, int leaving, const doubl
 template <int BS, int ITEMS>
 __device__ __forceinline__ void ratio_body(const double* alpha, const double* b, const int32_t* basis_indices, int m,
                                            const Tolerances& tol, const DeferredUpdate& du, int p, PivotRecord* rec) {
-    __shared__ double s_min[BS / 64];
-    __shared__ double s_bcast;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-
     // Each thread keeps its rows' ratios and leaving columns in registers (all loads issued at once, one
     // memory round trip); both passes then run out of registers.  m > 16 * 1024 falls back to re-reading.
     constexpr int kItems = ITEMS;
@@ -411,17 +437,7 @@ __device__ __forceinline__ void ratio_body(const double* alpha, const double* b,
             mn = fmin(mn, ratio);
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mn = fmin(mn, __shfl_down(mn, off, 64));
-    if (lane == 0) s_min[wave] = mn;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double g = s_min[0];
-        for (int w = 1; w < BS / 64; ++w) g = fmin(g, s_min[w]);
-        s_bcast = g;
-    }
-    __syncthreads();
-    const double gmin = s_bcast;
+    const double gmin = block_min_value<BS>(mn);
     if (gmin == INFINITY) {
         if (threadIdx.x == 0) rec->outcome = DEV_NO_ROW;
         return;
@@ -463,47 +479,28 @@ __device__ __forceinline__ double row_ratio(double a, double bi, const Tolerance
     return a > tol.pivot ? bi / a : INFINITY;
 }
 
-// Ratio test of a workgroup of BS threads from the minimum ratio of every block of `rpb` rows (`rmin`, nblk
-// entries, written by the kernel that formed alpha): the global minimum is the minimum of the block minima, and
-// a row inside the tie band lives in a block whose own minimum is inside the band, so only those blocks' rows
-// (usually one or two blocks) are read again.  Same choice as ratio_body.  Every thread of the workgroup returns with
-// (row, leaving column), row = -1 when no row qualifies; nothing is written.
-// `first` = rmin[threadIdx.x] when the caller loaded it together with the record (have_first)
-template <int BS>
-__device__ __forceinline__ void ratio_blocks_pick(const double* alpha, const double* b, const int32_t* basis_indices, int m,
-                                                  const Tolerances& tol, const double* rmin, int nblk, int* row_out, int* leave_out,
-                                                  double first = INFINITY, bool have_first = false, int rpb = kThreads) {
-    __shared__ double s_min[BS / 64];
-    __shared__ double s_bcast;
+// The pivot row from the minimum of every block of `rpb` rows (`minima`, nblk entries, written by the kernel that walked the
+// rows), by a workgroup of BS threads: the global minimum is the minimum of the block minima, and a row inside the tie band
+// lives in a block whose own minimum is inside the band, so only those blocks' rows (usually one or two blocks) are read
+// again.  key_of_row(i, bound) = the tie-break key of row i (tie_key), kNoTieKey when the row does not qualify or lies outside
+// the band; the smallest key wins (tie_reduce, `wide` = the keys use their upper half).  Every thread of the workgroup returns
+// with (row, leaving column), row = -1 when no row qualifies; nothing is written.
+// `first` = minima[threadIdx.x] when the caller loaded it together with the record (have_first)
+template <int BS, class KeyOfRow>
+__device__ __forceinline__ void block_minima_pick(const double* minima, int nblk, int rpb, int m, double tol_tie, double first,
+                                                  bool have_first, bool wide, int* row_out, int* leave_out, KeyOfRow&& key_of_row) {
     constexpr int kListMax = 64;
     __shared__ int s_list[kListMax];
     __shared__ int s_cnt;
     __shared__ tie_key_t s_cl[BS / 64];
     __shared__ int s_cr[BS / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     double mn = have_first ? first : INFINITY;
-    for (int t = threadIdx.x + (have_first ? BS : 0); t < nblk; t += BS) mn = fmin(mn, rmin[t]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mn = fmin(mn, __shfl_down(mn, off, 64));
-    if (lane == 0) s_min[wave] = mn;
-    if (threadIdx.x == 0) s_cnt = 0;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double g = s_min[0];
-        for (int w = 1; w < BS / 64; ++w) g = fmin(g, s_min[w]);
-        s_bcast = g;
-    }
-    __syncthreads();
-    const double gmin = s_bcast;
+    for (int t = threadIdx.x + (have_first ? BS : 0); t < nblk; t += BS) mn = fmin(mn, minima[t]);
+    if (threadIdx.x == 0) s_cnt = 0;                   // (visible after the barrier of the reduction)
+    const double gmin = block_min_value<BS>(mn);
     if (gmin == INFINITY) { *row_out = -1; *leave_out = 0x7fffffff; return; }
-    const double bound = gmin + tol.tie * fmax(1.0, fabs(gmin));
-    for (int t = threadIdx.x; t < nblk; t += BS) {
-        if (!(rmin[t] <= bound)) continue;
-        const int pos = atomicAdd(&s_cnt, 1);
-        if (pos < kListMax) s_list[pos] = t;
-    }
-    __syncthreads();
-    const int listed = s_cnt;
+    const double bound = gmin + tol_tie * fmax(1.0, fabs(gmin));
+    const int listed = band_slots<BS, kListMax>(minima, nblk, bound, s_list, s_cnt);
     const bool use_list = listed <= kListMax;
     const int total = (use_list ? listed : nblk) * rpb;
     tie_key_t best_key = kNoTieKey;
@@ -512,18 +509,28 @@ __device__ __forceinline__ void ratio_blocks_pick(const double* alpha, const dou
         const int t = use_list ? s_list[idx / rpb] : idx / rpb;
         const int i = t * rpb + idx % rpb;
         if (i >= m) continue;
+        const tie_key_t key = key_of_row(i, bound);
+        if (key < best_key) { best_key = key; best_row = i; }
+    }
+    tie_reduce<BS>(best_key, best_row, s_cl, s_cr, wide);
+    *row_out = best_row; *leave_out = tie_key_leaving(best_key);
+}
+
+// Ratio test from the minimum ratio of every block of `rpb` rows (`rmin`, written by the kernel that formed alpha).  Same choice
+// as ratio_body.
+template <int BS>
+__device__ __forceinline__ void ratio_blocks_pick(const double* alpha, const double* b, const int32_t* basis_indices, int m,
+                                                  const Tolerances& tol, const double* rmin, int nblk, int* row_out, int* leave_out,
+                                                  double first = INFINITY, bool have_first = false, int rpb = kThreads) {
+    block_minima_pick<BS>(rmin, nblk, rpb, m, tol.tie, first, have_first, tol.ratio_rule != 0, row_out, leave_out,
+                          [&](int i, double bound) {
         const double a = alpha[i];
         double bi = b[i];
         int lv = basis_indices[i];                     // with alpha and b: one round trip, not two
         asm volatile("" : "+v"(lv));
         if (bi <= tol.zero) bi = 0.0;   // also clamps a b_i that rounding pushed below 0: no negative step
-        if (a > tol.pivot && bi / a <= bound) {
-            const tie_key_t key = tie_key(a, lv, tol.ratio_rule);
-            if (key < best_key) { best_key = key; best_row = i; }
-        }
-    }
-    tie_reduce<BS>(best_key, best_row, s_cl, s_cr, tol.ratio_rule != 0);
-    *row_out = best_row; *leave_out = tie_key_leaving(best_key);
+        return (a > tol.pivot && bi / a <= bound) ? tie_key(a, lv, tol.ratio_rule) : kNoTieKey;
+    });
 }
 
 // The same as one whole step of a single-workgroup launch: the choice, then "no row" or the record and the block bookkeeping.

@@ -96,7 +96,6 @@ __global__ __launch_bounds__(kSingleBlock) void k_select_partials(SelectPartials
                                                                   DeviceCSC csc, ColumnTable ct, int m,
                                                                   double* __restrict__ aq, PivotRecord* rec) {
     if (rec->outcome != DEV_RUNNING) return;
-    __shared__ int s_j[kSingleBlock / 64];
     __shared__ int s_q;
     double k1 = INFINITY;
     int bj = 0x7fffffff;
@@ -106,7 +105,6 @@ __global__ __launch_bounds__(kSingleBlock) void k_select_partials(SelectPartials
         if (key < k1 || (key == k1 && j < bj)) { k1 = key; bj = j; }
     }
     block_min_key<kSingleBlock>(k1, bj);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (bj != 0x7fffffff && sp.rule == 2 && sp.tol_tie > 0.0) {
         // Dantzig ties: lowest index among the columns within the tie band of the minimum.  A column
         // inside the band lives in a workgroup whose own minimum is inside the band, so only those
@@ -120,13 +118,7 @@ __global__ __launch_bounds__(kSingleBlock) void k_select_partials(SelectPartials
         __shared__ int s_cnt;
         if (threadIdx.x == 0) s_cnt = 0;
         __syncthreads();
-        for (int t = threadIdx.x; t < count; t += kSingleBlock) {
-            if (!(sp.k1[t] <= bound)) continue;
-            const int pos = atomicAdd(&s_cnt, 1);
-            if (pos < kListMax) s_list[pos] = t;
-        }
-        __syncthreads();
-        const int listed = s_cnt;
+        const int listed = band_slots<kSingleBlock, kListMax>(sp.k1, count, bound, s_list, s_cnt);
         auto scan_slot = [&](int t, int u0, int ustep) {
             if (t < sp.nb_struct) {
                 const int p0 = sp.p_lo + t * sp.cols_per_slot;
@@ -148,15 +140,9 @@ __global__ __launch_bounds__(kSingleBlock) void k_select_partials(SelectPartials
                 }
             }
         };
-        auto block_low = [&](int v) {                      // minimum over the workgroup, in every thread
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_down(v, off, 64));
+        auto block_low = [&](int v) {                      // minimum over the workgroup, in every thread; called repeatedly
             __syncthreads();
-            if (lane == 0) s_j[wave] = v;
-            __syncthreads();
-            int low = s_j[0];
-            for (int w = 1; w < kSingleBlock / 64; ++w) low = min(low, s_j[w]);
-            return low;
+            return block_min_value<kSingleBlock>(v);
         };
         if (listed <= kListMax) {
             for (int i = 0; i < listed; ++i) scan_slot(s_list[i], threadIdx.x, kSingleBlock);
@@ -273,7 +259,6 @@ __global__ __launch_bounds__(kSingleBlock) void k_select_column(
     const double* __restrict__ d, const uint8_t* __restrict__ in_basis, int n, int rule, double tol_cost,
     double tol_tie, PivotRecord* rec) {
     if (rec->outcome != DEV_RUNNING) return;
-    __shared__ int s_j[kSingleBlock / 64];
     const int last = (rule == 1) ? rec->last_selected : -1;
     double k1 = INFINITY;
     int bj = 0x7fffffff;
@@ -289,7 +274,6 @@ __global__ __launch_bounds__(kSingleBlock) void k_select_column(
         }
     }
     block_min_key<kSingleBlock>(k1, bj);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (bj != 0x7fffffff && rule == 2 && tol_tie > 0.0) {
         // Dantzig ties: lowest index among the columns within the tie band of the minimum
         const double bound = k1 + tol_tie * fmax(1.0, fabs(k1));
@@ -298,16 +282,7 @@ __global__ __launch_bounds__(kSingleBlock) void k_select_column(
             const double v = d[j];
             if (!in_basis[j] && v < -tol_cost && v <= bound && j < lowest) lowest = j;
         }
-        __syncthreads();
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) lowest = min(lowest, __shfl_down(lowest, off, 64));
-        if (lane == 0) s_j[wave] = lowest;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            int low = 0x7fffffff;
-            for (int w = 0; w < kSingleBlock / 64; ++w) low = min(low, s_j[w]);
-            bj = low;                                  // the minimum itself is inside the band
-        }
+        bj = block_min_value<kSingleBlock>(lowest);    // the minimum itself is inside the band
     }
     if (threadIdx.x == 0) {
         if (bj == 0x7fffffff) {
@@ -510,7 +485,6 @@ __global__ __launch_bounds__(kThreads) void k_apply_w(DeferredUpdate du, int m, 
                                                       double* __restrict__ rmin, const PivotRecord* rec) {
     if (rec->outcome != DEV_RUNNING) return;
     __shared__ double s_vs[kMaxEta];
-    __shared__ double s_min[kThreads / 64];
     const int p = rec->n_eta;
     if ((int)threadIdx.x < p) s_vs[threadIdx.x] = v[du.S[threadIdx.x]];
     const int i = blockIdx.x * kThreads + threadIdx.x;
@@ -524,11 +498,8 @@ __global__ __launch_bounds__(kThreads) void k_apply_w(DeferredUpdate du, int m, 
         ratio = row_ratio(a, b_i, tol);
     }
     if (!rmin) return;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) ratio = fmin(ratio, __shfl_down(ratio, off, 64));
-    if ((threadIdx.x & 63) == 0) s_min[threadIdx.x >> 6] = ratio;
-    __syncthreads();
-    if (threadIdx.x == 0) rmin[blockIdx.x] = fmin(fmin(s_min[0], s_min[1]), fmin(s_min[2], s_min[3]));
+    ratio = block_min_value<kThreads>(ratio);
+    if (threadIdx.x == 0) rmin[blockIdx.x] = ratio;
 }
 
 // One wavefront-sized workgroup: save row r of W, choose the column that will receive u.

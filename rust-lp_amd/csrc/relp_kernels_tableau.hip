@@ -40,6 +40,27 @@ __device__ __forceinline__ void for_pending(const double* base, int64_t stride, 
     }
 }
 
+// Row r of W (its p pending entries) into s_w, one entry per thread; the caller's next barrier publishes it.
+__device__ __forceinline__ void stage_w_row(const DeferredUpdate& du, int r, int p, double* s_w) {
+    if ((int)threadIdx.x < p) s_w[threadIdx.x] = du.W[(int64_t)threadIdx.x * du.ld + r];
+}
+
+// T[r,c] = base + sum_j W[j][r] R0[j][c] over the p pending rows, ascending j.  s_w = row r of W (stage_w_row); base =
+// T0[c * ld_t + r], or row r's slot of R0, loaded by the caller where it wants that load to leave.
+template <int B>
+__device__ __forceinline__ double tab_row_entry(const TableauView& tv, int c, int p, const double* s_w, double base) {
+    for_pending<B>(tv.R0, tv.ld_r, c, p, [&](int j, double r0) { base = fma(s_w[j], r0, base); });
+    return base;
+}
+
+// alpha_i = t0 + sum_j W[j][i] R0[j][cq] over the p pending rows, ascending j.  s_vs = column cq of R0, staged by the caller;
+// t0 = T0[cq * ld_t + i], loaded by the caller where it wants that load to leave.
+template <int B>
+__device__ __forceinline__ double tab_column_entry(const DeferredUpdate& du, int i, int p, const double* s_vs, double t0) {
+    for_pending<B>(du.W, du.ld, i, p, [&](int j, double w) { t0 = fma(w, s_vs[j], t0); });
+    return t0;
+}
+
 // W <- E W for row i: W[j][i] = fma(u, w_r[j], W[j][i]) for the pending rows j0 <= j < j1, where neither factor is zero
 // (fma(u, 0.0, -0.0) is +0.0: an entry a zero factor would leave alone keeps its bits).
 template <int B>
@@ -141,9 +162,7 @@ __global__ __launch_bounds__(kThreads) void k_tab_column(TableauView tv, Deferre
     __syncthreads();
     const int i = blockIdx.x * kThreads + threadIdx.x;
     if (i >= tv.m) return;
-    double a = tv.T0[(int64_t)cq * tv.ld_t + i];
-    for_pending<B>(du.W, du.ld, i, p, [&](int j, double w) { a = fma(w, s_vs[j], a); });
-    alpha[i] = a;
+    alpha[i] = tab_column_entry<B>(du, i, p, s_vs, tv.T0[(int64_t)cq * tv.ld_t + i]);
 }
 
 // Row r of T before the pivot, the reduced-cost update and the next PRICE's partial argmin in one
@@ -171,8 +190,7 @@ __device__ __forceinline__ void tab_row_update_core(const TableauView& tv, const
             base = tv.T0[(int64_t)c * tv.ld_t + r];
             tv.R0[(int64_t)jt * tv.ld_r + c] = base;
         }
-        double row = base;
-        for_pending<B>(tv.R0, tv.ld_r, c, p_old, [&](int j, double r0) { row = fma(s_wr[j], r0, row); });
+        const double row = tab_row_entry<B>(tv, c, p_old, s_wr, base);
         const double theta = d_q / alpha_r;
         const int j = c - tv.col_off;
         double dn = fma(-theta, row, d_old);
@@ -312,7 +330,7 @@ __global__ __launch_bounds__(kThreads) void k_tab_ratio_update_all(TableauView t
     __shared__ double s_ab[2];
     __shared__ int s_jt;
     const int p_old = R.p_now;
-    if ((int)threadIdx.x < p_old) s_wr[threadIdx.x] = du.W[(int64_t)threadIdx.x * du.ld + r];
+    stage_w_row(du, r, p_old, s_wr);
     if (threadIdx.x == 0) {
         s_ab[0] = alpha[r]; s_ab[1] = b_in[r];
         const int slot = du.pos_of_row[r];
@@ -408,7 +426,6 @@ __global__ __launch_bounds__(kThreads) void k_tab_select_column(TableauView tv, 
     const double b_i = (rmin && i < tv.m) ? b[i] : 0.0;
     if (outcome != DEV_RUNNING) return;
     __shared__ double s_vs[kMaxEta];
-    __shared__ double s_min[kThreads / 64];
     tab_select_entering<kThreads>(tv, sp, count, k1, bj);
     if (bj == 0x7fffffff) {
         if (msg) {
@@ -435,8 +452,7 @@ __global__ __launch_bounds__(kThreads) void k_tab_select_column(TableauView tv, 
     __syncthreads();
     double ratio = INFINITY;
     if (i < tv.m) {
-        double a = t0;
-        for_pending<B>(du.W, du.ld, i, p, [&](int j, double w) { a = fma(w, s_vs[j], a); });
+        const double a = tab_column_entry<B>(du, i, p, s_vs, t0);
         alpha[i] = a;
         // the same expression as the ratio test's first pass (ratio_body), so min over the block minima is
         // bit for bit the minimum over all rows
@@ -444,11 +460,8 @@ __global__ __launch_bounds__(kThreads) void k_tab_select_column(TableauView tv, 
         if (a > tol.pivot) ratio = bz / a;
     }
     if (!rmin) return;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) ratio = fmin(ratio, __shfl_down(ratio, off, 64));
-    if ((threadIdx.x & 63) == 0) s_min[threadIdx.x >> 6] = ratio;
-    __syncthreads();
-    if (threadIdx.x == 0) rmin[blockIdx.x] = fmin(fmin(s_min[0], s_min[1]), fmin(s_min[2], s_min[3]));
+    ratio = block_min_value<kThreads>(ratio);
+    if (threadIdx.x == 0) rmin[blockIdx.x] = ratio;
 }
 
 // Ratio test from the per-block minima of k_tab_select_column (ratio_blocks_body): one workgroup.
@@ -786,13 +799,11 @@ __global__ __launch_bounds__(kThreads) void k_tab_row(TableauView tv, DeferredUp
                                                       const PivotRecord* rec) {
     __shared__ double s_w[kMaxEta];
     const int p = rec->n_eta;
-    if ((int)threadIdx.x < p) s_w[threadIdx.x] = du.W[(int64_t)threadIdx.x * du.ld + row];
+    stage_w_row(du, row, p, s_w);
     __syncthreads();
     const int c = tv.c_lo + blockIdx.x * kThreads + threadIdx.x;
     if (c >= tv.c_hi) return;
-    double v = tv.T0[(int64_t)c * tv.ld_t + row];
-    for_pending<B>(tv.R0, tv.ld_r, c, p, [&](int j, double r0) { v = fma(s_w[j], r0, v); });
-    out[c - tv.c_lo] = v;
+    out[c - tv.c_lo] = tab_row_entry<B>(tv, c, p, s_w, tv.T0[(int64_t)c * tv.ld_t + row]);
 }
 
 // phase_one.rs:236-244 for the sharded engine: among the owned columns, the candidates to replace a basic
@@ -804,15 +815,14 @@ __global__ __launch_bounds__(kThreads) void k_tab_zero_level_scan(TableauView tv
     const int outcome = rec->outcome, p = rec->n_eta;
     if (outcome != DEV_RUNNING) return;
     __shared__ double s_w[kMaxEta];
-    if ((int)threadIdx.x < p) s_w[threadIdx.x] = du.W[(int64_t)threadIdx.x * du.ld + row];
+    stage_w_row(du, row, p, s_w);
     __syncthreads();
     const int c = tv.c_lo + blockIdx.x * kThreads + threadIdx.x;
     const int j = c - tv.col_off;
     double key = INFINITY;
     int kj = 0x7fffffff;
     if (c < tv.c_hi && j >= nr_artificial && j < tv.n && !sp.in_basis[j] && fabs(tv.d[c]) <= tol.cost) {
-        double v = tv.T0[(int64_t)c * tv.ld_t + row];
-        for_pending<B>(tv.R0, tv.ld_r, c, p, [&](int k, double r0) { v = fma(s_w[k], r0, v); });
+        const double v = tab_row_entry<B>(tv, c, p, s_w, tv.T0[(int64_t)c * tv.ld_t + row]);
         if (fabs(v) > tol.pivot) { key = (double)j; kj = j; }
     }
     block_partial_min(key, kj, sp, blockIdx.x);
@@ -829,75 +839,27 @@ __global__ __launch_bounds__(kThreads) void k_tab_zero_level_scan(TableauView tv
 __global__ __launch_bounds__(kThreads) void k_dual_bmin(const double* __restrict__ b, int m, double tol_feas,
                                                         double* __restrict__ bmin, const PivotRecord* rec) {
     if (rec->outcome != DEV_RUNNING) return;
-    __shared__ double s_min[kThreads / 64];
     const int i = blockIdx.x * kThreads + threadIdx.x;
     double v = INFINITY;
     if (i < m) {
         const double bi = b[i];
         if (bi < -tol_feas) v = bi;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_down(v, off, 64));
-    if ((threadIdx.x & 63) == 0) s_min[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) bmin[blockIdx.x] = fmin(fmin(s_min[0], s_min[1]), fmin(s_min[2], s_min[3]));
+    v = block_min_value<kThreads>(v);
+    if (threadIdx.x == 0) bmin[blockIdx.x] = v;
 }
 
-// The leaving row from the block minima, by a workgroup of BS threads, the way ratio_blocks_pick picks from rmin: the minimum
-// of the minima, then only the blocks whose own minimum is inside the tie band are read again; Bland on the leaving column
-// among their infeasible rows inside the band.  Every thread returns with (row, leaving column), row = -1 when no row is
-// infeasible; nothing is written.
+// The leaving row from the block minima `bmin` (block_minima_pick): Bland on the leaving column among the infeasible rows inside
+// the tie band of the minimum.  Every thread returns with (row, leaving column), row = -1 when no row is infeasible; nothing is
+// written.
 template <int BS>
 __device__ __forceinline__ void dual_row_pick(const double* b, const int32_t* basis_indices, int m, double tol_feas, double tol_tie,
                                               const double* bmin, int nblk, int* row_out, int* leave_out) {
-    __shared__ double s_min[BS / 64];
-    __shared__ double s_bcast;
-    constexpr int kListMax = 64;
-    __shared__ int s_list[kListMax];
-    __shared__ int s_cnt;
-    __shared__ tie_key_t s_cl[BS / 64];
-    __shared__ int s_cr[BS / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    double mn = INFINITY;
-    for (int t = threadIdx.x; t < nblk; t += BS) mn = fmin(mn, bmin[t]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mn = fmin(mn, __shfl_down(mn, off, 64));
-    if (lane == 0) s_min[wave] = mn;
-    if (threadIdx.x == 0) s_cnt = 0;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double g = s_min[0];
-        for (int w = 1; w < BS / 64; ++w) g = fmin(g, s_min[w]);
-        s_bcast = g;
-    }
-    __syncthreads();
-    const double gmin = s_bcast;
-    if (gmin == INFINITY) { *row_out = -1; *leave_out = 0x7fffffff; return; }
-    const double bound = gmin + tol_tie * fmax(1.0, fabs(gmin));
-    for (int t = threadIdx.x; t < nblk; t += BS) {
-        if (!(bmin[t] <= bound)) continue;
-        const int pos = atomicAdd(&s_cnt, 1);
-        if (pos < kListMax) s_list[pos] = t;
-    }
-    __syncthreads();
-    const int listed = s_cnt;
-    const bool use_list = listed <= kListMax;
-    const int total = (use_list ? listed : nblk) * kThreads;
-    tie_key_t best_key = kNoTieKey;
-    int best_row = -1;
-    for (int idx = threadIdx.x; idx < total; idx += BS) {
-        const int t = use_list ? s_list[idx / kThreads] : idx / kThreads;
-        const int i = t * kThreads + idx % kThreads;
-        if (i >= m) continue;
+    block_minima_pick<BS>(bmin, nblk, kThreads, m, tol_tie, INFINITY, false, false, row_out, leave_out, [&](int i, double bound) {
         const double bi = b[i];
         const int lv = basis_indices[i];
-        if (bi < -tol_feas && bi <= bound) {
-            const tie_key_t key = tie_key(0.0, lv, 0);
-            if (key < best_key) { best_key = key; best_row = i; }
-        }
-    }
-    tie_reduce<BS>(best_key, best_row, s_cl, s_cr, false);
-    *row_out = best_row; *leave_out = tie_key_leaving(best_key);
+        return (bi < -tol_feas && bi <= bound) ? tie_key(0.0, lv, 0) : kNoTieKey;
+    });
 }
 
 // The pivot row of a dual kernel: the given one (step-wise call) or the pick from the block minima.
@@ -929,7 +891,7 @@ __global__ __launch_bounds__(kThreads) void k_dual_row(TableauView tv, DeferredU
     dual_pivot_row<kThreads>(b, basis_indices, tv.m, tol_feas, tol.tie, bmin, nblk, forced_row, &r, &leaving);
     if (r < 0) return;                                 // (k_dual_select_column ends the loop)
     __shared__ double s_w[kMaxEta];
-    if ((int)threadIdx.x < p) s_w[threadIdx.x] = du.W[(int64_t)threadIdx.x * du.ld + r];
+    stage_w_row(du, r, p, s_w);
     __syncthreads();
     const int c = tv.c_lo + blockIdx.x * kThreads + threadIdx.x;
     const int j = c - tv.col_off;
@@ -937,67 +899,11 @@ __global__ __launch_bounds__(kThreads) void k_dual_row(TableauView tv, DeferredU
     int kj = 0x7fffffff;
     if (c < tv.c_hi) {
         const double d_c = tv.d[c];
-        double v = tv.T0[(int64_t)c * tv.ld_t + r];
-        for_pending<B>(tv.R0, tv.ld_r, c, p, [&](int k, double r0) { v = fma(s_w[k], r0, v); });
+        const double v = tab_row_entry<B>(tv, c, p, s_w, tv.T0[(int64_t)c * tv.ld_t + r]);
         row[c - tv.c_lo] = v;
         if (j >= 0 && j < tv.n && sp.in_basis[j] == 0 && v < -tol.pivot) { key = dual_ratio(d_c, v, tol.zero); kj = j; }
     }
     block_partial_min(key, kj, sp, blockIdx.x);
-}
-
-// The entering column from the `count` partials of k_dual_row, by a workgroup of BS threads (the tab_select_entering pattern): the
-// minimum ratio, then the lowest column with a ratio <= min + tol_tie * max(1, |min|) -- only a slot whose own minimum is inside
-// that band can hold one, so only those slots are read again, from the row k_dual_row left and d.  On return every thread holds
-// the winner's ratio and column, bj = 0x7fffffff when there is no candidate.
-template <int BS>
-__device__ __forceinline__ void dual_select_entering(const TableauView& tv, const SelectPartials& sp, const Tolerances& tol,
-                                                     const double* row, int count, double& k1, int& bj) {
-    constexpr int kListMax = 32;
-    __shared__ int s_list[kListMax];
-    __shared__ int s_cnt;
-    __shared__ int s_low[BS / 64];
-    k1 = INFINITY; bj = 0x7fffffff;
-    for (int t = threadIdx.x; t < count; t += BS) {
-        const double key = sp.k1[t];
-        const int j = sp.j[t];
-        if (key < k1 || (key == k1 && j < bj)) { k1 = key; bj = j; }
-    }
-    if (threadIdx.x == 0) s_cnt = 0;                   // (visible after the barrier of the reduction)
-    block_min_key<BS>(k1, bj);
-    if (bj == 0x7fffffff || !(tol.tie > 0.0)) return;
-    const double bound = k1 + tol.tie * fmax(1.0, fabs(k1));
-    for (int t = threadIdx.x; t < count; t += BS) {
-        if (!(sp.k1[t] <= bound)) continue;
-        const int pos = atomicAdd(&s_cnt, 1);
-        if (pos < kListMax) s_list[pos] = t;
-    }
-    __syncthreads();
-    const int listed = s_cnt;
-    int lowest = 0x7fffffff;
-    auto scan_slot = [&](int t) {
-        const int c = tv.c_lo + t * kThreads + (int)(threadIdx.x % kThreads);
-        const int j = c - tv.col_off;
-        if (c < tv.c_hi && j >= 0 && j < tv.n) {
-            const double v = row[c - tv.c_lo];
-            const double d_c = tv.d[c];
-            if (sp.in_basis[j] == 0 && v < -tol.pivot && dual_ratio(d_c, v, tol.zero) <= bound && j < lowest) lowest = j;
-        }
-    };
-    constexpr int kGroups = BS / kThreads;
-    const int grp = threadIdx.x / kThreads;
-    if (listed <= kListMax) {
-        for (int i = grp; i < listed; i += kGroups) scan_slot(s_list[i]);
-    } else {
-        for (int t = grp; t < count; t += kGroups)
-            if (sp.k1[t] <= bound) scan_slot(t);
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) lowest = min(lowest, __shfl_down(lowest, off, 64));
-    if ((threadIdx.x & 63) == 0) s_low[threadIdx.x >> 6] = lowest;
-    __syncthreads();
-    bj = s_low[0];                                     // the minimum itself is inside the band: there is one
-#pragma unroll
-    for (int w = 1; w < BS / 64; ++w) bj = min(bj, s_low[w]);
 }
 
 // Leaving row, entering column and the tableau column alpha = T0[:,q] + W R0[:,q] (the code of k_tab_column) in one launch over
@@ -1019,9 +925,15 @@ __global__ __launch_bounds__(kThreads) void k_dual_select_column(TableauView tv,
         if (first) rec->outcome = DEV_NO_ROW;
         return;
     }
-    double k1;
-    int bj;
-    dual_select_entering<kThreads>(tv, sp, tol, row, count, k1, bj);
+    // the entering column from the partials of k_dual_row (select_entering): the minimum ratio, then the lowest column with a ratio
+    // inside its tie band, from the row k_dual_row left and d
+    double k1 = INFINITY;
+    int bj = 0x7fffffff;
+    select_entering<kThreads>(tv, sp, count, tol.tie, tol.tie > 0.0, false, k1, bj, [&](int c, int j, double bound) {
+        const double v = row[c - tv.c_lo];
+        const double d_c = tv.d[c];
+        return sp.in_basis[j] == 0 && v < -tol.pivot && dual_ratio(d_c, v, tol.zero) <= bound;
+    });
     if (bj == 0x7fffffff) {
         if (first) { rec->r = r; rec->leaving = leaving; rec->outcome = DEV_NO_CANDIDATE; }
         return;
@@ -1033,9 +945,7 @@ __global__ __launch_bounds__(kThreads) void k_dual_select_column(TableauView tv,
     __syncthreads();
     const int i = blockIdx.x * kThreads + threadIdx.x;
     if (i >= tv.m) return;
-    double a = tv.T0[(int64_t)cq * tv.ld_t + i];
-    for_pending<B>(du.W, du.ld, i, p, [&](int j, double w) { a = fma(w, s_vs[j], a); });
-    alpha[i] = a;
+    alpha[i] = tab_column_entry<B>(du, i, p, s_vs, tv.T0[(int64_t)cq * tv.ld_t + i]);
 }
 
 // Step-wise call: the leaving row alone, into the record (or DEV_NO_ROW).

@@ -158,7 +158,8 @@ def dual_simplex(md: MatrixData, basis: Sequence[int], exact=None, max_iters: in
             break
         ratios = [(d[j] if d[j] > tol["tol_zero"] else d[j] * 0) / (-T[r, j]) for j in range(ncol)
                   if not in_basis[j] and T[r, j] < -tol["tol_pivot"]]
-        max_band = max(max_band, sum(1 for v in ratios if v <= min(ratios) + tol["tol_tie"] * max(1, abs(min(ratios)))))
+        lo = min(ratios)
+        max_band = max(max_band, sum(1 for v in ratios if v <= lo + tol["tol_tie"] * max(1, abs(lo))))
         leaving = basis[r]
         trace.append((q, r, leaving))
         alpha = T[:, q].copy()

@@ -7,7 +7,8 @@ reference's pivots one for one; one case is built to tie exactly -- two rows of 
 smaller leaving column in the later row -- and the infeasible LP ties two ratios.  Shapes: one block of rows and columns; more than 256 stored columns (40 x 300: 340 of them, two
 workgroups of partials, the second one partial); more than 256 rows (257 x 8: the second block of minima holds one row; 300 x
 40); update_block 3 on 32 x 48 (21 pivots on 13 distinct rows: rows return to occupied slots of W and the block flushes seven
-times).  Tolerances: the project's own 1e-9 relative on objectives (OBJ_RTOL) and tol_feas = 1e-7 on b.
+times).  Two more cases tie on purpose, to overflow the lists the pickers keep of the blocks / slots inside a tie band: 16,385 rows
+that all share b_i = -1 (65 blocks against a list of 64) and 8,400 columns at ratio 1 (33 slots against a list of 32).  Tolerances: the project's own 1e-9 relative on objectives (OBJ_RTOL) and tol_feas = 1e-7 on b.
 """
 import functools
 import re
@@ -230,4 +231,55 @@ def test_reinversion_inside_the_dual_loop():
     assert_dual_solve(case, t)
     assert t.reinversions() - before >= 1
     assert t.check_basis()[2] >= -TOL_FEAS
+    t.close()
+
+
+def covering_from(A, b):
+    m, n = A.shape
+    return MatrixData(nr_normal=n, nr_eq=0, nr_range=0, nr_le=0, nr_ge=m, b=np.asarray(b, dtype=np.float64), cost=np.ones(n),
+                      upper_bound=np.full(n, np.inf), dense=np.asfortranarray(A, dtype=np.float64))
+
+
+def test_row_pick_with_more_blocks_in_the_tie_band_than_the_list_holds():
+    """16,385 rows = 65 blocks of 256, the last one of a single row, every b_i = -1.0 exactly: all 65 block minima are inside the
+    tie band, one more than the 64 the block list holds, so the pick walks every block.  The surplus columns of rows 0 and 16,384
+    are exchanged in the basis: the smallest leaving column sits in the last block's only row.  The step call picks with 1,024
+    threads, the loop's two kernels with 256 in every workgroup.  The tableau of 16,385 x 16,387 doubles (2.1 GB) is what 65
+    blocks cost; the reference solve at this size is not computed, only its row pick."""
+    m, n = 16385, 2
+    md = covering_from(np.ones((m, n)), np.ones(m))
+    basis = dr.surplus_basis(m, n)
+    basis[0], basis[m - 1] = basis[m - 1], basis[0]
+    t = engine.Tableau(md, engine=engine.ENGINE_TABLEAU, trace_capacity=16)
+    t.from_basis(basis)
+    assert t.b().min() == t.b().max() == -1.0
+    row = t.select_dual_pivot_row()
+    assert row == dr.select_dual_pivot_row(t.b(), t.basis_indices(), TOL["tol_feas"], TOL["tol_tie"]) == m - 1
+    assert t.run_dual(1)[0] == 1
+    (_, r, leaving), = dual_trace(t)
+    assert (r, leaving) == (m - 1, n)
+    t.close()
+
+
+def test_entering_column_with_more_slots_in_the_tie_band_than_the_list_holds():
+    """8,702 stored columns = 34 slots of 256.  Row 0 (b = -2) leaves; its entries are 0 in the columns below 300 and -1 from
+    there on, and every cost is 1: 8,400 columns tie at ratio exactly 1, the minima of slots 1 to 33 are inside the band (slot 0
+    holds no candidate), one more than the 32 the slot list holds, so the pick walks every slot.  Column 300 enters."""
+    m, n = 2, 8700
+    A = np.ones((m, n))
+    A[0, :300] = 0.0
+    md = covering_from(A, [2.0, 1.0])
+    basis = dr.surplus_basis(m, n)
+    ref = dr.dual_simplex(md, basis)
+    assert ref.outcome == "optimal" and ref.max_band >= 8400 and ref.trace[0] == (300, 0, n)
+    t = engine.Tableau(md, engine=engine.ENGINE_TABLEAU, trace_capacity=16)
+    t.from_basis(basis)
+    assert t.nr_columns() == 8702
+    assert t.run_dual(1 << 20) == (len(ref.trace), engine.OPTIMAL)
+    assert dual_trace(t) == ref.trace
+    assert close_to(t.objective_function_value(), ref.objective)
+    t.close()
+    t = engine.Tableau(md, engine=engine.ENGINE_TABLEAU)
+    t.from_basis(basis)
+    assert t.select_dual_pivot_column(0) == 300
     t.close()

@@ -1136,6 +1136,31 @@ def test_ratio_test_from_block_minima_on_many_degenerate_rows(degenerate_rows):
         assert traces[0][0][2] == 0 and traces[0][0][3] == n
 
 
+def test_dantzig_entering_column_with_more_slots_in_the_tie_band_than_the_list_holds():
+    """8,702 stored columns = 34 slots of 256 for the tableau engine's entering-column pick from the PRICE partials.  The costs
+    are 0 below column 300 and -1 from there on: under SteepestDescent 8,400 columns tie at d_j = -1, the minima of slots 1 to 33
+    are inside the band (slot 0 holds no candidate), one more than the 32 the slot list holds, so the pick walks every slot; the
+    lowest index, 300, enters.  The loop picks with 256 threads in every workgroup (k_tab_select_column), the step call with
+    1,024 (k_tab_select)."""
+    m, n = 2, 8700
+    c = -np.ones(n)
+    c[:300] = 0.0
+    md = MatrixData.from_dense_le(np.ones((m, n)), np.array([1.0, 2.0]), c)
+    rules = dict(phase_one_rule=engine.STEEPEST_DESCENT, phase_two_rule=engine.STEEPEST_DESCENT)
+    ref = relp_f64.OracleF64(md.ensure_csc(), phase_one_rule=relp_f64.RULE_STEEPEST_DESCENT,
+                             phase_two_rule=relp_f64.RULE_STEEPEST_DESCENT)
+    assert ref.run() == "optimal" and ref.trace[0][1] == 300
+    t = engine.Tableau(md, engine=engine.ENGINE_TABLEAU, trace_capacity=4096, **rules)
+    assert t.nr_columns() == 8702
+    assert t.solve_relaxation() == engine.OPTIMAL
+    assert t.trace() == ref.trace
+    t.close()
+    t = engine.Tableau(md, engine=engine.ENGINE_TABLEAU, **rules)
+    assert t.run(1 << 20)[1] == engine.PHASE_ONE_DONE      # (empty)
+    assert t.select_primal_pivot_column(engine.STEEPEST_DESCENT) == (300, -1.0)
+    t.close()
+
+
 @pytest.mark.parametrize("block", [8, 32, 64])
 def test_25fv47_on_the_tableau_engine_with_periodic_retabulation(block):
     """The dense tableau is only ever updated (T0 += W R0 at every flush); on 25FV47 it drifts until phase 1 ends in
