@@ -352,6 +352,17 @@ class Tableau {
         if ((int32_t)rhs.size() != nr_rows()) throw Error(RELP_E_ARG, "one right-hand side per row");
         ck(relp_set_right_hand_side(h_, rhs.data()));
     }
+    // single entries of it without a re-tabulation (relp_change_right_hand_side): rhs[rows[k]] = values[k], each row named once
+    void change_right_hand_side(const std::vector<int32_t>& rows, const std::vector<double>& values) {
+        if (rows.size() != values.size()) throw Error(RELP_E_ARG, "one value per row");
+        ck(relp_change_right_hand_side(h_, rows.data(), values.data(), (int32_t)rows.size()));
+    }
+    // the upper bound (finite at create) of structural column `column`: the in-place change of its bound row
+    void set_upper_bound(int32_t column, double value) { ck(relp_set_upper_bound(h_, column, value)); }
+    // the rhs in effect, engine row order
+    std::vector<double> right_hand_side() { std::vector<double> v(nr_rows()); ck(relp_get_right_hand_side(h_, v.data())); return v; }
+    // relp_rhs_stats: {in-place changes, columns of B^-1 they read, pending rows at the last change, shares of its last launch}
+    std::array<int64_t, 4> rhs_stats() { std::array<int64_t, 4> out{}; ck(relp_rhs_stats(h_, out.data())); return out; }
     // ---- one LP on several GPUs (no counterpart in the reference, which is single-threaded) ---------------------
     // Options::shard(rank, count) at construction, the owned structural columns in `MatrixData` (relp_shard_plan);
     // rank 0 makes the RCCL id, the host program hands it to every rank, every rank attaches, then the loop runs

@@ -246,6 +246,36 @@ relp_status_t relp_select_dual_pivot_column(relp_engine_t *h, int32_t row, int32
  * relp_reinversions but does not adapt the auto_reinversion interval (b moved with rhs, not by drift).  RELP_ENGINE_TABLEAU,
  * unsharded, phase 2. */
 relp_status_t relp_set_right_hand_side(relp_engine_t *h, const double *rhs_m);
+/* Single rhs entries moved on the current basis WITHOUT a re-tabulation (no counterpart in the reference): what a branch-and-bound
+ * or cutting-plane driver does at every node before relp_run_dual.  rhs[rows[k]] = values[k] for k < count; `rows` are engine rows
+ * in the current order (the indexing of relp_set_right_hand_side), values of any sign.  Nothing is rebuilt: B^-1 is in the tableau
+ * (the stored columns that were the identity at the start), so with delta_k = values[k] - rhs[rows[k]] and c_k the identity column
+ * of row rows[k]
+ *     b_i += sum_k delta_k * (T0[i,c_k] + sum_{j<p} W[j][i] * R0[j][c_k])          (p = pending rows of the open update block)
+ * in fixed summation orders (no atomics: the same call on the same state gives the same bits).  Entries with delta_k == 0 are dropped
+ * before anything is uploaded.  -obj is re-formed from the new b as a re-tabulation forms it, and the call synchronises.  The
+ * reduced costs, the basis, the pending update block (no flush happens) and relp_reinversions are untouched; every later
+ * re-tabulation (re-inversion interval, auto_reinversion, relp_from_basis, relp_set_right_hand_side) builds on the new values.
+ * RELP_E_ARG with nothing changed: a row out of range, a row named twice, a value that is not finite, count < 0.  count == 0 is a
+ * no-op.  The list is processed in `splits` shares: chosen so that the launch covers the device while every share keeps at least 256
+ * entries, or RELP_TAB_RHS_SPLITS=n at create (clamped to [1, min(entries, 256)]).  Measured at 10,000 x 10,000
+ * (profiles/r13_rhs_in_place.md): 0.08 ms for 1 or 64 entries and 0.24 ms for all 10,000 (0.28 ms with an update
+ * block open) against 517 ms of relp_set_right_hand_side -- the every-entry change beats the rebuild too.
+ * RELP_ENGINE_TABLEAU, unsharded, phase 2: RELP_E_UNSUPPORTED on another or a sharded engine, RELP_E_STATE in phase 1 (all four
+ * calls). */
+relp_status_t relp_change_right_hand_side(relp_engine_t *h, const int32_t *rows, const double *values, int32_t count);
+/* The upper bound of structural (provider) column `column`: relp_change_right_hand_side on its bound row with count = 1 ("tighten
+ * x_j <= floor(x_j), relp_run_dual").  RELP_E_ARG when the column is not structural, when its bound was +inf at create (it has no
+ * bound row, and none can be added or dropped here) or when `value` is not finite.  A value below 0 is accepted: relp_run_dual then
+ * reports RELP_INFEASIBLE.
+ * A lower bound l on x_j is not built; a caller gets it with what exists by substituting x_j = l + x'_j: rhs_i -= l * A_ij over the
+ * constraint rows (one relp_change_right_hand_side), the bound row becomes u - l, and the constant c_j * l goes on the objective. */
+relp_status_t relp_set_upper_bound(relp_engine_t *h, int32_t column, double value);
+/* The rhs in effect (b, upper bounds, ranges): relp_nr_rows entries in the engine's current row order. */
+relp_status_t relp_get_right_hand_side(relp_engine_t *h, double *out_m);
+/* out4 = { in-place changes so far, columns of B^-1 they read (entries with a nonzero delta), pending rows p of the update block
+ * at the last change, shares (k-splits) of its last launch }. */
+relp_status_t relp_rhs_stats(const relp_engine_t *h, int64_t *out4);
 /* InverseMaintener::from_basis (carry/mod.rs:428-463): warm start from provider column indices,
  * one per row; switches to phase 2.  RELP_ENGINE_LU: any basis (factorise, b = FTRAN(rhs), -pi = BTRAN(-c_B));
  * RELP_ENGINE_REVISED: any basis (basis_inverse_rows.rs:103-129: LU - factorised on the host like every

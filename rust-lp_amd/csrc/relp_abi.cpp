@@ -84,6 +84,12 @@ relp_status_t relp_select_dual_pivot_column(relp_engine_t* h, int32_t row, int32
 relp_status_t relp_set_right_hand_side(relp_engine_t* h, const double* rhs_m) {
     return (h && rhs_m) ? H(h).set_right_hand_side(rhs_m) : RELP_E_ARG;
 }
+relp_status_t relp_change_right_hand_side(relp_engine_t* h, const int32_t* rows, const double* values, int32_t count) {
+    return h ? H(h).change_right_hand_side(rows, values, count) : RELP_E_ARG;
+}
+relp_status_t relp_set_upper_bound(relp_engine_t* h, int32_t column, double value) { return h ? H(h).set_upper_bound(column, value) : RELP_E_ARG; }
+relp_status_t relp_get_right_hand_side(relp_engine_t* h, double* out_m) { return (h && out_m) ? H(h).get_right_hand_side(out_m) : RELP_E_ARG; }
+relp_status_t relp_rhs_stats(const relp_engine_t* h, int64_t* out4) { return (h && out4) ? H(h).rhs_stats(out4) : RELP_E_ARG; }
 relp_status_t relp_solve_relaxation(relp_engine_t* h, int64_t max_iters, int32_t* outcome) {
     return h ? H(h).solve_relaxation(max_iters, outcome) : RELP_E_ARG;
 }

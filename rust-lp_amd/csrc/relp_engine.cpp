@@ -118,6 +118,7 @@ Switches Switches::read() {
     if (s.dump_basis_set) s.dump_basis = std::getenv("RELP_DUMP_BASIS");
     s.retab_global = num("RELP_RETAB_GLOBAL", 0) != 0;
     s.retab_groups = std::max(0, num("RELP_RETAB_GROUPS", 0));
+    s.tab_rhs_splits = std::max(0, num("RELP_TAB_RHS_SPLITS", 0));
     return s;
 }
 
@@ -273,6 +274,11 @@ relp_status_t Engine::create(const relp_matrix_data_t& md, const relp_config_t& 
         }
         HIP_TRY(d_cost_store_.alloc(n_store_));
         HIP_TRY(d_idcol_.alloc(lay_.m));
+        if (cfg_.shard_count == 1) {                       // scratch of relp_change_right_hand_side
+            HIP_TRY(d_rhs_cols_.alloc(lay_.m));
+            HIP_TRY(d_rhs_delta_.alloc(lay_.m));
+            HIP_TRY(d_rhs_v_.alloc(std::max(block_, 1)));
+        }
     }
     if (block_ > 0) HIP_TRY(d_v_.alloc(ld_b_));
     if (block_ > 0 && !ft_) {                              // (Forrest-Tomlin: no W, the update file lives in FtState)
@@ -1054,6 +1060,86 @@ relp_status_t Engine::set_right_hand_side(const double* rhs_m) {
         return st ? st : fail(RELP_E_SINGULAR, "relp_set_right_hand_side: the basis could not be factorised");
     }
     tab_partials_valid_ = false;
+    return RELP_OK;
+}
+
+// Single rhs entries moved on the current basis without a re-tabulation.  B^-1 is in the tableau -- the stored columns that were
+// the identity at the start -- so b += sum_k delta_k T[:, idcol[row_k]] with T = T0 + W R0 over the pending rows of the open block
+// (launch_tab_rhs_change).  d, the PRICE partials, the basis, the flags, W, R0 and T0 stay as they are; -obj is re-formed from the
+// downloaded b as retabulate() forms it.  Settles the fused update's shadow row first, does not flush.
+relp_status_t Engine::change_right_hand_side(const int32_t* rows, const double* values, int32_t count) {
+    relp_status_t st = dual_ready("relp_change_right_hand_side");
+    if (st) return st;
+    if (count < 0 || (count > 0 && (!rows || !values))) return fail(RELP_E_ARG, "relp_change_right_hand_side: count < 0 or a list missing");
+    {
+        std::vector<uint8_t> named(lay_.m, 0);
+        for (int32_t k = 0; k < count; ++k) {
+            if (rows[k] < 0 || rows[k] >= lay_.m) return fail(RELP_E_ARG, "relp_change_right_hand_side: row out of range");
+            if (named[rows[k]]) return fail(RELP_E_ARG, "relp_change_right_hand_side: a row named twice");
+            if (!std::isfinite(values[k])) return fail(RELP_E_ARG, "relp_change_right_hand_side: a value that is not finite");
+            named[rows[k]] = 1;
+        }
+    }
+    if (count == 0) return RELP_OK;
+    std::vector<int32_t> cols;
+    std::vector<double> delta;
+    for (int32_t k = 0; k < count; ++k) {
+        const double dk = values[k] - lay_.rhs[rows[k]];
+        if (dk == 0.0) continue;
+        cols.push_back(idcol_h_[rows[k]]);
+        delta.push_back(dk);
+    }
+    const int32_t cnt = (int32_t)cols.size();
+    tab_settle();
+    if ((st = download_rec())) return st;
+    const int32_t p = h_rec_->n_eta;
+    h_rec_->outcome = DEV_RUNNING;
+    if (cnt > 0) {
+        const int32_t splits = tab_rhs_splits(lay_.m, cnt, sw_.tab_rhs_splits);
+        if (splits > 1 && splits > rhs_partial_splits_) {
+            HIP_TRY(d_rhs_partial_.alloc((int64_t)splits * ld_b_));
+            rhs_partial_splits_ = splits;
+        }
+        HIP_TRY(hipMemcpyAsync(d_rhs_cols_, cols.data(), sizeof(int32_t) * cnt, hipMemcpyHostToDevice, stream_));
+        HIP_TRY(hipMemcpyAsync(d_rhs_delta_, delta.data(), sizeof(double) * cnt, hipMemcpyHostToDevice, stream_));
+        launch_tab_rhs_change(tview(), deferred(), RhsChange{d_rhs_cols_, d_rhs_delta_, cnt}, p, splits, d_rhs_v_, d_b_, d_rhs_partial_,
+                              ld_b_, stream_);
+        std::vector<double> b(lay_.m);
+        std::vector<int32_t> basis(lay_.m);
+        HIP_TRY(hipMemcpyAsync(b.data(), d_b_, sizeof(double) * lay_.m, hipMemcpyDeviceToHost, stream_));
+        if ((st = fetch(basis.data(), d_basis_, sizeof(int32_t) * lay_.m))) return st;       // (waits for cols, delta and b too)
+        if (hipGetLastError() != hipSuccess) return fail(RELP_E_HIP, "relp_change_right_hand_side: a kernel launch failed");
+        h_rec_->minus_objective = -objective_of(basis, b);
+        rhs_last_splits_ = splits;
+    }
+    for (int32_t k = 0; k < count; ++k) lay_.rhs[rows[k]] = values[k];
+    ++rhs_changes_;
+    rhs_columns_ += cnt;
+    rhs_last_p_ = p;
+    return upload_rec();
+}
+
+relp_status_t Engine::set_upper_bound(int32_t column, double value) {
+    const relp_status_t st = dual_ready("relp_set_upper_bound");
+    if (st) return st;
+    if (column < 0 || column >= lay_.nr_normal) return fail(RELP_E_ARG, "relp_set_upper_bound: not a structural column");
+    const int32_t row = lay_.bound_row[column];
+    if (row < 0) return fail(RELP_E_ARG, "relp_set_upper_bound: the column had no finite upper bound at create (a bound row cannot be added here)");
+    if (!std::isfinite(value)) return fail(RELP_E_ARG, "relp_set_upper_bound: the bound must be finite (a bound row cannot be dropped here)");
+    return change_right_hand_side(&row, &value, 1);
+}
+
+relp_status_t Engine::get_right_hand_side(double* out_m) {
+    const relp_status_t st = dual_ready("relp_get_right_hand_side");
+    if (st) return st;
+    std::copy(lay_.rhs.begin(), lay_.rhs.begin() + lay_.m, out_m);
+    return RELP_OK;
+}
+
+relp_status_t Engine::rhs_stats(int64_t* out4) const {
+    if (!tableau_ || cfg_.shard_count > 1) return RELP_E_UNSUPPORTED;
+    if (phase_ != 2) return RELP_E_STATE;
+    out4[0] = rhs_changes_; out4[1] = rhs_columns_; out4[2] = rhs_last_p_; out4[3] = rhs_last_splits_;
     return RELP_OK;
 }
 

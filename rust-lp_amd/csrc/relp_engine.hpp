@@ -82,6 +82,7 @@ struct Switches {
     bool dump_basis_set = false; std::string dump_basis;  // RELP_DUMP_BASIS
     bool retab_global = false;                            // RELP_RETAB_GLOBAL
     int retab_groups = 0;                                 // RELP_RETAB_GROUPS (0: not given)
+    int tab_rhs_splits = 0;                               // RELP_TAB_RHS_SPLITS (0: the rule of tab_rhs_splits)
     static Switches read();
 };
 
@@ -120,6 +121,11 @@ class Engine : private EngineQueue {
     relp_status_t select_dual_pivot_row(int32_t* found, int32_t* row);
     relp_status_t select_dual_pivot_column(int32_t row, int32_t* found, int32_t* column);
     relp_status_t set_right_hand_side(const double* rhs_m);
+    // the same without a re-tabulation: single rhs entries (an upper bound is the rhs of its bound row) moved on the current basis
+    relp_status_t change_right_hand_side(const int32_t* rows, const double* values, int32_t count);
+    relp_status_t set_upper_bound(int32_t column, double value);
+    relp_status_t get_right_hand_side(double* out_m);
+    relp_status_t rhs_stats(int64_t* out4) const;
     int32_t engine_kind() const { return lay_.engine; }
     relp_status_t robust_stats(int64_t* out4) const;
     relp_status_t solve_relaxation(int64_t max_iters, int32_t* outcome);
@@ -268,6 +274,13 @@ class Engine : private EngineQueue {
     void enqueue_iteration_dual();
     relp_status_t dual_ready(const char* what);        // phase 2 on the unsharded tableau engine, or the error
     void tableau_reprice();
+    // relp_change_right_hand_side: the compacted list (identity column, delta) of a change, v = the pending rows' share and the
+    // per-split partial sums (relp_kernels.h: launch_tab_rhs_change); what relp_rhs_stats reports
+    DeviceBuf<int32_t> d_rhs_cols_;
+    DeviceBuf<double> d_rhs_delta_, d_rhs_v_, d_rhs_partial_;
+    int32_t rhs_partial_splits_ = 0;                   // splits d_rhs_partial_ holds (allocated at the first split launch, grown on demand)
+    int64_t rhs_changes_ = 0, rhs_columns_ = 0;
+    int32_t rhs_last_p_ = 0, rhs_last_splits_ = 0;
     // sparse LU engine (cfg.engine == RELP_ENGINE_LU): B^-1 = (I + W S') (L U)^-1, refactor every block_ pivots
     bool lu_ = false;
     std::vector<int64_t> hc_ptr_; std::vector<int32_t> hc_idx_; std::vector<double> hc_val_;   // host CSC of A

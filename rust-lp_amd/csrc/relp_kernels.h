@@ -488,6 +488,21 @@ void launch_dual_select_column(const TableauView& tv, const DeferredUpdate& du, 
                                int32_t forced_row, const double* row, double* alpha, PivotRecord* rec, hipStream_t s);
 // alpha_r, b_r and the block bookkeeping of the deferred update for the (r, leaving) of the record: ratio_commit_row, no guard
 void launch_dual_commit(const double* alpha, const double* b, const DeferredUpdate& du, PivotRecord* rec, hipStream_t s);
+// A change of rhs entries on the current basis (relp_change_right_hand_side): b += sum_k delta[k] T[:, cols[k]] with T = T0 + W R0
+// over the p pending rows, nothing else touched.  cols[k] = the stored column that was the identity column of the k-th changed row
+// (entries with delta 0 left out), ascending k as the caller gave them.
+struct RhsChange { const int32_t* cols; const double* delta; int32_t count; };
+// The list is cut into `splits` equal shares of ceil(count / splits) entries, one grid row of workgroups each.  tab_rhs_splits:
+// forced >= 1 (RELP_TAB_RHS_SPLITS) clamped to [1, min(count, kTabRhsMaxSplits)]; else as many as bring the grid of cdiv(m, 256)
+// workgroups per split up to kTabRhsGrid workgroups, as long as every split keeps a full LDS chunk (256 entries) of the list.
+static constexpr int32_t kTabRhsGrid = 512;
+static constexpr int32_t kTabRhsMaxSplits = 256;
+int32_t tab_rhs_splits(int32_t m, int32_t count, int32_t forced);
+// [k_tab_rhs_pending: v_j = sum_k delta_k R0[j][c_k], p > 0 only] -> [k_tab_rhs_apply: the T0 columns + W v per row; b += or
+// partial[split]] -> [k_tab_rhs_reduce: b += the partials in split order, splits > 1 only].  v: du.kmax doubles; partial:
+// splits * ld_partial doubles (unused when splits == 1).  No atomics: the same (list, p, splits) gives the same bits.
+void launch_tab_rhs_change(const TableauView& tv, const DeferredUpdate& du, const RhsChange& ch, int32_t p, int32_t splits,
+                           double* v, double* b, double* partial, int64_t ld_partial, hipStream_t s);
 
 // ---- sparse LU engine ------------------------------------------------------------------------------
 // PRICE over CSC columns (thread per column), partial argmin per 256 columns

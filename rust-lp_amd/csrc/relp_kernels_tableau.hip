@@ -970,6 +970,85 @@ __global__ __launch_bounds__(kSingleBlock) void k_dual_commit(const double* __re
     ratio_commit_row<kSingleBlock>(r, leaving, alpha, b, du, p, rec);
 }
 
+// ------------------------------------------------------------------------------------------------
+// A change of rhs entries in place (relp_change_right_hand_side): b += sum_k delta_k T[:, c_k] over the list (c_k, delta_k) of
+// the changed rows' identity columns, with T = T0 + W R0 while an update block is open:
+//   b_i += sum_k delta_k T0[i, c_k] + sum_{j<p} W[j][i] v_j,   v_j = sum_k delta_k R0[j][c_k]
+// No atomics: every sum has a fixed order, so a given (list, p, splits) gives the same bits every run.
+// ------------------------------------------------------------------------------------------------
+// v_j for pending row j = blockIdx.x: thread t sums its entries k = t, t + 256, ... in ascending order, then a fixed tree over the
+// 256 threads.  The identity columns of neighbouring rows are mostly neighbouring stored columns: the loads of a wavefront coalesce.
+__global__ __launch_bounds__(kThreads) void k_tab_rhs_pending(TableauView tv, RhsChange ch, double* __restrict__ v) {
+    __shared__ double s_sum[kThreads];
+    const double* row = tv.R0 + (int64_t)blockIdx.x * tv.ld_r;
+    double acc = 0.0;
+    for (int k = threadIdx.x; k < ch.count; k += kThreads) acc = fma(ch.delta[k], row[ch.cols[k]], acc);
+    s_sum[threadIdx.x] = acc;
+    __syncthreads();
+    for (int half = kThreads / 2; half > 0; half >>= 1) {
+        if ((int)threadIdx.x < half) s_sum[threadIdx.x] += s_sum[threadIdx.x + half];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) v[blockIdx.x] = s_sum[0];
+}
+
+// Row i = blockIdx.x * 256 + threadIdx.x, split blockIdx.y of the list: entries [lo, hi) in ascending k, staged in LDS 256 at a
+// time, their T0 loads issued B at a time before any is used (as in for_pending; consecutive threads read consecutive rows of
+// one column).  Split 0 then adds the pending rows' share through v (p > 0).  splits == 1: b[i] += acc, else partial[split][i].
+template <int B>
+__global__ __launch_bounds__(kThreads) void k_tab_rhs_apply(TableauView tv, DeferredUpdate du, RhsChange ch, int p,
+                                                            const double* __restrict__ v, double* __restrict__ b,
+                                                            double* __restrict__ partial, int64_t ld_partial) {
+    __shared__ int32_t s_c[kThreads];
+    __shared__ double s_delta[kThreads];
+    __shared__ double s_v[kMaxEta];
+    const int splits = gridDim.y, split = blockIdx.y;
+    const int share = (ch.count + splits - 1) / splits;
+    const int lo = min(split * share, ch.count), hi = min(lo + share, ch.count);
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    const bool mine = i < tv.m;
+    if (split == 0 && (int)threadIdx.x < p) s_v[threadIdx.x] = v[threadIdx.x];
+    double acc = 0.0;
+    for (int base = lo; base < hi; base += kThreads) {
+        __syncthreads();                               // (the previous chunk has been read)
+        const int n = min(kThreads, hi - base);
+        if ((int)threadIdx.x < n) { s_c[threadIdx.x] = ch.cols[base + threadIdx.x]; s_delta[threadIdx.x] = ch.delta[base + threadIdx.x]; }
+        __syncthreads();
+        if (!mine) continue;
+        int k0 = 0;
+        for (; k0 + B <= n; k0 += B) {
+            double t[B];
+#pragma unroll
+            for (int u = 0; u < B; ++u) t[u] = tv.T0[(int64_t)s_c[k0 + u] * tv.ld_t + i];
+#pragma unroll
+            for (int u = 0; u < B; ++u) acc = fma(s_delta[k0 + u], t[u], acc);
+        }
+        if (k0 < n) {
+            double t[B];
+#pragma unroll
+            for (int u = 0; u < B; ++u) t[u] = k0 + u < n ? tv.T0[(int64_t)s_c[k0 + u] * tv.ld_t + i] : 0.0;
+#pragma unroll
+            for (int u = 0; u < B; ++u)
+                if (k0 + u < n) acc = fma(s_delta[k0 + u], t[u], acc);
+        }
+    }
+    __syncthreads();                                   // s_v (a split with an empty share never entered the loop)
+    if (!mine) return;
+    if (split == 0) for_pending<B>(du.W, du.ld, i, p, [&](int j, double w) { acc = fma(w, s_v[j], acc); });
+    if (splits == 1) b[i] += acc;
+    else partial[(int64_t)split * ld_partial + i] = acc;
+}
+
+// b[i] += partial[0][i] + partial[1][i] + ... in ascending split order
+__global__ __launch_bounds__(kThreads) void k_tab_rhs_reduce(int m, int splits, const double* __restrict__ partial, int64_t ld_partial,
+                                                             double* __restrict__ b) {
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= m) return;
+    double sum = partial[i];
+    for (int s = 1; s < splits; ++s) sum += partial[(int64_t)s * ld_partial + i];
+    b[i] += sum;
+}
+
 int32_t tab_scan_blocks(int32_t n_owned_columns) { return cdiv(n_owned_columns, kThreads); }
 
 // The batch sizes of for_pending the kernels are instantiated for (DeferredUpdate::batch, RELP_TAB_LOAD_BATCH).  1 is the
@@ -1183,6 +1262,25 @@ void launch_dual_select_column(const TableauView& tv, const DeferredUpdate& du, 
 
 void launch_dual_commit(const double* alpha, const double* b, const DeferredUpdate& du, PivotRecord* rec, hipStream_t s) {
     hipLaunchKernelGGL(k_dual_commit, dim3(1), dim3(kSingleBlock), 0, s, alpha, b, du, rec);
+}
+
+int32_t tab_rhs_splits(int32_t m, int32_t count, int32_t forced) {
+    if (count < 1) return 1;
+    if (forced >= 1) return std::min({forced, count, kTabRhsMaxSplits});
+    const int32_t fill = kTabRhsGrid / cdiv(m, kThreads);              // splits until the grid covers the device ...
+    return std::max(1, std::min({fill, count / kThreads, kTabRhsMaxSplits}));   // ... each with a full LDS chunk of the list
+}
+
+void launch_tab_rhs_change(const TableauView& tv, const DeferredUpdate& du, const RhsChange& ch, int32_t p, int32_t splits,
+                           double* v, double* b, double* partial, int64_t ld_partial, hipStream_t s) {
+    if (ch.count < 1) return;
+    if (p > 0) hipLaunchKernelGGL(k_tab_rhs_pending, dim3(p), dim3(kThreads), 0, s, tv, ch, v);
+    const int nb = cdiv(tv.m, kThreads);
+    with_load_batch(du.batch, [&](auto B) {
+        hipLaunchKernelGGL((k_tab_rhs_apply<decltype(B)::value>), dim3(nb, splits), dim3(kThreads), 0, s, tv, du, ch, (int)p, v, b, partial,
+                           ld_partial);
+    });
+    if (splits > 1) hipLaunchKernelGGL(k_tab_rhs_reduce, dim3(nb), dim3(kThreads), 0, s, (int)tv.m, (int)splits, partial, ld_partial, b);
 }
 
 }  // namespace relp

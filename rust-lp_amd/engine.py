@@ -92,6 +92,10 @@ _SIGNATURES = {
     "relp_select_dual_pivot_row": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "relp_select_dual_pivot_column": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "relp_set_right_hand_side": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "relp_change_right_hand_side": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
+    "relp_set_upper_bound": (C.c_int, [C.c_void_p, C.c_int32, C.c_double]),
+    "relp_get_right_hand_side": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "relp_rhs_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "relp_solve_relaxation": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]),
     "relp_from_basis": (C.c_int, [C.c_void_p, C.c_void_p]),
     "relp_flush": (C.c_int, [C.c_void_p]),
@@ -398,6 +402,34 @@ class Tableau:
         if arr.shape != (self.nr_rows(),):
             raise ValueError("rhs must have nr_rows() entries")
         self._ck(self._lib.relp_set_right_hand_side(self._h, arr.ctypes.data))
+
+    def change_right_hand_side(self, rows, values) -> None:
+        """rhs[rows[k]] = values[k] on the current basis without a re-tabulation (relp_change_right_hand_side): b moves by the
+        changed rows' columns of B^-1, read off the tableau; the reduced costs, the basis and the open update block stay.  ``rows``
+        are engine rows in the current order, each named once; ``run_dual`` re-solves from there."""
+        r = np.ascontiguousarray(rows, dtype=np.int32)
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        if r.ndim != 1 or r.shape != v.shape:
+            raise ValueError("rows and values must be one-dimensional and of the same length")
+        self._ck(self._lib.relp_change_right_hand_side(self._h, r.ctypes.data, v.ctypes.data, r.shape[0]))
+
+    def set_upper_bound(self, column: int, value: float) -> None:
+        """The upper bound of structural column ``column`` (finite at create) becomes ``value``: the in-place change of its bound
+        row (relp_set_upper_bound)."""
+        self._ck(self._lib.relp_set_upper_bound(self._h, int(column), float(value)))
+
+    def right_hand_side(self) -> np.ndarray:
+        """The rhs in effect, nr_rows() entries in the engine's row order (relp_get_right_hand_side)."""
+        out = np.zeros(self.nr_rows())
+        self._ck(self._lib.relp_get_right_hand_side(self._h, out.ctypes.data))
+        return out
+
+    def rhs_stats(self) -> Tuple[int, int, int, int]:
+        """(in-place rhs changes so far, columns of B^-1 they read, pending rows of the update block at the last change, shares of
+        the list in its last launch); relp_rhs_stats."""
+        out = (C.c_int64 * 4)()
+        self._ck(self._lib.relp_rhs_stats(self._h, out))
+        return tuple(int(x) for x in out)
 
     def solve_relaxation(self, max_iters: int = 1 << 40) -> int:
         oc = C.c_int32()
