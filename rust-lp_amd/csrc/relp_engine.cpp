@@ -114,6 +114,8 @@ Switches Switches::read() {
     s.ft_grid_price = given("RELP_FT_GRID_PRICE") ? (num("RELP_FT_GRID_PRICE", 0) != 0 ? 1 : 0) : -1;
     if (given("RELP_LUF_BUMP_CAP")) s.luf_bump_cap = std::max(16, num("RELP_LUF_BUMP_CAP", 0));
     s.luf_dense = std::max(0, std::min(64, num("RELP_LUF_DENSE", 64)));
+    s.luf_lds = num("RELP_LUF_LDS", 1) != 0;
+    s.lu_peel_stacks = num("RELP_LU_PEEL_STACKS", 0) != 0;
     s.dump_basis_set = given("RELP_DUMP_BASIS");
     if (s.dump_basis_set) s.dump_basis = std::getenv("RELP_DUMP_BASIS");
     s.retab_global = num("RELP_RETAB_GLOBAL", 0) != 0;
@@ -1488,7 +1490,7 @@ relp_status_t Engine::refactor_current_basis(std::vector<int32_t>* basis, std::v
     relp_status_t st = build_basis_columns(*basis, &cols);
     if (st) return st;
     std::string msg;
-    if (!lu_factor(lay_.m, cols, &hlu_, &msg)) return RELP_OK;
+    if (!lu_factor(lay_.m, cols, &hlu_, &msg, sw_.lu_peel_stacks)) return RELP_OK;
     if ((st = lu_upload_factors())) return st;
     if ((st = ensure_lu_scratch())) return st;
     *factored = true;
@@ -1710,7 +1712,7 @@ relp_status_t Engine::from_basis(const int32_t* basis_columns) {
         std::vector<std::vector<std::pair<int32_t, double>>> cols;
         if ((st = build_basis_columns(columns, &cols))) return st;
         std::string msg;
-        if (!lu_factor(lay_.m, cols, &hlu_, &msg)) return fail(RELP_E_SINGULAR, "from_basis: " + msg);
+        if (!lu_factor(lay_.m, cols, &hlu_, &msg, sw_.lu_peel_stacks)) return fail(RELP_E_SINGULAR, "from_basis: " + msg);
         if ((st = lu_upload_factors())) return st;
         if ((st = ensure_lu_scratch())) return st;
         const std::vector<double> w = basic_costs(basis, 2, 1.0);

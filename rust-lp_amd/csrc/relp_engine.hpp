@@ -27,6 +27,7 @@
 #include "relp_kernels.h"
 #include "relp_layout.hpp"
 #include "relp_lu.hpp"
+#include "relp_pack.hpp"
 
 namespace relp {
 
@@ -79,6 +80,8 @@ struct Switches {
     int ft_grid_price = -1;                               // RELP_FT_GRID_PRICE (-1: not given)
     int luf_bump_cap = INT32_MAX;                         // RELP_LUF_BUMP_CAP (at least 16 when given)
     int luf_dense = 64;                                   // RELP_LUF_DENSE
+    bool luf_lds = true;                                  // RELP_LUF_LDS
+    bool lu_peel_stacks = false;                          // RELP_LU_PEEL_STACKS
     bool dump_basis_set = false; std::string dump_basis;  // RELP_DUMP_BASIS
     bool retab_global = false;                            // RELP_RETAB_GLOBAL
     int retab_groups = 0;                                 // RELP_RETAB_GROUPS (0: not given)
@@ -318,6 +321,15 @@ class Engine : private EngineQueue {
     relp_status_t lu_load_matrix(const relp_matrix_data_t& md);
     relp_status_t lu_refactor();
     relp_status_t lu_upload_factors();
+    // its steps, in the order of the pieces in the buffer (relp_engine_lu.cpp); LuUpload is what one step hands to the next
+    struct LuUpload;
+    void lu_pack_permutations(LuUpload& u);
+    relp_status_t lu_pack_images(LuUpload& u);
+    void lu_pack_pivot_info(LuUpload& u);
+    void lu_pack_row_schedules(LuUpload& u);
+    relp_status_t lu_copy_to_device(LuUpload& u);
+    relp_status_t lu_install(LuUpload& u);
+    int64_t ft_plan_staging(FtState& f) const;            // stage_bytes, stage[], lds_bytes from the four images; returns the LDS base
     relp_status_t reinvert();
     relp_status_t retabulate(bool adapt_interval = true);   // false: b moves because rhs did (relp_set_right_hand_side), not by drift
     bool retab_done_ = false;                             // the last retabulate() rebuilt the tableau (it keeps the old one otherwise)

@@ -1,6 +1,7 @@
 // relp_engine_lu.cpp -- Engine: the sparse LU engine (RELP_ENGINE_LU): CSC upload, host refactorisation,
 // one pivot.  See relp_engine.hpp and relp_lu.hpp.
 #include "relp_engine_internal.hpp"
+#include "relp_lu_image.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -11,8 +12,6 @@
 #include <initializer_list>
 
 namespace relp {
-
-static_assert(sizeof(EllPassHost) == 16 && sizeof(EllPass) == 16, "the packed pass header is one 16-byte load");
 
 // ------------------------------------------------------------------------------------------------
 // Sparse LU engine: matrix in CSC, factors from the host (relp_lu.cpp), solves on the device
@@ -95,7 +94,7 @@ relp_status_t Engine::lu_factor_downloaded_basis() {
         const relp_status_t fst = lu_basis_flat(basis_ptr_, basis_idx_, basis_val_);
         if (fst) return fst;
         std::string msg;
-        if (!lu_factor_csc(lay_.m, basis_ptr_.data(), basis_idx_.data(), basis_val_.data(), &hlu_, &msg)) return fail(RELP_E_SINGULAR, msg);
+        if (!lu_factor_csc(lay_.m, basis_ptr_.data(), basis_idx_.data(), basis_val_.data(), &hlu_, &msg, sw_.lu_peel_stacks)) return fail(RELP_E_SINGULAR, msg);
         return RELP_OK;
     }
     std::vector<std::vector<std::pair<int32_t, double>>>& cols = basis_cols_;     // (kept: no 790 allocations per refactorisation)
@@ -109,7 +108,7 @@ relp_status_t Engine::lu_factor_downloaded_basis() {
         }
     }
     std::string msg;
-    if (!lu_factor(lay_.m, cols, &hlu_, &msg)) return fail(RELP_E_SINGULAR, msg);
+    if (!lu_factor(lay_.m, cols, &hlu_, &msg, sw_.lu_peel_stacks)) return fail(RELP_E_SINGULAR, msg);
     return RELP_OK;
 }
 
@@ -211,254 +210,222 @@ relp_status_t Engine::lu_refactor_lookahead(int rule, int64_t budget, bool have_
     return RELP_OK;
 }
 
+// What the steps of lu_upload_factors hand on.  Every piece is put into the pinned buffer by the step that makes it, which
+// also says where its device address goes: into dlu / fts, which replace dlu_ / fts_ once everything has arrived.
+struct Engine::LuUpload {
+    // (assembled in pinned memory that lives as long as the engine: the copy to the device is one DMA, not a staged one)
+    Packer<PinnedStore> pk;
+    DeviceLU dlu{};
+    FtState fts;
+    const TriangularSchedule* sch[4];
+    EllPacked ell[4]; EllImageShape shape[4]; int64_t o_ell[4] = {0, 0, 0, 0};
+    std::vector<int32_t> lev_ub;
+    explicit LuUpload(Engine& e) : pk(PinnedStore{e.h_lu_buf_, e.h_lu_cap_}), fts(e.fts_), sch{&e.hlu_.Lf, &e.hlu_.Uf, &e.hlu_.Ub, &e.hlu_.Lb} {}
+};
+
 // hlu_ (host factors + level schedules) -> one device buffer, dlu_ points into it.  Also used by the revised
 // engine's warm start, which forms the rows of B^-1 with the device BTRAN.
 relp_status_t Engine::lu_upload_factors() {
-    // pack everything into one buffer (16-byte aligned pieces): rowperm, colperm, then per schedule the
-    // rows in solve order, the entry indices / values and the level offsets
-    const TriangularSchedule* sch[4] = {&hlu_.Lf, &hlu_.Uf, &hlu_.Ub, &hlu_.Lb};
-    // (assembled in pinned memory that lives as long as the engine: the copy to the device is one DMA, not a staged one)
-    size_t buf_size = 0;
-    bool buf_failed = false;
-    auto put = [&](const void* src, size_t bytes) {
-        const size_t o = buf_size, need = o + (bytes + 15) / 16 * 16;
-        if (need > h_lu_cap_) {
-            const size_t cap = std::max<size_t>(need * 2, size_t(1) << 20);
-            PinnedBuf<char> grown;
-            if (grown.alloc(cap) != hipSuccess) { buf_failed = true; return o; }
-            if (buf_size) std::memcpy(grown, h_lu_buf_, buf_size);
-            h_lu_buf_ = std::move(grown); h_lu_cap_ = cap;
-        }
-        if (bytes) std::memcpy(h_lu_buf_ + o, src, bytes);
-        buf_size = need;
-        return o;
-    };
-    const size_t o_rp = put(hlu_.rowperm.data(), sizeof(int32_t) * lay_.m), o_cp = put(hlu_.colperm.data(), sizeof(int32_t) * lay_.m);
-    // Forrest-Tomlin kernels: original row -> pivot, basis position -> pivot, pivot -> its row in the U / U' schedules
-    std::vector<int32_t> inv_rp(lay_.m), inv_cp(lay_.m), task_uf(lay_.m), task_ub(lay_.m);
-    for (int32_t k = 0; k < lay_.m; ++k) {
+    LuUpload u(*this);
+    relp_status_t st = RELP_OK;
+    lu_pack_permutations(u);
+    if (ft_ && (st = lu_pack_images(u))) return st;
+    lu_pack_pivot_info(u);
+    lu_pack_row_schedules(u);
+    if ((st = lu_copy_to_device(u))) return st;
+    return lu_install(u);
+}
+
+// rowperm, colperm; for the Forrest-Tomlin kernels: original row -> pivot, basis position -> pivot, pivot -> its row in the
+// U / U' schedules
+void Engine::lu_pack_permutations(LuUpload& u) {
+    const int32_t m = lay_.m;
+    u.dlu.m = m; u.dlu.pad_ = 0;
+    u.pk.put(&u.dlu.rowperm, hlu_.rowperm); u.pk.put(&u.dlu.colperm, hlu_.colperm);
+    std::vector<int32_t> inv_rp(m), inv_cp(m), task_uf(m), task_ub(m);
+    for (int32_t k = 0; k < m; ++k) {
         inv_rp[hlu_.rowperm[k]] = k; inv_cp[hlu_.colperm[k]] = k;
         task_uf[hlu_.Uf.level_rows[k]] = k; task_ub[hlu_.Ub.level_rows[k]] = k;
     }
-    const size_t o_irp = put(inv_rp.data(), sizeof(int32_t) * lay_.m), o_icp = put(inv_cp.data(), sizeof(int32_t) * lay_.m);
-    const size_t o_tuf = put(task_uf.data(), sizeof(int32_t) * lay_.m), o_tub = put(task_ub.data(), sizeof(int32_t) * lay_.m);
-    // the four schedules once more for the persistent pivot kernel: consecutive levels fused into groups one pass solves
-    // (relp_lu.hpp: fuse_levels), packed "ELL by pass", one contiguous image each (headers | lvl_pass | rdiag | sval | oval |
-    // rovf | sidx | oidx); rows of U and U' without entries are kept, an update may mask them
-    EllPacked ell[4];
-    size_t o_rpos[4] = {0, 0, 0, 0}, o_tbits[4] = {0, 0, 0, 0};
-    size_t o_ell[4] = {0, 0, 0, 0}, o_via_ptr[4] = {0, 0, 0, 0}, o_via_pos[4] = {0, 0, 0, 0}, o_triv[4] = {0, 0, 0, 0},
-           o_reach[4] = {0, 0, 0, 0}, o_rhs[4] = {0, 0, 0, 0};
-    int32_t rhs_base[4] = {0, 0, 0, 0};
-    std::vector<int32_t> lev_ub(lay_.m, 0);
-    for (int32_t l = 0; l + 1 < (int32_t)hlu_.Ub.level_ptr.size(); ++l)
-        for (int32_t t = hlu_.Ub.level_ptr[l]; t < hlu_.Ub.level_ptr[l + 1]; ++t) lev_ub[hlu_.Ub.level_rows[t]] = l;
-    static_assert(kEllLgShift == kEllLg, "host packing and device decoding of sidx");
-    if (ft_) {
-        const int32_t fuse_cap = sw_.fuse_lanes;       // (RELP_FUSE_LANES, read at create)
-        // (fused schedules read copies of some right-hand sides behind x: ft_rhs_cap_ words of LDS, and of index space)
-        const int32_t cap = ft_rhs_cap_ > 0 ? fuse_cap : 0;
-        const int64_t index_room = ft_big_ ? (int64_t(1) << kEllLgShiftWide) : (int64_t(1) << kEllLgShift);
-        bool uses_rhs[4] = {false, false, false, false};
-        // fusion and packing of the four schedules are independent: U on this thread, U' and L + L' on two helpers (the
-        // refactorisation runs beside the pivot kernel, and what the host takes longer than the kernel's look-ahead the
-        // device waits)
-        auto prepare = [&](int k) {
-            const bool maskable = k == 1 || k == 2;
-            FusedSchedule fs;
-            // (big layout: right-hand-side copies compacted, rows without entries as a list when that saves two passes or more;
-            // all-in-LDS layout: a copy per pivot by one LDS loop and every row a slot, as measured fastest on 25FV47)
-            const int32_t triv_min = ft_big_ ? 512 : 0x7fffffff;
-            fuse_levels(*sch[k], maskable, maskable, cap, &fs);
-            ell_pack(fs, maskable, &ell[k], ft_big_, ft_big_, triv_min);
-            if (ft_big_ && ((int64_t)ell[k].rhs_src.size() > ft_rhs_cap_ || (int64_t)lay_.m + 1 + (int64_t)ell[k].rhs_src.size() > index_room)) {
-                fuse_levels(*sch[k], maskable, maskable, 0, &fs);      // more copies than the layout has room for: level by level
-                ell_pack(fs, maskable, &ell[k], ft_big_, ft_big_, triv_min);
-            }
-            uses_rhs[k] = false;
-            for (int32_t v : fs.s.idx) if (v >= fs.rhs_base) { uses_rhs[k] = true; break; }
-            if (k == 2) lev_ub = fs.start_after;
-            if (uses_rhs[k]) rhs_base[k] = fs.rhs_base;
-        };
-        if (lay_.m >= 256) {
-            host_pool_.run(0, [&] { prepare(2); });
-            host_pool_.run(1, [&] { prepare(0); prepare(3); });
-            prepare(1);
-            host_pool_.wait();
-        } else {
-            for (int k = 0; k < 4; ++k) prepare(k);
+    u.pk.put(&u.fts.inv_rowperm, inv_rp); u.pk.put(&u.fts.inv_colperm, inv_cp);
+    u.pk.put(&u.fts.task_uf, task_uf); u.pk.put(&u.fts.task_ub, task_ub);
+}
+
+// The four schedules once more for the persistent pivot kernel: consecutive levels fused into groups one pass solves
+// (relp_lu.hpp: fuse_levels), packed "ELL by pass", one contiguous image each (relp_lu_image.hpp); rows of U and U' without
+// entries are kept, an update may mask them.  Behind the images what a sweep reads besides them.
+relp_status_t Engine::lu_pack_images(LuUpload& u) {
+    const int32_t m = lay_.m;
+    const int32_t fuse_cap = sw_.fuse_lanes;           // (RELP_FUSE_LANES, read at create)
+    // (fused schedules read copies of some right-hand sides behind x: ft_rhs_cap_ words of LDS, and of index space)
+    const int32_t cap = ft_rhs_cap_ > 0 ? fuse_cap : 0;
+    const int64_t index_room = ft_big_ ? (int64_t(1) << kEllLgShiftWide) : (int64_t(1) << kEllLgShift);
+    for (EllSchedule& d : u.fts.ell) d = EllSchedule{};
+    // fusion and packing of the four schedules are independent: U on this thread, U' and L + L' on two helpers (the
+    // refactorisation runs beside the pivot kernel, and what the host takes longer than the kernel's look-ahead the
+    // device waits)
+    auto prepare = [&](int k) {
+        const bool maskable = k == 1 || k == 2;
+        EllPacked& e = u.ell[k];
+        FusedSchedule fs;
+        // (big layout: right-hand-side copies compacted, rows without entries as a list when that saves two passes or more;
+        // all-in-LDS layout: a copy per pivot by one LDS loop and every row a slot, as measured fastest on 25FV47)
+        const int32_t triv_min = ft_big_ ? 512 : 0x7fffffff;
+        fuse_levels(*u.sch[k], maskable, maskable, cap, &fs);
+        ell_pack(fs, maskable, &e, ft_big_, ft_big_, triv_min);
+        if (ft_big_ && ((int64_t)e.rhs_src.size() > ft_rhs_cap_ || (int64_t)m + 1 + (int64_t)e.rhs_src.size() > index_room)) {
+            fuse_levels(*u.sch[k], maskable, maskable, 0, &fs);      // more copies than the layout has room for: level by level
+            ell_pack(fs, maskable, &e, ft_big_, ft_big_, triv_min);
         }
-        for (int k = 0; k < 4; ++k) {
-            const EllPacked& e = ell[k];
-            std::vector<EllPassHost> hdrs(e.passes);
-            hdrs.resize(hdrs.size() + kEllPadHeaders, EllPassHost{0, 0, 0, 0});       // the kernel reads headers ahead
-            o_ell[k] = put(hdrs.data(), sizeof(EllPassHost) * hdrs.size());
-            put(e.lvl_pass.data(), sizeof(int32_t) * e.lvl_pass.size());
-            put(e.rdiag.data(), sizeof(double) * e.rdiag.size());
-            put(e.sval.data(), sizeof(double) * e.sval.size());
-            put(e.oval.data(), sizeof(double) * e.oval.size());
-            put(e.rovf.data(), sizeof(int32_t) * e.rovf.size());
-            if (ft_big_) { put(e.sidx32.data(), sizeof(uint32_t) * e.sidx32.size()); put(e.oidx32.data(), sizeof(uint32_t) * e.oidx32.size()); }
-            else { put(e.sidx.data(), sizeof(uint16_t) * e.sidx.size()); put(e.oidx.data(), sizeof(uint16_t) * e.oidx.size()); }
-        }
-        for (int k = 1; k <= 2; ++k) {
-            o_via_ptr[k] = put(ell[k].via_ptr.data(), sizeof(int32_t) * ell[k].via_ptr.size());
-            o_via_pos[k] = put(ell[k].via_pos.data(), sizeof(int32_t) * ell[k].via_pos.size());
-        }
-        for (int k = 0; k < 4; ++k) {
-            o_rhs[k] = put(ell[k].rhs_src.data(), sizeof(int32_t) * ell[k].rhs_src.size());
-            o_triv[k] = put(ell[k].triv.data(), sizeof(int32_t) * ell[k].triv.size());
-            if (ft_tier_ >= 2) {                       // layout 2 walks the non-zeros of x: the inverse of rhs_src, `triv` as a bitmap
-                std::vector<int32_t> pos(lay_.m, -1);
-                for (size_t i = 0; i < ell[k].rhs_src.size(); ++i) pos[ell[k].rhs_src[i]] = (int32_t)i;
-                std::vector<uint32_t> tb((size_t)(lay_.m + 31) / 32 + 1, 0u);
-                for (int32_t r : ell[k].triv) tb[(size_t)r >> 5] |= 1u << (r & 31);
-                o_rpos[k] = put(pos.data(), sizeof(int32_t) * pos.size());
-                o_tbits[k] = put(tb.data(), sizeof(uint32_t) * tb.size());
-            }
-            o_reach[k] = put(ell[k].reach.data(), sizeof(int32_t) * ell[k].reach.size());
-        }
+        bool uses_rhs = false;
+        for (int32_t v : fs.s.idx) if (v >= fs.rhs_base) { uses_rhs = true; break; }
+        if (k == 2) u.lev_ub = fs.start_after;
+        u.fts.ell[k].rhs_base = uses_rhs ? fs.rhs_base : 0;
+    };
+    if (m >= 256) {
+        host_pool_.run(0, [&] { prepare(2); });
+        host_pool_.run(1, [&] { prepare(0); prepare(3); });
+        prepare(1);
+        host_pool_.wait();
+    } else {
+        for (int k = 0; k < 4; ++k) prepare(k);
     }
-    const size_t o_lub = put(lev_ub.data(), sizeof(int32_t) * lay_.m);
-    size_t o_pinfo = 0;
-    if (ft_) {
-        std::vector<FtPivotInfo> pinfo(lay_.m);
-        for (int32_t p = 0; p < lay_.m; ++p) {
-            FtPivotInfo& q = pinfo[p];
-            q.u_e0 = hlu_.Uf.ptr[p]; q.u_e1 = hlu_.Uf.ptr[p + 1];
-            const bool v1 = !ell[1].via_ptr.empty(), v2 = !ell[2].via_ptr.empty();
-            q.via_u0 = v1 ? ell[1].via_ptr[p] : 0; q.via_u1 = v1 ? ell[1].via_ptr[p + 1] : 0;
-            q.via_t0 = v2 ? ell[2].via_ptr[p] : 0; q.via_t1 = v2 ? ell[2].via_ptr[p + 1] : 0;
-            q.lev_ub = lev_ub[p]; q.pad_ = 0;
-        }
-        o_pinfo = put(pinfo.data(), sizeof(FtPivotInfo) * pinfo.size());
+    for (int k = 0; k < 4; ++k) {
+        u.shape[k] = ell_image_shape(u.ell[k], m, ft_big_);
+        char* const dst = u.pk.reserve(u.shape[k].layout().total, &u.o_ell[k]);
+        if (dst && !ell_image_write(u.ell[k], u.shape[k], dst)) return fail(RELP_E_STATE, "a packed schedule does not fit its image layout");
     }
-    size_t o_rows[4], o_idx[4], o_val[4], o_lp[4], o_seg[4];
-    int32_t n_seg[4] = {0, 0, 0, 0};
+    for (int k = 1; k <= 2; ++k) {
+        const bool has_via = !u.ell[k].via_ptr.empty();
+        u.pk.put(&u.fts.ell[k].via_ptr, u.ell[k].via_ptr, has_via);
+        u.pk.put(&u.fts.ell[k].via_pos, u.ell[k].via_pos, has_via);
+    }
+    for (int k = 0; k < 4; ++k) {
+        const EllPacked& e = u.ell[k];
+        EllSchedule& d = u.fts.ell[k];
+        u.pk.put(&d.rhs_src, e.rhs_src);
+        u.pk.put(&d.triv, e.triv);
+        d.n_triv = (int32_t)e.triv.size();
+        d.n_rhs = ft_big_ ? (int32_t)e.rhs_src.size() : -1;
+        if (ft_tier_ >= 2) {                           // layout 2 walks the non-zeros of x: the inverse of rhs_src, `triv` as a bitmap
+            std::vector<int32_t> pos(m, -1);
+            for (size_t i = 0; i < e.rhs_src.size(); ++i) pos[e.rhs_src[i]] = (int32_t)i;
+            std::vector<uint32_t> tb((size_t)(m + 31) / 32 + 1, 0u);
+            for (int32_t r : e.triv) tb[(size_t)r >> 5] |= 1u << (r & 31);
+            u.pk.put(&d.rhs_pos, pos);
+            u.pk.put(&d.triv_bits, tb);
+        }
+        u.pk.put(&d.reach, e.reach);
+    }
+    return RELP_OK;
+}
+
+// pivot -> level (group) of its row in the U' schedule, and what an update of a pivot needs in one load
+void Engine::lu_pack_pivot_info(LuUpload& u) {
+    const int32_t m = lay_.m;
+    if (!ft_) {                                            // (the persistent kernel's images: start_after of the fused U', lu_pack_images)
+        u.lev_ub.assign(m, 0);
+        for (int32_t l = 0; l + 1 < (int32_t)hlu_.Ub.level_ptr.size(); ++l)
+            for (int32_t t = hlu_.Ub.level_ptr[l]; t < hlu_.Ub.level_ptr[l + 1]; ++t) u.lev_ub[hlu_.Ub.level_rows[t]] = l;
+    }
+    u.pk.put(&u.fts.lev_ub, u.lev_ub);
+    if (!ft_) return;
+    std::vector<FtPivotInfo> pinfo(m);
+    const std::vector<int32_t>& via_u = u.ell[1].via_ptr;
+    const std::vector<int32_t>& via_t = u.ell[2].via_ptr;
+    for (int32_t p = 0; p < m; ++p) {
+        FtPivotInfo& q = pinfo[p];
+        q.u_e0 = hlu_.Uf.ptr[p]; q.u_e1 = hlu_.Uf.ptr[p + 1];
+        q.via_u0 = via_u.empty() ? 0 : via_u[p]; q.via_u1 = via_u.empty() ? 0 : via_u[p + 1];
+        q.via_t0 = via_t.empty() ? 0 : via_t[p]; q.via_t1 = via_t.empty() ? 0 : via_t[p + 1];
+        q.lev_ub = u.lev_ub[p]; q.pad_ = 0;
+    }
+    u.pk.put(&u.fts.pinfo, pinfo);
+}
+
+// the row-wise schedules of the product-form kernels: rows in solve order, entries, level offsets, runs of levels
+void Engine::lu_pack_row_schedules(LuUpload& u) {
+    DeviceSchedule* ds[4] = {&u.dlu.Lf, &u.dlu.Uf, &u.dlu.Ub, &u.dlu.Lb};
     std::vector<LuRow> rows(lay_.m);
     for (int k = 0; k < 4; ++k) {
-        const TriangularSchedule& t = *sch[k];
-        o_rows[k] = o_idx[k] = o_val[k] = o_lp[k] = o_seg[k] = 0;
+        const TriangularSchedule& t = *u.sch[k];
+        DeviceSchedule& d = *ds[k];
+        d.n_levels = (int32_t)t.level_ptr.size() - 1;
+        d.nnz = (int32_t)t.idx.size();
         if (ft_) {
             // the Forrest-Tomlin kernels solve from the ELL images; of the row-wise schedules they read one thing, the
             // entries of a row of U (the u_bar of an update)
-            if (k == 1) { o_idx[k] = put(t.idx.data(), sizeof(int32_t) * t.idx.size()); o_val[k] = put(t.val.data(), sizeof(double) * t.val.size()); }
+            if (k == 1) { u.pk.put(&d.idx, t.idx); u.pk.put(&d.val, t.val); }
             continue;
         }
         for (int32_t i = 0; i < lay_.m; ++i) {
             const int32_t r = t.level_rows[i];
             rows[i] = LuRow{r, t.ptr[r], t.ptr[r + 1], 0, 1.0 / t.diag[r]};
         }
-        o_rows[k] = put(rows.data(), sizeof(LuRow) * lay_.m);
-        o_idx[k] = put(t.idx.data(), sizeof(int32_t) * t.idx.size());
-        o_val[k] = put(t.val.data(), sizeof(double) * t.val.size());
-        o_lp[k] = put(t.level_ptr.data(), sizeof(int32_t) * t.level_ptr.size());
-        // runs of levels for the pipelined solve: "solo" runs (every level <= 8 rows, at least 2 levels) are walked by one
-        // wavefront without workgroup barriers.  Directly behind level_ptr: the kernel stages all five arrays in one copy.
-        std::vector<int32_t> segs;
-        constexpr int32_t kSoloRows = 8;                   // one pass of eight 8-lane groups
-        const int32_t nlev = (int32_t)t.level_ptr.size() - 1;
-        for (int32_t l = 1; l < nlev;) {
-            const bool narrow = t.level_ptr[l + 1] - t.level_ptr[l] <= kSoloRows;
-            int32_t e = l + 1;
-            while (e < nlev && ((t.level_ptr[e + 1] - t.level_ptr[e] <= kSoloRows) == narrow)) ++e;
-            const bool solo = narrow && e - l >= 2;
-            if (!segs.empty() && !solo && !segs[segs.size() - 1]) segs[segs.size() - 2] = e;      // merge wide runs
-            else { segs.push_back(l); segs.push_back(e); segs.push_back(solo ? 1 : 0); }
-            l = e;
-        }
-        n_seg[k] = (int32_t)segs.size() / 3;
-        o_seg[k] = put(segs.data(), sizeof(int32_t) * segs.size());
+        u.pk.put(&d.rows, rows);
+        u.pk.put(&d.idx, t.idx);
+        u.pk.put(&d.val, t.val);
+        u.pk.put(&d.level_ptr, t.level_ptr);
+        // (directly behind level_ptr: the kernel stages all five arrays in one copy)
+        const std::vector<int32_t> runs = lu_level_runs(t.level_ptr);
+        u.pk.put(&d.seg, runs);
+        d.n_seg = (int32_t)runs.size() / 3;
     }
-    if (buf_failed) return fail(RELP_E_ALLOC, "pinned staging buffer for the factors");
-    if ((int64_t)buf_size > lu_cap_) {
+}
+
+// the pinned buffer -> the device buffer (grown when it is too small); the pieces' addresses -> u.dlu / u.fts
+relp_status_t Engine::lu_copy_to_device(LuUpload& u) {
+    if (u.pk.failed()) return fail(RELP_E_ALLOC, "pinned staging buffer for the factors");
+    const int64_t bytes = u.pk.size();
+    if (bytes > lu_cap_) {
         // (pointer and capacity are cleared before the new allocation: if it fails nothing dangles, and the look-ahead's
-        // restore() below skips an empty buffer)
+        // restore() skips an empty buffer)
         lu_cap_ = 0;
-        const int64_t want = (int64_t)buf_size * 3 / 2 + 256;
+        const int64_t want = bytes * 3 / 2 + 256;
         HIP_TRY(d_lu_buf_.alloc_raw((size_t)want));         // (frees the old buffer first; null if the new one is refused)
         lu_cap_ = want;
     }
-    HIP_TRY(hipMemcpyAsync(d_lu_buf_, h_lu_buf_, buf_size, hipMemcpyHostToDevice, stream_));
-    dlu_.m = lay_.m; dlu_.pad_ = 0;
-    dlu_.rowperm = reinterpret_cast<const int32_t*>(d_lu_buf_ + o_rp);
-    dlu_.colperm = reinterpret_cast<const int32_t*>(d_lu_buf_ + o_cp);
-    DeviceSchedule* ds[4] = {&dlu_.Lf, &dlu_.Uf, &dlu_.Ub, &dlu_.Lb};
-    for (int k = 0; k < 4; ++k) {
-        ds[k]->rows = reinterpret_cast<const LuRow*>(d_lu_buf_ + o_rows[k]);
-        ds[k]->idx = reinterpret_cast<const int32_t*>(d_lu_buf_ + o_idx[k]);
-        ds[k]->val = reinterpret_cast<const double*>(d_lu_buf_ + o_val[k]);
-        ds[k]->level_ptr = reinterpret_cast<const int32_t*>(d_lu_buf_ + o_lp[k]);
-        ds[k]->n_levels = (int32_t)sch[k]->level_ptr.size() - 1;
-        ds[k]->nnz = (int32_t)sch[k]->idx.size();
-        ds[k]->seg = reinterpret_cast<const int32_t*>(d_lu_buf_ + o_seg[k]);
-        ds[k]->n_seg = n_seg[k]; ds[k]->pad_ = 0;
-    }
+    HIP_TRY(hipMemcpyAsync(d_lu_buf_, h_lu_buf_, (size_t)bytes, hipMemcpyHostToDevice, stream_));
+    u.pk.bind(d_lu_buf_);
     HIP_TRY(hipStreamSynchronize(stream_));             // (the pinned buffer is rewritten by the next refactorisation)
-    if (ft_) {
-        if (ft_tier_ >= 2 && fts_.m != lay_.m) {           // rows were removed: the bitmaps saved between launches describe another m
-            const int32_t reset[4] = {-1, -1, 0, 0};
-            HIP_TRY(hipMemcpyAsync(fts_.nzc, reset, sizeof reset, hipMemcpyHostToDevice, stream_));
-            HIP_TRY(hipStreamSynchronize(stream_));
-        }
-        fts_.m = lay_.m;
-        fts_.inv_rowperm = reinterpret_cast<const int32_t*>(d_lu_buf_ + o_irp);
-        fts_.inv_colperm = reinterpret_cast<const int32_t*>(d_lu_buf_ + o_icp);
-        fts_.task_uf = reinterpret_cast<const int32_t*>(d_lu_buf_ + o_tuf);
-        fts_.task_ub = reinterpret_cast<const int32_t*>(d_lu_buf_ + o_tub);
-        fts_.lev_ub = reinterpret_cast<const int32_t*>(d_lu_buf_ + o_lub);
-        fts_.pinfo = reinterpret_cast<const FtPivotInfo*>(d_lu_buf_ + o_pinfo);
-        // what is left of the CU's LDS after the work vectors stages one schedule image at a time
-        const int64_t base = (int64_t)ft_lds_base_bytes(lay_.m, ft_tcap_, ft_eta_cap_, ft_tier_, ft_rhs_cap_);
-        const int64_t idx_bytes = ft_big_ ? 4 : 2;
-        fts_.stage_bytes = (int32_t)std::max<int64_t>(0, kFtLdsBudget - base);
-        int64_t need = 0;
-        auto up16 = [](int64_t b) { return (b + 15) / 16 * 16; };
-        for (int k = 0; k < 4; ++k) {
-            const EllPacked& e = ell[k];
-            EllSchedule& d = fts_.ell[k];
-            const int64_t np = (int64_t)e.passes.size(), nlv = (int64_t)e.lvl_pass.size(), nln = (int64_t)e.lanes(),
-                          nov = (int64_t)e.overflow();
-            char* q = d_lu_buf_ + o_ell[k];
-            char* const q0 = q;
-            d.passes = reinterpret_cast<const EllPass*>(q); q += up16(16 * (np + kEllPadHeaders));
-            d.lvl_pass = reinterpret_cast<const int32_t*>(q); q += up16(4 * nlv);
-            d.rdiag = reinterpret_cast<double*>(q); q += up16(8 * ((int64_t)lay_.m + 1));
-            d.sval = reinterpret_cast<double*>(q); q += up16(8 * nln);
-            d.oval = reinterpret_cast<const double*>(q); q += up16(8 * nov);
-            d.rovf = reinterpret_cast<const int32_t*>(q); q += up16(4 * (int64_t)e.rovf.size());
-            d.sidx = reinterpret_cast<const uint16_t*>(q); q += up16(idx_bytes * nln);      // (uint32_t when FtState::big)
-            d.oidx = reinterpret_cast<const uint16_t*>(q); q += up16(idx_bytes * nov);
-            const int64_t total = q - q0;
-            d.n_passes = (int32_t)np; d.n_levels = (int32_t)nlv - 1; d.m = lay_.m; d.n_lanes = (int32_t)nln; d.n_ovf = (int32_t)nov;
-            d.bytes = (int32_t)total;
-            d.rhs_base = rhs_base[k];
-            d.n_triv = (int32_t)e.triv.size();
-            d.triv = reinterpret_cast<const int32_t*>(d_lu_buf_ + o_triv[k]);
-            d.reach = reinterpret_cast<const int32_t*>(d_lu_buf_ + o_reach[k]);
-            d.rhs_src = reinterpret_cast<const int32_t*>(d_lu_buf_ + o_rhs[k]);
-            d.n_rhs = ft_big_ ? (int32_t)e.rhs_src.size() : -1; d.pad_ = 0;
-            d.rhs_pos = ft_tier_ >= 2 ? reinterpret_cast<const int32_t*>(d_lu_buf_ + o_rpos[k]) : nullptr;
-            d.triv_bits = ft_tier_ >= 2 ? reinterpret_cast<const uint32_t*>(d_lu_buf_ + o_tbits[k]) : nullptr;
-            const bool has_via = !e.via_ptr.empty();
-            d.via_ptr = has_via ? reinterpret_cast<const int32_t*>(d_lu_buf_ + o_via_ptr[k]) : nullptr;
-            d.via_pos = has_via ? reinterpret_cast<const int32_t*>(d_lu_buf_ + o_via_pos[k]) : nullptr;
-            fts_.stage[k] = total <= fts_.stage_bytes ? 1 : 0;
-            if (fts_.stage[k]) need = std::max(need, total);
-        }
-        if (ft_tier_ >= 2)                                 // (layout 2 copies the pass headers of an image that is not staged: sweep())
-            for (int k = 0; k < 4; ++k) {
-                const int64_t hb = 16 * ((int64_t)fts_.ell[k].n_passes + kEllPadHeaders);
-                if (!fts_.stage[k] && hb <= fts_.stage_bytes) need = std::max(need, hb);
-            }
-        fts_.lds_bytes = (int32_t)(base + need);
-        if (sw_.debug && lu_refactors_ % 60 == 59)
-            for (int k = 0; k < 4; ++k)
-                std::fprintf(stderr, "[relp] schedule %d: %d levels, %d passes, %d lanes (%d entries), image %d bytes, staged %d (stage area %d, base %lld)\n",
-                             k, fts_.ell[k].n_levels, fts_.ell[k].n_passes, fts_.ell[k].n_lanes, (int)sch[k]->idx.size(),
-                             fts_.ell[k].bytes, fts_.stage[k], fts_.stage_bytes, (long long)base);
-    }
     return RELP_OK;
+}
+
+relp_status_t Engine::lu_install(LuUpload& u) {
+    dlu_ = u.dlu;
+    if (!ft_) return RELP_OK;
+    if (ft_tier_ >= 2 && fts_.m != lay_.m) {               // rows were removed: the bitmaps saved between launches describe another m
+        const int32_t reset[4] = {-1, -1, 0, 0};
+        HIP_TRY(hipMemcpyAsync(fts_.nzc, reset, sizeof reset, hipMemcpyHostToDevice, stream_));
+        HIP_TRY(hipStreamSynchronize(stream_));
+    }
+    fts_ = u.fts;
+    fts_.m = lay_.m;
+    for (int k = 0; k < 4; ++k) ell_image_view(d_lu_buf_ + u.o_ell[k], u.shape[k], &fts_.ell[k]);
+    const int64_t base = ft_plan_staging(fts_);
+    if (sw_.debug && lu_refactors_ % 60 == 59)
+        for (int k = 0; k < 4; ++k)
+            std::fprintf(stderr, "[relp] schedule %d: %d levels, %d passes, %d lanes (%d entries), image %d bytes, staged %d (stage area %d, base %lld)\n",
+                         k, fts_.ell[k].n_levels, fts_.ell[k].n_passes, fts_.ell[k].n_lanes, (int)u.sch[k]->idx.size(),
+                         fts_.ell[k].bytes, fts_.stage[k], fts_.stage_bytes, (long long)base);
+    return RELP_OK;
+}
+
+// What is left of the CU's LDS after the work vectors stages one schedule image at a time: which of f.ell fit, and the
+// dynamic LDS the kernels ask for.
+int64_t Engine::ft_plan_staging(FtState& f) const {
+    const int64_t base = (int64_t)ft_lds_base_bytes(lay_.m, ft_tcap_, ft_eta_cap_, ft_tier_, ft_rhs_cap_);
+    f.stage_bytes = (int32_t)std::max<int64_t>(0, kFtLdsBudget - base);
+    int64_t need = 0;
+    for (int k = 0; k < 4; ++k) {
+        f.stage[k] = f.ell[k].bytes <= f.stage_bytes ? 1 : 0;
+        // (layout 2 copies the pass headers of an image that is not staged: sweep())
+        const int64_t hb = 16 * ((int64_t)f.ell[k].n_passes + kEllPadHeaders);
+        if (f.stage[k]) need = std::max<int64_t>(need, f.ell[k].bytes);
+        else if (ft_tier_ >= 2 && hb <= f.stage_bytes) need = std::max(need, hb);
+    }
+    f.lds_bytes = (int32_t)(base + need);
+    return base;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -517,49 +484,35 @@ relp_status_t Engine::ft_plan_and_alloc() {
         std::fprintf(stderr, "[relp] persistent pivot kernel: m %d, layout %s, %d right-hand-side copies, dense tail %d, LDS base %zu bytes\n",
                      lay_.m, ft_tier_ >= 2 ? "nothing per row in LDS" : ft_big_ ? "big" : "all-in-LDS", ft_rhs_cap_, ft_tcap_,
                      ft_lds_base_bytes(lay_.m, ft_tcap_, ft_eta_cap_, ft_tier_, ft_rhs_cap_));
-    const int64_t tc = ft_tcap_, ldt = tc + 1, m = lay_.m, nwp = kFtWaves + 1;
-    int64_t o = 0;
-    auto take = [&](int64_t bytes) { const int64_t at = o; o += round_up(bytes, 16); return at; };
+    const int64_t tc = ft_tcap_, ldt = tc + 1, m = lay_.m, nwp = kFtWaves + 1, eta = ft_eta_cap_;
+    const bool t1 = ft_tier_ >= 1, t2 = ft_tier_ >= 2;
+    fts_ = FtState{};
+    Carver c;
     // (what a refactorisation clears to 0 first, then what it clears to -1, then the rest: two memsets per reset)
-    const int64_t o_hdr = take(16), o_sp = take(4 * tc), o_lv = take(4 * tc), o_tc = take(8 * tc * ldt), o_eo = take(4 * tc * nwp),
-                  o_so = take(4 * tc * nwp), o_pv = take(4 * tc), o_ts = take(4 * m), o_ei = take(4 * (int64_t)ft_eta_cap_),
-                  o_ev = take(8 * (int64_t)ft_eta_cap_), o_si = take(4 * tc * m), o_sv = take(8 * tc * m), o_spike = take(8 * m), o_prof = take(8 * 32),
-                  o_journal = take(8 * tc), o_spw = take(8 * m), o_xw = take(ft_tier_ >= 2 ? 8 * (m + 1 + ft_rhs_cap_) : 0),
-                  o_cm = take(ft_tier_ >= 1 ? 8 * ((m + 63) / 64 + 1) : 0), o_nzi = take(ft_tier_ >= 1 ? 4 * m : 0),
-                  o_nzv = take(ft_tier_ >= 1 ? 8 * m : 0), o_rhoi = take(ft_tier_ >= 2 ? 4 * m : 0), o_nzc = take(16),
-                  o_bits = take(ft_tier_ >= 2 ? kFtBitmapBytes + 1024 : 0);
-    ft_zero_bytes_ = o_pv - o_hdr; ft_ones_bytes_ = o_ei - o_pv;
-    HIP_TRY(d_ft_buf_.alloc_raw((size_t)o));
-    HIP_TRY(hipMemset(d_ft_buf_, 0, (size_t)o));
+    const int64_t o_zero = c.take(&fts_.hdr, 16);
+    c.take(&fts_.slot_pivot, 4 * tc); c.take(&fts_.slot_live, 4 * tc); c.take(&fts_.TC, 8 * tc * ldt);
+    c.take(&fts_.eta_off, 4 * tc * nwp); c.take(&fts_.spk_off, 4 * tc * nwp);
+    const int64_t o_ones = c.take(&fts_.slot_prev, 4 * tc);
+    c.take(&fts_.tslot, 4 * m);
+    const int64_t o_rest = c.take(&fts_.eta_idx, 4 * eta);
+    c.take(&fts_.eta_val, 8 * eta); c.take(&fts_.spk_idx, 4 * tc * m); c.take(&fts_.spk_val, 8 * tc * m); c.take(&fts_.spike, 8 * m);
+    c.take(&fts_.prof, 8 * 32); c.take(&fts_.journal, 8 * tc); c.take(&fts_.sp_work, 8 * m);
+    c.take_if(t2, &fts_.x_work, 8 * (m + 1 + ft_rhs_cap_));
+    c.take_if(t1, &fts_.chunk_mask, 8 * ((m + 63) / 64 + 1)); c.take_if(t1, &fts_.nz_idx, 4 * m); c.take_if(t1, &fts_.nz_val, 8 * m);
+    c.take_if(t2, &fts_.rho_idx, 4 * m);
+    c.take(&fts_.nzc, 16);
+    c.take_if(t2, &fts_.bits_save, kFtBitmapBytes + 1024);
+    ft_zero_bytes_ = o_ones - o_zero; ft_ones_bytes_ = o_rest - o_ones;
+    HIP_TRY(d_ft_buf_.alloc_raw((size_t)c.size()));
+    HIP_TRY(hipMemset(d_ft_buf_, 0, (size_t)c.size()));
+    c.bind(d_ft_buf_);
     HIP_TRY(h_ft_hdr_.alloc(4 * sizeof(int32_t)));
     std::memset(h_ft_hdr_, 0, 4 * sizeof(int32_t));
     {   // the kernel's report in mapped host memory; without it (allocation refused) the copies below do the same job
         if (h_mirror_.alloc(sizeof(FtMirror) + sizeof(int32_t) * (size_t)lay_.m, true) == hipSuccess) std::memset(h_mirror_, 0, sizeof(FtMirror));
         else (void)hipGetLastError();
     }
-    fts_ = FtState{};
     fts_.m = lay_.m; fts_.tcap = ft_tcap_; fts_.ldt = (int32_t)ldt; fts_.eta_cap = ft_eta_cap_;
-    fts_.hdr = reinterpret_cast<int32_t*>(d_ft_buf_ + o_hdr);
-    fts_.slot_pivot = reinterpret_cast<int32_t*>(d_ft_buf_ + o_sp);
-    fts_.slot_prev = reinterpret_cast<int32_t*>(d_ft_buf_ + o_pv);
-    fts_.slot_live = reinterpret_cast<int32_t*>(d_ft_buf_ + o_lv);
-    fts_.tslot = reinterpret_cast<int32_t*>(d_ft_buf_ + o_ts);
-    fts_.TC = reinterpret_cast<double*>(d_ft_buf_ + o_tc);
-    fts_.eta_off = reinterpret_cast<int32_t*>(d_ft_buf_ + o_eo);
-    fts_.spk_off = reinterpret_cast<int32_t*>(d_ft_buf_ + o_so);
-    fts_.eta_idx = reinterpret_cast<int32_t*>(d_ft_buf_ + o_ei);
-    fts_.eta_val = reinterpret_cast<double*>(d_ft_buf_ + o_ev);
-    fts_.spk_idx = reinterpret_cast<int32_t*>(d_ft_buf_ + o_si);
-    fts_.spk_val = reinterpret_cast<double*>(d_ft_buf_ + o_sv);
-    fts_.spike = reinterpret_cast<double*>(d_ft_buf_ + o_spike);
-    fts_.sp_work = reinterpret_cast<double*>(d_ft_buf_ + o_spw);
-    fts_.x_work = ft_tier_ >= 2 ? reinterpret_cast<double*>(d_ft_buf_ + o_xw) : nullptr;
-    fts_.chunk_mask = ft_tier_ >= 1 ? reinterpret_cast<unsigned long long*>(d_ft_buf_ + o_cm) : nullptr;
-    fts_.nz_idx = ft_tier_ >= 1 ? reinterpret_cast<int32_t*>(d_ft_buf_ + o_nzi) : nullptr;
-    fts_.nz_val = ft_tier_ >= 1 ? reinterpret_cast<double*>(d_ft_buf_ + o_nzv) : nullptr;
-    fts_.rho_idx = ft_tier_ >= 2 ? reinterpret_cast<int32_t*>(d_ft_buf_ + o_rhoi) : nullptr;
-    fts_.nzc = reinterpret_cast<int32_t*>(d_ft_buf_ + o_nzc);
-    fts_.bits_save = ft_tier_ >= 2 ? reinterpret_cast<uint32_t*>(d_ft_buf_ + o_bits) : nullptr;
     {   // (pb.alpha / pb.rho unknown, no bitmaps saved yet)
         const int32_t reset[4] = {-1, -1, 0, 0};
         HIP_TRY(hipMemcpy(fts_.nzc, reset, sizeof reset, hipMemcpyHostToDevice));
@@ -569,8 +522,6 @@ relp_status_t Engine::ft_plan_and_alloc() {
         fts_.hyper = sw_.ft_hyper;
         hyper_forced_ = sw_.ft_hyper_set;
     }
-    fts_.prof = reinterpret_cast<long long*>(d_ft_buf_ + o_prof);
-    fts_.journal = reinterpret_cast<int32_t*>(d_ft_buf_ + o_journal);
     // refactor when this many updates are pending (lower_upper/mod.rs:199-202 refactors when updates.len() > 10, i.e.
     // relp_config_t.update_block = 11 reproduces the reference's cadence)
     fts_.max_updates = cfg_.update_block < 0 ? ft_tcap_ : std::max(1, std::min(cfg_.update_block, ft_tcap_));
@@ -581,70 +532,55 @@ relp_status_t Engine::ft_plan_and_alloc() {
     return ft_build_price_ell();
 }
 
-// k-major PRICE copy of the structural columns (relp_kernels.h: PriceEll; rebuilt when rows are removed)
-relp_status_t Engine::ft_build_price_ell() {
-    const int64_t ns = std::max(lay_.nr_normal, 1);
-    std::vector<uint16_t> idx((size_t)kPriceSlots * ns, 0);
-    std::vector<double> val((size_t)kPriceSlots * ns, 0.0);
-    std::vector<int32_t> longs, very_long;
-    for (int32_t p = 0; p < lay_.nr_normal; ++p) {
-        const int64_t n = hc_ptr_[p + 1] - hc_ptr_[p];
-        for (int64_t k = 0; k < std::min<int64_t>(n, kPriceSlots); ++k) {
-            idx[(size_t)k * ns + p] = (uint16_t)hc_idx_[hc_ptr_[p] + k]; val[(size_t)k * ns + p] = hc_val_[hc_ptr_[p] + k];
-        }
-        if (n > kPriceSlots) {
-            idx[p] |= kPriceLongFlag;
-            (n > kPriceLongSlots ? very_long : longs).push_back(p);
-        }
-    }
-    const int64_t nl = std::max<int64_t>((int64_t)longs.size(), 1);
-    std::vector<uint16_t> lidx((size_t)kPriceLongSlots * nl, 0);
-    std::vector<double> lval((size_t)kPriceLongSlots * nl, 0.0);
+// One table pair of the PRICE copy with elements of type T, from the row indices or the values of the CSC columns: slot k of
+// column p at [k * ns + p] (the first kPriceSlots entries of every column), and the long columns once more, complete, at
+// [k * n_long + i].  Padding slots are 0.
+template <class T, class S>
+static void price_tables(const std::vector<int64_t>& ptr, const std::vector<S>& src, const std::vector<int32_t>& longs,
+                         std::vector<T>* tab, std::vector<T>* ltab) {
+    const int64_t n = (int64_t)ptr.size() - 1, ns = std::max<int64_t>(n, 1), nl = std::max<int64_t>((int64_t)longs.size(), 1);
+    tab->assign((size_t)kPriceSlots * ns, T(0));
+    ltab->assign((size_t)kPriceLongSlots * nl, T(0));
+    for (int64_t p = 0; p < n; ++p)
+        for (int64_t k = 0; k < std::min<int64_t>(ptr[p + 1] - ptr[p], kPriceSlots); ++k) (*tab)[(size_t)(k * ns + p)] = (T)src[ptr[p] + k];
     for (size_t i = 0; i < longs.size(); ++i) {
         const int32_t p = longs[i];
-        for (int64_t k = 0; k < hc_ptr_[p + 1] - hc_ptr_[p]; ++k) {
-            lidx[(size_t)k * nl + i] = (uint16_t)hc_idx_[hc_ptr_[p] + k]; lval[(size_t)k * nl + i] = hc_val_[hc_ptr_[p] + k];
-        }
+        for (int64_t k = 0; k < ptr[p + 1] - ptr[p]; ++k) (*ltab)[(size_t)(k * nl) + i] = (T)src[ptr[p] + k];
     }
-    std::vector<char> buf;
-    auto put = [&](const void* src, size_t bytes) {
-        const size_t o = buf.size();
-        buf.resize(o + (std::max<size_t>(bytes, 1) + 15) / 16 * 16);
-        if (bytes) std::memcpy(buf.data() + o, src, bytes);
-        return o;
-    };
-    const size_t o_val = put(val.data(), val.size() * 8), o_lval = put(lval.data(), lval.size() * 8);
-    const size_t o_idx = put(idx.data(), idx.size() * 2), o_lidx = put(lidx.data(), lidx.size() * 2);
-    const size_t o_long = put(longs.data(), longs.size() * 4), o_vl = put(very_long.data(), very_long.size() * 4);
-    std::vector<uint16_t> long_of((size_t)ns, 0xFFFF);
+}
+
+// k-major PRICE copy of the structural columns (relp_kernels.h: PriceEll; rebuilt when rows are removed)
+relp_status_t Engine::ft_build_price_ell() {
+    std::vector<int32_t> longs, very_long, more;           // columns beyond kPriceSlots entries: up to kPriceLongSlots, beyond, both
+    for (int32_t p = 0; p < lay_.nr_normal; ++p) {
+        const int64_t n = hc_ptr_[p + 1] - hc_ptr_[p];
+        if (n <= kPriceSlots) continue;
+        more.push_back(p);
+        (n > kPriceLongSlots ? very_long : longs).push_back(p);
+    }
+    std::vector<uint16_t> long_of((size_t)std::max(lay_.nr_normal, 1), 0xFFFF);
     if (longs.size() < 0xFFFF) for (size_t i = 0; i < longs.size(); ++i) long_of[longs[i]] = (uint16_t)i;
-    const size_t o_lof = put(long_of.data(), long_of.size() * 2);
-    size_t o_idx32 = 0, o_lidx32 = 0;
+    std::vector<double> val, lval;
+    std::vector<uint16_t> idx, lidx;
+    std::vector<uint32_t> idx32, lidx32;
+    price_tables(hc_ptr_, hc_val_, longs, &val, &lval);
+    price_tables(hc_ptr_, hc_idx_, longs, &idx, &lidx);
+    for (int32_t p : more) idx[p] |= kPriceLongFlag;
+    pe_ = PriceEll{};
+    Packer<VectorStore> pk(VectorStore{}, 1);
+    pk.put(&pe_.val, val); pk.put(&pe_.lval, lval);
+    pk.put(&pe_.idx, idx); pk.put(&pe_.lidx, lidx);
+    pk.put(&pe_.long_cols, longs); pk.put(&pe_.very_long, very_long);
+    pk.put(&pe_.long_of, long_of);
     if (ft_tier_ >= 2) {                                   // the same two tables with 32-bit row indices (bit 31 = long column)
-        std::vector<uint32_t> w(idx.size(), 0), lw(lidx.size(), 0);
-        for (int32_t p = 0; p < lay_.nr_normal; ++p) {
-            const int64_t n = hc_ptr_[p + 1] - hc_ptr_[p];
-            for (int64_t k = 0; k < std::min<int64_t>(n, kPriceSlots); ++k) w[(size_t)k * ns + p] = (uint32_t)hc_idx_[hc_ptr_[p] + k];
-            if (n > kPriceSlots) w[p] |= kPriceLongFlag32;
-        }
-        for (size_t i = 0; i < longs.size(); ++i) {
-            const int32_t p = longs[i];
-            for (int64_t k = 0; k < hc_ptr_[p + 1] - hc_ptr_[p]; ++k) lw[(size_t)k * nl + i] = (uint32_t)hc_idx_[hc_ptr_[p] + k];
-        }
-        o_idx32 = put(w.data(), w.size() * 4); o_lidx32 = put(lw.data(), lw.size() * 4);
+        price_tables(hc_ptr_, hc_idx_, longs, &idx32, &lidx32);
+        for (int32_t p : more) idx32[p] |= kPriceLongFlag32;
+        pk.put(&pe_.idx32, idx32); pk.put(&pe_.lidx32, lidx32);
     }
-    HIP_TRY(d_pe_buf_.alloc_raw(buf.size()));              // (frees the copy of before a row removal)
-    HIP_TRY(hipMemcpy(d_pe_buf_, buf.data(), buf.size(), hipMemcpyHostToDevice));
-    pe_.val = reinterpret_cast<const double*>(d_pe_buf_ + o_val);
-    pe_.lval = reinterpret_cast<const double*>(d_pe_buf_ + o_lval);
-    pe_.idx = reinterpret_cast<const uint16_t*>(d_pe_buf_ + o_idx);
-    pe_.lidx = reinterpret_cast<const uint16_t*>(d_pe_buf_ + o_lidx);
-    pe_.long_cols = reinterpret_cast<const int32_t*>(d_pe_buf_ + o_long);
-    pe_.very_long = reinterpret_cast<const int32_t*>(d_pe_buf_ + o_vl);
-    pe_.long_of = reinterpret_cast<const uint16_t*>(d_pe_buf_ + o_lof);
-    pe_.idx32 = ft_tier_ >= 2 ? reinterpret_cast<const uint32_t*>(d_pe_buf_ + o_idx32) : nullptr;
-    pe_.lidx32 = ft_tier_ >= 2 ? reinterpret_cast<const uint32_t*>(d_pe_buf_ + o_lidx32) : nullptr;
     pe_.n_long = (int32_t)longs.size(); pe_.n_very_long = (int32_t)very_long.size();
+    HIP_TRY(d_pe_buf_.alloc_raw((size_t)pk.size()));       // (frees the copy of before a row removal)
+    HIP_TRY(hipMemcpy(d_pe_buf_, pk.data(), (size_t)pk.size(), hipMemcpyHostToDevice));
+    pk.bind(d_pe_buf_);
     return RELP_OK;
 }
 

@@ -3,7 +3,7 @@
 // from (built at create, after a row removal and at the phase switch), and the buffers.
 #include "relp_engine_internal.hpp"
 #include "relp_lu_factor_core.h"
-#include "relp_lu_schedule_core.h"
+#include "relp_lu_image.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -54,53 +54,59 @@ relp_status_t Engine::luf_prepare() {
                                                                   4 * std::min<int64_t>((int64_t)S.nb_cap * S.nb_cap, int64_t(1) << 21));
     S.cap = (int32_t)arena_cap;
     const int32_t nt = luf_threads();
-    int64_t o = 0;
-    auto take = [&](int64_t bytes) { const int64_t at = o; o += round_up(std::max<int64_t>(bytes, 16), 16); return at; };
-    const int64_t o_rptr = take(4 * ((int64_t)m + 1)), o_rcol = take(4 * nnz), o_rval = take(8 * nnz), o_art = take(4 * (int64_t)m),
-                  o_wr = take(4 * (int64_t)std::max<int32_t>(lay_.wrapped_na, 1));
-    const int64_t o_posp = take(4 * ((int64_t)nprov + 1)), o_posa = take(4 * ((int64_t)na + 1));
-    int64_t o_m[13];
-    for (auto& v : o_m) v = take(4 * (int64_t)m);       // wrow_pos rcount ccount claim claim2 list list2 piv brow bcol lrow lcol (+1 spare)
-    const int64_t o_part = take(4 * ((int64_t)nt + 2));
-    int64_t o_nb[11];
-    for (auto& v : o_nb) v = take(4 * (int64_t)S.nb_cap);     // rbeg rlen rcap ract cact bcc bstep_row bstep_col cpiv prank acc
-    int64_t o_nb8[5];
-    for (auto& v : o_nb8) v = take(8 * (int64_t)std::max(S.nb_cap, 512));     // (>= 512: the dense finish keeps 8 x 64 partials there)    // pval cmax rowmark colbest cprio
-    const int64_t o_ecol = take(4 * arena_cap), o_eval = take(8 * arena_cap);
-    const int64_t o_ltr = take(4 * arena_cap), o_lts = take(4 * arena_cap), o_ltv = take(8 * arena_cap), o_ltp = take(4 * ((int64_t)S.nb_cap + 1)),
-                  o_lto = take(4 * arena_cap), o_cnt = take(512);
-    const int64_t o_red = take(8 * 8), o_sc = take(64);
-    const int32_t dense_cap = sw_.luf_dense;                                // RELP_LUF_DENSE: rows of the dense finish (<= 64; 0 = off)
-    const int64_t o_dense = take(8 * (int64_t)64 * 64), o_dint = take(4 * 8 * 64);
-    const int64_t o_utr = take(4 * arena_cap), o_utc = take(4 * arena_cap), o_utv = take(8 * arena_cap), o_vw = take(4 * ((int64_t)m + 2)),
-                  o_vtmp = take(4 * arena_cap);
-    const int64_t o_status = take(32), o_rowperm = take(4 * (int64_t)m), o_colperm = take(4 * (int64_t)m), o_rstep = take(4 * (int64_t)m),
-                  o_cstep = take(4 * (int64_t)m), o_diag = take(8 * (int64_t)m);
-    int64_t o_tp[4], o_ti[4], o_tv[4];
-    for (int q = 0; q < 4; ++q) { o_tp[q] = take(4 * ((int64_t)m + 1)); o_ti[q] = take(4 * (int64_t)S.cap); o_tv[q] = take(8 * (int64_t)S.cap); }
+    const int64_t R = m, NB = S.nb_cap, NB8 = std::max(S.nb_cap, 512), AC = arena_cap;
     // the schedules: one set of work arrays, one image arena, lists and descriptors per schedule (four workgroups build them side by side)
     const int32_t nlev_cap = m + 1;
     S.x_cap = (int32_t)std::min<int64_t>(INT32_MAX / 8, 4 * (int64_t)S.cap / 3 + 2 * (int64_t)m + 64);       // expanded rows of the fused groups
     S.pool_cap = (int32_t)std::min<int64_t>(INT32_MAX / 8, 2 * (int64_t)S.x_cap);
     S.img_cap = 64 + 40 * ((int64_t)S.x_cap + 2 * (int64_t)m + 64) + 16 * ((int64_t)m + 8);
-    const int64_t n_words = m / 32 + 3;
-    struct SchedOff { int64_t m4[10], lv[6], bits[2], xs, xc, xv0, xvn, pool, tmp, tmp2, ovf, sc, img, desc, triv, reach, lof, viap, viapos, rhs_src, rhs_pos, tbits; } so[4];
+    const int64_t n_words = m / 32 + 3, LV = (int64_t)nlev_cap + 2, XC = S.x_cap, PC = S.pool_cap;
+    const bool bits = ft_tier_ >= 2;
+    S.M = LufMatrix{}; S.W = LufWork{}; S.O = LufOut{};
+    LufMatrix& A = S.M; LufWork& W = S.W; LufOut& O = S.O;
+    Carver c(16);                                          // (every piece at least 16 bytes)
+    const int64_t o_rptr = c.take(&A.rptr, 4 * (R + 1)), o_rcol = c.take(&A.rcol, 4 * nnz), o_rval = c.take(&A.rval, 8 * nnz),
+                  o_art = c.take(&A.art_of_row, 4 * R), o_wr = c.take(&A.wrapped_row, 4 * (int64_t)std::max<int32_t>(lay_.wrapped_na, 1));
+    c.take(&W.pos_p, 4 * ((int64_t)nprov + 1)); c.take(&W.pos_a, 4 * ((int64_t)na + 1));
+    c.take(&W.wrow_pos, 4 * R); c.take(&W.rcount, 4 * R); c.take(&W.ccount, 4 * R); c.take(&W.claim, 4 * R); c.take(&W.claim2, 4 * R);
+    c.take(&W.list, 4 * R); c.take(&W.list2, 4 * R); c.take(&W.piv, 4 * R); c.take(&W.brow, 4 * R); c.take(&W.bcol, 4 * R);
+    c.take(&W.lrow, 4 * R); c.take(&W.lcol, 4 * R); c.take(4 * R);      // (+ one spare)
+    c.take(&W.part, 4 * ((int64_t)nt + 2));
+    c.take(&W.rbeg, 4 * NB); c.take(&W.rlen, 4 * NB); c.take(&W.rcap, 4 * NB); c.take(&W.ract, 4 * NB); c.take(&W.cact, 4 * NB); c.take(&W.bcc, 4 * NB);
+    c.take(&W.bstep_row, 4 * NB); c.take(&W.bstep_col, 4 * NB); c.take(&W.cpiv, 4 * NB); c.take(&W.prank, 4 * NB); c.take(&W.acc, 4 * NB);
+    // (>= 512 words each: the dense finish keeps 8 x 64 partials there)
+    c.take(&W.pval, 8 * NB8); c.take(&W.cmax, 8 * NB8); c.take(&W.rowmark, 8 * NB8); c.take(&W.colbest, 8 * NB8); c.take(&W.cprio, 8 * NB8);
+    c.take(&W.ecol, 4 * AC); c.take(&W.eval, 8 * AC);
+    c.take(&W.lt_row, 4 * AC); c.take(&W.lt_step, 4 * AC); c.take(&W.lt_val, 8 * AC); c.take(&W.lt_ptr, 4 * (NB + 1)); c.take(&W.lt_ord, 4 * AC);
+    c.take(&W.counters, 512); c.take(&W.red, 8 * 8); c.take(&W.scalars, 64);
+    c.take(&W.dense, 8 * (int64_t)64 * 64); c.take(&W.dint, 4 * 8 * 64);
+    c.take(&W.ut_row, 4 * AC); c.take(&W.ut_col, 4 * AC); c.take(&W.ut_val, 8 * AC); c.take(&W.vw, 4 * (R + 2)); c.take(&W.vtmp, 4 * AC);
+    c.take(&O.status, 32); c.take(&O.rowperm, 4 * R); c.take(&O.colperm, 4 * R); c.take(&O.row_step, 4 * R); c.take(&O.col_step, 4 * R);
+    c.take(&O.diag, 8 * R);
+    for (LufTriangle* t : {&O.Lf, &O.Uf, &O.Ub, &O.Lb}) { c.take(&t->ptr, 4 * (R + 1)); c.take(&t->idx, 4 * (int64_t)S.cap); c.take(&t->val, 8 * (int64_t)S.cap); }
     for (int q = 0; q < 4; ++q) {
-        SchedOff& f = so[q];
-        for (auto& v : f.m4) v = take(4 * (int64_t)m);      // indeg lev order grp xbeg xlen lg loff rhs_id (+1 spare)
-        for (auto& v : f.lv) v = take(4 * ((int64_t)nlev_cap + 2));
-        for (auto& v : f.bits) v = take(4 * n_words);
-        f.xs = take(4 * (int64_t)S.x_cap); f.xc = take(8 * (int64_t)S.x_cap); f.xv0 = take(4 * (int64_t)S.x_cap); f.xvn = take(4 * (int64_t)S.x_cap);
-        f.pool = take(4 * (int64_t)S.pool_cap);
-        f.tmp = take(4 * ((int64_t)m + 2)); f.tmp2 = take(4 * ((int64_t)m + 2)); f.ovf = take(4 * ((int64_t)m + 1)); f.sc = take(128);
-        f.img = take(S.img_cap); f.desc = take(4 * LUF_D_WORDS); f.triv = take(4 * (int64_t)m); f.reach = take(4 * (int64_t)m); f.lof = take(4 * (int64_t)m);
-        f.viap = take(4 * ((int64_t)m + 1)); f.viapos = take(4 * (int64_t)S.pool_cap); f.rhs_src = take(4 * (int64_t)m); f.rhs_pos = take(4 * (int64_t)m);
-        f.tbits = take(4 * n_words);
+        LufSchedWork& w = S.SW[q];
+        LufSchedOut& out = S.sout[q];
+        w = LufSchedWork{}; out = LufSchedOut{};
+        c.take(&w.indeg, 4 * R); c.take(&w.lev, 4 * R); c.take(&w.order, 4 * R); c.take(&w.grp, 4 * R); c.take(&w.xbeg, 4 * R); c.take(&w.xlen, 4 * R);
+        c.take(&w.lg, 4 * R); c.take(&w.loff, 4 * R); c.take(&w.rhs_id, 4 * R); c.take(4 * R);      // (+ one spare)
+        c.take(&w.lvl_ptr, 4 * LV); c.take(&w.lvl_grp, 4 * LV); c.take(&w.grp_lvl0, 4 * LV); c.take(&w.grp_lane0, 4 * LV); c.take(&w.grp_pass0, 4 * LV);
+        c.take(&w.grp_lanes, 4 * LV);
+        c.take(&w.bits0, 4 * n_words); c.take(&w.bits1, 4 * n_words);
+        c.take(&w.x_src, 4 * XC); c.take(&w.x_coef, 8 * XC); c.take(&w.x_v0, 4 * XC); c.take(&w.x_vn, 4 * XC);
+        c.take(&w.pool, 4 * PC);
+        c.take(&w.tmp, 4 * (R + 2)); c.take(&w.tmp2, 4 * (R + 2)); c.take(&w.ovf_off, 4 * (R + 1)); c.take(&w.sc, 128);
+        c.take(&out.image, S.img_cap); c.take(&out.desc, 4 * LUF_D_WORDS); c.take(&out.triv, 4 * R); c.take(&out.reach, 4 * R); c.take(&out.level_of, 4 * R);
+        c.take(&out.via_ptr, 4 * (R + 1)); c.take(&out.via_pos, 4 * PC); c.take(&out.rhs_src, 4 * R);
+        c.take(&out.rhs_pos, 4 * R, bits); c.take(&out.triv_bits, 4 * n_words, bits);
+        w.x_cap = S.x_cap; w.pool_cap = S.pool_cap; w.nlev_cap = nlev_cap;
+        out.image_cap = S.img_cap; out.via_cap = S.pool_cap;
     }
-    const int64_t o_pinfo = take((int64_t)sizeof(FtPivotInfo) * m);
-    HIP_TRY(S.d_buf.alloc_raw((size_t)o));
-    HIP_TRY(hipMemset(S.d_buf, 0, (size_t)o));
+    c.take(&S.pinfo, (int64_t)sizeof(FtPivotInfo) * R);
+    HIP_TRY(S.d_buf.alloc_raw((size_t)c.size()));
+    HIP_TRY(hipMemset(S.d_buf, 0, (size_t)c.size()));
     char* const B = S.d_buf;
+    c.bind(B);
     HIP_TRY(hipMemcpy(B + o_rptr, rcount.data(), 4 * ((size_t)m + 1), hipMemcpyHostToDevice));
     if (nnz) {
         HIP_TRY(hipMemcpy(B + o_rcol, rcol.data(), 4 * (size_t)nnz, hipMemcpyHostToDevice));
@@ -108,34 +114,12 @@ relp_status_t Engine::luf_prepare() {
     }
     HIP_TRY(hipMemcpy(B + o_art, art_of_row.data(), 4 * (size_t)m, hipMemcpyHostToDevice));
     if (lay_.wrapped_na > 0) HIP_TRY(hipMemcpy(B + o_wr, lay_.column_to_row.data(), 4 * (size_t)lay_.wrapped_na, hipMemcpyHostToDevice));
-    auto I32 = [&](int64_t at) { return reinterpret_cast<int32_t*>(B + at); };
-    auto F64 = [&](int64_t at) { return reinterpret_cast<double*>(B + at); };
-    S.M = LufMatrix{};
-    S.M.m = m; S.M.na = na; S.M.n_provider = nprov;
-    S.M.csc = csc(); S.M.ct = table();
-    S.M.rptr = I32(o_rptr); S.M.rcol = I32(o_rcol); S.M.rval = F64(o_rval); S.M.art_of_row = I32(o_art);
-    S.M.wrapped_na = lay_.wrapped_na; S.M.wrapped_row = I32(o_wr);
-    LufWork& W = S.W;
-    W.pos_p = I32(o_posp); W.pos_a = I32(o_posa);
-    W.wrow_pos = I32(o_m[0]); W.rcount = I32(o_m[1]); W.ccount = I32(o_m[2]); W.claim = I32(o_m[3]); W.claim2 = I32(o_m[4]);
-    W.list = I32(o_m[5]); W.list2 = I32(o_m[6]); W.piv = I32(o_m[7]); W.brow = I32(o_m[8]); W.bcol = I32(o_m[9]);
-    W.lrow = I32(o_m[10]); W.lcol = I32(o_m[11]); W.part = I32(o_part);
+    A.m = m; A.na = na; A.n_provider = nprov;
+    A.csc = csc(); A.ct = table();
+    A.wrapped_na = lay_.wrapped_na;
     W.nb_cap = S.nb_cap;
-    W.rbeg = I32(o_nb[0]); W.rlen = I32(o_nb[1]); W.rcap = I32(o_nb[2]); W.ract = I32(o_nb[3]); W.cact = I32(o_nb[4]); W.bcc = I32(o_nb[5]);
-    W.bstep_row = I32(o_nb[6]); W.bstep_col = I32(o_nb[7]); W.cpiv = I32(o_nb[8]); W.prank = I32(o_nb[9]); W.acc = I32(o_nb[10]);
-    auto U64 = [&](int64_t at) { return reinterpret_cast<unsigned long long*>(B + at); };
-    W.pval = F64(o_nb8[0]); W.cmax = U64(o_nb8[1]); W.rowmark = U64(o_nb8[2]); W.colbest = U64(o_nb8[3]); W.cprio = U64(o_nb8[4]);
-    W.ecol = I32(o_ecol); W.eval = F64(o_eval); W.arena_cap = (int32_t)arena_cap;
-    W.lt_row = I32(o_ltr); W.lt_step = I32(o_lts); W.lt_val = F64(o_ltv); W.lt_cap = (int32_t)arena_cap; W.lt_ptr = I32(o_ltp); W.lt_ord = I32(o_lto);
-    W.counters = I32(o_cnt); W.red = U64(o_red);
-    W.scalars = I32(o_sc);
-    W.dense = F64(o_dense); W.dint = I32(o_dint); W.dense_cap = dense_cap;
-    W.ut_row = I32(o_utr); W.ut_col = I32(o_utc); W.ut_val = F64(o_utv); W.vw = I32(o_vw); W.vtmp = I32(o_vtmp); W.vtmp_cap = (int32_t)arena_cap;
-    LufOut& O = S.O;
-    O.status = I32(o_status); O.rowperm = I32(o_rowperm); O.colperm = I32(o_colperm); O.row_step = I32(o_rstep); O.col_step = I32(o_cstep);
-    O.diag = F64(o_diag);
-    LufTriangle* tri[4] = {&O.Lf, &O.Uf, &O.Ub, &O.Lb};
-    for (int q = 0; q < 4; ++q) { tri[q]->ptr = I32(o_tp[q]); tri[q]->idx = I32(o_ti[q]); tri[q]->val = F64(o_tv[q]); }
+    W.arena_cap = W.lt_cap = W.vtmp_cap = (int32_t)arena_cap;
+    W.dense_cap = sw_.luf_dense;                          // RELP_LUF_DENSE: rows of the dense finish (<= 64; 0 = off)
     O.cap = S.cap;
     {
         const bool wide = ft_big_;
@@ -144,23 +128,11 @@ relp_status_t Engine::luf_prepare() {
         // (fused schedules read copies of some right-hand sides behind x: ft_rhs_cap_ words of the layout; RELP_FUSE_LANES, read at create)
         const int32_t fuse = ft_rhs_cap_ > 0 ? sw_.fuse_lanes : 0;
         for (int q = 0; q < 4; ++q) {
-            const SchedOff& f = so[q];
             const bool maskable = q == 1 || q == 2;
             S.sin[q] = LufSchedIn{m, tri4[q]->ptr, tri4[q]->idx, tri4[q]->val, trt4[q]->ptr, trt4[q]->idx, maskable ? O.diag : nullptr, maskable ? 1 : 0,
                                   wide ? 1 : 0, wide ? 512 : 0x7fffffff, fuse, ft_rhs_cap_, ft_tier_ >= 2 ? 1 : 0};
-            LufSchedWork& w = S.SW[q];
-            w = LufSchedWork{};
-            w.indeg = I32(f.m4[0]); w.lev = I32(f.m4[1]); w.order = I32(f.m4[2]); w.grp = I32(f.m4[3]); w.xbeg = I32(f.m4[4]); w.xlen = I32(f.m4[5]);
-            w.lg = I32(f.m4[6]); w.loff = I32(f.m4[7]); w.rhs_id = I32(f.m4[8]);
-            w.lvl_ptr = I32(f.lv[0]); w.lvl_grp = I32(f.lv[1]); w.grp_lvl0 = I32(f.lv[2]); w.grp_lane0 = I32(f.lv[3]); w.grp_pass0 = I32(f.lv[4]); w.grp_lanes = I32(f.lv[5]);
-            w.bits0 = reinterpret_cast<uint32_t*>(B + f.bits[0]); w.bits1 = reinterpret_cast<uint32_t*>(B + f.bits[1]);
-            w.x_src = I32(f.xs); w.x_coef = F64(f.xc); w.x_v0 = I32(f.xv0); w.x_vn = I32(f.xvn); w.x_cap = S.x_cap; w.pool = I32(f.pool); w.pool_cap = S.pool_cap;
-            w.tmp = I32(f.tmp); w.tmp2 = I32(f.tmp2); w.ovf_off = I32(f.ovf); w.sc = I32(f.sc); w.nlev_cap = nlev_cap;
-            S.sout[q] = LufSchedOut{B + f.img, S.img_cap, I32(f.desc), I32(f.triv), I32(f.reach), I32(f.lof), I32(f.viap), I32(f.viapos), S.pool_cap,
-                                    I32(f.rhs_src), ft_tier_ >= 2 ? I32(f.rhs_pos) : nullptr, ft_tier_ >= 2 ? reinterpret_cast<uint32_t*>(B + f.tbits) : nullptr};
         }
     }
-    S.pinfo = reinterpret_cast<FtPivotInfo*>(B + o_pinfo);
     S.dirty = false;
     S.key[0] = lay_.m; S.key[1] = lay_.nr_artificial; S.key[2] = phase_; S.key[3] = lay_.wrapped_na;
     return RELP_OK;
@@ -184,8 +156,7 @@ relp_status_t Engine::lu_factor_on_device(int32_t* device_status) {
     S.M.csc = csc(); S.M.ct = table();                  // (pointers may have been re-allocated)
     int32_t status[8] = {0}, desc[4][LUF_D_WORDS] = {};
     // (the bump's working set in LDS when it fits, RELP_LUF_LDS=0 keeps it in L2; an arena that overflows in LDS: once more from L2)
-    static const bool lds_env = !(std::getenv("RELP_LUF_LDS") && std::atoi(std::getenv("RELP_LUF_LDS")) == 0);
-    for (int attempt = lds_env ? 0 : 1; attempt < 2; ++attempt) {
+    for (int attempt = sw_.luf_lds ? 0 : 1; attempt < 2; ++attempt) {
         launch_lu_factor(S.M, d_basis_, S.W, S.O, stream_, attempt == 0);
         if (resident) launch_lu_schedules(S.sin, S.SW, S.sout, S.O.status, S.pinfo, stream_);
         HIP_TRY(hipMemcpyAsync(status, S.O.status, sizeof status, hipMemcpyDeviceToHost, stream_));
@@ -236,32 +207,21 @@ relp_status_t Engine::lu_factor_on_device(int32_t* device_status) {
     fts_.m = m;
     fts_.inv_rowperm = S.O.row_step; fts_.inv_colperm = S.O.col_step; fts_.task_uf = S.O.row_step; fts_.task_ub = S.O.row_step;
     fts_.lev_ub = S.sout[2].level_of; fts_.pinfo = S.pinfo;
-    const int64_t base = (int64_t)ft_lds_base_bytes(m, ft_tcap_, ft_eta_cap_, ft_tier_, ft_rhs_cap_);
-    fts_.stage_bytes = (int32_t)std::max<int64_t>(0, kFtLdsBudget - base);
-    int64_t need = 0;
     for (int q = 0; q < 4; ++q) {
         const int32_t* d = desc[q];
-        const LufImageLayout L = luf_image_layout(m, d[LUF_D_PASSES], d[LUF_D_LEVELS], d[LUF_D_LANES], d[LUF_D_OVF], ft_big_);
-        char* const img = S.sout[q].image;
         EllSchedule& e = fts_.ell[q];
         e = EllSchedule{};
-        e.passes = reinterpret_cast<const EllPass*>(img + L.passes); e.lvl_pass = reinterpret_cast<const int32_t*>(img + L.lvl_pass);
-        e.rdiag = reinterpret_cast<double*>(img + L.rdiag); e.sval = reinterpret_cast<double*>(img + L.sval);
-        e.oval = reinterpret_cast<const double*>(img + L.oval); e.rovf = reinterpret_cast<const int32_t*>(img + L.rovf);
-        e.sidx = reinterpret_cast<const uint16_t*>(img + L.sidx); e.oidx = reinterpret_cast<const uint16_t*>(img + L.oidx);
+        ell_image_view(S.sout[q].image, EllImageShape{m, d[LUF_D_PASSES], d[LUF_D_LEVELS], d[LUF_D_LANES], d[LUF_D_OVF], ft_big_}, &e);
         const bool maskable = q == 1 || q == 2;
         e.via_ptr = maskable ? S.sout[q].via_ptr : nullptr; e.via_pos = maskable ? S.sout[q].via_pos : nullptr;
-        e.n_passes = d[LUF_D_PASSES]; e.n_levels = d[LUF_D_LEVELS]; e.m = m; e.n_lanes = d[LUF_D_LANES]; e.n_ovf = d[LUF_D_OVF];
-        e.bytes = d[LUF_D_BYTES]; e.rhs_base = d[LUF_D_USES_RHS] ? m + 1 : 0;
+        e.rhs_base = d[LUF_D_USES_RHS] ? m + 1 : 0;
         e.n_triv = d[LUF_D_TRIV]; e.triv = S.sout[q].triv; e.reach = S.sout[q].reach; e.rhs_src = S.sout[q].rhs_src;
         e.n_rhs = ft_big_ ? std::max(d[LUF_D_NRHS], 0) : -1;
         e.rhs_pos = S.sout[q].rhs_pos; e.triv_bits = S.sout[q].triv_bits;
-        fts_.stage[q] = e.bytes <= fts_.stage_bytes ? 1 : 0;
-        if (fts_.stage[q]) need = std::max<int64_t>(need, e.bytes);
         ds[q]->n_levels = d[LUF_D_LEVELS];
         hs[q]->level_ptr.assign((size_t)d[LUF_D_KAHN_LEVELS] + 1, 0);     // (lu_stats reports the level counts)
     }
-    fts_.lds_bytes = (int32_t)(base + need);
+    ft_plan_staging(fts_);
     return RELP_OK;
 }
 

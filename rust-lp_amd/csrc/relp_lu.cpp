@@ -105,12 +105,28 @@ struct ListArena {
 
 }  // namespace
 
+std::vector<int32_t> lu_level_runs(const std::vector<int32_t>& level_ptr) {
+    std::vector<int32_t> runs;
+    const int32_t nlev = (int32_t)level_ptr.size() - 1;
+    auto narrow_at = [&](int32_t l) { return level_ptr[l + 1] - level_ptr[l] <= kSoloRows; };
+    for (int32_t l = 1; l < nlev;) {
+        const bool narrow = narrow_at(l);
+        int32_t e = l + 1;
+        while (e < nlev && narrow_at(e) == narrow) ++e;
+        const bool solo = narrow && e - l >= 2;
+        if (!runs.empty() && !solo && !runs.back()) runs[runs.size() - 2] = e;      // merge wide runs
+        else { runs.push_back(l); runs.push_back(e); runs.push_back(solo ? 1 : 0); }
+        l = e;
+    }
+    return runs;
+}
+
 void lu_levels_from_rows(int32_t m, const std::vector<double>& diag, bool ascending, TriangularSchedule* s) {
     finish_schedule(m, diag, ascending, s);
 }
 
 bool lu_factor(int32_t m, const std::vector<std::vector<std::pair<int32_t, double>>>& columns, LUFactors* out,
-               std::string* err) {
+               std::string* err, bool peel_stacks) {
     std::vector<int64_t> ptr((size_t)m + 1, 0);
     for (int32_t j = 0; j < m; ++j) ptr[(size_t)j + 1] = ptr[j] + (int64_t)columns[j].size();
     std::vector<int32_t> idx((size_t)ptr[m]);
@@ -119,12 +135,13 @@ bool lu_factor(int32_t m, const std::vector<std::vector<std::pair<int32_t, doubl
         int64_t o = ptr[j];
         for (auto& e : columns[j]) { idx[(size_t)o] = e.first; val[(size_t)o] = e.second; ++o; }
     }
-    return lu_factor_csc(m, ptr.data(), idx.data(), val.data(), out, err);
+    return lu_factor_csc(m, ptr.data(), idx.data(), val.data(), out, err, peel_stacks);
 }
 
 // The same on a flat copy of the basis (column j = entries [ptr[j], ptr[j + 1]) of idx / val): what the engine hands over at
 // every refactorisation -- 64,000 separately allocated column vectors were a cache miss each, twice per factorisation.
-bool lu_factor_csc(int32_t m, const int64_t* cptr, const int32_t* cidx, const double* cval, LUFactors* out, std::string* err) {
+bool lu_factor_csc(int32_t m, const int64_t* cptr, const int32_t* cidx, const double* cval, LUFactors* out, std::string* err,
+                   bool peel_stacks) {
     // active submatrix, row major: entries (column, value) of row i at rc / rv [rows.beg[i], + rows.len[i]); colrows: the rows
     // that (may) hold an entry of a column (stale members are dropped whenever the list is scanned for its maximum)
     const size_t nnz = (size_t)cptr[m];
@@ -186,7 +203,6 @@ bool lu_factor_csc(int32_t m, const int64_t* cptr, const int32_t* cidx, const do
     col_single.reserve(4 * (size_t)m); row_single.reserve(4 * (size_t)m);
     for (int32_t j = 0; j < m; ++j) if (ccount[j] == 1) col_single.push_back(j);
     for (int32_t i = 0; i < m; ++i) if (rows.len[i] == 1) row_single.push_back(i);
-    static const bool peel_stacks = std::getenv("RELP_LU_PEEL_STACKS") && std::atoi(std::getenv("RELP_LU_PEEL_STACKS")) != 0;
     int64_t col_head = 0, col_end = (int64_t)col_single.size(), row_head = 0, row_end = 0;
     bool peel_cols = true;
     // the sparsest active row / column of the bump, ties to the lower index

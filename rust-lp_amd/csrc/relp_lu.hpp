@@ -41,14 +41,24 @@ struct LUFactors {
 
 // columns[j] = sorted sparse column j of the basis matrix B (m columns over m rows).
 // Returns false (and a message) when B is numerically singular.
+// peel_stacks: the singletons in the order of the first rounds (columns while there are any, then rows, newest first), for
+// measurements (RELP_LU_PEEL_STACKS, relp_engine.hpp: Switches).
 bool lu_factor(int32_t m, const std::vector<std::vector<std::pair<int32_t, double>>>& columns, LUFactors* out,
-               std::string* err);
+               std::string* err, bool peel_stacks = false);
 // the same from a flat copy of the columns (column j = entries [ptr[j], ptr[j + 1]) of idx / val)
-bool lu_factor_csc(int32_t m, const int64_t* ptr, const int32_t* idx, const double* val, LUFactors* out, std::string* err);
+bool lu_factor_csc(int32_t m, const int64_t* ptr, const int32_t* idx, const double* val, LUFactors* out, std::string* err,
+                   bool peel_stacks = false);
 
 // Levels for a schedule whose rows (ptr / idx / val) are given, e.g. by the device factorisation (relp_lu_factor_core.h):
 // fills diag, level_ptr, level_rows.  ascending: the dependencies of a row have smaller indices.
 void lu_levels_from_rows(int32_t m, const std::vector<double>& diag, bool ascending, TriangularSchedule* s);
+
+// Runs of levels for the pipelined solve of the product-form engine (relp_kernels.h: DeviceSchedule::seg), from level 1 on, as
+// triples (begin, end, solo).  A level of at most kSoloRows rows is narrow; a run of at least 2 narrow levels is "solo": one
+// wavefront walks it without workgroup barriers.  Everything else is wide, and adjacent wide runs are one run (a single narrow
+// level between two wide ones joins them).
+constexpr int32_t kSoloRows = 8;         // one pass of eight 8-lane groups
+std::vector<int32_t> lu_level_runs(const std::vector<int32_t>& level_ptr);
 
 // Level fusion by local inversion.  A basis factor of an LP has dozens of levels of a handful of rows each, and on the device a
 // level costs a fixed ~800 clocks whatever it holds, so consecutive levels are merged into GROUPS that one

@@ -368,6 +368,7 @@ __device__ __forceinline__ EllImage<kWide> ell_stage(const EllSchedule& s, char*
 #pragma unroll
             for (int u = 0; u < 8; ++u) { const int i = min(i0 + u * NT, n16 - 1); dst[i] = buf[u]; }
         }
+        // (the offsets of relp_lu_schedule_core.h: luf_image_layout, spelled out; the two must agree)
         char* q = base;
         im.passes = reinterpret_cast<const EllPass*>(q); q += lu_up16(16LL * (s.n_passes + kEllPadHeaders));
         im.lvl_pass = reinterpret_cast<const int32_t*>(q); q += lu_up16(4LL * (s.n_levels + 1));

@@ -60,6 +60,7 @@ struct LufSchedOut {
 
 LUF_FN int64_t luf_up16(int64_t b) { return (b + 15) / 16 * 16; }
 // byte offsets of the arrays inside an image with the given counts
+// (relp_lu_device.h: ell_stage spells the same offsets out for the staged copy; the two must agree)
 struct LufImageLayout { int64_t passes, lvl_pass, rdiag, sval, oval, rovf, sidx, oidx, total; };
 LUF_FN LufImageLayout luf_image_layout(int32_t m, int32_t n_passes, int32_t n_levels, int32_t n_lanes, int32_t n_ovf, bool wide) {
     LufImageLayout L;

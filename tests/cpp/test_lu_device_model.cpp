@@ -1,7 +1,8 @@
 // The device-side LU factorisation (rust-lp_amd/csrc/relp_lu_factor_core.h) compiled for the HOST: the
 // very code the kernel k_lu_factor runs, with its parallel loops as plain loops.  Checked on the reference's factorisation
 // cases (decomposition/mod.rs:301-491) and on seeded LP-like bases -- with structural, slack, bound and artificial columns --
-// against P B Q = L U, against dense solves and against the host factorisation lu_factor.  No GPU.
+// against P B Q = L U, against dense solves and against the host factorisation lu_factor.  The image the HOST packs for the
+// same factors (fuse_levels + ell_pack + relp_lu_image.hpp) is executed by the same image_solve.  No GPU.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -12,6 +13,7 @@
 
 #include "relp_lu.hpp"
 #include "relp_lu_factor_core.h"
+#include "relp_lu_image.hpp"
 #include "relp_lu_schedule_core.h"
 
 using namespace relp;
@@ -265,6 +267,107 @@ static void image_solve(const char* img, const int32_t* desc, int32_t m, bool wi
     for (int32_t i = 0; i < m; ++i) xm[i] = x[i];
 }
 
+// The host's image of the rows in T: fuse_levels + ell_pack written by ell_image_write, for 16-bit slots and for wide slots with
+// compacted right-hand-side copies and listed trivial rows, fused and level by level.  Every array of the EllPacked lies at the
+// offset luf_image_layout gives it, the padding is zero, and image_solve on it gives the plain solve's result.
+// expect_overflow: 1 / 0 = the unfused packing must / must not have an overflow list, -1 = either.
+static void check_host_image(const char* name, const char* which, const LufTriangle& T, const double* diag, bool ascending, int32_t m, std::mt19937_64& rng,
+                             int expect_overflow = -1) {
+    TriangularSchedule t;
+    t.ptr.assign(T.ptr, T.ptr + m + 1); t.idx.assign(T.idx, T.idx + T.ptr[m]); t.val.assign(T.val, T.val + T.ptr[m]);
+    const bool maskable = diag != nullptr;
+    lu_levels_from_rows(m, diag ? std::vector<double>(diag, diag + m) : std::vector<double>(m, 1.0), ascending, &t);
+    for (int wide = 0; wide < 2; ++wide)
+        for (int cap : {0, 256}) {
+            if (!wide && 2 * m + 2 >= (1 << kEllLg)) continue;
+            FusedSchedule fs; EllPacked e;
+            fuse_levels(t, maskable, maskable, cap, &fs);
+            if (wide) ell_pack(fs, maskable, &e, true, true, 4);
+            else ell_pack(fs, maskable, &e);
+            const EllImageShape shape = ell_image_shape(e, m, wide != 0);
+            const LufImageLayout L = shape.layout();
+            const int64_t isz = wide ? 4 : 2;
+            struct Piece { const char* what; int64_t at; const void* src; int64_t bytes; };
+            const Piece pieces[8] = {
+                {"passes", L.passes, e.passes.data(), 16 * (int64_t)e.passes.size()}, {"lvl_pass", L.lvl_pass, e.lvl_pass.data(), 4 * (int64_t)e.lvl_pass.size()},
+                {"rdiag", L.rdiag, e.rdiag.data(), 8 * (int64_t)e.rdiag.size()}, {"sval", L.sval, e.sval.data(), 8 * (int64_t)e.sval.size()},
+                {"oval", L.oval, e.oval.data(), 8 * (int64_t)e.oval.size()}, {"rovf", L.rovf, e.rovf.data(), 4 * (int64_t)e.rovf.size()},
+                {"sidx", L.sidx, wide ? (const void*)e.sidx32.data() : (const void*)e.sidx.data(), isz * (int64_t)e.lanes()},
+                {"oidx", L.oidx, wide ? (const void*)e.oidx32.data() : (const void*)e.oidx.data(), isz * (int64_t)e.overflow()}};
+            // the layout is the eight arrays, each padded to 16 bytes, one behind the other (the headers with kEllPadHeaders empty ones)
+            int64_t sum = 0;
+            for (int i = 0; i < 8; ++i) {
+                const int64_t bytes = pieces[i].bytes + (i == 0 ? 16 * kEllPadHeaders : 0);
+                CHECK(pieces[i].at == sum, "%s %s wide %d cap %d: %s at %lld, not at %lld", name, which, wide, cap, pieces[i].what, (long long)pieces[i].at, (long long)sum);
+                sum += (bytes + 15) / 16 * 16;
+            }
+            CHECK(L.total == sum, "%s %s wide %d cap %d: image of %lld bytes, arrays of %lld", name, which, wide, cap, (long long)L.total, (long long)sum);
+            if (L.total != sum) continue;
+            if (cap == 0 && expect_overflow >= 0) {
+                CHECK((e.overflow() > 0) == (expect_overflow == 1), "%s %s wide %d: %zu overflow entries", name, which, wide, e.overflow());
+                if (expect_overflow == 1) CHECK(e.rovf.size() == 2 * (size_t)m && L.sidx - L.rovf == (8 * (int64_t)m + 15) / 16 * 16, "%s %s wide %d: rovf is not 2 m words", name, which, wide);
+                else CHECK(e.rovf.empty() && L.sidx == L.oval, "%s %s wide %d: sidx does not follow oval directly", name, which, wide);
+            }
+            std::vector<char> image((size_t)L.total, (char)0x5a);          // (the writer must not rely on a cleared buffer)
+            const bool written = ell_image_write(e, shape, image.data());
+            CHECK(written, "%s %s wide %d cap %d: ell_image_write refused the packing", name, which, wide, cap);
+            if (!written) continue;
+            std::vector<char> is_data((size_t)L.total, 0);
+            for (const Piece& pc : pieces) {
+                CHECK(pc.bytes == 0 || std::memcmp(image.data() + pc.at, pc.src, (size_t)pc.bytes) == 0, "%s %s wide %d cap %d: %s is not at its offset", name, which, wide, cap, pc.what);
+                std::fill(is_data.begin() + pc.at, is_data.begin() + pc.at + pc.bytes, 1);
+            }
+            bool pad_zero = true;
+            for (int64_t i = 0; i < L.total; ++i) if (!is_data[(size_t)i] && image[(size_t)i] != 0) pad_zero = false;
+            CHECK(pad_zero, "%s %s wide %d cap %d: padding (or an empty header) is not zero", name, which, wide, cap);
+            // the view addresses the same arrays
+            EllSchedule d{};
+            ell_image_view(image.data(), shape, &d);
+            CHECK((const char*)d.passes == image.data() + L.passes && (const char*)d.lvl_pass == image.data() + L.lvl_pass && (const char*)d.rdiag == image.data() + L.rdiag &&
+                  (const char*)d.sval == image.data() + L.sval && (const char*)d.oval == image.data() + L.oval && (const char*)d.rovf == image.data() + L.rovf &&
+                  (const char*)d.sidx == image.data() + L.sidx && (const char*)d.oidx == image.data() + L.oidx && d.bytes == L.total && d.m == m &&
+                  d.n_passes == (int32_t)e.passes.size() && d.n_levels == (int32_t)e.lvl_pass.size() - 1 && d.n_lanes == (int32_t)e.lanes() && d.n_ovf == (int32_t)e.overflow(),
+                  "%s %s wide %d cap %d: ell_image_view", name, which, wide, cap);
+            // executed like the device-built image
+            int32_t desc[LUF_D_WORDS] = {0};
+            desc[LUF_D_PASSES] = shape.n_passes; desc[LUF_D_LEVELS] = shape.n_levels; desc[LUF_D_LANES] = shape.n_lanes; desc[LUF_D_OVF] = shape.n_ovf;
+            desc[LUF_D_BYTES] = (int32_t)L.total; desc[LUF_D_TRIV] = (int32_t)e.triv.size(); desc[LUF_D_NRHS] = wide ? (int32_t)e.rhs_src.size() : -1;
+            for (int32_t v : fs.s.idx) if (v >= fs.rhs_base) desc[LUF_D_USES_RHS] = 1;
+            CHECK(fs.rhs_base == m + 1, "%s %s: right-hand-side copies from %d on", name, which, fs.rhs_base);
+            std::vector<double> b(m), want, got;
+            for (auto& v : b) v = (rng() % 3 == 0) ? (double)((int)(rng() % 13) - 6) : 0.0;
+            if (m <= 5) for (auto& v : b) v = (double)((int)(rng() % 13) + 1);
+            want = b; got = b;
+            plain_solve(T, diag, ascending, m, want);
+            image_solve(image.data(), desc, m, wide != 0, e.triv.data(), e.rhs_src.data(), got, 0);
+            CHECK(max_rel(got, want) <= 1e-9, "%s %s wide %d cap %d: host image solve differs by %.3e", name, which, wide, cap, max_rel(got, want));
+        }
+}
+
+// hand-made rows of U (row k reads later pivots, solved from the back): the smallest images of each kind
+static void check_host_image_shapes(std::mt19937_64& rng) {
+    auto rows_of = [&](int32_t m, const std::vector<std::vector<int32_t>>& reads, const char* name, int expect_overflow) {
+        std::vector<int32_t> ptr{0}, idx; std::vector<double> val, diag(m);
+        for (int32_t k = 0; k < m; ++k) {
+            for (int32_t j : reads[k]) { idx.push_back(j); val.push_back((double)((int)(rng() % 7) + 1) * 0.25); }
+            ptr.push_back((int32_t)idx.size());
+            diag[k] = (double)((int)(rng() % 5) + 2);
+        }
+        // (never read through empty vectors: the factor has no entries when every row is trivial)
+        idx.push_back(0); val.push_back(0.0);
+        const LufTriangle T{ptr.data(), idx.data(), val.data()};
+        check_host_image(name, "U", T, diag.data(), false, m, rng, expect_overflow);      // trivial rows kept as slots (16-bit) and listed (wide)
+        if (ptr[m] == 0) check_host_image(name, "L'", T, nullptr, false, m, rng, expect_overflow);      // unit diagonal: an image with no lanes
+    };
+    rows_of(1, {{}}, "m = 1", 0);
+    rows_of(5, {{}, {}, {}, {}, {}}, "diagonal 5", 0);
+    for (int n : {69, 63}) {
+        std::vector<std::vector<int32_t>> reads(70);
+        for (int j = 1; j <= n; ++j) reads[0].push_back(j);
+        rows_of(70, reads, n == 69 ? "a row of 69 entries" : "a row of 63 entries", n == 69 ? 1 : 0);
+    }
+}
+
 struct SchedBuffers {
     std::vector<int32_t> wi, oi; std::vector<double> wd; std::vector<uint32_t> wb; std::vector<char> image;
     LufSchedWork S{}; LufSchedOut SO{};
@@ -346,6 +449,7 @@ static void check_schedules(const char* name, const LufOut& O, const LufWork& W,
                 CHECK(max_rel(got, want) <= 1e-9, "%s %s variant %d: sweep behind pivot %d (group %d) differs by %.3e", name, nm[q], variant, p, SO.level_of[p] + 1,
                       max_rel(got, want));
             }
+            if (variant == 0) check_host_image(name, nm[q], *tri[q], T.diag, asc[q], m, rng);
             if (!maskable || m < 2) continue;
             // mask a few pivots the way ft_update does: 1 / diagonal := 0, the listed slots := 0, x[p] := 0 on entry
             const LufImageLayout L = luf_image_layout(m, SO.desc[LUF_D_PASSES], SO.desc[LUF_D_LEVELS], SO.desc[LUF_D_LANES], SO.desc[LUF_D_OVF], wide);
@@ -458,6 +562,7 @@ static int probe(const char* path) {
 
 static void all_checks() {
     std::mt19937_64 rng(20250611);
+    check_host_image_shapes(rng);
     // the reference's factorisation cases (decomposition/mod.rs:301-491), column by column
     check_square("identity 2", 2, {{{0, 1.0}}, {{1, 1.0}}}, rng);
     check_square("identity 3", 3, {{{0, 1.0}}, {{1, 1.0}}, {{2, 1.0}}}, rng);

@@ -211,8 +211,30 @@ static void check_matrix(const char* name, int m, const Cols& cols_in, std::mt19
     }
 }
 
+// lu_level_runs on hand-made level_ptr arrays: level l has sizes[l] rows (level 0 belongs to no run)
+static void check_level_runs(const char* name, const std::vector<int>& sizes, const std::vector<int32_t>& want) {
+    std::vector<int32_t> level_ptr{0};
+    for (int n : sizes) level_ptr.push_back(level_ptr.back() + n);
+    const std::vector<int32_t> got = lu_level_runs(level_ptr);
+    std::string text;
+    for (int32_t v : got) text += std::to_string(v) + " ";
+    CHECK(got == want, "level runs, %s: got ( %s)", name, text.c_str());
+}
+
 int main() {
     std::mt19937_64 rng(20250104);
+    for (int z : {1, 5, 40}) {                             // (the size of level 0 does not matter)
+        check_level_runs("one level", {z}, {});
+        check_level_runs("two levels", {z, 3}, {1, 2, 0});
+        check_level_runs("two levels, wide", {z, 30}, {1, 2, 0});
+        check_level_runs("solo, wide with one narrow level inside, solo", {z, 3, 3, 20, 4, 30, 2, 2}, {1, 3, 1, 3, 6, 0, 6, 8, 1});
+        check_level_runs("8 rows are narrow", {z, 8, 8}, {1, 3, 1});
+        check_level_runs("9 rows are wide", {z, 9, 9}, {1, 3, 0});
+        check_level_runs("8 then 9", {z, 8, 9}, {1, 3, 0});
+        check_level_runs("a lone narrow level at the end", {z, 20, 3}, {1, 3, 0});
+        check_level_runs("a lone narrow level behind a solo run and a wide one", {z, 3, 3, 20, 3}, {1, 3, 1, 3, 5, 0});
+        check_level_runs("three narrow levels at the end", {z, 20, 1, 8, 2}, {1, 2, 0, 2, 5, 1});
+    }
     // the reference's factorisation cases, column by column (decomposition/mod.rs:301-491 gives them row by row)
     check_matrix("identity 2", 2, {{{0, 1.0}}, {{1, 1.0}}}, rng);
     check_matrix("identity 3", 3, {{{0, 1.0}}, {{1, 1.0}}, {{2, 1.0}}}, rng);
