@@ -363,6 +363,27 @@ class Tableau {
     std::vector<double> right_hand_side() { std::vector<double> v(nr_rows()); ck(relp_get_right_hand_side(h_, v.data())); return v; }
     // relp_rhs_stats: {in-place changes, columns of B^-1 they read, pending rows at the last change, shares of its last launch}
     std::array<int64_t, 4> rhs_stats() { std::array<int64_t, 4> out{}; ck(relp_rhs_stats(h_, out.data())); return out; }
+    // relp_row_ratios: per listed row the minimum d_j / |T[r,j]| over the non-basic columns with T[r,j] < 0 (down) and > 0 (up), and
+    // the column that attains it (+inf, -1 without one): branching penalties, and the cost range [c - down, c + up] of the row's
+    // basic variable.  Read-only.
+    struct RowRatios { std::vector<double> down_ratio; std::vector<int32_t> down_column; std::vector<double> up_ratio; std::vector<int32_t> up_column; };
+    RowRatios row_ratios(const std::vector<int32_t>& rows) {
+        const size_t n = rows.size();
+        RowRatios out{std::vector<double>(n), std::vector<int32_t>(n), std::vector<double>(n), std::vector<int32_t>(n)};
+        ck(relp_row_ratios(h_, rows.data(), (int32_t)n, out.down_ratio.data(), out.down_column.data(), out.up_ratio.data(), out.up_column.data()));
+        return out;
+    }
+    // relp_rhs_ranging: per listed row how far its rhs may fall and rise before the basis stops being primal feasible, and the row
+    // that blocks (+inf, -1 without one).  Read-only.
+    struct RhsRanging { std::vector<double> decrease; std::vector<int32_t> decrease_row; std::vector<double> increase; std::vector<int32_t> increase_row; };
+    RhsRanging rhs_ranging(const std::vector<int32_t>& rows) {
+        const size_t n = rows.size();
+        RhsRanging out{std::vector<double>(n), std::vector<int32_t>(n), std::vector<double>(n), std::vector<int32_t>(n)};
+        ck(relp_rhs_ranging(h_, rows.data(), (int32_t)n, out.decrease.data(), out.decrease_row.data(), out.increase.data(), out.increase_row.data()));
+        return out;
+    }
+    // relp_ranging_stats: {row-ratio calls, rows they covered, ranging calls, pending rows at the last call}
+    std::array<int64_t, 4> ranging_stats() { std::array<int64_t, 4> out{}; ck(relp_ranging_stats(h_, out.data())); return out; }
     // ---- one LP on several GPUs (no counterpart in the reference, which is single-threaded) ---------------------
     // Options::shard(rank, count) at construction, the owned structural columns in `MatrixData` (relp_shard_plan);
     // rank 0 makes the RCCL id, the host program hands it to every rank, every rank attaches, then the loop runs

@@ -276,6 +276,41 @@ relp_status_t relp_get_right_hand_side(relp_engine_t *h, double *out_m);
 /* out4 = { in-place changes so far, columns of B^-1 they read (entries with a nonzero delta), pending rows p of the update block
  * at the last change, shares (k-splits) of its last launch }. */
 relp_status_t relp_rhs_stats(const relp_engine_t *h, int64_t *out4);
+/* Batched ratio tests over the tableau as it stands (no counterpart in the reference): what a branch-and-bound driver asks at a
+ * node ("which fractional row is the dearest to branch on?") and a solve asks at its end (the ranging report).  Both are read-only:
+ * nothing is flushed or re-tabulated, and T0, R0, W, d, b, the basis, the flags, the PRICE partials, the record, the trace and
+ * relp_reinversions stay as they are; while an update block is open the entries are T0 + W R0 over its p pending rows, formed in the
+ * order of relp_generate_column and relp_select_dual_pivot_column.  Deterministic: minima in total orders, no atomics on results,
+ * the same call on the same state gives the same bits.  `rows` are engine rows in the current order (the indexing of
+ * relp_change_right_hand_side), in any order, a row may be named twice; outputs are per list entry and any of them may be NULL.
+ * RELP_E_ARG with nothing written: a row out of range, count < 0.  count == 0 is a no-op.  Two launches and one download per call,
+ * the list in chunks of 8 entries per workgroup (a fixed size).  RELP_ENGINE_TABLEAU, unsharded, phase 2: RELP_E_UNSUPPORTED on
+ * another or a sharded engine, RELP_E_STATE in phase 1 (all three calls).
+ *
+ * relp_row_ratios, entry k with r = rows[k], over the non-basic columns 0 <= j < n (a barred column is excluded as in the dual loop):
+ *   down_ratio[k]  = min d'_j / (-T[r,j]) over T[r,j] < -tol_pivot, d'_j = 0 when d_j <= tol_zero, else d_j
+ *   up_ratio[k]    = min d'_j /   T[r,j]  over T[r,j] >  tol_pivot
+ *   *_column[k]    = the lowest j among the ratios <= min + tol_tie * max(1, |min|); (+inf, -1) without a candidate
+ * down is literally the entering rule of relp_select_dual_pivot_column(r): the same bits and the same column.  Dual feasibility is
+ * not required.  Two readings, x_B the basic variable of row r and c its cost:
+ *   penalty     the objective degrades by down_ratio per unit x_B is pushed down (the dual pivot that removes b_r < 0 enters
+ *               down_column), by up_ratio per unit it is pushed up: the Driebeek/Tomlin penalties of branching on x_B
+ *   cost range  the basis stays optimal while the cost of x_B stays within [c - down_ratio, c + up_ratio]
+ *
+ * relp_rhs_ranging, entry k with row rows[k] and a = T[:, idcol] = B^-1 e_row, bz_i = 0 when b_i <= tol_zero, else b_i:
+ *   decrease[k]    = min bz_i /   a_i  over a_i >  tol_pivot
+ *   increase[k]    = min bz_i / (-a_i) over a_i < -tol_pivot
+ *   *_row[k]       = among the ratios inside the tie band the row with the smallest leaving column; (+inf, -1) without a candidate
+ * The basis stays primal feasible while rhs[row] stays within [rhs - decrease, rhs + increase]; *_row is the row that blocks.
+ * decrease is the reference ratio test (RELP_RATIO_REFERENCE) of relp_select_primal_pivot_row on that column, whatever ratio_rule is
+ * configured.  Measured at 10,000 x 10,000: profiles/r14_ranging.md, DESIGN.md 10. */
+relp_status_t relp_row_ratios(relp_engine_t *h, const int32_t *rows, int32_t count, double *down_ratio, int32_t *down_column,
+                              double *up_ratio, int32_t *up_column);
+relp_status_t relp_rhs_ranging(relp_engine_t *h, const int32_t *rows, int32_t count, double *decrease, int32_t *decrease_row,
+                               double *increase, int32_t *increase_row);
+/* out4 = { relp_row_ratios calls so far, rows they covered, relp_rhs_ranging calls so far, pending rows p of the update block at
+ * the last call of either }.  (Calls with count == 0 and refused calls are not counted.) */
+relp_status_t relp_ranging_stats(const relp_engine_t *h, int64_t *out4);
 /* InverseMaintener::from_basis (carry/mod.rs:428-463): warm start from provider column indices,
  * one per row; switches to phase 2.  RELP_ENGINE_LU: any basis (factorise, b = FTRAN(rhs), -pi = BTRAN(-c_B));
  * RELP_ENGINE_REVISED: any basis (basis_inverse_rows.rs:103-129: LU - factorised on the host like every

@@ -1145,6 +1145,73 @@ relp_status_t Engine::rhs_stats(int64_t* out4) const {
     return RELP_OK;
 }
 
+// The two batched ratio queries.  Both read the tableau as it stands -- T0, and W R0 over the p pending rows of an open block -- and
+// write to scratch of their own: d, b, the basis, the flags, W, R0, T0, the PRICE partials and the record stay as they are (the
+// record is downloaded for p, never uploaded).  Settles the fused update's shadow row first, does not flush.
+// columns == false: rows of T against d (launch_tab_row_ratios); true: the rows' identity columns against b (launch_tab_rhs_ranging).
+relp_status_t Engine::ranging_query(bool columns, const char* what, const int32_t* rows, int32_t count, double* ratio0, int32_t* index0,
+                                    double* ratio1, int32_t* index1) {
+    relp_status_t st = dual_ready(what);
+    if (st) return st;
+    if (count < 0 || (count > 0 && !rows)) return fail(RELP_E_ARG, std::string(what) + ": count < 0 or the list missing");
+    for (int32_t k = 0; k < count; ++k)
+        if (rows[k] < 0 || rows[k] >= lay_.m) return fail(RELP_E_ARG, std::string(what) + ": row out of range");
+    if (count == 0) return RELP_OK;
+    tab_settle();
+    if ((st = download_rec())) return st;
+    const int32_t p = h_rec_->n_eta;
+    const TableauView tv = tview();
+    const int64_t blocks = columns ? (lay_.m + 255) / 256 : tab_scan_blocks(lay_.sc_hi - lay_.sc_lo);
+    if (count > rng_list_cap_) {
+        HIP_TRY(d_rng_list_.alloc_raw(sizeof(int32_t) * (size_t)count));
+        HIP_TRY(d_rng_ratio_.alloc_raw(sizeof(double) * 2 * (size_t)count));
+        HIP_TRY(d_rng_index_.alloc_raw(sizeof(int32_t) * 2 * (size_t)count));
+        rng_list_cap_ = count;
+    }
+    if (2 * count * blocks > rng_part_cap_) {
+        HIP_TRY(d_rng_part_k_.alloc_raw(sizeof(double) * (size_t)(2 * count * blocks)));
+        HIP_TRY(d_rng_part_j_.alloc_raw(sizeof(int32_t) * (size_t)(2 * count * blocks)));
+        rng_part_cap_ = 2 * count * blocks;
+    }
+    std::vector<int32_t> list(rows, rows + count);
+    if (columns) for (int32_t& r : list) r = idcol_h_[r];
+    HIP_TRY(hipMemcpyAsync(d_rng_list_, list.data(), sizeof(int32_t) * count, hipMemcpyHostToDevice, stream_));
+    if (columns) launch_tab_rhs_ranging(tv, deferred(), d_b_, d_basis_, tolerances(), d_rng_list_, count, p, d_rng_part_k_, d_rng_ratio_,
+                                        d_rng_index_, stream_);
+    else launch_tab_row_ratios(tv, deferred(), tab_partials(current_rule()), tolerances(), d_rng_list_, count, p, d_rng_part_k_,
+                               d_rng_part_j_, d_rng_ratio_, d_rng_index_, stream_);
+    std::vector<double> ratio(2 * (size_t)count);
+    std::vector<int32_t> index(2 * (size_t)count);
+    HIP_TRY(hipMemcpyAsync(ratio.data(), d_rng_ratio_, sizeof(double) * 2 * count, hipMemcpyDeviceToHost, stream_));
+    if ((st = fetch(index.data(), d_rng_index_, sizeof(int32_t) * 2 * count))) return st;       // (waits for the list and the ratios too)
+    if (hipGetLastError() != hipSuccess) return fail(RELP_E_HIP, std::string(what) + ": a kernel launch failed");
+    if (ratio0) std::copy(ratio.begin(), ratio.begin() + count, ratio0);
+    if (index0) std::copy(index.begin(), index.begin() + count, index0);
+    if (ratio1) std::copy(ratio.begin() + count, ratio.end(), ratio1);
+    if (index1) std::copy(index.begin() + count, index.end(), index1);
+    if (columns) ++rng_ranging_calls_;
+    else { ++rng_ratio_calls_; rng_ratio_rows_ += count; }
+    rng_last_p_ = p;
+    return RELP_OK;
+}
+
+relp_status_t Engine::row_ratios(const int32_t* rows, int32_t count, double* down_ratio, int32_t* down_column, double* up_ratio,
+                                 int32_t* up_column) {
+    return ranging_query(false, "relp_row_ratios", rows, count, down_ratio, down_column, up_ratio, up_column);
+}
+
+relp_status_t Engine::rhs_ranging(const int32_t* rows, int32_t count, double* decrease, int32_t* decrease_row, double* increase,
+                                  int32_t* increase_row) {
+    return ranging_query(true, "relp_rhs_ranging", rows, count, decrease, decrease_row, increase, increase_row);
+}
+
+relp_status_t Engine::ranging_stats(int64_t* out4) const {
+    if (!tableau_ || cfg_.shard_count > 1) return RELP_E_UNSUPPORTED;
+    if (phase_ != 2) return RELP_E_STATE;
+    out4[0] = rng_ratio_calls_; out4[1] = rng_ratio_rows_; out4[2] = rng_ranging_calls_; out4[3] = rng_last_p_;
+    return RELP_OK;
+}
+
 // phase_one.rs:146-166: objective == 0 -> feasible (remove artificials, switch) else infeasible
 relp_status_t Engine::finish_phase_one(int32_t* outcome) {
     tab_settle();

@@ -129,6 +129,13 @@ class Engine : private EngineQueue {
     relp_status_t set_upper_bound(int32_t column, double value);
     relp_status_t get_right_hand_side(double* out_m);
     relp_status_t rhs_stats(int64_t* out4) const;
+    // batched ratio tests over the tableau as it stands, read-only: rows of T against d (penalties, cost ranges), identity columns
+    // against b (rhs ranges)
+    relp_status_t row_ratios(const int32_t* rows, int32_t count, double* down_ratio, int32_t* down_column, double* up_ratio,
+                             int32_t* up_column);
+    relp_status_t rhs_ranging(const int32_t* rows, int32_t count, double* decrease, int32_t* decrease_row, double* increase,
+                              int32_t* increase_row);
+    relp_status_t ranging_stats(int64_t* out4) const;
     int32_t engine_kind() const { return lay_.engine; }
     relp_status_t robust_stats(int64_t* out4) const;
     relp_status_t solve_relaxation(int64_t max_iters, int32_t* outcome);
@@ -284,6 +291,16 @@ class Engine : private EngineQueue {
     int32_t rhs_partial_splits_ = 0;                   // splits d_rhs_partial_ holds (allocated at the first split launch, grown on demand)
     int64_t rhs_changes_ = 0, rhs_columns_ = 0;
     int32_t rhs_last_p_ = 0, rhs_last_splits_ = 0;
+    // relp_row_ratios / relp_rhs_ranging: the uploaded list (rows, or their identity columns), the per-(direction, entry, block)
+    // minima and the results [direction][entry] (relp_kernels.h: launch_tab_row_ratios, launch_tab_rhs_ranging); allocated at the
+    // first query, grown on demand; what relp_ranging_stats reports
+    relp_status_t ranging_query(bool columns, const char* what, const int32_t* rows, int32_t count, double* ratio0, int32_t* index0,
+                                double* ratio1, int32_t* index1);
+    DeviceBuf<int32_t> d_rng_list_, d_rng_part_j_, d_rng_index_;
+    DeviceBuf<double> d_rng_part_k_, d_rng_ratio_;
+    int64_t rng_list_cap_ = 0, rng_part_cap_ = 0;
+    int64_t rng_ratio_calls_ = 0, rng_ratio_rows_ = 0, rng_ranging_calls_ = 0;
+    int32_t rng_last_p_ = 0;
     // sparse LU engine (cfg.engine == RELP_ENGINE_LU): B^-1 = (I + W S') (L U)^-1, refactor every block_ pivots
     bool lu_ = false;
     std::vector<int64_t> hc_ptr_; std::vector<int32_t> hc_idx_; std::vector<double> hc_val_;   // host CSC of A

@@ -503,6 +503,24 @@ int32_t tab_rhs_splits(int32_t m, int32_t count, int32_t forced);
 // splits * ld_partial doubles (unused when splits == 1).  No atomics: the same (list, p, splits) gives the same bits.
 void launch_tab_rhs_change(const TableauView& tv, const DeferredUpdate& du, const RhsChange& ch, int32_t p, int32_t splits,
                            double* v, double* b, double* partial, int64_t ld_partial, hipStream_t s);
+// Batched ratio tests over the tableau as it stands, T = T0 + W R0 over the p pending rows, read-only (relp_row_ratios,
+// relp_rhs_ranging).  The list is taken kTabRatioChunk entries per workgroup (a fixed size, not a rule: eight rows of one column are
+// one 64-byte sector of T0), grid = chunks x blocks of 256 columns (rows); the second launch has one workgroup per list entry.
+// No sums, no global atomics: minima of (ratio, index) and tie keys in total orders, the same bits every run.
+static constexpr int32_t kTabRatioChunk = 8;
+// Rows rows[k] of T, k < count (device list, any order, repeats allowed): per direction (0 = down: entries < -tol.pivot, ratio
+// dz_j / -entry; 1 = up: entries > tol.pivot, ratio dz_j / entry) over the non-basic columns (sp.in_basis[j] == 0) the entering
+// rule of launch_dual_select_column -- minimum ratio, lowest column inside its tie band.  ratio / column[dir * count + k], (+inf,
+// -1) without a candidate.  part_k / part_j: 2 * count * tab_scan_blocks(owned columns) entries of scratch.
+void launch_tab_row_ratios(const TableauView& tv, const DeferredUpdate& du, const SelectPartials& sp, Tolerances tol,
+                           const int32_t* rows, int32_t count, int32_t p, double* part_k, int32_t* part_j, double* ratio,
+                           int32_t* column, hipStream_t s);
+// Stored columns cols[k] of T, k < count: per direction (0 = decrease: entries a_i > tol.pivot, ratio bz_i / a_i; 1 = increase:
+// a_i < -tol.pivot, bz_i / -a_i) the reference ratio test -- minimum ratio, smallest leaving column inside its tie band, whatever
+// tol.ratio_rule says.  ratio / row[dir * count + k], (+inf, -1) without a candidate.  part: 2 * count * cdiv(m, 256) doubles.
+void launch_tab_rhs_ranging(const TableauView& tv, const DeferredUpdate& du, const double* b, const int32_t* basis_indices,
+                            Tolerances tol, const int32_t* cols, int32_t count, int32_t p, double* part, double* ratio, int32_t* row,
+                            hipStream_t s);
 
 // ---- sparse LU engine ------------------------------------------------------------------------------
 // PRICE over CSC columns (thread per column), partial argmin per 256 columns

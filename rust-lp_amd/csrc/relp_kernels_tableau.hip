@@ -1049,6 +1049,218 @@ __global__ __launch_bounds__(kThreads) void k_tab_rhs_reduce(int m, int splits, 
     b[i] += sum;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Batched ratio tests over the tableau as it stands (relp_row_ratios, relp_rhs_ranging): read-only streams over T0 (+ W R0 while
+// an update block is open, p = its pending rows).  Two launches each: [the minimum of every (list entry, block of 256 columns or
+// rows) into scratch] -> [one workgroup per list entry: the minimum of its blocks, then the tie band from the blocks whose own
+// minimum is inside it, their entries recomputed by the same fma chain].  Minima of (ratio, index) pairs and of keys only: no
+// sums, no global atomics, the same call on the same state gives the same bits.
+// ------------------------------------------------------------------------------------------------
+// Rows rows[k0 .. k0 + RB) of T (k0 = blockIdx.x * RB) over the 256 stored columns of block blockIdx.y, one column per thread:
+// d_c, the flag and the p entries of column c of R0 are loaded once and serve all RB rows; a sorted chunk's T0 entries of one
+// column share a 64-byte sector.  Entry (u, c) = T0[rows[u], c], then fma over the pending rows in ascending j (tab_row_entry).
+// part_k / part_j[(dir * count + k) * gridDim.y + blockIdx.y] = the block's minimum (ratio, column) of list entry k, dir 0 = down
+// (entry < -tol_pivot, ratio d / -entry), 1 = up (entry > tol_pivot, ratio d / entry): dual_ratio on the entry with its sign turned.
+template <int B, int RB>
+__global__ __launch_bounds__(kThreads) void k_tab_row_ratios(TableauView tv, DeferredUpdate du, const uint8_t* __restrict__ in_basis,
+                                                             Tolerances tol, const int32_t* __restrict__ rows, int count, int p,
+                                                             double* __restrict__ part_k, int32_t* __restrict__ part_j) {
+    __shared__ double s_w[RB * kMaxEta];
+    __shared__ int s_rows[RB];
+    __shared__ double s_k[2 * RB][kThreads / 64];
+    __shared__ int s_j[2 * RB][kThreads / 64];
+    const int k0 = blockIdx.x * RB, nk = min(RB, count - k0);
+    if ((int)threadIdx.x < RB) s_rows[threadIdx.x] = rows[k0 + min((int)threadIdx.x, nk - 1)];     // (a short chunk repeats its last row)
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < RB * p; idx += kThreads) {
+        const int u = idx / p, j = idx - u * p;
+        s_w[u * kMaxEta + j] = du.W[(int64_t)j * du.ld + s_rows[u]];
+    }
+    const int c = tv.c_lo + blockIdx.y * kThreads + threadIdx.x;
+    const int j = c - tv.col_off;
+    const bool live = c < tv.c_hi;
+    double acc[RB];
+    double d_c = 0.0;
+    bool cand = false;
+#pragma unroll
+    for (int u = 0; u < RB; ++u) acc[u] = 0.0;
+    if (live) {
+        d_c = tv.d[c];
+        cand = j >= 0 && j < tv.n && in_basis[j] == 0;
+        const double* col = tv.T0 + (int64_t)c * tv.ld_t;
+#pragma unroll
+        for (int u = 0; u < RB; ++u) acc[u] = col[s_rows[u]];
+    }
+    __syncthreads();
+    if (live) {
+        for_pending<B>(tv.R0, tv.ld_r, c, p, [&](int jj, double r0) {
+#pragma unroll
+            for (int u = 0; u < RB; ++u) acc[u] = fma(s_w[u * kMaxEta + jj], r0, acc[u]);
+        });
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int u = 0; u < RB; ++u) {
+#pragma unroll
+        for (int dir = 0; dir < 2; ++dir) {
+            double key = INFINITY;
+            int kj = 0x7fffffff;
+            const double v = dir ? -acc[u] : acc[u];
+            if (cand && v < -tol.pivot) { key = dual_ratio(d_c, v, tol.zero); kj = j; }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                const double ok = __shfl_down(key, off, 64);
+                const int oj = __shfl_down(kj, off, 64);
+                if (ok < key || (ok == key && oj < kj)) { key = ok; kj = oj; }
+            }
+            if (lane == 0) { s_k[dir * RB + u][wave] = key; s_j[dir * RB + u][wave] = kj; }
+        }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < 2 * RB) {
+        const int dir = threadIdx.x / RB, u = threadIdx.x % RB;
+        if (u < nk) {
+            double key = s_k[threadIdx.x][0];
+            int kj = s_j[threadIdx.x][0];
+#pragma unroll
+            for (int w = 1; w < kThreads / 64; ++w)
+                if (s_k[threadIdx.x][w] < key || (s_k[threadIdx.x][w] == key && s_j[threadIdx.x][w] < kj)) {
+                    key = s_k[threadIdx.x][w]; kj = s_j[threadIdx.x][w];
+                }
+            const int64_t slot = ((int64_t)dir * count + k0 + u) * gridDim.y + blockIdx.y;
+            part_k[slot] = key;
+            part_j[slot] = kj;
+        }
+    }
+}
+
+// List entry k = blockIdx.x, row r = rows[k]: per direction the entering rule of k_dual_select_column on the entry's nbc partials
+// (select_entering: the minimum ratio, then the lowest column inside its tie band, from the entries recomputed by tab_row_entry).
+// ratio / column[dir * count + k] = (the minimum, that column), (+inf, -1) without a candidate.
+template <int B>
+__global__ __launch_bounds__(kThreads) void k_tab_row_ratios_pick(TableauView tv, DeferredUpdate du, SelectPartials sp, Tolerances tol,
+                                                                  const int32_t* __restrict__ rows, int count, int p, int nbc,
+                                                                  double* part_k, int32_t* part_j, double* __restrict__ ratio,
+                                                                  int32_t* __restrict__ column) {
+    __shared__ double s_w[kMaxEta];
+    const int k = blockIdx.x, r = rows[k];
+    stage_w_row(du, r, p, s_w);
+    __syncthreads();
+    for (int dir = 0; dir < 2; ++dir) {
+        SelectPartials spd = sp;
+        spd.k1 = part_k + ((int64_t)dir * count + k) * nbc;
+        spd.j = part_j + ((int64_t)dir * count + k) * nbc;
+        double k1 = INFINITY;
+        int bj = 0x7fffffff;
+        select_entering<kThreads>(tv, spd, nbc, tol.tie, tol.tie > 0.0, false, k1, bj, [&](int c, int j, double bound) {
+            if (sp.in_basis[j] != 0) return false;
+            const double d_c = tv.d[c];
+            const double e = tab_row_entry<B>(tv, c, p, s_w, tv.T0[(int64_t)c * tv.ld_t + r]);
+            const double v = dir ? -e : e;
+            return v < -tol.pivot && dual_ratio(d_c, v, tol.zero) <= bound;
+        });
+        if (threadIdx.x == 0) {
+            const bool none = bj == 0x7fffffff;
+            ratio[(int64_t)dir * count + k] = none ? INFINITY : k1;
+            column[(int64_t)dir * count + k] = none ? -1 : bj;
+        }
+        __syncthreads();                               // (select_entering's LDS words before the other direction reuses them)
+    }
+}
+
+// Stored columns cols[k0 .. k0 + CB) of T (k0 = blockIdx.x * CB) over the 256 rows of block blockIdx.y, one row per thread: b_i
+// and the p entries of row i of W are loaded once and serve all CB columns, whose R0 columns are staged in LDS.  Entry (i, u) =
+// T0[i, cols[u]], then fma over the pending rows in ascending j (tab_column_entry).  part[(dir * count + k) * gridDim.y +
+// blockIdx.y] = the block's minimum ratio of list entry k, dir 0 = decrease (row_ratio on the entry), 1 = increase (on its negative).
+template <int B, int CB>
+__global__ __launch_bounds__(kThreads) void k_tab_rhs_ranging(TableauView tv, DeferredUpdate du, const double* __restrict__ b,
+                                                              Tolerances tol, const int32_t* __restrict__ cols, int count, int p,
+                                                              double* __restrict__ part) {
+    __shared__ double s_r0[CB * kMaxEta];
+    __shared__ int s_cols[CB];
+    __shared__ double s_m[2 * CB][kThreads / 64];
+    const int k0 = blockIdx.x * CB, nk = min(CB, count - k0);
+    if ((int)threadIdx.x < CB) s_cols[threadIdx.x] = cols[k0 + min((int)threadIdx.x, nk - 1)];     // (a short chunk repeats its last column)
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < CB * p; idx += kThreads) {
+        const int u = idx / p, j = idx - u * p;
+        s_r0[u * kMaxEta + j] = tv.R0[(int64_t)j * tv.ld_r + s_cols[u]];
+    }
+    const int i = blockIdx.y * kThreads + threadIdx.x;
+    const bool live = i < tv.m;
+    double acc[CB];
+    double b_i = 0.0;
+#pragma unroll
+    for (int u = 0; u < CB; ++u) acc[u] = 0.0;
+    if (live) {
+        b_i = b[i];
+#pragma unroll
+        for (int u = 0; u < CB; ++u) acc[u] = tv.T0[(int64_t)s_cols[u] * tv.ld_t + i];
+    }
+    __syncthreads();
+    if (live) {
+        for_pending<B>(du.W, du.ld, i, p, [&](int jj, double w) {
+#pragma unroll
+            for (int u = 0; u < CB; ++u) acc[u] = fma(w, s_r0[u * kMaxEta + jj], acc[u]);
+        });
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int u = 0; u < CB; ++u) {
+#pragma unroll
+        for (int dir = 0; dir < 2; ++dir) {
+            double ratio = live ? row_ratio(dir ? -acc[u] : acc[u], b_i, tol) : INFINITY;
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) ratio = fmin(ratio, __shfl_down(ratio, off, 64));
+            if (lane == 0) s_m[dir * CB + u][wave] = ratio;
+        }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < 2 * CB) {
+        const int dir = threadIdx.x / CB, u = threadIdx.x % CB;
+        if (u < nk) {
+            double ratio = s_m[threadIdx.x][0];
+#pragma unroll
+            for (int w = 1; w < kThreads / 64; ++w) ratio = fmin(ratio, s_m[threadIdx.x][w]);
+            part[((int64_t)dir * count + k0 + u) * gridDim.y + blockIdx.y] = ratio;
+        }
+    }
+}
+
+// List entry k = blockIdx.x, column c = cols[k]: per direction the reference ratio test on the entry's nbr block minima
+// (block_minima_pick: the minimum ratio, then the smallest leaving column among the rows inside its tie band, their entries
+// recomputed by tab_column_entry).  ratio / row[dir * count + k] = (the minimum, that row), (+inf, -1) without a candidate.
+template <int B>
+__global__ __launch_bounds__(kThreads) void k_tab_rhs_ranging_pick(TableauView tv, DeferredUpdate du, const double* __restrict__ b,
+                                                                   const int32_t* __restrict__ basis_indices, Tolerances tol,
+                                                                   const int32_t* __restrict__ cols, int count, int p, int nbr,
+                                                                   const double* part, double* __restrict__ ratio,
+                                                                   int32_t* __restrict__ row) {
+    __shared__ double s_vs[kMaxEta];
+    const int k = blockIdx.x, c = cols[k];
+    if ((int)threadIdx.x < p) s_vs[threadIdx.x] = tv.R0[(int64_t)threadIdx.x * tv.ld_r + c];
+    __syncthreads();
+    for (int dir = 0; dir < 2; ++dir) {
+        const double* minima = part + ((int64_t)dir * count + k) * nbr;
+        double mn = INFINITY;
+        for (int t = threadIdx.x; t < nbr; t += kThreads) mn = fmin(mn, minima[t]);
+        const double gmin = block_min_value<kThreads>(mn);
+        __syncthreads();                               // (block_minima_pick makes the same reduction)
+        int r, leaving;
+        block_minima_pick<kThreads>(minima, nbr, kThreads, tv.m, tol.tie, INFINITY, false, false, &r, &leaving, [&](int i, double bound) {
+            const double a = tab_column_entry<B>(du, i, p, s_vs, tv.T0[(int64_t)c * tv.ld_t + i]);
+            const double bi = b[i];
+            const int lv = basis_indices[i];
+            return row_ratio(dir ? -a : a, bi, tol) <= bound ? tie_key(0.0, lv, 0) : kNoTieKey;
+        });
+        if (threadIdx.x == 0) {
+            ratio[(int64_t)dir * count + k] = gmin;    // (+inf when no row qualifies)
+            row[(int64_t)dir * count + k] = r;         // (-1 then)
+        }
+        __syncthreads();                               // (the pick's LDS words before the other direction reuses them)
+    }
+}
+
 int32_t tab_scan_blocks(int32_t n_owned_columns) { return cdiv(n_owned_columns, kThreads); }
 
 // The batch sizes of for_pending the kernels are instantiated for (DeferredUpdate::batch, RELP_TAB_LOAD_BATCH).  1 is the
@@ -1281,6 +1493,32 @@ void launch_tab_rhs_change(const TableauView& tv, const DeferredUpdate& du, cons
                            ld_partial);
     });
     if (splits > 1) hipLaunchKernelGGL(k_tab_rhs_reduce, dim3(nb), dim3(kThreads), 0, s, (int)tv.m, (int)splits, partial, ld_partial, b);
+}
+
+void launch_tab_row_ratios(const TableauView& tv, const DeferredUpdate& du, const SelectPartials& sp, Tolerances tol,
+                           const int32_t* rows, int32_t count, int32_t p, double* part_k, int32_t* part_j, double* ratio,
+                           int32_t* column, hipStream_t s) {
+    if (count < 1 || tv.c_hi <= tv.c_lo) return;
+    const int nbc = tab_scan_blocks(tv.c_hi - tv.c_lo);
+    with_load_batch(du.batch, [&](auto B) {
+        hipLaunchKernelGGL((k_tab_row_ratios<decltype(B)::value, kTabRatioChunk>), dim3(cdiv(count, kTabRatioChunk), nbc), dim3(kThreads), 0,
+                           s, tv, du, sp.in_basis, tol, rows, (int)count, (int)p, part_k, part_j);
+        hipLaunchKernelGGL((k_tab_row_ratios_pick<decltype(B)::value>), dim3(count), dim3(kThreads), 0, s, tv, du, sp, tol, rows, (int)count,
+                           (int)p, nbc, part_k, part_j, ratio, column);
+    });
+}
+
+void launch_tab_rhs_ranging(const TableauView& tv, const DeferredUpdate& du, const double* b, const int32_t* basis_indices,
+                            Tolerances tol, const int32_t* cols, int32_t count, int32_t p, double* part, double* ratio, int32_t* row,
+                            hipStream_t s) {
+    if (count < 1) return;
+    const int nbr = cdiv(tv.m, kThreads);
+    with_load_batch(du.batch, [&](auto B) {
+        hipLaunchKernelGGL((k_tab_rhs_ranging<decltype(B)::value, kTabRatioChunk>), dim3(cdiv(count, kTabRatioChunk), nbr), dim3(kThreads), 0,
+                           s, tv, du, b, tol, cols, (int)count, (int)p, part);
+        hipLaunchKernelGGL((k_tab_rhs_ranging_pick<decltype(B)::value>), dim3(count), dim3(kThreads), 0, s, tv, du, b, basis_indices, tol,
+                           cols, (int)count, (int)p, nbr, part, ratio, row);
+    });
 }
 
 }  // namespace relp

@@ -96,6 +96,9 @@ _SIGNATURES = {
     "relp_set_upper_bound": (C.c_int, [C.c_void_p, C.c_int32, C.c_double]),
     "relp_get_right_hand_side": (C.c_int, [C.c_void_p, C.c_void_p]),
     "relp_rhs_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "relp_row_ratios": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "relp_rhs_ranging": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "relp_ranging_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "relp_solve_relaxation": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]),
     "relp_from_basis": (C.c_int, [C.c_void_p, C.c_void_p]),
     "relp_flush": (C.c_int, [C.c_void_p]),
@@ -430,6 +433,57 @@ class Tableau:
         out = (C.c_int64 * 4)()
         self._ck(self._lib.relp_rhs_stats(self._h, out))
         return tuple(int(x) for x in out)
+
+    def _ratio_query(self, call, rows):
+        r = np.ascontiguousarray(rows, dtype=np.int32)
+        if r.ndim != 1:
+            raise ValueError("rows must be one-dimensional")
+        n = r.shape[0]
+        ratio0, ratio1 = np.full(n, np.inf), np.full(n, np.inf)
+        index0, index1 = np.full(n, -1, dtype=np.int32), np.full(n, -1, dtype=np.int32)
+        self._ck(call(self._h, r.ctypes.data, n, ratio0.ctypes.data, index0.ctypes.data, ratio1.ctypes.data, index1.ctypes.data))
+        return ratio0, index0, ratio1, index1
+
+    def row_ratios(self, rows):
+        """(down_ratio, down_column, up_ratio, up_column), one entry per listed engine row (relp_row_ratios): the minimum of
+        d_j / -T[r,j] over the non-basic columns with T[r,j] < -tol_pivot (down) and of d_j / T[r,j] over T[r,j] > tol_pivot
+        (up), with the lowest column inside the tie band; (inf, -1) without a candidate.  down is the entering rule of
+        ``select_dual_pivot_column(r)``.  Read as the penalty per unit the row's basic variable is pushed down / up, or as the
+        range [c - down, c + up] of its cost.  Read-only; any order, repeats allowed."""
+        return self._ratio_query(self._lib.relp_row_ratios, rows)
+
+    def rhs_ranging(self, rows):
+        """(decrease, decrease_row, increase, increase_row), one entry per listed engine row (relp_rhs_ranging): the basis stays
+        primal feasible while rhs[row] stays within [rhs - decrease, rhs + increase]; ``*_row`` is the row that blocks, (inf, -1)
+        when nothing does.  Read-only."""
+        return self._ratio_query(self._lib.relp_rhs_ranging, rows)
+
+    def ranging_stats(self) -> Tuple[int, int, int, int]:
+        """(row_ratios calls so far, rows they covered, rhs_ranging calls so far, pending rows of the update block at the last
+        call of either); relp_ranging_stats."""
+        out = (C.c_int64 * 4)()
+        self._ck(self._lib.relp_ranging_stats(self._h, out))
+        return tuple(int(x) for x in out)
+
+    def cost_ranging(self, columns):
+        """(decrease, increase) per structural column j of ``columns``: the basis stays optimal while c_j stays within
+        [c_j - decrease, c_j + increase].  A non-basic column gives (d_j, inf); a basic one the (down, up) of ``row_ratios`` on
+        its row.  Built on relative_costs(), basis_indices() and row_ratios()."""
+        cols = np.ascontiguousarray(columns, dtype=np.int64)
+        if cols.ndim != 1:
+            raise ValueError("columns must be one-dimensional")
+        basis = self.basis_indices()
+        row_of = {int(c): i for i, c in enumerate(basis)}
+        d = np.asarray(self.relative_costs())
+        dec, inc = np.empty(cols.shape[0]), np.full(cols.shape[0], np.inf)
+        basic = [k for k, j in enumerate(cols) if int(j) in row_of]
+        for k, j in enumerate(cols):
+            if int(j) not in row_of:
+                dec[k] = d[int(j)]
+        if basic:
+            down, _, up, _ = self.row_ratios([row_of[int(cols[k])] for k in basic])
+            dec[basic], inc[basic] = down, up
+        return dec, inc
 
     def solve_relaxation(self, max_iters: int = 1 << 40) -> int:
         oc = C.c_int32()
