@@ -69,23 +69,15 @@ DeferredUpdate Engine::deferred() const {
     return du;
 }
 
-// device -> host on the engine's stream, and wait for it
-relp_status_t Engine::fetch(void* dst, const void* src, size_t bytes) {
-    HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream_));
-    HIP_TRY(hipStreamSynchronize(stream_));
-    return RELP_OK;
-}
+// device -> host on the engine's stream, and wait for it (a caller's output array, or a piece carved out of a buffer)
+relp_status_t Engine::fetch(void* dst, const void* src, size_t bytes) { HIP_RETURN(download_from((char*)dst, src, bytes, stream_)); }
 
-relp_status_t Engine::download_rec() { return fetch(h_rec_, d_rec_, sizeof(PivotRecord)); }
+relp_status_t Engine::download_rec() { HIP_RETURN(d_rec_.download(h_rec_, 1, stream_)); }
 
-relp_status_t Engine::upload_rec() {
-    HIP_TRY(hipMemcpyAsync(d_rec_, h_rec_, sizeof(PivotRecord), hipMemcpyHostToDevice, stream_));
-    HIP_TRY(hipStreamSynchronize(stream_));
-    return RELP_OK;
-}
+relp_status_t Engine::upload_rec() { HIP_RETURN(d_rec_.upload(h_rec_, 1, stream_)); }
 
 relp_status_t Engine::set_stream(hipStream_t s) {
-    if (stream_) HIP_TRY(hipStreamSynchronize(stream_));
+    if (stream_) HIP_TRY(hipStreamSynchronize(stream_));       // the new stream does not order with work left on the old one
     if (owns_stream_ && stream_) HIP_TRY(hipStreamDestroy(stream_));
     stream_ = s;
     owns_stream_ = false;
@@ -157,13 +149,11 @@ relp_status_t Engine::create(const relp_matrix_data_t& md, const relp_config_t& 
         if (src_ld < lay_.mc) return fail(RELP_E_ARG, "dense_ld < nr_constraints");
         // In sharded mode `dense` holds only the owned columns [col_lo, col_hi).
         if (md.matrix_memory == RELP_MEM_DEVICE && (src_ld % 2) == 0) {
-            dA_.adopt(const_cast<double*>(md.dense)); ld_a_ = src_ld;                      // zero-copy adoption
+            dA_.adopt(const_cast<double*>(md.dense), src_ld * std::max(n_local, 1)); ld_a_ = src_ld;      // zero-copy adoption
         } else {
             ld_a_ = round_up(std::max<int64_t>(lay_.mc, 1), 2);
             HIP_TRY(dA_.alloc(ld_a_ * std::max(n_local, 1)));
-            if (n_local > 0 && lay_.mc > 0)
-                HIP_TRY(hipMemcpy2D(dA_, ld_a_ * sizeof(double), md.dense, src_ld * sizeof(double), lay_.mc * sizeof(double),
-                                    n_local, md.matrix_memory == RELP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+            HIP_TRY(dA_.copy_2d(md.matrix_memory == RELP_MEM_DEVICE ? kFromDevice : kFromHost, md.dense, src_ld, lay_.mc, n_local, ld_a_, stream_));
         }
     } else if (md.format == RELP_FORMAT_CSC) {
         if (md.matrix_memory != RELP_MEM_HOST) return fail(RELP_E_UNSUPPORTED, "CSC input must be in host memory");
@@ -175,19 +165,19 @@ relp_status_t Engine::create(const relp_matrix_data_t& md, const relp_config_t& 
             if (md.row_idx[p] < 0 || md.row_idx[p] >= lay_.mc) return fail(RELP_E_ARG, "row index out of range");
         const int64_t cells = ld_a_ * std::max(n_local, 1);
         HIP_TRY(dA_.alloc(cells));
-        HIP_TRY(hipMemset(dA_, 0, (size_t)cells * sizeof(double)));
+        HIP_TRY(dA_.zero(cells, stream_));
         if (e1 > e0) {
             DeviceBuf<int64_t> t_ptr; DeviceBuf<int32_t> t_idx; DeviceBuf<double> t_val;       // staging: freed on every way out
             if (t_ptr.alloc_raw(sizeof(int64_t) * (size_t)(n_local + 1)) != hipSuccess ||
                 t_idx.alloc_raw(sizeof(int32_t) * (size_t)(e1 - e0)) != hipSuccess ||
                 t_val.alloc_raw(sizeof(double) * (size_t)(e1 - e0)) != hipSuccess)
                 return fail(RELP_E_ALLOC, "staging the CSC arrays");
-            hipError_t err = hipMemcpy(t_ptr, md.col_ptr + lay_.col_lo, sizeof(int64_t) * (size_t)(n_local + 1), hipMemcpyHostToDevice);
-            if (err == hipSuccess) err = hipMemcpy(t_idx, md.row_idx + e0, sizeof(int32_t) * (size_t)(e1 - e0), hipMemcpyHostToDevice);
-            if (err == hipSuccess) err = hipMemcpy(t_val, md.values + e0, sizeof(double) * (size_t)(e1 - e0), hipMemcpyHostToDevice);
+            hipError_t err = t_ptr.upload(md.col_ptr + lay_.col_lo, n_local + 1, stream_);
+            if (err == hipSuccess) err = t_idx.upload(md.row_idx + e0, e1 - e0, stream_);
+            if (err == hipSuccess) err = t_val.upload(md.values + e0, e1 - e0, stream_);
             if (err == hipSuccess) {
                 launch_csc_to_dense(t_ptr, t_idx, t_val, n_local, dA_, ld_a_, nullptr);
-                err = hipDeviceSynchronize();
+                err = hipDeviceSynchronize();              // (the staging buffers are freed at the end of this block)
             }
             if (err != hipSuccess) return fail(RELP_E_HIP, "dense copy of the CSC input");
         }
@@ -271,7 +261,7 @@ relp_status_t Engine::create(const relp_matrix_data_t& md, const relp_config_t& 
                 HIP_TRY(d_shadow_.alloc(std::max(block_, 1) + 1));
                 HIP_TRY(d_shadow_meta_.alloc_raw(2 * sizeof(int32_t)));
                 const int32_t none[2] = {-1, 0};
-                HIP_TRY(hipMemcpy(d_shadow_meta_, none, sizeof none, hipMemcpyHostToDevice));
+                HIP_TRY(d_shadow_meta_.upload(none, 2, stream_));
             }
         }
         HIP_TRY(d_cost_store_.alloc(n_store_));
@@ -289,41 +279,38 @@ relp_status_t Engine::create(const relp_matrix_data_t& md, const relp_config_t& 
         HIP_TRY(d_wr_.alloc(block_));
         HIP_TRY(d_S_.alloc(block_));
         HIP_TRY(d_pos_of_row_.alloc(lay_.m));
-        HIP_TRY(hipMemset(d_pos_of_row_, 0xFF, sizeof(int32_t) * lay_.m));      // -1 everywhere
+        HIP_TRY(d_pos_of_row_.fill_bytes(0xFF, lay_.m, stream_));               // -1 everywhere
     }
     HIP_TRY(d_rmin_.alloc(lay_.m / 8 + 2));          // block minima of the ratio test (8 or 256 rows per block)
     HIP_TRY(h_rec_.alloc(sizeof(PivotRecord)));
     trace_cap_ = std::max(cfg_.trace_capacity, 0);
     if (trace_cap_ > 0) HIP_TRY(d_trace_.alloc(4 * trace_cap_));
 
-    auto up = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
-        return bytes ? hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) : hipSuccess;
-    };
-    HIP_TRY(up(d_cost_, lay_.cost.data(), sizeof(double) * lay_.nr_normal));
-    HIP_TRY(up(d_bound_row_, lay_.bound_row.data(), sizeof(int32_t) * lay_.nr_normal));
-    HIP_TRY(up(d_vrow0_, lay_.vrow0.data(), sizeof(int32_t) * lay_.nr_virtual));
-    HIP_TRY(up(d_vrow1_, lay_.vrow1.data(), sizeof(int32_t) * lay_.nr_virtual));
-    HIP_TRY(up(d_vsign_, lay_.vsign.data(), sizeof(int32_t) * lay_.nr_virtual));
-    HIP_TRY(up(d_column_to_row_, lay_.column_to_row.data(), sizeof(int32_t) * lay_.nr_artificial));
-    HIP_TRY(up(d_basis_, lay_.basis.data(), sizeof(int32_t) * lay_.m));
-    HIP_TRY(up(d_b_, lay_.rhs.data(), sizeof(double) * lay_.m));
-    HIP_TRY(up(d_minus_pi_, lay_.minus_pi.data(), sizeof(double) * lay_.m));
+    HIP_TRY(d_cost_.upload(lay_.cost.data(), lay_.nr_normal, stream_));
+    HIP_TRY(d_bound_row_.upload(lay_.bound_row.data(), lay_.nr_normal, stream_));
+    HIP_TRY(d_vrow0_.upload(lay_.vrow0.data(), lay_.nr_virtual, stream_));
+    HIP_TRY(d_vrow1_.upload(lay_.vrow1.data(), lay_.nr_virtual, stream_));
+    HIP_TRY(d_vsign_.upload(lay_.vsign.data(), lay_.nr_virtual, stream_));
+    HIP_TRY(d_column_to_row_.upload(lay_.column_to_row.data(), lay_.nr_artificial, stream_));
+    HIP_TRY(d_basis_.upload(lay_.basis.data(), lay_.m, stream_));
+    HIP_TRY(d_b_.upload(lay_.rhs.data(), lay_.m, stream_));
+    HIP_TRY(d_minus_pi_.upload(lay_.minus_pi.data(), lay_.m, stream_));
     std::vector<uint8_t> flags(n_alloc_, 0);
     for (int32_t r = 0; r < lay_.m; ++r) flags[lay_.basis[r]] = 1;
-    HIP_TRY(up(d_in_basis_, flags.data(), flags.size()));
+    HIP_TRY(d_in_basis_.upload(flags, stream_));
     // identity rows [row_lo, row_hi): local row i has its 1 in column row_lo + i (BasisInverse::identity)
     if (lay_.row_hi > lay_.row_lo && !tableau_ && !lu_) launch_set_identity(dBinv_, ld_b_, lay_.row_lo, lay_.row_hi, stream_);
     if (tableau_) {
         // T0 = the original matrix in row space (B = I), d = c - c_B' T0 with the phase-1 costs
         idcol_h_ = lay_.basis;                               // the initial basis column of row k is e_k
-        HIP_TRY(up(d_idcol_, idcol_h_.data(), sizeof(int32_t) * lay_.m));
+        HIP_TRY(d_idcol_.upload(idcol_h_.data(), lay_.m, stream_));
         launch_tab_build(tview(), A_base(), ld_a_, table(), stream_);
         cost_store_h_.assign(n_store_, 0.0);
         for (int32_t k = 0; k < lay_.nr_artificial; ++k) cost_store_h_[k] = 1.0;
         std::vector<double> w(ld_b_, 0.0);
         for (int32_t k = 0; k < lay_.nr_artificial; ++k) w[lay_.column_to_row[k]] = 1.0;
-        HIP_TRY(up(d_cost_store_, cost_store_h_.data(), sizeof(double) * n_store_));
-        HIP_TRY(up(d_w_, w.data(), sizeof(double) * ld_b_));
+        HIP_TRY(d_cost_store_.upload(cost_store_h_, stream_));
+        HIP_TRY(d_w_.upload(w, stream_));
         launch_tab_price_init(tview(), d_w_, d_cost_store_, stream_);
     }
     // f64 only: the explicit inverse / the tableau is updated thousands of times on long solves; for sparse problems
@@ -344,7 +331,7 @@ relp_status_t Engine::create(const relp_matrix_data_t& md, const relp_config_t& 
     h_rec_->phase = 1;
     relp_status_t st = upload_rec();
     if (st) return st;
-    HIP_TRY(hipDeviceSynchronize());   // hipMemset on the null stream vs. our non-blocking stream
+    HIP_TRY(hipDeviceSynchronize());   // the end of create: the set-up kernels have run before the launch check below reads their errors
     // (a refused launch -- e.g. more than 2^32 - 1 threads -- returns nothing by itself: without this the engine would start
     // from a tableau that was never built)
     if (hipGetLastError() != hipSuccess) return fail(RELP_E_HIP, "a kernel launch of the set-up failed");
@@ -358,7 +345,7 @@ relp_status_t Engine::create(const relp_matrix_data_t& md, const relp_config_t& 
 relp_status_t Engine::profile_enable(bool enable, int64_t max_launches, int32_t sample_every) {
     prof_stride_ = sample_every > 0 ? sample_every : 1;
     prof_tick_ = 0;
-    HIP_TRY(hipStreamSynchronize(stream_));
+    HIP_TRY(hipStreamSynchronize(stream_));                // the events destroyed below may still be pending
     for (auto e : prof_ev_) (void)hipEventDestroy(e);
     prof_ev_.clear(); prof_kid_.clear(); prof_open_ = false;
     prof_on_ = enable;
@@ -386,7 +373,7 @@ void Engine::prof_end(hipStream_t on) {
 }
 
 relp_status_t Engine::profile_read(int kernel_id, int64_t* launches, double* total_ms) {
-    HIP_TRY(hipStreamSynchronize(stream_));
+    HIP_TRY(hipStreamSynchronize(stream_));                // the events read below must have been reached
     int64_t n = 0; double ms = 0.0;
     for (size_t k = 0; k < prof_kid_.size(); ++k) {
         if (prof_kid_[k] != kernel_id) continue;
@@ -619,8 +606,7 @@ relp_status_t Engine::select_primal_pivot_column(int rule, int32_t* found, int32
 
 relp_status_t Engine::relative_costs(double* out_n) {
     if (!tableau_) enqueue_price(phase_, d_minus_pi_, nullptr, lay_.col_lo, lay_.col_hi);
-    const double* src = tableau_ ? d_d_ + (phase_ == 1 ? 0 : tab_na_) : d_d_;     // the tableau keeps d up to date
-    return fetch(out_n, src, sizeof(double) * nr_columns());
+    HIP_RETURN(d_d_.download(out_n, nr_columns(), stream_, tableau_ && phase_ != 1 ? tab_na_ : 0));     // the tableau keeps d up to date
 }
 
 relp_status_t Engine::generate_column(int32_t column, double* out_m) {
@@ -640,9 +626,8 @@ relp_status_t Engine::generate_column(int32_t column, double* out_m) {
         launch_build_column(A_base(), ld_a_, table(), lay_.m, d_aq_, d_rec_, stream_);
         launch_ftran(Binv_base(), ld_b_, lay_.m, lay_.row_lo, lay_.row_hi, d_aq_, d_alpha_, 0, d_rec_, stream_);
     }
-    if (out_m) HIP_TRY(hipMemcpyAsync(out_m, d_alpha_, sizeof(double) * lay_.m, hipMemcpyDeviceToHost, stream_));
-    HIP_TRY(hipStreamSynchronize(stream_));
-    return RELP_OK;
+    // step-wise call: a failure of its kernels is reported by this call, with or without an output array
+    HIP_RETURN(out_m ? d_alpha_.download(out_m, lay_.m, stream_) : hipStreamSynchronize(stream_));
 }
 
 relp_status_t Engine::generate_element(int32_t row, int32_t column, double* out) {
@@ -671,7 +656,7 @@ relp_status_t Engine::select_primal_pivot_row(int32_t* found, int32_t* row) {
 }
 
 relp_status_t Engine::select_primal_pivot_row_of(const double* column, int32_t* found, int32_t* row) {
-    HIP_TRY(hipMemcpyAsync(d_aq_, column, sizeof(double) * lay_.m, hipMemcpyHostToDevice, stream_));
+    HIP_TRY(d_aq_.upload(column, lay_.m, stream_));
     launch_ratio(d_aq_, d_b_, d_basis_, lay_.m, tolerances(), d_rec_, stream_);
     return read_pivot_row(found, row);
 }
@@ -681,9 +666,9 @@ relp_status_t Engine::bring_into_basis(int32_t column, int32_t row, double cost,
     relp_status_t st = download_rec();
     if (st) return st;
     double alpha_r = 0.0, b_r = 0.0; int32_t lv = 0;
-    HIP_TRY(hipMemcpy(&alpha_r, d_alpha_ + row, sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(&b_r, d_b_ + row, sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(&lv, d_basis_ + row, sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(d_alpha_.download(&alpha_r, 1, stream_, row));
+    HIP_TRY(d_b_.download(&b_r, 1, stream_, row));
+    HIP_TRY(d_basis_.download(&lv, 1, stream_, row));
     if (alpha_r == 0.0) return fail(RELP_E_ZERO_PIVOT, "Pivot value can't be zero.");
     if (!tableau_ && !lu_) enqueue_flush();
     st = edit_rec([&](PivotRecord& r) {                 // (a download of its own: the flush may have reset the block counters)
@@ -699,7 +684,7 @@ relp_status_t Engine::bring_into_basis(int32_t column, int32_t row, double cost,
         launch_update_w(du, lay_.m, d_alpha_, d_rec_, stream_);
         launch_tab_update_vectors(lay_.m, d_alpha_, d_b_, d_basis_, d_in_basis_, d_trace_, trace_cap_, d_rec_, stream_);
         if (++since_flush_ >= block_) enqueue_flush();
-        HIP_TRY(hipStreamSynchronize(stream_));
+        HIP_TRY(hipStreamSynchronize(stream_));            // step-wise call: a failure of its kernels is reported by this call
         if (leaving) *leaving = lv;
         return RELP_OK;
     }
@@ -713,11 +698,10 @@ relp_status_t Engine::bring_into_basis(int32_t column, int32_t row, double cost,
             // r did not fit the eta pool: refactorise the CURRENT basis, form the spike of the entering column again on
             // the fresh factors (alpha itself is unchanged) and update those
             std::vector<double> keep_alpha(lay_.m);
-            HIP_TRY(hipMemcpy(keep_alpha.data(), d_alpha_, sizeof(double) * lay_.m, hipMemcpyDeviceToHost));
+            HIP_TRY(d_alpha_.download(keep_alpha, stream_));
             if ((st = lu_refactor())) return st;
             launch_ft_ftran(dlu_, fts_, pb, column, nullptr, d_alpha_, stream_);
-            HIP_TRY(hipMemcpyAsync(d_alpha_, keep_alpha.data(), sizeof(double) * lay_.m, hipMemcpyHostToDevice, stream_));
-            HIP_TRY(hipStreamSynchronize(stream_));
+            HIP_TRY(d_alpha_.upload(keep_alpha, stream_));
             launch_ft_update(dlu_, fts_, pb, stream_);
         }
         launch_ft_btran(dlu_, fts_, pb, -2, nullptr, d_rho_, stream_);
@@ -736,7 +720,7 @@ relp_status_t Engine::bring_into_basis(int32_t column, int32_t row, double cost,
         launch_update_vectors(lay_.m, d_alpha_, d_rho_, d_b_, d_minus_pi_, d_basis_, d_in_basis_, d_trace_, trace_cap_,
                               d_rec_, stream_);
         if (++since_flush_ >= block_) enqueue_flush();
-        HIP_TRY(hipStreamSynchronize(stream_));
+        HIP_TRY(hipStreamSynchronize(stream_));            // as above
         if (leaving) *leaving = lv;
         return take_lu_status();
     }
@@ -745,7 +729,7 @@ relp_status_t Engine::bring_into_basis(int32_t column, int32_t row, double cost,
     launch_update_vectors(lay_.m, d_alpha_, d_rho_, d_b_, d_minus_pi_, d_basis_, d_in_basis_, d_trace_, trace_cap_, d_rec_,
                           stream_);
     launch_update_inverse(Binv, ld_b_, lay_.m, lay_.row_lo, lay_.row_hi, d_alpha_, d_rho_, d_rec_, stream_);
-    HIP_TRY(hipStreamSynchronize(stream_));
+    HIP_TRY(hipStreamSynchronize(stream_));                // as above
     if (leaving) *leaving = lv;
     return RELP_OK;
 }
@@ -762,9 +746,8 @@ relp_status_t Engine::robust_stats(int64_t* out4) const {
 
 relp_status_t Engine::rescue_unbar_all() {
     if (barred_.empty()) return RELP_OK;
-    HIP_TRY(hipStreamSynchronize(stream_));
     const uint8_t zero = 0;
-    for (int32_t j : barred_) HIP_TRY(hipMemcpy(d_in_basis_ + j, &zero, 1, hipMemcpyHostToDevice));
+    for (int32_t j : barred_) HIP_TRY(d_in_basis_.upload(&zero, 1, stream_, j));
     barred_.clear();
     return RELP_OK;
 }
@@ -793,8 +776,7 @@ relp_status_t Engine::run(int64_t max_iters, int64_t* done, int32_t* outcome) {
             const int32_t q = h_rec_->q;
             const double d_q = h_rec_->d_q;
             std::vector<double> alpha(lay_.m);
-            HIP_TRY(hipStreamSynchronize(stream_));
-            HIP_TRY(hipMemcpy(alpha.data(), d_alpha_, sizeof(double) * lay_.m, hipMemcpyDeviceToHost));
+            HIP_TRY(d_alpha_.download(alpha, stream_));
             double amax = 0.0, apos = 0.0;
             for (double v : alpha) { amax = std::max(amax, std::fabs(v)); apos = std::max(apos, v); }
             const double rel = guard_rel_ > 0.0 ? guard_rel_ : cfg_.tol_pivot;       // the rescue's tolerance is relative to the column
@@ -823,7 +805,7 @@ relp_status_t Engine::run(int64_t max_iters, int64_t* done, int32_t* outcome) {
                 if (apos <= 0.0) break;                                    // a genuinely unbounded column beside barred ones
                 // positive entries that are noise beside the column's size (or below every tolerance): not a column to enter now
                 const uint8_t two = 2;
-                HIP_TRY(hipMemcpy(d_in_basis_ + q, &two, 1, hipMemcpyHostToDevice));
+                HIP_TRY(d_in_basis_.upload(&two, 1, stream_, q));
                 barred_.push_back(q);
                 ++rescue_barred_;
                 if ((st = edit_rec())) return st;
@@ -1098,18 +1080,16 @@ relp_status_t Engine::change_right_hand_side(const int32_t* rows, const double* 
     h_rec_->outcome = DEV_RUNNING;
     if (cnt > 0) {
         const int32_t splits = tab_rhs_splits(lay_.m, cnt, sw_.tab_rhs_splits);
-        if (splits > 1 && splits > rhs_partial_splits_) {
-            HIP_TRY(d_rhs_partial_.alloc((int64_t)splits * ld_b_));
-            rhs_partial_splits_ = splits;
-        }
-        HIP_TRY(hipMemcpyAsync(d_rhs_cols_, cols.data(), sizeof(int32_t) * cnt, hipMemcpyHostToDevice, stream_));
-        HIP_TRY(hipMemcpyAsync(d_rhs_delta_, delta.data(), sizeof(double) * cnt, hipMemcpyHostToDevice, stream_));
-        launch_tab_rhs_change(tview(), deferred(), RhsChange{d_rhs_cols_, d_rhs_delta_, cnt}, p, splits, d_rhs_v_, d_b_, d_rhs_partial_,
-                              ld_b_, stream_);
-        std::vector<double> b(lay_.m);
+        if (splits > 1) HIP_TRY(d_rhs_partial_.ensure((int64_t)splits * ld_b_));
+        // the two lists, b and the basis under one wait (no return before it: cols, delta, b are in flight; no launch on lost lists)
+        hipError_t e = d_rhs_cols_.upload(cols, enqueue_only(stream_));
+        e = first_error(e, d_rhs_delta_.upload(delta, enqueue_only(stream_)));
+        if (e == hipSuccess) launch_tab_rhs_change(tview(), deferred(), RhsChange{d_rhs_cols_, d_rhs_delta_, cnt}, p, splits, d_rhs_v_, d_b_,
+                                                   d_rhs_partial_, ld_b_, stream_);
+        std::vector<double> b(lay_.m);                     // (allocated while the kernel runs)
         std::vector<int32_t> basis(lay_.m);
-        HIP_TRY(hipMemcpyAsync(b.data(), d_b_, sizeof(double) * lay_.m, hipMemcpyDeviceToHost, stream_));
-        if ((st = fetch(basis.data(), d_basis_, sizeof(int32_t) * lay_.m))) return st;       // (waits for cols, delta and b too)
+        e = first_error(e, d_b_.download(b, enqueue_only(stream_)));
+        HIP_TRY(first_error(e, d_basis_.download(basis, stream_)));
         if (hipGetLastError() != hipSuccess) return fail(RELP_E_HIP, "relp_change_right_hand_side: a kernel launch failed");
         h_rec_->minus_objective = -objective_of(basis, b);
         rhs_last_splits_ = splits;
@@ -1162,28 +1142,23 @@ relp_status_t Engine::ranging_query(bool columns, const char* what, const int32_
     const int32_t p = h_rec_->n_eta;
     const TableauView tv = tview();
     const int64_t blocks = columns ? (lay_.m + 255) / 256 : tab_scan_blocks(lay_.sc_hi - lay_.sc_lo);
-    if (count > rng_list_cap_) {
-        HIP_TRY(d_rng_list_.alloc_raw(sizeof(int32_t) * (size_t)count));
-        HIP_TRY(d_rng_ratio_.alloc_raw(sizeof(double) * 2 * (size_t)count));
-        HIP_TRY(d_rng_index_.alloc_raw(sizeof(int32_t) * 2 * (size_t)count));
-        rng_list_cap_ = count;
-    }
-    if (2 * count * blocks > rng_part_cap_) {
-        HIP_TRY(d_rng_part_k_.alloc_raw(sizeof(double) * (size_t)(2 * count * blocks)));
-        HIP_TRY(d_rng_part_j_.alloc_raw(sizeof(int32_t) * (size_t)(2 * count * blocks)));
-        rng_part_cap_ = 2 * count * blocks;
-    }
+    HIP_TRY(d_rng_list_.ensure_raw(sizeof(int32_t) * (size_t)count));
+    HIP_TRY(d_rng_ratio_.ensure_raw(sizeof(double) * 2 * (size_t)count));
+    HIP_TRY(d_rng_index_.ensure_raw(sizeof(int32_t) * 2 * (size_t)count));
+    HIP_TRY(d_rng_part_k_.ensure_raw(sizeof(double) * (size_t)(2 * count * blocks)));
+    HIP_TRY(d_rng_part_j_.ensure_raw(sizeof(int32_t) * (size_t)(2 * count * blocks)));
     std::vector<int32_t> list(rows, rows + count);
     if (columns) for (int32_t& r : list) r = idcol_h_[r];
-    HIP_TRY(hipMemcpyAsync(d_rng_list_, list.data(), sizeof(int32_t) * count, hipMemcpyHostToDevice, stream_));
-    if (columns) launch_tab_rhs_ranging(tv, deferred(), d_b_, d_basis_, tolerances(), d_rng_list_, count, p, d_rng_part_k_, d_rng_ratio_,
-                                        d_rng_index_, stream_);
-    else launch_tab_row_ratios(tv, deferred(), tab_partials(current_rule()), tolerances(), d_rng_list_, count, p, d_rng_part_k_,
-                               d_rng_part_j_, d_rng_ratio_, d_rng_index_, stream_);
-    std::vector<double> ratio(2 * (size_t)count);
+    // the list, the ratios and the indices under one wait (no return before it: list, ratio are in flight; no launch on a lost list)
+    hipError_t e = d_rng_list_.upload(list, enqueue_only(stream_));
+    if (e == hipSuccess && columns) launch_tab_rhs_ranging(tv, deferred(), d_b_, d_basis_, tolerances(), d_rng_list_, count, p, d_rng_part_k_,
+                                                           d_rng_ratio_, d_rng_index_, stream_);
+    else if (e == hipSuccess) launch_tab_row_ratios(tv, deferred(), tab_partials(current_rule()), tolerances(), d_rng_list_, count, p,
+                                                    d_rng_part_k_, d_rng_part_j_, d_rng_ratio_, d_rng_index_, stream_);
+    std::vector<double> ratio(2 * (size_t)count);          // (allocated while the kernel runs)
     std::vector<int32_t> index(2 * (size_t)count);
-    HIP_TRY(hipMemcpyAsync(ratio.data(), d_rng_ratio_, sizeof(double) * 2 * count, hipMemcpyDeviceToHost, stream_));
-    if ((st = fetch(index.data(), d_rng_index_, sizeof(int32_t) * 2 * count))) return st;       // (waits for the list and the ratios too)
+    e = first_error(e, d_rng_ratio_.download(ratio, enqueue_only(stream_)));
+    HIP_TRY(first_error(e, d_rng_index_.download(index, stream_)));
     if (hipGetLastError() != hipSuccess) return fail(RELP_E_HIP, std::string(what) + ": a kernel launch failed");
     if (ratio0) std::copy(ratio.begin(), ratio.begin() + count, ratio0);
     if (index0) std::copy(index.begin(), index.begin() + count, index0);
@@ -1229,9 +1204,8 @@ relp_status_t Engine::finish_phase_one(int32_t* outcome) {
 
 // The head the two zero-level removers share: the basis on the host and the basic artificial variables, ascending.
 relp_status_t Engine::basic_artificials(std::vector<int32_t>* basis, std::vector<int32_t>* arts) {
-    HIP_TRY(hipStreamSynchronize(stream_));            // null-stream copy below vs. kernels on stream_
     basis->resize(lay_.m);
-    HIP_TRY(hipMemcpy(basis->data(), d_basis_, sizeof(int32_t) * lay_.m, hipMemcpyDeviceToHost));
+    HIP_TRY(d_basis_.download(*basis, stream_));
     arts->clear();
     for (int32_t v : *basis) if (v < lay_.nr_artificial) arts->push_back(v);
     std::sort(arts->begin(), arts->end());
@@ -1268,9 +1242,9 @@ relp_status_t Engine::remove_artificial_basis_variables(std::vector<int32_t>& ro
         } else {
             enqueue_price(0, Binv_base() + (int64_t)pivot_row * ld_b_, nullptr, lay_.col_lo, lay_.col_hi);
         }
-        HIP_TRY(hipMemcpyAsync(tau.data(), tableau_ ? d_aq_big() : (double*)d_d_, sizeof(double) * n, hipMemcpyDeviceToHost, stream_));
-        HIP_TRY(hipMemcpyAsync(inb.data(), d_in_basis_, n, hipMemcpyDeviceToHost, stream_));
-        HIP_TRY(hipStreamSynchronize(stream_));
+        if (tableau_) HIP_TRY(download_from(tau, d_aq_big(), stream_));
+        else HIP_TRY(d_d_.download(tau, stream_));
+        HIP_TRY(d_in_basis_.download(inb, stream_));
         int32_t q = -1;
         for (int32_t j = lay_.nr_artificial; j < n; ++j) {
             if (inb[j]) continue;
@@ -1289,9 +1263,6 @@ relp_status_t Engine::remove_artificial_basis_variables(std::vector<int32_t>& ro
 relp_status_t Engine::switch_to_phase_two(const std::vector<int32_t>& rows_to_remove) {
     relp_status_t st;
     if (cfg_.shard_count == 1 || tableau_) enqueue_flush();     // zero-level pivots may have left updates pending
-    // the host-side copies below go through the null stream, which does not order with stream_: everything
-    // enqueued so far (the flush, a possible re-pricing that uses d_w_) must have finished first
-    HIP_TRY(hipStreamSynchronize(stream_));
     if (!rows_to_remove.empty()) {
         std::vector<int32_t> rows(rows_to_remove);          // ascending and distinct: remove_rows walks the list beside the rows
         std::sort(rows.begin(), rows.end());
@@ -1301,7 +1272,7 @@ relp_status_t Engine::switch_to_phase_two(const std::vector<int32_t>& rows_to_re
         if (st) return st;
     }
     std::vector<int32_t> basis(lay_.m);
-    HIP_TRY(hipMemcpy(basis.data(), d_basis_, sizeof(int32_t) * lay_.m, hipMemcpyDeviceToHost));
+    HIP_TRY(d_basis_.download(basis, stream_));
     const int32_t na = lay_.nr_artificial;
     // An artificial variable can survive remove_artificial_basis_variables: when it re-entered the basis in
     // another row than its own, the zero-level pivot of phase_one.rs:236 is made in its ORIGINAL row.  In
@@ -1313,20 +1284,20 @@ relp_status_t Engine::switch_to_phase_two(const std::vector<int32_t>& rows_to_re
     lay_.wrapped_na = na;
     lay_.nr_artificial = 0;
     phase_ = 2;
-    HIP_TRY(hipMemcpy(d_basis_, basis.data(), sizeof(int32_t) * lay_.m, hipMemcpyHostToDevice));
+    HIP_TRY(d_basis_.upload(basis, stream_));
     std::vector<uint8_t> flags(n_alloc_, 0);
     for (int32_t v : basis) {
         if (v >= kWrappedArtificialBase) continue;
         if (v < 0 || v >= lay_.n_provider) return fail(RELP_E_STATE, "basis column out of range at the phase switch");
         flags[v] = 1;
     }
-    HIP_TRY(hipMemcpy(d_in_basis_, flags.data(), flags.size(), hipMemcpyHostToDevice));
+    HIP_TRY(d_in_basis_.upload(flags, stream_));
     // -pi = -(c_B' B^-1) (create_minus_pi_from_artificial, carry/mod.rs:214-248), accumulated over rows in order
     std::vector<double> w = basic_costs(basis, 2, 1.0), b(lay_.m);
     if (cfg_.shard_count > 1 && !tableau_)
         for (double v : w) if (v != 0.0) return fail(RELP_E_UNSUPPORTED, "sharded phase switch needs an all-slack basis");
     if (lu_) for (auto& v : w) v = -v;                 // BTRAN with rhs -c_B gives -pi directly
-    HIP_TRY(hipMemcpy(d_w_, w.data(), sizeof(double) * lay_.m, hipMemcpyHostToDevice));
+    HIP_TRY(d_w_.upload(w.data(), lay_.m, stream_));
     if (lu_) {
         if (lu_status_) return take_lu_status();
         lu_btran(-1, d_w_, d_minus_pi_);
@@ -1334,14 +1305,14 @@ relp_status_t Engine::switch_to_phase_two(const std::vector<int32_t>& rows_to_re
         // phase-2 reduced costs of every stored column: d = c - c_B' T (the artificial block keeps cost 0)
         cost_store_h_.assign(n_store_, 0.0);
         for (int32_t p = 0; p < lay_.nr_normal; ++p) cost_store_h_[tab_na_ + p] = lay_.cost[p];
-        HIP_TRY(hipMemcpy(d_cost_store_, cost_store_h_.data(), sizeof(double) * n_store_, hipMemcpyHostToDevice));
+        HIP_TRY(d_cost_store_.upload(cost_store_h_, stream_));
         launch_tab_price_init(tview(), d_w_, d_cost_store_, stream_);
         tab_partials_valid_ = false;
     } else {
         launch_weighted_column_sums(Binv_base(), ld_b_, lay_.m, d_w_, d_minus_pi_, stream_);
     }
-    // -obj = -sum_i b_i c_B(i) (create_minus_obj_from_artificial, carry/mod.rs:258-271); b has arrived once the record has
-    HIP_TRY(hipMemcpyAsync(b.data(), d_b_, sizeof(double) * lay_.m, hipMemcpyDeviceToHost, stream_));
+    // -obj = -sum_i b_i c_B(i) (create_minus_obj_from_artificial, carry/mod.rs:258-271)
+    HIP_TRY(d_b_.download(b, stream_));
     return edit_rec([&](PivotRecord& r) { r.minus_objective = -objective_of(basis, b); r.last_selected = -1; r.phase = 2; });
 }
 
@@ -1373,67 +1344,65 @@ double Engine::objective_of(const std::vector<int32_t>& basis, const std::vector
 
 // Rank-deficient problems (filter/generic_wrapper.rs:51, carry/mod.rs:650-689, basis_inverse_rows.rs:190-204):
 // delete the given rows (and the same columns of B^-1) everywhere.  Rare, host round trip.
+// The steps are named in the order they run; their copies take their lengths from the buffers and from the old and the new m
+// (lay_.m is the old one until lay_.remove_rows).
 relp_status_t Engine::remove_rows(const std::vector<int32_t>& rows) {
-    if (cfg_.shard_count > 1 && !tableau_) return fail(RELP_E_UNSUPPORTED, "row removal in the sharded revised engine");
-    for (size_t k = 0; k < rows.size(); ++k)
-        if (rows[k] < 0 || rows[k] >= lay_.m || (k > 0 && rows[k] <= rows[k - 1])) return fail(RELP_E_STATE, "rows to remove must be ascending and distinct");
-    std::vector<int32_t> map(lay_.m, 0);   // old row -> new row, -1 = removed
-    {
+    const int32_t m_old = lay_.m, m_new = lay_.m - (int32_t)rows.size();
+    std::vector<int32_t> map(m_old, 0);                // old row -> new row, -1 = removed
+    std::vector<int32_t> perm(m_old), basis_perm;      // RELP_ARTIFICIAL_TEXTBOOK (plan); basis_perm: the basis array after the exchange
+    bool identity_perm = true;
+
+    auto plan = [&]() -> relp_status_t {               // the row map and the permutation
+        if (cfg_.shard_count > 1 && !tableau_) return fail(RELP_E_UNSUPPORTED, "row removal in the sharded revised engine");
+        for (size_t k = 0; k < rows.size(); ++k)
+            if (rows[k] < 0 || rows[k] >= lay_.m || (k > 0 && rows[k] <= rows[k - 1])) return fail(RELP_E_STATE, "rows to remove must be ascending and distinct");
         size_t f = 0; int32_t out = 0;
         for (int32_t i = 0; i < lay_.m; ++i) {
             if (f < rows.size() && rows[f] == i) { map[i] = -1; ++f; } else map[i] = out++;
         }
-    }
-    const int32_t m_new = lay_.m - (int32_t)rows.size();
-    for (int32_t r : rows) if (r >= lay_.mc) return fail(RELP_E_STATE, "only constraint rows can be redundant");
-    // The reference marks the INDEX of a stuck artificial as the redundant row (phase_one.rs:252).  When that index
-    // lands on a <= or >= row, a row that is not redundant is deleted and what remains is no longer the inverse of a
-    // basis of the filtered problem: the literal state is kept from here on, never rebuilt from the columns.
-    for (int32_t r : rows) if (r >= lay_.nr_eq + lay_.nr_range) reinvert_interval_ = 0;
-    // RELP_ARTIFICIAL_TEXTBOOK: an artificial variable that is stuck in basis position r but started in row o != r takes
-    // its own constraint with it, i.e. the pair (constraint o, position r) goes -- always a basis of the filtered problem,
-    // which (r, r) is only if (B^-1)[r][r] != 0.  Positions are labels: exchanging r and o (rows of B^-1 / of the tableau,
-    // b, the basis array) first lets one index name both.  perm: position i of the new order holds the old position perm[i].
-    std::vector<int32_t> perm(lay_.m), basis_perm;
-    for (int32_t i = 0; i < lay_.m; ++i) perm[i] = i;
-    bool identity_perm = true;
-    if (!stuck_artificials_.empty()) {
-        basis_perm.resize(lay_.m);
-        HIP_TRY(hipStreamSynchronize(stream_));
-        HIP_TRY(hipMemcpy(basis_perm.data(), d_basis_, sizeof(int32_t) * lay_.m, hipMemcpyDeviceToHost));
-        for (int32_t a : stuck_artificials_) {
-            const int32_t o = lay_.column_to_row[a];
-            const int32_t cur = (int32_t)(std::find(basis_perm.begin(), basis_perm.end(), a) - basis_perm.begin());
-            if (cur >= lay_.m) return fail(RELP_E_STATE, "a stuck artificial variable is not basic");
-            if (cur == o) continue;
-            std::swap(basis_perm[cur], basis_perm[o]); std::swap(perm[cur], perm[o]);
-            identity_perm = false;
+        for (int32_t r : rows) if (r >= lay_.mc) return fail(RELP_E_STATE, "only constraint rows can be redundant");
+        // The reference marks the INDEX of a stuck artificial as the redundant row (phase_one.rs:252).  When that index
+        // lands on a <= or >= row, a row that is not redundant is deleted and what remains is no longer the inverse of a
+        // basis of the filtered problem: the literal state is kept from here on, never rebuilt from the columns.
+        for (int32_t r : rows) if (r >= lay_.nr_eq + lay_.nr_range) reinvert_interval_ = 0;
+        // RELP_ARTIFICIAL_TEXTBOOK: an artificial variable that is stuck in basis position r but started in row o != r takes
+        // its own constraint with it, i.e. the pair (constraint o, position r) goes -- always a basis of the filtered problem,
+        // which (r, r) is only if (B^-1)[r][r] != 0.  Positions are labels: exchanging r and o (rows of B^-1 / of the tableau,
+        // b, the basis array) first lets one index name both.  perm: position i of the new order holds the old position perm[i].
+        for (int32_t i = 0; i < lay_.m; ++i) perm[i] = i;
+        if (!stuck_artificials_.empty()) {
+            basis_perm.resize(lay_.m);
+            HIP_TRY(d_basis_.download(basis_perm, stream_));
+            for (int32_t a : stuck_artificials_) {
+                const int32_t o = lay_.column_to_row[a];
+                const int32_t cur = (int32_t)(std::find(basis_perm.begin(), basis_perm.end(), a) - basis_perm.begin());
+                if (cur >= lay_.m) return fail(RELP_E_STATE, "a stuck artificial variable is not basic");
+                if (cur == o) continue;
+                std::swap(basis_perm[cur], basis_perm[o]); std::swap(perm[cur], perm[o]);
+                identity_perm = false;
+            }
         }
-    }
-    // B^-1 (or the tableau), b, basis
-    const bool no_inv = tableau_ || lu_;
-    std::vector<double> Bh(no_inv ? 1 : (size_t)lay_.m * ld_b_), b(lay_.m);
-    std::vector<int32_t> basis(lay_.m);
-    if (tableau_) {
-        // every stored column loses the rows; the columns that were the identity of those rows stay as
-        // (never priced) artificial columns.  Column by column to bound the host buffer.
-        HIP_TRY(hipStreamSynchronize(stream_));
-        std::vector<double> col(ld_t_), coln(ld_t_);
-        const int32_t n_owned = lay_.sc_hi - lay_.sc_lo;           // the stored columns of this rank (all of them unsharded)
+        return RELP_OK;
+    };
+    // The tableau: every stored column loses the rows; the columns that were the identity of those rows stay as (never priced)
+    // artificial columns.  Column by column to bound the host buffer.
+    auto tableau_columns = [&]() -> relp_status_t {
+        std::vector<double> col(m_old), coln(ld_t_);
+        const int32_t n_owned = lay_.sc_hi - lay_.sc_lo;               // the stored columns of this rank (all of them unsharded)
         for (int32_t c = 0; c < n_owned; ++c) {
-            HIP_TRY(hipMemcpy(col.data(), dT0_ + (int64_t)c * ld_t_, sizeof(double) * lay_.m, hipMemcpyDeviceToHost));
+            HIP_TRY(dT0_.download(col, stream_, (int64_t)c * ld_t_));
             std::fill(coln.begin(), coln.end(), 0.0);
-            for (int32_t i = 0; i < lay_.m; ++i) if (map[i] >= 0) coln[map[i]] = col[perm[i]];
-            HIP_TRY(hipMemcpy(dT0_ + (int64_t)c * ld_t_, coln.data(), sizeof(double) * ld_t_, hipMemcpyHostToDevice));
+            for (int32_t i = 0; i < m_old; ++i) if (map[i] >= 0) coln[map[i]] = col[perm[i]];
+            HIP_TRY(dT0_.upload(coln, stream_, (int64_t)c * ld_t_));
         }
         std::vector<int32_t> idn;
-        for (int32_t i = 0; i < lay_.m; ++i) if (map[i] >= 0) idn.push_back(idcol_h_[i]);
+        for (int32_t i = 0; i < m_old; ++i) if (map[i] >= 0) idn.push_back(idcol_h_[i]);
         idcol_h_ = idn;
-        HIP_TRY(hipMemcpy(d_idcol_, idcol_h_.data(), sizeof(int32_t) * idcol_h_.size(), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemset(d_pos_of_row_, 0xFF, sizeof(int32_t) * lay_.m));
-    } else if (lu_) {
-        // the CSC matrix loses the rows; the factors are rebuilt below
-        HIP_TRY(hipStreamSynchronize(stream_));
+        HIP_TRY(d_idcol_.upload(idcol_h_, stream_));
+        HIP_RETURN(d_pos_of_row_.fill_bytes(0xFF, m_old, stream_));
+    };
+    // The LU engine: the CSC matrix loses the rows; the factors are rebuilt at the end
+    auto csc_matrix = [&]() -> relp_status_t {
         std::vector<int64_t> np(lay_.nr_normal + 1, 0);
         size_t o = 0;
         for (int32_t j = 0; j < lay_.nr_normal; ++j) {
@@ -1442,64 +1411,69 @@ relp_status_t Engine::remove_rows(const std::vector<int32_t>& rows) {
             np[j + 1] = (int64_t)o;
         }
         hc_idx_.resize(o); hc_val_.resize(o); hc_ptr_ = np;
-        HIP_TRY(hipMemcpy(d_cptr_, hc_ptr_.data(), sizeof(int64_t) * hc_ptr_.size(), hipMemcpyHostToDevice));
-        if (o) {
-            HIP_TRY(hipMemcpy(d_cidx_, hc_idx_.data(), sizeof(int32_t) * o, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(d_cval_, hc_val_.data(), sizeof(double) * o, hipMemcpyHostToDevice));
-        }
-        if (ft_) { const relp_status_t pst = ft_build_price_ell(); if (pst) return pst; }
-    } else {
-        HIP_TRY(hipMemcpy(Bh.data(), dBinv_, Bh.size() * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    HIP_TRY(hipMemcpy(b.data(), d_b_, sizeof(double) * lay_.m, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(basis.data(), d_basis_, sizeof(int32_t) * lay_.m, hipMemcpyDeviceToHost));
-    if (!identity_perm) {                              // the stuck artificial variables move into their own rows (see above)
-        std::vector<double> b0(b), B0;
-        for (int32_t i = 0; i < lay_.m; ++i) b[i] = b0[perm[i]];
-        basis = basis_perm;
-        if (!no_inv) {
-            B0 = Bh;
-            for (int32_t i = 0; i < lay_.m; ++i)
+        HIP_TRY(d_cptr_.upload(hc_ptr_, stream_));
+        HIP_TRY(d_cidx_.upload(hc_idx_, stream_));
+        HIP_TRY(d_cval_.upload(hc_val_, stream_));
+        return ft_ ? ft_build_price_ell() : RELP_OK;
+    };
+    // The m-vectors b and basis -- and the explicit inverse, whose rows move as they do and whose columns go with the rows
+    auto m_vectors = [&]() -> relp_status_t {
+        const bool no_inv = tableau_ || lu_;
+        std::vector<double> Bh(no_inv ? 0 : (size_t)m_old * ld_b_), b(m_old);
+        std::vector<int32_t> basis(m_old);
+        HIP_TRY(dBinv_.download(Bh, stream_));
+        HIP_TRY(d_b_.download(b, stream_));
+        HIP_TRY(d_basis_.download(basis, stream_));
+        if (!identity_perm) {                              // the stuck artificial variables move into their own rows (plan)
+            const std::vector<double> b0(b), B0(Bh);
+            for (int32_t i = 0; i < m_old; ++i) b[i] = b0[perm[i]];
+            basis = basis_perm;
+            for (int32_t i = 0; i < m_old && !no_inv; ++i)
                 if (perm[i] != i) std::copy(B0.begin() + (size_t)perm[i] * ld_b_, B0.begin() + (size_t)(perm[i] + 1) * ld_b_, Bh.begin() + (size_t)i * ld_b_);
         }
-    }
-    std::vector<double> Bn(no_inv ? 1 : (size_t)lay_.m * ld_b_, 0.0), bn(lay_.m, 0.0);
-    std::vector<int32_t> basisn(lay_.m, 0);
-    for (int32_t i = 0; i < lay_.m; ++i) {
-        if (map[i] < 0) continue;
-        if (!no_inv)
-            for (int32_t j = 0; j < lay_.m; ++j) if (map[j] >= 0) Bn[(size_t)map[i] * ld_b_ + map[j]] = Bh[(size_t)i * ld_b_ + j];
-        bn[map[i]] = b[i];
-        basisn[map[i]] = basis[i];
-    }
-    if (!no_inv) HIP_TRY(hipMemcpy(dBinv_, Bn.data(), Bn.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(d_b_, 0, sizeof(double) * ld_b_));
-    HIP_TRY(hipMemcpy(d_b_, bn.data(), sizeof(double) * m_new, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_basis_, basisn.data(), sizeof(int32_t) * m_new, hipMemcpyHostToDevice));
-    // A: drop the rows inside every structural column (the tableau engine no longer reads A)
-    if (lay_.nr_normal > 0 && !lu_ && cfg_.shard_count == 1) {   // (the unsharded tableau engine re-tabulates from A)
+        std::vector<double> Bn(Bh.size(), 0.0), bn(m_new, 0.0);
+        std::vector<int32_t> basisn(m_new, 0);
+        for (int32_t i = 0; i < m_old; ++i) {
+            if (map[i] < 0) continue;
+            if (!no_inv)
+                for (int32_t j = 0; j < m_old; ++j) if (map[j] >= 0) Bn[(size_t)map[i] * ld_b_ + map[j]] = Bh[(size_t)i * ld_b_ + j];
+            bn[map[i]] = b[i];
+            basisn[map[i]] = basis[i];
+        }
+        HIP_TRY(dBinv_.upload(Bn, stream_));
+        HIP_TRY(d_b_.zero(ld_b_, stream_));
+        HIP_TRY(d_b_.upload(bn, stream_));
+        HIP_RETURN(d_basis_.upload(basisn, stream_));
+    };
+    // A: drop the rows inside every structural column (the LU engine holds no dense A; a sharded tableau no longer reads it, the
+    // unsharded one re-tabulates from it)
+    auto dense_matrix = [&]() -> relp_status_t {
+        if (lay_.nr_normal <= 0 || lu_ || cfg_.shard_count != 1) return RELP_OK;
         std::vector<double> Ah((size_t)ld_a_ * lay_.nr_normal);
-        HIP_TRY(hipMemcpy(Ah.data(), dA_, Ah.size() * sizeof(double), hipMemcpyDeviceToHost));
-        std::vector<double> An((size_t)ld_a_ * lay_.nr_normal, 0.0);
+        HIP_TRY(dA_.download(Ah, stream_));
+        std::vector<double> An(Ah.size(), 0.0);
         for (int32_t j = 0; j < lay_.nr_normal; ++j)
             for (int32_t i = 0; i < lay_.mc; ++i) if (map[i] >= 0) An[(size_t)j * ld_a_ + map[i]] = Ah[(size_t)j * ld_a_ + i];
-        if (!dA_.owned()) HIP_TRY(dA_.alloc((int64_t)An.size()));      // (the caller's matrix was adopted: it stays as it is)
-        HIP_TRY(hipMemcpy(dA_, An.data(), An.size() * sizeof(double), hipMemcpyHostToDevice));
-    }
-    lay_.remove_rows(map);
-    HIP_TRY(hipMemcpy(d_bound_row_, lay_.bound_row.data(), sizeof(int32_t) * lay_.nr_normal, hipMemcpyHostToDevice));
-    if (lay_.nr_virtual) {
-        HIP_TRY(hipMemcpy(d_vrow0_, lay_.vrow0.data(), sizeof(int32_t) * lay_.nr_virtual, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_vrow1_, lay_.vrow1.data(), sizeof(int32_t) * lay_.nr_virtual, hipMemcpyHostToDevice));
-    }
-    // stale tails of the m-vectors must be zero for the 16-byte loads
-    HIP_TRY(hipMemset(d_alpha_, 0, sizeof(double) * ld_b_));
-    HIP_TRY(hipMemset(d_aq_, 0, sizeof(double) * ld_b_));
-    HIP_TRY(hipMemset(d_rho_, 0, sizeof(double) * ld_b_));
-    HIP_TRY(hipMemset(d_minus_pi_, 0, sizeof(double) * ld_b_));
-    HIP_TRY(hipDeviceSynchronize());
-    if (lu_) return lu_refactor();
-    return RELP_OK;
+        if (!dA_.owned()) HIP_TRY(dA_.alloc((int64_t)An.size()));          // (the caller's matrix was adopted: it stays as it is)
+        HIP_RETURN(dA_.upload(An, stream_));
+    };
+    // The layout's tables (from here on lay_.m is the new m), and the stale tails of the other m-vectors, which must be zero for
+    // the 16-byte loads
+    auto layout_tables = [&]() -> relp_status_t {
+        lay_.remove_rows(map);
+        HIP_TRY(d_bound_row_.upload(lay_.bound_row.data(), lay_.nr_normal, stream_));
+        HIP_TRY(d_vrow0_.upload(lay_.vrow0.data(), lay_.nr_virtual, stream_));
+        HIP_TRY(d_vrow1_.upload(lay_.vrow1.data(), lay_.nr_virtual, stream_));
+        for (DeviceBuf<double>* v : {&d_alpha_, &d_aq_, &d_rho_, &d_minus_pi_}) HIP_TRY(v->zero(ld_b_, stream_));
+        return RELP_OK;
+    };
+    relp_status_t st = plan();
+    if (!st && tableau_) st = tableau_columns();
+    if (!st && lu_ && !tableau_) st = csc_matrix();
+    if (!st) st = m_vectors();
+    if (!st) st = dense_matrix();
+    if (!st) st = layout_tables();
+    return !st && lu_ ? lu_refactor() : st;
 }
 
 relp_status_t Engine::set_reinversion_interval(int64_t pivots) {
@@ -1520,7 +1494,7 @@ relp_status_t Engine::build_basis_columns(const std::vector<int32_t>& basis,
     std::vector<double> colbuf(std::max(lay_.mc, 1));
     hipError_t copied = hipSuccess;
     auto dense_column = [&](int32_t p, auto&& put) {
-        copied = hipMemcpy(colbuf.data(), dA_ + (int64_t)(p - lay_.col_lo) * ld_a_, sizeof(double) * lay_.mc, hipMemcpyDeviceToHost);
+        copied = dA_.download(colbuf.data(), lay_.mc, stream_, (int64_t)(p - lay_.col_lo) * ld_a_);
         if (copied == hipSuccess)
             for (int32_t r = 0; r < lay_.mc; ++r) if (colbuf[r] != 0.0) put(r, colbuf[r]);
     };
@@ -1549,10 +1523,9 @@ relp_status_t Engine::refactor_current_basis(std::vector<int32_t>* basis, std::v
     *factored = false;
     since_reinvert_ = 0;
     enqueue_flush();
-    HIP_TRY(hipStreamSynchronize(stream_));
-    if (cfg_.auto_reinversion) { b_before->resize(lay_.m); HIP_TRY(hipMemcpy(b_before->data(), d_b_, sizeof(double) * lay_.m, hipMemcpyDeviceToHost)); }
+    if (cfg_.auto_reinversion) { b_before->resize(lay_.m); HIP_TRY(d_b_.download(*b_before, stream_)); }
     basis->resize(lay_.m);
-    HIP_TRY(hipMemcpy(basis->data(), d_basis_, sizeof(int32_t) * lay_.m, hipMemcpyDeviceToHost));
+    HIP_TRY(d_basis_.download(*basis, stream_));
     std::vector<std::vector<std::pair<int32_t, double>>> cols;
     relp_status_t st = build_basis_columns(*basis, &cols);
     if (st) return st;
@@ -1564,10 +1537,7 @@ relp_status_t Engine::refactor_current_basis(std::vector<int32_t>* basis, std::v
     return RELP_OK;
 }
 
-relp_status_t Engine::ensure_lu_scratch() {
-    if (!d_lu_scratch_) HIP_TRY(d_lu_scratch_.alloc(ld_b_));
-    return RELP_OK;
-}
+relp_status_t Engine::ensure_lu_scratch() { HIP_RETURN(d_lu_scratch_.ensure(ld_b_)); }
 
 // Where the batch solve over `rhs_count` right-hand sides keeps x.  In LDS while it fits (groups = 0).  Otherwise, or with
 // RELP_RETAB_GLOBAL=1, in slabs of global memory: G = min(right-hand sides, 2 workgroups per CU, the slabs that fit into
@@ -1583,11 +1553,7 @@ relp_status_t Engine::batch_solve_slabs(int32_t rhs_count, LuSlabs* slabs) {
     groups = std::min<int64_t>(groups, (int64_t(256) << 20) / ((int64_t)sizeof(double) * ld_b_));
     if (sw_.retab_groups > 0) groups = std::min<int64_t>(groups, sw_.retab_groups);
     groups = std::max<int64_t>(groups, 1);
-    if (lu_slab_cap_ < groups * ld_b_) {
-        lu_slab_cap_ = 0;
-        HIP_TRY(d_lu_slabs_.alloc(groups * ld_b_));
-        lu_slab_cap_ = groups * ld_b_;
-    }
+    HIP_TRY(d_lu_slabs_.ensure(groups * ld_b_));
     slabs->x = d_lu_slabs_;
     slabs->groups = (int32_t)groups;
     slab_groups_last_ = slabs->groups;
@@ -1597,29 +1563,27 @@ relp_status_t Engine::batch_solve_slabs(int32_t rhs_count, LuSlabs* slabs) {
 
 relp_status_t Engine::retab_stats(int64_t* out4) const {
     out4[0] = batch_solves_lds_; out4[1] = batch_solves_slab_; out4[2] = slab_groups_last_;
-    out4[3] = lu_slab_cap_ * (int64_t)sizeof(double);
+    out4[3] = d_lu_slabs_.count() * (int64_t)sizeof(double);
     return RELP_OK;
 }
 
 // With the factors of the basis on the device: the rows of B^-1 by m unit BTRANs written in place (the one-off
-// `BasisInverseRows::invert`, basis_inverse_rows.rs:103-129), -pi = -(w' B^-1) (carry/mod.rs:214-248) and b = B^-1 rhs, whose
-// download into `b` is enqueued, not awaited.  `rearm`: the record is re-armed before the FTRAN (a warm start may find it decided).
+// `BasisInverseRows::invert`, basis_inverse_rows.rs:103-129), -pi = -(w' B^-1) (carry/mod.rs:214-248) and b = B^-1 rhs, also
+// downloaded into `b`.  `rearm`: the record is re-armed before the FTRAN (a warm start may find it decided).
 relp_status_t Engine::inverse_from_factors(const std::vector<double>& w, bool rearm, std::vector<double>* b) {
     LuSlabs slabs;
     if (const relp_status_t st = batch_solve_slabs(lay_.m, &slabs)) return st;
-    HIP_TRY(hipMemsetAsync(dBinv_, 0, sizeof(double) * (size_t)lay_.m * ld_b_, stream_));
+    HIP_TRY(dBinv_.zero((int64_t)lay_.m * ld_b_, stream_));
     DeferredUpdate none = deferred();
     none.kmax = 0;
     launch_lu_btran_rows(dlu_, none, dBinv_, ld_b_, slabs, stream_);
-    HIP_TRY(hipMemcpyAsync(d_w_, w.data(), sizeof(double) * ld_b_, hipMemcpyHostToDevice, stream_));
-    HIP_TRY(hipMemcpyAsync(d_aq_, lay_.rhs.data(), sizeof(double) * lay_.m, hipMemcpyHostToDevice, stream_));
-    HIP_TRY(hipStreamSynchronize(stream_));             // w, lay_.rhs are host buffers
+    HIP_TRY(d_w_.upload(w, stream_));
+    HIP_TRY(d_aq_.upload(lay_.rhs.data(), lay_.m, stream_));
     launch_weighted_column_sums(dBinv_, ld_b_, lay_.m, d_w_, d_minus_pi_, stream_);
     if (rearm) { const relp_status_t st = edit_rec(); if (st) return st; }
     launch_ftran(dBinv_, ld_b_, lay_.m, 0, lay_.m, d_aq_, d_b_, 0, d_rec_, stream_);
     b->resize(lay_.m);
-    HIP_TRY(hipMemcpyAsync(b->data(), d_b_, sizeof(double) * lay_.m, hipMemcpyDeviceToHost, stream_));
-    return RELP_OK;
+    HIP_RETURN(d_b_.download(*b, stream_));
 }
 
 static double weighted_sum(const std::vector<double>& w, const std::vector<double>& b) {     // over the rows in order
@@ -1645,13 +1609,12 @@ relp_status_t Engine::retabulate(bool adapt_interval) {
     LuSlabs slabs;
     if ((st = batch_solve_slabs(lay_.sc_hi - c_first, &slabs))) return st;
     launch_lu_ftran_cols(dlu_, tv, A_base(), ld_a_, storage, c_first, lay_.sc_hi - c_first, slabs, stream_);
-    HIP_TRY(hipMemcpyAsync(d_aq_, lay_.rhs.data(), sizeof(double) * lay_.m, hipMemcpyHostToDevice, stream_));
-    HIP_TRY(hipStreamSynchronize(stream_));
+    HIP_TRY(d_aq_.upload(lay_.rhs.data(), lay_.m, stream_));
     launch_lu_ftran(dlu_, d_aq_, d_b_, d_lu_scratch_, nullptr, stream_);                 // b = B^-1 rhs
     tableau_reprice();                                  // as after every few flushes
     tab_partials_valid_ = true;
     std::vector<double> b(lay_.m);
-    HIP_TRY(hipMemcpyAsync(b.data(), d_b_, sizeof(double) * lay_.m, hipMemcpyDeviceToHost, stream_));
+    HIP_TRY(d_b_.download(b, stream_));
     if ((st = download_rec())) return st;
     h_rec_->minus_objective = -objective_of(basis, b);
     ++reinversions_;
@@ -1713,43 +1676,40 @@ relp_status_t Engine::from_basis(const int32_t* basis_columns) {
         // T = B^-1 [A | I] for the given basis: factorise it (host, like every refactorisation), then every stored column
         // by one FTRAN each in a single launch (re-tabulation), b = B^-1 rhs, d = c - c_B' T
         enqueue_flush();
-        HIP_TRY(hipStreamSynchronize(stream_));
         if ((st = check_basis_columns(basis, &flags))) return st;
         const int32_t keep_na = lay_.nr_artificial, keep_phase = phase_;
         lay_.nr_artificial = 0; phase_ = 2;
-        HIP_TRY(hipMemcpy(d_basis_, basis.data(), sizeof(int32_t) * lay_.m, hipMemcpyHostToDevice));
+        HIP_TRY(d_basis_.upload(basis, stream_));
         cost_store_h_.assign(n_store_, 0.0);
         for (int32_t p = 0; p < lay_.nr_normal; ++p) cost_store_h_[tab_na_ + p] = lay_.cost[p];
-        HIP_TRY(hipMemcpy(d_cost_store_, cost_store_h_.data(), sizeof(double) * n_store_, hipMemcpyHostToDevice));
+        HIP_TRY(d_cost_store_.upload(cost_store_h_, stream_));
         st = retabulate();
         if (st || !retab_done_) {
             lay_.nr_artificial = keep_na; phase_ = keep_phase;
             return st ? st : fail(RELP_E_SINGULAR, "from_basis: the basis could not be factorised");
         }
-        HIP_TRY(hipMemcpy(d_in_basis_, flags.data(), flags.size(), hipMemcpyHostToDevice));
+        HIP_TRY(d_in_basis_.upload(flags, stream_));
         tab_partials_valid_ = false;
         return edit_rec(phase_two);
     }
     if (lu_) {
         // any basis: factorise it, b = B^-1 rhs (FTRAN), -pi = -c_B' B^-1 (BTRAN), carry/mod.rs:428-463
-        HIP_TRY(hipStreamSynchronize(stream_));
         if ((st = check_basis_columns(basis, &flags))) return st;
         lay_.nr_artificial = 0; phase_ = 2;
-        HIP_TRY(hipMemcpy(d_basis_, basis.data(), sizeof(int32_t) * lay_.m, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_in_basis_, flags.data(), flags.size(), hipMemcpyHostToDevice));
+        HIP_TRY(d_basis_.upload(basis, stream_));
+        HIP_TRY(d_in_basis_.upload(flags, stream_));
         since_flush_ = 1;                              // force: the factors are stale
         if ((st = lu_refactor())) return st;
         const std::vector<double> w = basic_costs(basis, 2, -1.0);        // BTRAN with rhs -c_B gives -pi directly
         std::vector<double> b(lay_.m);
-        HIP_TRY(hipMemcpy(d_w_, w.data(), sizeof(double) * lay_.m, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_aq_, lay_.rhs.data(), sizeof(double) * lay_.m, hipMemcpyHostToDevice));
+        HIP_TRY(d_w_.upload(w.data(), lay_.m, stream_));
+        HIP_TRY(d_aq_.upload(lay_.rhs.data(), lay_.m, stream_));
         lu_ftran(d_aq_, d_b_, nullptr);
         lu_btran(-1, d_w_, d_minus_pi_);
-        HIP_TRY(hipMemcpyAsync(b.data(), d_b_, sizeof(double) * lay_.m, hipMemcpyDeviceToHost, stream_));
+        HIP_TRY(d_b_.download(b, stream_));
         return edit_rec([&](PivotRecord& r) { r.minus_objective = -objective_of(basis, b); phase_two(r); });
     }
     enqueue_flush();                                   // leaves the deferred state empty
-    HIP_TRY(hipStreamSynchronize(stream_));
     if ((st = check_basis_columns(basis, &flags))) return st;
     double objective = 0.0;
     bool unit_basis = true;
@@ -1769,9 +1729,9 @@ relp_status_t Engine::from_basis(const int32_t* basis_columns) {
             Bn[(size_t)i * ld_b_ + row] = (double)lay_.vsign[v];
             b[i] = (double)lay_.vsign[v] * lay_.rhs[row];
         }
-        HIP_TRY(hipMemcpy(dBinv_, Bn.data(), Bn.size() * sizeof(double), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_b_, b.data(), sizeof(double) * lay_.m, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_minus_pi_, minus_pi.data(), sizeof(double) * ld_b_, hipMemcpyHostToDevice));
+        HIP_TRY(dBinv_.upload(Bn, stream_));
+        HIP_TRY(d_b_.upload(b, stream_));
+        HIP_TRY(d_minus_pi_.upload(minus_pi, stream_));
     } else {
         // any basis: factorise it on the host (relp_lu.cpp, like every refactorisation); the rows of B^-1, -pi and b on the device
         std::vector<int32_t> columns(basis);               // tableau column indices of the current kind
@@ -1785,11 +1745,10 @@ relp_status_t Engine::from_basis(const int32_t* basis_columns) {
         const std::vector<double> w = basic_costs(basis, 2, 1.0);
         std::vector<double> b;
         if ((st = inverse_from_factors(w, true, &b))) return st;
-        HIP_TRY(hipStreamSynchronize(stream_));
         objective = weighted_sum(w, b);
     }
-    HIP_TRY(hipMemcpy(d_basis_, basis.data(), sizeof(int32_t) * lay_.m, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_in_basis_, flags.data(), flags.size(), hipMemcpyHostToDevice));
+    HIP_TRY(d_basis_.upload(basis, stream_));
+    HIP_TRY(d_in_basis_.upload(flags, stream_));
     lay_.nr_artificial = 0; phase_ = 2;
     return edit_rec([&](PivotRecord& r) { r.minus_objective = -objective; phase_two(r); });
 }
@@ -1809,15 +1768,15 @@ relp_status_t Engine::get_vector(int which, double* out) {
         if (cfg_.shard_count > 1) return fail(RELP_E_UNSUPPORTED, "-pi of the sharded tableau: d is column-sharded");
         // -pi_k = d_j - c_j for the stored column j that was e_k originally
         std::vector<double> d(n_store_);
-        if (const relp_status_t st = fetch(d.data(), d_d_, sizeof(double) * n_store_)) return st;
+        HIP_TRY(d_d_.download(d, stream_));
         for (int32_t k = 0; k < lay_.m; ++k) out[k] = d[idcol_h_[k]] - cost_store_h_[idcol_h_[k]];
         return RELP_OK;
     }
-    const double* src = which == 0 ? d_b_ : which == 1 ? d_minus_pi_ : d_alpha_;
-    return fetch(out, src, sizeof(double) * lay_.m);
+    const DeviceBuf<double>& src = which == 0 ? d_b_ : which == 1 ? d_minus_pi_ : d_alpha_;
+    HIP_RETURN(src.download(out, lay_.m, stream_));
 }
 
-relp_status_t Engine::get_basis_indices(int32_t* out) { return fetch(out, d_basis_, sizeof(int32_t) * lay_.m); }
+relp_status_t Engine::get_basis_indices(int32_t* out) { HIP_RETURN(d_basis_.download(out, lay_.m, stream_)); }
 
 relp_status_t Engine::get_basis_inverse(double* out) {
     if (cfg_.shard_count > 1) return fail(RELP_E_UNSUPPORTED, "B^-1 is row-sharded");
@@ -1829,11 +1788,9 @@ relp_status_t Engine::get_basis_inverse(double* out) {
         // columns of the original identity columns
         if (lu_) for (int32_t i = 0; i < lay_.m; ++i) lu_btran(i, nullptr, tmp + (int64_t)i * lay_.m);
         else launch_tab_gather_columns(tview(), d_idcol_, tmp, stream_);
-        return fetch(out, tmp, sizeof(double) * lay_.m * lay_.m);
+        HIP_RETURN(tmp.download(out, (int64_t)lay_.m * lay_.m, stream_));
     }
-    HIP_TRY(hipStreamSynchronize(stream_));
-    HIP_TRY(hipMemcpy2D(out, sizeof(double) * lay_.m, dBinv_, sizeof(double) * ld_b_, sizeof(double) * lay_.m, lay_.m, hipMemcpyDeviceToHost));
-    return RELP_OK;
+    HIP_RETURN(dBinv_.copy_2d(kToHost, out, lay_.m, lay_.m, lay_.m, ld_b_, stream_));
 }
 
 relp_status_t Engine::current_bfs(int32_t* cols, double* vals, int32_t cap, int32_t* count) {
@@ -1866,7 +1823,7 @@ relp_status_t Engine::get_degenerate_pivots(int64_t* out) {
 
 relp_status_t Engine::tab_flush_stats(int64_t* out2) {
     unsigned long long h[2] = {0, 0};
-    if (d_fstats_) { const relp_status_t st = fetch(h, d_fstats_, sizeof h); if (st) return st; }
+    if (d_fstats_) HIP_TRY(d_fstats_.download(h, 2, stream_));
     out2[0] = (int64_t)h[0]; out2[1] = (int64_t)h[1];
     return RELP_OK;
 }
@@ -1879,7 +1836,7 @@ relp_status_t Engine::get_trace(int32_t* phase, int32_t* entering, int32_t* row,
     const int64_t k = std::min(n, cap);
     int32_t* outs[4] = {phase, entering, row, leaving};
     for (int f = 0; f < 4; ++f)
-        if (outs[f] && k > 0) HIP_TRY(hipMemcpy(outs[f], d_trace_ + f * trace_cap_, sizeof(int32_t) * k, hipMemcpyDeviceToHost));
+        if (outs[f] && k > 0) HIP_TRY(d_trace_.download(outs[f], k, stream_, f * trace_cap_));
     if (count) *count = n;
     return RELP_OK;
 }

@@ -287,8 +287,7 @@ class Engine : private EngineQueue {
     // relp_change_right_hand_side: the compacted list (identity column, delta) of a change, v = the pending rows' share and the
     // per-split partial sums (relp_kernels.h: launch_tab_rhs_change); what relp_rhs_stats reports
     DeviceBuf<int32_t> d_rhs_cols_;
-    DeviceBuf<double> d_rhs_delta_, d_rhs_v_, d_rhs_partial_;
-    int32_t rhs_partial_splits_ = 0;                   // splits d_rhs_partial_ holds (allocated at the first split launch, grown on demand)
+    DeviceBuf<double> d_rhs_delta_, d_rhs_v_, d_rhs_partial_;      // (d_rhs_partial_: allocated at the first split launch, grown on demand)
     int64_t rhs_changes_ = 0, rhs_columns_ = 0;
     int32_t rhs_last_p_ = 0, rhs_last_splits_ = 0;
     // relp_row_ratios / relp_rhs_ranging: the uploaded list (rows, or their identity columns), the per-(direction, entry, block)
@@ -298,7 +297,6 @@ class Engine : private EngineQueue {
                                 double* ratio1, int32_t* index1);
     DeviceBuf<int32_t> d_rng_list_, d_rng_part_j_, d_rng_index_;
     DeviceBuf<double> d_rng_part_k_, d_rng_ratio_;
-    int64_t rng_list_cap_ = 0, rng_part_cap_ = 0;
     int64_t rng_ratio_calls_ = 0, rng_ratio_rows_ = 0, rng_ranging_calls_ = 0;
     int32_t rng_last_p_ = 0;
     // sparse LU engine (cfg.engine == RELP_ENGINE_LU): B^-1 = (I + W S') (L U)^-1, refactor every block_ pivots
@@ -306,19 +304,19 @@ class Engine : private EngineQueue {
     std::vector<int64_t> hc_ptr_; std::vector<int32_t> hc_idx_; std::vector<double> hc_val_;   // host CSC of A
     DeviceBuf<int64_t> d_cptr_; DeviceBuf<int32_t> d_cidx_; DeviceBuf<double> d_cval_;         // device CSC of A
     LUFactors hlu_;
-    DeviceBuf<char> d_lu_buf_; int64_t lu_cap_ = 0;      // packed factors (permutations, rows, entries, levels)
+    DeviceBuf<char> d_lu_buf_;                           // packed factors (permutations, rows, entries, levels)
     std::vector<std::vector<std::pair<int32_t, double>>> basis_cols_;      // the basis columns handed to lu_factor
     std::vector<int64_t> basis_ptr_; std::vector<int32_t> basis_idx_; std::vector<double> basis_val_;   // ... as one flat copy (lu_factor_csc)
     HostPool host_pool_;                                  // the host side of a refactorisation (created at first use, joined with the engine)
-    PinnedBuf<char> h_lu_buf_; size_t h_lu_cap_ = 0;      // the same, assembled in pinned host memory
-    DeviceBuf<char> d_lu_buf_alt_; int64_t lu_cap_alt_ = 0;   // second device buffer: the factors the host prepares while the kernel runs
+    PinnedBuf<char> h_lu_buf_;                            // the same, assembled in pinned host memory
+    DeviceBuf<char> d_lu_buf_alt_;                        // second device buffer: the factors the host prepares while the kernel runs
     PinnedBuf<int32_t> h_basis_;                          // the basis a refactorisation downloads
     PinnedBuf<FtMirror> h_mirror_;                        // mapped: what k_ft_run reports (relp_kernels.h); .device() is its address there
     DeviceBuf<double> d_lu_scratch_;
     relp_status_t ensure_lu_scratch();
     // the batch solves of a rebuild (re-inversion, re-tabulation, warm start) with x in global memory (relp_kernels.h: LuSlabs):
     // one slab of ld_b_ doubles per workgroup, allocated at first use and kept; what relp_retab_stats reports
-    DeviceBuf<double> d_lu_slabs_; int64_t lu_slab_cap_ = 0;
+    DeviceBuf<double> d_lu_slabs_;
     int64_t batch_solves_lds_ = 0, batch_solves_slab_ = 0;
     int32_t slab_groups_last_ = 0;
     relp_status_t batch_solve_slabs(int32_t rhs_count, LuSlabs* slabs);
@@ -380,7 +378,7 @@ class Engine : private EngineQueue {
     bool ft_need_refactor_ = false;
     relp_status_t ft_plan_and_alloc();
     relp_status_t ft_reset();
-    relp_status_t ft_read_hdr();
+    relp_status_t ft_read_hdr(bool with_record = false);
     FtProblem ft_problem(int rule) const;
     void ft_enqueue_pivots(const FtState& go, int rule, int64_t left);
     DeviceBuf<char> d_pe_buf_; PriceEll pe_{};            // PRICE copy of the structural columns (relp_kernels.h: PriceEll)

@@ -16,18 +16,18 @@ relp_status_t Engine::basis_inverse_row(int32_t row, double* out_m) {
     if (cfg_.shard_count > 1) return fail(RELP_E_UNSUPPORTED, "B^-1 is sharded");
     if (lu_) {
         lu_btran(row, nullptr, d_rho_);
-        return fetch(out_m, d_rho_, sizeof(double) * lay_.m);
+        HIP_RETURN(d_rho_.download(out_m, lay_.m, stream_));
     }
     if (tableau_) {
         // B^-1 = the tableau columns that were the identity originally: row r of T over those columns
         launch_tab_row(tview(), deferred(), row, d_aq_big(), d_rec_, stream_);
         std::vector<double> trow(n_store_);
-        if (const relp_status_t st = fetch(trow.data(), d_aq_big(), sizeof(double) * n_store_)) return st;
+        HIP_TRY(download_from(trow, d_aq_big(), stream_));
         for (int32_t k = 0; k < lay_.m; ++k) out_m[k] = trow[idcol_h_[k]];
         return RELP_OK;
     }
     enqueue_flush();
-    return fetch(out_m, dBinv_ + (int64_t)row * ld_b_, sizeof(double) * lay_.m);
+    HIP_RETURN(dBinv_.download(out_m, lay_.m, stream_, (int64_t)row * ld_b_));
 }
 
 // BasisInverse::should_refactor: lower_upper/mod.rs:199-202 (`updates.len() > 10`; here: the configured number of
@@ -68,15 +68,13 @@ relp_status_t Engine::generate_column_of(const int32_t* idx, const double* val, 
             for (int32_t k = 0; k < nnz; ++k) s = std::fma(binv[(size_t)i * lay_.m + idx[k]], val[k], s);
             alpha[i] = s;
         }
-        HIP_TRY(hipMemcpyAsync(d_alpha_, alpha.data(), sizeof(double) * lay_.m, hipMemcpyHostToDevice, stream_));
-        HIP_TRY(hipStreamSynchronize(stream_));
+        HIP_TRY(d_alpha_.upload(alpha, stream_));
         if (out_m) std::memcpy(out_m, alpha.data(), sizeof(double) * lay_.m);
         return RELP_OK;
     }
     const relp_status_t st = edit_rec();
     if (st) return st;
-    HIP_TRY(hipMemcpyAsync(d_aq_, a.data(), sizeof(double) * ld_b_, hipMemcpyHostToDevice, stream_));
-    HIP_TRY(hipStreamSynchronize(stream_));              // `a` is stack-owned
+    HIP_TRY(d_aq_.upload(a, stream_));
     if (lu_) {
         lu_ftran(d_aq_, ft_ ? d_alpha_ : d_v_, d_rec_);
         if (!ft_) launch_apply_w(deferred(), lay_.m, d_v_, d_alpha_, d_rec_, stream_);      // the product form's pending W
@@ -84,9 +82,8 @@ relp_status_t Engine::generate_column_of(const int32_t* idx, const double* val, 
         enqueue_flush();
         launch_ftran(Binv_base(), ld_b_, lay_.m, lay_.row_lo, lay_.row_hi, d_aq_, d_alpha_, 0, d_rec_, stream_);
     }
-    if (out_m) HIP_TRY(hipMemcpyAsync(out_m, d_alpha_, sizeof(double) * lay_.m, hipMemcpyDeviceToHost, stream_));
-    HIP_TRY(hipStreamSynchronize(stream_));
-    return RELP_OK;
+    // step-wise call: a failure of its kernels is reported by this call, with or without an output array
+    HIP_RETURN(out_m ? d_alpha_.download(out_m, lay_.m, stream_) : hipStreamSynchronize(stream_));
 }
 
 // InverseMaintener::cost_difference (carry/mod.rs:572-577): (-pi) . a for a column the caller supplies
@@ -131,12 +128,12 @@ relp_status_t Engine::lu_set_factors(const int64_t* l_ptr, const int32_t* l_idx,
     }
     std::string msg;
     if (!lu_from_triangles(lay_.m, lc, uc, &hlu_, &msg)) return fail(RELP_E_ARG, msg);
-    HIP_TRY(hipStreamSynchronize(stream_));
+    HIP_TRY(hipStreamSynchronize(stream_));                // queued kernels read the factors that are replaced next
     relp_status_t st = lu_upload_factors();
     if (st) return st;
     if (ft_) { if ((st = ft_reset())) return st; }
     else launch_flush_reset(deferred(), d_rec_, stream_);
-    HIP_TRY(hipStreamSynchronize(stream_));
+    HIP_TRY(hipStreamSynchronize(stream_));                // a failure of the reset is reported by this call
     since_flush_ = 0;
     return RELP_OK;
 }
@@ -161,24 +158,25 @@ struct FtHostView {
 }  // namespace
 
 static relp_status_t ft_download(const FtState& st, hipStream_t stream, FtHostView* v, std::string* err) {
-    auto get = [&](void* dst, const void* src, size_t bytes) { return bytes ? hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) : hipSuccess; };
-    if (hipStreamSynchronize(stream) != hipSuccess) { *err = "sync failed"; return RELP_E_HIP; }
     int32_t hdr[4];
-    if (get(hdr, st.hdr, sizeof(hdr)) != hipSuccess) { *err = "copy failed"; return RELP_E_HIP; }
+    if (download_from(hdr, st.hdr, 4, stream) != hipSuccess) { *err = "copy failed"; return RELP_E_HIP; }
     v->t = hdr[0]; v->eta_used = hdr[1]; v->tcap = st.tcap; v->ldt = st.ldt; v->m = st.m;
     const int nwp = kFtWaves + 1;
     v->slot_pivot.resize(st.tcap); v->slot_prev.resize(st.tcap); v->slot_live.resize(st.tcap); v->tslot.resize(st.m);
     v->eta_off.resize((size_t)st.tcap * nwp); v->spk_off.resize((size_t)st.tcap * nwp);
     v->TC.resize((size_t)st.tcap * st.ldt); v->eta_idx.resize(std::max(v->eta_used, 1)); v->eta_val.resize(std::max(v->eta_used, 1));
     v->spk_idx.resize((size_t)std::max(v->t, 1) * st.m); v->spk_val.resize((size_t)std::max(v->t, 1) * st.m);
-    hipError_t e = hipSuccess;
-    auto acc = [&](hipError_t x) { if (e == hipSuccess) e = x; };
-    acc(get(v->slot_pivot.data(), st.slot_pivot, 4 * (size_t)st.tcap)); acc(get(v->slot_prev.data(), st.slot_prev, 4 * (size_t)st.tcap));
-    acc(get(v->slot_live.data(), st.slot_live, 4 * (size_t)st.tcap)); acc(get(v->tslot.data(), st.tslot, 4 * (size_t)st.m));
-    acc(get(v->eta_off.data(), st.eta_off, 4 * v->eta_off.size())); acc(get(v->spk_off.data(), st.spk_off, 4 * v->spk_off.size()));
-    acc(get(v->TC.data(), st.TC, 8 * v->TC.size()));
-    acc(get(v->eta_idx.data(), st.eta_idx, 4 * (size_t)v->eta_used)); acc(get(v->eta_val.data(), st.eta_val, 8 * (size_t)v->eta_used));
-    acc(get(v->spk_idx.data(), st.spk_idx, 4 * (size_t)v->t * st.m)); acc(get(v->spk_val.data(), st.spk_val, 8 * (size_t)v->t * st.m));
+    hipError_t e = download_from(v->slot_pivot, st.slot_pivot, stream);
+    e = first_error(e, download_from(v->slot_prev, st.slot_prev, stream));
+    e = first_error(e, download_from(v->slot_live, st.slot_live, stream));
+    e = first_error(e, download_from(v->tslot, st.tslot, stream));
+    e = first_error(e, download_from(v->eta_off, st.eta_off, stream));
+    e = first_error(e, download_from(v->spk_off, st.spk_off, stream));
+    e = first_error(e, download_from(v->TC, st.TC, stream));
+    e = first_error(e, download_from(v->eta_idx.data(), st.eta_idx, (size_t)v->eta_used, stream));
+    e = first_error(e, download_from(v->eta_val.data(), st.eta_val, (size_t)v->eta_used, stream));
+    e = first_error(e, download_from(v->spk_idx.data(), st.spk_idx, (size_t)v->t * st.m, stream));
+    e = first_error(e, download_from(v->spk_val.data(), st.spk_val, (size_t)v->t * st.m, stream));
     if (e != hipSuccess) { *err = std::string("copy failed: ") + hipGetErrorString(e); return RELP_E_HIP; }
     return RELP_OK;
 }

@@ -39,7 +39,7 @@ relp_status_t Engine::lu_load_matrix(const relp_matrix_data_t& md) {
         for (int32_t j = 0; j < lay_.nr_normal; ++j) {
             const double* src = md.dense + (int64_t)j * src_ld;
             if (md.matrix_memory == RELP_MEM_DEVICE) {
-                HIP_TRY(hipMemcpy(col.data(), src, sizeof(double) * lay_.mc, hipMemcpyDeviceToHost));
+                if (const relp_status_t st = fetch(col.data(), src, sizeof(double) * lay_.mc)) return st;     // (the caller's matrix)
                 src = col.data();
             }
             for (int32_t i = 0; i < lay_.mc; ++i)
@@ -52,16 +52,13 @@ relp_status_t Engine::lu_load_matrix(const relp_matrix_data_t& md) {
     HIP_TRY(d_cptr_.alloc(lay_.nr_normal + 1));
     HIP_TRY(d_cidx_.alloc((int64_t)hc_idx_.size()));
     HIP_TRY(d_cval_.alloc((int64_t)hc_val_.size()));
-    HIP_TRY(hipMemcpy(d_cptr_, hc_ptr_.data(), sizeof(int64_t) * hc_ptr_.size(), hipMemcpyHostToDevice));
-    if (!hc_idx_.empty()) {
-        HIP_TRY(hipMemcpy(d_cidx_, hc_idx_.data(), sizeof(int32_t) * hc_idx_.size(), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_cval_, hc_val_.data(), sizeof(double) * hc_val_.size(), hipMemcpyHostToDevice));
-    }
-    return RELP_OK;
+    HIP_TRY(d_cptr_.upload(hc_ptr_, stream_));
+    HIP_TRY(d_cidx_.upload(hc_idx_, stream_));
+    HIP_RETURN(d_cval_.upload(hc_val_, stream_));
 }
 
 // The basis as it is on the device -> pinned host memory.  Synchronises the stream.
-relp_status_t Engine::lu_download_basis() { return fetch(h_basis_, d_basis_, sizeof(int32_t) * lay_.m); }
+relp_status_t Engine::lu_download_basis() { HIP_RETURN(d_basis_.download(h_basis_, lay_.m, stream_)); }
 
 // the columns of the basis in h_basis_ from the host copy of the matrix (the LU engine never holds A densely)
 relp_status_t Engine::lu_basis_columns(std::vector<std::vector<std::pair<int32_t, double>>>& cols) {
@@ -144,7 +141,7 @@ relp_status_t Engine::lu_refactor() {
     if (!(on_device && luf_is_resident()) && (st = lu_upload_factors())) return st;
     if (ft_) { if ((st = ft_reset())) return st; }
     else launch_flush_reset(deferred(), d_rec_, stream_);
-    HIP_TRY(hipStreamSynchronize(stream_));
+    HIP_TRY(hipStreamSynchronize(stream_));                // the reset has run: the clock below and the callers count on it
     lu_refactor_clock(tb, t0, t1, std::chrono::steady_clock::now());
     since_flush_ = 0;
     ++lu_refactors_;
@@ -174,11 +171,10 @@ relp_status_t Engine::lu_refactor_lookahead(int rule, int64_t budget, bool have_
     LUFactors old_h = std::move(hlu_);
     const DeviceLU old_d = dlu_;
     const FtState old_f = fts_;
-    auto swap_buffers = [&]() { d_lu_buf_.swap(d_lu_buf_alt_); std::swap(lu_cap_, lu_cap_alt_); };
-    swap_buffers();                                        // the new factors go into the other buffer, the old one stays in use
+    d_lu_buf_.swap(d_lu_buf_alt_);                         // the new factors go into the other buffer, the old one stays in use
     hlu_ = LUFactors{};
     auto restore = [&]() {
-        swap_buffers();                                    // (the other buffer may be null, capacity 0, after a failed re-allocation)
+        d_lu_buf_.swap(d_lu_buf_alt_);                     // (the other buffer may be empty after a refused re-allocation)
         hlu_ = std::move(old_h); dlu_ = old_d; fts_ = old_f;
     };
     st = lu_factor_downloaded_basis();
@@ -220,7 +216,7 @@ struct Engine::LuUpload {
     const TriangularSchedule* sch[4];
     EllPacked ell[4]; EllImageShape shape[4]; int64_t o_ell[4] = {0, 0, 0, 0};
     std::vector<int32_t> lev_ub;
-    explicit LuUpload(Engine& e) : pk(PinnedStore{e.h_lu_buf_, e.h_lu_cap_}), fts(e.fts_), sch{&e.hlu_.Lf, &e.hlu_.Uf, &e.hlu_.Ub, &e.hlu_.Lb} {}
+    explicit LuUpload(Engine& e) : pk(PinnedStore{e.h_lu_buf_}), fts(e.fts_), sch{&e.hlu_.Lf, &e.hlu_.Uf, &e.hlu_.Ub, &e.hlu_.Lb} {}
 };
 
 // hlu_ (host factors + level schedules) -> one device buffer, dlu_ points into it.  Also used by the revised
@@ -377,17 +373,9 @@ void Engine::lu_pack_row_schedules(LuUpload& u) {
 relp_status_t Engine::lu_copy_to_device(LuUpload& u) {
     if (u.pk.failed()) return fail(RELP_E_ALLOC, "pinned staging buffer for the factors");
     const int64_t bytes = u.pk.size();
-    if (bytes > lu_cap_) {
-        // (pointer and capacity are cleared before the new allocation: if it fails nothing dangles, and the look-ahead's
-        // restore() skips an empty buffer)
-        lu_cap_ = 0;
-        const int64_t want = bytes * 3 / 2 + 256;
-        HIP_TRY(d_lu_buf_.alloc_raw((size_t)want));         // (frees the old buffer first; null if the new one is refused)
-        lu_cap_ = want;
-    }
-    HIP_TRY(hipMemcpyAsync(d_lu_buf_, h_lu_buf_, (size_t)bytes, hipMemcpyHostToDevice, stream_));
+    HIP_TRY(d_lu_buf_.ensure_raw((size_t)bytes, (size_t)(bytes * 3 / 2 + 256)));
+    HIP_TRY(d_lu_buf_.upload(h_lu_buf_, bytes, stream_));  // (waits: the pinned buffer is rewritten by the next refactorisation)
     u.pk.bind(d_lu_buf_);
-    HIP_TRY(hipStreamSynchronize(stream_));             // (the pinned buffer is rewritten by the next refactorisation)
     return RELP_OK;
 }
 
@@ -396,8 +384,7 @@ relp_status_t Engine::lu_install(LuUpload& u) {
     if (!ft_) return RELP_OK;
     if (ft_tier_ >= 2 && fts_.m != lay_.m) {               // rows were removed: the bitmaps saved between launches describe another m
         const int32_t reset[4] = {-1, -1, 0, 0};
-        HIP_TRY(hipMemcpyAsync(fts_.nzc, reset, sizeof reset, hipMemcpyHostToDevice, stream_));
-        HIP_TRY(hipStreamSynchronize(stream_));
+        HIP_TRY(upload_to(fts_.nzc, reset, 4, stream_));
     }
     fts_ = u.fts;
     fts_.m = lay_.m;
@@ -504,7 +491,7 @@ relp_status_t Engine::ft_plan_and_alloc() {
     c.take_if(t2, &fts_.bits_save, kFtBitmapBytes + 1024);
     ft_zero_bytes_ = o_ones - o_zero; ft_ones_bytes_ = o_rest - o_ones;
     HIP_TRY(d_ft_buf_.alloc_raw((size_t)c.size()));
-    HIP_TRY(hipMemset(d_ft_buf_, 0, (size_t)c.size()));
+    HIP_TRY(d_ft_buf_.zero(d_ft_buf_.count(), stream_));
     c.bind(d_ft_buf_);
     HIP_TRY(h_ft_hdr_.alloc(4 * sizeof(int32_t)));
     std::memset(h_ft_hdr_, 0, 4 * sizeof(int32_t));
@@ -515,7 +502,7 @@ relp_status_t Engine::ft_plan_and_alloc() {
     fts_.m = lay_.m; fts_.tcap = ft_tcap_; fts_.ldt = (int32_t)ldt; fts_.eta_cap = ft_eta_cap_;
     {   // (pb.alpha / pb.rho unknown, no bitmaps saved yet)
         const int32_t reset[4] = {-1, -1, 0, 0};
-        HIP_TRY(hipMemcpy(fts_.nzc, reset, sizeof reset, hipMemcpyHostToDevice));
+        HIP_TRY(upload_to(fts_.nzc, reset, 4, stream_));
     }
     fts_.big = ft_tier_; fts_.rhs_cap = ft_rhs_cap_;
     {   // hyper-sparse starts: L and L' by default (U' starts from the leaving pivot's level anyway; on U the spike reaches the first groups: measured 31.4 of 31.4 passes on 25FV47, not worth the reduction); RELP_FT_HYPER = bit mask
@@ -579,22 +566,23 @@ relp_status_t Engine::ft_build_price_ell() {
     }
     pe_.n_long = (int32_t)longs.size(); pe_.n_very_long = (int32_t)very_long.size();
     HIP_TRY(d_pe_buf_.alloc_raw((size_t)pk.size()));       // (frees the copy of before a row removal)
-    HIP_TRY(hipMemcpy(d_pe_buf_, pk.data(), (size_t)pk.size(), hipMemcpyHostToDevice));
+    HIP_TRY(d_pe_buf_.upload(pk.data(), pk.size(), stream_));
     pk.bind(d_pe_buf_);
     return RELP_OK;
 }
 
 // empty update file: t = 0, every pivot "never updated", TC = 0 (after a refactorisation)
 relp_status_t Engine::ft_reset() {
-    HIP_TRY(hipMemsetAsync(fts_.hdr, 0, (size_t)ft_zero_bytes_, stream_));                 // hdr, slot_pivot, slot_live, TC, offsets
-    HIP_TRY(hipMemsetAsync(fts_.slot_prev, 0xFF, (size_t)ft_ones_bytes_, stream_));        // slot_prev, tslot: -1
+    HIP_TRY(fill_bytes_at(fts_.hdr, 0, (size_t)ft_zero_bytes_, stream_));                  // hdr, slot_pivot, slot_live, TC, offsets
+    HIP_TRY(fill_bytes_at(fts_.slot_prev, 0xFF, (size_t)ft_ones_bytes_, stream_));         // slot_prev, tslot: -1
     ft_need_refactor_ = false;
     return RELP_OK;
 }
 
-relp_status_t Engine::ft_read_hdr() {
-    HIP_TRY(hipMemcpyAsync(h_ft_hdr_, fts_.hdr, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
-    HIP_TRY(hipStreamSynchronize(stream_));
+// `with_record`: the pivot record comes down under the same wait
+relp_status_t Engine::ft_read_hdr(bool with_record) {
+    const hipError_t rec = with_record ? d_rec_.download(h_rec_, 1, enqueue_only(stream_)) : hipSuccess;
+    HIP_TRY(first_error(rec, download_from(static_cast<int32_t*>(h_ft_hdr_), fts_.hdr, 4, stream_)));
     since_flush_ = h_ft_hdr_[0];
     ft_need_refactor_ = h_ft_hdr_[2] != 0;
     return RELP_OK;
@@ -603,11 +591,8 @@ relp_status_t Engine::ft_read_hdr() {
 // After a k_ft_run launch: record, header and (mirror only) the basis on the host.  Synchronises the stream.
 relp_status_t Engine::ft_read_report(bool* have_basis) {
     if (have_basis) *have_basis = false;
-    if (!h_mirror_) {
-        HIP_TRY(hipMemcpyAsync(h_rec_, d_rec_, sizeof(PivotRecord), hipMemcpyDeviceToHost, stream_));
-        return ft_read_hdr();
-    }
-    HIP_TRY(hipStreamSynchronize(stream_));
+    if (!h_mirror_) return ft_read_hdr(true);
+    HIP_TRY(hipStreamSynchronize(stream_));                // the kernel has written its report into the mirror
     *h_rec_ = h_mirror_->rec;
     std::memcpy(h_ft_hdr_, h_mirror_->hdr, 4 * sizeof(int32_t));
     // Hyper-sparse starts pay when they skip more passes than the scan for the first group costs (~1,500 clocks = 2 passes):
@@ -644,7 +629,7 @@ void Engine::ft_enqueue_pivots(const FtState& go, int rule, int64_t left) {
     }
     const int64_t room = std::max<int64_t>((int64_t)go.max_updates - since_flush_, 0);
     const int64_t batch = std::min<int64_t>(left, room + 1);
-    (void)hipMemsetAsync(fts_.hdr + 2, 0, 2 * sizeof(int32_t), stream_);
+    (void)fill_bytes_at(fts_.hdr + 2, 0, 2 * sizeof(int32_t), enqueue_only(stream_));    // (no host side; the launches below follow it on the stream)
     FtProblem pb = ft_problem(rule);
     pb.external_price = 1;
     const ColumnTable ct = table();
@@ -684,7 +669,7 @@ relp_status_t Engine::run_ft(int64_t max_iters, int64_t* done, int32_t* outcome)
     if (st) return st;
     // (layout 2 keeps lists of where alpha and rho are not zero and rewrites those places only; whatever ran since the last call --
     // step-wise API, phase switch, warm start -- may have written the two vectors: the first pivot rewrites them densely)
-    if (ft_tier_ >= 2) HIP_TRY(hipMemsetAsync(fts_.nzc, 0xFF, 2 * sizeof(int32_t), stream_));
+    if (ft_tier_ >= 2) HIP_TRY(fill_bytes_at(fts_.nzc, 0xFF, 2 * sizeof(int32_t), stream_));
     const long long start = h_rec_->iterations;
     const int rule = current_rule();
     struct Tick { int64_t& t; ~Tick() { ++t; } };
@@ -739,11 +724,10 @@ relp_status_t Engine::run_ft(int64_t max_iters, int64_t* done, int32_t* outcome)
 // shader clocks (thread 0 of the persistent kernel) per phase of the pivot, accumulated since create
 relp_status_t Engine::lu_phase_cycles(int64_t* out16) {
     if (!lu_ || !ft_) return fail(RELP_E_UNSUPPORTED, "phase clocks are the persistent pivot kernel's");
-    HIP_TRY(hipStreamSynchronize(stream_));
-    HIP_TRY(hipMemcpy(out16, fts_.prof, 16 * sizeof(int64_t), hipMemcpyDeviceToHost));
+    if (const relp_status_t st = fetch(out16, fts_.prof, 16 * sizeof(int64_t))) return st;
     if (sw_.debug) {                       // passes walked per sweep of L, U, U', L' against the whole schedule
         int64_t ex[16];
-        HIP_TRY(hipMemcpy(ex, fts_.prof + 16, sizeof ex, hipMemcpyDeviceToHost));
+        if (const relp_status_t st = fetch(ex, fts_.prof + 16, sizeof ex)) return st;
         if (ex[15]) std::fprintf(stderr, "[relp] non-zeros per pivot (layout 2): entering column %.1f, eta row %.1f, spike %.1f\n",
                                  (double)ex[12] / ex[15], (double)ex[13] / ex[15], (double)ex[14] / ex[15]);
         static const char* nm[4] = {"L", "U", "U'", "L'"};

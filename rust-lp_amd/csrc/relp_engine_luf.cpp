@@ -104,16 +104,14 @@ relp_status_t Engine::luf_prepare() {
     }
     c.take(&S.pinfo, (int64_t)sizeof(FtPivotInfo) * R);
     HIP_TRY(S.d_buf.alloc_raw((size_t)c.size()));
-    HIP_TRY(hipMemset(S.d_buf, 0, (size_t)c.size()));
+    HIP_TRY(S.d_buf.zero(S.d_buf.count(), stream_));
     char* const B = S.d_buf;
     c.bind(B);
-    HIP_TRY(hipMemcpy(B + o_rptr, rcount.data(), 4 * ((size_t)m + 1), hipMemcpyHostToDevice));
-    if (nnz) {
-        HIP_TRY(hipMemcpy(B + o_rcol, rcol.data(), 4 * (size_t)nnz, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(B + o_rval, rval.data(), 8 * (size_t)nnz, hipMemcpyHostToDevice));
-    }
-    HIP_TRY(hipMemcpy(B + o_art, art_of_row.data(), 4 * (size_t)m, hipMemcpyHostToDevice));
-    if (lay_.wrapped_na > 0) HIP_TRY(hipMemcpy(B + o_wr, lay_.column_to_row.data(), 4 * (size_t)lay_.wrapped_na, hipMemcpyHostToDevice));
+    HIP_TRY(upload_to(B + o_rptr, rcount.data(), (size_t)m + 1, stream_));
+    HIP_TRY(upload_to(B + o_rcol, rcol.data(), (size_t)nnz, stream_));
+    HIP_TRY(upload_to(B + o_rval, rval.data(), (size_t)nnz, stream_));
+    HIP_TRY(upload_to(B + o_art, art_of_row.data(), (size_t)m, stream_));
+    if (lay_.wrapped_na > 0) HIP_TRY(upload_to(B + o_wr, lay_.column_to_row.data(), (size_t)lay_.wrapped_na, stream_));
     A.m = m; A.na = na; A.n_provider = nprov;
     A.csc = csc(); A.ct = table();
     A.wrapped_na = lay_.wrapped_na;
@@ -159,9 +157,11 @@ relp_status_t Engine::lu_factor_on_device(int32_t* device_status) {
     for (int attempt = sw_.luf_lds ? 0 : 1; attempt < 2; ++attempt) {
         launch_lu_factor(S.M, d_basis_, S.W, S.O, stream_, attempt == 0);
         if (resident) launch_lu_schedules(S.sin, S.SW, S.sout, S.O.status, S.pinfo, stream_);
-        HIP_TRY(hipMemcpyAsync(status, S.O.status, sizeof status, hipMemcpyDeviceToHost, stream_));
-        if (resident) for (int q = 0; q < 4; ++q) HIP_TRY(hipMemcpyAsync(desc[q], S.sout[q].desc, sizeof desc[q], hipMemcpyDeviceToHost, stream_));
-        HIP_TRY(hipStreamSynchronize(stream_));
+        // the status and the descriptors under one wait: the last copy is the waiting one
+        hipError_t got = download_from(status, S.O.status, 8, resident ? enqueue_only(stream_) : On(stream_));
+        for (int q = 0; resident && q < 4; ++q)
+            got = first_error(got, download_from(desc[q], S.sout[q].desc, LUF_D_WORDS, q < 3 ? enqueue_only(stream_) : On(stream_)));
+        HIP_TRY(got);
         if (!(attempt == 0 && status[0] == LUF_NO_ROOM)) break;
         ++luf_lds_retries_;
     }
@@ -169,7 +169,7 @@ relp_status_t Engine::lu_factor_on_device(int32_t* device_status) {
     ++luf_runs_;
     if (sw_.debug && luf_runs_ % 200 == 0) {          // phase clocks of the factorisation kernel (relp_lu_factor_core.h: LUF_LAP)
         int32_t cnt[128] = {0};
-        HIP_TRY(hipMemcpy(cnt, S.W.counters, sizeof cnt, hipMemcpyDeviceToHost));
+        HIP_TRY(download_from(cnt, S.W.counters, 128, stream_));
         const unsigned long long* ph = reinterpret_cast<const unsigned long long*>(cnt + 8);
         static const char* nm[11] = {"maps+counts", "peel", "bump setup", "r:column max", "r:proposals", "r:independence+accept", "r:elimination", "r:leave + dense finish",
                                      "triplets", "row views", "column views"};
@@ -182,7 +182,7 @@ relp_status_t Engine::lu_factor_on_device(int32_t* device_status) {
         static const char* sn[4] = {"L", "U", "U'", "L'"};
         for (int q = 0; q < 4 && resident; ++q) {
             int32_t sc[32] = {0};
-            HIP_TRY(hipMemcpy(sc, S.SW[q].sc, sizeof sc, hipMemcpyDeviceToHost));
+            HIP_TRY(download_from(sc, S.SW[q].sc, 32, stream_));
             const unsigned long long* sp = reinterpret_cast<const unsigned long long*>(sc + 8);
             std::fprintf(stderr, "[relp]   schedule %s clocks per run: levels %.0f, fusion %.0f, classify + offsets %.0f, image %.0f, via %.0f\n", sn[q],
                          (double)sp[0] / luf_runs_, (double)sp[1] / luf_runs_, (double)sp[2] / luf_runs_, (double)sp[3] / luf_runs_, (double)sp[4] / luf_runs_);
@@ -231,21 +231,21 @@ relp_status_t Engine::luf_download_factors() {
     const int32_t m = lay_.m, nl = (int32_t)hlu_.nnz_l, nu = (int32_t)(hlu_.nnz_u - m);
     hlu_.rowperm.resize(m); hlu_.colperm.resize(m);
     std::vector<double> diag(m), ones(m, 1.0);
-    HIP_TRY(hipMemcpyAsync(hlu_.rowperm.data(), S.O.rowperm, 4 * (size_t)m, hipMemcpyDeviceToHost, stream_));
-    HIP_TRY(hipMemcpyAsync(hlu_.colperm.data(), S.O.colperm, 4 * (size_t)m, hipMemcpyDeviceToHost, stream_));
-    HIP_TRY(hipMemcpyAsync(diag.data(), S.O.diag, 8 * (size_t)m, hipMemcpyDeviceToHost, stream_));
+    // every piece under one wait: the last copy (the values of L', or its row pointers when it has no entry) is the waiting one
+    hipError_t got = download_from(hlu_.rowperm, S.O.rowperm, enqueue_only(stream_));
+    got = first_error(got, download_from(hlu_.colperm, S.O.colperm, enqueue_only(stream_)));
+    got = first_error(got, download_from(diag, S.O.diag, enqueue_only(stream_)));
     TriangularSchedule* sch[4] = {&hlu_.Lf, &hlu_.Uf, &hlu_.Ub, &hlu_.Lb};
     const LufTriangle* tri[4] = {&S.O.Lf, &S.O.Uf, &S.O.Ub, &S.O.Lb};
     const int32_t cnt[4] = {nl, nu, nu, nl};
     for (int q = 0; q < 4; ++q) {
         sch[q]->ptr.resize(m + 1); sch[q]->idx.resize(cnt[q]); sch[q]->val.resize(cnt[q]);
-        HIP_TRY(hipMemcpyAsync(sch[q]->ptr.data(), tri[q]->ptr, 4 * ((size_t)m + 1), hipMemcpyDeviceToHost, stream_));
-        if (cnt[q]) {
-            HIP_TRY(hipMemcpyAsync(sch[q]->idx.data(), tri[q]->idx, 4 * (size_t)cnt[q], hipMemcpyDeviceToHost, stream_));
-            HIP_TRY(hipMemcpyAsync(sch[q]->val.data(), tri[q]->val, 8 * (size_t)cnt[q], hipMemcpyDeviceToHost, stream_));
-        }
+        const bool last = q == 3;
+        got = first_error(got, download_from(sch[q]->ptr, tri[q]->ptr, last && !cnt[q] ? On(stream_) : enqueue_only(stream_)));
+        got = first_error(got, download_from(sch[q]->idx, tri[q]->idx, enqueue_only(stream_)));
+        got = first_error(got, download_from(sch[q]->val, tri[q]->val, last ? On(stream_) : enqueue_only(stream_)));
     }
-    HIP_TRY(hipStreamSynchronize(stream_));
+    HIP_TRY(got);
     lu_levels_from_rows(m, ones, true, &hlu_.Lf);
     lu_levels_from_rows(m, diag, false, &hlu_.Uf);
     lu_levels_from_rows(m, diag, true, &hlu_.Ub);

@@ -312,16 +312,14 @@ relp_status_t Engine::shard_agree_on_status(relp_status_t local) {
     if (coll_broken_) return local ? local : RELP_E_HIP;
     const int32_t g = std::max(cfg_.shard_count, 1);
     const double mine[2] = {(double)local, (double)cfg_.shard_rank};
-    if (hipMemcpyAsync(d_msg_status_, mine, sizeof(mine), hipMemcpyHostToDevice, stream_) != hipSuccess ||
-        hipStreamSynchronize(stream_) != hipSuccess)
+    if (d_msg_status_.upload(mine, 2, stream_) != hipSuccess)
         return local ? local : fail(RELP_E_HIP, "status upload failed");
     if (coll_allgather_(coll_ctx_, d_msg_status_, d_msg_statuses_, 2 * (int64_t)sizeof(double), stream_)) {
         coll_broken_ = true;
         return local ? local : fail(RELP_E_HIP, "all-gather of the rank statuses failed");
     }
     std::vector<double> all(2 * (size_t)g, 0.0);
-    if (hipMemcpyAsync(all.data(), d_msg_statuses_, sizeof(double) * all.size(), hipMemcpyDeviceToHost, stream_) != hipSuccess ||
-        hipStreamSynchronize(stream_) != hipSuccess)
+    if (d_msg_statuses_.download(all, stream_) != hipSuccess)
         return local ? local : fail(RELP_E_HIP, "status download failed");
     for (int32_t r = 0; r < g; ++r)
         if (all[2 * r] != 0.0) {

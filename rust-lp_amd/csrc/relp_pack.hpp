@@ -50,14 +50,13 @@ struct VectorStore {
 // pinned memory that outlives the Packer (the copy to the device is one DMA, not a staged one); grows to twice what is
 // asked for, at least 1 MiB
 struct PinnedStore {
-    PinnedBuf<char>& buf; size_t& cap;
+    PinnedBuf<char>& buf;
     char* ensure(size_t used, size_t need) {
-        if (need > cap) {
-            const size_t grown_cap = std::max<size_t>(need * 2, size_t(1) << 20);
+        if (need > buf.bytes()) {
             PinnedBuf<char> grown;
-            if (grown.alloc(grown_cap) != hipSuccess) return nullptr;
+            if (grown.alloc(std::max<size_t>(need * 2, size_t(1) << 20)) != hipSuccess) return nullptr;
             if (used) std::memcpy(grown, buf, used);
-            buf = std::move(grown); cap = grown_cap;
+            buf = std::move(grown);
         }
         return buf;
     }

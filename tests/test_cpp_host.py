@@ -54,6 +54,17 @@ def test_standard_form_layout():
     assert " 0 failed" in res.stdout
 
 
+def test_device_and_pinned_buffers_against_recording_stubs():
+    """tests/cpp/test_buffers.cpp (no GPU): DeviceBuf / PinnedBuf (rust-lp_amd/csrc/relp_buffers.hpp) against stubs of the HIP
+    calls they make -- lengths through alloc, ensure, adopt, swap and move, an empty buffer after a refused allocation, every copy
+    and fill as one call on the caller's stream followed by one wait (none for the enqueue-only download), ranges that do not
+    fit refused without a call, every allocation freed once."""
+    subprocess.check_call(["make", "-C", CPP, "test_buffers"], stdout=subprocess.DEVNULL)
+    res = subprocess.run([os.path.join(CPP, "test_buffers")], capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-1000:]
+    assert " 0 failed" in res.stdout
+
+
 @pytest.mark.gpu
 def test_cpp_host_tests_pass_on_the_gpu():
     if not os.access(BINARY, os.X_OK):

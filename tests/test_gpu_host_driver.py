@@ -1,6 +1,7 @@
 """Host-driver paths of the three engines that no other GPU test pins: what `from_basis` refuses and the state it leaves
 behind, its two paths (signed-permutation shortcut and the general factorisation), the two row selectors of the step-wise
-API, and `basis_inverse()` with updates pending.
+API, `basis_inverse()` with updates pending, a trace shorter than the solve, the ranging lists growing on one handle and an
+rhs change summed in shares.
 
 The LP is `synthetic.dense_lp(24, 32, SEED)` with SEED = 1: through the CPU oracle it is feasible and optimal after 18
 pivots, all of them in phase 2 (b > 0: the all-slack basis is feasible, phase 1 is empty and no row is removed).
@@ -117,6 +118,55 @@ def test_the_two_row_selectors_agree(problem, kind):
         of_copy = t.select_primal_pivot_row(column=col)
         assert on_device is not None and on_device == of_copy
         t.bring_into_basis(q, on_device, dq)
+    t.close()
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_trace_with_a_capacity_below_the_pivot_count(problem, kind):
+    """The trace keeps the first `trace_capacity` pivots; the four arrays sit `trace_capacity` apart in one buffer."""
+    ref = relp_f64.OracleF64(problem["md"].ensure_csc())
+    assert ref.run() == "optimal"
+    t = engine.Tableau(problem["md"], engine=kind, trace_capacity=5)
+    assert_reaches_the_optimum(t, problem)
+    assert t.iterations() == len(ref.trace) > 5
+    assert t.trace() == ref.trace[:5]
+    t.close()
+
+
+def optimal_tableau(problem, **kwargs):
+    t = engine.Tableau(problem["md"], engine=engine.ENGINE_TABLEAU, **kwargs)
+    assert_reaches_the_optimum(t, problem)
+    return t
+
+
+def test_ranging_lists_grow_and_are_reused(problem):
+    """A 1-row query, 17 rows, 1 row on one handle (its device lists are allocated, grown, reused) against three fresh handles."""
+    lists = [np.array([3], dtype=np.int32), np.arange(17, dtype=np.int32), np.array([M - 1], dtype=np.int32)]
+    one = optimal_tableau(problem)
+    for rows in lists:
+        fresh = optimal_tableau(problem)
+        for query in ("row_ratios", "rhs_ranging"):
+            got, want = getattr(one, query)(rows), getattr(fresh, query)(rows)
+            for g, w in zip(got, want):
+                assert g.shape == (len(rows),) and np.array_equal(g, w)
+        fresh.close()
+    one.close()
+
+
+@pytest.mark.parametrize("splits", [4, 2])
+def test_rhs_change_in_shares(problem, splits, monkeypatch):
+    """RELP_TAB_RHS_SPLITS (read at create) 4 and 2: the per-share partial sums of a full-list change against B b = rhs solved
+    on the CPU from the problem's own columns, and (a consistency check) against the engine's own B^-1 times the new rhs."""
+    monkeypatch.setenv("RELP_TAB_RHS_SPLITS", str(splits))
+    t = optimal_tableau(problem)
+    rhs = t.right_hand_side()
+    new_rhs = rhs * (1.0 + 0.01 * (1 + np.arange(M) % 3))
+    Binv = t.basis_inverse()
+    t.change_right_hand_side(np.arange(M), new_rhs)
+    assert t.rhs_stats()[3] == splits
+    np.testing.assert_allclose(t.b(), np.linalg.solve(basis_matrix(problem["A"], t.basis_indices()), new_rhs), rtol=TOL, atol=TOL)
+    np.testing.assert_allclose(t.b(), Binv @ new_rhs, rtol=TOL, atol=TOL)
+    np.testing.assert_array_equal(t.right_hand_side(), new_rhs)
     t.close()
 
 
