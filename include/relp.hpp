@@ -230,10 +230,11 @@ class Tableau {
             throw Error(st, msg);
         }
         h_ = h;
+        nr_normal_ = data.nr_normal_variables();
     }
     ~Tableau() { if (h_) relp_engine_destroy(h_); }
-    Tableau(Tableau&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
-    Tableau& operator=(Tableau&& o) noexcept { if (this != &o) { if (h_) relp_engine_destroy(h_); h_ = o.h_; o.h_ = nullptr; } return *this; }
+    Tableau(Tableau&& o) noexcept : h_(o.h_), nr_normal_(o.nr_normal_) { o.h_ = nullptr; }
+    Tableau& operator=(Tableau&& o) noexcept { if (this != &o) { if (h_) relp_engine_destroy(h_); h_ = o.h_; nr_normal_ = o.nr_normal_; o.h_ = nullptr; } return *this; }
     Tableau(const Tableau&) = delete;
     Tableau& operator=(const Tableau&) = delete;
 
@@ -363,6 +364,21 @@ class Tableau {
     std::vector<double> right_hand_side() { std::vector<double> v(nr_rows()); ck(relp_get_right_hand_side(h_, v.data())); return v; }
     // relp_rhs_stats: {in-place changes, columns of B^-1 they read, pending rows at the last change, shares of its last launch}
     std::array<int64_t, 4> rhs_stats() { std::array<int64_t, 4> out{}; ck(relp_rhs_stats(h_, out.data())); return out; }
+    // structural costs moved in place on the current basis (relp_change_cost): cost[columns[k]] = values[k], each column named once;
+    // run() continues from there
+    void change_cost(const std::vector<int32_t>& columns, const std::vector<double>& values) {
+        if (columns.size() != values.size()) throw Error(RELP_E_ARG, "one value per column");
+        ck(relp_change_cost(h_, columns.data(), values.data(), (int32_t)columns.size()));
+    }
+    // every structural cost at once: flush, reprice (relp_set_cost)
+    void set_cost(const std::vector<double>& cost) {
+        if ((int32_t)cost.size() != nr_normal_) throw Error(RELP_E_ARG, "one cost per structural column");
+        ck(relp_set_cost(h_, cost.data()));
+    }
+    // the structural costs in effect
+    std::vector<double> cost() { std::vector<double> v(nr_normal_); ck(relp_get_cost(h_, v.data())); return v; }
+    // relp_cost_stats: {in-place changes, tableau rows they read, pending rows at the last change, shares of its last launch}
+    std::array<int64_t, 4> cost_stats() { std::array<int64_t, 4> out{}; ck(relp_cost_stats(h_, out.data())); return out; }
     // relp_row_ratios: per listed row the minimum d_j / |T[r,j]| over the non-basic columns with T[r,j] < 0 (down) and > 0 (up), and
     // the column that attains it (+inf, -1 without one): branching penalties, and the cost range [c - down, c + up] of the row's
     // basic variable.  Read-only.
@@ -445,6 +461,7 @@ class Tableau {
         if (st != RELP_OK) throw Error(st, relp_last_error(h_));
     }
     relp_engine_t* h_ = nullptr;
+    int32_t nr_normal_ = 0;                 // structural columns of the MatrixData the handle was made from
 };
 
 // zeros dropped, like the SparseVector the reference's generate_column returns

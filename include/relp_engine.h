@@ -276,6 +276,39 @@ relp_status_t relp_get_right_hand_side(relp_engine_t *h, double *out_m);
 /* out4 = { in-place changes so far, columns of B^-1 they read (entries with a nonzero delta), pending rows p of the update block
  * at the last change, shares (k-splits) of its last launch }. */
 relp_status_t relp_rhs_stats(const relp_engine_t *h, int64_t *out4);
+/* Cost coefficients moved on the current basis WITHOUT a flush or a re-tabulation (no counterpart in the reference): what a
+ * parametric objective, a feasibility pump or a Lagrangian loop does between re-solves, and the call that moves a cost as far as
+ * Tableau.cost_ranging says it may go.  cost[columns[k]] = values[k] for k < count; `columns` are structural provider columns,
+ * 0 <= column < nr_normal (virtual columns have cost 0 and keep it), values of any sign.  b does not depend on the cost: the basis
+ * stays primal feasible and relp_run continues from it; neither primal nor dual feasibility is required.  Nothing is rebuilt: with
+ * delta_k = values[k] - cost[columns[k]], r_k the row in which a changed BASIC column is basic and the basic entries sorted by r_k
+ * ascending (the summation order: the order of the caller's list cannot change a bit),
+ *     d_c -= sum_k delta_k * (T0[r_k,c] + sum_{j<p} W[j][r_k] * R0[j][c])          (p = pending rows of the open update block)
+ * for every stored column c the pivot update maintains d for, the kept artificial block (relp_get_minus_pi reads it) and barred
+ * columns included; a changed NON-BASIC column also gets d_c += its delta.  A column flagged basic keeps its d to the bit (the
+ * pivot update pinned it at exactly 0).  Fixed summation orders, no atomics: the same call on the same state gives the same bits.
+ * Entries with delta_k == 0 are dropped before anything is uploaded; a call whose deltas are all zero leaves d bit-identical.
+ * -obj is re-formed from b with the new costs, and the call synchronises.  b, the basis, the flags, the pending update block (no
+ * flush happens), the trace, relp_reinversions and relp_tab_flush_stats are untouched; every later reprice and re-tabulation
+ * (re-inversion interval, relp_from_basis, relp_set_right_hand_side) builds on the new costs.
+ * RELP_E_ARG with nothing changed: a column out of range, a column named twice, a value that is not finite, count < 0, a missing
+ * list.  count == 0 is a no-op.  The basic list is processed in `splits` shares: the rule of DESIGN.md 10, or
+ * RELP_TAB_COST_SPLITS=n at create (clamped to [1, min(basic entries, 256)]).
+ * RELP_ENGINE_TABLEAU, unsharded, phase 2: RELP_E_UNSUPPORTED on another or a sharded engine, RELP_E_STATE in phase 1 (all four
+ * calls). */
+relp_status_t relp_change_cost(relp_engine_t *h, const int32_t *columns, const double *values, int32_t count);
+/* All nr_normal structural costs at once by the route the engine has: an open update block is flushed (it counts in
+ * relp_tab_flush_stats), the costs are replaced, d = c - c_B' T0 in one coalesced pass over T0 and -obj = -c_B' b.  No LU, no
+ * re-tabulation, relp_reinversions unchanged.  The yardstick of relp_change_cost, and the call to make when most costs move: the
+ * in-place walk reads T0 by rows (strided), this one by columns (DESIGN.md 10 has the crossover).  RELP_E_ARG with nothing
+ * changed when a value is not finite. */
+relp_status_t relp_set_cost(relp_engine_t *h, const double *cost_n);
+/* The structural costs in effect, nr_normal entries. */
+relp_status_t relp_get_cost(relp_engine_t *h, double *out_n);
+/* out4 = { in-place changes so far, tableau rows they read (basic entries with a nonzero delta), pending rows p of the update block
+ * at the last change, shares (k-splits) of its last launch }.  Refused calls and calls with count == 0 are not counted; a call
+ * whose deltas are all zero counts as a change that read 0 rows. */
+relp_status_t relp_cost_stats(const relp_engine_t *h, int64_t *out4);
 /* Batched ratio tests over the tableau as it stands (no counterpart in the reference): what a branch-and-bound driver asks at a
  * node ("which fractional row is the dearest to branch on?") and a solve asks at its end (the ranging report).  Both are read-only:
  * nothing is flushed or re-tabulated, and T0, R0, W, d, b, the basis, the flags, the PRICE partials, the record, the trace and

@@ -90,6 +90,12 @@ relp_status_t relp_change_right_hand_side(relp_engine_t* h, const int32_t* rows,
 relp_status_t relp_set_upper_bound(relp_engine_t* h, int32_t column, double value) { return h ? H(h).set_upper_bound(column, value) : RELP_E_ARG; }
 relp_status_t relp_get_right_hand_side(relp_engine_t* h, double* out_m) { return (h && out_m) ? H(h).get_right_hand_side(out_m) : RELP_E_ARG; }
 relp_status_t relp_rhs_stats(const relp_engine_t* h, int64_t* out4) { return (h && out4) ? H(h).rhs_stats(out4) : RELP_E_ARG; }
+relp_status_t relp_change_cost(relp_engine_t* h, const int32_t* columns, const double* values, int32_t count) {
+    return h ? H(h).change_cost(columns, values, count) : RELP_E_ARG;
+}
+relp_status_t relp_set_cost(relp_engine_t* h, const double* cost_n) { return (h && cost_n) ? H(h).set_cost(cost_n) : RELP_E_ARG; }
+relp_status_t relp_get_cost(relp_engine_t* h, double* out_n) { return (h && out_n) ? H(h).get_cost(out_n) : RELP_E_ARG; }
+relp_status_t relp_cost_stats(const relp_engine_t* h, int64_t* out4) { return (h && out4) ? H(h).cost_stats(out4) : RELP_E_ARG; }
 relp_status_t relp_row_ratios(relp_engine_t* h, const int32_t* rows, int32_t count, double* down_ratio, int32_t* down_column,
                               double* up_ratio, int32_t* up_column) {
     return h ? H(h).row_ratios(rows, count, down_ratio, down_column, up_ratio, up_column) : RELP_E_ARG;

@@ -113,6 +113,7 @@ Switches Switches::read() {
     s.retab_global = num("RELP_RETAB_GLOBAL", 0) != 0;
     s.retab_groups = std::max(0, num("RELP_RETAB_GROUPS", 0));
     s.tab_rhs_splits = std::max(0, num("RELP_TAB_RHS_SPLITS", 0));
+    s.tab_cost_splits = std::max(0, num("RELP_TAB_COST_SPLITS", 0));
     return s;
 }
 
@@ -270,6 +271,13 @@ relp_status_t Engine::create(const relp_matrix_data_t& md, const relp_config_t& 
             HIP_TRY(d_rhs_cols_.alloc(lay_.m));
             HIP_TRY(d_rhs_delta_.alloc(lay_.m));
             HIP_TRY(d_rhs_v_.alloc(std::max(block_, 1)));
+            // ... and of relp_change_cost: a structural column is basic in at most one row, or not at all
+            const int32_t basic_most = std::min(lay_.m, lay_.nr_normal);
+            HIP_TRY(d_cost_rows_.alloc(basic_most));
+            HIP_TRY(d_cost_delta_.alloc(basic_most));
+            HIP_TRY(d_cost_ncols_.alloc(lay_.nr_normal));
+            HIP_TRY(d_cost_ndelta_.alloc(lay_.nr_normal));
+            HIP_TRY(d_cost_u_.alloc(std::max(block_, 1)));
         }
     }
     if (block_ > 0) HIP_TRY(d_v_.alloc(ld_b_));
@@ -1122,6 +1130,121 @@ relp_status_t Engine::rhs_stats(int64_t* out4) const {
     if (!tableau_ || cfg_.shard_count > 1) return RELP_E_UNSUPPORTED;
     if (phase_ != 2) return RELP_E_STATE;
     out4[0] = rhs_changes_; out4[1] = rhs_columns_; out4[2] = rhs_last_p_; out4[3] = rhs_last_splits_;
+    return RELP_OK;
+}
+
+// The three copies of lay_.cost[lo, hi) the tableau engine keeps: d_cost_ (ColumnTable), cost_store_h_ (relp_get_minus_pi) and
+// d_cost_store_ (every reprice and re-tabulation), the latter two by storage column.
+relp_status_t Engine::store_costs(int32_t lo, int32_t hi) {
+    if (hi <= lo) return RELP_OK;
+    std::copy(lay_.cost.begin() + lo, lay_.cost.begin() + hi, cost_store_h_.begin() + tab_na_ + lo);
+    hipError_t e = d_cost_.upload(lay_.cost.data() + lo, hi - lo, enqueue_only(stream_), lo);
+    HIP_RETURN(first_error(e, d_cost_store_.upload(lay_.cost.data() + lo, hi - lo, stream_, tab_na_ + lo)));
+}
+
+// Cost coefficients moved on the current basis without a flush or a re-tabulation: the mirror image of change_right_hand_side.
+// d = c - c_B' T, so a changed basic column (basic in row r_k, delta_k) moves every non-basic d by -delta_k T[r_k, :] and a changed
+// non-basic column moves its own d by +delta; T = T0 + W R0 over the pending rows of the open block (launch_tab_cost_change).  The
+// basic list is sorted by row: the summation order, and neighbouring rows of a column of T0 share a sector.  b, the basis, the
+// flags, W, R0 and T0 stay as they are; -obj is re-formed from the downloaded b with the new costs.
+relp_status_t Engine::change_cost(const int32_t* columns, const double* values, int32_t count) {
+    relp_status_t st = dual_ready("relp_change_cost");
+    if (st) return st;
+    if (count < 0 || (count > 0 && (!columns || !values))) return fail(RELP_E_ARG, "relp_change_cost: count < 0 or a list missing");
+    {
+        std::vector<uint8_t> named(lay_.nr_normal, 0);
+        for (int32_t k = 0; k < count; ++k) {
+            if (columns[k] < 0 || columns[k] >= lay_.nr_normal) return fail(RELP_E_ARG, "relp_change_cost: not a structural column");
+            if (named[columns[k]]) return fail(RELP_E_ARG, "relp_change_cost: a column named twice");
+            if (!std::isfinite(values[k])) return fail(RELP_E_ARG, "relp_change_cost: a value that is not finite");
+            named[columns[k]] = 1;
+        }
+    }
+    if (count == 0) return RELP_OK;
+    tab_settle();
+    if ((st = download_rec())) return st;
+    const int32_t p = h_rec_->n_eta;
+    h_rec_->outcome = DEV_RUNNING;
+    std::vector<int32_t> basis(lay_.m);
+    HIP_TRY(d_basis_.download(basis, stream_));
+    std::vector<int32_t> row_of(lay_.nr_normal, -1);       // structural column -> the row it is basic in
+    for (int32_t i = 0; i < lay_.m; ++i)
+        if (basis[i] >= 0 && basis[i] < lay_.nr_normal) row_of[basis[i]] = i;
+    std::vector<std::pair<int32_t, double>> basic, nonbasic;      // (row, delta), (storage column, delta)
+    int32_t lo = lay_.nr_normal, hi = 0;
+    for (int32_t k = 0; k < count; ++k) {
+        const double dk = values[k] - lay_.cost[columns[k]];
+        if (dk == 0.0) continue;
+        lo = std::min(lo, columns[k]); hi = std::max(hi, columns[k] + 1);
+        if (row_of[columns[k]] >= 0) basic.emplace_back(row_of[columns[k]], dk);
+        else nonbasic.emplace_back(tab_na_ + columns[k], dk);
+    }
+    const auto by_index = [](const std::pair<int32_t, double>& a, const std::pair<int32_t, double>& b) { return a.first < b.first; };
+    std::sort(basic.begin(), basic.end(), by_index);
+    std::sort(nonbasic.begin(), nonbasic.end(), by_index);
+    const int32_t cnt = (int32_t)basic.size(), ncnt = (int32_t)nonbasic.size();
+    if (cnt + ncnt > 0) {
+        std::vector<int32_t> rows(cnt), ncols(ncnt);
+        std::vector<double> delta(cnt), ndelta(ncnt);
+        for (int32_t k = 0; k < cnt; ++k) { rows[k] = basic[k].first; delta[k] = basic[k].second; }
+        for (int32_t k = 0; k < ncnt; ++k) { ncols[k] = nonbasic[k].first; ndelta[k] = nonbasic[k].second; }
+        const int32_t splits = tab_cost_splits(n_store_, cnt, sw_.tab_cost_splits);
+        if (splits > 1) HIP_TRY(d_cost_partial_.ensure((int64_t)splits * ld_r_));
+        // the four lists and b under one wait (no return before it: the lists and b are in flight; no launch on lost lists)
+        hipError_t e = d_cost_rows_.upload(rows, enqueue_only(stream_));
+        e = first_error(e, d_cost_delta_.upload(delta, enqueue_only(stream_)));
+        e = first_error(e, d_cost_ncols_.upload(ncols, enqueue_only(stream_)));
+        e = first_error(e, d_cost_ndelta_.upload(ndelta, enqueue_only(stream_)));
+        if (e == hipSuccess) launch_tab_cost_change(tview(), deferred(), CostChange{d_cost_rows_, d_cost_delta_, cnt, d_cost_ncols_, d_cost_ndelta_, ncnt},
+                                                    d_in_basis_, p, splits, d_cost_u_, d_cost_partial_, ld_r_, stream_);
+        std::vector<double> b(lay_.m);                     // (allocated while the kernel runs)
+        HIP_TRY(first_error(e, d_b_.download(b, stream_)));
+        if (hipGetLastError() != hipSuccess) return fail(RELP_E_HIP, "relp_change_cost: a kernel launch failed");
+        for (int32_t k = 0; k < count; ++k) lay_.cost[columns[k]] = values[k];
+        if ((st = store_costs(lo, hi))) return st;
+        h_rec_->minus_objective = -objective_of(basis, b);
+        tab_partials_valid_ = false;
+        cost_last_splits_ = splits;
+    }
+    ++cost_changes_;
+    cost_rows_ += cnt;
+    cost_last_p_ = p;
+    return upload_rec();
+}
+
+// Every structural cost at once by the route the engine has: the open block flushed, d = c - c_B' T0 in one coalesced pass over T0
+// (tableau_reprice), -obj from b.  No factorisation and no re-tabulation.
+relp_status_t Engine::set_cost(const double* cost_n) {
+    relp_status_t st = dual_ready("relp_set_cost");
+    if (st) return st;
+    for (int32_t j = 0; j < lay_.nr_normal; ++j)
+        if (!std::isfinite(cost_n[j])) return fail(RELP_E_ARG, "relp_set_cost: a value that is not finite");
+    tab_settle();
+    if ((st = edit_rec())) return st;
+    if (h_rec_->n_eta > 0 && (st = flush())) return st;
+    std::copy(cost_n, cost_n + lay_.nr_normal, lay_.cost.begin());
+    if ((st = store_costs(0, lay_.nr_normal))) return st;
+    tableau_reprice();
+    tab_partials_valid_ = false;
+    std::vector<double> b(lay_.m);
+    std::vector<int32_t> basis(lay_.m);
+    hipError_t e = d_b_.download(b, enqueue_only(stream_));
+    HIP_TRY(first_error(e, d_basis_.download(basis, stream_)));
+    if (hipGetLastError() != hipSuccess) return fail(RELP_E_HIP, "relp_set_cost: a kernel launch failed");
+    return edit_rec([&](PivotRecord& r) { r.minus_objective = -objective_of(basis, b); });
+}
+
+relp_status_t Engine::get_cost(double* out_n) {
+    const relp_status_t st = dual_ready("relp_get_cost");
+    if (st) return st;
+    std::copy(lay_.cost.begin(), lay_.cost.begin() + lay_.nr_normal, out_n);
+    return RELP_OK;
+}
+
+relp_status_t Engine::cost_stats(int64_t* out4) const {
+    if (!tableau_ || cfg_.shard_count > 1) return RELP_E_UNSUPPORTED;
+    if (phase_ != 2) return RELP_E_STATE;
+    out4[0] = cost_changes_; out4[1] = cost_rows_; out4[2] = cost_last_p_; out4[3] = cost_last_splits_;
     return RELP_OK;
 }
 

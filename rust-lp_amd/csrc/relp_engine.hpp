@@ -86,6 +86,7 @@ struct Switches {
     bool retab_global = false;                            // RELP_RETAB_GLOBAL
     int retab_groups = 0;                                 // RELP_RETAB_GROUPS (0: not given)
     int tab_rhs_splits = 0;                               // RELP_TAB_RHS_SPLITS (0: the rule of tab_rhs_splits)
+    int tab_cost_splits = 0;                              // RELP_TAB_COST_SPLITS (0: the rule of tab_cost_splits)
     static Switches read();
 };
 
@@ -129,6 +130,12 @@ class Engine : private EngineQueue {
     relp_status_t set_upper_bound(int32_t column, double value);
     relp_status_t get_right_hand_side(double* out_m);
     relp_status_t rhs_stats(int64_t* out4) const;
+    // the objective's side of it: structural costs moved on the current basis in place, or all of them by a reprice of the
+    // flushed tableau (no re-tabulation either way); relp_run continues from there
+    relp_status_t change_cost(const int32_t* columns, const double* values, int32_t count);
+    relp_status_t set_cost(const double* cost_n);
+    relp_status_t get_cost(double* out_n);
+    relp_status_t cost_stats(int64_t* out4) const;
     // batched ratio tests over the tableau as it stands, read-only: rows of T against d (penalties, cost ranges), identity columns
     // against b (rhs ranges)
     relp_status_t row_ratios(const int32_t* rows, int32_t count, double* down_ratio, int32_t* down_column, double* up_ratio,
@@ -290,6 +297,14 @@ class Engine : private EngineQueue {
     DeviceBuf<double> d_rhs_delta_, d_rhs_v_, d_rhs_partial_;      // (d_rhs_partial_: allocated at the first split launch, grown on demand)
     int64_t rhs_changes_ = 0, rhs_columns_ = 0;
     int32_t rhs_last_p_ = 0, rhs_last_splits_ = 0;
+    // relp_change_cost: the two compacted lists of a change -- (row, delta) of the basic columns, (storage column, delta) of the
+    // non-basic ones --, u = the pending rows' share and the per-split partial sums (relp_kernels.h: launch_tab_cost_change);
+    // what relp_cost_stats reports
+    DeviceBuf<int32_t> d_cost_rows_, d_cost_ncols_;
+    DeviceBuf<double> d_cost_delta_, d_cost_ndelta_, d_cost_u_, d_cost_partial_;
+    int64_t cost_changes_ = 0, cost_rows_ = 0;
+    int32_t cost_last_p_ = 0, cost_last_splits_ = 0;
+    relp_status_t store_costs(int32_t lo, int32_t hi);  // d_cost_, cost_store_h_, d_cost_store_ <- lay_.cost[lo, hi)
     // relp_row_ratios / relp_rhs_ranging: the uploaded list (rows, or their identity columns), the per-(direction, entry, block)
     // minima and the results [direction][entry] (relp_kernels.h: launch_tab_row_ratios, launch_tab_rhs_ranging); allocated at the
     // first query, grown on demand; what relp_ranging_stats reports

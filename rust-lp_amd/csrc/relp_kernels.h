@@ -503,6 +503,28 @@ int32_t tab_rhs_splits(int32_t m, int32_t count, int32_t forced);
 // splits * ld_partial doubles (unused when splits == 1).  No atomics: the same (list, p, splits) gives the same bits.
 void launch_tab_rhs_change(const TableauView& tv, const DeferredUpdate& du, const RhsChange& ch, int32_t p, int32_t splits,
                            double* v, double* b, double* partial, int64_t ld_partial, hipStream_t s);
+// A change of cost coefficients on the current basis (relp_change_cost): d_c -= sum_k delta[k] T[rows[k], c] with T = T0 + W R0
+// over the p pending rows, for every stored column c that is not flagged basic (in_basis == 1 keeps its d to the bit; the kept
+// artificial block and barred columns move).  rows[k] = the row in which the k-th changed basic column is basic, ascending (the
+// summation order, whatever order the caller named the columns in).  ncols / ndelta: the changed non-basic columns as storage
+// columns, ascending, each of which also gets d_c += ndelta.  Entries with delta 0 are in neither list.
+struct CostChange { const int32_t* rows; const double* delta; int32_t count; const int32_t* ncols; const double* ndelta; int32_t ncount; };
+// The basic list is cut into `splits` equal shares of ceil(count / splits) entries, one grid row of workgroups each.
+// tab_cost_splits: forced >= 1 (RELP_TAB_COST_SPLITS) clamped to [1, min(count, kTabCostMaxSplits)]; else as many as bring the grid
+// of cdiv(n_columns, 256) workgroups per split up to kTabCostGrid workgroups (five per CU), as long as every split keeps
+// kTabCostShareMin entries (three load batches of 8).  A thread's walk down its column is a chain of strided round trips, so
+// shares pay long before a share fills an LDS chunk: measured at 10,000 x 10,000, 408 entries take 0.31 ms in one
+// share and 0.18 ms in 16, 64 entries 0.124 ms in one and 0.116 ms in 2.
+static constexpr int32_t kTabCostGrid = 1280;
+static constexpr int32_t kTabCostShareMin = 24;
+static constexpr int32_t kTabCostMaxSplits = 256;
+int32_t tab_cost_splits(int32_t n_columns, int32_t count, int32_t forced);
+// [k_tab_cost_pending: u_j = sum_k delta_k W[j][rows[k]], p > 0 only] -> [k_tab_cost_apply: the T0 rows + u R0 and the direct term
+// per stored column; d -= or partial[split]] -> [k_tab_cost_reduce: d -= the partials in split order, splits > 1 only].  u: du.kmax
+// doubles; partial: splits * ld_partial doubles, ld_partial >= n_store (unused when splits == 1).  count == 0 with ncount > 0 is one
+// launch that reads no tableau entry.  No atomics: the same (lists, p, splits) gives the same bits.
+void launch_tab_cost_change(const TableauView& tv, const DeferredUpdate& du, const CostChange& ch, const uint8_t* in_basis, int32_t p,
+                            int32_t splits, double* u, double* partial, int64_t ld_partial, hipStream_t s);
 // Batched ratio tests over the tableau as it stands, T = T0 + W R0 over the p pending rows, read-only (relp_row_ratios,
 // relp_rhs_ranging).  The list is taken kTabRatioChunk entries per workgroup (a fixed size, not a rule: eight rows of one column are
 // one 64-byte sector of T0), grid = chunks x blocks of 256 columns (rows); the second launch has one workgroup per list entry.

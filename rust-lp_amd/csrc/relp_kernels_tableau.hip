@@ -1050,6 +1050,106 @@ __global__ __launch_bounds__(kThreads) void k_tab_rhs_reduce(int m, int splits, 
 }
 
 // ------------------------------------------------------------------------------------------------
+// A change of cost coefficients in place (relp_change_cost): the mirror image of the rhs change, rows in place of columns and d in
+// place of b.  With (r_k, delta_k) the rows of the changed basic columns, ascending r_k, and T = T0 + W R0 while a block is open:
+//   d_c -= sum_k delta_k T0[r_k, c] + sum_{j<p} u_j R0[j][c],   u_j = sum_k delta_k W[j][r_k]
+// for every stored column not flagged basic; a changed non-basic column also gets d_c += its own delta.
+// No atomics: every sum has a fixed order, so a given (list, p, splits) gives the same bits every run.
+// ------------------------------------------------------------------------------------------------
+// The stored column c is one the change moves: every one the pivot update maintains d for (the kept artificial block in front of
+// col_off included), except a column flagged basic (1), whose d the pivot update pinned at exactly 0.  A barred column (2) moves.
+__device__ __forceinline__ bool cost_moves_column(const TableauView& tv, const uint8_t* __restrict__ in_basis, int c) {
+    if (c >= tv.c_hi) return false;
+    const int j = c - tv.col_off;
+    return !(j >= 0 && j < tv.n && in_basis[j] == 1);
+}
+
+// u_j for pending row j = blockIdx.x: thread t sums its entries k = t, t + 256, ... in ascending order, then a fixed tree over the
+// 256 threads.  Column j of W is contiguous and the rows ascend: neighbouring entries share sectors.
+__global__ __launch_bounds__(kThreads) void k_tab_cost_pending(DeferredUpdate du, CostChange ch, double* __restrict__ u) {
+    __shared__ double s_sum[kThreads];
+    const double* col = du.W + (int64_t)blockIdx.x * du.ld;
+    double acc = 0.0;
+    for (int k = threadIdx.x; k < ch.count; k += kThreads) acc = fma(ch.delta[k], col[ch.rows[k]], acc);
+    s_sum[threadIdx.x] = acc;
+    __syncthreads();
+    for (int half = kThreads / 2; half > 0; half >>= 1) {
+        if ((int)threadIdx.x < half) s_sum[threadIdx.x] += s_sum[threadIdx.x + half];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) u[blockIdx.x] = s_sum[0];
+}
+
+// Stored column c = c_lo + blockIdx.x * 256 + threadIdx.x, split blockIdx.y of the basic list: entries [lo, hi) in ascending k,
+// staged in LDS 256 at a time, their T0 loads issued B at a time before any is used (a thread walks down its own column: eight
+// neighbouring rows are one 64-byte sector).  Split 0 then adds the pending rows' share through u (p > 0, R0 row j is contiguous
+// in c) and takes the direct term of a changed non-basic column from the second list (storage columns ascending, binary search).
+// splits == 1: d[c] -= acc, else partial[split][c] = acc.
+template <int B>
+__global__ __launch_bounds__(kThreads) void k_tab_cost_apply(TableauView tv, CostChange ch, const uint8_t* __restrict__ in_basis, int p,
+                                                             const double* __restrict__ u, double* __restrict__ partial,
+                                                             int64_t ld_partial) {
+    __shared__ int32_t s_r[kThreads];
+    __shared__ double s_delta[kThreads];
+    __shared__ double s_u[kMaxEta];
+    const int splits = gridDim.y, split = blockIdx.y;
+    const int share = (ch.count + splits - 1) / splits;
+    const int lo = min(split * share, ch.count), hi = min(lo + share, ch.count);
+    const int c = tv.c_lo + blockIdx.x * kThreads + threadIdx.x;
+    const bool mine = cost_moves_column(tv, in_basis, c);
+    const double* col = tv.T0 + (int64_t)(mine ? c : tv.c_lo) * tv.ld_t;
+    if (split == 0 && (int)threadIdx.x < p) s_u[threadIdx.x] = u[threadIdx.x];
+    double acc = 0.0;
+    for (int base = lo; base < hi; base += kThreads) {
+        __syncthreads();                               // (the previous chunk has been read)
+        const int n = min(kThreads, hi - base);
+        if ((int)threadIdx.x < n) { s_r[threadIdx.x] = ch.rows[base + threadIdx.x]; s_delta[threadIdx.x] = ch.delta[base + threadIdx.x]; }
+        __syncthreads();
+        if (!mine) continue;
+        int k0 = 0;
+        for (; k0 + B <= n; k0 += B) {
+            double t[B];
+#pragma unroll
+            for (int v = 0; v < B; ++v) t[v] = col[s_r[k0 + v]];
+#pragma unroll
+            for (int v = 0; v < B; ++v) acc = fma(s_delta[k0 + v], t[v], acc);
+        }
+        if (k0 < n) {
+            double t[B];
+#pragma unroll
+            for (int v = 0; v < B; ++v) t[v] = k0 + v < n ? col[s_r[k0 + v]] : 0.0;
+#pragma unroll
+            for (int v = 0; v < B; ++v)
+                if (k0 + v < n) acc = fma(s_delta[k0 + v], t[v], acc);
+        }
+    }
+    __syncthreads();                                   // s_u (a split with an empty share never entered the loop)
+    if (!mine) return;
+    if (split == 0) {
+        for_pending<B>(tv.R0, tv.ld_r, c, p, [&](int j, double r0) { acc = fma(s_u[j], r0, acc); });
+        int a = 0, z = ch.ncount;
+        while (a < z) {
+            const int mid = (a + z) >> 1;
+            if (ch.ncols[mid] < c) a = mid + 1;
+            else z = mid;
+        }
+        if (a < ch.ncount && ch.ncols[a] == c) acc -= ch.ndelta[a];
+    }
+    if (splits == 1) tv.d[c] -= acc;
+    else partial[(int64_t)split * ld_partial + c] = acc;
+}
+
+// d[c] -= partial[0][c] + partial[1][c] + ... in ascending split order, for the columns k_tab_cost_apply wrote
+__global__ __launch_bounds__(kThreads) void k_tab_cost_reduce(TableauView tv, const uint8_t* __restrict__ in_basis, int splits,
+                                                              const double* __restrict__ partial, int64_t ld_partial) {
+    const int c = tv.c_lo + blockIdx.x * kThreads + threadIdx.x;
+    if (!cost_moves_column(tv, in_basis, c)) return;
+    double sum = partial[c];
+    for (int s = 1; s < splits; ++s) sum += partial[(int64_t)s * ld_partial + c];
+    tv.d[c] -= sum;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Batched ratio tests over the tableau as it stands (relp_row_ratios, relp_rhs_ranging): read-only streams over T0 (+ W R0 while
 // an update block is open, p = its pending rows).  Two launches each: [the minimum of every (list entry, block of 256 columns or
 // rows) into scratch] -> [one workgroup per list entry: the minimum of its blocks, then the tie band from the blocks whose own
@@ -1493,6 +1593,26 @@ void launch_tab_rhs_change(const TableauView& tv, const DeferredUpdate& du, cons
                            ld_partial);
     });
     if (splits > 1) hipLaunchKernelGGL(k_tab_rhs_reduce, dim3(nb), dim3(kThreads), 0, s, (int)tv.m, (int)splits, partial, ld_partial, b);
+}
+
+int32_t tab_cost_splits(int32_t n_columns, int32_t count, int32_t forced) {
+    if (count < 1) return 1;
+    if (forced >= 1) return std::min({forced, count, kTabCostMaxSplits});
+    const int32_t fill = kTabCostGrid / cdiv(n_columns, kThreads);     // splits until the grid covers the device five times ...
+    return std::max(1, std::min({fill, count / kTabCostShareMin, kTabCostMaxSplits}));  // ... each with three load batches of the list
+}
+
+void launch_tab_cost_change(const TableauView& tv, const DeferredUpdate& du, const CostChange& ch, const uint8_t* in_basis, int32_t p,
+                            int32_t splits, double* u, double* partial, int64_t ld_partial, hipStream_t s) {
+    if ((ch.count < 1 && ch.ncount < 1) || tv.c_hi <= tv.c_lo) return;
+    if (ch.count < 1) { p = 0; splits = 1; }           // only direct terms: no row of the tableau is read
+    if (p > 0) hipLaunchKernelGGL(k_tab_cost_pending, dim3(p), dim3(kThreads), 0, s, du, ch, u);
+    const int nb = tab_scan_blocks(tv.c_hi - tv.c_lo);
+    with_load_batch(du.batch, [&](auto B) {
+        hipLaunchKernelGGL((k_tab_cost_apply<decltype(B)::value>), dim3(nb, splits), dim3(kThreads), 0, s, tv, ch, in_basis, (int)p, u, partial,
+                           ld_partial);
+    });
+    if (splits > 1) hipLaunchKernelGGL(k_tab_cost_reduce, dim3(nb), dim3(kThreads), 0, s, tv, in_basis, (int)splits, partial, ld_partial);
 }
 
 void launch_tab_row_ratios(const TableauView& tv, const DeferredUpdate& du, const SelectPartials& sp, Tolerances tol,

@@ -96,6 +96,10 @@ _SIGNATURES = {
     "relp_set_upper_bound": (C.c_int, [C.c_void_p, C.c_int32, C.c_double]),
     "relp_get_right_hand_side": (C.c_int, [C.c_void_p, C.c_void_p]),
     "relp_rhs_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "relp_change_cost": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
+    "relp_set_cost": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "relp_get_cost": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "relp_cost_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "relp_row_ratios": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "relp_rhs_ranging": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "relp_ranging_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
@@ -432,6 +436,37 @@ class Tableau:
         the list in its last launch); relp_rhs_stats."""
         out = (C.c_int64 * 4)()
         self._ck(self._lib.relp_rhs_stats(self._h, out))
+        return tuple(int(x) for x in out)
+
+    def change_cost(self, columns, values) -> None:
+        """cost[columns[k]] = values[k] on the current basis without a flush or a re-tabulation (relp_change_cost): the reduced
+        costs move by the tableau rows of the changed basic columns, read off T0 + W R0; b, the basis and the open update block
+        stay.  ``columns`` are structural columns, each named once; ``run`` re-solves from there."""
+        c = np.ascontiguousarray(columns, dtype=np.int32)
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        if c.ndim != 1 or c.shape != v.shape:
+            raise ValueError("columns and values must be one-dimensional and of the same length")
+        self._ck(self._lib.relp_change_cost(self._h, c.ctypes.data, v.ctypes.data, c.shape[0]))
+
+    def set_cost(self, cost) -> None:
+        """Every structural cost at once (relp_set_cost): an open update block is flushed, then d = c - c_B' T0 in one pass over
+        the tableau.  No re-tabulation; the call to make when most costs move."""
+        arr = np.ascontiguousarray(cost, dtype=np.float64)
+        if arr.shape != (self.provider.nr_normal,):
+            raise ValueError("cost must have one entry per structural column")
+        self._ck(self._lib.relp_set_cost(self._h, arr.ctypes.data))
+
+    def cost(self) -> np.ndarray:
+        """The structural costs in effect, one per structural column (relp_get_cost)."""
+        out = np.zeros(self.provider.nr_normal)
+        self._ck(self._lib.relp_get_cost(self._h, out.ctypes.data))
+        return out
+
+    def cost_stats(self) -> Tuple[int, int, int, int]:
+        """(in-place cost changes so far, tableau rows they read, pending rows of the update block at the last change, shares of
+        the basic list in its last launch); relp_cost_stats."""
+        out = (C.c_int64 * 4)()
+        self._ck(self._lib.relp_cost_stats(self._h, out))
         return tuple(int(x) for x in out)
 
     def _ratio_query(self, call, rows):
