@@ -10,11 +10,16 @@ to ``fma_exact`` bit for bit, and every GPU case re-checks a fixed sample of its
 Layouts.  Logical arrays are C-ordered: T0[c][i] (n_owned x m), W[j][i] (p x m), R0[j][c] (p x n_owned), Binv[i][j] (m x m).
 The harness returns whole device images: T0 n_owned x ld_t, W kmax x ld_b, R0 (kmax + 1) x ld_r, Binv m x ld_b; the functions
 below cut them into the logical part and the rest.
+
+T5 - T8 (the in-place changes and the batched ratio queries, at the end of the file): the models return the whole EXPECTED image
+of every buffer, the sentinel where the launcher must not write, and ``diff_image`` compares image with image.  Their case tables
+are in tests/kernel_query_cases.py.
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
+import subprocess
 from fractions import Fraction
 
 import numpy as np
@@ -62,6 +67,12 @@ _lib = None
 def load():
     global _lib
     if _lib is None:
+        if not os.path.exists(LIB_PATH):
+            # build() makes it; a tests/ directory put in place after the build has lost it, so make it here as the tests of
+            # tests/cpp make their programs (the Makefile needs the engine library build() made: without it make fails)
+            made = subprocess.run(["make", "-C", os.path.dirname(LIB_PATH), "ARCH=gfx950"], capture_output=True, text=True)
+            if made.returncode:
+                raise FileNotFoundError(f"{LIB_PATH} is missing and make -C tests/kernels failed: run build()\n{made.stderr[-2000:]}")
         if not os.path.exists(LIB_PATH):
             raise FileNotFoundError(f"{LIB_PATH} is missing: run build() (make -C tests/kernels)")
         _lib = C.CDLL(LIB_PATH)
@@ -592,3 +603,455 @@ def int_data(rng, shape, zeros=0.3):
 
 def distinct_rows(rng, m, p):
     return rng.permutation(m)[:p].astype(np.int32)
+
+
+# ========================================================================================================================
+# T5 - T8: the in-place changes (launch_tab_rhs_change, launch_tab_cost_change) and the batched ratio queries
+# (launch_tab_row_ratios, launch_tab_rhs_ranging)
+# ========================================================================================================================
+REFUSED_SPLITS, REFUSED_ORDER = -5, -6
+MAX_SPLITS = 256                         # kTabRhsMaxSplits = kTabCostMaxSplits
+RHS_GRID, COST_GRID, COST_SHARE_MIN = 512, 1280, 24
+RATIO_CHUNK = 8                          # kTabRatioChunk
+SCRATCH_TAIL = 64                        # sentinel words behind the partial minima of T7 / T8
+ENTERING_LIST_MAX, LEAVING_LIST_MAX = 32, 64     # select_entering / block_minima_pick: listed slots before every slot is walked
+
+
+def _u8(a): return np.ascontiguousarray(a, dtype=np.uint8)
+
+
+def _outs(L, lengths, dt):
+    L = dict(L)
+    L.update(lengths or {})
+    return {k: np.zeros(v, dtype=dt.get(k, np.float64)) for k, v in L.items()}
+
+
+def tab_splits(which, size, count, forced=0, lengths=None):
+    """tab_rhs_splits (which = 0, size = m) / tab_cost_splits (which = 1, size = stored columns); no HIP call."""
+    out = np.zeros((lengths or {}).get("out", 1), dtype=np.int32)
+    _call("rkh_tab_splits", [_n(which), _w(size), _w(count), _w(forced)], [out])
+    return int(out[0])
+
+
+def tab_rhs_change(T0, W, R0, b, cols, delta, kmax, splits=1, c_lo=0, batch=8, fill=True, lengths=None):
+    """launch_tab_rhs_change.  cols: storage columns.  Whole images back."""
+    T0, W, R0 = _f64(T0), _f64(W), _f64(R0)
+    n, m = T0.shape
+    p = W.shape[0]
+    cols, delta = _i32(cols), _f64(delta)
+    count = cols.size
+    out = _outs(dict(b=ld_b(m), v=kmax, partial=max(splits, 0) * ld_b(m), T0=n * ld_t(m), W=kmax * ld_b(m), R0=(kmax + 1) * ld_r(n),
+                     cols=count, delta=count), lengths, dict(cols=np.int32))
+    _call("rkh_tab_rhs_change", [_w(m), _w(n), _w(p), _w(kmax), _w(c_lo), _n(batch), _w(count), _w(splits), _n(fill)],
+          [T0, W, R0, _f64(b), cols, delta] + [out[k] for k in ("b", "v", "partial", "T0", "W", "R0", "cols", "delta")])
+    return out
+
+
+def tab_cost_change(T0, W, R0, d, in_basis, rows, delta, ncols, ndelta, kmax, splits=1, c_lo=0, col_off=0, batch=8, fill=True,
+                    lengths=None):
+    """launch_tab_cost_change.  d: the owned columns; in_basis: c_lo + n_owned - col_off flags by tableau column; ncols: storage
+    columns."""
+    T0, W, R0 = _f64(T0), _f64(W), _f64(R0)
+    n, m = T0.shape
+    p = W.shape[0]
+    rows, delta, ncols, ndelta, in_basis = _i32(rows), _f64(delta), _i32(ncols), _f64(ndelta), _u8(in_basis)
+    out = _outs(dict(d=c_lo + n, u=kmax, partial=max(splits, 0) * ld_r(n), in_basis=max(c_lo + n - col_off, 0), T0=n * ld_t(m),
+                     W=kmax * ld_b(m), R0=(kmax + 1) * ld_r(n), rows=rows.size, delta=rows.size, ncols=ncols.size, ndelta=ncols.size),
+                lengths, dict(in_basis=np.uint8, rows=np.int32, ncols=np.int32))
+    _call("rkh_tab_cost_change",
+          [_w(m), _w(n), _w(p), _w(kmax), _w(c_lo), _w(col_off), _n(batch), _w(rows.size), _w(ncols.size), _w(splits), _n(fill)],
+          [T0, W, R0, _f64(d), in_basis, rows, delta, ncols, ndelta] +
+          [out[k] for k in ("d", "u", "partial", "in_basis", "T0", "W", "R0", "rows", "delta", "ncols", "ndelta")])
+    return out
+
+
+def tab_row_ratios(T0, W, R0, d, in_basis, rows, tol, kmax, c_lo=0, col_off=0, batch=8, fill=True, lengths=None):
+    """launch_tab_row_ratios.  tol = (pivot, zero, tie).  ratio / column: [direction][list entry]."""
+    T0, W, R0 = _f64(T0), _f64(W), _f64(R0)
+    n, m = T0.shape
+    p = W.shape[0]
+    rows, in_basis = _i32(rows), _u8(in_basis)
+    count = rows.size
+    scratch = 2 * count * scan_blocks(n) + SCRATCH_TAIL
+    out = _outs(dict(ratio=2 * count, column=2 * count, part_k=scratch, part_j=scratch, d=c_lo + n, in_basis=max(c_lo + n - col_off, 0),
+                     T0=n * ld_t(m), W=kmax * ld_b(m), R0=(kmax + 1) * ld_r(n), rows=count), lengths,
+                dict(column=np.int32, part_j=np.int32, in_basis=np.uint8, rows=np.int32))
+    _call("rkh_tab_row_ratios", [_w(m), _w(n), _w(p), _w(kmax), _w(c_lo), _w(col_off), _n(batch), _w(count), _n(fill)],
+          [_f64(tol), T0, W, R0, _f64(d), in_basis, rows] +
+          [out[k] for k in ("ratio", "column", "part_k", "part_j", "d", "in_basis", "T0", "W", "R0", "rows")])
+    return out
+
+
+def tab_rhs_ranging(T0, W, R0, b, basis, cols, tol, kmax, c_lo=0, batch=8, fill=True, lengths=None):
+    """launch_tab_rhs_ranging.  cols: storage columns.  ratio / row: [direction][list entry]."""
+    T0, W, R0 = _f64(T0), _f64(W), _f64(R0)
+    n, m = T0.shape
+    p = W.shape[0]
+    cols, basis = _i32(cols), _i32(basis)
+    count = cols.size
+    scratch = 2 * count * scan_blocks(m) + SCRATCH_TAIL
+    out = _outs(dict(ratio=2 * count, row=2 * count, part=scratch, b=ld_b(m), basis=m, T0=n * ld_t(m), W=kmax * ld_b(m),
+                     R0=(kmax + 1) * ld_r(n), cols=count), lengths, dict(row=np.int32, basis=np.int32, cols=np.int32))
+    _call("rkh_tab_rhs_ranging", [_w(m), _w(n), _w(p), _w(kmax), _w(c_lo), _n(batch), _w(count), _n(fill)],
+          [_f64(tol), T0, W, R0, _f64(b), basis, cols] +
+          [out[k] for k in ("ratio", "row", "part", "b", "basis", "T0", "W", "R0", "cols")])
+    return out
+
+
+# ---- models of the sums --------------------------------------------------------------------------------------------------
+def model_splits(which, size, count, forced=0):
+    """tab_rhs_splits / tab_cost_splits as relp_kernels.h states the rule."""
+    if count < 1:
+        return 1
+    if forced >= 1:
+        return min(forced, count, MAX_SPLITS)
+    blocks = scan_blocks(size)
+    if which == 0:
+        return max(1, min(RHS_GRID // blocks, count // 256, MAX_SPLITS))
+    return max(1, min(COST_GRID // blocks, count // COST_SHARE_MIN, MAX_SPLITS))
+
+
+def share_bounds(count, splits):
+    """[lo, hi) of every split: equal shares of ceil(count / splits) entries, the last ones short or empty."""
+    share = (count + splits - 1) // splits
+    return [(min(s * share, count), min(min(s * share, count) + share, count)) for s in range(splits)]
+
+
+def model_pending(delta, X, order="tree"):
+    """sum_k delta[k] X[j][k] for every row j of X (p x count) as k_tab_rhs_pending / k_tab_cost_pending form it: thread t's fma
+    chain over k = t, t + 256, ... from 0.0, then the tree s[t] += s[t + half], half = 128 .. 1.  order = "plain": the 256 thread
+    sums added left to right instead (what the tree is NOT; the CPU tier uses it)."""
+    X = np.asarray(X, dtype=np.float64)
+    p, count = X.shape
+    trips = (count + 255) // 256
+    s = np.zeros((p, 256))
+    for trip in range(trips):
+        k = np.arange(trip * 256, min((trip + 1) * 256, count))
+        s[:, :k.size] = fma_vec(delta[k][None, :], X[:, k], s[:, :k.size])
+    if order == "plain":
+        acc = s[:, 0].copy()
+        for t in range(1, 256):
+            acc = acc + s[:, t]
+        return acc
+    half = 128
+    while half:
+        s[:, :half] = s[:, :half] + s[:, half:2 * half]
+        half //= 2
+    return s[:, 0].copy()
+
+
+def model_shares(term, delta, count, splits, width):
+    """parts[s] = the fma chain from 0.0 over the share of split s, term(k) = the vector entry k multiplies."""
+    parts = np.zeros((splits, width))
+    for s, (lo, hi) in enumerate(share_bounds(count, splits)):
+        acc = np.zeros(width)
+        for k in range(lo, hi):
+            acc = fma_vec(delta[k], term(k), acc)
+        parts[s] = acc
+    return parts
+
+
+def sum_in_split_order(parts):
+    total = parts[0].copy()
+    for s in range(1, parts.shape[0]):
+        total = total + parts[s]
+    return total
+
+
+def rhs_change_expected(T0, W, R0, b, cols, delta, kmax, splits=1, c_lo=0, swap_shares=None):
+    """Every image launch_tab_rhs_change must leave, by the comments of k_tab_rhs_pending / _apply / _reduce.
+    swap_shares = (s, t): the partials of splits s and t added in swapped places (a wrong order, for the CPU tier)."""
+    T0, W, R0, b, delta = (np.asarray(x, dtype=np.float64) for x in (T0, W, R0, b, delta))
+    n, m = T0.shape
+    p = W.shape[0]
+    cl = np.asarray(cols, dtype=np.int64) - c_lo
+    count = cl.size
+    v = model_pending(delta, R0[:, cl]) if p else np.zeros(0)
+    parts = model_shares(lambda k: T0[cl[k]], delta, count, splits, m)
+    for j in range(p):
+        parts[0] = fma_vec(W[j], v[j], parts[0])
+    order = list(range(splits))
+    if swap_shares:
+        s, t = swap_shares
+        order[s], order[t] = order[t], order[s]
+    bn = b + (parts[0] if splits == 1 else sum_in_split_order(parts[order]))
+    partial = np.full((max(splits, 1), ld_b(m)), SENTINEL)
+    if splits > 1:
+        partial[:, :m] = parts
+    t_up, w_up, r_up = tab_images(None, m, n, p, kmax, T0, W, R0)
+    return dict(b=vec_image(bn, m, ld_b(m)), v=vec_image(v, p, kmax), partial=partial.reshape(-1)[:splits * ld_b(m)], T0=t_up.reshape(-1),
+                W=w_up.reshape(-1), R0=r_up.reshape(-1), cols=np.asarray(cols, dtype=np.int32), delta=delta.copy(), parts=parts)
+
+
+def cost_moves(n, c_lo, col_off, in_basis):
+    """The owned columns launch_tab_cost_change moves (cost_moves_column): all but those flagged 1 by TABLEAU column c - col_off."""
+    c = c_lo + np.arange(n)
+    j = c - col_off
+    flags = np.asarray(in_basis)
+    inside = (j >= 0) & (j < flags.size)
+    basic = np.zeros(n, dtype=bool)
+    basic[inside] = flags[j[inside]] == 1
+    return ~basic
+
+
+def cost_change_expected(T0, W, R0, d, in_basis, rows, delta, ncols, ndelta, kmax, splits=1, c_lo=0, col_off=0, swap_shares=None):
+    """Every image launch_tab_cost_change must leave, by the comments of k_tab_cost_pending / _apply / _reduce."""
+    T0, W, R0, d, delta, ndelta = (np.asarray(x, dtype=np.float64) for x in (T0, W, R0, d, delta, ndelta))
+    n, m = T0.shape
+    p_img = W.shape[0]
+    rows = np.asarray(rows, dtype=np.int64)
+    ncl = np.asarray(ncols, dtype=np.int64) - c_lo
+    count = rows.size
+    p = p_img if count else 0                              # only direct terms: the launcher forces p = 0 and splits = 1
+    assert count or splits == 1
+    u = model_pending(delta, W[:, rows]) if p else np.zeros(0)
+    parts = model_shares(lambda k: T0[:, rows[k]], delta, count, splits, n)
+    for j in range(p):
+        parts[0] = fma_vec(u[j], R0[j], parts[0])
+    parts[0][ncl] = parts[0][ncl] - ndelta
+    order = list(range(splits))
+    if swap_shares:
+        s, t = swap_shares
+        order[s], order[t] = order[t], order[s]
+    moves = cost_moves(n, c_lo, col_off, in_basis)
+    total = parts[0] if splits == 1 else sum_in_split_order(parts[order])
+    dn = np.full(c_lo + n, SENTINEL)
+    dn[c_lo:] = np.where(moves, d - total, d)
+    keep = bits(d)[~moves]
+    dn_bits = bits(dn).copy()
+    dn_bits[c_lo:][~moves] = keep                          # a column flagged 1 keeps its d to the bit (np.where keeps NaN payloads, this is explicit)
+    partial = np.full((max(splits, 1), ld_r(n)), SENTINEL)
+    if splits > 1:
+        partial[:, :n][:, moves] = parts[:, moves]
+    t_up, w_up, r_up = tab_images(None, m, n, p_img, kmax, T0, W, R0)
+    return dict(d=dn_bits.view(np.float64), u=vec_image(u, p, kmax), partial=partial.reshape(-1)[:splits * ld_r(n)],
+                in_basis=np.asarray(in_basis, dtype=np.uint8).copy(), T0=t_up.reshape(-1), W=w_up.reshape(-1), R0=r_up.reshape(-1),
+                rows=rows.astype(np.int32), delta=delta.copy(), ncols=np.asarray(ncols, dtype=np.int32), ndelta=ndelta.copy(),
+                parts=parts, moves=moves)
+
+
+def diff_image(got, want, what, limit=5):
+    """A whole returned image against the expected one, bit for bit: where `want` holds the sentinel the word must still hold it,
+    elsewhere the bits are equal and no NaN has appeared."""
+    got, want = np.asarray(got), np.asarray(want)
+    if got.shape != want.shape:
+        return [f"{what}: shape {got.shape} != {want.shape}"]
+    if got.dtype.kind != "f":
+        return diff_unchanged(got, want, what, limit)
+    bg, bw = bits(got).reshape(got.shape), bits(want).reshape(want.shape)
+    bad = (bg != bw) | (np.isnan(got) & (bw != SENTINEL_BITS))
+    idx = np.argwhere(bad)
+    return [f"{what}{tuple(i)}: got {got[tuple(i)]!r} ({bg[tuple(i)]:#x}), want {want[tuple(i)]!r} ({bw[tuple(i)]:#x})"
+            for i in idx[:limit]] + ([f"{what}: {len(idx)} words differ"] if len(idx) > limit else [])
+
+
+RHS_IMAGES = ("b", "v", "partial", "T0", "W", "R0", "cols", "delta")
+COST_IMAGES = ("d", "u", "partial", "in_basis", "T0", "W", "R0", "rows", "delta", "ncols", "ndelta")
+
+
+def compare_images(out, exp, names):
+    return [f for k in names for f in diff_image(out[k], exp[k], k)]
+
+
+# ---- exact values (integers and rationals) -----------------------------------------------------------------------------------
+def rhs_change_int(T0, W, R0, b, cols, delta, c_lo=0):
+    """b + T0' delta + W' (R0 delta) in int64 for integer-valued operands: every order of summation gives this float64."""
+    Ti, Wi, Ri, bi, di = (np.asarray(x).astype(np.int64) for x in (T0, W, R0, b, delta))
+    assert all((a == x).all() for a, x in ((Ti, T0), (Wi, W), (Ri, R0), (bi, b), (di, delta))), "integer data expected"
+    cl = np.asarray(cols, dtype=np.int64) - c_lo
+    out = bi + di @ Ti[cl] + (Ri[:, cl] @ di) @ Wi
+    assert np.abs(out).max() < 2 ** 52
+    return out.astype(np.float64)
+
+
+def cost_change_int(T0, W, R0, d, rows, delta, ncols, ndelta, moves, c_lo=0):
+    Ti, Wi, Ri, di, ni = (np.asarray(x).astype(np.int64) for x in (T0, W, R0, delta, ndelta))
+    dd = np.asarray(d, dtype=np.float64)                   # (integer-valued where a column moves; anything where it is pinned)
+    rows = np.asarray(rows, dtype=np.int64)
+    acc = Ti[:, rows] @ di + ((Wi[:, rows] @ di) @ Ri if rows.size else 0)
+    acc[np.asarray(ncols, dtype=np.int64) - c_lo] -= ni
+    assert np.abs(acc).max() < 2 ** 52
+    with np.errstate(all="ignore"):
+        return np.where(moves, dd - acc, dd)
+
+
+_SCALE = 60
+
+
+def _ints(a):
+    """float64 array -> Python ints of a * 2^60 (exact: asserted)."""
+    y = np.asarray(a, dtype=np.float64) * 2.0 ** _SCALE
+    assert np.all(np.floor(y) == y) and np.all(np.abs(y) < 2.0 ** 1000), "data finer than 2^-60"
+    return [int(v) for v in y.reshape(-1).tolist()]
+
+
+def gamma(N):
+    """gamma_N = N u / (1 - N u), u = 2^-53 (Higham, Accuracy and Stability of Numerical Algorithms, Lemma 3.1)."""
+    return Fraction(N) * Fraction(EPS53) / (1 - Fraction(N) * Fraction(EPS53))
+
+
+def sum_roundings(count, splits, p):
+    """Roundings on the longest path from an input to the output: share length + ceil(count / 256) + 8 tree levels + p + splits + 1."""
+    return (count + splits - 1) // max(splits, 1) + (count + 255) // 256 + 8 + p + splits + 1
+
+
+def exact_check(got, base, A, delta, U, X, N, sample, sign=1, extra=None):
+    """got[e] against base[e] + sign * (sum_k delta[k] A[k][e] + sum_j U[j][e] sum_k delta[k] X[j][k]) as exact rationals
+    (fractions.Fraction over integers scaled by powers of two), bound gamma_N * S, S = the sum of the absolute values of all terms,
+    |base[e]| included; extra[e] (a direct term) is added as it stands.  A: count x width, U: p x width, X: p x count.  Returns (violations, largest error / (2^-53 S))."""
+    count, p = len(delta), U.shape[0]
+    di = _ints(delta)
+    xi = [_ints(X[j]) for j in range(p)]
+    vj = [sum(a * b for a, b in zip(di, xi[j])) for j in range(p)]                     # scale 2^120
+    vabs = [sum(abs(a * b) for a, b in zip(di, xi[j])) for j in range(p)]
+    bad, worst = [], 0.0
+    one = 1 << _SCALE
+    for e in sample:
+        ai = _ints(A[:, e]) if count else []
+        ui = _ints(U[:, e]) if p else []
+        bi = _ints(base[e:e + 1])[0]
+        xe = _ints(extra[e:e + 1])[0] if extra is not None else 0
+        t1 = sum(a * b for a, b in zip(di, ai))                                          # scale 2^120
+        s1 = sum(abs(a * b) for a, b in zip(di, ai))
+        t2 = sum(a * b for a, b in zip(ui, vj))                                          # scale 2^180
+        s2 = sum(abs(a) * b for a, b in zip(ui, vabs))
+        exact = Fraction(bi + xe, one) + sign * (Fraction(t1, one ** 2) + Fraction(t2, one ** 3))
+        S = Fraction(abs(bi) + abs(xe), one) + Fraction(s1, one ** 2) + Fraction(s2, one ** 3)
+        g = float(got[e])
+        if not np.isfinite(g):
+            bad.append((e, g, "not finite"))
+            continue
+        err = abs(Fraction(g) - exact)
+        if S > 0:
+            worst = max(worst, float(err / (Fraction(EPS53) * S)))
+        if err > gamma(N) * S:
+            bad.append((e, g, float(exact)))
+    return bad, worst
+
+
+# ---- models of the ratio queries ---------------------------------------------------------------------------------------------
+def band_bounds(k1, tie):
+    """k1 + tie * max(1, |k1|) with two roundings and as one fma: the compiler may contract the expression."""
+    s = max(1.0, abs(float(k1)))
+    return float(k1) + float(tie) * s, fma_exact(tie, s, k1)
+
+
+def model_rows_of_T(T0, W, R0, rows):
+    """E[k][c] = T[rows[k], c]: T0, then one fma per pending row in ascending j (tab_row_entry)."""
+    rows = np.asarray(rows, dtype=np.int64)
+    E = np.array(T0[:, rows].T, dtype=np.float64)
+    for j in range(W.shape[0]):
+        E = fma_vec(W[j, rows][:, None], R0[j][None, :], E)
+    return E
+
+
+def model_columns_of_T(T0, W, R0, cl):
+    """A[k][i] = T[i, cl[k]]: T0, then one fma per pending row in ascending j (tab_column_entry)."""
+    cl = np.asarray(cl, dtype=np.int64)
+    A = np.array(T0[cl], dtype=np.float64)
+    for j in range(W.shape[0]):
+        A = fma_vec(W[j][None, :], R0[j, cl][:, None], A)
+    return A
+
+
+def _pick_lowest(ratio, key, bound):
+    inside = ratio <= bound
+    return int(key[inside].min())
+
+
+def model_row_ratios(T0, W, R0, d, in_basis, rows, tol, c_lo=0, col_off=0):
+    """launch_tab_row_ratios.  Returns ratio, column (2 x count, [direction][entry], the pick with the two-rounding bound),
+    column_fma (the pick with the contracted bound) and between (candidates whose ratio lies between the two bounds)."""
+    T0, W, R0, d = (np.asarray(x, dtype=np.float64) for x in (T0, W, R0, d))
+    n = T0.shape[0]
+    flags = np.asarray(in_basis)
+    tol_pivot, tol_zero, tol_tie = (float(t) for t in tol)
+    j = c_lo + np.arange(n) - col_off
+    inside = (j >= 0) & (j < flags.size)
+    nonbasic = np.zeros(n, dtype=bool)
+    nonbasic[inside] = flags[j[inside]] == 0
+    E = model_rows_of_T(T0, W, R0, rows)
+    count = E.shape[0]
+    dz = np.where(d <= tol_zero, 0.0, d)
+    ratio = np.full((2, count), np.inf)
+    column = np.full((2, count), -1, dtype=np.int32)
+    column_fma = column.copy()
+    between = np.zeros((2, count), dtype=np.int64)
+    for direction in range(2):
+        V = -E if direction else E
+        for k in range(count):
+            cand = nonbasic & (V[k] < -tol_pivot)
+            if not cand.any():
+                continue
+            with np.errstate(all="ignore"):
+                r = dz[cand] / (-V[k][cand])
+            k1 = r.min()
+            b2, b1 = band_bounds(k1, tol_tie)
+            ratio[direction, k] = k1
+            column[direction, k] = _pick_lowest(r, j[cand], b2)
+            column_fma[direction, k] = _pick_lowest(r, j[cand], b1)
+            between[direction, k] = int(((r > min(b1, b2)) & (r <= max(b1, b2))).sum())
+    return dict(ratio=ratio.reshape(-1), column=column.reshape(-1), column_fma=column_fma.reshape(-1), between=between.reshape(-1), E=E)
+
+
+def model_rhs_ranging(T0, W, R0, b, basis, cols, tol, c_lo=0, signed_keys=False):
+    """launch_tab_rhs_ranging.  As model_row_ratios; the pick is the row inside the band with the smallest basis entry as an
+    UNSIGNED 32-bit value (signed_keys: the wrong comparison, for the CPU tier)."""
+    T0, W, R0, b = (np.asarray(x, dtype=np.float64) for x in (T0, W, R0, b))
+    m = T0.shape[1]
+    tol_pivot, tol_zero, tol_tie = (float(t) for t in tol)
+    key = np.asarray(basis, dtype=np.int32).astype(np.int64)
+    if not signed_keys:
+        key = key & 0xFFFFFFFF
+    A = model_columns_of_T(T0, W, R0, np.asarray(cols, dtype=np.int64) - c_lo)
+    count = A.shape[0]
+    bz = np.where(b <= tol_zero, 0.0, b)
+    ratio = np.full((2, count), np.inf)
+    row = np.full((2, count), -1, dtype=np.int32)
+    row_fma = row.copy()
+    between = np.zeros((2, count), dtype=np.int64)
+    idx = np.arange(m)
+    for direction in range(2):
+        V = -A if direction else A
+        for k in range(count):
+            q = V[k] > tol_pivot
+            if not q.any():
+                continue
+            with np.errstate(all="ignore"):
+                r = bz[q] / V[k][q]
+            gmin = r.min()
+            b2, b1 = band_bounds(gmin, tol_tie)
+            ratio[direction, k] = gmin
+            for bound, dst in ((b2, row), (b1, row_fma)):
+                ins = r <= bound
+                dst[direction, k] = int(idx[q][ins][np.argmin(key[q][ins])])
+            between[direction, k] = int(((r > min(b1, b2)) & (r <= max(b1, b2))).sum())
+    return dict(ratio=ratio.reshape(-1), row=row.reshape(-1), row_fma=row_fma.reshape(-1), between=between.reshape(-1), A=A)
+
+
+def compare_row_ratios(out, exp, before):
+    """`before`: dict of the uploaded images (d, in_basis, T0, W, R0, rows) the launcher must leave alone."""
+    nscr = out["part_k"].size - SCRATCH_TAIL
+    return (diff_bits(out["ratio"], exp["ratio"], "ratio") + diff_values(out["column"], exp["column"], "column") +
+            sentinel_violations(out["part_k"][nscr:], "part_k tail") + sentinel_violations(out["part_j"][nscr:], "part_j tail") +
+            [f for k in ("d", "in_basis", "T0", "W", "R0", "rows") for f in diff_unchanged(out[k], before[k], k)])
+
+
+def compare_rhs_ranging(out, exp, before):
+    nscr = out["part"].size - SCRATCH_TAIL
+    return (diff_bits(out["ratio"], exp["ratio"], "ratio") + diff_values(out["row"], exp["row"], "row") +
+            sentinel_violations(out["part"][nscr:], "part tail") +
+            [f for k in ("b", "basis", "T0", "W", "R0", "cols") for f in diff_unchanged(out[k], before[k], k)])
+
+
+def query_images(T0, W, R0, kmax, c_lo=0, d=None, b=None):
+    """What the harness uploads for a read-only query (flat images)."""
+    n, m = T0.shape
+    t, w, r = tab_images(None, m, n, W.shape[0], kmax, T0, W, R0)
+    img = dict(T0=t.reshape(-1), W=w.reshape(-1), R0=r.reshape(-1))
+    if d is not None:
+        img["d"] = np.full(c_lo + n, SENTINEL)
+        img["d"][c_lo:] = d
+    if b is not None:
+        img["b"] = vec_image(b, m, ld_b(m))
+    return img

@@ -1,4 +1,5 @@
-// harness.cpp -- test infrastructure: one extern "C" entry per launcher family of the blocked update, so that a test can
+// harness.cpp -- test infrastructure: one extern "C" entry per launcher family of the blocked update (T1 - T4, R1 - R5) and of the
+// in-place changes and batched ratio queries of the tableau engine (T5 - T8, at the end of the file), so that a test can
 // run a single relp::launch_* of the shipped library on operands it constructs (tests/kernel_harness.py binds it).
 //
 // Rules of every entry:
@@ -10,7 +11,7 @@
 //   * fill != 0: pitch padding and stale regions (rows m..ld-1, rows of R0 / columns of W / entries of wr at and beyond p,
 //     R0's scratch row, R0c and cols) are filled with the quiet NaN kSentinel before the upload; the WHOLE of every buffer
 //     comes back so that the test sees what was written;
-//   * refusals (negative return codes) happen before any HIP call;
+//   * refusals (negative return codes) happen before any HIP call; every list index an entry accepts is in range;
 //   * the first HIP error is sticky: every later entry returns kHipErrorBase + that error without touching the GPU.
 //
 // Layouts of the logical arrays (C order): T0[c][i] (n_owned x m), W[j][i] (p x m), R0[j][c] (p x n_owned),
@@ -35,6 +36,8 @@ constexpr int kRefusedShape = -1;    // m < 1, n_owned < 1, p < 0, p > kmax, kma
 constexpr int kRefusedIndex = -2;    // a row or column index out of range
 constexpr int kRefusedBatch = -3;    // a batch tab_load_batch would remap
 constexpr int kRefusedLength = -4;   // a wrong array length
+constexpr int kRefusedSplits = -5;   // splits < 1 or beyond min(count, the launcher's maximum)
+constexpr int kRefusedOrder = -6;    // a list that is not strictly ascending, a repeated basis entry, a direct term on a basic column
 constexpr int kHipErrorBase = 1000;  // + hipError_t of the first failed HIP call (sticky)
 
 constexpr uint64_t kSentinelBits = 0x7ff80000c0ffee01ull;
@@ -494,6 +497,270 @@ int rkh_explicit_update(int64_t m, int64_t r, int fill, const double* alpha, int
     HIP_OK(hipGetLastError());
     HIP_OK(hipDeviceSynchronize());
     TRY(rho.back(rho_out, ld_b)); TRY(binv.back(Binv_out, Binv_out_len)); TRY(al.back(alpha_out, ld_b));
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- T5 - T8: the in-place changes and the batched ratio queries (relp_kernels_tableau.hip: k_tab_rhs_*, k_tab_cost_*,
+// k_tab_row_ratios*, k_tab_rhs_ranging*).  These take a view with a column offset: tv.n = n_store - col_off tableau columns,
+// in_basis indexed by tableau column.  d_in holds the owned columns' d; the image has n_store entries, sentinel below c_lo.
+namespace {
+
+constexpr int64_t kScratchTail = 64;   // sentinel words behind the partial minima of T7 / T8
+
+TableauView view_at(const TabOperands& op, double* d, int64_t col_off) {
+    TableauView tv = op.view(d);
+    tv.col_off = (int32_t)col_off; tv.n = (int32_t)(op.c_lo + op.n - col_off);
+    return tv;
+}
+
+PivotRecord pending_record(int64_t p) {
+    PivotRecord R = blank_record();
+    R.n_eta = (int32_t)p; R.n_eta_old = (int32_t)p; R.p_now = (int32_t)p;
+    return R;
+}
+
+bool list_refused(const int32_t* list, int64_t count, int64_t lo, int64_t hi, bool ascending) {
+    for (int64_t k = 0; k < count; ++k) {
+        if (list[k] < lo || list[k] >= hi) return true;
+        if (ascending && k > 0 && list[k] <= list[k - 1]) return true;
+    }
+    return false;
+}
+
+bool tol_refused(const double* tol) {   // {pivot, zero, tie}: finite and not negative
+    for (int t = 0; t < 3; ++t) if (!(tol[t] >= 0.0) || tol[t] > 1e300) return true;
+    return false;
+}
+
+Tolerances tolerances(const double* tol) {
+    Tolerances t;
+    memset(&t, 0, sizeof t);
+    t.pivot = tol[0]; t.zero = tol[1]; t.tie = tol[2];
+    return t;
+}
+
+template <class T>
+void fill_from(Dev<T>& dev, int64_t n, T fill, const T* src, int64_t count, int64_t at = 0) {
+    dev.init(n, fill);
+    for (int64_t k = 0; k < count; ++k) dev.h[(size_t)(at + k)] = src[k];
+}
+
+}  // namespace
+
+extern "C" {
+
+// tab_rhs_splits (which = 0, size = m) / tab_cost_splits (which = 1, size = stored columns): host functions, no HIP call
+int rkh_tab_splits(int which, int64_t size, int64_t count, int64_t forced, int32_t* out, int64_t out_len) {
+    REFUSE_IF(which < 0 || which > 1 || size < 1 || size > (1ll << 30), kRefusedShape);
+    REFUSE_IF(count < -(1ll << 30) || count > (1ll << 30) || forced < -(1ll << 30) || forced > (1ll << 30), kRefusedShape);
+    REFUSE_LEN(out_len, 1);
+    out[0] = which ? tab_cost_splits((int32_t)size, (int32_t)count, (int32_t)forced) : tab_rhs_splits((int32_t)size, (int32_t)count, (int32_t)forced);
+    return 0;
+}
+
+// T5: launch_tab_rhs_change.  cols: storage columns in [c_lo, c_lo + n_owned), repeats allowed.  Out: b (ld_b), v (kmax),
+// partial (splits x ld_b, the engine's ld_partial), the operands and the list.
+int rkh_tab_rhs_change(int64_t m, int64_t n_owned, int64_t p, int64_t kmax, int64_t c_lo, int batch, int64_t count, int64_t splits,
+                       int fill, const double* T0, int64_t T0_len, const double* W, int64_t W_len, const double* R0, int64_t R0_len,
+                       const double* b, int64_t b_len, const int32_t* cols, int64_t cols_len, const double* delta, int64_t delta_len,
+                       double* b_out, int64_t b_out_len, double* v_out, int64_t v_out_len, double* partial_out, int64_t partial_out_len,
+                       double* T0_out, int64_t T0_out_len, double* W_out, int64_t W_out_len, double* R0_out, int64_t R0_out_len,
+                       int32_t* cols_out, int64_t cols_out_len, double* delta_out, int64_t delta_out_len) {
+    if (g_sticky) return g_sticky;
+    REFUSE_IF(shape_refused(m, n_owned, p, kmax), kRefusedShape);
+    REFUSE_IF(c_lo < 0 || c_lo > (1 << 20), kRefusedIndex);
+    REFUSE_IF(count < 1 || count > (1 << 20), kRefusedShape);
+    REFUSE_IF(splits < 1 || splits > std::min<int64_t>(count, kTabRhsMaxSplits), kRefusedSplits);
+    REFUSE_IF(batch_refused(batch), kRefusedBatch);
+    const int64_t ld_b = round_up(m, 16), ld_t = round_up(m, 2), ld_r = round_up(n_owned, 2);
+    REFUSE_LEN(T0_len, n_owned * m); REFUSE_LEN(W_len, p * m); REFUSE_LEN(R0_len, p * n_owned); REFUSE_LEN(b_len, m);
+    REFUSE_LEN(cols_len, count); REFUSE_LEN(delta_len, count);
+    REFUSE_LEN(b_out_len, ld_b); REFUSE_LEN(v_out_len, kmax); REFUSE_LEN(partial_out_len, splits * ld_b);
+    REFUSE_LEN(T0_out_len, n_owned * ld_t); REFUSE_LEN(W_out_len, kmax * ld_b); REFUSE_LEN(R0_out_len, (kmax + 1) * ld_r);
+    REFUSE_LEN(cols_out_len, count); REFUSE_LEN(delta_out_len, count);
+    REFUSE_IF(list_refused(cols, count, c_lo, c_lo + n_owned, false), kRefusedIndex);
+    TabOperands op;
+    TRY(op.build(m, n_owned, p, kmax, c_lo, fill, T0, W, R0, pending_record(p)));
+    Dev<double> bb, v, partial, dl;
+    Dev<int32_t> cl;
+    fill_from(bb, ld_b, fill ? sentinel() : 0.0, b, m);
+    v.init(kmax, sentinel()); partial.init(splits * ld_b, sentinel());
+    fill_from(cl, count, 0, cols, count); fill_from(dl, count, 0.0, delta, count);
+    TRY(bb.upload()); TRY(v.upload()); TRY(partial.upload()); TRY(cl.upload()); TRY(dl.upload());
+    launch_tab_rhs_change(view_at(op, nullptr, 0), op.deferred(batch), RhsChange{cl.d, dl.d, (int32_t)count}, (int32_t)p, (int32_t)splits,
+                          v.d, bb.d, partial.d, ld_b, 0);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipDeviceSynchronize());
+    TRY(bb.back(b_out, ld_b)); TRY(v.back(v_out, kmax)); TRY(partial.back(partial_out, splits * ld_b));
+    TRY(op.T0.back(T0_out, T0_out_len)); TRY(op.W.back(W_out, W_out_len)); TRY(op.R0.back(R0_out, R0_out_len));
+    TRY(cl.back(cols_out, count)); TRY(dl.back(delta_out, count));
+    return 0;
+}
+
+// T6: launch_tab_cost_change.  rows: strictly ascending rows of [0, m); ncols: strictly ascending storage columns of
+// [c_lo, c_lo + n_owned), none flagged 1; in_basis: n_store - col_off flags (0 / 1 / 2) by tableau column; d: the owned columns.
+// count == 0 needs splits == 1 (the launcher forces it).  Out: d (n_store), u (kmax), partial (splits x ld_r, the engine's
+// ld_partial; the pointer handed over is shifted by c_lo as T0 and R0 are), the flags, the operands and the lists.
+int rkh_tab_cost_change(int64_t m, int64_t n_owned, int64_t p, int64_t kmax, int64_t c_lo, int64_t col_off, int batch, int64_t count,
+                        int64_t ncount, int64_t splits, int fill,
+                        const double* T0, int64_t T0_len, const double* W, int64_t W_len, const double* R0, int64_t R0_len,
+                        const double* d, int64_t d_len, const uint8_t* in_basis, int64_t in_basis_len,
+                        const int32_t* rows, int64_t rows_len, const double* delta, int64_t delta_len,
+                        const int32_t* ncols, int64_t ncols_len, const double* ndelta, int64_t ndelta_len,
+                        double* d_out, int64_t d_out_len, double* u_out, int64_t u_out_len, double* partial_out, int64_t partial_out_len,
+                        uint8_t* in_basis_out, int64_t in_basis_out_len,
+                        double* T0_out, int64_t T0_out_len, double* W_out, int64_t W_out_len, double* R0_out, int64_t R0_out_len,
+                        int32_t* rows_out, int64_t rows_out_len, double* delta_out, int64_t delta_out_len,
+                        int32_t* ncols_out, int64_t ncols_out_len, double* ndelta_out, int64_t ndelta_out_len) {
+    if (g_sticky) return g_sticky;
+    REFUSE_IF(shape_refused(m, n_owned, p, kmax), kRefusedShape);
+    REFUSE_IF(c_lo < 0 || c_lo > (1 << 20), kRefusedIndex);
+    const int64_t n_all = c_lo + n_owned, n_tab = n_all - col_off;
+    REFUSE_IF(col_off < 0 || col_off >= n_all, kRefusedIndex);
+    REFUSE_IF(count < 0 || ncount < 0 || count + ncount < 1 || count > (1 << 20) || ncount > (1 << 20), kRefusedShape);
+    REFUSE_IF(splits < 1 || splits > std::max<int64_t>(1, std::min<int64_t>(count, kTabCostMaxSplits)), kRefusedSplits);
+    REFUSE_IF(batch_refused(batch), kRefusedBatch);
+    const int64_t ld_b = round_up(m, 16), ld_t = round_up(m, 2), ld_r = round_up(n_owned, 2);
+    REFUSE_LEN(T0_len, n_owned * m); REFUSE_LEN(W_len, p * m); REFUSE_LEN(R0_len, p * n_owned); REFUSE_LEN(d_len, n_owned);
+    REFUSE_LEN(in_basis_len, n_tab); REFUSE_LEN(rows_len, count); REFUSE_LEN(delta_len, count); REFUSE_LEN(ncols_len, ncount);
+    REFUSE_LEN(ndelta_len, ncount);
+    REFUSE_LEN(d_out_len, n_all); REFUSE_LEN(u_out_len, kmax); REFUSE_LEN(partial_out_len, splits * ld_r); REFUSE_LEN(in_basis_out_len, n_tab);
+    REFUSE_LEN(T0_out_len, n_owned * ld_t); REFUSE_LEN(W_out_len, kmax * ld_b); REFUSE_LEN(R0_out_len, (kmax + 1) * ld_r);
+    REFUSE_LEN(rows_out_len, count); REFUSE_LEN(delta_out_len, count); REFUSE_LEN(ncols_out_len, ncount); REFUSE_LEN(ndelta_out_len, ncount);
+    REFUSE_IF(list_refused(rows, count, 0, m, false) || list_refused(ncols, ncount, c_lo, n_all, false), kRefusedIndex);
+    REFUSE_IF(list_refused(rows, count, 0, m, true) || list_refused(ncols, ncount, c_lo, n_all, true), kRefusedOrder);
+    for (int64_t j = 0; j < n_tab; ++j) REFUSE_IF(in_basis[j] > 2, kRefusedIndex);
+    for (int64_t k = 0; k < ncount; ++k) REFUSE_IF(ncols[k] >= col_off && in_basis[ncols[k] - col_off] == 1, kRefusedOrder);
+    TabOperands op;
+    TRY(op.build(m, n_owned, p, kmax, c_lo, fill, T0, W, R0, pending_record(p)));
+    Dev<double> dd, u, partial, dl, ndl;
+    Dev<int32_t> rw, ncl;
+    Dev<uint8_t> inb;
+    fill_from(dd, n_all, sentinel(), d, n_owned, c_lo);
+    u.init(kmax, sentinel()); partial.init(splits * ld_r, sentinel());
+    fill_from(inb, n_tab, (uint8_t)0, in_basis, n_tab);
+    fill_from(rw, count, 0, rows, count); fill_from(dl, count, 0.0, delta, count);
+    fill_from(ncl, ncount, 0, ncols, ncount); fill_from(ndl, ncount, 0.0, ndelta, ncount);
+    TRY(dd.upload()); TRY(u.upload()); TRY(partial.upload()); TRY(inb.upload()); TRY(rw.upload()); TRY(dl.upload()); TRY(ncl.upload());
+    TRY(ndl.upload());
+    launch_tab_cost_change(view_at(op, dd.d, col_off), op.deferred(batch),
+                           CostChange{rw.d, dl.d, (int32_t)count, ncl.d, ndl.d, (int32_t)ncount}, inb.d, (int32_t)p, (int32_t)splits, u.d,
+                           partial.d - c_lo, ld_r, 0);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipDeviceSynchronize());
+    TRY(dd.back(d_out, n_all)); TRY(u.back(u_out, kmax)); TRY(partial.back(partial_out, splits * ld_r)); TRY(inb.back(in_basis_out, n_tab));
+    TRY(op.T0.back(T0_out, T0_out_len)); TRY(op.W.back(W_out, W_out_len)); TRY(op.R0.back(R0_out, R0_out_len));
+    TRY(rw.back(rows_out, count)); TRY(dl.back(delta_out, count)); TRY(ncl.back(ncols_out, ncount)); TRY(ndl.back(ndelta_out, ncount));
+    return 0;
+}
+
+// T7: launch_tab_row_ratios.  rows: any order, repeats allowed; tol: {pivot, zero, tie}.  Out: ratio / column (2 x count,
+// pre-filled with the sentinels), the scratch part_k / part_j (2 x count x scan blocks, then kScratchTail sentinel words), d
+// (n_store), the flags, the operands and the list.
+int rkh_tab_row_ratios(int64_t m, int64_t n_owned, int64_t p, int64_t kmax, int64_t c_lo, int64_t col_off, int batch, int64_t count,
+                       int fill, const double* tol, int64_t tol_len,
+                       const double* T0, int64_t T0_len, const double* W, int64_t W_len, const double* R0, int64_t R0_len,
+                       const double* d, int64_t d_len, const uint8_t* in_basis, int64_t in_basis_len, const int32_t* rows, int64_t rows_len,
+                       double* ratio_out, int64_t ratio_out_len, int32_t* column_out, int64_t column_out_len,
+                       double* part_k_out, int64_t part_k_out_len, int32_t* part_j_out, int64_t part_j_out_len,
+                       double* d_out, int64_t d_out_len, uint8_t* in_basis_out, int64_t in_basis_out_len,
+                       double* T0_out, int64_t T0_out_len, double* W_out, int64_t W_out_len, double* R0_out, int64_t R0_out_len,
+                       int32_t* rows_out, int64_t rows_out_len) {
+    if (g_sticky) return g_sticky;
+    REFUSE_IF(shape_refused(m, n_owned, p, kmax), kRefusedShape);
+    REFUSE_IF(c_lo < 0 || c_lo > (1 << 20), kRefusedIndex);
+    const int64_t n_all = c_lo + n_owned, n_tab = n_all - col_off;
+    REFUSE_IF(col_off < 0 || col_off >= n_all, kRefusedIndex);
+    REFUSE_IF(count < 1 || count > (1 << 16), kRefusedShape);
+    REFUSE_IF(batch_refused(batch), kRefusedBatch);
+    REFUSE_LEN(tol_len, 3);
+    REFUSE_IF(tol_refused(tol), kRefusedShape);
+    const int64_t ld_b = round_up(m, 16), ld_t = round_up(m, 2), ld_r = round_up(n_owned, 2);
+    const int64_t scratch = 2 * count * tab_scan_blocks((int32_t)n_owned) + kScratchTail;
+    REFUSE_LEN(T0_len, n_owned * m); REFUSE_LEN(W_len, p * m); REFUSE_LEN(R0_len, p * n_owned); REFUSE_LEN(d_len, n_owned);
+    REFUSE_LEN(in_basis_len, n_tab); REFUSE_LEN(rows_len, count);
+    REFUSE_LEN(ratio_out_len, 2 * count); REFUSE_LEN(column_out_len, 2 * count); REFUSE_LEN(part_k_out_len, scratch);
+    REFUSE_LEN(part_j_out_len, scratch); REFUSE_LEN(d_out_len, n_all); REFUSE_LEN(in_basis_out_len, n_tab);
+    REFUSE_LEN(T0_out_len, n_owned * ld_t); REFUSE_LEN(W_out_len, kmax * ld_b); REFUSE_LEN(R0_out_len, (kmax + 1) * ld_r);
+    REFUSE_LEN(rows_out_len, count);
+    REFUSE_IF(list_refused(rows, count, 0, m, false), kRefusedIndex);
+    for (int64_t j = 0; j < n_tab; ++j) REFUSE_IF(in_basis[j] > 2, kRefusedIndex);
+    TabOperands op;
+    TRY(op.build(m, n_owned, p, kmax, c_lo, fill, T0, W, R0, pending_record(p)));
+    Dev<double> dd, pk, ratio;
+    Dev<int32_t> pj, column, rw;
+    Dev<uint8_t> inb;
+    fill_from(dd, n_all, sentinel(), d, n_owned, c_lo);
+    fill_from(inb, n_tab, (uint8_t)0, in_basis, n_tab);
+    fill_from(rw, count, 0, rows, count);
+    pk.init(scratch, sentinel()); pj.init(scratch, kSentinelInt); ratio.init(2 * count, sentinel()); column.init(2 * count, kSentinelInt);
+    TRY(dd.upload()); TRY(inb.upload()); TRY(rw.upload()); TRY(pk.upload()); TRY(pj.upload()); TRY(ratio.upload()); TRY(column.upload());
+    SelectPartials sp;
+    memset(&sp, 0, sizeof sp);
+    sp.in_basis = inb.d; sp.n = (int32_t)n_tab; sp.cols_per_slot = 8;
+    launch_tab_row_ratios(view_at(op, dd.d, col_off), op.deferred(batch), sp, tolerances(tol), rw.d, (int32_t)count, (int32_t)p, pk.d, pj.d,
+                          ratio.d, column.d, 0);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipDeviceSynchronize());
+    TRY(ratio.back(ratio_out, 2 * count)); TRY(column.back(column_out, 2 * count)); TRY(pk.back(part_k_out, scratch));
+    TRY(pj.back(part_j_out, scratch)); TRY(dd.back(d_out, n_all)); TRY(inb.back(in_basis_out, n_tab));
+    TRY(op.T0.back(T0_out, T0_out_len)); TRY(op.W.back(W_out, W_out_len)); TRY(op.R0.back(R0_out, R0_out_len));
+    TRY(rw.back(rows_out, count));
+    return 0;
+}
+
+// T8: launch_tab_rhs_ranging.  cols: storage columns of [c_lo, c_lo + n_owned), any order, repeats allowed; basis: m distinct
+// leaving columns >= 0 (wrapped artificials from kWrappedArtificialBase).  Out: ratio / row (2 x count), the scratch part
+// (2 x count x cdiv(m, 256), then kScratchTail sentinel words), b (ld_b), the basis, the operands and the list.
+int rkh_tab_rhs_ranging(int64_t m, int64_t n_owned, int64_t p, int64_t kmax, int64_t c_lo, int batch, int64_t count, int fill,
+                        const double* tol, int64_t tol_len,
+                        const double* T0, int64_t T0_len, const double* W, int64_t W_len, const double* R0, int64_t R0_len,
+                        const double* b, int64_t b_len, const int32_t* basis, int64_t basis_len, const int32_t* cols, int64_t cols_len,
+                        double* ratio_out, int64_t ratio_out_len, int32_t* row_out, int64_t row_out_len,
+                        double* part_out, int64_t part_out_len, double* b_out, int64_t b_out_len, int32_t* basis_out, int64_t basis_out_len,
+                        double* T0_out, int64_t T0_out_len, double* W_out, int64_t W_out_len, double* R0_out, int64_t R0_out_len,
+                        int32_t* cols_out, int64_t cols_out_len) {
+    if (g_sticky) return g_sticky;
+    REFUSE_IF(shape_refused(m, n_owned, p, kmax), kRefusedShape);
+    REFUSE_IF(c_lo < 0 || c_lo > (1 << 20), kRefusedIndex);
+    REFUSE_IF(count < 1 || count > (1 << 16), kRefusedShape);
+    REFUSE_IF(batch_refused(batch), kRefusedBatch);
+    REFUSE_LEN(tol_len, 3);
+    REFUSE_IF(tol_refused(tol), kRefusedShape);
+    const int64_t ld_b = round_up(m, 16), ld_t = round_up(m, 2), ld_r = round_up(n_owned, 2);
+    const int64_t scratch = 2 * count * ((m + 255) / 256) + kScratchTail;
+    REFUSE_LEN(T0_len, n_owned * m); REFUSE_LEN(W_len, p * m); REFUSE_LEN(R0_len, p * n_owned); REFUSE_LEN(b_len, m);
+    REFUSE_LEN(basis_len, m); REFUSE_LEN(cols_len, count);
+    REFUSE_LEN(ratio_out_len, 2 * count); REFUSE_LEN(row_out_len, 2 * count); REFUSE_LEN(part_out_len, scratch);
+    REFUSE_LEN(b_out_len, ld_b); REFUSE_LEN(basis_out_len, m);
+    REFUSE_LEN(T0_out_len, n_owned * ld_t); REFUSE_LEN(W_out_len, kmax * ld_b); REFUSE_LEN(R0_out_len, (kmax + 1) * ld_r);
+    REFUSE_LEN(cols_out_len, count);
+    REFUSE_IF(list_refused(cols, count, c_lo, c_lo + n_owned, false), kRefusedIndex);
+    {
+        std::vector<int32_t> sorted(basis, basis + m);
+        std::sort(sorted.begin(), sorted.end());
+        REFUSE_IF(sorted[0] < 0, kRefusedIndex);
+        for (int64_t i = 1; i < m; ++i) REFUSE_IF(sorted[(size_t)i] == sorted[(size_t)i - 1], kRefusedOrder);
+    }
+    TabOperands op;
+    TRY(op.build(m, n_owned, p, kmax, c_lo, fill, T0, W, R0, pending_record(p)));
+    Dev<double> bb, part, ratio;
+    Dev<int32_t> bas, row, cl;
+    fill_from(bb, ld_b, fill ? sentinel() : 0.0, b, m);
+    fill_from(bas, m, 0, basis, m);
+    fill_from(cl, count, 0, cols, count);
+    part.init(scratch, sentinel()); ratio.init(2 * count, sentinel()); row.init(2 * count, kSentinelInt);
+    TRY(bb.upload()); TRY(bas.upload()); TRY(cl.upload()); TRY(part.upload()); TRY(ratio.upload()); TRY(row.upload());
+    launch_tab_rhs_ranging(view_at(op, nullptr, 0), op.deferred(batch), bb.d, bas.d, tolerances(tol), cl.d, (int32_t)count, (int32_t)p, part.d,
+                           ratio.d, row.d, 0);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipDeviceSynchronize());
+    TRY(ratio.back(ratio_out, 2 * count)); TRY(row.back(row_out, 2 * count)); TRY(part.back(part_out, scratch));
+    TRY(bb.back(b_out, ld_b)); TRY(bas.back(basis_out, m));
+    TRY(op.T0.back(T0_out, T0_out_len)); TRY(op.W.back(W_out, W_out_len)); TRY(op.R0.back(R0_out, R0_out_len));
+    TRY(cl.back(cols_out, count));
     return 0;
 }
 
