@@ -379,6 +379,19 @@ class Tableau {
     std::vector<double> cost() { std::vector<double> v(nr_normal_); ck(relp_get_cost(h_, v.data())); return v; }
     // relp_cost_stats: {in-place changes, tableau rows they read, pending rows at the last change, shares of its last launch}
     std::array<int64_t, 4> cost_stats() { std::array<int64_t, 4> out{}; ck(relp_cost_stats(h_, out.data())); return out; }
+    // cut rows added in place on the current basis (relp_add_cuts): cut k is sum_e values[e] x[col_idx[e]] <= rhs[k] over
+    // e in [row_ptr[k], row_ptr[k + 1]), structural columns only; it becomes row nr_rows() + k with its slack, column
+    // nr_columns() + k, basic in it.  run_dual() re-solves from there.
+    void add_cuts(const std::vector<int64_t>& row_ptr, const std::vector<int32_t>& col_idx, const std::vector<double>& values,
+                  const std::vector<double>& rhs) {
+        if (row_ptr.size() != rhs.size() + 1) throw Error(RELP_E_ARG, "row_ptr has one entry more than there are cuts");
+        if (col_idx.size() != values.size() || (int64_t)values.size() < row_ptr.back()) throw Error(RELP_E_ARG, "one value per column index, row_ptr within them");
+        ck(relp_add_cuts(h_, (int32_t)rhs.size(), row_ptr.data(), col_idx.data(), values.data(), rhs.data()));
+    }
+    // room for `rows` cut rows in all, without adding any (relp_reserve_cuts)
+    void reserve_cuts(int32_t rows) { ck(relp_reserve_cuts(h_, rows)); }
+    // relp_cut_stats: {cuts in the tableau, cut rows there is room for, tableau rows the last add read, pending rows at that call}
+    std::array<int64_t, 4> cut_stats() { std::array<int64_t, 4> out{}; ck(relp_cut_stats(h_, out.data())); return out; }
     // relp_row_ratios: per listed row the minimum d_j / |T[r,j]| over the non-basic columns with T[r,j] < 0 (down) and > 0 (up), and
     // the column that attains it (+inf, -1 without one): branching penalties, and the cost range [c - down, c + up] of the row's
     // basic variable.  Read-only.

@@ -309,6 +309,49 @@ relp_status_t relp_get_cost(relp_engine_t *h, double *out_n);
  * at the last change, shares (k-splits) of its last launch }.  Refused calls and calls with count == 0 are not counted; a call
  * whose deltas are all zero counts as a change that read 0 rows. */
 relp_status_t relp_cost_stats(const relp_engine_t *h, int64_t *out4);
+/* Cut rows added to the tableau on the current basis WITHOUT a flush or a re-tabulation (no counterpart in the reference): what a
+ * cutting-plane or branch-and-cut driver does between re-solves.  `count` cuts
+ *     sum_e values[e] * x[col_idx[e]] <= rhs[k]        (e in [row_ptr[k], row_ptr[k + 1]))
+ * in CSR over the structural provider columns, 0 <= col_idx[e] < nr_normal.
+ * Where a cut goes: cut k of the call becomes engine row relp_nr_rows() + k, behind every existing row (bound and range-bound rows
+ * included); its slack becomes provider column relp_nr_columns() + k, behind every existing column.  No existing row or column
+ * index moves.
+ * The new slack is basic in its row, with cost 0 and sign +1, and behaves like a <= slack everywhere: relp_get_basis_indices,
+ * relp_current_bfs, relp_get_trace and relp_from_basis name it by that index; relp_change_right_hand_side, relp_rhs_ranging and
+ * relp_row_ratios take the cut row by its row index; relp_get_right_hand_side, relp_set_right_hand_side, relp_get_b and
+ * relp_get_minus_pi have the new length.
+ * Other cut forms: rhs may have any sign, a >= cut is passed negated, an equality is two cuts.  A coefficient on a virtual column
+ * is not accepted; the caller substitutes it.
+ * What the call changes: nothing is flushed or re-tabulated.  With B(r) the basic column of row r, the row of cut k in the current
+ * basis is
+ *     T[new,c] = g_c - sum_r g_B(r) * (T0[r,c] + sum_{j<p} W[j][r] * R0[j][c])      b_new = rhs[k] - sum_r g_B(r) * b_r
+ * over the rows r whose basic column is structural with a nonzero coefficient (p = pending rows of the open update block), written
+ * into T0.  The bits of d over the old columns, the bits of b over the old rows, -obj, the basis entries of the old rows, the
+ * flags of the old columns, W, R0 and T0 over the old rows and old columns, the trace, relp_reinversions and relp_tab_flush_stats
+ * stay exactly as they were.  A violated cut shows as b_new < 0: the state relp_run_dual starts from.
+ * Pinned values: new-row entries of stored columns flagged basic are exactly 0.0; the new slack columns are exactly unit columns
+ * and their d is exactly 0.0.  A barred column and the kept artificial block are computed like every other column.
+ * After the call the PRICE partials are invalid and the record is re-armed; relp_run_dual or relp_run may follow.  The call
+ * synchronises.  Every later rebuild (re-inversion interval, auto_reinversion, relp_from_basis, relp_set_right_hand_side)
+ * includes the cuts.
+ * Deterministic: the rows r are walked in ascending order whatever the order of the entries inside the caller's CSR, no atomics;
+ * the same call on the same state gives the same bits.
+ * RELP_E_ARG with nothing changed: count < 0, a missing array, a row_ptr that does not ascend from 0, a column outside
+ * [0, nr_normal), a column named twice in one cut, a coefficient or rhs that is not finite.  count == 0 is a no-op.
+ * RELP_ENGINE_TABLEAU, unsharded, phase 2: RELP_E_UNSUPPORTED on another or a sharded engine, RELP_E_STATE in phase 1 (all three
+ * calls).  RELP_E_ALLOC when growing fails: every new buffer is allocated before an old one is released, so the handle is then as
+ * it was.
+ * Capacity: relp_reserve_cuts(rows) makes room for `rows` cut rows in all (a no-op when there is room already; it never shrinks,
+ * adds nothing and changes no getter).  relp_add_cuts grows by itself when room lacks, to max(cuts then in the tableau, 2 x the
+ * room so far, 16).  Growing re-allocates and copies the tableau: old and new T0 live side by side for a moment, so a driver
+ * that knows its cut budget reserves it once, while memory is plentiful.
+ * Dropping a cut is not built: relax it instead, relp_change_right_hand_side(cut row, a value it cannot bind at). */
+relp_status_t relp_add_cuts(relp_engine_t *h, int32_t count, const int64_t *row_ptr, const int32_t *col_idx, const double *values,
+                            const double *rhs);
+relp_status_t relp_reserve_cuts(relp_engine_t *h, int32_t rows);
+/* out4 = { cuts in the tableau, cut rows there is room for, tableau rows the last relp_add_cuts read (the rows r above, over all
+ * cuts of the call), pending rows p of the update block at that call }. */
+relp_status_t relp_cut_stats(const relp_engine_t *h, int64_t *out4);
 /* Batched ratio tests over the tableau as it stands (no counterpart in the reference): what a branch-and-bound driver asks at a
  * node ("which fractional row is the dearest to branch on?") and a solve asks at its end (the ranging report).  Both are read-only:
  * nothing is flushed or re-tabulated, and T0, R0, W, d, b, the basis, the flags, the PRICE partials, the record, the trace and

@@ -96,6 +96,12 @@ relp_status_t relp_change_cost(relp_engine_t* h, const int32_t* columns, const d
 relp_status_t relp_set_cost(relp_engine_t* h, const double* cost_n) { return (h && cost_n) ? H(h).set_cost(cost_n) : RELP_E_ARG; }
 relp_status_t relp_get_cost(relp_engine_t* h, double* out_n) { return (h && out_n) ? H(h).get_cost(out_n) : RELP_E_ARG; }
 relp_status_t relp_cost_stats(const relp_engine_t* h, int64_t* out4) { return (h && out4) ? H(h).cost_stats(out4) : RELP_E_ARG; }
+relp_status_t relp_add_cuts(relp_engine_t* h, int32_t count, const int64_t* row_ptr, const int32_t* col_idx, const double* values,
+                            const double* rhs) {
+    return h ? H(h).add_cuts(count, row_ptr, col_idx, values, rhs) : RELP_E_ARG;
+}
+relp_status_t relp_reserve_cuts(relp_engine_t* h, int32_t rows) { return h ? H(h).reserve_cuts(rows) : RELP_E_ARG; }
+relp_status_t relp_cut_stats(const relp_engine_t* h, int64_t* out4) { return (h && out4) ? H(h).cut_stats(out4) : RELP_E_ARG; }
 relp_status_t relp_row_ratios(relp_engine_t* h, const int32_t* rows, int32_t count, double* down_ratio, int32_t* down_column,
                               double* up_ratio, int32_t* up_column) {
     return h ? H(h).row_ratios(rows, count, down_ratio, down_column, up_ratio, up_column) : RELP_E_ARG;

@@ -85,13 +85,13 @@ class DeviceBuf {
         return fits(0, n) ? fill_bytes_at(p_, value, (size_t)n * sizeof(T), on) : hipErrorInvalidValue;
     }
     // 2-D: `columns` runs of `width` elements, `ld` apart here and `other_ld` apart at `other`: read into host memory there
-    // (kToHost), or written from host (kFromHost) or device memory (kFromDevice) there
-    hipError_t copy_2d(Dir2d dir, const T* other, int64_t other_ld, int64_t width, int64_t columns, int64_t ld, On on) const {
-        if (width < 0 || columns < 0 || width > ld || (width && columns && !fits((columns - 1) * ld, width))) return hipErrorInvalidValue;
+    // (kToHost), or written from host (kFromHost) or device memory (kFromDevice) there; the first run starts at element `at` here
+    hipError_t copy_2d(Dir2d dir, const T* other, int64_t other_ld, int64_t width, int64_t columns, int64_t ld, On on, int64_t at = 0) const {
+        if (width < 0 || columns < 0 || at < 0 || width > ld || (width && columns && !fits(at + (columns - 1) * ld, width))) return hipErrorInvalidValue;
         if (!width || !columns) return hipSuccess;
         const size_t here = ld * sizeof(T), there = other_ld * sizeof(T), w = width * sizeof(T);
-        return on.done(dir == kToHost ? hipMemcpy2DAsync(const_cast<T*>(other), there, p_, here, w, columns, (hipMemcpyKind)dir, on.s)
-                                      : hipMemcpy2DAsync(p_, here, other, there, w, columns, (hipMemcpyKind)dir, on.s));
+        return on.done(dir == kToHost ? hipMemcpy2DAsync(const_cast<T*>(other), there, p_ + at, here, w, columns, (hipMemcpyKind)dir, on.s)
+                                      : hipMemcpy2DAsync(p_ + at, here, other, there, w, columns, (hipMemcpyKind)dir, on.s));
     }
 
   private:

@@ -32,6 +32,8 @@ ColumnTable Engine::table() const {
     ct.vrow1 = d_vrow1_;
     ct.vsign = d_vsign_;
     ct.cost = d_cost_;
+    ct.cut_row0 = lay_.cut_row0;
+    ct.nr_cuts = lay_.nr_cuts;
     return ct;
 }
 
@@ -1245,6 +1247,192 @@ relp_status_t Engine::cost_stats(int64_t* out4) const {
     if (!tableau_ || cfg_.shard_count > 1) return RELP_E_UNSUPPORTED;
     if (phase_ != 2) return RELP_E_STATE;
     out4[0] = cost_changes_; out4[1] = cost_rows_; out4[2] = cost_last_p_; out4[3] = cost_last_splits_;
+    return RELP_OK;
+}
+
+// Room for `room` cut rows and their slack columns in every buffer of the tableau path that create() sizes from the rows or the
+// columns: the only function that grows the tableau engine.  The new pitches are the roundings of create() applied to the room.
+// Every new buffer is allocated (zeroed: the kernels' 16-byte loads read the tails) before an old one is released, so a refused
+// allocation leaves the handle as it was; then the contents move, 2-D where the pitch changes, and once every copy has succeeded
+// the buffers are exchanged: old and new T0 live side by side for that moment.  A pending update block survives unchanged (same p, same bits); lay_, n_store_,
+// n_alloc_ and the host mirrors are not touched (they follow at the add).
+relp_status_t Engine::grow_for_cuts(int32_t room) {
+    if (room <= cut_room_) return RELP_OK;
+    tab_settle();
+    HIP_TRY(hipStreamSynchronize(stream_));
+    const int32_t m_now = lay_.m, n_now = n_store_;
+    const int64_t m_cap = (int64_t)m_now - lay_.nr_cuts + room, n_cap = (int64_t)n_now - lay_.nr_cuts + room;
+    const int64_t v_cap = (int64_t)lay_.nr_virtual - lay_.nr_cuts + room;
+    if (m_cap > INT32_MAX - 16 || n_cap > INT32_MAX - 16) return fail(RELP_E_ARG, "relp_reserve_cuts: more rows or columns than an index holds");
+    // The pitches and sizes never shrink: after row removal at the phase switch (remove_rows lowers lay_.m and lay_.mc and leaves
+    // every buffer as create() sized it) the rounding of the room can be below what is there.
+    const int64_t ld_b = std::max(ld_b_, round_up(m_cap, 16)), ld_t = std::max(ld_t_, round_up(m_cap, 2));
+    const int64_t ld_r = std::max(ld_r_, round_up(std::max<int64_t>(n_cap, 1), 2));
+    const int64_t ld_a = std::max(ld_a_, round_up(std::max<int64_t>((int64_t)lay_.mc + room, 1), 2));
+
+    // per buffer: copy old -> new, and exchange them; the closures own the new buffers.  The exchanges run only after every copy
+    // has succeeded: a refused copy leaves the handle as it was, like a refused allocation.
+    std::vector<std::function<hipError_t()>> copies;
+    std::vector<std::function<void()>> exchanges;
+    bool refused = false;
+    // `columns` runs of `width` elements, old_ld apart in buf and new_ld apart in its replacement of at least `count` elements
+    auto regrow = [&](auto& buf, int64_t count, int64_t width, int64_t columns, int64_t old_ld, int64_t new_ld, int fill) {
+        using Buf = std::decay_t<decltype(buf)>;
+        if (refused || !buf) return;                   // (a buffer this engine's configuration does not have)
+        count = std::max(count, buf.count());
+        auto fresh = std::make_shared<Buf>();
+        hipError_t e = fresh->alloc(count);
+        if (e == hipSuccess && fill) e = fresh->fill_bytes(fill, count, stream_);
+        if (e != hipSuccess) { refused = true; return; }
+        Buf* old = &buf;
+        hipStream_t s = stream_;
+        copies.push_back([=]() { return fresh->copy_2d(kFromDevice, *old, old_ld, width, columns, new_ld, s); });
+        exchanges.push_back([=]() { old->swap(*fresh); });
+    };
+    auto regrow_1d = [&](auto& buf, int64_t count, int64_t keep, int fill = 0) { regrow(buf, count, keep, 1, keep, keep, fill); };
+
+    // m-sized
+    regrow_1d(d_basis_, m_cap, m_now);
+    regrow_1d(d_basis_alt_, m_cap, m_now);
+    regrow_1d(d_idcol_, m_cap, m_now);
+    regrow_1d(d_pos_of_row_, m_cap, m_now, 0xFF);      // -1 in the new part
+    regrow_1d(d_rmin_, m_cap / 8 + 2, d_rmin_.count());
+    regrow_1d(d_rhs_cols_, m_cap, 0);
+    regrow_1d(d_rhs_delta_, m_cap, 0);
+    {
+        const int64_t basic_most = std::min<int64_t>(m_cap, lay_.nr_normal);
+        regrow_1d(d_cost_rows_, basic_most, 0);
+        regrow_1d(d_cost_delta_, basic_most, 0);
+    }
+    // ld_b_-sized
+    for (DeviceBuf<double>* v : {&d_b_, &d_b_alt_, &d_alpha_, &d_aq_, &d_rho_, &d_w_, &d_v_, &d_minus_pi_}) regrow_1d(*v, ld_b, ld_b_);
+    // pitched
+    regrow(d_W_, ld_b * block_, ld_b_, block_, ld_b_, ld_b, 0);
+    regrow(dT0_, ld_t * std::max<int64_t>(n_cap, 1), ld_t_, n_now, ld_t_, ld_t, 0);
+    regrow(dR0_, ld_r * (block_ + 1), ld_r_, block_ + 1, ld_r_, ld_r, 0);
+    regrow(d_R0c_, ld_r * block_, ld_r_, block_, ld_r_, ld_r, 0);
+    // per stored or tableau column
+    regrow_1d(d_d_, n_cap, n_now);
+    regrow_1d(d_in_basis_, n_cap, d_in_basis_.count());
+    regrow_1d(d_cost_store_, n_cap, n_now);
+    regrow_1d(d_fcols_, n_cap, d_fcols_.count());
+    regrow_1d(d_fmask_, (n_cap + 63) / 64, d_fmask_.count());
+    {
+        const int64_t slots = price_structural_blocks(lay_.col_lo, lay_.col_hi) + (tab_na_ + v_cap + 255) / 256 + 8 + tab_scan_blocks((int32_t)n_cap) +
+                              price_csc_blocks(0, lay_.nr_normal);
+        regrow_1d(d_part_k1_, std::max(slots, d_part_k1_.count()), d_part_k1_.count());
+        regrow_1d(d_part_j_, std::max(slots, d_part_j_.count()), d_part_j_.count());
+    }
+    regrow_1d(d_vrow0_, v_cap, lay_.nr_virtual);
+    regrow_1d(d_vrow1_, v_cap, lay_.nr_virtual);
+    regrow_1d(d_vsign_, v_cap, lay_.nr_virtual);
+    // A with room for the cut rows behind the constraints (an adopted caller matrix gets an owned copy and stays as it is)
+    regrow(dA_, ld_a * std::max(lay_.nr_normal, 1), lay_.mc + lay_.nr_cuts, lay_.nr_normal, ld_a_, ld_a, 0);
+    if (refused) { (void)hipGetLastError(); return fail(RELP_E_ALLOC, "growing the tableau for cut rows: out of device memory"); }
+
+    hipError_t e = hipSuccess;
+    for (auto& copy : copies) e = first_error(e, copy());
+    HIP_TRY(e);                                        // (nothing exchanged: the new buffers go, the handle is as it was)
+    for (auto& exchange : exchanges) exchange();
+    copies.clear(); exchanges.clear();                 // releases the old buffers
+    ld_b_ = ld_b; ld_t_ = ld_t; ld_r_ = ld_r; ld_a_ = ld_a;
+    cut_room_ = room;
+    return RELP_OK;
+}
+
+relp_status_t Engine::reserve_cuts(int32_t rows) {
+    const relp_status_t st = dual_ready("relp_reserve_cuts");
+    if (st) return st;
+    if (rows < 0) return fail(RELP_E_ARG, "relp_reserve_cuts: rows < 0");
+    return grow_for_cuts(rows);
+}
+
+// Cut rows added on the current basis without a flush or a re-tabulation.  The slack of cut k is basic in its new row, so the row
+// in the current basis is g_k - sum_r g_k,B(r) T[r, :] over the rows r whose basic column is structural with a nonzero coefficient,
+// T = T0 + W R0 over the pending rows of the open block (launch_tab_add_cuts), and b_new = beta_k - sum_r g_k,B(r) b_r.  The slack
+// costs 0: d over the old columns, -obj, b and the basis entries of the old rows, W, R0 and T0 over the old rows and columns stay
+// as they are.  The coefficients go into the engine's copy of A (rows mc + cut) and into lay_ (the host LU), so every later rebuild
+// includes the cuts.
+relp_status_t Engine::add_cuts(int32_t count, const int64_t* row_ptr, const int32_t* col_idx, const double* values, const double* rhs) {
+    relp_status_t st = dual_ready("relp_add_cuts");
+    if (st) return st;
+    if ((st = lay_.check_cuts(count, row_ptr, col_idx, values, rhs, &err_))) return st;
+    if (count == 0) return RELP_OK;
+    if ((int64_t)lay_.nr_cuts + count > cut_room_) {
+        const int64_t want = std::max<int64_t>({(int64_t)lay_.nr_cuts + count, 2 * (int64_t)cut_room_, 16});
+        if (want > INT32_MAX / 2) return fail(RELP_E_ARG, "relp_add_cuts: too many cuts");
+        if ((st = grow_for_cuts((int32_t)want))) return st;
+    }
+    tab_settle();
+    if ((st = download_rec())) return st;
+    const int32_t p = h_rec_->n_eta;
+    const int32_t m_old = lay_.m, cuts_old = lay_.nr_cuts;
+    std::vector<double> b(m_old);
+    std::vector<int32_t> basis(m_old);
+    hipError_t e = d_b_.download(b, enqueue_only(stream_));
+    HIP_TRY(first_error(e, d_basis_.download(basis, stream_)));
+
+    // the cuts as a dense block over the structural columns: column sp holds its `count` coefficients contiguously (the cut rows of A)
+    std::vector<double> G((size_t)count * std::max(lay_.nr_normal, 1), 0.0);
+    for (int32_t k = 0; k < count; ++k)
+        for (int64_t x = row_ptr[k]; x < row_ptr[k + 1]; ++x) G[(size_t)col_idx[x] * count + k] = values[x];
+    // the union list: rows, ascending, whose basic column is structural with a nonzero coefficient in some cut; coef[entry][cut]
+    std::vector<int32_t> rows;
+    std::vector<double> coef;
+    for (int32_t i = 0; i < m_old; ++i) {
+        const int32_t j = basis[i];
+        if (j < 0 || j >= lay_.nr_normal) continue;
+        const double* g = &G[(size_t)j * count];
+        if (std::all_of(g, g + count, [](double v) { return v == 0.0; })) continue;
+        rows.push_back(i);
+        coef.insert(coef.end(), g, g + count);
+    }
+    const int32_t entries = (int32_t)rows.size();
+    // b of the new rows: beta_k - sum_r g_k,B(r) b_r with fma in ascending r
+    std::vector<double> b_new(count);
+    for (int32_t k = 0; k < count; ++k) {
+        double acc = 0.0;
+        for (int32_t x = 0; x < entries; ++x) acc = std::fma(coef[(size_t)x * count + k], b[rows[x]], acc);
+        b_new[k] = rhs[k] - acc;
+    }
+    HIP_TRY(d_cut_rows_.ensure(std::max(entries, 1), std::min<int64_t>(lay_.m, lay_.nr_normal)));
+    HIP_TRY(d_cut_coef_.ensure(std::max<int64_t>((int64_t)entries * count, 1)));
+    HIP_TRY(d_cut_u_.ensure((int64_t)count * std::max(block_, 1)));
+    HIP_TRY(d_cut_g_.ensure((int64_t)G.size()));
+
+    const TableauView tv = tview();                    // the tableau before the add
+    CutRows cr{d_cut_rows_, d_cut_coef_, entries, count, A_base(), ld_a_, lay_.mc + cuts_old, tab_na_, lay_.nr_normal};
+    CutTail ct{d_cost_store_, d_in_basis_, d_idcol_, d_basis_, d_vrow0_, d_vrow1_, d_vsign_, lay_.nr_virtual, block_ + 1};
+    // the list, the cut rows of A and b of the new rows under one wait (no return before it: the host arrays are in flight; no
+    // launch on a lost list)
+    e = d_cut_rows_.upload(rows, enqueue_only(stream_));
+    e = first_error(e, d_cut_coef_.upload(coef, enqueue_only(stream_)));
+    // (G goes up in one piece and is spread over the columns of A on the device: a strided copy from host memory is a transfer per
+    // column)
+    e = first_error(e, d_cut_g_.upload(G, enqueue_only(stream_)));
+    e = first_error(e, dA_.copy_2d(kFromDevice, d_cut_g_, count, count, lay_.nr_normal, ld_a_, enqueue_only(stream_), lay_.mc + cuts_old));
+    e = first_error(e, d_b_.upload(b_new.data(), count, enqueue_only(stream_), m_old));
+    if (e == hipSuccess) launch_tab_add_cuts(tv, deferred(), cr, d_in_basis_, p, d_cut_u_, ct, stream_);
+    HIP_TRY(first_error(e, hipStreamSynchronize(stream_)));
+    if (hipGetLastError() != hipSuccess) return fail(RELP_E_HIP, "relp_add_cuts: a kernel launch failed");
+
+    // the layout and the host mirrors follow (check_cuts passed: add_cuts cannot fail)
+    const int32_t n_old = n_store_;
+    (void)lay_.add_cuts(count, row_ptr, col_idx, values, rhs, &err_);
+    for (int32_t k = 0; k < count; ++k) idcol_h_.push_back(n_old + k);
+    cost_store_h_.resize((size_t)n_old + count, 0.0);
+    n_store_ += count; n_alloc_ += count; lay_.sc_hi += count;
+    tab_partials_valid_ = false;
+    cut_last_rows_ = entries;
+    cut_last_p_ = p;
+    h_rec_->outcome = DEV_RUNNING;
+    return upload_rec();
+}
+
+relp_status_t Engine::cut_stats(int64_t* out4) const {
+    if (!tableau_ || cfg_.shard_count > 1) return RELP_E_UNSUPPORTED;
+    if (phase_ != 2) return RELP_E_STATE;
+    out4[0] = lay_.nr_cuts; out4[1] = cut_room_; out4[2] = cut_last_rows_; out4[3] = cut_last_p_;
     return RELP_OK;
 }
 

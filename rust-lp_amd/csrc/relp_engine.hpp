@@ -136,6 +136,11 @@ class Engine : private EngineQueue {
     relp_status_t set_cost(const double* cost_n);
     relp_status_t get_cost(double* out_n);
     relp_status_t cost_stats(int64_t* out4) const;
+    // cut rows g'x <= beta over the structural columns added behind every row, their slacks behind every column, in place on the
+    // current basis (no flush, no re-tabulation); relp_run_dual continues from there.  reserve_cuts makes room without adding.
+    relp_status_t add_cuts(int32_t count, const int64_t* row_ptr, const int32_t* col_idx, const double* values, const double* rhs);
+    relp_status_t reserve_cuts(int32_t rows);
+    relp_status_t cut_stats(int64_t* out4) const;
     // batched ratio tests over the tableau as it stands, read-only: rows of T against d (penalties, cost ranges), identity columns
     // against b (rhs ranges)
     relp_status_t row_ratios(const int32_t* rows, int32_t count, double* down_ratio, int32_t* down_column, double* up_ratio,
@@ -305,6 +310,14 @@ class Engine : private EngineQueue {
     int64_t cost_changes_ = 0, cost_rows_ = 0;
     int32_t cost_last_p_ = 0, cost_last_splits_ = 0;
     relp_status_t store_costs(int32_t lo, int32_t hi);  // d_cost_, cost_store_h_, d_cost_store_ <- lay_.cost[lo, hi)
+    // relp_add_cuts: cut_room_ = the cut rows (and slack columns) every buffer of the tableau path has room for; grow_for_cuts
+    // takes them to a larger room (the only function that does).  The list of a call (rows, coef[entry][cut]) and u[cut][pending row]
+    // (relp_kernels.h: launch_tab_add_cuts) are grown on demand; what relp_cut_stats reports
+    int32_t cut_room_ = 0;
+    relp_status_t grow_for_cuts(int32_t room);
+    DeviceBuf<int32_t> d_cut_rows_;
+    DeviceBuf<double> d_cut_coef_, d_cut_u_, d_cut_g_;   // (d_cut_g_: the cuts of a call by structural column, on their way into A)
+    int32_t cut_last_rows_ = 0, cut_last_p_ = 0;
     // relp_row_ratios / relp_rhs_ranging: the uploaded list (rows, or their identity columns), the per-(direction, entry, block)
     // minima and the results [direction][entry] (relp_kernels.h: launch_tab_row_ratios, launch_tab_rhs_ranging); allocated at the
     // first query, grown on demand; what relp_ranging_stats reports

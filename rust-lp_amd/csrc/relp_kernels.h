@@ -72,6 +72,9 @@ struct ColumnTable {
     const int32_t* vrow1;         // virtual v -> second row or -1 (range slack)
     const int32_t* vsign;         // virtual v -> +1 / -1 on vrow0
     const double*  cost;          // structural p -> phase-2 cost             (nr_normal)
+    // cut rows (relp_add_cuts): rows [cut_row0, cut_row0 + nr_cuts) of a structural column p are A[p * ld_a + nr_constraints + k]
+    int32_t cut_row0 = 0;
+    int32_t nr_cuts = 0;
 };
 
 // ratio_rule: relp_ratio_rule_t.  pivot_guard (relp_config_t.pivot_rescue): a pivot row whose element is below `pivot` times the
@@ -525,6 +528,34 @@ int32_t tab_cost_splits(int32_t n_columns, int32_t count, int32_t forced);
 // launch that reads no tableau entry.  No atomics: the same (lists, p, splits) gives the same bits.
 void launch_tab_cost_change(const TableauView& tv, const DeferredUpdate& du, const CostChange& ch, const uint8_t* in_basis, int32_t p,
                             int32_t splits, double* u, double* partial, int64_t ld_partial, hipStream_t s);
+// Cut rows added on the current basis (relp_add_cuts).  `count` cuts over the structural columns become the rows tv.m .. tv.m + count
+// - 1 of the tableau, their slacks the stored columns tv.n_store .. (tableau columns tv.n ..), basic in their rows; tv is the view
+// BEFORE the add, and every buffer has room for the new rows and columns behind it.  Row of cut k in the current basis:
+// T[m + k, c] = g_kc - sum_e coef[e][k] T[rows[e], c], T = T0 + W R0 over the p pending rows.  rows: the rows whose basic column is
+// structural with a nonzero coefficient in some cut of the call, ascending (the summation order); coef[e * count + k] = that
+// column's coefficient in cut k, 0.0 where cut k does not touch it.  A: the engine's matrix, whose rows a_row0 .. a_row0 + count - 1
+// of structural column sp (stored column struct_c0 + sp) hold the cuts' coefficients g.
+struct CutRows {
+    const int32_t* rows; const double* coef; int32_t entries, count;
+    const double* A; int64_t ld_a; int32_t a_row0, struct_c0, nr_normal;
+};
+// What the add sets for the new rows and columns besides T0, R0, W and d: stored cost 0, flag basic (1), identity column and basis
+// entry of the new rows, the descriptors of the new virtual columns (first_virtual: the first one's index).  r0_rows: rows of R0
+// to clear in the new columns (du.kmax + the scratch row).
+struct CutTail {
+    double* cost_store; uint8_t* in_basis; int32_t* idcol; int32_t* basis; int32_t *vrow0, *vrow1, *vsign;
+    int32_t first_virtual, r0_rows;
+};
+static constexpr int32_t kTabCutTile = 8;              // cuts per workgroup: eight rows of one column are one 64-byte run of T0
+// [k_tab_cut_pending: u[k][j] = sum_e coef[e][k] W[j][rows[e]], grid (p, count), p > 0 only] -> [k_tab_cut_rows: one old stored column
+// per thread, kTabCutTile cuts per workgroup, the list staged in LDS 256 entries at a time, every T0 and R0 load shared by the tile;
+// writes T0[m + k, c]: g - acc for a structural column, 0.0 - acc for any other, exactly 0.0 for a column flagged basic (in_basis == 1)]
+// -> [k_tab_cut_tail: unit columns of the new slacks in T0, zeros in their R0 entries and in the new rows of W, d = cost = 0 and flag 1
+// for the new columns, idcol / basis / pos_of_row (-1) of the new rows, the new virtual descriptors].  b of the new rows is the
+// caller's.  The list is not cut into shares.  u: count * du.kmax doubles.  No atomics, fixed summation orders: the same call on the
+// same state gives the same bits.
+void launch_tab_add_cuts(const TableauView& tv, const DeferredUpdate& du, const CutRows& cr, const uint8_t* in_basis, int32_t p, double* u,
+                         const CutTail& ct, hipStream_t s);
 // Batched ratio tests over the tableau as it stands, T = T0 + W R0 over the p pending rows, read-only (relp_row_ratios,
 // relp_rhs_ranging).  The list is taken kTabRatioChunk entries per workgroup (a fixed size, not a rule: eight rows of one column are
 // one 64-byte sector of T0), grid = chunks x blocks of 256 columns (rows); the second launch has one workgroup per list entry.

@@ -172,6 +172,7 @@ __device__ __forceinline__ double stored_column_entry(const ColumnTable& ct, con
     const int p = c - ct.nr_artificial;
     if (p < ct.nr_normal) {
         if (i < ct.nr_constraints) return A[(int64_t)p * ld_a + i];
+        if (ct.nr_cuts > 0 && i >= ct.cut_row0) return A[(int64_t)p * ld_a + ct.nr_constraints + (i - ct.cut_row0)];      // cut rows sit behind the constraints
         return (i == ct.bound_row[p]) ? 1.0 : 0.0;
     }
     const int vv = p - ct.nr_normal;

@@ -1150,6 +1150,135 @@ __global__ __launch_bounds__(kThreads) void k_tab_cost_reduce(TableauView tv, co
 }
 
 // ------------------------------------------------------------------------------------------------
+// Cut rows added on the current basis (relp_add_cuts): cut k of the call, g_k' x <= beta_k over the structural columns, becomes
+// row m + k of the tableau with its new slack basic in it,
+//   T[m + k, c] = g_kc - sum_e coef[e][k] T0[r_e, c] - sum_{j<p} u[k][j] R0[j][c],   u[k][j] = sum_e coef[e][k] W[j][r_e]
+// over the list of rows r_e (ascending) whose basic column is structural with a nonzero coefficient in some cut of the call;
+// coef[e][k] = the coefficient of that basic column in cut k, 0.0 where cut k does not touch it.  The rows are written into T0;
+// nothing else of the old rows and columns is.  No atomics: every sum has a fixed order, the same call gives the same bits.
+// ------------------------------------------------------------------------------------------------
+// u[k][j] for pending row j = blockIdx.x and cut k = blockIdx.y: thread t sums its entries e = t, t + 256, ... in ascending order,
+// then a fixed tree over the 256 threads (k_tab_cost_pending with a coefficient per (entry, cut)).
+__global__ __launch_bounds__(kThreads) void k_tab_cut_pending(DeferredUpdate du, CutRows cr, double* __restrict__ u) {
+    __shared__ double s_sum[kThreads];
+    const double* col = du.W + (int64_t)blockIdx.x * du.ld;
+    const int k = blockIdx.y;
+    double acc = 0.0;
+    for (int e = threadIdx.x; e < cr.entries; e += kThreads) acc = fma(cr.coef[(int64_t)e * cr.count + k], col[cr.rows[e]], acc);
+    s_sum[threadIdx.x] = acc;
+    __syncthreads();
+    for (int half = kThreads / 2; half > 0; half >>= 1) {
+        if ((int)threadIdx.x < half) s_sum[threadIdx.x] += s_sum[threadIdx.x + half];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) u[(int64_t)k * du.kmax + blockIdx.x] = s_sum[0];
+}
+
+// Old stored column c = c_lo + blockIdx.x * 256 + threadIdx.x, the kTabCutTile cuts from blockIdx.y * kTabCutTile on.  The list is
+// staged in LDS 256 entries at a time (rows and the tile's coefficients); a thread issues the T0 loads of its column B at a time
+// before any is used and feeds every loaded entry into the tile's accumulators, entries ascending: one strided load serves the
+// whole tile.  Then the pending rows' share through u, ascending j, one R0 load for the tile.  Written: T0[m + k, c] = g - acc for
+// a structural column (g from the cut rows of A), 0.0 - acc for any other, exactly 0.0 for a column flagged basic.  The tile's
+// rows of one column are contiguous.  Nothing else is written; tv describes the tableau before the add.
+template <int B>
+__global__ __launch_bounds__(kThreads) void k_tab_cut_rows(TableauView tv, CutRows cr, const uint8_t* __restrict__ in_basis, int p,
+                                                           const double* __restrict__ u, int kmax) {
+    __shared__ int32_t s_r[kThreads];
+    __shared__ double s_coef[kThreads][kTabCutTile];
+    __shared__ double s_u[kTabCutTile][kMaxEta];
+    const int k0 = blockIdx.y * kTabCutTile, nv = min(kTabCutTile, cr.count - k0);
+    const int c = tv.c_lo + blockIdx.x * kThreads + threadIdx.x;
+    const bool mine = c < tv.c_hi;
+    const double* col = tv.T0 + (int64_t)(mine ? c : tv.c_lo) * tv.ld_t;
+    for (int x = threadIdx.x; x < kTabCutTile * p; x += kThreads) {
+        const int v = x / p, j = x - v * p;
+        s_u[v][j] = v < nv ? u[(int64_t)(k0 + v) * kmax + j] : 0.0;
+    }
+    double acc[kTabCutTile];
+#pragma unroll
+    for (int v = 0; v < kTabCutTile; ++v) acc[v] = 0.0;
+    for (int base = 0; base < cr.entries; base += kThreads) {
+        __syncthreads();                               // (the previous chunk has been read)
+        const int n = min(kThreads, cr.entries - base);
+        if ((int)threadIdx.x < n) {
+            s_r[threadIdx.x] = cr.rows[base + threadIdx.x];
+            const double* g = cr.coef + (int64_t)(base + threadIdx.x) * cr.count + k0;
+#pragma unroll
+            for (int v = 0; v < kTabCutTile; ++v) s_coef[threadIdx.x][v] = v < nv ? g[v] : 0.0;
+        }
+        __syncthreads();
+        if (!mine) continue;
+        int e0 = 0;
+        for (; e0 + B <= n; e0 += B) {
+            double t[B];
+#pragma unroll
+            for (int x = 0; x < B; ++x) t[x] = col[s_r[e0 + x]];
+#pragma unroll
+            for (int x = 0; x < B; ++x)
+#pragma unroll
+                for (int v = 0; v < kTabCutTile; ++v) acc[v] = fma(s_coef[e0 + x][v], t[x], acc[v]);
+        }
+        if (e0 < n) {
+            double t[B];
+#pragma unroll
+            for (int x = 0; x < B; ++x) t[x] = e0 + x < n ? col[s_r[e0 + x]] : 0.0;
+#pragma unroll
+            for (int x = 0; x < B; ++x)
+                if (e0 + x < n) {
+#pragma unroll
+                    for (int v = 0; v < kTabCutTile; ++v) acc[v] = fma(s_coef[e0 + x][v], t[x], acc[v]);
+                }
+        }
+    }
+    __syncthreads();                                   // s_u (an empty list never entered the loop)
+    if (!mine) return;
+    for_pending<B>(tv.R0, tv.ld_r, c, p, [&](int j, double r0) {
+#pragma unroll
+        for (int v = 0; v < kTabCutTile; ++v) acc[v] = fma(s_u[v][j], r0, acc[v]);
+    });
+    const int j = c - tv.col_off;
+    const bool basic = j >= 0 && j < tv.n && in_basis[j] == 1;
+    const int sp = c - cr.struct_c0;
+    const double* g = (sp >= 0 && sp < cr.nr_normal) ? cr.A + (int64_t)sp * cr.ld_a + cr.a_row0 + k0 : nullptr;
+    double* out = tv.T0 + (int64_t)c * tv.ld_t + tv.m + k0;
+#pragma unroll
+    for (int v = 0; v < kTabCutTile; ++v)
+        if (v < nv && (int64_t)tv.m + k0 + v < tv.ld_t) out[v] = basic ? 0.0 : (g ? g[v] : 0.0) - acc[v];
+}
+
+// The rest of an add, for the `count` new rows m .. and new stored columns n_store ..: the new slack columns of T0 are unit columns,
+// their entries of R0 (all rows, the scratch row included) and the new rows' entries of W are zero, d and the stored cost of the
+// new columns are 0 and their flag is basic, the new rows are identity rows of their slacks and sit in no column of W.
+__global__ void k_tab_cut_tail(TableauView tv, DeferredUpdate du, CutTail ct, int count) {
+    const int64_t n_t = (int64_t)(tv.m + count) * count, n_r = (int64_t)ct.r0_rows * count, n_w = (int64_t)du.kmax * count;
+    const int64_t total = n_t + n_r + n_w + count;
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
+        if (idx < n_t) {
+            const int k = (int)(idx / (tv.m + count)), i = (int)(idx % (tv.m + count));
+            tv.T0[(int64_t)(tv.n_store + k) * tv.ld_t + i] = i == tv.m + k ? 1.0 : 0.0;
+        } else if (idx < n_t + n_r) {
+            const int64_t x = idx - n_t;
+            tv.R0[(x / count) * tv.ld_r + tv.n_store + (x % count)] = 0.0;
+        } else if (idx < n_t + n_r + n_w) {
+            const int64_t x = idx - n_t - n_r;
+            du.W[(x / count) * du.ld + tv.m + (x % count)] = 0.0;
+        } else {
+            const int k = (int)(idx - n_t - n_r - n_w);
+            const int c = tv.n_store + k, row = tv.m + k, j = tv.n + k;
+            tv.d[c] = 0.0;
+            ct.cost_store[c] = 0.0;
+            ct.in_basis[j] = 1;
+            ct.idcol[row] = c;
+            ct.basis[row] = j;
+            if (du.pos_of_row) du.pos_of_row[row] = -1;
+            ct.vrow0[ct.first_virtual + k] = row;
+            ct.vrow1[ct.first_virtual + k] = -1;
+            ct.vsign[ct.first_virtual + k] = 1;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Batched ratio tests over the tableau as it stands (relp_row_ratios, relp_rhs_ranging): read-only streams over T0 (+ W R0 while
 // an update block is open, p = its pending rows).  Two launches each: [the minimum of every (list entry, block of 256 columns or
 // rows) into scratch] -> [one workgroup per list entry: the minimum of its blocks, then the tie band from the blocks whose own
@@ -1613,6 +1742,20 @@ void launch_tab_cost_change(const TableauView& tv, const DeferredUpdate& du, con
                            ld_partial);
     });
     if (splits > 1) hipLaunchKernelGGL(k_tab_cost_reduce, dim3(nb), dim3(kThreads), 0, s, tv, in_basis, (int)splits, partial, ld_partial);
+}
+
+void launch_tab_add_cuts(const TableauView& tv, const DeferredUpdate& du, const CutRows& cr, const uint8_t* in_basis, int32_t p, double* u,
+                         const CutTail& ct, hipStream_t s) {
+    if (cr.count < 1) return;
+    if (cr.entries < 1) p = 0;                         // no row of the tableau is read: every u would be 0
+    if (p > 0) hipLaunchKernelGGL(k_tab_cut_pending, dim3(p, cr.count), dim3(kThreads), 0, s, du, cr, u);
+    if (tv.c_hi > tv.c_lo)
+        with_load_batch(du.batch, [&](auto B) {
+            hipLaunchKernelGGL((k_tab_cut_rows<decltype(B)::value>), dim3(tab_scan_blocks(tv.c_hi - tv.c_lo), cdiv(cr.count, kTabCutTile)),
+                               dim3(kThreads), 0, s, tv, cr, in_basis, (int)p, u, (int)du.kmax);
+        });
+    const int64_t total = (int64_t)(tv.m + cr.count + ct.r0_rows + du.kmax + 1) * cr.count;
+    hipLaunchKernelGGL(k_tab_cut_tail, dim3(element_blocks(total)), dim3(256), 0, s, tv, du, ct, (int)cr.count);
 }
 
 void launch_tab_row_ratios(const TableauView& tv, const DeferredUpdate& du, const SelectPartials& sp, Tolerances tol,

@@ -151,4 +151,44 @@ void Layout::remove_rows(const std::vector<int32_t>& map) {
     candidate_len = candidate_len_for(m);
 }
 
+relp_status_t Layout::check_cuts(int32_t count, const int64_t* row_ptr, const int32_t* col_idx, const double* values, const double* cut_rhs,
+                                 std::string* err) const {
+    if (count < 0) return fail(err, RELP_E_ARG, "relp_add_cuts: count < 0");
+    if (count == 0) return RELP_OK;
+    if (!row_ptr || !cut_rhs) return fail(err, RELP_E_ARG, "relp_add_cuts: row_ptr or rhs missing");
+    if (row_ptr[0] != 0) return fail(err, RELP_E_ARG, "relp_add_cuts: row_ptr does not start at 0");
+    for (int32_t k = 0; k < count; ++k)
+        if (row_ptr[k + 1] < row_ptr[k]) return fail(err, RELP_E_ARG, "relp_add_cuts: row_ptr does not ascend");
+    if (row_ptr[count] > 0 && (!col_idx || !values)) return fail(err, RELP_E_ARG, "relp_add_cuts: col_idx or values missing");
+    std::vector<int32_t> named(nr_normal, -1);         // the last cut that named the column
+    for (int32_t k = 0; k < count; ++k) {
+        if (!std::isfinite(cut_rhs[k])) return fail(err, RELP_E_ARG, "relp_add_cuts: a right-hand side that is not finite");
+        for (int64_t e = row_ptr[k]; e < row_ptr[k + 1]; ++e) {
+            if (col_idx[e] < 0 || col_idx[e] >= nr_normal) return fail(err, RELP_E_ARG, "relp_add_cuts: not a structural column");
+            if (named[col_idx[e]] == k) return fail(err, RELP_E_ARG, "relp_add_cuts: a column named twice in one cut");
+            if (!std::isfinite(values[e])) return fail(err, RELP_E_ARG, "relp_add_cuts: a coefficient that is not finite");
+            named[col_idx[e]] = k;
+        }
+    }
+    return RELP_OK;
+}
+
+relp_status_t Layout::add_cuts(int32_t count, const int64_t* row_ptr, const int32_t* col_idx, const double* values, const double* cut_rhs,
+                               std::string* err) {
+    const relp_status_t st = check_cuts(count, row_ptr, col_idx, values, cut_rhs, err);
+    if (st || count == 0) return st;
+    if (nr_cuts == 0) { cut_row0 = m; cut_entries.assign(nr_normal, {}); }
+    for (int32_t k = 0; k < count; ++k) {
+        for (int64_t e = row_ptr[k]; e < row_ptr[k + 1]; ++e)
+            if (values[e] != 0.0) cut_entries[col_idx[e]].emplace_back(nr_cuts + k, values[e]);      // (ascending by cut: k ascends)
+        rhs.push_back(cut_rhs[k]);
+        vrow0.push_back(m + k); vrow1.push_back(-1); vsign.push_back(1);
+    }
+    nr_cuts += count; m += count; nr_virtual += count; n_provider += count;
+    row_lo = 0; row_hi = m;
+    row_stride = (int32_t)round_up_even(m);
+    candidate_len = candidate_len_for(m);
+    return RELP_OK;
+}
+
 }  // namespace relp

@@ -10,6 +10,7 @@
 #pragma once
 #include <cstdint>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/relp_engine.h"
@@ -37,6 +38,10 @@ struct Layout {
     std::vector<int32_t> bound_row;           // per structural column: its bound row, -1 = none
     std::vector<int32_t> vrow0, vrow1, vsign; // per virtual column: its row (-1: removed), the second row or -1, the sign
     int32_t engine = RELP_ENGINE_AUTO;        // relp_engine_kind_t, AUTO resolved
+    // cut rows added behind every other row (relp_add_cuts): cut k is row cut_row0 + k, its slack the k-th virtual column behind
+    // the ones of build(); cut_row0 is fixed at the first add (rows are only removed at the phase switch, before any cut)
+    int32_t nr_cuts = 0, cut_row0 = 0;
+    std::vector<std::vector<std::pair<int32_t, double>>> cut_entries;   // per structural column: (cut, coefficient != 0), ascending by cut
 
     // Kind: the artificial columns are numbered before all provider columns
     int32_t nr_artificial = 0;                // 0 from phase 2 on
@@ -60,6 +65,14 @@ struct Layout {
     // Rows deleted (map: old row -> new row, -1 = removed; only constraint rows go): every remaining row index shifts
     // down (Column::into_filtered, matrix_data.rs:592-614), rhs loses the rows, the shards own all rows.
     void remove_rows(const std::vector<int32_t>& map);
+    // `count` cuts  sum_e values[e] x[col_idx[e]] <= cut_rhs[k]  (e in [row_ptr[k], row_ptr[k + 1])) over the structural columns, as
+    // rows behind every existing row, each with a +1 slack behind every existing column: appends to rhs, vrow0 (the cut row),
+    // vrow1 (-1) and vsign (+1), raises m, nr_virtual and n_provider; mc, the row classes, bound_row and every existing index stay.
+    // check_cuts decides the RELP_E_ARG cases alone; add_cuts runs it first and touches nothing when it fails.
+    relp_status_t check_cuts(int32_t count, const int64_t* row_ptr, const int32_t* col_idx, const double* values, const double* cut_rhs,
+                             std::string* err) const;
+    relp_status_t add_cuts(int32_t count, const int64_t* row_ptr, const int32_t* col_idx, const double* values, const double* cut_rhs,
+                           std::string* err);
 
     int32_t nr_columns() const { return nr_artificial + n_provider; }
 
@@ -69,7 +82,8 @@ struct Layout {
     }
 
     // The entries (row, value) of tableau column j, in order: an artificial column is e_row; a structural column is what
-    // `structural(p, put)` supplies for it, then its bound row; a virtual column its descriptor rows.  False if j is no column.
+    // `structural(p, put)` supplies for it (constraint rows only), then its bound row, then its cut rows (rows ascend); a virtual
+    // column its descriptor rows.  False if j is no column.
     // It runs for every basis column of every LU refactorisation: forced inline (left to itself the compiler calls it per
     // column, 20 % slower at 64,000 rows); the unsigned compares also reject j < 0.
     template <class S, class P>
@@ -82,6 +96,8 @@ struct Layout {
         if ((uint32_t)p < (uint32_t)nr_normal) {
             structural(p, put);
             if (bound_row[p] >= 0) put(bound_row[p], 1.0);
+            if (nr_cuts > 0)
+                for (const auto& e : cut_entries[p]) put(cut_row0 + e.first, e.second);
             return true;
         }
         const uint32_t v = (uint32_t)(p - nr_normal);

@@ -100,6 +100,9 @@ _SIGNATURES = {
     "relp_set_cost": (C.c_int, [C.c_void_p, C.c_void_p]),
     "relp_get_cost": (C.c_int, [C.c_void_p, C.c_void_p]),
     "relp_cost_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "relp_add_cuts": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "relp_reserve_cuts": (C.c_int, [C.c_void_p, C.c_int32]),
+    "relp_cut_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "relp_row_ratios": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "relp_rhs_ranging": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "relp_ranging_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
@@ -467,6 +470,48 @@ class Tableau:
         the basic list in its last launch); relp_cost_stats."""
         out = (C.c_int64 * 4)()
         self._ck(self._lib.relp_cost_stats(self._h, out))
+        return tuple(int(x) for x in out)
+
+    def add_cuts(self, G, rhs) -> None:
+        """The cuts ``G x <= rhs`` over the structural columns become rows behind every existing row, on the current basis and
+        without a flush or a re-tabulation (relp_add_cuts); cut k is row ``nr_rows() + k`` and its slack, basic in that row,
+        column ``nr_columns() + k`` (both read before the call).  ``G`` is a dense ``count x nr_normal`` array or a CSR triple
+        ``(row_ptr, col_idx, values)``; ``run_dual`` re-solves from there."""
+        n = self.provider.nr_normal
+        if isinstance(G, tuple):
+            if len(G) != 3:
+                raise ValueError("a CSR triple is (row_ptr, col_idx, values)")
+            ptr = np.ascontiguousarray(G[0], dtype=np.int64)
+            idx = np.ascontiguousarray(G[1], dtype=np.int32)
+            val = np.ascontiguousarray(G[2], dtype=np.float64)
+            if ptr.ndim != 1 or ptr.shape[0] < 1 or idx.ndim != 1 or idx.shape != val.shape:
+                raise ValueError("row_ptr, col_idx and values must be one-dimensional, the latter two of the same length")
+            if ptr.shape[0] > 1 and ptr[-1] > idx.shape[0]:
+                raise ValueError("row_ptr reaches beyond col_idx")
+        else:
+            dense = np.atleast_2d(np.asarray(G, dtype=np.float64))
+            if dense.ndim != 2 or dense.shape[1] != n:
+                raise ValueError("G must have one column per structural column")
+            rows, cols = np.nonzero(dense)             # row-major: ascending row, then column
+            ptr = np.concatenate(([0], np.cumsum(np.bincount(rows, minlength=dense.shape[0])))).astype(np.int64)
+            idx = np.ascontiguousarray(cols, dtype=np.int32)
+            val = np.ascontiguousarray(dense[rows, cols], dtype=np.float64)
+        count = ptr.shape[0] - 1
+        beta = np.ascontiguousarray(np.atleast_1d(rhs), dtype=np.float64)
+        if beta.shape != (count,):
+            raise ValueError("rhs must have one entry per cut")
+        self._ck(self._lib.relp_add_cuts(self._h, count, ptr.ctypes.data, idx.ctypes.data, val.ctypes.data, beta.ctypes.data))
+
+    def reserve_cuts(self, rows: int) -> None:
+        """Room for ``rows`` cut rows in all, without adding any (relp_reserve_cuts): the tableau is re-allocated and copied
+        once, here, instead of inside an ``add_cuts``."""
+        self._ck(self._lib.relp_reserve_cuts(self._h, int(rows)))
+
+    def cut_stats(self) -> Tuple[int, int, int, int]:
+        """(cuts in the tableau, cut rows there is room for, tableau rows the last add_cuts read, pending rows of the update block
+        at that call); relp_cut_stats."""
+        out = (C.c_int64 * 4)()
+        self._ck(self._lib.relp_cut_stats(self._h, out))
         return tuple(int(x) for x in out)
 
     def _ratio_query(self, call, rows):
