@@ -392,6 +392,19 @@ class Tableau {
     void reserve_cuts(int32_t rows) { ck(relp_reserve_cuts(h_, rows)); }
     // relp_cut_stats: {cuts in the tableau, cut rows there is room for, tableau rows the last add read, pending rows at that call}
     std::array<int64_t, 4> cut_stats() { std::array<int64_t, 4> out{}; ck(relp_cut_stats(h_, out.data())); return out; }
+    // columns added in place on the current basis (relp_add_columns): column k has the coefficients values[e] in the engine rows
+    // row_idx[e], e in [col_ptr[k], col_ptr[k + 1]), cost[k] and x >= 0; it becomes column nr_columns() + k, non-basic.  run()
+    // re-solves from there.
+    void add_columns(const std::vector<int64_t>& col_ptr, const std::vector<int32_t>& row_idx, const std::vector<double>& values,
+                     const std::vector<double>& cost) {
+        if (col_ptr.size() != cost.size() + 1) throw Error(RELP_E_ARG, "col_ptr has one entry more than there are columns");
+        if (row_idx.size() != values.size() || (int64_t)values.size() < col_ptr.back()) throw Error(RELP_E_ARG, "one value per row index, col_ptr within them");
+        ck(relp_add_columns(h_, (int32_t)cost.size(), col_ptr.data(), row_idx.data(), values.data(), cost.data()));
+    }
+    // room for `columns` added columns in all, without adding any (relp_reserve_columns)
+    void reserve_columns(int32_t columns) { ck(relp_reserve_columns(h_, columns)); }
+    // relp_column_stats: {added columns in the tableau, columns there is room for, identity columns the last add read, pending rows at that call}
+    std::array<int64_t, 4> column_stats() { std::array<int64_t, 4> out{}; ck(relp_column_stats(h_, out.data())); return out; }
     // relp_row_ratios: per listed row the minimum d_j / |T[r,j]| over the non-basic columns with T[r,j] < 0 (down) and > 0 (up), and
     // the column that attains it (+inf, -1 without one): branching penalties, and the cost range [c - down, c + up] of the row's
     // basic variable.  Read-only.

@@ -352,6 +352,53 @@ relp_status_t relp_reserve_cuts(relp_engine_t *h, int32_t rows);
 /* out4 = { cuts in the tableau, cut rows there is room for, tableau rows the last relp_add_cuts read (the rows r above, over all
  * cuts of the call), pending rows p of the update block at that call }. */
 relp_status_t relp_cut_stats(const relp_engine_t *h, int64_t *out4);
+/* Columns added to the tableau on the current basis WITHOUT a flush or a re-tabulation (no counterpart in the reference): what
+ * column generation (cutting stock, Dantzig-Wolfe, branch-and-price) does between re-solves -- take relp_get_minus_pi, price columns
+ * outside the LP, add the ones with a negative reduced cost, relp_run.  `count` columns in CSC over the engine rows in their current
+ * order, the indexing of relp_change_right_hand_side (cut rows and bound rows included): column k has the coefficients values[e] in
+ * the rows row_idx[e], e in [col_ptr[k], col_ptr[k + 1]), 0 <= row_idx[e] < relp_nr_rows().
+ * Where a column goes: column k of the call becomes provider column relp_nr_columns() + k as it is at the call, behind every
+ * existing column (cut slacks and earlier added columns included).  No existing row or column index moves.
+ * What the variable is: x >= 0 without an upper bound, cost cost[k], non-basic (flag 0).  relp_get_basis_indices, relp_current_bfs,
+ * relp_get_trace, relp_from_basis, relp_generate_column and relp_relative_costs name it by that index.
+ * What the call changes: nothing is flushed or re-tabulated.  The stored columns that were the identity at the start are B^-1, in
+ * the update-block form T = (I + W S') T0, which is linear in T0, so with idcol(i) the identity column of row i
+ *     T0[:, new_k] = sum_e a_k[rows_e] * T0[:, idcol(rows_e)]      (rows_e ascending, an fma chain from 0.0)
+ *     R0[j][new_k] = T0[S[j], new_k]  for the p pending rows        (R0 = S' T0 still holds; W is not read)
+ *     d[new_k]     = c_k + sum_i (-pi)_i * a_k[i]                   (i ascending over the column's nonzero entries, an fma chain from
+ *                                                                    c_k, -pi as relp_get_minus_pi gives it at the call)
+ * and T0 + W R0 of the new column is B^-1 a_k with the open block left open.  The new columns' stored cost and flag are written.
+ * b, -obj, the basis, T0 / R0 / W and d over the old columns, the flags of the old columns, the trace, relp_reinversions,
+ * relp_tab_flush_stats, relp_cut_stats and relp_nr_rows stay exactly as they were, to the bit.  After the call the PRICE partials
+ * are invalid and the record is re-armed; relp_run or relp_run_dual may follow.  The call synchronises.
+ * Deterministic: the rows are walked in ascending order whatever the order of the entries inside the caller's CSC, no atomics, the
+ * list is not cut into shares; the same call on the same state gives the same bits.  An explicit zero coefficient is dropped
+ * before anything is uploaded.
+ * Every later rebuild (re-inversion interval, auto_reinversion, relp_from_basis, relp_set_right_hand_side) includes the columns:
+ * the host LU sees them when they are basic, the re-tabulation recomputes their stored columns, the objective uses their costs.
+ * relp_set_cost replaces the nr_normal structural costs only: the added columns keep theirs, and their d is recomputed with the
+ * rest.  relp_change_cost, relp_get_cost, relp_set_upper_bound and the col_idx of relp_add_cuts keep refusing an index >= nr_normal:
+ * a cut added later has coefficient 0 on every added column; changing the cost of an added column and cuts over added columns
+ * are not built.  relp_add_cuts after relp_add_columns works, and so do columns with entries in cut rows.
+ * RELP_E_ARG with nothing changed: count < 0, a missing array, a col_ptr that does not ascend from 0, a row outside
+ * [0, relp_nr_rows()), a row named twice in one column, a coefficient or cost that is not finite, more than 524,280 columns in one
+ * call.  count == 0 is a no-op.  A column without entries is accepted: T0 = 0, d = cost.
+ * RELP_ENGINE_TABLEAU, unsharded, phase 2: RELP_E_UNSUPPORTED on another or a sharded engine, RELP_E_STATE in phase 1 (all three
+ * calls).  RELP_E_ALLOC when growing fails: every new buffer is allocated before an old one is released, so the handle is then as
+ * it was.
+ * Capacity: relp_reserve_columns(columns) makes room for `columns` added columns in all (a no-op when there is room already; it
+ * never shrinks, adds nothing and changes no getter).  relp_add_columns grows by itself when room lacks, to max(added columns then
+ * in the tableau, 2 x the room so far, 16).  The room for cuts and the room for columns are independent: relp_reserve_cuts and
+ * relp_cut_stats report exactly what they report without added columns.  Growing re-allocates and copies the tableau, as for cuts;
+ * room for columns alone leaves the row-sized buffers and the matrix where they are (a caller's device matrix stays adopted).
+ * Dropping a column is not built: a column nobody wants any more stays non-basic once its reduced cost is positive. */
+relp_status_t relp_add_columns(relp_engine_t *h, int32_t count, const int64_t *col_ptr, const int32_t *row_idx, const double *values,
+                               const double *cost);
+relp_status_t relp_reserve_columns(relp_engine_t *h, int32_t columns);
+/* out4 = { added columns in the tableau, columns there is room for, identity columns the last relp_add_columns read (the rows with
+ * a nonzero coefficient in some column of the call), pending rows p of the update block at that call }.  Refused calls and calls
+ * with count == 0 are not counted. */
+relp_status_t relp_column_stats(const relp_engine_t *h, int64_t *out4);
 /* Batched ratio tests over the tableau as it stands (no counterpart in the reference): what a branch-and-bound driver asks at a
  * node ("which fractional row is the dearest to branch on?") and a solve asks at its end (the ranging report).  Both are read-only:
  * nothing is flushed or re-tabulated, and T0, R0, W, d, b, the basis, the flags, the PRICE partials, the record, the trace and

@@ -1250,25 +1250,30 @@ relp_status_t Engine::cost_stats(int64_t* out4) const {
     return RELP_OK;
 }
 
-// Room for `room` cut rows and their slack columns in every buffer of the tableau path that create() sizes from the rows or the
-// columns: the only function that grows the tableau engine.  The new pitches are the roundings of create() applied to the room.
+// Room for `cut_room` cut rows with their slack columns and for `col_room` added columns in every buffer of the tableau path that
+// create() sizes from the rows or the columns: the only function that grows the tableau engine, for both kinds of room (they are
+// independent; neither ever shrinks).  The new pitches are the roundings of create() applied to the room.
 // Every new buffer is allocated (zeroed: the kernels' 16-byte loads read the tails) before an old one is released, so a refused
 // allocation leaves the handle as it was; then the contents move, 2-D where the pitch changes, and once every copy has succeeded
 // the buffers are exchanged: old and new T0 live side by side for that moment.  A pending update block survives unchanged (same p, same bits); lay_, n_store_,
 // n_alloc_ and the host mirrors are not touched (they follow at the add).
-relp_status_t Engine::grow_for_cuts(int32_t room) {
-    if (room <= cut_room_) return RELP_OK;
+relp_status_t Engine::grow_tableau(int32_t cut_room, int32_t col_room) {
+    cut_room = std::max(cut_room, cut_room_); col_room = std::max(col_room, col_room_);
+    if (cut_room == cut_room_ && col_room == col_room_) return RELP_OK;
     tab_settle();
     HIP_TRY(hipStreamSynchronize(stream_));
+    const int32_t room = cut_room;
     const int32_t m_now = lay_.m, n_now = n_store_;
-    const int64_t m_cap = (int64_t)m_now - lay_.nr_cuts + room, n_cap = (int64_t)n_now - lay_.nr_cuts + room;
-    const int64_t v_cap = (int64_t)lay_.nr_virtual - lay_.nr_cuts + room;
-    if (m_cap > INT32_MAX - 16 || n_cap > INT32_MAX - 16) return fail(RELP_E_ARG, "relp_reserve_cuts: more rows or columns than an index holds");
+    const int64_t m_cap = (int64_t)m_now - lay_.nr_cuts + room;
+    const int64_t n_cap = (int64_t)n_now - lay_.nr_cuts + room - lay_.nr_added + col_room;
+    const int64_t v_cap = (int64_t)lay_.nr_virtual - lay_.nr_cuts + room - lay_.nr_added + col_room;
+    if (m_cap > INT32_MAX - 16 || n_cap > INT32_MAX - 16) return fail(RELP_E_ARG, "relp_reserve_cuts / relp_reserve_columns: more rows or columns than an index holds");
     // The pitches and sizes never shrink: after row removal at the phase switch (remove_rows lowers lay_.m and lay_.mc and leaves
     // every buffer as create() sized it) the rounding of the room can be below what is there.
     const int64_t ld_b = std::max(ld_b_, round_up(m_cap, 16)), ld_t = std::max(ld_t_, round_up(m_cap, 2));
     const int64_t ld_r = std::max(ld_r_, round_up(std::max<int64_t>(n_cap, 1), 2));
     const int64_t ld_a = std::max(ld_a_, round_up(std::max<int64_t>((int64_t)lay_.mc + room, 1), 2));
+    const int64_t ld_c = std::max(ld_c_, round_up(m_cap, 2));
 
     // per buffer: copy old -> new, and exchange them; the closures own the new buffers.  The exchanges run only after every copy
     // has succeeded: a refused copy leaves the handle as it was, like a refused allocation.
@@ -1276,9 +1281,9 @@ relp_status_t Engine::grow_for_cuts(int32_t room) {
     std::vector<std::function<void()>> exchanges;
     bool refused = false;
     // `columns` runs of `width` elements, old_ld apart in buf and new_ld apart in its replacement of at least `count` elements
-    auto regrow = [&](auto& buf, int64_t count, int64_t width, int64_t columns, int64_t old_ld, int64_t new_ld, int fill) {
+    auto regrow = [&](auto& buf, int64_t count, int64_t width, int64_t columns, int64_t old_ld, int64_t new_ld, int fill, bool create = false) {
         using Buf = std::decay_t<decltype(buf)>;
-        if (refused || !buf) return;                   // (a buffer this engine's configuration does not have)
+        if (refused || (!buf && !create)) return;      // (a buffer this engine's configuration does not have)
         count = std::max(count, buf.count());
         auto fresh = std::make_shared<Buf>();
         hipError_t e = fresh->alloc(count);
@@ -1291,23 +1296,30 @@ relp_status_t Engine::grow_for_cuts(int32_t room) {
     };
     auto regrow_1d = [&](auto& buf, int64_t count, int64_t keep, int fill = 0) { regrow(buf, count, keep, 1, keep, keep, fill); };
 
-    // m-sized
-    regrow_1d(d_basis_, m_cap, m_now);
-    regrow_1d(d_basis_alt_, m_cap, m_now);
-    regrow_1d(d_idcol_, m_cap, m_now);
-    regrow_1d(d_pos_of_row_, m_cap, m_now, 0xFF);      // -1 in the new part
-    regrow_1d(d_rmin_, m_cap / 8 + 2, d_rmin_.count());
-    regrow_1d(d_rhs_cols_, m_cap, 0);
-    regrow_1d(d_rhs_delta_, m_cap, 0);
-    {
-        const int64_t basic_most = std::min<int64_t>(m_cap, lay_.nr_normal);
-        regrow_1d(d_cost_rows_, basic_most, 0);
-        regrow_1d(d_cost_delta_, basic_most, 0);
+    // What only the rows size -- the m-sized and ld_b_-sized vectors, W and A -- moves only when the room for cut rows grows: room
+    // for columns alone leaves them, and an adopted caller matrix stays adopted (no owned copy of A for a reserve of columns).
+    const bool rows_grow = cut_room != cut_room_;
+    if (rows_grow) {
+        // m-sized
+        regrow_1d(d_basis_, m_cap, m_now);
+        regrow_1d(d_basis_alt_, m_cap, m_now);
+        regrow_1d(d_idcol_, m_cap, m_now);
+        regrow_1d(d_pos_of_row_, m_cap, m_now, 0xFF);      // -1 in the new part
+        regrow_1d(d_rmin_, m_cap / 8 + 2, d_rmin_.count());
+        regrow_1d(d_rhs_cols_, m_cap, 0);
+        regrow_1d(d_rhs_delta_, m_cap, 0);
+        {
+            const int64_t basic_most = std::min<int64_t>(m_cap, lay_.nr_normal);
+            regrow_1d(d_cost_rows_, basic_most, 0);
+            regrow_1d(d_cost_delta_, basic_most, 0);
+        }
+        // ld_b_-sized
+        for (DeviceBuf<double>* v : {&d_b_, &d_b_alt_, &d_alpha_, &d_aq_, &d_rho_, &d_w_, &d_v_, &d_minus_pi_}) regrow_1d(*v, ld_b, ld_b_);
+        regrow(d_W_, ld_b * block_, ld_b_, block_, ld_b_, ld_b, 0);
+        // A with room for the cut rows behind the constraints (an adopted caller matrix gets an owned copy and stays as it is)
+        regrow(dA_, ld_a * std::max(lay_.nr_normal, 1), lay_.mc + lay_.nr_cuts, lay_.nr_normal, ld_a_, ld_a, 0);
     }
-    // ld_b_-sized
-    for (DeviceBuf<double>* v : {&d_b_, &d_b_alt_, &d_alpha_, &d_aq_, &d_rho_, &d_w_, &d_v_, &d_minus_pi_}) regrow_1d(*v, ld_b, ld_b_);
     // pitched
-    regrow(d_W_, ld_b * block_, ld_b_, block_, ld_b_, ld_b, 0);
     regrow(dT0_, ld_t * std::max<int64_t>(n_cap, 1), ld_t_, n_now, ld_t_, ld_t, 0);
     regrow(dR0_, ld_r * (block_ + 1), ld_r_, block_ + 1, ld_r_, ld_r, 0);
     regrow(d_R0c_, ld_r * block_, ld_r_, block_, ld_r_, ld_r, 0);
@@ -1326,17 +1338,17 @@ relp_status_t Engine::grow_for_cuts(int32_t room) {
     regrow_1d(d_vrow0_, v_cap, lay_.nr_virtual);
     regrow_1d(d_vrow1_, v_cap, lay_.nr_virtual);
     regrow_1d(d_vsign_, v_cap, lay_.nr_virtual);
-    // A with room for the cut rows behind the constraints (an adopted caller matrix gets an owned copy and stays as it is)
-    regrow(dA_, ld_a * std::max(lay_.nr_normal, 1), lay_.mc + lay_.nr_cuts, lay_.nr_normal, ld_a_, ld_a, 0);
-    if (refused) { (void)hipGetLastError(); return fail(RELP_E_ALLOC, "growing the tableau for cut rows: out of device memory"); }
+    // the added columns in row space (allocated with the first room for columns): the pitch follows the row capacity
+    if (col_room > 0) regrow(d_col_a_, ld_c * col_room, std::min<int64_t>(m_now, ld_c_), lay_.nr_added, std::max<int64_t>(ld_c_, 1), ld_c, 0, true);
+    if (refused) { (void)hipGetLastError(); return fail(RELP_E_ALLOC, "growing the tableau for cut rows or columns: out of device memory"); }
 
     hipError_t e = hipSuccess;
     for (auto& copy : copies) e = first_error(e, copy());
     HIP_TRY(e);                                        // (nothing exchanged: the new buffers go, the handle is as it was)
     for (auto& exchange : exchanges) exchange();
     copies.clear(); exchanges.clear();                 // releases the old buffers
-    ld_b_ = ld_b; ld_t_ = ld_t; ld_r_ = ld_r; ld_a_ = ld_a;
-    cut_room_ = room;
+    ld_b_ = ld_b; ld_t_ = ld_t; ld_r_ = ld_r; ld_a_ = ld_a; ld_c_ = ld_c;
+    cut_room_ = cut_room; col_room_ = col_room;
     return RELP_OK;
 }
 
@@ -1433,6 +1445,97 @@ relp_status_t Engine::cut_stats(int64_t* out4) const {
     if (!tableau_ || cfg_.shard_count > 1) return RELP_E_UNSUPPORTED;
     if (phase_ != 2) return RELP_E_STATE;
     out4[0] = lay_.nr_cuts; out4[1] = cut_room_; out4[2] = cut_last_rows_; out4[3] = cut_last_p_;
+    return RELP_OK;
+}
+
+relp_status_t Engine::reserve_columns(int32_t columns) {
+    const relp_status_t st = dual_ready("relp_reserve_columns");
+    if (st) return st;
+    if (columns < 0) return fail(RELP_E_ARG, "relp_reserve_columns: columns < 0");
+    return grow_tableau(cut_room_, columns);
+}
+
+// Columns from outside added on the current basis without a flush or a re-tabulation: the mirror image of add_cuts.  B^-1 is in the
+// tableau -- the stored columns that were the identity at the start -- in the form (I + W S') T0 like every other column, and that
+// form is linear in T0: T0[:, new] = sum_i a_i T0[:, idcol[i]] over the rows i with a nonzero coefficient, ascending, and the new
+// entries of R0 are the new T0 entries at the pending rows (launch_tab_add_columns; W is not read).  d_new = c + sum_i (-pi)_i a_i
+// with -pi as relp_get_minus_pi reads it off d, an fma chain from c in ascending i, formed here.  The new variable is non-basic:
+// b, -obj, the basis and everything over the old columns stay as they are.  The entries go into lay_ (the host LU) and into
+// d_col_a_ (the re-tabulation), so every later rebuild includes the columns.
+relp_status_t Engine::add_columns(int32_t count, const int64_t* col_ptr, const int32_t* row_idx, const double* values, const double* cost) {
+    relp_status_t st = dual_ready("relp_add_columns");
+    if (st) return st;
+    if (count > kTabColTile * 65535) return fail(RELP_E_ARG, "relp_add_columns: more than 524,280 columns in one call");       // (the grid's second dimension)
+    if ((st = lay_.check_columns(count, col_ptr, row_idx, values, cost, &err_))) return st;
+    if (count == 0) return RELP_OK;
+    if ((int64_t)lay_.nr_added + count > col_room_) {
+        const int64_t want = std::max<int64_t>({(int64_t)lay_.nr_added + count, 2 * (int64_t)col_room_, 16});
+        if (want > INT32_MAX / 2) return fail(RELP_E_ARG, "relp_add_columns: too many columns");
+        if ((st = grow_tableau(cut_room_, (int32_t)want))) return st;
+    }
+    tab_settle();
+    if ((st = download_rec())) return st;
+    const int32_t p = h_rec_->n_eta;
+    const int32_t m = lay_.m, n_old = n_store_, added_old = lay_.nr_added;
+    std::vector<double> d(n_old);
+    HIP_TRY(d_d_.download(d, stream_));
+
+    // the columns as a dense block in row space (explicit zeros dropped: they stay 0.0), and the union list: rows, ascending, with
+    // a nonzero coefficient in some column of the call, as their identity columns; coef[entry][column]
+    std::vector<double> dense((size_t)count * m, 0.0);
+    std::vector<uint8_t> touched(m, 0);
+    for (int32_t k = 0; k < count; ++k)
+        for (int64_t x = col_ptr[k]; x < col_ptr[k + 1]; ++x)
+            if (values[x] != 0.0) { dense[(size_t)k * m + row_idx[x]] = values[x]; touched[row_idx[x]] = 1; }
+    std::vector<int32_t> cols;
+    std::vector<double> coef;
+    std::vector<double> d_new(cost, cost + count);
+    for (int32_t i = 0; i < m; ++i) {
+        if (!touched[i]) continue;
+        cols.push_back(idcol_h_[i]);
+        const double minus_pi = d[idcol_h_[i]] - cost_store_h_[idcol_h_[i]];      // as get_vector forms it
+        for (int32_t k = 0; k < count; ++k) {
+            const double a = dense[(size_t)k * m + i];
+            coef.push_back(a);
+            if (a != 0.0) d_new[k] = std::fma(minus_pi, a, d_new[k]);
+        }
+    }
+    const int32_t entries = (int32_t)cols.size();
+    HIP_TRY(d_col_cols_.ensure(std::max(entries, 1), lay_.m));
+    HIP_TRY(d_col_coef_.ensure(std::max<int64_t>((int64_t)entries * count, 1)));
+    HIP_TRY(d_col_d_.ensure(count, 16));
+    HIP_TRY(d_col_cost_.ensure(count, 16));
+
+    const TableauView tv = tview();                    // the tableau before the add
+    const ColumnAdd ca{d_col_cols_, d_col_coef_, entries, count, d_col_d_, d_col_cost_};
+    const ColumnTail ct{d_cost_store_, d_in_basis_, d_vrow0_, d_vrow1_, d_vsign_, lay_.nr_virtual, block_ + 1};
+    // the list, d and cost of the new columns and their rows of d_col_a_ under one wait (no return before it: the host arrays are
+    // in flight; no launch on a lost list)
+    hipError_t e = d_col_cols_.upload(cols, enqueue_only(stream_));
+    e = first_error(e, d_col_coef_.upload(coef, enqueue_only(stream_)));
+    e = first_error(e, d_col_d_.upload(d_new, enqueue_only(stream_)));
+    e = first_error(e, d_col_cost_.upload(cost, count, enqueue_only(stream_)));
+    e = first_error(e, d_col_a_.copy_2d(kFromHost, dense.data(), m, m, count, ld_c_, enqueue_only(stream_), (int64_t)added_old * ld_c_));
+    if (e == hipSuccess) launch_tab_add_columns(tv, deferred(), ca, p, ct, stream_);
+    HIP_TRY(first_error(e, hipStreamSynchronize(stream_)));
+    if (hipGetLastError() != hipSuccess) return fail(RELP_E_HIP, "relp_add_columns: a kernel launch failed");
+
+    // the layout and the host mirrors follow (check_columns passed: add_columns cannot fail)
+    (void)lay_.add_columns(count, col_ptr, row_idx, values, cost, &err_);
+    cost_store_h_.resize((size_t)n_old + count);
+    std::copy(cost, cost + count, cost_store_h_.begin() + n_old);
+    n_store_ += count; n_alloc_ += count; lay_.sc_hi += count;
+    tab_partials_valid_ = false;
+    col_last_cols_ = entries;
+    col_last_p_ = p;
+    h_rec_->outcome = DEV_RUNNING;
+    return upload_rec();
+}
+
+relp_status_t Engine::column_stats(int64_t* out4) const {
+    if (!tableau_ || cfg_.shard_count > 1) return RELP_E_UNSUPPORTED;
+    if (phase_ != 2) return RELP_E_STATE;
+    out4[0] = lay_.nr_added; out4[1] = col_room_; out4[2] = col_last_cols_; out4[3] = col_last_p_;
     return RELP_OK;
 }
 
@@ -1636,6 +1739,7 @@ std::vector<double> Engine::basic_costs(const std::vector<int32_t>& basis, int p
         if (j >= kWrappedArtificialBase) continue;
         if (phase == 1) w[i] = j < lay_.nr_artificial ? sign : 0.0;
         else if (j < lay_.nr_normal) w[i] = sign * lay_.cost[j];
+        else if (lay_.added_of(j) >= 0) w[i] = sign * lay_.cost_of(j);       // (relp_add_columns; every other virtual column costs 0)
     }
     return w;
 }
@@ -1649,6 +1753,7 @@ double Engine::objective_of(const std::vector<int32_t>& basis, const std::vector
         if (j >= kWrappedArtificialBase) continue;
         if (phase_ == 1) { if (j < lay_.nr_artificial) objective += b[i]; }
         else if (j < lay_.nr_normal) objective += lay_.cost[j] * b[i];
+        else if (lay_.added_of(j) >= 0) objective += lay_.cost_of(j) * b[i];   // (relp_add_columns; every other virtual column costs 0)
     }
     return objective;
 }
@@ -1919,7 +2024,23 @@ relp_status_t Engine::retabulate(bool adapt_interval) {
     storage.nr_artificial = tab_na_;                    // storage columns keep the artificial block in front
     LuSlabs slabs;
     if ((st = batch_solve_slabs(lay_.sc_hi - c_first, &slabs))) return st;
-    launch_lu_ftran_cols(dlu_, tv, A_base(), ld_a_, storage, c_first, lay_.sc_hi - c_first, slabs, stream_);
+    // Without added columns one launch over all stored columns.  With them (relp_add_columns) the stored columns are walked in
+    // segments, every column solved once: the columns between two runs of added columns from A and the column table as ever (a
+    // column's solve does not depend on the launch it is in: the same bits), every contiguous run of added columns from d_col_a_
+    // by the same kernel, presented as "structural" columns over all m rows.
+    int32_t c_next = c_first;
+    for (int32_t a = 0; a < lay_.nr_added;) {
+        int32_t run = 1;
+        while (a + run < lay_.nr_added && lay_.added_virtual[a + run] == lay_.added_virtual[a] + run) ++run;
+        ColumnTable block = storage;
+        block.nr_artificial = tab_na_ + lay_.nr_normal + lay_.added_virtual[a];      // the run's first storage column
+        block.nr_normal = run; block.nr_constraints = lay_.m; block.nr_cuts = 0;
+        launch_lu_ftran_cols(dlu_, tv, A_base(), ld_a_, storage, c_next, block.nr_artificial - c_next, slabs, stream_);
+        launch_lu_ftran_cols(dlu_, tv, d_col_a_ + (int64_t)a * ld_c_, ld_c_, block, block.nr_artificial, run, slabs, stream_);
+        c_next = block.nr_artificial + run;
+        a += run;
+    }
+    launch_lu_ftran_cols(dlu_, tv, A_base(), ld_a_, storage, c_next, lay_.sc_hi - c_next, slabs, stream_);
     HIP_TRY(d_aq_.upload(lay_.rhs.data(), lay_.m, stream_));
     launch_lu_ftran(dlu_, d_aq_, d_b_, d_lu_scratch_, nullptr, stream_);                 // b = B^-1 rhs
     tableau_reprice();                                  // as after every few flushes
@@ -1993,6 +2114,7 @@ relp_status_t Engine::from_basis(const int32_t* basis_columns) {
         HIP_TRY(d_basis_.upload(basis, stream_));
         cost_store_h_.assign(n_store_, 0.0);
         for (int32_t p = 0; p < lay_.nr_normal; ++p) cost_store_h_[tab_na_ + p] = lay_.cost[p];
+        for (int32_t a = 0; a < lay_.nr_added; ++a) cost_store_h_[tab_na_ + lay_.nr_normal + lay_.added_virtual[a]] = lay_.added_cost[a];
         HIP_TRY(d_cost_store_.upload(cost_store_h_, stream_));
         st = retabulate();
         if (st || !retab_done_) {

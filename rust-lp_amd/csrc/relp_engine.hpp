@@ -141,6 +141,11 @@ class Engine : private EngineQueue {
     relp_status_t add_cuts(int32_t count, const int64_t* row_ptr, const int32_t* col_idx, const double* values, const double* rhs);
     relp_status_t reserve_cuts(int32_t rows);
     relp_status_t cut_stats(int64_t* out4) const;
+    // columns x >= 0 from outside (CSC over the engine rows) added behind every column, non-basic, in place on the current basis
+    // (no flush, no re-tabulation); relp_run continues from there.  reserve_columns makes room without adding.
+    relp_status_t add_columns(int32_t count, const int64_t* col_ptr, const int32_t* row_idx, const double* values, const double* cost);
+    relp_status_t reserve_columns(int32_t columns);
+    relp_status_t column_stats(int64_t* out4) const;
     // batched ratio tests over the tableau as it stands, read-only: rows of T against d (penalties, cost ranges), identity columns
     // against b (rhs ranges)
     relp_status_t row_ratios(const int32_t* rows, int32_t count, double* down_ratio, int32_t* down_column, double* up_ratio,
@@ -314,10 +319,22 @@ class Engine : private EngineQueue {
     // takes them to a larger room (the only function that does).  The list of a call (rows, coef[entry][cut]) and u[cut][pending row]
     // (relp_kernels.h: launch_tab_add_cuts) are grown on demand; what relp_cut_stats reports
     int32_t cut_room_ = 0;
-    relp_status_t grow_for_cuts(int32_t room);
+    relp_status_t grow_for_cuts(int32_t room) { return grow_tableau(room, col_room_); }
+    // The one growth function of the tableau engine, for both kinds of room (cut rows with their slacks; added columns): never shrinks
+    relp_status_t grow_tableau(int32_t cut_room, int32_t col_room);
     DeviceBuf<int32_t> d_cut_rows_;
     DeviceBuf<double> d_cut_coef_, d_cut_u_, d_cut_g_;   // (d_cut_g_: the cuts of a call by structural column, on their way into A)
     int32_t cut_last_rows_ = 0, cut_last_p_ = 0;
+    // relp_add_columns: col_room_ = the added columns every per-column buffer has room for, independent of cut_room_.  d_col_a_:
+    // the added columns as a dense block in row space, column a at a * ld_c_ (ld_c_ >= the row capacity), what a re-tabulation
+    // solves them from (retabulate).  The list of a call (identity columns, coef[entry][column]), d and cost of the new columns
+    // (relp_kernels.h: launch_tab_add_columns) are grown on demand; what relp_column_stats reports
+    int32_t col_room_ = 0;
+    int64_t ld_c_ = 0;
+    DeviceBuf<double> d_col_a_;
+    DeviceBuf<int32_t> d_col_cols_;
+    DeviceBuf<double> d_col_coef_, d_col_d_, d_col_cost_;
+    int32_t col_last_cols_ = 0, col_last_p_ = 0;
     // relp_row_ratios / relp_rhs_ranging: the uploaded list (rows, or their identity columns), the per-(direction, entry, block)
     // minima and the results [direction][entry] (relp_kernels.h: launch_tab_row_ratios, launch_tab_rhs_ranging); allocated at the
     // first query, grown on demand; what relp_ranging_stats reports

@@ -556,6 +556,33 @@ static constexpr int32_t kTabCutTile = 8;              // cuts per workgroup: ei
 // same state gives the same bits.
 void launch_tab_add_cuts(const TableauView& tv, const DeferredUpdate& du, const CutRows& cr, const uint8_t* in_basis, int32_t p, double* u,
                          const CutTail& ct, hipStream_t s);
+// Columns added on the current basis (relp_add_columns).  `count` columns from outside become the stored columns tv.n_store ..
+// tv.n_store + count - 1 (tableau columns tv.n ..), non-basic; tv is the view BEFORE the add, and every buffer has room for the
+// new columns behind it.  T = (I + W S') T0 is linear in T0 and the stored columns that were the identity at the start are B^-1
+// in that form, so the new column k needs no read of W:
+//   T0[:, n_store + k] = sum_e coef[e][k] T0[:, cols[e]]        R0[j][n_store + k] = T0[S[j], n_store + k]   (j < p)
+// cols: the identity columns (storage columns, inside [tv.c_lo, tv.c_hi)) of the rows with a nonzero coefficient in some column
+// of the call, rows ascending (the summation order); coef[e * count + k] = the coefficient of column k in that row, 0.0 where
+// column k does not touch it.  d_new / cost_new: reduced cost and cost of the new columns (count each; the host forms d from -pi).
+struct ColumnAdd {
+    const int32_t* cols; const double* coef; int32_t entries, count;
+    const double* d_new; const double* cost_new;
+};
+// What the add sets for the new columns besides T0 and R0: d, the stored cost, flag non-basic (0) and the empty descriptors
+// (vrow0 = vrow1 = -1, vsign = 1) of the new virtual columns (first_virtual: the first one's index).  r0_rows: rows of R0 the new
+// columns have (du.kmax + the scratch row); the ones from p on are cleared.
+struct ColumnTail {
+    double* cost_store; uint8_t* in_basis; int32_t *vrow0, *vrow1, *vsign;
+    int32_t first_virtual, r0_rows;
+};
+static constexpr int32_t kTabColTile = 8;              // new columns per workgroup: every T0 load feeds eight accumulators
+// [k_tab_col_apply: one row per thread, 256 rows and kTabColTile new columns per workgroup, the list staged in LDS 256 entries at a
+// time, every (coalesced) T0 load shared by the tile, one fma chain per new column from 0.0 in ascending list order; writes
+// T0[i, n_store + k] for i < m] -> [k_tab_col_tail: R0[j][n_store + k] = the T0 entry just written at row du.S[j] for j < p and
+// 0.0 for the other rows of R0, d, stored cost, flag 0 and the descriptors of the new columns].  The list is not cut into shares.
+// No atomics, fixed summation orders: the same call on the same state gives the same bits.
+void launch_tab_add_columns(const TableauView& tv, const DeferredUpdate& du, const ColumnAdd& ca, int32_t p, const ColumnTail& ct,
+                            hipStream_t s);
 // Batched ratio tests over the tableau as it stands, T = T0 + W R0 over the p pending rows, read-only (relp_row_ratios,
 // relp_rhs_ranging).  The list is taken kTabRatioChunk entries per workgroup (a fixed size, not a rule: eight rows of one column are
 // one 64-byte sector of T0), grid = chunks x blocks of 256 columns (rows); the second launch has one workgroup per list entry.

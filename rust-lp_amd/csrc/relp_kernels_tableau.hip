@@ -1279,6 +1279,89 @@ __global__ void k_tab_cut_tail(TableauView tv, DeferredUpdate du, CutTail ct, in
 }
 
 // ------------------------------------------------------------------------------------------------
+// Columns added on the current basis (relp_add_columns): the mirror image of the cut rows.  B^-1 sits in the stored columns that
+// were the identity at the start, in the form T = (I + W S') T0 like every other column, and that form is linear in T0: the new
+// column k of the call is
+//   T0[:, n_store + k] = sum_e coef[e][k] T0[:, cols[e]],   R0[j][n_store + k] = T0[S[j], n_store + k]  (so that R0 = S' T0 holds)
+// over the list of identity columns cols[e] of the rows (ascending) with a nonzero coefficient in some column of the call, and
+// T0 + W R0 of it is B^-1 a_k with the open block left open.  W is not read.  No atomics: one chain per entry, fixed order.
+// ------------------------------------------------------------------------------------------------
+// Row i = blockIdx.x * 256 + threadIdx.x, the kTabColTile new columns from blockIdx.y * kTabColTile on.  The list is staged in LDS
+// 256 entries at a time (identity columns and the tile's coefficients); a thread issues its T0 loads B at a time before any is used
+// (consecutive threads read consecutive rows of one column) and feeds every loaded entry into the tile's accumulators, entries
+// ascending.  Written: T0[i, n_store + k] = acc for i < m.  Nothing else is written; tv describes the tableau before the add.
+template <int B>
+__global__ __launch_bounds__(kThreads) void k_tab_col_apply(TableauView tv, ColumnAdd ca) {
+    __shared__ int32_t s_c[kThreads];
+    __shared__ double s_coef[kThreads][kTabColTile];
+    const int k0 = blockIdx.y * kTabColTile, nv = min(kTabColTile, ca.count - k0);
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    const bool mine = i < tv.m;
+    double acc[kTabColTile];
+#pragma unroll
+    for (int v = 0; v < kTabColTile; ++v) acc[v] = 0.0;
+    for (int base = 0; base < ca.entries; base += kThreads) {
+        __syncthreads();                               // (the previous chunk has been read)
+        const int n = min(kThreads, ca.entries - base);
+        if ((int)threadIdx.x < n) {
+            s_c[threadIdx.x] = ca.cols[base + threadIdx.x];
+            const double* a = ca.coef + (int64_t)(base + threadIdx.x) * ca.count + k0;
+#pragma unroll
+            for (int v = 0; v < kTabColTile; ++v) s_coef[threadIdx.x][v] = v < nv ? a[v] : 0.0;
+        }
+        __syncthreads();
+        if (!mine) continue;
+        int e0 = 0;
+        for (; e0 + B <= n; e0 += B) {
+            double t[B];
+#pragma unroll
+            for (int x = 0; x < B; ++x) t[x] = tv.T0[(int64_t)s_c[e0 + x] * tv.ld_t + i];
+#pragma unroll
+            for (int x = 0; x < B; ++x)
+#pragma unroll
+                for (int v = 0; v < kTabColTile; ++v) acc[v] = fma(s_coef[e0 + x][v], t[x], acc[v]);
+        }
+        if (e0 < n) {
+            double t[B];
+#pragma unroll
+            for (int x = 0; x < B; ++x) t[x] = e0 + x < n ? tv.T0[(int64_t)s_c[e0 + x] * tv.ld_t + i] : 0.0;
+#pragma unroll
+            for (int x = 0; x < B; ++x)
+                if (e0 + x < n) {
+#pragma unroll
+                    for (int v = 0; v < kTabColTile; ++v) acc[v] = fma(s_coef[e0 + x][v], t[x], acc[v]);
+                }
+        }
+    }
+    if (!mine) return;
+#pragma unroll
+    for (int v = 0; v < kTabColTile; ++v)
+        if (v < nv) tv.T0[(int64_t)(tv.n_store + k0 + v) * tv.ld_t + i] = acc[v];
+}
+
+// The rest of an add, for the `count` new stored columns n_store ..: their entries of R0 are the T0 entries k_tab_col_apply wrote at
+// the p pending rows S[j] and zero in the other rows of R0 (the scratch row included); d and the stored cost are the caller's,
+// the flag is non-basic, the descriptors are those of an empty column.
+__global__ void k_tab_col_tail(TableauView tv, DeferredUpdate du, ColumnAdd ca, ColumnTail ct, int p) {
+    const int64_t n_r = (int64_t)ct.r0_rows * ca.count, total = n_r + ca.count;
+    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
+        if (idx < n_r) {
+            const int64_t j = idx / ca.count, c = tv.n_store + idx % ca.count;
+            tv.R0[j * tv.ld_r + c] = j < p ? tv.T0[c * tv.ld_t + du.S[j]] : 0.0;
+        } else {
+            const int k = (int)(idx - n_r);
+            const int c = tv.n_store + k;
+            tv.d[c] = ca.d_new[k];
+            ct.cost_store[c] = ca.cost_new[k];
+            ct.in_basis[tv.n + k] = 0;
+            ct.vrow0[ct.first_virtual + k] = -1;
+            ct.vrow1[ct.first_virtual + k] = -1;
+            ct.vsign[ct.first_virtual + k] = 1;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Batched ratio tests over the tableau as it stands (relp_row_ratios, relp_rhs_ranging): read-only streams over T0 (+ W R0 while
 // an update block is open, p = its pending rows).  Two launches each: [the minimum of every (list entry, block of 256 columns or
 // rows) into scratch] -> [one workgroup per list entry: the minimum of its blocks, then the tie band from the blocks whose own
@@ -1756,6 +1839,18 @@ void launch_tab_add_cuts(const TableauView& tv, const DeferredUpdate& du, const 
         });
     const int64_t total = (int64_t)(tv.m + cr.count + ct.r0_rows + du.kmax + 1) * cr.count;
     hipLaunchKernelGGL(k_tab_cut_tail, dim3(element_blocks(total)), dim3(256), 0, s, tv, du, ct, (int)cr.count);
+}
+
+void launch_tab_add_columns(const TableauView& tv, const DeferredUpdate& du, const ColumnAdd& ca, int32_t p, const ColumnTail& ct,
+                            hipStream_t s) {
+    if (ca.count < 1) return;
+    if (tv.m > 0)
+        with_load_batch(du.batch, [&](auto B) {
+            hipLaunchKernelGGL((k_tab_col_apply<decltype(B)::value>), dim3(cdiv(tv.m, kThreads), cdiv(ca.count, kTabColTile)), dim3(kThreads), 0,
+                               s, tv, ca);
+        });
+    const int64_t total = (int64_t)(ct.r0_rows + 1) * ca.count;
+    hipLaunchKernelGGL(k_tab_col_tail, dim3(element_blocks(total)), dim3(256), 0, s, tv, du, ca, ct, (int)p);
 }
 
 void launch_tab_row_ratios(const TableauView& tv, const DeferredUpdate& du, const SelectPartials& sp, Tolerances tol,

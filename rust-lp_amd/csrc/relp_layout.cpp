@@ -183,11 +183,54 @@ relp_status_t Layout::add_cuts(int32_t count, const int64_t* row_ptr, const int3
             if (values[e] != 0.0) cut_entries[col_idx[e]].emplace_back(nr_cuts + k, values[e]);      // (ascending by cut: k ascends)
         rhs.push_back(cut_rhs[k]);
         vrow0.push_back(m + k); vrow1.push_back(-1); vsign.push_back(1);
+        if (nr_added > 0) added_slot.push_back(-1);
     }
     nr_cuts += count; m += count; nr_virtual += count; n_provider += count;
     row_lo = 0; row_hi = m;
     row_stride = (int32_t)round_up_even(m);
     candidate_len = candidate_len_for(m);
+    return RELP_OK;
+}
+
+relp_status_t Layout::check_columns(int32_t count, const int64_t* col_ptr, const int32_t* row_idx, const double* values, const double* col_cost,
+                                    std::string* err) const {
+    if (count < 0) return fail(err, RELP_E_ARG, "relp_add_columns: count < 0");
+    if (count == 0) return RELP_OK;
+    if (!col_ptr || !col_cost) return fail(err, RELP_E_ARG, "relp_add_columns: col_ptr or cost missing");
+    if (col_ptr[0] != 0) return fail(err, RELP_E_ARG, "relp_add_columns: col_ptr does not start at 0");
+    for (int32_t k = 0; k < count; ++k)
+        if (col_ptr[k + 1] < col_ptr[k]) return fail(err, RELP_E_ARG, "relp_add_columns: col_ptr does not ascend");
+    if (col_ptr[count] > 0 && (!row_idx || !values)) return fail(err, RELP_E_ARG, "relp_add_columns: row_idx or values missing");
+    std::vector<int32_t> named(m, -1);                 // the last column that named the row
+    for (int32_t k = 0; k < count; ++k) {
+        if (!std::isfinite(col_cost[k])) return fail(err, RELP_E_ARG, "relp_add_columns: a cost that is not finite");
+        for (int64_t e = col_ptr[k]; e < col_ptr[k + 1]; ++e) {
+            if (row_idx[e] < 0 || row_idx[e] >= m) return fail(err, RELP_E_ARG, "relp_add_columns: row out of range");
+            if (named[row_idx[e]] == k) return fail(err, RELP_E_ARG, "relp_add_columns: a row named twice in one column");
+            if (!std::isfinite(values[e])) return fail(err, RELP_E_ARG, "relp_add_columns: a coefficient that is not finite");
+            named[row_idx[e]] = k;
+        }
+    }
+    return RELP_OK;
+}
+
+relp_status_t Layout::add_columns(int32_t count, const int64_t* col_ptr, const int32_t* row_idx, const double* values, const double* col_cost,
+                                  std::string* err) {
+    const relp_status_t st = check_columns(count, col_ptr, row_idx, values, col_cost, err);
+    if (st || count == 0) return st;
+    if (nr_added == 0) added_slot.assign(nr_virtual, -1);
+    for (int32_t k = 0; k < count; ++k) {
+        std::vector<std::pair<int32_t, double>> entries;
+        for (int64_t e = col_ptr[k]; e < col_ptr[k + 1]; ++e)
+            if (values[e] != 0.0) entries.emplace_back(row_idx[e], values[e]);
+        std::sort(entries.begin(), entries.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+        added_entries.push_back(std::move(entries));
+        added_cost.push_back(col_cost[k]);
+        added_virtual.push_back(nr_virtual + k);
+        added_slot.push_back(nr_added + k);
+        vrow0.push_back(-1); vrow1.push_back(-1); vsign.push_back(1);
+    }
+    nr_added += count; nr_virtual += count; n_provider += count;
     return RELP_OK;
 }
 

@@ -42,6 +42,13 @@ struct Layout {
     // the ones of build(); cut_row0 is fixed at the first add (rows are only removed at the phase switch, before any cut)
     int32_t nr_cuts = 0, cut_row0 = 0;
     std::vector<std::vector<std::pair<int32_t, double>>> cut_entries;   // per structural column: (cut, coefficient != 0), ascending by cut
+    // columns added behind every other column (relp_add_columns): the a-th added column is the virtual column added_virtual[a] with
+    // the empty descriptor of a removed row (vrow0 = vrow1 = -1: device code reads an empty column); its entries (row, coefficient
+    // != 0, rows ascending) and its cost are kept here.  added_slot: per virtual column its a, or -1 (empty while nothing was added)
+    int32_t nr_added = 0;
+    std::vector<int32_t> added_virtual, added_slot;
+    std::vector<std::vector<std::pair<int32_t, double>>> added_entries;
+    std::vector<double> added_cost;
 
     // Kind: the artificial columns are numbered before all provider columns
     int32_t nr_artificial = 0;                // 0 from phase 2 on
@@ -74,6 +81,23 @@ struct Layout {
     relp_status_t add_cuts(int32_t count, const int64_t* row_ptr, const int32_t* col_idx, const double* values, const double* cut_rhs,
                            std::string* err);
 
+    // `count` columns x >= 0 in CSC over the rows in their current order (cut and bound rows included), cost[k] each, behind every
+    // existing column: appends an empty descriptor per column to vrow0 / vrow1 / vsign, keeps entries and costs (above), raises
+    // nr_virtual and n_provider; m, rhs, the rows and every existing index stay.  An explicit zero is dropped, the entries of a
+    // column are kept by ascending row whatever the caller's order.  check_columns decides the RELP_E_ARG cases alone; add_columns
+    // runs it first and touches nothing when it fails.
+    relp_status_t check_columns(int32_t count, const int64_t* col_ptr, const int32_t* row_idx, const double* values, const double* col_cost,
+                                std::string* err) const;
+    relp_status_t add_columns(int32_t count, const int64_t* col_ptr, const int32_t* row_idx, const double* values, const double* col_cost,
+                              std::string* err);
+    // the a of provider column p when it is an added column, else -1; the phase-2 cost of provider column p
+    int32_t added_of(int32_t p) const { return (nr_added > 0 && p >= nr_normal && p < n_provider) ? added_slot[p - nr_normal] : -1; }
+    double cost_of(int32_t p) const {
+        if (p < nr_normal) return cost[p];
+        const int32_t a = added_of(p);
+        return a >= 0 ? added_cost[a] : 0.0;
+    }
+
     int32_t nr_columns() const { return nr_artificial + n_provider; }
 
     // the row of an artificial column: j < nr_artificial, or a wrapped index after the phase switch
@@ -83,7 +107,7 @@ struct Layout {
 
     // The entries (row, value) of tableau column j, in order: an artificial column is e_row; a structural column is what
     // `structural(p, put)` supplies for it (constraint rows only), then its bound row, then its cut rows (rows ascend); a virtual
-    // column its descriptor rows.  False if j is no column.
+    // column its descriptor rows, an added column (relp_add_columns) its entries, rows ascending.  False if j is no column.
     // It runs for every basis column of every LU refactorisation: forced inline (left to itself the compiler calls it per
     // column, 20 % slower at 64,000 rows); the unsigned compares also reject j < 0.
     template <class S, class P>
@@ -104,6 +128,8 @@ struct Layout {
         if (v >= (uint32_t)nr_virtual) return false;
         if (vrow0[v] >= 0) put(vrow0[v], (double)vsign[v]);     // -1: its row was removed
         if (vrow1[v] >= 0) put(vrow1[v], 1.0);
+        if (nr_added > 0 && added_slot[v] >= 0)
+            for (const auto& e : added_entries[added_slot[v]]) put(e.first, e.second);
         return true;
     }
     // the same for provider column p (no artificial columns in front)

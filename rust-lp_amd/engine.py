@@ -103,6 +103,9 @@ _SIGNATURES = {
     "relp_add_cuts": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "relp_reserve_cuts": (C.c_int, [C.c_void_p, C.c_int32]),
     "relp_cut_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "relp_add_columns": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "relp_reserve_columns": (C.c_int, [C.c_void_p, C.c_int32]),
+    "relp_column_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "relp_row_ratios": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "relp_rhs_ranging": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "relp_ranging_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
@@ -512,6 +515,49 @@ class Tableau:
         at that call); relp_cut_stats."""
         out = (C.c_int64 * 4)()
         self._ck(self._lib.relp_cut_stats(self._h, out))
+        return tuple(int(x) for x in out)
+
+    def add_columns(self, A_new, cost) -> None:
+        """New variables ``x >= 0`` with the columns ``A_new`` over the engine rows and the costs ``cost`` become columns behind
+        every existing column, non-basic, on the current basis and without a flush or a re-tabulation (relp_add_columns); column k
+        is column ``nr_columns() + k`` (read before the call).  ``A_new`` is a dense ``nr_rows() x count`` array, one vector with a
+        scalar cost, or a CSC triple ``(col_ptr, row_idx, values)``; ``run`` re-solves from there."""
+        if isinstance(A_new, tuple):
+            if len(A_new) != 3:
+                raise ValueError("a CSC triple is (col_ptr, row_idx, values)")
+            ptr = np.ascontiguousarray(A_new[0], dtype=np.int64)
+            idx = np.ascontiguousarray(A_new[1], dtype=np.int32)
+            val = np.ascontiguousarray(A_new[2], dtype=np.float64)
+            if ptr.ndim != 1 or ptr.shape[0] < 1 or idx.ndim != 1 or idx.shape != val.shape:
+                raise ValueError("col_ptr, row_idx and values must be one-dimensional, the latter two of the same length")
+            if ptr.shape[0] > 1 and ptr[-1] > idx.shape[0]:
+                raise ValueError("col_ptr reaches beyond row_idx")
+        else:
+            dense = np.asarray(A_new, dtype=np.float64)
+            if dense.ndim == 1:
+                dense = dense.reshape(-1, 1)
+            if dense.ndim != 2 or dense.shape[0] != self.nr_rows():
+                raise ValueError("A_new must have one row per engine row")
+            cols, rows = np.nonzero(dense.T)           # column-major: ascending column, then row
+            ptr = np.concatenate(([0], np.cumsum(np.bincount(cols, minlength=dense.shape[1])))).astype(np.int64)
+            idx = np.ascontiguousarray(rows, dtype=np.int32)
+            val = np.ascontiguousarray(dense[rows, cols], dtype=np.float64)
+        count = ptr.shape[0] - 1
+        c = np.ascontiguousarray(np.atleast_1d(cost), dtype=np.float64)
+        if c.shape != (count,):
+            raise ValueError("cost must have one entry per column")
+        self._ck(self._lib.relp_add_columns(self._h, count, ptr.ctypes.data, idx.ctypes.data, val.ctypes.data, c.ctypes.data))
+
+    def reserve_columns(self, columns: int) -> None:
+        """Room for ``columns`` added columns in all, without adding any (relp_reserve_columns): the tableau is re-allocated and
+        copied once, here, instead of inside an ``add_columns``."""
+        self._ck(self._lib.relp_reserve_columns(self._h, int(columns)))
+
+    def column_stats(self) -> Tuple[int, int, int, int]:
+        """(added columns in the tableau, columns there is room for, identity columns the last add_columns read, pending rows of
+        the update block at that call); relp_column_stats."""
+        out = (C.c_int64 * 4)()
+        self._ck(self._lib.relp_column_stats(self._h, out))
         return tuple(int(x) for x in out)
 
     def _ratio_query(self, call, rows):

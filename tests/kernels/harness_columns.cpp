@@ -1,0 +1,100 @@
+// The kernel harness of the columns added in place (test infrastructure): one extern "C" entry that runs
+// relp::launch_tab_add_columns of the shipped librelp_engine.so once on whole device IMAGES a test constructs
+// (tests/kernel_harness_columns.py) and hands every image back.  `make -C tests/kernels -f columns.mk`
+//
+// The caller owns the layout: it passes the pitches and every buffer as the image the device shall hold (its own sentinels where
+// the launch must not write).  This file only checks that nothing the launch may touch lies outside an image -- a refused call
+// (negative code) launches nothing -- uploads, launches, synchronises and downloads.  A HIP error is returned as 1000 + code and is
+// sticky: nothing is launched any more in this process.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <vector>
+
+#include "relp_kernels.h"
+
+using namespace relp;
+
+namespace {
+
+constexpr int kRefusedShape = -1, kRefusedIndex = -2, kRefusedBatch = -3, kRefusedLength = -4;
+constexpr int kHipErrorBase = 1000;
+int g_sticky = 0;
+
+#define REFUSE_IF(cond, code) do { if (cond) return (code); } while (0)
+#define HIP_OK(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) { g_sticky = kHipErrorBase + (int)e_; return g_sticky; } } while (0)
+
+// a device copy of a host image; freed on every way out
+template <class T>
+struct Image {
+    T* d = nullptr; T* h; int64_t n;
+    Image(T* host, int64_t len) : h(host), n(len) {}
+    ~Image() { if (d) (void)hipFree(d); }
+    hipError_t up() {
+        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), sizeof(T) * (size_t)(n > 0 ? n : 1));
+        return (e != hipSuccess || n == 0) ? e : hipMemcpy(d, h, sizeof(T) * (size_t)n, hipMemcpyHostToDevice);
+    }
+    hipError_t back() { return n == 0 ? hipSuccess : hipMemcpy(h, d, sizeof(T) * (size_t)n, hipMemcpyDeviceToHost); }
+};
+
+}  // namespace
+
+extern "C" {
+
+int rkcol_sticky_error() { return g_sticky; }
+int rkcol_col_tile() { return kTabColTile; }
+
+// launch_tab_add_columns on the view (m rows, owned stored columns [c_lo, c_lo + n_owned) = all up to n_store, tableau columns from
+// col_off on) with p pending rows of at most kmax.  Images, in and out: T0 (columns ld_t apart, from column c_lo), R0 ((kmax + 1) x
+// ld_r, from column c_lo), d and cost_store (by storage column from 0), in_basis (by tableau column), S (kmax pending rows), vrow0 /
+// vrow1 / vsign (by virtual column), cols (entries identity columns, each an owned stored column), coef (entries x count), d_new and
+// cost_new (count each).
+int rkcol_tab_add_columns(int64_t m, int64_t n_owned, int64_t c_lo, int64_t col_off, int64_t p, int64_t kmax, int64_t batch, int64_t count,
+                          int64_t entries, int64_t ld_t, int64_t ld_r, int64_t first_virtual,
+                          double* T0, int64_t T0_len, double* R0, int64_t R0_len, double* d, int64_t d_len, double* cost_store,
+                          int64_t cost_store_len, uint8_t* in_basis, int64_t in_basis_len, int32_t* S, int64_t S_len, int32_t* vrow0,
+                          int64_t vrow0_len, int32_t* vrow1, int64_t vrow1_len, int32_t* vsign, int64_t vsign_len, int32_t* cols,
+                          int64_t cols_len, double* coef, int64_t coef_len, double* d_new, int64_t d_new_len, double* cost_new,
+                          int64_t cost_new_len) {
+    if (g_sticky) return g_sticky;
+    const int64_t cap = 1 << 20;
+    REFUSE_IF(m < 1 || m > cap || n_owned < 1 || n_owned > cap || count < 1 || count > 4096 || entries < 0 || entries > cap, kRefusedShape);
+    REFUSE_IF(kmax < 1 || kmax > 128 || p < 0 || p > kmax, kRefusedShape);
+    REFUSE_IF(batch != 1 && batch != 8 && batch != 16 && batch != 32, kRefusedBatch);
+    const int64_t n_all = c_lo + n_owned, n_tab = n_all - col_off;
+    REFUSE_IF(c_lo < 0 || c_lo > cap || col_off < 0 || col_off >= n_all, kRefusedIndex);
+    REFUSE_IF(ld_t < m || ld_r < n_owned + count || ld_t > 2 * cap || ld_r > 2 * cap, kRefusedShape);
+    REFUSE_IF(first_virtual < 0 || first_virtual > cap, kRefusedIndex);
+    REFUSE_IF(T0_len != (n_owned + count) * ld_t || R0_len != (kmax + 1) * ld_r, kRefusedLength);
+    REFUSE_IF(d_len != n_all + count || cost_store_len != n_all + count || in_basis_len != n_tab + count || S_len != kmax, kRefusedLength);
+    REFUSE_IF(vrow0_len != first_virtual + count || vrow1_len != vrow0_len || vsign_len != vrow0_len, kRefusedLength);
+    REFUSE_IF(cols_len != entries || coef_len != entries * count || d_new_len != count || cost_new_len != count, kRefusedLength);
+    for (int64_t e = 0; e < entries; ++e) REFUSE_IF(cols[e] < c_lo || cols[e] >= n_all, kRefusedIndex);
+    for (int64_t j = 0; j < p; ++j) REFUSE_IF(S[j] < 0 || S[j] >= m, kRefusedIndex);
+
+    Image<double> iT0(T0, T0_len), iR0(R0, R0_len), id(d, d_len), ic(cost_store, cost_store_len), icoef(coef, coef_len), idn(d_new, d_new_len),
+        icn(cost_new, cost_new_len);
+    Image<uint8_t> iflag(in_basis, in_basis_len);
+    Image<int32_t> iS(S, S_len), iv0(vrow0, vrow0_len), iv1(vrow1, vrow1_len), ivs(vsign, vsign_len), icols(cols, cols_len);
+    HIP_OK(iT0.up()); HIP_OK(iR0.up()); HIP_OK(id.up()); HIP_OK(ic.up()); HIP_OK(icoef.up()); HIP_OK(idn.up()); HIP_OK(icn.up());
+    HIP_OK(iflag.up()); HIP_OK(iS.up()); HIP_OK(iv0.up()); HIP_OK(iv1.up()); HIP_OK(ivs.up()); HIP_OK(icols.up());
+
+    TableauView tv{};
+    tv.T0 = iT0.d - c_lo * ld_t; tv.ld_t = ld_t;
+    tv.R0 = iR0.d - c_lo; tv.ld_r = ld_r;
+    tv.d = id.d; tv.m = (int32_t)m; tv.n_store = (int32_t)n_all; tv.col_off = (int32_t)col_off; tv.n = (int32_t)n_tab;
+    tv.c_lo = (int32_t)c_lo; tv.c_hi = (int32_t)n_all;
+    DeferredUpdate du{};
+    du.kmax = (int32_t)kmax; du.S = iS.d; du.batch = (int32_t)batch;
+    const ColumnAdd ca{icols.d, icoef.d, (int32_t)entries, (int32_t)count, idn.d, icn.d};
+    const ColumnTail ct{ic.d, iflag.d, iv0.d, iv1.d, ivs.d, (int32_t)first_virtual, (int32_t)kmax + 1};
+    launch_tab_add_columns(tv, du, ca, (int32_t)p, ct, 0);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipDeviceSynchronize());
+
+    HIP_OK(iT0.back()); HIP_OK(iR0.back()); HIP_OK(id.back()); HIP_OK(ic.back()); HIP_OK(icoef.back()); HIP_OK(idn.back()); HIP_OK(icn.back());
+    HIP_OK(iflag.back()); HIP_OK(iS.back()); HIP_OK(iv0.back()); HIP_OK(iv1.back()); HIP_OK(ivs.back()); HIP_OK(icols.back());
+    return 0;
+}
+
+}  // extern "C"
