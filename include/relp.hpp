@@ -405,6 +405,12 @@ class Tableau {
     void reserve_columns(int32_t columns) { ck(relp_reserve_columns(h_, columns)); }
     // relp_column_stats: {added columns in the tableau, columns there is room for, identity columns the last add read, pending rows at that call}
     std::array<int64_t, 4> column_stats() { std::array<int64_t, 4> out{}; ck(relp_column_stats(h_, out.data())); return out; }
+    // cut rows (engine rows, their slacks basic) and added columns (provider columns, non-basic) taken out of the tableau in place
+    // (relp_remove_cuts, relp_remove_columns): the open block is flushed, the survivors close up in order and keep their bits
+    void remove_cuts(const std::vector<int32_t>& rows) { ck(relp_remove_cuts(h_, rows.data(), (int32_t)rows.size())); }
+    void remove_columns(const std::vector<int32_t>& columns) { ck(relp_remove_columns(h_, columns.data(), (int32_t)columns.size())); }
+    // relp_removal_stats: {cuts removed, added columns removed, tableau entries the last removal moved, pending rows it flushed}
+    std::array<int64_t, 4> removal_stats() { std::array<int64_t, 4> out{}; ck(relp_removal_stats(h_, out.data())); return out; }
     // relp_row_ratios: per listed row the minimum d_j / |T[r,j]| over the non-basic columns with T[r,j] < 0 (down) and > 0 (up), and
     // the column that attains it (+inf, -1 without one): branching penalties, and the cost range [c - down, c + up] of the row's
     // basic variable.  Read-only.

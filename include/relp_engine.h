@@ -345,7 +345,8 @@ relp_status_t relp_cost_stats(const relp_engine_t *h, int64_t *out4);
  * adds nothing and changes no getter).  relp_add_cuts grows by itself when room lacks, to max(cuts then in the tableau, 2 x the
  * room so far, 16).  Growing re-allocates and copies the tableau: old and new T0 live side by side for a moment, so a driver
  * that knows its cut budget reserves it once, while memory is plentiful.
- * Dropping a cut is not built: relax it instead, relp_change_right_hand_side(cut row, a value it cannot bind at). */
+ * A cut is taken back with relp_remove_cuts (below) once its slack is basic; a tight cut can be relaxed instead,
+ * relp_change_right_hand_side(cut row, a value it cannot bind at). */
 relp_status_t relp_add_cuts(relp_engine_t *h, int32_t count, const int64_t *row_ptr, const int32_t *col_idx, const double *values,
                             const double *rhs);
 relp_status_t relp_reserve_cuts(relp_engine_t *h, int32_t rows);
@@ -391,7 +392,7 @@ relp_status_t relp_cut_stats(const relp_engine_t *h, int64_t *out4);
  * in the tableau, 2 x the room so far, 16).  The room for cuts and the room for columns are independent: relp_reserve_cuts and
  * relp_cut_stats report exactly what they report without added columns.  Growing re-allocates and copies the tableau, as for cuts;
  * room for columns alone leaves the row-sized buffers and the matrix where they are (a caller's device matrix stays adopted).
- * Dropping a column is not built: a column nobody wants any more stays non-basic once its reduced cost is positive. */
+ * A column nobody wants any more is taken back with relp_remove_columns (below) while it is non-basic. */
 relp_status_t relp_add_columns(relp_engine_t *h, int32_t count, const int64_t *col_ptr, const int32_t *row_idx, const double *values,
                                const double *cost);
 relp_status_t relp_reserve_columns(relp_engine_t *h, int32_t columns);
@@ -399,6 +400,40 @@ relp_status_t relp_reserve_columns(relp_engine_t *h, int32_t columns);
  * a nonzero coefficient in some column of the call), pending rows p of the update block at that call }.  Refused calls and calls
  * with count == 0 are not counted. */
 relp_status_t relp_column_stats(const relp_engine_t *h, int64_t *out4);
+/* Cut rows and added columns taken out of the tableau IN PLACE (no counterpart in the reference): what a branch-and-cut or
+ * column-generation driver does when it purges -- cuts whose slack has gone basic after a round, columns whose reduced cost stays
+ * positive after pricing, everything a node added when branch-and-bound backtracks.  Both are exact deletions, without arithmetic
+ * and without a re-tabulation; nothing is re-allocated or shrunk, and the freed room is what the next relp_add_cuts /
+ * relp_add_columns uses (relp_cut_stats and relp_column_stats report fewer cuts or columns and the same room).
+ * relp_remove_cuts: `rows` are `count` engine rows of cut rows, the indexing of relp_change_right_hand_side (with cuts in the
+ * tableau these are the last rows: [relp_nr_rows() - cuts, relp_nr_rows())), each at most once, in any order.  With i the row of a
+ * cut and s its slack, s must be basic, in whichever tableau row r that is (after pivots r need not be i: read
+ * relp_get_basis_indices).  Constraint i leaves everything indexed by constraint (the right-hand side, relp_get_minus_pi, the cut
+ * rows of the matrix, the entries added columns hold in it), tableau row r everything indexed by basis position (the rows of the
+ * tableau, relp_get_b, relp_get_basis_indices), column s everything indexed by column (relp_relative_costs, relp_generate_column, the
+ * flags, the costs).  Both index spaces close up in order: a surviving row or column keeps its place relative to every other
+ * survivor, so an index above a removed one drops by the number of removed ones below it -- the column indices inside
+ * relp_get_basis_indices and relp_current_bfs too.  relp_nr_rows and relp_nr_columns drop by count.
+ * relp_remove_columns: `columns` are `count` provider columns added by relp_add_columns, each at most once, in any order, each
+ * NON-basic.  The column, its reduced cost, cost and flag go; the columns behind it (cut slacks and later added columns) close up in
+ * order.  relp_nr_columns drops by count, no row moves.
+ * The flush: both calls first settle and flush the open update block exactly as relp_flush does (a removed row that is pending
+ * would leave the block without its row), so relp_tab_flush_stats may move; relp_reinversions, relp_retab_stats and the trace do
+ * not.  Trace entries recorded before the call keep the row and column indices of their time.
+ * The bit contract: after the call every surviving entry of the tableau -- every column over the surviving rows, d over the
+ * surviving columns, b over the surviving rows, -obj, the flags and the costs -- has exactly the bits it has on a handle that went
+ * through the same calls and called relp_flush instead; relp_get_minus_pi loses entry i and keeps the other bits.  The PRICE partials
+ * are invalid and the record is re-armed; relp_run and relp_run_dual may follow.  The call synchronises.  Every later rebuild
+ * (re-inversion interval, auto_reinversion, relp_from_basis, relp_set_right_hand_side) works on the smaller LP.
+ * Refusals leave the handle untouched and do not flush.  RELP_E_ARG: count < 0, a missing array, an index that is no cut row (no
+ * added column), an index named twice.  RELP_E_STATE: a cut whose slack is not basic (a tight cut: relax it, or pivot), an added
+ * column that is basic, phase 1.  RELP_E_UNSUPPORTED: another or a sharded engine.  count == 0 is a no-op (no flush either). */
+relp_status_t relp_remove_cuts(relp_engine_t *h, const int32_t *rows, int32_t count);
+relp_status_t relp_remove_columns(relp_engine_t *h, const int32_t *columns, int32_t count);
+/* out4 = { cuts removed so far, added columns removed so far, (stored column x row) entries of the tableau the last removal moved
+ * (rows: every stored column from the first removed tableau row down; columns: every row of the columns behind the first removed
+ * one), pending rows p of the update block the last removal flushed }.  Refused calls and calls with count == 0 are not counted. */
+relp_status_t relp_removal_stats(const relp_engine_t *h, int64_t *out4);
 /* Batched ratio tests over the tableau as it stands (no counterpart in the reference): what a branch-and-bound driver asks at a
  * node ("which fractional row is the dearest to branch on?") and a solve asks at its end (the ranging report).  Both are read-only:
  * nothing is flushed or re-tabulated, and T0, R0, W, d, b, the basis, the flags, the PRICE partials, the record, the trace and

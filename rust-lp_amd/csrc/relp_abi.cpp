@@ -108,6 +108,9 @@ relp_status_t relp_add_columns(relp_engine_t* h, int32_t count, const int64_t* c
 }
 relp_status_t relp_reserve_columns(relp_engine_t* h, int32_t columns) { return h ? H(h).reserve_columns(columns) : RELP_E_ARG; }
 relp_status_t relp_column_stats(const relp_engine_t* h, int64_t* out4) { return (h && out4) ? H(h).column_stats(out4) : RELP_E_ARG; }
+relp_status_t relp_remove_cuts(relp_engine_t* h, const int32_t* rows, int32_t count) { return h ? H(h).remove_cuts(rows, count) : RELP_E_ARG; }
+relp_status_t relp_remove_columns(relp_engine_t* h, const int32_t* columns, int32_t count) { return h ? H(h).remove_columns(columns, count) : RELP_E_ARG; }
+relp_status_t relp_removal_stats(const relp_engine_t* h, int64_t* out4) { return (h && out4) ? H(h).removal_stats(out4) : RELP_E_ARG; }
 relp_status_t relp_row_ratios(relp_engine_t* h, const int32_t* rows, int32_t count, double* down_ratio, int32_t* down_column,
                               double* up_ratio, int32_t* up_column) {
     return h ? H(h).row_ratios(rows, count, down_ratio, down_column, up_ratio, up_column) : RELP_E_ARG;

@@ -1539,6 +1539,172 @@ relp_status_t Engine::column_stats(int64_t* out4) const {
     return RELP_OK;
 }
 
+// Cut rows and added columns taken back: exact deletions, no arithmetic.  A cut whose slack is basic takes with it the tableau row
+// the slack is basic in (basis position r, not necessarily the cut's own row i) and the slack's column: in the basis without them
+// every other entry of the tableau keeps its value, because column s is e_r and no other basic column has an entry in row r.  A
+// non-basic column is simply gone.  What moves: everything indexed by constraint loses i, everything indexed by basis position
+// loses r, everything indexed by stored column loses s; survivors close up in order (launch_tab_compact for the images, the host
+// for the small vectors: copies, nothing is recomputed).  The callers have validated, settled and flushed: p = 0, T = T0.
+//   rows_t / rows_c: the basis positions and the constraints that go (ascending each, the same number); cols_p: the provider columns
+//   that go (ascending); basis: the downloaded basis.
+relp_status_t Engine::compact_tableau(const std::vector<int32_t>& rows_t, const std::vector<int32_t>& rows_c, const std::vector<int32_t>& cols_p,
+                                      const std::vector<int32_t>& basis) {
+    const int32_t m_old = lay_.m, n_old = n_store_, nr = (int32_t)rows_t.size(), nc = (int32_t)cols_p.size();
+    const int32_t m_new = m_old - nr, n_new = n_old - nc, cuts_old = lay_.nr_cuts, added_old = lay_.nr_added;
+    // the lists, one upload: [basis positions | constraints | stored columns | cut rows of A | added columns]
+    std::vector<int32_t> lists;
+    lists.insert(lists.end(), rows_t.begin(), rows_t.end());
+    lists.insert(lists.end(), rows_c.begin(), rows_c.end());
+    for (int32_t p : cols_p) lists.push_back(tab_na_ + p);
+    for (int32_t i : rows_c) lists.push_back(lay_.mc + (i - lay_.cut_row0));
+    int32_t na = 0;
+    for (int32_t p : cols_p)
+        if (lay_.added_of(p) >= 0) { lists.push_back(lay_.added_of(p)); ++na; }
+    HIP_TRY(d_rm_lists_.ensure((int64_t)lists.size(), 256));
+    const int32_t* l_rows_t = d_rm_lists_;
+    const int32_t* l_rows_c = l_rows_t + nr;
+    const int32_t* l_cols_s = l_rows_c + nr;
+    const int32_t* l_rows_a = l_cols_s + nc;
+    const int32_t* l_cols_a = l_rows_a + nr;
+
+    // the small vectors on the host: d, b, the flags (by tableau column), the stored costs, idcol, the basis
+    std::vector<double> b(m_old), d(n_old);
+    std::vector<uint8_t> flags(n_old - tab_na_);
+    hipError_t e = d_b_.download(b, enqueue_only(stream_));
+    e = first_error(e, d_d_.download(d, enqueue_only(stream_)));
+    HIP_TRY(first_error(e, d_in_basis_.download(flags, stream_)));
+    std::vector<int32_t> col_map(n_old - tab_na_ + 1, 0);          // provider column -> its new index (a removed one: its successor's)
+    {
+        size_t f = 0;
+        for (int32_t p = 0, out = 0; p <= n_old - tab_na_; ++p) {
+            col_map[p] = out;
+            if (f < cols_p.size() && cols_p[f] == p) ++f; else ++out;
+        }
+    }
+    auto drop = [](auto& v, const std::vector<int32_t>& gone, int32_t offset) {      // v without the entries gone[k] + offset, padded with zeros
+        size_t f = 0, o = 0;
+        for (size_t x = 0; x < v.size(); ++x) {
+            if (f < gone.size() && (size_t)(gone[f] + offset) == x) { ++f; continue; }
+            v[o++] = v[x];
+        }
+        std::fill(v.begin() + o, v.end(), 0);
+    };
+    std::vector<int32_t> basis_new(basis);
+    drop(b, rows_t, 0); drop(basis_new, rows_t, 0);
+    for (int32_t r = 0; r < m_new; ++r)
+        if (basis_new[r] >= 0 && basis_new[r] < n_old - tab_na_) basis_new[r] = col_map[basis_new[r]];      // (a wrapped artificial keeps its index)
+    drop(d, cols_p, tab_na_); drop(cost_store_h_, cols_p, tab_na_); drop(flags, cols_p, 0);
+    drop(idcol_h_, rows_c, 0);
+    for (int32_t i = 0; i < m_new; ++i)
+        if (idcol_h_[i] >= tab_na_) idcol_h_[i] = tab_na_ + col_map[idcol_h_[i] - tab_na_];
+
+    // everything under one wait (no return before it: the host arrays are in flight).  The host mirrors above are already those of
+    // the smaller tableau: a HIP error from here on leaves the handle unusable, like a failed launch of a pivot
+    e = d_rm_lists_.upload(lists, enqueue_only(stream_));
+    if (e == hipSuccess) {
+        launch_tab_compact(dT0_, ld_t_, m_old, n_old, l_rows_t, nr, l_cols_s, nc, 0, stream_);
+        launch_tab_compact(d_W_, ld_b_, m_old, block_, l_rows_t, nr, nullptr, 0, 0, stream_);
+        // R0 and its compacted copy hold a stored column per "row" of their images
+        launch_tab_compact(dR0_, ld_r_, n_old, block_ + 1, l_cols_s, nc, nullptr, 0, 0, stream_);
+        if (d_R0c_) launch_tab_compact(d_R0c_, ld_r_, n_old, block_, l_cols_s, nc, nullptr, 0, 0, stream_);
+        // the cut rows of the device matrix (an owned copy since the first room for cuts) and the added columns in row space
+        if (nr > 0 && dA_.owned()) launch_tab_compact(dA_, ld_a_, lay_.mc + cuts_old, lay_.nr_normal, l_rows_a, nr, nullptr, 0, 0, stream_);
+        if (added_old > 0) launch_tab_compact(d_col_a_, ld_c_, m_old, added_old, l_rows_c, nr, l_cols_a, na, 0, stream_);
+    }
+    e = first_error(e, d_b_.upload(b, enqueue_only(stream_)));
+    e = first_error(e, d_basis_.upload(basis_new, enqueue_only(stream_)));
+    e = first_error(e, d_d_.upload(d, enqueue_only(stream_)));
+    e = first_error(e, d_cost_store_.upload(cost_store_h_, enqueue_only(stream_)));
+    e = first_error(e, d_in_basis_.upload(flags, enqueue_only(stream_)));
+    e = first_error(e, d_idcol_.upload(idcol_h_, enqueue_only(stream_)));
+    e = first_error(e, d_pos_of_row_.fill_bytes(0xFF, m_old, enqueue_only(stream_)));              // (the flush left no pending row)
+    // the tails of the other m-vectors are zero for the 16-byte loads
+    for (DeviceBuf<double>* v : {&d_alpha_, &d_aq_, &d_rho_, &d_minus_pi_, &d_w_, &d_v_, &d_b_alt_})
+        if (*v && nr > 0) e = first_error(e, fill_bytes_at(*v + m_new, 0, sizeof(double) * (size_t)nr, enqueue_only(stream_)));
+    HIP_TRY(first_error(e, hipStreamSynchronize(stream_)));
+    if (hipGetLastError() != hipSuccess) return fail(RELP_E_HIP, "removing rows or columns of the tableau: a kernel launch failed");
+    idcol_h_.resize(m_new); cost_store_h_.resize(n_new);
+    for (int32_t& j : barred_) j = (j >= 0 && j < n_old - tab_na_) ? col_map[j] : j;
+    n_store_ = n_new; n_alloc_ -= nc; lay_.sc_hi -= nc;
+    tab_partials_valid_ = false;
+    rm_last_moved_ = (nr > 0 ? (int64_t)(m_old - rows_t.front()) * n_old : 0) +
+                     (nc > 0 ? (int64_t)m_new * (n_old - (tab_na_ + cols_p.front())) : 0);
+    return RELP_OK;
+}
+
+// The shared front of the two removals: the flush of the open block exactly as relp_flush does it (a removed row that is pending
+// would leave R0 = S' T0 without its row), p of that block for the stats.
+relp_status_t Engine::flush_for_removal() {
+    tab_settle();
+    relp_status_t st = download_rec();
+    if (st) return st;
+    rm_last_p_ = h_rec_->n_eta;
+    return flush();
+}
+
+relp_status_t Engine::remove_cuts(const int32_t* rows, int32_t count) {
+    relp_status_t st = dual_ready("relp_remove_cuts");
+    if (st) return st;
+    if (count < 0 || (count > 0 && !rows)) return lay_.check_remove_cuts(rows, count, {}, &err_);
+    if (count == 0) return RELP_OK;
+    tab_settle();
+    std::vector<int32_t> basis(lay_.m);
+    HIP_TRY(d_basis_.download(basis, stream_));
+    if ((st = lay_.check_remove_cuts(rows, count, basis, &err_))) return st;
+    if ((st = flush_for_removal())) return st;
+
+    const std::vector<int32_t> slack = lay_.cut_slacks();
+    std::vector<int32_t> row_of(lay_.n_provider, -1);              // provider column -> its basis position
+    for (int32_t r = 0; r < lay_.m; ++r)
+        if (basis[r] >= 0 && basis[r] < lay_.n_provider) row_of[basis[r]] = r;
+    std::vector<int32_t> rows_t, rows_c(rows, rows + count), cols_p;
+    for (int32_t i : rows_c) {
+        const int32_t s = lay_.nr_normal + slack[i - lay_.cut_row0];
+        cols_p.push_back(s);
+        rows_t.push_back(row_of[s]);
+    }
+    std::sort(rows_t.begin(), rows_t.end()); std::sort(rows_c.begin(), rows_c.end()); std::sort(cols_p.begin(), cols_p.end());
+    if ((st = compact_tableau(rows_t, rows_c, cols_p, basis))) return st;
+    // the layout follows (check_remove_cuts passed: remove_cuts cannot fail), then its tables on the device
+    (void)lay_.remove_cuts(rows, count, basis, &err_);
+    rm_cuts_ += count;
+    return finish_removal();
+}
+
+relp_status_t Engine::remove_columns(const int32_t* columns, int32_t count) {
+    relp_status_t st = dual_ready("relp_remove_columns");
+    if (st) return st;
+    if (count < 0 || (count > 0 && !columns)) return lay_.check_remove_columns(columns, count, {}, &err_);
+    if (count == 0) return RELP_OK;
+    tab_settle();
+    std::vector<int32_t> basis(lay_.m);
+    HIP_TRY(d_basis_.download(basis, stream_));
+    if ((st = lay_.check_remove_columns(columns, count, basis, &err_))) return st;
+    if ((st = flush_for_removal())) return st;
+    std::vector<int32_t> cols_p(columns, columns + count);
+    std::sort(cols_p.begin(), cols_p.end());
+    if ((st = compact_tableau({}, {}, cols_p, basis))) return st;
+    (void)lay_.remove_columns(columns, count, basis, &err_);
+    rm_columns_ += count;
+    return finish_removal();
+}
+
+// the descriptors of the virtual columns as the layout has them now, and the record re-armed (a remembered column moves with the
+// columns; the trace keeps the indices of its time)
+relp_status_t Engine::finish_removal() {
+    hipError_t e = d_vrow0_.upload(lay_.vrow0.data(), lay_.nr_virtual, enqueue_only(stream_));
+    e = first_error(e, d_vrow1_.upload(lay_.vrow1.data(), lay_.nr_virtual, enqueue_only(stream_)));
+    HIP_TRY(first_error(e, d_vsign_.upload(lay_.vsign.data(), lay_.nr_virtual, stream_)));
+    return edit_rec([&](PivotRecord& r) { if (r.last_selected >= nr_columns()) r.last_selected = -1; });
+}
+
+relp_status_t Engine::removal_stats(int64_t* out4) const {
+    if (!tableau_ || cfg_.shard_count > 1) return RELP_E_UNSUPPORTED;
+    if (phase_ != 2) return RELP_E_STATE;
+    out4[0] = rm_cuts_; out4[1] = rm_columns_; out4[2] = rm_last_moved_; out4[3] = rm_last_p_;
+    return RELP_OK;
+}
+
 // The two batched ratio queries.  Both read the tableau as it stands -- T0, and W R0 over the p pending rows of an open block -- and
 // write to scratch of their own: d, b, the basis, the flags, W, R0, T0, the PRICE partials and the record stay as they are (the
 // record is downloaded for p, never uploaded).  Settles the fused update's shadow row first, does not flush.

@@ -146,6 +146,11 @@ class Engine : private EngineQueue {
     relp_status_t add_columns(int32_t count, const int64_t* col_ptr, const int32_t* row_idx, const double* values, const double* cost);
     relp_status_t reserve_columns(int32_t columns);
     relp_status_t column_stats(int64_t* out4) const;
+    // the way back: cut rows whose slack is basic and non-basic added columns leave the tableau in place (a flush, then an
+    // order-preserving compaction: no arithmetic, no re-tabulation, nothing re-allocated); relp_run / relp_run_dual continue
+    relp_status_t remove_cuts(const int32_t* rows, int32_t count);
+    relp_status_t remove_columns(const int32_t* columns, int32_t count);
+    relp_status_t removal_stats(int64_t* out4) const;
     // batched ratio tests over the tableau as it stands, read-only: rows of T against d (penalties, cost ranges), identity columns
     // against b (rhs ranges)
     relp_status_t row_ratios(const int32_t* rows, int32_t count, double* down_ratio, int32_t* down_column, double* up_ratio,
@@ -335,6 +340,15 @@ class Engine : private EngineQueue {
     DeviceBuf<int32_t> d_col_cols_;
     DeviceBuf<double> d_col_coef_, d_col_d_, d_col_cost_;
     int32_t col_last_cols_ = 0, col_last_p_ = 0;
+    // relp_remove_cuts / relp_remove_columns: the lists of a call on the device (relp_kernels.h: launch_tab_compact), grown on demand;
+    // what relp_removal_stats reports.  The rooms stay: the next add reuses what a removal freed.
+    DeviceBuf<int32_t> d_rm_lists_;
+    int64_t rm_cuts_ = 0, rm_columns_ = 0, rm_last_moved_ = 0;
+    int32_t rm_last_p_ = 0;
+    relp_status_t flush_for_removal();
+    relp_status_t compact_tableau(const std::vector<int32_t>& rows_t, const std::vector<int32_t>& rows_c, const std::vector<int32_t>& cols_p,
+                                  const std::vector<int32_t>& basis);
+    relp_status_t finish_removal();
     // relp_row_ratios / relp_rhs_ranging: the uploaded list (rows, or their identity columns), the per-(direction, entry, block)
     // minima and the results [direction][entry] (relp_kernels.h: launch_tab_row_ratios, launch_tab_rhs_ranging); allocated at the
     // first query, grown on demand; what relp_ranging_stats reports

@@ -583,6 +583,22 @@ static constexpr int32_t kTabColTile = 8;              // new columns per workgr
 // No atomics, fixed summation orders: the same call on the same state gives the same bits.
 void launch_tab_add_columns(const TableauView& tv, const DeferredUpdate& du, const ColumnAdd& ca, int32_t p, const ColumnTail& ct,
                             hipStream_t s);
+// Rows and columns taken out of a column-major image in place, order preserved (relp_remove_cuts, relp_remove_columns): img holds m
+// rows and n columns, column c at c * ld; rows (nr, ascending, distinct, inside [0, m)) and cols (nc, ascending, distinct, inside
+// [0, n)) are device lists.  Afterwards the m - nr surviving rows of the n - nc surviving columns stand in rows [0, m - nr) of columns
+// [0, n - nc) in their old order with their old bits, and rows [m - nr, m) of every column and rows [0, m) of columns [n - nc, n) are
+// 0.0 (what room rows and room columns hold); rows from m on and columns from n on are not touched, nor are the rows above rows[0]
+// in the columns left of cols[0].  Copies only: nothing is recomputed.
+// [k_tab_drop_rows<B>, if nr > 0: a workgroup owns whole columns (grid min(n, kTabCompactGrid), columns strided over it) and walks
+// them from rows[0] down in chunks of 256 B destination rows -- B coalesced loads per thread, their wait, __syncthreads(), B coalesced
+// stores; chunk k stores only below where chunk k + 1 loads] -> [k_tab_drop_columns<B>, if nc > 0: one row per thread over the
+// m - nr rows, 64 threads per workgroup, destination columns ascending from cols[0], B loads before their B stores; sources lie
+// right of everything the thread has written].  B = kTabCompactB; batch == 1: B = 1, one by one (the control).  No atomics, no
+// flags, no communication between workgroups; the result does not depend on the order in which workgroups run.
+static constexpr int32_t kTabCompactB = 4;
+static constexpr int32_t kTabCompactGrid = 2048;        // 256 CUs x 8 workgroups of 256 threads
+void launch_tab_compact(double* img, int64_t ld, int32_t m, int32_t n, const int32_t* rows, int32_t nr, const int32_t* cols, int32_t nc,
+                        int32_t batch, hipStream_t s);
 // Batched ratio tests over the tableau as it stands, T = T0 + W R0 over the p pending rows, read-only (relp_row_ratios,
 // relp_rhs_ranging).  The list is taken kTabRatioChunk entries per workgroup (a fixed size, not a rule: eight rows of one column are
 // one 64-byte sector of T0), grid = chunks x blocks of 256 columns (rows); the second launch has one workgroup per list entry.

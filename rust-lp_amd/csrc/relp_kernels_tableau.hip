@@ -1362,6 +1362,82 @@ __global__ void k_tab_col_tail(TableauView tv, DeferredUpdate du, ColumnAdd ca, 
 }
 
 // ------------------------------------------------------------------------------------------------
+// Rows and columns taken out of a column-major image in place (relp_remove_cuts, relp_remove_columns): an order-preserving
+// compaction, copies only.  No second image, no atomics, no flags, no communication between workgroups: every element is read before
+// it is overwritten by the workgroup (rows) or the thread (columns) that overwrites it, so the order in which workgroups run does
+// not matter.
+// ------------------------------------------------------------------------------------------------
+// Columns c = blockIdx.x, blockIdx.x + gridDim.x, ... belong to this workgroup alone.  Destination rows from the first removed row
+// rows[0] on, in chunks of 256 B: thread t owns the rows base + x * 256 + t (x < B; consecutive threads, consecutive rows).  The
+// source of destination row dst is dst + #{k : rows[k] - k <= dst} >= dst (rows[k] - k ascends: an upper bound by bisection), the
+// same in every column, so a chunk's B sources are found once and serve all the workgroup's columns.  Per (chunk, column): B loads,
+// the wait for them, __syncthreads(), B stores.  Within a chunk every load precedes every store; chunk k stores below base + 256 B,
+// chunk k + 1 loads at or above it.  Destination rows [m - nr, m) get 0.0, the value of the room rows; rows above rows[0] are not
+// touched.
+template <int B>
+__global__ __launch_bounds__(kThreads) void k_tab_drop_rows(double* img, int64_t ld, int m, int n, const int32_t* __restrict__ rows,
+                                                            int nr) {
+    const int m_new = m - nr;
+    for (int base = rows[0]; base < m; base += kThreads * B) {
+        int src[B];
+#pragma unroll
+        for (int x = 0; x < B; ++x) {
+            const int dst = base + x * kThreads + (int)threadIdx.x;
+            int lo = 0, hi = nr;
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (rows[mid] - mid <= dst) lo = mid + 1; else hi = mid;
+            }
+            src[x] = dst < m_new ? dst + lo : -1;
+        }
+        for (int c = blockIdx.x; c < n; c += gridDim.x) {
+            double* col = img + (int64_t)c * ld;
+            double t[B];
+#pragma unroll
+            for (int x = 0; x < B; ++x) t[x] = src[x] >= 0 ? col[src[x]] : 0.0;
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // the loads have returned before any thread of the chunk stores
+            __syncthreads();
+#pragma unroll
+            for (int x = 0; x < B; ++x) {
+                const int dst = base + x * kThreads + (int)threadIdx.x;
+                if (dst < m) col[dst] = t[x];
+            }
+        }
+    }
+}
+
+// Row i = blockIdx.x * 64 + threadIdx.x of the image belongs to this thread alone (consecutive threads, consecutive rows of one
+// column: the access pattern of k_tab_col_apply; 64 threads per workgroup so that 10,000 rows are 157 workgroups).  Destination
+// columns ascending from the first removed column cols[0], B at a time: the B loads, then the B stores.  The source of dst is
+// dst + #{removed columns <= source}, found by walking the list along (the same in every thread: scalar work); it lies at or right
+// of dst, and right of every column the thread has written.  Destination columns [n - nc, n) get 0.0; columns left of cols[0] are
+// not touched.
+template <int B>
+__global__ __launch_bounds__(64) void k_tab_drop_columns(double* img, int64_t ld, int m, int n, const int32_t* __restrict__ cols,
+                                                         int nc) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= m) return;
+    const int n_new = n - nc;
+    double* row = img + i;
+    int k = 0;                                         // removed columns left of the next source
+    for (int dst = cols[0]; dst < n; dst += B) {
+        double t[B];
+#pragma unroll
+        for (int x = 0; x < B; ++x) {
+            t[x] = 0.0;
+            if (dst + x < n_new) {
+                int src = dst + x + k;
+                while (k < nc && cols[k] <= src) { ++k; ++src; }
+                t[x] = row[(int64_t)src * ld];
+            }
+        }
+#pragma unroll
+        for (int x = 0; x < B; ++x)
+            if (dst + x < n) row[(int64_t)(dst + x) * ld] = t[x];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Batched ratio tests over the tableau as it stands (relp_row_ratios, relp_rhs_ranging): read-only streams over T0 (+ W R0 while
 // an update block is open, p = its pending rows).  Two launches each: [the minimum of every (list entry, block of 256 columns or
 // rows) into scratch] -> [one workgroup per list entry: the minimum of its blocks, then the tie band from the blocks whose own
@@ -1851,6 +1927,24 @@ void launch_tab_add_columns(const TableauView& tv, const DeferredUpdate& du, con
         });
     const int64_t total = (int64_t)(ct.r0_rows + 1) * ca.count;
     hipLaunchKernelGGL(k_tab_col_tail, dim3(element_blocks(total)), dim3(256), 0, s, tv, du, ca, ct, (int)p);
+}
+
+void launch_tab_compact(double* img, int64_t ld, int32_t m, int32_t n, const int32_t* rows, int32_t nr, const int32_t* cols, int32_t nc,
+                        int32_t batch, hipStream_t s) {
+    if (m < 1 || n < 1 || nr < 0 || nc < 0 || nr > m || nc > n) return;
+    auto with_batch = [&](auto&& launch) {
+        if (batch == 1) launch(std::integral_constant<int, 1>{}); else launch(std::integral_constant<int, kTabCompactB>{});
+    };
+    if (nr > 0)                                        // (all n columns: the vacated rows of a column that goes are cleared too)
+        with_batch([&](auto B) {
+            hipLaunchKernelGGL((k_tab_drop_rows<decltype(B)::value>), dim3(std::min(n, kTabCompactGrid)), dim3(kThreads), 0, s, img, ld, (int)m, (int)n,
+                               rows, (int)nr);
+        });
+    if (nc > 0 && m - nr > 0)
+        with_batch([&](auto B) {
+            hipLaunchKernelGGL((k_tab_drop_columns<decltype(B)::value>), dim3(cdiv(m - nr, 64)), dim3(64), 0, s, img, ld, (int)(m - nr), (int)n, cols,
+                               (int)nc);
+        });
 }
 
 void launch_tab_row_ratios(const TableauView& tv, const DeferredUpdate& du, const SelectPartials& sp, Tolerances tol,

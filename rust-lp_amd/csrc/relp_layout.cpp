@@ -234,4 +234,119 @@ relp_status_t Layout::add_columns(int32_t count, const int64_t* col_ptr, const i
     return RELP_OK;
 }
 
+std::vector<int32_t> Layout::cut_slacks() const {
+    std::vector<int32_t> slack(nr_cuts, -1);
+    if (nr_cuts > 0)
+        for (int32_t v = 0; v < nr_virtual; ++v)
+            if (vrow0[v] >= cut_row0) slack[vrow0[v] - cut_row0] = v;       // (every row from cut_row0 on is a cut row)
+    return slack;
+}
+
+relp_status_t Layout::check_remove_cuts(const int32_t* rows, int32_t count, const std::vector<int32_t>& basis_now, std::string* err) const {
+    if (count < 0) return fail(err, RELP_E_ARG, "relp_remove_cuts: count < 0");
+    if (count == 0) return RELP_OK;
+    if (!rows) return fail(err, RELP_E_ARG, "relp_remove_cuts: rows missing");
+    std::vector<uint8_t> named(nr_cuts, 0);
+    for (int32_t x = 0; x < count; ++x) {
+        if (nr_cuts == 0 || rows[x] < cut_row0 || rows[x] >= cut_row0 + nr_cuts) return fail(err, RELP_E_ARG, "relp_remove_cuts: not a cut row");
+        if (named[rows[x] - cut_row0]) return fail(err, RELP_E_ARG, "relp_remove_cuts: a row named twice");
+        named[rows[x] - cut_row0] = 1;
+    }
+    if (nr_artificial > 0) return fail(err, RELP_E_STATE, "relp_remove_cuts: phase 1");
+    std::vector<uint8_t> basic(nr_virtual, 0);
+    for (int32_t j : basis_now)
+        if (j >= nr_normal && j < n_provider) basic[j - nr_normal] = 1;
+    const std::vector<int32_t> slack = cut_slacks();
+    for (int32_t k = 0; k < nr_cuts; ++k)
+        if (named[k] && (slack[k] < 0 || !basic[slack[k]]))
+            return fail(err, RELP_E_STATE, "relp_remove_cuts: the slack of a cut is not basic (the cut is tight: pivot its slack in, or relax it)");
+    return RELP_OK;
+}
+
+relp_status_t Layout::check_remove_columns(const int32_t* columns, int32_t count, const std::vector<int32_t>& basis_now, std::string* err) const {
+    if (count < 0) return fail(err, RELP_E_ARG, "relp_remove_columns: count < 0");
+    if (count == 0) return RELP_OK;
+    if (!columns) return fail(err, RELP_E_ARG, "relp_remove_columns: columns missing");
+    std::vector<uint8_t> named(nr_added, 0);
+    for (int32_t x = 0; x < count; ++x) {
+        const int32_t a = added_of(columns[x]);
+        if (a < 0) return fail(err, RELP_E_ARG, "relp_remove_columns: not a column added by relp_add_columns");
+        if (named[a]) return fail(err, RELP_E_ARG, "relp_remove_columns: a column named twice");
+        named[a] = 1;
+    }
+    if (nr_artificial > 0) return fail(err, RELP_E_STATE, "relp_remove_columns: phase 1");
+    for (int32_t j : basis_now) {
+        const int32_t a = added_of(j);
+        if (a >= 0 && named[a]) return fail(err, RELP_E_STATE, "relp_remove_columns: a column that is basic");
+    }
+    return RELP_OK;
+}
+
+void Layout::drop_virtuals(const std::vector<uint8_t>& gone_v, const std::vector<uint8_t>& gone_a) {
+    std::vector<int32_t> a_map(nr_added, -1);
+    int32_t kept_a = 0;
+    for (int32_t a = 0; a < nr_added; ++a) {
+        if (gone_a[a]) continue;
+        if (kept_a != a) { added_entries[kept_a] = std::move(added_entries[a]); added_cost[kept_a] = added_cost[a]; }
+        a_map[a] = kept_a++;
+    }
+    added_entries.resize(kept_a); added_cost.resize(kept_a); added_virtual.assign(kept_a, -1);
+    const bool slots = nr_added > 0;
+    int32_t kept_v = 0;
+    for (int32_t v = 0; v < nr_virtual; ++v) {
+        if (gone_v[v]) continue;
+        vrow0[kept_v] = vrow0[v]; vrow1[kept_v] = vrow1[v]; vsign[kept_v] = vsign[v];
+        if (slots) {
+            const int32_t a = added_slot[v] >= 0 ? a_map[added_slot[v]] : -1;
+            added_slot[kept_v] = a;
+            if (a >= 0) added_virtual[a] = kept_v;
+        }
+        ++kept_v;
+    }
+    vrow0.resize(kept_v); vrow1.resize(kept_v); vsign.resize(kept_v);
+    if (slots) added_slot.resize(kept_v);
+    n_provider -= nr_virtual - kept_v;
+    nr_virtual = kept_v; nr_added = kept_a;
+}
+
+relp_status_t Layout::remove_cuts(const int32_t* rows, int32_t count, const std::vector<int32_t>& basis_now, std::string* err) {
+    const relp_status_t st = check_remove_cuts(rows, count, basis_now, err);
+    if (st || count == 0) return st;
+    const std::vector<int32_t> slack = cut_slacks();
+    std::vector<int32_t> cut_map(nr_cuts, 0);          // cut -> its new number, -1 = removed
+    std::vector<uint8_t> gone_v(nr_virtual, 0);
+    for (int32_t x = 0; x < count; ++x) { cut_map[rows[x] - cut_row0] = -1; gone_v[slack[rows[x] - cut_row0]] = 1; }
+    int32_t kept = 0;
+    for (int32_t k = 0; k < nr_cuts; ++k)
+        if (cut_map[k] >= 0) { cut_map[k] = kept; rhs[cut_row0 + kept] = rhs[cut_row0 + k]; ++kept; }
+    rhs.resize(cut_row0 + kept);
+    auto keep_entries = [&](std::vector<std::pair<int32_t, double>>& entries, int32_t first) {       // first: the index of cut 0 in `entries`
+        size_t o = 0;
+        for (const auto& e : entries) {
+            if (e.first < first) { entries[o++] = e; continue; }
+            if (cut_map[e.first - first] >= 0) entries[o++] = {first + cut_map[e.first - first], e.second};
+        }
+        entries.resize(o);
+    };
+    for (auto& entries : cut_entries) keep_entries(entries, 0);
+    for (auto& entries : added_entries) keep_entries(entries, cut_row0);
+    for (int32_t v = 0; v < nr_virtual; ++v)
+        if (!gone_v[v] && vrow0[v] >= cut_row0) vrow0[v] = cut_row0 + cut_map[vrow0[v] - cut_row0];
+    drop_virtuals(gone_v, std::vector<uint8_t>(nr_added, 0));
+    nr_cuts = kept; m = cut_row0 + kept;
+    row_lo = 0; row_hi = m;
+    row_stride = (int32_t)round_up_even(m);
+    candidate_len = candidate_len_for(m);
+    return RELP_OK;
+}
+
+relp_status_t Layout::remove_columns(const int32_t* columns, int32_t count, const std::vector<int32_t>& basis_now, std::string* err) {
+    const relp_status_t st = check_remove_columns(columns, count, basis_now, err);
+    if (st || count == 0) return st;
+    std::vector<uint8_t> gone_v(nr_virtual, 0), gone_a(nr_added, 0);
+    for (int32_t x = 0; x < count; ++x) { gone_v[columns[x] - nr_normal] = 1; gone_a[added_of(columns[x])] = 1; }
+    drop_virtuals(gone_v, gone_a);
+    return RELP_OK;
+}
+
 }  // namespace relp

@@ -39,7 +39,8 @@ struct Layout {
     std::vector<int32_t> vrow0, vrow1, vsign; // per virtual column: its row (-1: removed), the second row or -1, the sign
     int32_t engine = RELP_ENGINE_AUTO;        // relp_engine_kind_t, AUTO resolved
     // cut rows added behind every other row (relp_add_cuts): cut k is row cut_row0 + k, its slack the k-th virtual column behind
-    // the ones of build(); cut_row0 is fixed at the first add (rows are only removed at the phase switch, before any cut)
+    // the ones of build() that is no added column; cut_row0 is fixed at the first add: the phase switch removes rows before any cut,
+    // and relp_remove_cuts removes cut rows only (the cuts behind a removed one move down a number, cut_row0 stays)
     int32_t nr_cuts = 0, cut_row0 = 0;
     std::vector<std::vector<std::pair<int32_t, double>>> cut_entries;   // per structural column: (cut, coefficient != 0), ascending by cut
     // columns added behind every other column (relp_add_columns): the a-th added column is the virtual column added_virtual[a] with
@@ -90,6 +91,22 @@ struct Layout {
                                 std::string* err) const;
     relp_status_t add_columns(int32_t count, const int64_t* col_ptr, const int32_t* row_idx, const double* values, const double* col_cost,
                               std::string* err);
+    // Cut rows taken back (relp_remove_cuts): `rows` are engine rows in [cut_row0, cut_row0 + nr_cuts), each once, each with its slack
+    // in `basis` (the current basis as tableau columns, one per row).  The constraint goes from rhs, cut_entries and the entries the
+    // added columns hold in it, its slack from the virtual columns; both index spaces close up in order: cut numbers, the vrow0 of
+    // later slacks and the rows of added_entries move down, added_virtual / added_slot are renumbered, m, nr_cuts, nr_virtual and
+    // n_provider drop by count.  After it for_each_entry yields the LP without the cuts.  check_remove_cuts decides RELP_E_ARG
+    // (count < 0, a missing array, not a cut row, named twice) and RELP_E_STATE (phase 1; a slack that is not basic) alone;
+    // remove_cuts runs it first and touches nothing when it fails.
+    relp_status_t check_remove_cuts(const int32_t* rows, int32_t count, const std::vector<int32_t>& basis, std::string* err) const;
+    relp_status_t remove_cuts(const int32_t* rows, int32_t count, const std::vector<int32_t>& basis, std::string* err);
+    // Added columns taken back (relp_remove_columns): `columns` are provider columns added by add_columns, each once, none in
+    // `basis`.  The virtual column, its entries and its cost go; the virtual columns behind it (cut slacks included) close up in
+    // order.  The same pair of check and removal as above.
+    relp_status_t check_remove_columns(const int32_t* columns, int32_t count, const std::vector<int32_t>& basis, std::string* err) const;
+    relp_status_t remove_columns(const int32_t* columns, int32_t count, const std::vector<int32_t>& basis, std::string* err);
+    // per cut k the virtual column of its slack (the one whose descriptor names row cut_row0 + k)
+    std::vector<int32_t> cut_slacks() const;
     // the a of provider column p when it is an added column, else -1; the phase-2 cost of provider column p
     int32_t added_of(int32_t p) const { return (nr_added > 0 && p >= nr_normal && p < n_provider) ? added_slot[p - nr_normal] : -1; }
     double cost_of(int32_t p) const {
@@ -139,6 +156,9 @@ struct Layout {
     }
 
   private:
+    // the virtual columns with gone_v set and the added columns with gone_a set leave vrow0 / vrow1 / vsign / added_*; the rest
+    // closes up in order
+    void drop_virtuals(const std::vector<uint8_t>& gone_v, const std::vector<uint8_t>& gone_a);
     void plan_shards(int32_t count, int32_t rank);
     int64_t candidate_len_for(int32_t rows) const;
 };

@@ -106,6 +106,9 @@ _SIGNATURES = {
     "relp_add_columns": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "relp_reserve_columns": (C.c_int, [C.c_void_p, C.c_int32]),
     "relp_column_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "relp_remove_cuts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "relp_remove_columns": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "relp_removal_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "relp_row_ratios": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "relp_rhs_ranging": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "relp_ranging_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
@@ -558,6 +561,30 @@ class Tableau:
         the update block at that call); relp_column_stats."""
         out = (C.c_int64 * 4)()
         self._ck(self._lib.relp_column_stats(self._h, out))
+        return tuple(int(x) for x in out)
+
+    def remove_cuts(self, rows) -> None:
+        """The cut rows ``rows`` (engine row indices, each once, any order) leave the tableau in place, each with its slack, which
+        must be basic -- in whichever tableau row (relp_remove_cuts).  The open update block is flushed first; surviving rows and
+        columns close up in order and keep their bits; the room stays for the next ``add_cuts``."""
+        r = np.ascontiguousarray(np.atleast_1d(rows), dtype=np.int32)
+        if r.ndim != 1:
+            raise ValueError("rows must be one-dimensional")
+        self._ck(self._lib.relp_remove_cuts(self._h, r.ctypes.data, r.shape[0]))
+
+    def remove_columns(self, columns) -> None:
+        """The added columns ``columns`` (provider column indices of columns from ``add_columns``, each once, any order, each
+        non-basic) leave the tableau in place (relp_remove_columns); the columns behind them close up in order."""
+        c = np.ascontiguousarray(np.atleast_1d(columns), dtype=np.int32)
+        if c.ndim != 1:
+            raise ValueError("columns must be one-dimensional")
+        self._ck(self._lib.relp_remove_columns(self._h, c.ctypes.data, c.shape[0]))
+
+    def removal_stats(self) -> Tuple[int, int, int, int]:
+        """(cuts removed so far, added columns removed so far, tableau entries the last removal moved, pending rows of the update
+        block it flushed); relp_removal_stats."""
+        out = (C.c_int64 * 4)()
+        self._ck(self._lib.relp_removal_stats(self._h, out))
         return tuple(int(x) for x in out)
 
     def _ratio_query(self, call, rows):

@@ -8,8 +8,8 @@ columns have the statistics of the LP's own: coefficients (1 + r) / 1000, r < 99
 default_rng(1000 * seed + k); dense (m entries) or sparse (8 entries in random rows).  Timed, host clock around calls that
 synchronise, the CSC prepared by the caller:
   add        relp_add_columns of k = 1, 8, 64 columns, dense and sparse, with the room for every repetition reserved beforehand: two
-             warm-up calls, then the median / min / max of the repetitions.  A column cannot be taken back, so the repetitions stack
-             the same k columns again on the same handle (the basis stays: nothing is run in between); with the update block flushed
+             warm-up calls, then the median / min / max of the repetitions.  The columns stay (scripts/remove_bench.py times taking
+             them back): the repetitions stack the same k columns again on the same handle (the basis stays: nothing is run in between); with the update block flushed
              (p = 0) and open (a second engine taken through exactly the pivots of the first)
   growth     relp_reserve_columns on the tableau as created, and the first relp_add_columns of a handle without room (growth + add);
              a rebuild (relp_set_right_hand_side with the rhs in effect) without and with the k columns present

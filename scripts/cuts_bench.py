@@ -7,8 +7,8 @@ b = n (1000 + r) / 4000, c = -(1000 + r) / 1000) on the tableau engine at the de
 those of tests/test_gpu_cuts_in_place.py: G = default_rng(1000 * seed + k).integers(0, 8, (k, n)), beta = 0.9 G x*; G >= 0 and
 b >= 0, so x = 0 satisfies every cut and the stacked LP stays feasible for any k.  Timed, host clock around calls that synchronise:
   add        relp_add_cuts of k = 1, 8, 64, 256 cuts with the room for every repetition reserved beforehand: two warm-up calls, then
-             the median / min / max of the repetitions.  A cut cannot be taken back, so the repetitions stack the same k cuts again
-             on the same handle: the basis and the list (the basic structural rows G touches) stay, the tableau is k rows and columns
+             the median / min / max of the repetitions.  The cuts stay (scripts/remove_bench.py times taking them back): the
+             repetitions stack the same k cuts again on the same handle: the basis and the list (the basic structural rows G touches) stay, the tableau is k rows and columns
              longer per call (`rows_first`, `rows_last`); with the update block flushed (p = 0) and open (a second engine taken through
              exactly the pivots of the first, scripts/rhs_bench.py says why)
   growth     relp_reserve_cuts on the tableau as created, for every k: one call each on a fresh room (the re-allocation and the
