@@ -930,6 +930,41 @@ relp_status_t Engine::dual_ready(const char* what) {
     return RELP_OK;
 }
 
+// The shared front of everything that works in place on the tableau as it stands: the fused update's shadow row settled, the
+// record downloaded, *p = the pending rows of the open block.  Does not flush.
+relp_status_t Engine::settled_pending(int32_t* p) {
+    tab_settle();
+    const relp_status_t st = download_rec();
+    if (st) return st;
+    *p = h_rec_->n_eta;
+    return RELP_OK;
+}
+
+// The four counters of an in-place function's *_stats, behind the guard they share (no error text: a stats query leaves the
+// handle's last error alone).
+relp_status_t Engine::in_place_stats(int64_t* out4, int64_t s0, int64_t s1, int64_t s2, int64_t s3) const {
+    if (!tableau_ || cfg_.shard_count > 1) return RELP_E_UNSUPPORTED;
+    if (phase_ != 2) return RELP_E_STATE;
+    out4[0] = s0; out4[1] = s1; out4[2] = s2; out4[3] = s3;
+    return RELP_OK;
+}
+
+// A named list (index_k, value_k) of a change: the lists are there, every index is in [0, bound) (else `what`: `outside`), none is
+// named twice (`noun`) and every value is finite.
+relp_status_t Engine::check_named_list(const char* what, const int32_t* index, const double* values, int32_t count, int32_t bound,
+                                       const char* noun, const char* outside) {
+    const std::string fn = std::string(what) + ": ";
+    if (count < 0 || (count > 0 && (!index || !values))) return fail(RELP_E_ARG, fn + "count < 0 or a list missing");
+    std::vector<uint8_t> named(bound, 0);
+    for (int32_t k = 0; k < count; ++k) {
+        if (index[k] < 0 || index[k] >= bound) return fail(RELP_E_ARG, fn + outside);
+        if (named[index[k]]) return fail(RELP_E_ARG, fn + "a " + noun + " named twice");
+        if (!std::isfinite(values[k])) return fail(RELP_E_ARG, fn + "a value that is not finite");
+        named[index[k]] = 1;
+    }
+    return RELP_OK;
+}
+
 // One dual pivot: 5 launches.  [block minima of the infeasible b_i] -> [row r of T + partial minima of the dual ratios] ->
 // [entering column + tableau column] -> [alpha_r, b_r, block bookkeeping] -> [the update of the primal loop]
 void Engine::enqueue_iteration_dual() {
@@ -1064,16 +1099,7 @@ relp_status_t Engine::set_right_hand_side(const double* rhs_m) {
 relp_status_t Engine::change_right_hand_side(const int32_t* rows, const double* values, int32_t count) {
     relp_status_t st = dual_ready("relp_change_right_hand_side");
     if (st) return st;
-    if (count < 0 || (count > 0 && (!rows || !values))) return fail(RELP_E_ARG, "relp_change_right_hand_side: count < 0 or a list missing");
-    {
-        std::vector<uint8_t> named(lay_.m, 0);
-        for (int32_t k = 0; k < count; ++k) {
-            if (rows[k] < 0 || rows[k] >= lay_.m) return fail(RELP_E_ARG, "relp_change_right_hand_side: row out of range");
-            if (named[rows[k]]) return fail(RELP_E_ARG, "relp_change_right_hand_side: a row named twice");
-            if (!std::isfinite(values[k])) return fail(RELP_E_ARG, "relp_change_right_hand_side: a value that is not finite");
-            named[rows[k]] = 1;
-        }
-    }
+    if ((st = check_named_list("relp_change_right_hand_side", rows, values, count, lay_.m, "row", "row out of range"))) return st;
     if (count == 0) return RELP_OK;
     std::vector<int32_t> cols;
     std::vector<double> delta;
@@ -1084,9 +1110,8 @@ relp_status_t Engine::change_right_hand_side(const int32_t* rows, const double* 
         delta.push_back(dk);
     }
     const int32_t cnt = (int32_t)cols.size();
-    tab_settle();
-    if ((st = download_rec())) return st;
-    const int32_t p = h_rec_->n_eta;
+    int32_t p;
+    if ((st = settled_pending(&p))) return st;
     h_rec_->outcome = DEV_RUNNING;
     if (cnt > 0) {
         const int32_t splits = tab_rhs_splits(lay_.m, cnt, sw_.tab_rhs_splits);
@@ -1128,12 +1153,7 @@ relp_status_t Engine::get_right_hand_side(double* out_m) {
     return RELP_OK;
 }
 
-relp_status_t Engine::rhs_stats(int64_t* out4) const {
-    if (!tableau_ || cfg_.shard_count > 1) return RELP_E_UNSUPPORTED;
-    if (phase_ != 2) return RELP_E_STATE;
-    out4[0] = rhs_changes_; out4[1] = rhs_columns_; out4[2] = rhs_last_p_; out4[3] = rhs_last_splits_;
-    return RELP_OK;
-}
+relp_status_t Engine::rhs_stats(int64_t* out4) const { return in_place_stats(out4, rhs_changes_, rhs_columns_, rhs_last_p_, rhs_last_splits_); }
 
 // The three copies of lay_.cost[lo, hi) the tableau engine keeps: d_cost_ (ColumnTable), cost_store_h_ (relp_get_minus_pi) and
 // d_cost_store_ (every reprice and re-tabulation), the latter two by storage column.
@@ -1152,20 +1172,10 @@ relp_status_t Engine::store_costs(int32_t lo, int32_t hi) {
 relp_status_t Engine::change_cost(const int32_t* columns, const double* values, int32_t count) {
     relp_status_t st = dual_ready("relp_change_cost");
     if (st) return st;
-    if (count < 0 || (count > 0 && (!columns || !values))) return fail(RELP_E_ARG, "relp_change_cost: count < 0 or a list missing");
-    {
-        std::vector<uint8_t> named(lay_.nr_normal, 0);
-        for (int32_t k = 0; k < count; ++k) {
-            if (columns[k] < 0 || columns[k] >= lay_.nr_normal) return fail(RELP_E_ARG, "relp_change_cost: not a structural column");
-            if (named[columns[k]]) return fail(RELP_E_ARG, "relp_change_cost: a column named twice");
-            if (!std::isfinite(values[k])) return fail(RELP_E_ARG, "relp_change_cost: a value that is not finite");
-            named[columns[k]] = 1;
-        }
-    }
+    if ((st = check_named_list("relp_change_cost", columns, values, count, lay_.nr_normal, "column", "not a structural column"))) return st;
     if (count == 0) return RELP_OK;
-    tab_settle();
-    if ((st = download_rec())) return st;
-    const int32_t p = h_rec_->n_eta;
+    int32_t p;
+    if ((st = settled_pending(&p))) return st;
     h_rec_->outcome = DEV_RUNNING;
     std::vector<int32_t> basis(lay_.m);
     HIP_TRY(d_basis_.download(basis, stream_));
@@ -1243,12 +1253,7 @@ relp_status_t Engine::get_cost(double* out_n) {
     return RELP_OK;
 }
 
-relp_status_t Engine::cost_stats(int64_t* out4) const {
-    if (!tableau_ || cfg_.shard_count > 1) return RELP_E_UNSUPPORTED;
-    if (phase_ != 2) return RELP_E_STATE;
-    out4[0] = cost_changes_; out4[1] = cost_rows_; out4[2] = cost_last_p_; out4[3] = cost_last_splits_;
-    return RELP_OK;
-}
+relp_status_t Engine::cost_stats(int64_t* out4) const { return in_place_stats(out4, cost_changes_, cost_rows_, cost_last_p_, cost_last_splits_); }
 
 // Room for `cut_room` cut rows with their slack columns and for `col_room` added columns in every buffer of the tableau path that
 // create() sizes from the rows or the columns: the only function that grows the tableau engine, for both kinds of room (they are
@@ -1375,9 +1380,8 @@ relp_status_t Engine::add_cuts(int32_t count, const int64_t* row_ptr, const int3
         if (want > INT32_MAX / 2) return fail(RELP_E_ARG, "relp_add_cuts: too many cuts");
         if ((st = grow_for_cuts((int32_t)want))) return st;
     }
-    tab_settle();
-    if ((st = download_rec())) return st;
-    const int32_t p = h_rec_->n_eta;
+    int32_t p;
+    if ((st = settled_pending(&p))) return st;
     const int32_t m_old = lay_.m, cuts_old = lay_.nr_cuts;
     std::vector<double> b(m_old);
     std::vector<int32_t> basis(m_old);
@@ -1441,12 +1445,7 @@ relp_status_t Engine::add_cuts(int32_t count, const int64_t* row_ptr, const int3
     return upload_rec();
 }
 
-relp_status_t Engine::cut_stats(int64_t* out4) const {
-    if (!tableau_ || cfg_.shard_count > 1) return RELP_E_UNSUPPORTED;
-    if (phase_ != 2) return RELP_E_STATE;
-    out4[0] = lay_.nr_cuts; out4[1] = cut_room_; out4[2] = cut_last_rows_; out4[3] = cut_last_p_;
-    return RELP_OK;
-}
+relp_status_t Engine::cut_stats(int64_t* out4) const { return in_place_stats(out4, lay_.nr_cuts, cut_room_, cut_last_rows_, cut_last_p_); }
 
 relp_status_t Engine::reserve_columns(int32_t columns) {
     const relp_status_t st = dual_ready("relp_reserve_columns");
@@ -1473,9 +1472,8 @@ relp_status_t Engine::add_columns(int32_t count, const int64_t* col_ptr, const i
         if (want > INT32_MAX / 2) return fail(RELP_E_ARG, "relp_add_columns: too many columns");
         if ((st = grow_tableau(cut_room_, (int32_t)want))) return st;
     }
-    tab_settle();
-    if ((st = download_rec())) return st;
-    const int32_t p = h_rec_->n_eta;
+    int32_t p;
+    if ((st = settled_pending(&p))) return st;
     const int32_t m = lay_.m, n_old = n_store_, added_old = lay_.nr_added;
     std::vector<double> d(n_old);
     HIP_TRY(d_d_.download(d, stream_));
@@ -1532,12 +1530,7 @@ relp_status_t Engine::add_columns(int32_t count, const int64_t* col_ptr, const i
     return upload_rec();
 }
 
-relp_status_t Engine::column_stats(int64_t* out4) const {
-    if (!tableau_ || cfg_.shard_count > 1) return RELP_E_UNSUPPORTED;
-    if (phase_ != 2) return RELP_E_STATE;
-    out4[0] = lay_.nr_added; out4[1] = col_room_; out4[2] = col_last_cols_; out4[3] = col_last_p_;
-    return RELP_OK;
-}
+relp_status_t Engine::column_stats(int64_t* out4) const { return in_place_stats(out4, lay_.nr_added, col_room_, col_last_cols_, col_last_p_); }
 
 // Cut rows and added columns taken back: exact deletions, no arithmetic.  A cut whose slack is basic takes with it the tableau row
 // the slack is basic in (basis position r, not necessarily the cut's own row i) and the slack's column: in the basis without them
@@ -1635,11 +1628,8 @@ relp_status_t Engine::compact_tableau(const std::vector<int32_t>& rows_t, const 
 // The shared front of the two removals: the flush of the open block exactly as relp_flush does it (a removed row that is pending
 // would leave R0 = S' T0 without its row), p of that block for the stats.
 relp_status_t Engine::flush_for_removal() {
-    tab_settle();
-    relp_status_t st = download_rec();
-    if (st) return st;
-    rm_last_p_ = h_rec_->n_eta;
-    return flush();
+    const relp_status_t st = settled_pending(&rm_last_p_);
+    return st ? st : flush();
 }
 
 relp_status_t Engine::remove_cuts(const int32_t* rows, int32_t count) {
@@ -1698,12 +1688,7 @@ relp_status_t Engine::finish_removal() {
     return edit_rec([&](PivotRecord& r) { if (r.last_selected >= nr_columns()) r.last_selected = -1; });
 }
 
-relp_status_t Engine::removal_stats(int64_t* out4) const {
-    if (!tableau_ || cfg_.shard_count > 1) return RELP_E_UNSUPPORTED;
-    if (phase_ != 2) return RELP_E_STATE;
-    out4[0] = rm_cuts_; out4[1] = rm_columns_; out4[2] = rm_last_moved_; out4[3] = rm_last_p_;
-    return RELP_OK;
-}
+relp_status_t Engine::removal_stats(int64_t* out4) const { return in_place_stats(out4, rm_cuts_, rm_columns_, rm_last_moved_, rm_last_p_); }
 
 // The two batched ratio queries.  Both read the tableau as it stands -- T0, and W R0 over the p pending rows of an open block -- and
 // write to scratch of their own: d, b, the basis, the flags, W, R0, T0, the PRICE partials and the record stay as they are (the
@@ -1717,9 +1702,8 @@ relp_status_t Engine::ranging_query(bool columns, const char* what, const int32_
     for (int32_t k = 0; k < count; ++k)
         if (rows[k] < 0 || rows[k] >= lay_.m) return fail(RELP_E_ARG, std::string(what) + ": row out of range");
     if (count == 0) return RELP_OK;
-    tab_settle();
-    if ((st = download_rec())) return st;
-    const int32_t p = h_rec_->n_eta;
+    int32_t p;
+    if ((st = settled_pending(&p))) return st;
     const TableauView tv = tview();
     const int64_t blocks = columns ? (lay_.m + 255) / 256 : tab_scan_blocks(lay_.sc_hi - lay_.sc_lo);
     HIP_TRY(d_rng_list_.ensure_raw(sizeof(int32_t) * (size_t)count));
@@ -1760,12 +1744,7 @@ relp_status_t Engine::rhs_ranging(const int32_t* rows, int32_t count, double* de
     return ranging_query(true, "relp_rhs_ranging", rows, count, decrease, decrease_row, increase, increase_row);
 }
 
-relp_status_t Engine::ranging_stats(int64_t* out4) const {
-    if (!tableau_ || cfg_.shard_count > 1) return RELP_E_UNSUPPORTED;
-    if (phase_ != 2) return RELP_E_STATE;
-    out4[0] = rng_ratio_calls_; out4[1] = rng_ratio_rows_; out4[2] = rng_ranging_calls_; out4[3] = rng_last_p_;
-    return RELP_OK;
-}
+relp_status_t Engine::ranging_stats(int64_t* out4) const { return in_place_stats(out4, rng_ratio_calls_, rng_ratio_rows_, rng_ranging_calls_, rng_last_p_); }
 
 // phase_one.rs:146-166: objective == 0 -> feasible (remove artificials, switch) else infeasible
 relp_status_t Engine::finish_phase_one(int32_t* outcome) {

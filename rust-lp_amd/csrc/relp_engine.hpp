@@ -305,6 +305,12 @@ class Engine : private EngineQueue {
     void enqueue_iteration_tableau(int rule);
     void enqueue_iteration_dual();
     relp_status_t dual_ready(const char* what);        // phase 2 on the unsharded tableau engine, or the error
+    // what the in-place functions below share: their front (settle, download the record, *p = the open block's pending rows), the
+    // guard and the four counters of their *_stats, and the validation of a named list (index in [0, bound), named once, finite)
+    relp_status_t settled_pending(int32_t* p);
+    relp_status_t in_place_stats(int64_t* out4, int64_t s0, int64_t s1, int64_t s2, int64_t s3) const;
+    relp_status_t check_named_list(const char* what, const int32_t* index, const double* values, int32_t count, int32_t bound,
+                                   const char* noun, const char* outside);
     void tableau_reprice();
     // relp_change_right_hand_side: the compacted list (identity column, delta) of a change, v = the pending rows' share and the
     // per-split partial sums (relp_kernels.h: launch_tab_rhs_change); what relp_rhs_stats reports

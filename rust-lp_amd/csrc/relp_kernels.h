@@ -491,6 +491,10 @@ void launch_dual_select_column(const TableauView& tv, const DeferredUpdate& du, 
                                int32_t forced_row, const double* row, double* alpha, PivotRecord* rec, hipStream_t s);
 // alpha_r, b_r and the block bookkeeping of the deferred update for the (r, leaving) of the record: ratio_commit_row, no guard
 void launch_dual_commit(const double* alpha, const double* b, const DeferredUpdate& du, PivotRecord* rec, hipStream_t s);
+// The four in-place changes below (rhs, cost, cut rows, added columns) are built from two device helpers of
+// relp_kernels_tableau.hip, which state their summation orders once: for_list<B, V>, a thread's walk over a list staged in LDS 256
+// entries at a time with the loads B at a time and V fma chains in ascending entry order (the *_apply kernels and k_tab_cut_rows),
+// and list_sum, a workgroup's sum over a list by thread chains and a fixed halving tree (the *_pending kernels).
 // A change of rhs entries on the current basis (relp_change_right_hand_side): b += sum_k delta[k] T[:, cols[k]] with T = T0 + W R0
 // over the p pending rows, nothing else touched.  cols[k] = the stored column that was the identity column of the k-th changed row
 // (entries with delta 0 left out), ascending k as the caller gave them.
@@ -548,7 +552,7 @@ struct CutTail {
 };
 static constexpr int32_t kTabCutTile = 8;              // cuts per workgroup: eight rows of one column are one 64-byte run of T0
 // [k_tab_cut_pending: u[k][j] = sum_e coef[e][k] W[j][rows[e]], grid (p, count), p > 0 only] -> [k_tab_cut_rows: one old stored column
-// per thread, kTabCutTile cuts per workgroup, the list staged in LDS 256 entries at a time, every T0 and R0 load shared by the tile;
+// per thread, kTabCutTile cuts per workgroup, the list walked by for_list, every T0 and R0 load shared by the tile;
 // writes T0[m + k, c]: g - acc for a structural column, 0.0 - acc for any other, exactly 0.0 for a column flagged basic (in_basis == 1)]
 // -> [k_tab_cut_tail: unit columns of the new slacks in T0, zeros in their R0 entries and in the new rows of W, d = cost = 0 and flag 1
 // for the new columns, idcol / basis / pos_of_row (-1) of the new rows, the new virtual descriptors].  b of the new rows is the
@@ -576,8 +580,8 @@ struct ColumnTail {
     int32_t first_virtual, r0_rows;
 };
 static constexpr int32_t kTabColTile = 8;              // new columns per workgroup: every T0 load feeds eight accumulators
-// [k_tab_col_apply: one row per thread, 256 rows and kTabColTile new columns per workgroup, the list staged in LDS 256 entries at a
-// time, every (coalesced) T0 load shared by the tile, one fma chain per new column from 0.0 in ascending list order; writes
+// [k_tab_col_apply: one row per thread, 256 rows and kTabColTile new columns per workgroup, the list walked by for_list, every
+// (coalesced) T0 load shared by the tile, one fma chain per new column from 0.0 in ascending list order; writes
 // T0[i, n_store + k] for i < m] -> [k_tab_col_tail: R0[j][n_store + k] = the T0 entry just written at row du.S[j] for j < p and
 // 0.0 for the other rows of R0, d, stored cost, flag 0 and the descriptors of the new columns].  The list is not cut into shares.
 // No atomics, fixed summation orders: the same call on the same state gives the same bits.

@@ -40,6 +40,78 @@ __device__ __forceinline__ void for_pending(const double* base, int64_t stride, 
     }
 }
 
+// The staged walk over entries [lo, hi) of a list (an index and V coefficients per entry) by a block of 256 threads, each with
+// V chains of its own:  acc[v] = fma(coefficient v of entry e, load(index of entry e), acc[v])  for e = lo .. hi-1, ascending.
+//   Chunks: 256 entries at a time go into the caller's LDS arrays s_idx / s_coef, entry base + t by thread t through index(e) and
+//   coef(e, dst) (dst = the V LDS slots of that entry; coef forms its source address once).  Two barriers per chunk: the first one
+//   stands in front of the staging, because until every thread has passed it some may still be reading the previous chunk; the
+//   second one publishes the chunk.  Every thread of the block takes part in both, `mine` or not: a thread that is not `mine`
+//   stages its entry and loads nothing.  An empty range passes no barrier: a kernel that staged something of its own before the
+//   walk publishes it with a barrier of its own after the walk.
+//   Batches: the B loads of a batch are issued into registers before any of them is used, as in for_pending, so a thread makes
+//   ceil(n / B) round trips per chunk of n entries.  The tail batch is masked: nothing at or past the end of the range is read or
+//   used, so neither an index nor a coefficient behind hi is ever touched.  B = 1 is the plain loop.
+// The order of every chain is the entry order, whatever B, the chunking and V are.
+template <int B, int V, class Index, class Coef, class Load>
+__device__ __forceinline__ void for_list(int lo, int hi, int32_t* s_idx, double (*s_coef)[V], Index&& index, Coef&& coef, Load&& load,
+                                         bool mine, double (&acc)[V]) {
+    for (int base = lo; base < hi; base += kThreads) {
+        __syncthreads();                               // (the previous chunk has been read)
+        const int n = min(kThreads, hi - base);
+        if ((int)threadIdx.x < n) {
+            s_idx[threadIdx.x] = index(base + threadIdx.x);
+            coef(base + threadIdx.x, s_coef[threadIdx.x]);
+        }
+        __syncthreads();
+        if (!mine) continue;
+        int e0 = 0;
+        for (; e0 + B <= n; e0 += B) {
+            double t[B];
+#pragma unroll
+            for (int x = 0; x < B; ++x) t[x] = load(s_idx[e0 + x]);
+#pragma unroll
+            for (int x = 0; x < B; ++x)
+#pragma unroll
+                for (int v = 0; v < V; ++v) acc[v] = fma(s_coef[e0 + x][v], t[x], acc[v]);
+        }
+        if (e0 < n) {
+            double t[B];
+#pragma unroll
+            for (int x = 0; x < B; ++x) t[x] = e0 + x < n ? load(s_idx[e0 + x]) : 0.0;
+#pragma unroll
+            for (int x = 0; x < B; ++x)
+                if (e0 + x < n) {
+#pragma unroll
+                    for (int v = 0; v < V; ++v) acc[v] = fma(s_coef[e0 + x][v], t[x], acc[v]);
+                }
+        }
+    }
+}
+
+// The list reduction of a block of 256 threads:  sum_k coef(k) * value(k)  over k = 0 .. n-1.  Thread t chains its entries
+// k = t, t + 256, ... in ascending order (acc = fma(coef(k), value(k), acc) from 0.0), then a fixed halving tree over the 256
+// chains in s_sum: s_sum[t] += s_sum[t + half] for half = 128, 64, .. 1.  Returns s_sum[0]; thread 0 writes it out.  (Not
+// block_reduce_value: that one reduces by wave shuffles in another order, and the order is the specification here.)
+template <class Coef, class Value>
+__device__ __forceinline__ double list_sum(int n, double* s_sum, Coef&& coef, Value&& value) {
+    double acc = 0.0;
+    for (int k = threadIdx.x; k < n; k += kThreads) acc = fma(coef(k), value(k), acc);
+    s_sum[threadIdx.x] = acc;
+    __syncthreads();
+    for (int half = kThreads / 2; half > 0; half >>= 1) {
+        if ((int)threadIdx.x < half) s_sum[threadIdx.x] += s_sum[threadIdx.x + half];
+        __syncthreads();
+    }
+    return s_sum[0];
+}
+
+// The stored column c carries the flag basic (1): the pivot update pins its d at exactly 0.  A barred column (2) and every stored
+// column outside [col_off, col_off + n) (the kept artificial block in front of col_off) do not.
+__device__ __forceinline__ bool column_flagged_basic(const TableauView& tv, const uint8_t* __restrict__ in_basis, int c) {
+    const int j = c - tv.col_off;
+    return j >= 0 && j < tv.n && in_basis[j] == 1;
+}
+
 // Row r of W (its p pending entries) into s_w, one entry per thread; the caller's next barrier publishes it.
 __device__ __forceinline__ void stage_w_row(const DeferredUpdate& du, int r, int p, double* s_w) {
     if ((int)threadIdx.x < p) s_w[threadIdx.x] = du.W[(int64_t)threadIdx.x * du.ld + r];
@@ -975,32 +1047,28 @@ __global__ __launch_bounds__(kSingleBlock) void k_dual_commit(const double* __re
 // the changed rows' identity columns, with T = T0 + W R0 while an update block is open:
 //   b_i += sum_k delta_k T0[i, c_k] + sum_{j<p} W[j][i] v_j,   v_j = sum_k delta_k R0[j][c_k]
 // No atomics: every sum has a fixed order, so a given (list, p, splits) gives the same bits every run.
+// The two list patterns of this section and of the three after it (cost, cut rows, added columns) are defined once, beside
+// for_pending at the top of the file: list_sum (the *_pending kernels) and for_list (the *_apply kernels and k_tab_cut_rows).
 // ------------------------------------------------------------------------------------------------
 // v_j for pending row j = blockIdx.x: thread t sums its entries k = t, t + 256, ... in ascending order, then a fixed tree over the
-// 256 threads.  The identity columns of neighbouring rows are mostly neighbouring stored columns: the loads of a wavefront coalesce.
+// 256 threads (list_sum).  The identity columns of neighbouring rows are mostly neighbouring stored columns: the loads of a
+// wavefront coalesce.
 __global__ __launch_bounds__(kThreads) void k_tab_rhs_pending(TableauView tv, RhsChange ch, double* __restrict__ v) {
     __shared__ double s_sum[kThreads];
     const double* row = tv.R0 + (int64_t)blockIdx.x * tv.ld_r;
-    double acc = 0.0;
-    for (int k = threadIdx.x; k < ch.count; k += kThreads) acc = fma(ch.delta[k], row[ch.cols[k]], acc);
-    s_sum[threadIdx.x] = acc;
-    __syncthreads();
-    for (int half = kThreads / 2; half > 0; half >>= 1) {
-        if ((int)threadIdx.x < half) s_sum[threadIdx.x] += s_sum[threadIdx.x + half];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) v[blockIdx.x] = s_sum[0];
+    const double sum = list_sum(ch.count, s_sum, [&](int k) { return ch.delta[k]; }, [&](int k) { return row[ch.cols[k]]; });
+    if (threadIdx.x == 0) v[blockIdx.x] = sum;
 }
 
 // Row i = blockIdx.x * 256 + threadIdx.x, split blockIdx.y of the list: entries [lo, hi) in ascending k, staged in LDS 256 at a
-// time, their T0 loads issued B at a time before any is used (as in for_pending; consecutive threads read consecutive rows of
-// one column).  Split 0 then adds the pending rows' share through v (p > 0).  splits == 1: b[i] += acc, else partial[split][i].
+// time, their T0 loads issued B at a time before any is used (for_list; consecutive threads read consecutive rows of one
+// column).  Split 0 then adds the pending rows' share through v (p > 0).  splits == 1: b[i] += acc, else partial[split][i].
 template <int B>
 __global__ __launch_bounds__(kThreads) void k_tab_rhs_apply(TableauView tv, DeferredUpdate du, RhsChange ch, int p,
                                                             const double* __restrict__ v, double* __restrict__ b,
                                                             double* __restrict__ partial, int64_t ld_partial) {
     __shared__ int32_t s_c[kThreads];
-    __shared__ double s_delta[kThreads];
+    __shared__ double s_delta[kThreads][1];
     __shared__ double s_v[kMaxEta];
     const int splits = gridDim.y, split = blockIdx.y;
     const int share = (ch.count + splits - 1) / splits;
@@ -1008,35 +1076,14 @@ __global__ __launch_bounds__(kThreads) void k_tab_rhs_apply(TableauView tv, Defe
     const int i = blockIdx.x * kThreads + threadIdx.x;
     const bool mine = i < tv.m;
     if (split == 0 && (int)threadIdx.x < p) s_v[threadIdx.x] = v[threadIdx.x];
-    double acc = 0.0;
-    for (int base = lo; base < hi; base += kThreads) {
-        __syncthreads();                               // (the previous chunk has been read)
-        const int n = min(kThreads, hi - base);
-        if ((int)threadIdx.x < n) { s_c[threadIdx.x] = ch.cols[base + threadIdx.x]; s_delta[threadIdx.x] = ch.delta[base + threadIdx.x]; }
-        __syncthreads();
-        if (!mine) continue;
-        int k0 = 0;
-        for (; k0 + B <= n; k0 += B) {
-            double t[B];
-#pragma unroll
-            for (int u = 0; u < B; ++u) t[u] = tv.T0[(int64_t)s_c[k0 + u] * tv.ld_t + i];
-#pragma unroll
-            for (int u = 0; u < B; ++u) acc = fma(s_delta[k0 + u], t[u], acc);
-        }
-        if (k0 < n) {
-            double t[B];
-#pragma unroll
-            for (int u = 0; u < B; ++u) t[u] = k0 + u < n ? tv.T0[(int64_t)s_c[k0 + u] * tv.ld_t + i] : 0.0;
-#pragma unroll
-            for (int u = 0; u < B; ++u)
-                if (k0 + u < n) acc = fma(s_delta[k0 + u], t[u], acc);
-        }
-    }
+    double acc[1] = {0.0};
+    for_list<B>(lo, hi, s_c, s_delta, [&](int k) { return ch.cols[k]; }, [&](int k, double* dst) { dst[0] = ch.delta[k]; },
+                [&](int c) { return tv.T0[(int64_t)c * tv.ld_t + i]; }, mine, acc);
     __syncthreads();                                   // s_v (a split with an empty share never entered the loop)
     if (!mine) return;
-    if (split == 0) for_pending<B>(du.W, du.ld, i, p, [&](int j, double w) { acc = fma(w, s_v[j], acc); });
-    if (splits == 1) b[i] += acc;
-    else partial[(int64_t)split * ld_partial + i] = acc;
+    if (split == 0) for_pending<B>(du.W, du.ld, i, p, [&](int j, double w) { acc[0] = fma(w, s_v[j], acc[0]); });
+    if (splits == 1) b[i] += acc[0];
+    else partial[(int64_t)split * ld_partial + i] = acc[0];
 }
 
 // b[i] += partial[0][i] + partial[1][i] + ... in ascending split order
@@ -1057,32 +1104,23 @@ __global__ __launch_bounds__(kThreads) void k_tab_rhs_reduce(int m, int splits, 
 // No atomics: every sum has a fixed order, so a given (list, p, splits) gives the same bits every run.
 // ------------------------------------------------------------------------------------------------
 // The stored column c is one the change moves: every one the pivot update maintains d for (the kept artificial block in front of
-// col_off included), except a column flagged basic (1), whose d the pivot update pinned at exactly 0.  A barred column (2) moves.
+// col_off included), except a column flagged basic, whose d the pivot update pinned at exactly 0.  A barred column moves.
 __device__ __forceinline__ bool cost_moves_column(const TableauView& tv, const uint8_t* __restrict__ in_basis, int c) {
-    if (c >= tv.c_hi) return false;
-    const int j = c - tv.col_off;
-    return !(j >= 0 && j < tv.n && in_basis[j] == 1);
+    return c < tv.c_hi && !column_flagged_basic(tv, in_basis, c);
 }
 
 // u_j for pending row j = blockIdx.x: thread t sums its entries k = t, t + 256, ... in ascending order, then a fixed tree over the
-// 256 threads.  Column j of W is contiguous and the rows ascend: neighbouring entries share sectors.
+// 256 threads (list_sum).  Column j of W is contiguous and the rows ascend: neighbouring entries share sectors.
 __global__ __launch_bounds__(kThreads) void k_tab_cost_pending(DeferredUpdate du, CostChange ch, double* __restrict__ u) {
     __shared__ double s_sum[kThreads];
     const double* col = du.W + (int64_t)blockIdx.x * du.ld;
-    double acc = 0.0;
-    for (int k = threadIdx.x; k < ch.count; k += kThreads) acc = fma(ch.delta[k], col[ch.rows[k]], acc);
-    s_sum[threadIdx.x] = acc;
-    __syncthreads();
-    for (int half = kThreads / 2; half > 0; half >>= 1) {
-        if ((int)threadIdx.x < half) s_sum[threadIdx.x] += s_sum[threadIdx.x + half];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) u[blockIdx.x] = s_sum[0];
+    const double sum = list_sum(ch.count, s_sum, [&](int k) { return ch.delta[k]; }, [&](int k) { return col[ch.rows[k]]; });
+    if (threadIdx.x == 0) u[blockIdx.x] = sum;
 }
 
 // Stored column c = c_lo + blockIdx.x * 256 + threadIdx.x, split blockIdx.y of the basic list: entries [lo, hi) in ascending k,
-// staged in LDS 256 at a time, their T0 loads issued B at a time before any is used (a thread walks down its own column: eight
-// neighbouring rows are one 64-byte sector).  Split 0 then adds the pending rows' share through u (p > 0, R0 row j is contiguous
+// staged in LDS 256 at a time, their T0 loads issued B at a time before any is used (for_list; a thread walks down its own column:
+// eight neighbouring rows are one 64-byte sector).  Split 0 then adds the pending rows' share through u (p > 0, R0 row j is contiguous
 // in c) and takes the direct term of a changed non-basic column from the second list (storage columns ascending, binary search).
 // splits == 1: d[c] -= acc, else partial[split][c] = acc.
 template <int B>
@@ -1090,7 +1128,7 @@ __global__ __launch_bounds__(kThreads) void k_tab_cost_apply(TableauView tv, Cos
                                                              const double* __restrict__ u, double* __restrict__ partial,
                                                              int64_t ld_partial) {
     __shared__ int32_t s_r[kThreads];
-    __shared__ double s_delta[kThreads];
+    __shared__ double s_delta[kThreads][1];
     __shared__ double s_u[kMaxEta];
     const int splits = gridDim.y, split = blockIdx.y;
     const int share = (ch.count + splits - 1) / splits;
@@ -1099,44 +1137,23 @@ __global__ __launch_bounds__(kThreads) void k_tab_cost_apply(TableauView tv, Cos
     const bool mine = cost_moves_column(tv, in_basis, c);
     const double* col = tv.T0 + (int64_t)(mine ? c : tv.c_lo) * tv.ld_t;
     if (split == 0 && (int)threadIdx.x < p) s_u[threadIdx.x] = u[threadIdx.x];
-    double acc = 0.0;
-    for (int base = lo; base < hi; base += kThreads) {
-        __syncthreads();                               // (the previous chunk has been read)
-        const int n = min(kThreads, hi - base);
-        if ((int)threadIdx.x < n) { s_r[threadIdx.x] = ch.rows[base + threadIdx.x]; s_delta[threadIdx.x] = ch.delta[base + threadIdx.x]; }
-        __syncthreads();
-        if (!mine) continue;
-        int k0 = 0;
-        for (; k0 + B <= n; k0 += B) {
-            double t[B];
-#pragma unroll
-            for (int v = 0; v < B; ++v) t[v] = col[s_r[k0 + v]];
-#pragma unroll
-            for (int v = 0; v < B; ++v) acc = fma(s_delta[k0 + v], t[v], acc);
-        }
-        if (k0 < n) {
-            double t[B];
-#pragma unroll
-            for (int v = 0; v < B; ++v) t[v] = k0 + v < n ? col[s_r[k0 + v]] : 0.0;
-#pragma unroll
-            for (int v = 0; v < B; ++v)
-                if (k0 + v < n) acc = fma(s_delta[k0 + v], t[v], acc);
-        }
-    }
+    double acc[1] = {0.0};
+    for_list<B>(lo, hi, s_r, s_delta, [&](int k) { return ch.rows[k]; }, [&](int k, double* dst) { dst[0] = ch.delta[k]; },
+                [&](int r) { return col[r]; }, mine, acc);
     __syncthreads();                                   // s_u (a split with an empty share never entered the loop)
     if (!mine) return;
     if (split == 0) {
-        for_pending<B>(tv.R0, tv.ld_r, c, p, [&](int j, double r0) { acc = fma(s_u[j], r0, acc); });
+        for_pending<B>(tv.R0, tv.ld_r, c, p, [&](int j, double r0) { acc[0] = fma(s_u[j], r0, acc[0]); });
         int a = 0, z = ch.ncount;
         while (a < z) {
             const int mid = (a + z) >> 1;
             if (ch.ncols[mid] < c) a = mid + 1;
             else z = mid;
         }
-        if (a < ch.ncount && ch.ncols[a] == c) acc -= ch.ndelta[a];
+        if (a < ch.ncount && ch.ncols[a] == c) acc[0] -= ch.ndelta[a];
     }
-    if (splits == 1) tv.d[c] -= acc;
-    else partial[(int64_t)split * ld_partial + c] = acc;
+    if (splits == 1) tv.d[c] -= acc[0];
+    else partial[(int64_t)split * ld_partial + c] = acc[0];
 }
 
 // d[c] -= partial[0][c] + partial[1][c] + ... in ascending split order, for the columns k_tab_cost_apply wrote
@@ -1158,26 +1175,20 @@ __global__ __launch_bounds__(kThreads) void k_tab_cost_reduce(TableauView tv, co
 // nothing else of the old rows and columns is.  No atomics: every sum has a fixed order, the same call gives the same bits.
 // ------------------------------------------------------------------------------------------------
 // u[k][j] for pending row j = blockIdx.x and cut k = blockIdx.y: thread t sums its entries e = t, t + 256, ... in ascending order,
-// then a fixed tree over the 256 threads (k_tab_cost_pending with a coefficient per (entry, cut)).
+// then a fixed tree over the 256 threads (list_sum; k_tab_cost_pending with a coefficient per (entry, cut)).
 __global__ __launch_bounds__(kThreads) void k_tab_cut_pending(DeferredUpdate du, CutRows cr, double* __restrict__ u) {
     __shared__ double s_sum[kThreads];
     const double* col = du.W + (int64_t)blockIdx.x * du.ld;
     const int k = blockIdx.y;
-    double acc = 0.0;
-    for (int e = threadIdx.x; e < cr.entries; e += kThreads) acc = fma(cr.coef[(int64_t)e * cr.count + k], col[cr.rows[e]], acc);
-    s_sum[threadIdx.x] = acc;
-    __syncthreads();
-    for (int half = kThreads / 2; half > 0; half >>= 1) {
-        if ((int)threadIdx.x < half) s_sum[threadIdx.x] += s_sum[threadIdx.x + half];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) u[(int64_t)k * du.kmax + blockIdx.x] = s_sum[0];
+    const double sum = list_sum(cr.entries, s_sum, [&](int e) { return cr.coef[(int64_t)e * cr.count + k]; },
+                                [&](int e) { return col[cr.rows[e]]; });
+    if (threadIdx.x == 0) u[(int64_t)k * du.kmax + blockIdx.x] = sum;
 }
 
 // Old stored column c = c_lo + blockIdx.x * 256 + threadIdx.x, the kTabCutTile cuts from blockIdx.y * kTabCutTile on.  The list is
-// staged in LDS 256 entries at a time (rows and the tile's coefficients); a thread issues the T0 loads of its column B at a time
-// before any is used and feeds every loaded entry into the tile's accumulators, entries ascending: one strided load serves the
-// whole tile.  Then the pending rows' share through u, ascending j, one R0 load for the tile.  Written: T0[m + k, c] = g - acc for
+// staged in LDS 256 entries at a time (rows and the tile's coefficients, 0.0 past the last cut); a thread issues the T0 loads of
+// its column B at a time before any is used and feeds every loaded entry into the tile's accumulators, entries ascending
+// (for_list): one strided load serves the whole tile.  Then the pending rows' share through u, ascending j, one R0 load for the tile.  Written: T0[m + k, c] = g - acc for
 // a structural column (g from the cut rows of A), 0.0 - acc for any other, exactly 0.0 for a column flagged basic.  The tile's
 // rows of one column are contiguous.  Nothing else is written; tv describes the tableau before the add.
 template <int B>
@@ -1197,47 +1208,20 @@ __global__ __launch_bounds__(kThreads) void k_tab_cut_rows(TableauView tv, CutRo
     double acc[kTabCutTile];
 #pragma unroll
     for (int v = 0; v < kTabCutTile; ++v) acc[v] = 0.0;
-    for (int base = 0; base < cr.entries; base += kThreads) {
-        __syncthreads();                               // (the previous chunk has been read)
-        const int n = min(kThreads, cr.entries - base);
-        if ((int)threadIdx.x < n) {
-            s_r[threadIdx.x] = cr.rows[base + threadIdx.x];
-            const double* g = cr.coef + (int64_t)(base + threadIdx.x) * cr.count + k0;
+    for_list<B>(0, cr.entries, s_r, s_coef, [&](int e) { return cr.rows[e]; },
+                [&](int e, double* dst) {
+                    const double* g = cr.coef + (int64_t)e * cr.count + k0;
 #pragma unroll
-            for (int v = 0; v < kTabCutTile; ++v) s_coef[threadIdx.x][v] = v < nv ? g[v] : 0.0;
-        }
-        __syncthreads();
-        if (!mine) continue;
-        int e0 = 0;
-        for (; e0 + B <= n; e0 += B) {
-            double t[B];
-#pragma unroll
-            for (int x = 0; x < B; ++x) t[x] = col[s_r[e0 + x]];
-#pragma unroll
-            for (int x = 0; x < B; ++x)
-#pragma unroll
-                for (int v = 0; v < kTabCutTile; ++v) acc[v] = fma(s_coef[e0 + x][v], t[x], acc[v]);
-        }
-        if (e0 < n) {
-            double t[B];
-#pragma unroll
-            for (int x = 0; x < B; ++x) t[x] = e0 + x < n ? col[s_r[e0 + x]] : 0.0;
-#pragma unroll
-            for (int x = 0; x < B; ++x)
-                if (e0 + x < n) {
-#pragma unroll
-                    for (int v = 0; v < kTabCutTile; ++v) acc[v] = fma(s_coef[e0 + x][v], t[x], acc[v]);
-                }
-        }
-    }
+                    for (int v = 0; v < kTabCutTile; ++v) dst[v] = v < nv ? g[v] : 0.0;
+                },
+                [&](int r) { return col[r]; }, mine, acc);
     __syncthreads();                                   // s_u (an empty list never entered the loop)
     if (!mine) return;
     for_pending<B>(tv.R0, tv.ld_r, c, p, [&](int j, double r0) {
 #pragma unroll
         for (int v = 0; v < kTabCutTile; ++v) acc[v] = fma(s_u[v][j], r0, acc[v]);
     });
-    const int j = c - tv.col_off;
-    const bool basic = j >= 0 && j < tv.n && in_basis[j] == 1;
+    const bool basic = column_flagged_basic(tv, in_basis, c);
     const int sp = c - cr.struct_c0;
     const double* g = (sp >= 0 && sp < cr.nr_normal) ? cr.A + (int64_t)sp * cr.ld_a + cr.a_row0 + k0 : nullptr;
     double* out = tv.T0 + (int64_t)c * tv.ld_t + tv.m + k0;
@@ -1287,9 +1271,9 @@ __global__ void k_tab_cut_tail(TableauView tv, DeferredUpdate du, CutTail ct, in
 // T0 + W R0 of it is B^-1 a_k with the open block left open.  W is not read.  No atomics: one chain per entry, fixed order.
 // ------------------------------------------------------------------------------------------------
 // Row i = blockIdx.x * 256 + threadIdx.x, the kTabColTile new columns from blockIdx.y * kTabColTile on.  The list is staged in LDS
-// 256 entries at a time (identity columns and the tile's coefficients); a thread issues its T0 loads B at a time before any is used
-// (consecutive threads read consecutive rows of one column) and feeds every loaded entry into the tile's accumulators, entries
-// ascending.  Written: T0[i, n_store + k] = acc for i < m.  Nothing else is written; tv describes the tableau before the add.
+// 256 entries at a time (identity columns and the tile's coefficients, 0.0 past the last column); a thread issues its T0 loads B at
+// a time before any is used (consecutive threads read consecutive rows of one column) and feeds every loaded entry into the tile's
+// accumulators, entries ascending (for_list).  Written: T0[i, n_store + k] = acc for i < m.  Nothing else is written; tv describes the tableau before the add.
 template <int B>
 __global__ __launch_bounds__(kThreads) void k_tab_col_apply(TableauView tv, ColumnAdd ca) {
     __shared__ int32_t s_c[kThreads];
@@ -1300,39 +1284,13 @@ __global__ __launch_bounds__(kThreads) void k_tab_col_apply(TableauView tv, Colu
     double acc[kTabColTile];
 #pragma unroll
     for (int v = 0; v < kTabColTile; ++v) acc[v] = 0.0;
-    for (int base = 0; base < ca.entries; base += kThreads) {
-        __syncthreads();                               // (the previous chunk has been read)
-        const int n = min(kThreads, ca.entries - base);
-        if ((int)threadIdx.x < n) {
-            s_c[threadIdx.x] = ca.cols[base + threadIdx.x];
-            const double* a = ca.coef + (int64_t)(base + threadIdx.x) * ca.count + k0;
+    for_list<B>(0, ca.entries, s_c, s_coef, [&](int e) { return ca.cols[e]; },
+                [&](int e, double* dst) {
+                    const double* a = ca.coef + (int64_t)e * ca.count + k0;
 #pragma unroll
-            for (int v = 0; v < kTabColTile; ++v) s_coef[threadIdx.x][v] = v < nv ? a[v] : 0.0;
-        }
-        __syncthreads();
-        if (!mine) continue;
-        int e0 = 0;
-        for (; e0 + B <= n; e0 += B) {
-            double t[B];
-#pragma unroll
-            for (int x = 0; x < B; ++x) t[x] = tv.T0[(int64_t)s_c[e0 + x] * tv.ld_t + i];
-#pragma unroll
-            for (int x = 0; x < B; ++x)
-#pragma unroll
-                for (int v = 0; v < kTabColTile; ++v) acc[v] = fma(s_coef[e0 + x][v], t[x], acc[v]);
-        }
-        if (e0 < n) {
-            double t[B];
-#pragma unroll
-            for (int x = 0; x < B; ++x) t[x] = e0 + x < n ? tv.T0[(int64_t)s_c[e0 + x] * tv.ld_t + i] : 0.0;
-#pragma unroll
-            for (int x = 0; x < B; ++x)
-                if (e0 + x < n) {
-#pragma unroll
-                    for (int v = 0; v < kTabColTile; ++v) acc[v] = fma(s_coef[e0 + x][v], t[x], acc[v]);
-                }
-        }
-    }
+                    for (int v = 0; v < kTabColTile; ++v) dst[v] = v < nv ? a[v] : 0.0;
+                },
+                [&](int c) { return tv.T0[(int64_t)c * tv.ld_t + i]; }, mine, acc);
     if (!mine) return;
 #pragma unroll
     for (int v = 0; v < kTabColTile; ++v)
