@@ -432,6 +432,20 @@ class Tableau {
     }
     // relp_ranging_stats: {row-ratio calls, rows they covered, ranging calls, pending rows at the last call}
     std::array<int64_t, 4> ranging_stats() { std::array<int64_t, 4> out{}; ck(relp_ranging_stats(h_, out.data())); return out; }
+    // relp_gomory_cuts: per listed row the Gomory cut coefficients[k,:] x <= rhs[k] over the structural columns (row-major, the form
+    // add_cuts takes), fraction[k] = b_r - floor(b_r) and status[k] (0: a cut was made; 1 - 4: skipped, all zero).  is_integer: one
+    // flag per provider column, empty = all integer.  Read-only.
+    struct GomoryCuts { std::vector<double> coefficients, rhs, fraction; std::vector<int32_t> status; };
+    GomoryCuts gomory_cuts(const std::vector<int32_t>& rows, const std::vector<uint8_t>& is_integer = {}, int32_t kind = RELP_GOMORY_FRACTIONAL,
+                           double away = 1e-6) {
+        const size_t n = rows.size();
+        GomoryCuts out{std::vector<double>(n * (size_t)nr_normal_), std::vector<double>(n), std::vector<double>(n), std::vector<int32_t>(n)};
+        ck(relp_gomory_cuts(h_, rows.data(), (int32_t)n, is_integer.empty() ? nullptr : is_integer.data(), kind, away, out.coefficients.data(),
+                            out.rhs.data(), out.fraction.data(), out.status.data()));
+        return out;
+    }
+    // relp_gomory_stats: {calls, list entries they covered, cuts made, pending rows at the last call}
+    std::array<int64_t, 4> gomory_stats() { std::array<int64_t, 4> out{}; ck(relp_gomory_stats(h_, out.data())); return out; }
     // ---- one LP on several GPUs (no counterpart in the reference, which is single-threaded) ---------------------
     // Options::shard(rank, count) at construction, the owned structural columns in `MatrixData` (relp_shard_plan);
     // rank 0 makes the RCCL id, the host program hands it to every rank, every rank attaches, then the loop runs

@@ -469,6 +469,46 @@ relp_status_t relp_rhs_ranging(relp_engine_t *h, const int32_t *rows, int32_t co
 /* out4 = { relp_row_ratios calls so far, rows they covered, relp_rhs_ranging calls so far, pending rows p of the update block at
  * the last call of either }.  (Calls with count == 0 and refused calls are not counted.) */
 relp_status_t relp_ranging_stats(const relp_engine_t *h, int64_t *out4);
+/* Gomory cuts from rows of the tableau as it stands, in structural space, in the form relp_add_cuts takes (no counterpart in the
+ * reference): relp_gomory_cuts -> relp_add_cuts -> relp_run_dual is one round of a cutting-plane loop.  Read-only and deterministic
+ * like relp_row_ratios: nothing is flushed or re-tabulated, T0, R0, W, d, b, the basis, the flags, the PRICE partials, the record,
+ * the trace, relp_reinversions and relp_tab_flush_stats keep their bits; no atomics, the same call on the same state gives the same
+ * bits.  `rows` as in relp_row_ratios: engine rows in the current order, in any order, a row may be named twice.
+ *
+ * Entry k, r = rows[k], f0 = b_r - floor(b_r).  Over the non-basic provider columns j (flag != basic; a barred column counts like
+ * any other; the kept artificial block is left out: those variables are 0 in every feasible point) the cut in provider space is
+ * sum_j pi_j x_j >= f0, pi_j from the entry a = T[r,j] (T0 + W R0 over the pending rows, formed in the order of relp_row_ratios):
+ *   |a| <= tol_zero                                    pi_j = 0
+ *   integer column, f = a - floor(a)                   f <= tol_zero or f >= 1 - tol_zero: pi_j = 0
+ *       RELP_GOMORY_FRACTIONAL                         pi_j = f
+ *       RELP_GOMORY_MIXED                              pi_j = f if f <= f0, else (f0 (1 - f)) / (1 - f0)
+ *   continuous column, RELP_GOMORY_MIXED               pi_j = a if a > 0, else (f0 (-a)) / (1 - f0)
+ *   continuous column, RELP_GOMORY_FRACTIONAL          the entry is skipped (status 4)
+ * every difference, product and quotient rounded once in the order written.  The virtual columns go out through their rows: with
+ * row i written as (A x)_i [+ x_c in the bound row of c] + sigma_i s_i = rhs_i and y_i = sigma_i pi_{s_i},
+ *   g_c  = -pi_c + sum_i y_i A[i,c] + y_{bound_row(c)}     i over the constraint rows and the cut rows already added
+ *   beta = -f0 + sum_i y_i rhs_i                           i ascending over the rows with y_i != 0, one fma each from -f0
+ * (the order of the sum in g_c: DESIGN.md 10).  coefficients[k,:] = g (count x structural columns, row-major), rhs[k] = beta:
+ * the cut g'x <= beta, violated by the current vertex by f0.  fraction[k] = f0 (may be NULL).  is_integer: one flag per provider
+ * column (relp_nr_columns() of them), NULL = all integer.  status[k]:
+ *   0  a cut was made
+ *   1  the basic column of row r is not flagged integer
+ *   2  f0 < away or f0 > 1 - away                        (0 <= away < 0.5)
+ *   3  the basic column of row r is a kept artificial
+ *   4  a continuous column with |a| > tol_zero in a fractional cut
+ * decided in the order 3, 1, 2, 4.  A skipped entry gets an all-zero coefficient row, rhs = 0 and fraction = f0.
+ * Refusals leave nothing written.  RELP_E_ARG: a row out of range, count < 0, rows / coefficients / rhs / status missing, a kind
+ * other than the two, away outside [0, 0.5) or not finite.  RELP_E_UNSUPPORTED: another or a sharded engine, an LP with range rows
+ * (their virtual columns have two rows).  RELP_E_STATE: phase 1; added columns in the tableau (relp_add_cuts cannot hold a
+ * coefficient on one).  count == 0 is a no-op.  Two launches, one download per call; f0 and the statuses 1 - 3 are decided on the
+ * host from b and the basis.  Out of scope: range rows, cuts while added columns are present, sharded engines, lifting or
+ * strengthening of the cuts, and any choice of which rows to cut (engine.gomory_rounds in Python has a simple rule). */
+enum { RELP_GOMORY_FRACTIONAL = 0, RELP_GOMORY_MIXED = 1 };
+relp_status_t relp_gomory_cuts(relp_engine_t *h, const int32_t *rows, int32_t count, const uint8_t *is_integer, int32_t kind,
+                               double away, double *coefficients, double *rhs, double *fraction, int32_t *status);
+/* out4 = { relp_gomory_cuts calls so far, list entries they covered, cuts made (status 0), pending rows p of the update block at
+ * the last call }.  (Calls with count == 0 and refused calls are not counted.) */
+relp_status_t relp_gomory_stats(const relp_engine_t *h, int64_t *out4);
 /* InverseMaintener::from_basis (carry/mod.rs:428-463): warm start from provider column indices,
  * one per row; switches to phase 2.  RELP_ENGINE_LU: any basis (factorise, b = FTRAN(rhs), -pi = BTRAN(-c_B));
  * RELP_ENGINE_REVISED: any basis (basis_inverse_rows.rs:103-129: LU - factorised on the host like every

@@ -120,6 +120,11 @@ relp_status_t relp_rhs_ranging(relp_engine_t* h, const int32_t* rows, int32_t co
     return h ? H(h).rhs_ranging(rows, count, decrease, decrease_row, increase, increase_row) : RELP_E_ARG;
 }
 relp_status_t relp_ranging_stats(const relp_engine_t* h, int64_t* out4) { return (h && out4) ? H(h).ranging_stats(out4) : RELP_E_ARG; }
+relp_status_t relp_gomory_cuts(relp_engine_t* h, const int32_t* rows, int32_t count, const uint8_t* is_integer, int32_t kind, double away,
+                               double* coefficients, double* rhs, double* fraction, int32_t* status) {
+    return h ? H(h).gomory_cuts(rows, count, is_integer, kind, away, coefficients, rhs, fraction, status) : RELP_E_ARG;
+}
+relp_status_t relp_gomory_stats(const relp_engine_t* h, int64_t* out4) { return (h && out4) ? H(h).gomory_stats(out4) : RELP_E_ARG; }
 relp_status_t relp_solve_relaxation(relp_engine_t* h, int64_t max_iters, int32_t* outcome) {
     return h ? H(h).solve_relaxation(max_iters, outcome) : RELP_E_ARG;
 }

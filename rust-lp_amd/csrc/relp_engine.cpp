@@ -1,5 +1,6 @@
 // relp_engine.cpp -- host driver: problem upload, phase logic, launch sequencing.  See relp_engine.hpp.
 #include "relp_engine_internal.hpp"
+#include "relp_gomory.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -1745,6 +1746,73 @@ relp_status_t Engine::rhs_ranging(const int32_t* rows, int32_t count, double* de
 }
 
 relp_status_t Engine::ranging_stats(int64_t* out4) const { return in_place_stats(out4, rng_ratio_calls_, rng_ratio_rows_, rng_ranging_calls_, rng_last_p_); }
+
+// Gomory cuts from the listed rows of the tableau as it stands, in structural space.  The steps of ranging_query: validate, settle
+// the fused update's shadow row (no flush), upload the list, launch, one download.  Decided here from b and the basis (one
+// download before the launch): f0 and the statuses 1 - 3 of every entry (gomory_entry); a skipped entry goes up with f0 = -1 and
+// comes back all zero.  Decided on the device: pi over the stored columns, y over the rows through the virtual descriptors the
+// layout uploaded (table()), g over the structural columns from the engine's A (cut rows behind the constraints) and bound_row,
+// and the status 4 of a fractional cut.  beta is the fma chain of gomory_beta over the downloaded y and lay_.rhs.
+relp_status_t Engine::gomory_cuts(const int32_t* rows, int32_t count, const uint8_t* is_integer, int32_t kind, double away,
+                                  double* coefficients, double* rhs, double* fraction, int32_t* status) {
+    relp_status_t st = dual_ready("relp_gomory_cuts");
+    if (st) return st;
+    if (lay_.nr_range > 0) return fail(RELP_E_UNSUPPORTED, "relp_gomory_cuts: range rows are not substituted out of a cut");
+    if (lay_.nr_added > 0) return fail(RELP_E_STATE, "relp_gomory_cuts: added columns in the tableau (relp_add_cuts holds no coefficient on one)");
+    if (const char* why = gomory_check_args(rows, count, lay_.m, kind, away, coefficients, rhs, status)) return fail(RELP_E_ARG, std::string("relp_gomory_cuts: ") + why);
+    if (count == 0) return RELP_OK;
+    int32_t p;
+    if ((st = settled_pending(&p))) return st;
+    const int32_t m = lay_.m, nn = lay_.nr_normal;
+    std::vector<double> b(m);
+    std::vector<int32_t> basis(m);
+    hipError_t e = d_b_.download(b, enqueue_only(stream_));
+    HIP_TRY(first_error(e, d_basis_.download(basis, stream_)));
+    std::vector<double> f0(count), f0_dev(count);
+    std::vector<int32_t> stat(count);
+    for (int32_t k = 0; k < count; ++k) {
+        stat[k] = gomory_entry(b[rows[k]], basis[rows[k]], is_integer, lay_.n_provider, away, &f0[k]);
+        f0_dev[k] = stat[k] == kGomoryCut ? f0[k] : -1.0;
+    }
+    const TableauView tv = tview();
+    const int64_t n_st = tv.c_hi - tv.c_lo, nbc = tab_scan_blocks((int32_t)n_st);
+    const size_t n_g = (size_t)count * nn, n_y = (size_t)count * m, n_bad = (size_t)count * nbc, n_pi = (size_t)count * n_st;
+    HIP_TRY(d_gom_rows_.ensure_raw(sizeof(int32_t) * (size_t)count));
+    HIP_TRY(d_gom_f0_.ensure_raw(sizeof(double) * (size_t)count));
+    HIP_TRY(d_gom_out_.ensure_raw(sizeof(double) * (n_g + n_y + n_bad + n_pi)));
+    if (is_integer) HIP_TRY(d_gom_int_.ensure_raw((size_t)lay_.n_provider));
+    GomoryCuts gc{d_gom_rows_, d_gom_f0_, is_integer ? (const uint8_t*)d_gom_int_ : nullptr, count, kind, A_base(), ld_a_, tab_na_, nn,
+                  d_gom_out_ + n_g + n_y + n_bad, d_gom_out_ + n_g, d_gom_out_ + n_g + n_y, d_gom_out_};
+    // the list and the results under one wait (no return before it: the host arrays are in flight; no launch on a lost list)
+    e = d_gom_rows_.upload(rows, count, enqueue_only(stream_));
+    e = first_error(e, d_gom_f0_.upload(f0_dev, enqueue_only(stream_)));
+    if (is_integer) e = first_error(e, d_gom_int_.upload(is_integer, lay_.n_provider, enqueue_only(stream_)));
+    if (e == hipSuccess) launch_tab_gomory(tv, deferred(), table(), d_in_basis_, tolerances(), gc, p, stream_);
+    std::vector<double> out(n_g + n_y + n_bad);            // (allocated while the kernels run)
+    HIP_TRY(first_error(e, d_gom_out_.download(out, stream_)));
+    if (hipGetLastError() != hipSuccess) return fail(RELP_E_HIP, "relp_gomory_cuts: a kernel launch failed");
+    int64_t made = 0;
+    for (int32_t k = 0; k < count; ++k) {
+        const double* bad = &out[n_g + n_y + (size_t)k * nbc];
+        if (stat[k] == kGomoryCut && std::any_of(bad, bad + nbc, [](double v) { return v != 0.0; })) stat[k] = kGomoryContinuous;
+        double* g = coefficients + (size_t)k * nn;
+        if (stat[k] == kGomoryCut) {
+            std::copy(&out[(size_t)k * nn], &out[(size_t)k * nn] + nn, g);
+            rhs[k] = gomory_beta(f0[k], &out[n_g + (size_t)k * m], lay_.rhs.data(), m);
+            ++made;
+        } else {
+            std::fill(g, g + nn, 0.0);
+            rhs[k] = 0.0;
+        }
+        if (fraction) fraction[k] = f0[k];
+        status[k] = stat[k];
+    }
+    ++gom_calls_; gom_entries_ += count; gom_cuts_ += made;
+    gom_last_p_ = p;
+    return RELP_OK;
+}
+
+relp_status_t Engine::gomory_stats(int64_t* out4) const { return in_place_stats(out4, gom_calls_, gom_entries_, gom_cuts_, gom_last_p_); }
 
 // phase_one.rs:146-166: objective == 0 -> feasible (remove artificials, switch) else infeasible
 relp_status_t Engine::finish_phase_one(int32_t* outcome) {

@@ -158,6 +158,10 @@ class Engine : private EngineQueue {
     relp_status_t rhs_ranging(const int32_t* rows, int32_t count, double* decrease, int32_t* decrease_row, double* increase,
                               int32_t* increase_row);
     relp_status_t ranging_stats(int64_t* out4) const;
+    // Gomory cuts from rows of the tableau as it stands, in structural space (the form add_cuts takes), read-only
+    relp_status_t gomory_cuts(const int32_t* rows, int32_t count, const uint8_t* is_integer, int32_t kind, double away, double* coefficients,
+                              double* rhs, double* fraction, int32_t* status);
+    relp_status_t gomory_stats(int64_t* out4) const;
     int32_t engine_kind() const { return lay_.engine; }
     relp_status_t robust_stats(int64_t* out4) const;
     relp_status_t solve_relaxation(int64_t max_iters, int32_t* outcome);
@@ -364,6 +368,13 @@ class Engine : private EngineQueue {
     DeviceBuf<double> d_rng_part_k_, d_rng_ratio_;
     int64_t rng_ratio_calls_ = 0, rng_ratio_rows_ = 0, rng_ranging_calls_ = 0;
     int32_t rng_last_p_ = 0;
+    // relp_gomory_cuts: the uploaded list (rows, f0, the integer flags) and the scratch of launch_tab_gomory -- [g | y | bad], one
+    // download, then pi -- allocated at the first call, grown on demand; what relp_gomory_stats reports
+    DeviceBuf<int32_t> d_gom_rows_;
+    DeviceBuf<double> d_gom_f0_, d_gom_out_;
+    DeviceBuf<uint8_t> d_gom_int_;
+    int64_t gom_calls_ = 0, gom_entries_ = 0, gom_cuts_ = 0;
+    int32_t gom_last_p_ = 0;
     // sparse LU engine (cfg.engine == RELP_ENGINE_LU): B^-1 = (I + W S') (L U)^-1, refactor every block_ pivots
     bool lu_ = false;
     std::vector<int64_t> hc_ptr_; std::vector<int32_t> hc_idx_; std::vector<double> hc_val_;   // host CSC of A

@@ -621,6 +621,28 @@ void launch_tab_row_ratios(const TableauView& tv, const DeferredUpdate& du, cons
 void launch_tab_rhs_ranging(const TableauView& tv, const DeferredUpdate& du, const double* b, const int32_t* basis_indices,
                             Tolerances tol, const int32_t* cols, int32_t count, int32_t p, double* part, double* ratio, int32_t* row,
                             hipStream_t s);
+// Gomory cuts from rows of the tableau as it stands, in structural space (relp_gomory_cuts), read-only like the ratio queries.
+// Entry k < count: row rows[k] with fraction f0[k] of its b (f0[k] < 0: the entry is skipped, every pi of it is 0.0).  is_integer:
+// one flag per tableau column (tv.n), nullptr = all integer.  kind: 0 fractional, 1 mixed.  A: the engine's matrix with the cut rows
+// behind the ct.nr_constraints constraint rows (ct.nr_cuts of them, tableau rows ct.cut_row0 ..), structural column sp the stored
+// column struct_c0 + sp.  Scratch, all written by the launch: pi count x (tv.c_hi - tv.c_lo), y count x tv.m (both row-major by
+// entry), bad count x tab_scan_blocks(stored columns) (1.0: a continuous column with |entry| > tol.zero in a fractional cut), g
+// count x nr_normal.
+struct GomoryCuts {
+    const int32_t* rows; const double* f0; const uint8_t* is_integer;
+    int32_t count, kind;
+    const double* A; int64_t ld_a; int32_t struct_c0, nr_normal;
+    double *pi, *y, *bad, *g;
+};
+// [y = 0] -> [k_tab_gomory_rows<B, 8>: grid chunks of kTabRatioChunk entries x blocks of 256 stored columns, one column per thread,
+// the entry of k_tab_row_ratios (T0, then one fma per pending row in ascending j), the rule of relp_gomory_cuts on it; writes pi,
+// exactly 0.0 for a basic column and for the kept artificial block, y[k][vrow0[v]] = vsign[v] * pi for the virtual column v, and bad]
+// -> [k_tab_gomory_structural<B, 8>: one structural column per workgroup, the chunk's eight cuts together, lanes along the rows of
+// A: thread t chains  acc = fma(y_i, A[i, c], acc)  over the rows t, t + 256, .. of A ascending from 0.0 (every row of A: y is 0.0
+// where a row has no slack or pi is 0.0), the halving tree of list_sum, then  (sum - pi_c) + y[bound_row(c)]  (the last term only
+// where c has a bound row); writes g].  No atomics, fixed orders: the same call on the same state gives the same bits.
+void launch_tab_gomory(const TableauView& tv, const DeferredUpdate& du, const ColumnTable& ct, const uint8_t* in_basis, Tolerances tol,
+                       const GomoryCuts& gc, int32_t p, hipStream_t s);
 
 // ---- sparse LU engine ------------------------------------------------------------------------------
 // PRICE over CSC columns (thread per column), partial argmin per 256 columns

@@ -1607,6 +1607,139 @@ __global__ __launch_bounds__(kThreads) void k_tab_rhs_ranging_pick(TableauView t
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Gomory cuts from rows of the tableau as it stands (relp_gomory_cuts): the row stream of k_tab_row_ratios with the rounding rule
+// on every entry, then the virtual columns substituted out through their rows over the dense A.  Read-only on the tableau; every
+// sum has a fixed order, no atomics: the same call on the same state gives the same bits.
+// ------------------------------------------------------------------------------------------------
+// The coefficient pi_j of a non-basic column from its entry a of the row, the row's fraction f0 and the column's flag (kind 0 =
+// fractional, 1 = mixed).  Every difference, product and quotient is rounded once, in the order written, nothing is contracted.
+// *bad: a continuous column with |a| > tol_zero in a fractional cut (the entry is skipped by the host).
+__device__ __forceinline__ double gomory_pi(double a, double f0, bool integer, int kind, double tol_zero, bool* bad) {
+#pragma clang fp contract(off)
+    if (fabs(a) <= tol_zero) return 0.0;
+    if (integer) {
+        const double f = a - floor(a);
+        if (f <= tol_zero || f >= 1.0 - tol_zero) return 0.0;
+        if (kind == 0 || f <= f0) return f;
+        const double num = f0 * (1.0 - f);
+        return num / (1.0 - f0);
+    }
+    if (kind == 0) { *bad = true; return 0.0; }
+    if (a > 0.0) return a;
+    const double num = f0 * (-a);
+    return num / (1.0 - f0);
+}
+
+// Rows rows[k0 .. k0 + RB) of T (k0 = blockIdx.x * RB) over the 256 stored columns of block blockIdx.y, one column per thread, the
+// entries formed as in k_tab_row_ratios: one T0 load per row, the R0 column shared by all RB, fma over the pending rows in
+// ascending j (tab_row_entry).  Written per entry k of the chunk: pi[k][c - c_lo] = gomory_pi of the entry for a non-basic
+// tableau column (flag != 1: a barred column counts), exactly 0.0 for a basic one, for the kept artificial block in front of
+// col_off and for a skipped entry (f0 < 0); y[k][vrow0[v]] = vsign[v] * pi where c is the virtual column v with a row;
+// bad[k * gridDim.y + blockIdx.y] = 1.0 if any column of the block was bad for entry k, else 0.0.
+template <int B, int RB>
+__global__ __launch_bounds__(kThreads) void k_tab_gomory_rows(TableauView tv, DeferredUpdate du, ColumnTable ct,
+                                                              const uint8_t* __restrict__ in_basis, double tol_zero, GomoryCuts gc, int p) {
+    __shared__ double s_w[RB * kMaxEta];
+    __shared__ int s_rows[RB];
+    __shared__ double s_f0[RB];
+    const int k0 = blockIdx.x * RB, nk = min(RB, gc.count - k0);
+    if ((int)threadIdx.x < RB) {
+        const int k = k0 + min((int)threadIdx.x, nk - 1);  // (a short chunk repeats its last row)
+        s_rows[threadIdx.x] = gc.rows[k];
+        s_f0[threadIdx.x] = gc.f0[k];
+    }
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < RB * p; idx += kThreads) {
+        const int u = idx / p, j = idx - u * p;
+        s_w[u * kMaxEta + j] = du.W[(int64_t)j * du.ld + s_rows[u]];
+    }
+    const int c = tv.c_lo + blockIdx.y * kThreads + threadIdx.x;
+    const int j = c - tv.col_off;
+    const bool live = c < tv.c_hi;
+    double acc[RB];
+    bool cand = false, integer = true;
+#pragma unroll
+    for (int u = 0; u < RB; ++u) acc[u] = 0.0;
+    if (live) {
+        cand = j >= 0 && j < tv.n && in_basis[j] != 1;
+        if (cand && gc.is_integer) integer = gc.is_integer[j] != 0;
+        const double* col = tv.T0 + (int64_t)c * tv.ld_t;
+#pragma unroll
+        for (int u = 0; u < RB; ++u) acc[u] = col[s_rows[u]];
+    }
+    __syncthreads();
+    if (live && cand) {
+        for_pending<B>(tv.R0, tv.ld_r, c, p, [&](int jj, double r0) {
+#pragma unroll
+            for (int u = 0; u < RB; ++u) acc[u] = fma(s_w[u * kMaxEta + jj], r0, acc[u]);
+        });
+    }
+    // the row of the virtual column's slack and its sign (0: c is no virtual column with a row)
+    int y_row = -1, y_sign = 0;
+    if (live && j >= ct.nr_artificial + ct.nr_normal) {
+        const int v = j - ct.nr_artificial - ct.nr_normal;
+        if (v < ct.nr_virtual && ct.vrow0[v] >= 0 && ct.vrow0[v] < tv.m) { y_row = ct.vrow0[v]; y_sign = ct.vsign[v]; }
+    }
+    const int n_st = tv.c_hi - tv.c_lo;
+#pragma unroll
+    for (int u = 0; u < RB; ++u) {
+        bool bad = false;
+        const double f0 = s_f0[u];
+        const double v = (cand && f0 >= 0.0) ? gomory_pi(acc[u], f0, integer, gc.kind, tol_zero, &bad) : 0.0;
+        if (live && u < nk) {
+            gc.pi[(int64_t)(k0 + u) * n_st + (c - tv.c_lo)] = v;
+            if (y_row >= 0) gc.y[(int64_t)(k0 + u) * tv.m + y_row] = y_sign < 0 ? -v : v;
+        }
+        const int any = __syncthreads_or(bad ? 1 : 0);
+        if (threadIdx.x == 0 && u < nk) gc.bad[(int64_t)(k0 + u) * gridDim.y + blockIdx.y] = any ? 1.0 : 0.0;
+    }
+}
+
+// Structural column sp = blockIdx.x, the RB cuts from k0 = blockIdx.y * RB on together; lanes run along the rows of the column of A
+// (coalesced), and every load of A serves the chunk.  Thread t chains  acc[u] = fma(y[k0 + u][row(i)], A[i, sp], acc[u])  over the
+// rows i = t, t + 256, .. of A in ascending order from 0.0, the loads of A min(B, 16) at a time (for_pending); row(i) = i for a constraint
+// row, cut_row0 + (i - nr_constraints) for a cut row.  Then the fixed halving tree of list_sum over the 256 chains of every cut,
+// and g[k][sp] = (sum - pi[k][sp]) + y[k][bound_row(sp)], the last term only where sp has a bound row.
+template <int B, int RB>
+__global__ __launch_bounds__(kThreads) void k_tab_gomory_structural(TableauView tv, ColumnTable ct, GomoryCuts gc) {
+    __shared__ double s_sum[RB][kThreads];
+    const int sp = blockIdx.x;
+    const int k0 = blockIdx.y * RB, nk = min(RB, gc.count - k0);
+    const int n_a = ct.nr_constraints + ct.nr_cuts;
+    const int t = threadIdx.x;
+    const double* y[RB];
+#pragma unroll
+    for (int u = 0; u < RB; ++u) y[u] = gc.y + (int64_t)(k0 + min(u, nk - 1)) * tv.m;     // (a short chunk repeats its last cut)
+    double acc[RB];
+#pragma unroll
+    for (int u = 0; u < RB; ++u) acc[u] = 0.0;
+    constexpr int BA = B > 16 ? 16 : B;                // (32 loads in flight beside 8 chains and 8 row pointers spill scalar registers)
+    for_pending<BA>(gc.A + (int64_t)sp * gc.ld_a, kThreads, t, t < n_a ? (n_a - t + kThreads - 1) / kThreads : 0, [&](int jj, double a) {
+        const int i = jj * kThreads + t;
+        const int row = i < ct.nr_constraints ? i : ct.cut_row0 + (i - ct.nr_constraints);
+#pragma unroll
+        for (int u = 0; u < RB; ++u) acc[u] = fma(y[u][row], a, acc[u]);
+    });
+#pragma unroll
+    for (int u = 0; u < RB; ++u) s_sum[u][t] = acc[u];
+    __syncthreads();
+    for (int half = kThreads / 2; half > 0; half >>= 1) {
+        if (t < half) {
+#pragma unroll
+            for (int u = 0; u < RB; ++u) s_sum[u][t] += s_sum[u][t + half];
+        }
+        __syncthreads();
+    }
+    if (t < nk) {
+        const int c = gc.struct_c0 + sp;
+        double v = s_sum[t][0] - gc.pi[(int64_t)(k0 + t) * (tv.c_hi - tv.c_lo) + (c - tv.c_lo)];
+        const int br = ct.bound_row[sp];
+        if (br >= 0 && br < tv.m) v = v + gc.y[(int64_t)(k0 + t) * tv.m + br];
+        gc.g[(int64_t)(k0 + t) * gc.nr_normal + sp] = v;
+    }
+}
+
 int32_t tab_scan_blocks(int32_t n_owned_columns) { return cdiv(n_owned_columns, kThreads); }
 
 // The batch sizes of for_pending the kernels are instantiated for (DeferredUpdate::batch, RELP_TAB_LOAD_BATCH).  1 is the
@@ -1928,6 +2061,20 @@ void launch_tab_rhs_ranging(const TableauView& tv, const DeferredUpdate& du, con
                            s, tv, du, b, tol, cols, (int)count, (int)p, part);
         hipLaunchKernelGGL((k_tab_rhs_ranging_pick<decltype(B)::value>), dim3(count), dim3(kThreads), 0, s, tv, du, b, basis_indices, tol,
                            cols, (int)count, (int)p, nbr, part, ratio, row);
+    });
+}
+
+void launch_tab_gomory(const TableauView& tv, const DeferredUpdate& du, const ColumnTable& ct, const uint8_t* in_basis, Tolerances tol,
+                       const GomoryCuts& gc, int32_t p, hipStream_t s) {
+    if (gc.count < 1 || tv.c_hi <= tv.c_lo || tv.m < 1) return;
+    const int chunks = cdiv(gc.count, kTabRatioChunk);
+    (void)hipMemsetAsync(gc.y, 0, sizeof(double) * (size_t)gc.count * (size_t)tv.m, s);
+    with_load_batch(du.batch, [&](auto B) {
+        hipLaunchKernelGGL((k_tab_gomory_rows<decltype(B)::value, kTabRatioChunk>), dim3(chunks, tab_scan_blocks(tv.c_hi - tv.c_lo)),
+                           dim3(kThreads), 0, s, tv, du, ct, in_basis, tol.zero, gc, (int)p);
+        if (gc.nr_normal > 0)
+            hipLaunchKernelGGL((k_tab_gomory_structural<decltype(B)::value, kTabRatioChunk>), dim3(gc.nr_normal, chunks), dim3(kThreads), 0, s,
+                               tv, ct, gc);
     });
 }
 

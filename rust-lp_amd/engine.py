@@ -28,6 +28,9 @@ LIB_PATH = os.path.join(_HERE, "librelp_engine.so")
 FIRST_PROFITABLE, FIRST_PROFITABLE_WITH_MEMORY, STEEPEST_DESCENT = 0, 1, 2
 # relp_outcome_t
 RUNNING, OPTIMAL, UNBOUNDED, INFEASIBLE, PHASE_ONE_DONE, NO_ROW_PHASE_ONE = range(6)
+# kind of relp_gomory_cuts, and its status per list entry
+GOMORY_FRACTIONAL, GOMORY_MIXED = 0, 1
+GOMORY_CUT, GOMORY_NOT_INTEGER, GOMORY_FRACTION, GOMORY_ARTIFICIAL, GOMORY_CONTINUOUS = range(5)
 OUTCOME_NAMES = {RUNNING: "running", OPTIMAL: "optimal", UNBOUNDED: "unbounded", INFEASIBLE: "infeasible",
                  PHASE_ONE_DONE: "phase_one_done", NO_ROW_PHASE_ONE: "no_row_phase_one"}
 # relp_kernel_id_t
@@ -112,6 +115,9 @@ _SIGNATURES = {
     "relp_row_ratios": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "relp_rhs_ranging": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "relp_ranging_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "relp_gomory_cuts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),
+    "relp_gomory_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "relp_solve_relaxation": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]),
     "relp_from_basis": (C.c_int, [C.c_void_p, C.c_void_p]),
     "relp_flush": (C.c_int, [C.c_void_p]),
@@ -618,6 +624,36 @@ class Tableau:
         self._ck(self._lib.relp_ranging_stats(self._h, out))
         return tuple(int(x) for x in out)
 
+    def gomory_cuts(self, rows, is_integer=None, kind=GOMORY_FRACTIONAL, away=1e-6):
+        """(G, rhs, fraction, status), one entry per listed engine row (relp_gomory_cuts): the Gomory cut ``G[k] x <= rhs[k]`` of
+        tableau row ``rows[k]`` over the structural columns, in the form ``add_cuts`` takes, violated by the current vertex by
+        ``fraction[k] = b_r - floor(b_r)``.  ``is_integer``: one flag per provider column (``nr_columns()``), None = all integer;
+        ``kind`` GOMORY_FRACTIONAL or GOMORY_MIXED.  ``status[k]``: GOMORY_CUT (0) a cut was made, else the entry is skipped (all
+        zero): GOMORY_NOT_INTEGER (the basic column is not flagged), GOMORY_FRACTION (the fraction is within ``away`` of 0 or
+        1), GOMORY_ARTIFICIAL, GOMORY_CONTINUOUS (a continuous column in a fractional cut).  Read-only; any order, repeats
+        allowed."""
+        r = np.ascontiguousarray(rows, dtype=np.int32)
+        if r.ndim != 1:
+            raise ValueError("rows must be one-dimensional")
+        flags = None
+        if is_integer is not None:
+            flags = np.ascontiguousarray(np.asarray(is_integer) != 0, dtype=np.uint8)
+            if flags.shape != (self.nr_columns(),):
+                raise ValueError("is_integer must have one flag per provider column")
+        n = r.shape[0]
+        G, rhs = np.zeros((n, self.provider.nr_normal)), np.zeros(n)
+        fraction, status = np.zeros(n), np.full(n, -1, dtype=np.int32)
+        self._ck(self._lib.relp_gomory_cuts(self._h, r.ctypes.data, n, None if flags is None else flags.ctypes.data, int(kind),
+                                            float(away), G.ctypes.data, rhs.ctypes.data, fraction.ctypes.data, status.ctypes.data))
+        return G, rhs, fraction, status
+
+    def gomory_stats(self) -> Tuple[int, int, int, int]:
+        """(gomory_cuts calls so far, list entries they covered, cuts made, pending rows of the update block at the last call);
+        relp_gomory_stats."""
+        out = (C.c_int64 * 4)()
+        self._ck(self._lib.relp_gomory_stats(self._h, out))
+        return tuple(int(x) for x in out)
+
     def cost_ranging(self, columns):
         """(decrease, increase) per structural column j of ``columns``: the basis stays optimal while c_j stays within
         [c_j - decrease, c_j + increase].  A non-basic column gives (d_j, inf); a basic one the (down, up) of ``row_ratios`` on
@@ -884,6 +920,40 @@ def phase_two_dual(tableau: Tableau, max_iters: int = 1 << 40) -> int:
     if tableau.phase != 2:
         raise RelpError("tableau still has artificial variables")
     return tableau.run_dual(max_iters)[1]
+
+
+def gomory_rounds(tableau: Tableau, is_integer=None, max_rounds: int = 20, cuts_per_round: int = 3, kind: int = GOMORY_FRACTIONAL,
+                  away: float = 1e-6, max_iters: int = 1 << 40):
+    """Rounds of Gomory cuts on an optimal phase-2 tableau.  A round reads ``b`` and the basis, takes the first ``cuts_per_round``
+    rows whose basic column is flagged integer (``is_integer`` per provider column of the tableau as it stands -- a cut's slack is
+    integer when the cut's columns are --, None = all) and whose fraction lies inside [away, 1 - away], and runs ``gomory_cuts`` ->
+    ``add_cuts`` (the cuts made) -> ``run_dual``.  Stops when no such row is left, no cut was made, the LP is infeasible or after
+    ``max_rounds`` rounds.  Returns (rounds, cuts added, [objective after each round], last outcome)."""
+    rounds, added, objectives, outcome = 0, 0, [], OPTIMAL
+    while rounds < max_rounds:
+        b, basis = tableau.b(), tableau.basis_indices()
+        n = tableau.nr_columns()
+        flags = np.ones(n, dtype=np.uint8)             # (behind the caller's flags: the slacks of the cuts added since)
+        if is_integer is not None:
+            given = np.asarray(is_integer)[:n] != 0
+            flags[:given.shape[0]] = given
+        fraction = b - np.floor(b)
+        rows = [i for i in range(b.shape[0])
+                if 0 <= basis[i] < n and flags[basis[i]] and away <= fraction[i] <= 1.0 - away][:cuts_per_round]
+        if not rows:
+            break
+        G, rhs, _, status = tableau.gomory_cuts(rows, flags, kind, away)
+        made = status == GOMORY_CUT
+        if not made.any():
+            break
+        tableau.add_cuts(G[made], rhs[made])
+        outcome = tableau.run_dual(max_iters)[1]
+        rounds += 1
+        added += int(made.sum())
+        if outcome != OPTIMAL:
+            break
+        objectives.append(tableau.objective_function_value())
+    return rounds, added, objectives, outcome
 
 
 def solve_relaxation(provider: MatrixData, **config_overrides):
