@@ -446,6 +446,25 @@ class Tableau {
     }
     // relp_gomory_stats: {calls, list entries they covered, cuts made, pending rows at the last call}
     std::array<int64_t, 4> gomory_stats() { std::array<int64_t, 4> out{}; ck(relp_gomory_stats(h_, out.data())); return out; }
+    // relp_trial_begin / relp_trial_end: a trial scope -- what the in-place changes, add_cuts within the reserved room and run_dual
+    // can change is saved without a flush and without a copy of the tableau; trial_end(false) puts every getter back to the bit,
+    // trial_end(true) keeps the state.  Trials do not nest; inside one, whatever flushes, rebuilds or re-allocates is refused.
+    void trial_begin() { ck(relp_trial_begin(h_)); }
+    void trial_end(bool keep = false) { ck(relp_trial_end(h_, keep ? 1 : 0)); }
+    // relp_trial_stats: {trials begun, trials rolled back, bytes the last snapshot held, pivots the last trial could still have made}
+    std::array<int64_t, 4> trial_stats() { std::array<int64_t, 4> out{}; ck(relp_trial_stats(h_, out.data())); return out; }
+    // relp_strong_branch: per listed row (down, up) at slots 2k, 2k + 1 -- the objective after at most max_pivots dual pivots on the
+    // child x_j <= floor(b_r) / x_j >= ceil(b_r), its outcome (RELP_OPTIMAL, RELP_INFEASIBLE with +inf, RELP_RUNNING: still a valid
+    // bound) and the pivots made -- and status[k] (0 evaluated; 1 not a structural column, 2 the fraction within `away` of 0 or 1:
+    // NaN, -1, 0).  Rolled back after every child; may grow the room for one cut and flush the open block once before the first.
+    struct StrongBranch { std::vector<double> objective; std::vector<int32_t> outcome, pivots, status; };
+    StrongBranch strong_branch(const std::vector<int32_t>& rows, int32_t max_pivots, double away = 1e-6) {
+        const size_t n = rows.size();
+        StrongBranch out{std::vector<double>(2 * n), std::vector<int32_t>(2 * n), std::vector<int32_t>(2 * n), std::vector<int32_t>(n)};
+        ck(relp_strong_branch(h_, rows.data(), (int32_t)n, max_pivots, away, out.objective.data(), out.outcome.data(), out.pivots.data(),
+                              out.status.data()));
+        return out;
+    }
     // ---- one LP on several GPUs (no counterpart in the reference, which is single-threaded) ---------------------
     // Options::shard(rank, count) at construction, the owned structural columns in `MatrixData` (relp_shard_plan);
     // rank 0 makes the RCCL id, the host program hands it to every rank, every rank attaches, then the loop runs

@@ -509,6 +509,66 @@ relp_status_t relp_gomory_cuts(relp_engine_t *h, const int32_t *rows, int32_t co
 /* out4 = { relp_gomory_cuts calls so far, list entries they covered, cuts made (status 0), pending rows p of the update block at
  * the last call }.  (Calls with count == 0 and refused calls are not counted.) */
 relp_status_t relp_gomory_stats(const relp_engine_t *h, int64_t *out4);
+/* A trial scope on the unsharded tableau engine in phase 2 (no counterpart in the reference): try something on the current basis,
+ * look at the result, and come back.  Between two flushes the tableau is T = (I + W S') T0 and nothing a trial may call writes T0
+ * over the rows and columns that exist, or a pending row of R0; so the way back is a copy of a few arrays of length m or n, the
+ * pending columns of W and the record, not of the tableau (DESIGN.md 10 lists every array and why it is or is not saved).
+ *
+ * relp_trial_begin settles the fused update's shadow row, does NOT flush, and saves what a trial can change: on the device in one
+ * launch of k_tab_trial_copy (RELP_TRIAL_MEMCPY=1 at create: the same copies as a chain of hipMemcpyAsync, the control), on the
+ * host the layout (rhs, costs, cuts) and every counter.  Trials do not nest (RELP_E_STATE).
+ * Inside a trial these work as usual: every getter but relp_get_basis_inverse (it flushes), the read-only queries (relp_row_ratios,
+ * relp_rhs_ranging, relp_gomory_cuts, relp_generate_column, relp_relative_costs, relp_check_basis, ...), relp_change_right_hand_side,
+ * relp_set_upper_bound, relp_change_cost, relp_add_cuts within the room that exists, relp_run_dual and relp_select_dual_pivot_row /
+ * _column.  These return RELP_E_STATE with nothing changed -- they flush, rebuild, re-allocate or compact --: relp_flush,
+ * relp_set_cost, relp_set_right_hand_side, relp_from_basis, relp_get_basis_inverse, relp_remove_cuts, relp_remove_columns,
+ * relp_reserve_cuts, relp_reserve_columns, a relp_add_cuts that would have to grow, relp_add_columns,
+ * relp_set_reinversion_interval, and relp_run, relp_solve_relaxation, relp_bring_into_basis (the primal loop's rescue and barring
+ * state is not part of the snapshot).  relp_engine_destroy inside a trial is fine.
+ * relp_run_dual inside a trial never flushes and never re-inverts (the interval and auto_reinversion are suspended; their counters
+ * are part of the saved state): it pivots only while since_flush + 1 < update_block, since_flush counted in pivots made, so the
+ * block is never left full.  When that room is used up the loop returns RELP_RUNNING with *iterations_done = the pivots made, and
+ * relp_trial_stats reports 0 pivots of room.
+ *
+ * relp_trial_end(h, 0) restores the handle to the bit: every getter and every *_stats call returns exactly what it returned before
+ * relp_trial_begin -- b, d, -obj, -pi, the basis, the flags, rhs, the costs, relp_nr_rows / relp_nr_columns, the trace with its
+ * count, the iterations, the degenerate pivots, relp_cut_stats, relp_rhs_stats, relp_cost_stats, relp_ranging_stats,
+ * relp_gomory_stats, relp_tab_flush_stats, relp_reinversions -- and every later call gives the bits it gives on a handle that never
+ * opened the trial.  Only relp_trial_stats and the profile timers move.  The PRICE partials are marked invalid and the record is
+ * re-armed, as the in-place calls do; the call synchronises.  What a cut added inside the trial left behind the old rows and
+ * columns is unreachable once the counts are back; the room stays.
+ * relp_trial_end(h, 1) drops the snapshot and leaves the state as it is; a pending re-inversion or a due flush happens at the next
+ * loop, as usual.  RELP_E_STATE without an open trial; RELP_E_ARG for a keep other than 0 and 1.
+ * All three: RELP_E_UNSUPPORTED on another or a sharded engine, RELP_E_STATE in phase 1.  Out of scope: trials on sharded or other
+ * engines, the primal loop or relp_add_columns inside a trial, nested trials. */
+relp_status_t relp_trial_begin(relp_engine_t *h);
+relp_status_t relp_trial_end(relp_engine_t *h, int32_t keep);   /* 0: roll back, 1: keep */
+/* out4 = { trials begun, trials rolled back, bytes the last snapshot held on the device, pivots the last trial could still have
+ * made when it ended (0: relp_run_dual stopped, or would have stopped, for want of room) }. */
+relp_status_t relp_trial_stats(const relp_engine_t *h, int64_t *out4);
+/* Strong branching over the trial scope, host code over relp_trial_begin, relp_add_cuts, relp_run_dual and relp_trial_end: no kernel
+ * of its own.  Entry k, r = rows[k], j = the basic column of row r, f0 = b_r - floor(b_r).  status[k], decided on the host from b
+ * and the basis:
+ *   0  evaluated
+ *   1  j is not a structural column (j >= the structural columns, or a kept artificial)
+ *   2  f0 < away or f0 > 1 - away                        (0 <= away < 0.5)
+ * A skipped entry gets objective = NaN, outcome = -1, pivots = 0 in both slots.  An evaluated entry takes slot 2k for down and
+ * 2k + 1 for up; each side is one trial: relp_trial_begin, relp_add_cuts of the single cut (down: x_j <= floor(b_r); up:
+ * -x_j <= -ceil(b_r)), relp_run_dual(max_pivots), the objective exactly as relp_get_objective returns it, relp_trial_end(0).
+ * outcome is RELP_OPTIMAL, RELP_INFEASIBLE (objective +inf) or RELP_RUNNING (the iteration limit); the dual objective is monotone,
+ * so the objective of a RELP_RUNNING slot is still a valid bound on the child.  pivots = the dual pivots made.
+ * Before the first trial, outside any trial, and only when some entry is evaluated: without room for one more cut the room is grown
+ * as relp_add_cuts itself would grow it (to max(cuts + 1, twice the room, 16): relp_reserve_cuts); and if since_flush + max_pivots
+ * + 1 > update_block (since_flush: the iterations the host has enqueued since the last flush) the open block is flushed once,
+ * exactly as relp_flush does.  The call is otherwise read-only in the sense of relp_row_ratios: b, d, the basis, the flags, the
+ * trace, every count and every *_stats but relp_trial_stats (two trials per evaluated entry) keep their bits.
+ * Refusals leave nothing written.  RELP_E_ARG: a row out of range, count < 0, a missing array, max_pivots < 1 or
+ * > update_block - 1, away outside [0, 0.5).  RELP_E_STATE: phase 1, an open trial, a basis that is not dual feasible (as
+ * relp_run_dual).  RELP_E_UNSUPPORTED: another or a sharded engine.  count == 0 is a no-op.  Out of scope: a branch-and-bound
+ * driver, and any choice of which rows to branch on. */
+relp_status_t relp_strong_branch(relp_engine_t *h, const int32_t *rows, int32_t count, int32_t max_pivots, double away,
+                                 double *objective /* 2*count */, int32_t *outcome /* 2*count */,
+                                 int32_t *pivots /* 2*count */, int32_t *status /* count */);
 /* InverseMaintener::from_basis (carry/mod.rs:428-463): warm start from provider column indices,
  * one per row; switches to phase 2.  RELP_ENGINE_LU: any basis (factorise, b = FTRAN(rhs), -pi = BTRAN(-c_B));
  * RELP_ENGINE_REVISED: any basis (basis_inverse_rows.rs:103-129: LU - factorised on the host like every

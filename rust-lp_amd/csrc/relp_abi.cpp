@@ -125,6 +125,13 @@ relp_status_t relp_gomory_cuts(relp_engine_t* h, const int32_t* rows, int32_t co
     return h ? H(h).gomory_cuts(rows, count, is_integer, kind, away, coefficients, rhs, fraction, status) : RELP_E_ARG;
 }
 relp_status_t relp_gomory_stats(const relp_engine_t* h, int64_t* out4) { return (h && out4) ? H(h).gomory_stats(out4) : RELP_E_ARG; }
+relp_status_t relp_trial_begin(relp_engine_t* h) { return h ? H(h).trial_begin() : RELP_E_ARG; }
+relp_status_t relp_trial_end(relp_engine_t* h, int32_t keep) { return h ? H(h).trial_end(keep) : RELP_E_ARG; }
+relp_status_t relp_trial_stats(const relp_engine_t* h, int64_t* out4) { return (h && out4) ? H(h).trial_stats(out4) : RELP_E_ARG; }
+relp_status_t relp_strong_branch(relp_engine_t* h, const int32_t* rows, int32_t count, int32_t max_pivots, double away, double* objective,
+                                 int32_t* outcome, int32_t* pivots, int32_t* status) {
+    return h ? H(h).strong_branch(rows, count, max_pivots, away, objective, outcome, pivots, status) : RELP_E_ARG;
+}
 relp_status_t relp_solve_relaxation(relp_engine_t* h, int64_t max_iters, int32_t* outcome) {
     return h ? H(h).solve_relaxation(max_iters, outcome) : RELP_E_ARG;
 }

@@ -117,6 +117,7 @@ Switches Switches::read() {
     s.retab_groups = std::max(0, num("RELP_RETAB_GROUPS", 0));
     s.tab_rhs_splits = std::max(0, num("RELP_TAB_RHS_SPLITS", 0));
     s.tab_cost_splits = std::max(0, num("RELP_TAB_COST_SPLITS", 0));
+    s.trial_memcpy = num("RELP_TRIAL_MEMCPY", 0) != 0;
     return s;
 }
 
@@ -575,6 +576,7 @@ void Engine::tableau_reprice() {
 }
 
 relp_status_t Engine::flush() {
+    if (const relp_status_t st = in_trial("relp_flush")) return st;
     tab_settle();
     if (cfg_.shard_count > 1 && block_ > 0 && !tableau_) {
         // the rows S' B0inv live on different ranks: with the collective hooks attached the library completes the
@@ -674,7 +676,9 @@ relp_status_t Engine::select_primal_pivot_row_of(const double* column, int32_t* 
 
 relp_status_t Engine::bring_into_basis(int32_t column, int32_t row, double cost, int32_t* leaving) {
     if (column < 0 || column >= nr_columns() || row < 0 || row >= lay_.m) return fail(RELP_E_ARG, "index out of range");
-    relp_status_t st = download_rec();
+    relp_status_t st = in_trial("relp_bring_into_basis");
+    if (st) return st;
+    st = download_rec();
     if (st) return st;
     double alpha_r = 0.0, b_r = 0.0; int32_t lv = 0;
     HIP_TRY(d_alpha_.download(&alpha_r, 1, stream_, row));
@@ -767,6 +771,7 @@ relp_status_t Engine::rescue_unbar_all() {
 // row (phase_one.rs:143 panics there, phase_two.rs:44 returns Unbounded) is believed only when the entering column really has no
 // entry worth pivoting on.
 relp_status_t Engine::run(int64_t max_iters, int64_t* done, int32_t* outcome) {
+    if (const relp_status_t st0 = in_trial("relp_run")) return st0;
     if (!cfg_.pivot_rescue || cfg_.shard_count > 1) return run_loop(max_iters, done, outcome);
     struct GuardScope { bool& g; GuardScope(bool& x) : g(x) { g = true; } ~GuardScope() { g = false; } } guard_scope(pivot_guard_on_);
     int64_t total = 0;
@@ -910,6 +915,7 @@ relp_status_t Engine::run_loop(int64_t max_iters, int64_t* done, int32_t* outcom
 relp_status_t Engine::solve_relaxation(int64_t max_iters, int32_t* outcome) {
     int32_t oc = RELP_RUNNING; int64_t done = 0, total = 0;
     relp_status_t st;
+    if ((st = in_trial("relp_solve_relaxation"))) return st;
     if (phase_ == 1) {
         if ((st = run(max_iters, &done, &oc))) return st;
         total += done;
@@ -997,32 +1003,19 @@ void Engine::enqueue_iteration_dual() {
 relp_status_t Engine::run_dual(int64_t max_iters, int64_t* done, int32_t* outcome) {
     relp_status_t st = dual_ready("relp_run_dual");
     if (st) return st;
-    tab_settle();
-    if ((st = edit_rec())) return st;
+    if ((st = check_dual_feasible("relp_run_dual"))) return st;
     const long long start = h_rec_->iterations;
-    {   // dual feasibility: PRICE finds no candidate among the non-basic columns
-        const SelectPartials sp = tab_partials(RELP_RULE_STEEPEST_DESCENT);
-        launch_tab_scan(tview(), sp, d_rec_, stream_);
-        launch_tab_select(tview(), sp, tab_scan_blocks(lay_.sc_hi - lay_.sc_lo), d_rec_, stream_);
-        if ((st = download_rec())) return st;
-        const bool dual_feasible = h_rec_->outcome == DEV_NO_CANDIDATE;
-        const int32_t q = h_rec_->q;
-        const double d_q = h_rec_->d_q;
-        h_rec_->outcome = DEV_RUNNING;
-        if ((st = upload_rec())) return st;
-        if (!dual_feasible) {
-            char msg[160];
-            std::snprintf(msg, sizeof msg, "relp_run_dual: the basis is not dual feasible (column %d has reduced cost %.3e)", (int)q, d_q);
-            return fail(RELP_E_STATE, msg);
-        }
-    }
+    const int64_t since_flush_start = since_flush_;
     tab_partials_valid_ = false;
     int64_t next_poll = cfg_.poll_interval;
     {
     LoopScope loop(*this);
     for (int64_t it = 0; it < max_iters && h_rec_->outcome == DEV_RUNNING; ++it) {
+        // Inside a trial nothing may flush or re-invert (T0 and the pending rows of R0 are not in the snapshot): the loop pivots
+        // only while the block is not left full, and the interval is suspended.
+        if (trial_open_ && since_flush_ + 1 >= block_) break;
         enqueue_iteration_dual();
-        if (reinvert_interval_ > 0 && ++since_reinvert_ >= reinvert_interval_) {
+        if (!trial_open_ && reinvert_interval_ > 0 && ++since_reinvert_ >= reinvert_interval_) {
             if ((st = download_rec())) return st;
             if (h_rec_->outcome != DEV_RUNNING) break;
             if ((st = reinvert())) return st;
@@ -1041,8 +1034,33 @@ relp_status_t Engine::run_dual(int64_t max_iters, int64_t* done, int32_t* outcom
     else if (h_rec_->outcome == DEV_NO_CANDIDATE) oc = RELP_INFEASIBLE;    // an infeasible row without an entry to pivot on
     if (done) *done = h_rec_->iterations - start;
     if (outcome) *outcome = oc;
+    // (inside a trial the room is counted in pivots made, not in iterations enqueued: the no-op iterations up to a poll use none)
+    if (trial_open_) since_flush_ = since_flush_start + (h_rec_->iterations - start);
     h_rec_->outcome = DEV_RUNNING;                                          // (a primal loop may follow on this handle)
     return upload_rec();
+}
+
+// Dual feasibility of the current basis: PRICE finds no candidate among the non-basic columns.  Settles, re-arms the record and
+// leaves it downloaded; the PRICE partials hold the scan's.
+relp_status_t Engine::check_dual_feasible(const char* what) {
+    tab_settle();
+    relp_status_t st = edit_rec();
+    if (st) return st;
+    const SelectPartials sp = tab_partials(RELP_RULE_STEEPEST_DESCENT);
+    launch_tab_scan(tview(), sp, d_rec_, stream_);
+    launch_tab_select(tview(), sp, tab_scan_blocks(lay_.sc_hi - lay_.sc_lo), d_rec_, stream_);
+    if ((st = download_rec())) return st;
+    const bool dual_feasible = h_rec_->outcome == DEV_NO_CANDIDATE;
+    const int32_t q = h_rec_->q;
+    const double d_q = h_rec_->d_q;
+    h_rec_->outcome = DEV_RUNNING;
+    if ((st = upload_rec())) return st;
+    if (!dual_feasible) {
+        char msg[160];
+        std::snprintf(msg, sizeof msg, "%s: the basis is not dual feasible (column %d has reduced cost %.3e)", what, (int)q, d_q);
+        return fail(RELP_E_STATE, msg);
+    }
+    return RELP_OK;
 }
 
 relp_status_t Engine::select_dual_pivot_row(int32_t* found, int32_t* row) {
@@ -1079,6 +1097,7 @@ relp_status_t Engine::select_dual_pivot_column(int32_t row, int32_t* found, int3
 relp_status_t Engine::set_right_hand_side(const double* rhs_m) {
     relp_status_t st = dual_ready("relp_set_right_hand_side");
     if (st) return st;
+    if ((st = in_trial("relp_set_right_hand_side"))) return st;
     if ((st = edit_rec())) return st;
     std::vector<double> keep(rhs_m, rhs_m + lay_.m);
     keep.swap(lay_.rhs);
@@ -1230,6 +1249,7 @@ relp_status_t Engine::change_cost(const int32_t* columns, const double* values, 
 relp_status_t Engine::set_cost(const double* cost_n) {
     relp_status_t st = dual_ready("relp_set_cost");
     if (st) return st;
+    if ((st = in_trial("relp_set_cost"))) return st;
     for (int32_t j = 0; j < lay_.nr_normal; ++j)
         if (!std::isfinite(cost_n[j])) return fail(RELP_E_ARG, "relp_set_cost: a value that is not finite");
     tab_settle();
@@ -1359,8 +1379,9 @@ relp_status_t Engine::grow_tableau(int32_t cut_room, int32_t col_room) {
 }
 
 relp_status_t Engine::reserve_cuts(int32_t rows) {
-    const relp_status_t st = dual_ready("relp_reserve_cuts");
+    relp_status_t st = dual_ready("relp_reserve_cuts");
     if (st) return st;
+    if ((st = in_trial("relp_reserve_cuts"))) return st;
     if (rows < 0) return fail(RELP_E_ARG, "relp_reserve_cuts: rows < 0");
     return grow_for_cuts(rows);
 }
@@ -1377,6 +1398,7 @@ relp_status_t Engine::add_cuts(int32_t count, const int64_t* row_ptr, const int3
     if ((st = lay_.check_cuts(count, row_ptr, col_idx, values, rhs, &err_))) return st;
     if (count == 0) return RELP_OK;
     if ((int64_t)lay_.nr_cuts + count > cut_room_) {
+        if ((st = in_trial("relp_add_cuts beyond the reserved room"))) return st;
         const int64_t want = std::max<int64_t>({(int64_t)lay_.nr_cuts + count, 2 * (int64_t)cut_room_, 16});
         if (want > INT32_MAX / 2) return fail(RELP_E_ARG, "relp_add_cuts: too many cuts");
         if ((st = grow_for_cuts((int32_t)want))) return st;
@@ -1449,8 +1471,9 @@ relp_status_t Engine::add_cuts(int32_t count, const int64_t* row_ptr, const int3
 relp_status_t Engine::cut_stats(int64_t* out4) const { return in_place_stats(out4, lay_.nr_cuts, cut_room_, cut_last_rows_, cut_last_p_); }
 
 relp_status_t Engine::reserve_columns(int32_t columns) {
-    const relp_status_t st = dual_ready("relp_reserve_columns");
+    relp_status_t st = dual_ready("relp_reserve_columns");
     if (st) return st;
+    if ((st = in_trial("relp_reserve_columns"))) return st;
     if (columns < 0) return fail(RELP_E_ARG, "relp_reserve_columns: columns < 0");
     return grow_tableau(cut_room_, columns);
 }
@@ -1465,6 +1488,7 @@ relp_status_t Engine::reserve_columns(int32_t columns) {
 relp_status_t Engine::add_columns(int32_t count, const int64_t* col_ptr, const int32_t* row_idx, const double* values, const double* cost) {
     relp_status_t st = dual_ready("relp_add_columns");
     if (st) return st;
+    if ((st = in_trial("relp_add_columns"))) return st;
     if (count > kTabColTile * 65535) return fail(RELP_E_ARG, "relp_add_columns: more than 524,280 columns in one call");       // (the grid's second dimension)
     if ((st = lay_.check_columns(count, col_ptr, row_idx, values, cost, &err_))) return st;
     if (count == 0) return RELP_OK;
@@ -1636,6 +1660,7 @@ relp_status_t Engine::flush_for_removal() {
 relp_status_t Engine::remove_cuts(const int32_t* rows, int32_t count) {
     relp_status_t st = dual_ready("relp_remove_cuts");
     if (st) return st;
+    if ((st = in_trial("relp_remove_cuts"))) return st;
     if (count < 0 || (count > 0 && !rows)) return lay_.check_remove_cuts(rows, count, {}, &err_);
     if (count == 0) return RELP_OK;
     tab_settle();
@@ -1665,6 +1690,7 @@ relp_status_t Engine::remove_cuts(const int32_t* rows, int32_t count) {
 relp_status_t Engine::remove_columns(const int32_t* columns, int32_t count) {
     relp_status_t st = dual_ready("relp_remove_columns");
     if (st) return st;
+    if ((st = in_trial("relp_remove_columns"))) return st;
     if (count < 0 || (count > 0 && !columns)) return lay_.check_remove_columns(columns, count, {}, &err_);
     if (count == 0) return RELP_OK;
     tab_settle();
@@ -2107,6 +2133,7 @@ relp_status_t Engine::remove_rows(const std::vector<int32_t>& rows) {
 
 relp_status_t Engine::set_reinversion_interval(int64_t pivots) {
     if (pivots < 0) return fail(RELP_E_ARG, "negative interval");
+    if (const relp_status_t st = in_trial("relp_set_reinversion_interval")) return st;
     if (pivots > 0 && (lu_ || cfg_.shard_count > 1))
         return fail(RELP_E_UNSUPPORTED, "re-inversion is for the unsharded revised and tableau engines (the LU engine refactorises anyway)");
     reinvert_interval_ = pivots;
@@ -2313,6 +2340,7 @@ relp_status_t Engine::from_basis(const int32_t* basis_columns) {
     // InverseMaintener::from_basis (carry/mod.rs:428-463): any basis on the LU and the revised engine (the
     // latter factorises on the host and runs the m unit solves on the device; slack bases are a signed permutation and take a shortcut).
     if (cfg_.shard_count > 1) return fail(RELP_E_UNSUPPORTED, "from_basis in sharded mode");
+    if (const relp_status_t st = in_trial("relp_from_basis")) return st;
     const std::vector<int32_t> basis(basis_columns, basis_columns + lay_.m);
     std::vector<uint8_t> flags;
     relp_status_t st;
@@ -2426,6 +2454,7 @@ relp_status_t Engine::get_basis_indices(int32_t* out) { HIP_RETURN(d_basis_.down
 
 relp_status_t Engine::get_basis_inverse(double* out) {
     if (cfg_.shard_count > 1) return fail(RELP_E_UNSUPPORTED, "B^-1 is row-sharded");
+    if (const relp_status_t st = in_trial("relp_get_basis_inverse (it flushes the open block)")) return st;
     if (!lu_) enqueue_flush();
     if (lu_ || tableau_) {
         DeviceBuf<double> tmp;                             // (freed on every way out)

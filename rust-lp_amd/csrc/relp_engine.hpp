@@ -87,6 +87,7 @@ struct Switches {
     int retab_groups = 0;                                 // RELP_RETAB_GROUPS (0: not given)
     int tab_rhs_splits = 0;                               // RELP_TAB_RHS_SPLITS (0: the rule of tab_rhs_splits)
     int tab_cost_splits = 0;                              // RELP_TAB_COST_SPLITS (0: the rule of tab_cost_splits)
+    bool trial_memcpy = false;                            // RELP_TRIAL_MEMCPY
     static Switches read();
 };
 
@@ -162,6 +163,13 @@ class Engine : private EngineQueue {
     relp_status_t gomory_cuts(const int32_t* rows, int32_t count, const uint8_t* is_integer, int32_t kind, double away, double* coefficients,
                               double* rhs, double* fraction, int32_t* status);
     relp_status_t gomory_stats(int64_t* out4) const;
+    // a trial scope: everything a trial can change between two flushes is saved on the device (one launch) and on the host, and
+    // trial_end(0) puts it back to the bit; strong_branch is host code over it, relp_add_cuts and relp_run_dual
+    relp_status_t trial_begin();
+    relp_status_t trial_end(int32_t keep);
+    relp_status_t trial_stats(int64_t* out4) const;
+    relp_status_t strong_branch(const int32_t* rows, int32_t count, int32_t max_pivots, double away, double* objective, int32_t* outcome,
+                                int32_t* pivots, int32_t* status);
     int32_t engine_kind() const { return lay_.engine; }
     relp_status_t robust_stats(int64_t* out4) const;
     relp_status_t solve_relaxation(int64_t max_iters, int32_t* outcome);
@@ -375,6 +383,36 @@ class Engine : private EngineQueue {
     DeviceBuf<uint8_t> d_gom_int_;
     int64_t gom_calls_ = 0, gom_entries_ = 0, gom_cuts_ = 0;
     int32_t gom_last_p_ = 0;
+    // relp_trial_begin / relp_trial_end (relp_engine_trial.cpp): the plan of the open trial's snapshot (relp_trial.hpp) over
+    // d_trial_ -- one device buffer, allocated at the first begin, grown on demand --, the host side of the snapshot, and what
+    // relp_trial_stats reports.  in_trial(what): RELP_E_STATE for a call that flushes, rebuilds, re-allocates or compacts.
+    struct TrialExtents { int32_t m = 0, n_store = 0, n = 0, nr_normal = 0, p = 0; };   // rows, stored / tableau / structural columns, pending rows at the begin
+    struct TrialHost {
+        TrialExtents extents;
+        Layout lay;
+        int32_t n_store = 0, n_alloc = 0;
+        std::vector<int32_t> idcol_h;
+        std::vector<double> cost_store_h;
+        int64_t since_flush = 0, since_reinvert = 0, reinvert_interval = 0, reinversions = 0;
+        int32_t flushes_since_reprice = 0;
+        double last_reinvert_drift = -1.0;
+        bool retab_done = false;
+        int64_t rhs_changes = 0, rhs_columns = 0, cost_changes = 0, cost_rows = 0, rm_cuts = 0, rm_columns = 0, rm_last_moved = 0;
+        int64_t rng_ratio_calls = 0, rng_ratio_rows = 0, rng_ranging_calls = 0, gom_calls = 0, gom_entries = 0, gom_cuts = 0;
+        int32_t rhs_last_p = 0, rhs_last_splits = 0, cost_last_p = 0, cost_last_splits = 0, cut_last_rows = 0, cut_last_p = 0;
+        int32_t col_last_cols = 0, col_last_p = 0, rm_last_p = 0, rng_last_p = 0, gom_last_p = 0;
+    };
+    bool trial_open_ = false;
+    TrialPlan trial_plan_;
+    DeviceBuf<char> d_trial_;
+    TrialHost trial_host_;
+    int64_t trials_begun_ = 0, trials_rolled_back_ = 0, trial_last_bytes_ = 0, trial_last_room_ = 0;
+    relp_status_t in_trial(const char* what);
+    TrialPlan trial_layout(const TrialExtents& x, bool* ok);
+    relp_status_t trial_copy(bool save);
+    void trial_host_save();
+    void trial_host_restore();
+    relp_status_t check_dual_feasible(const char* what);   // the front of relp_run_dual: PRICE finds no candidate, or RELP_E_STATE
     // sparse LU engine (cfg.engine == RELP_ENGINE_LU): B^-1 = (I + W S') (L U)^-1, refactor every block_ pivots
     bool lu_ = false;
     std::vector<int64_t> hc_ptr_; std::vector<int32_t> hc_idx_; std::vector<double> hc_val_;   // host CSC of A

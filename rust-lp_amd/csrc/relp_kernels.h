@@ -12,6 +12,7 @@
 #include <stdint.h>
 
 #include "relp_layout.hpp"   // kWrappedArtificialBase
+#include "relp_trial.hpp"    // TrialTable
 
 namespace relp {
 
@@ -643,6 +644,13 @@ struct GomoryCuts {
 // where c has a bound row); writes g].  No atomics, fixed orders: the same call on the same state gives the same bits.
 void launch_tab_gomory(const TableauView& tv, const DeferredUpdate& du, const ColumnTable& ct, const uint8_t* in_basis, Tolerances tol,
                        const GomoryCuts& gc, int32_t p, hipStream_t s);
+// The snapshot of a trial (relp_trial_begin / relp_trial_end), either direction: the segments of `t` (relp_trial.hpp: at most
+// kTrialMaxSegments, every src, dst 16-byte aligned, no overlap) copied src -> dst in one launch of k_tab_trial_copy.  The grid
+// strides over the 16-byte units of all segments together -- 16-byte loads and stores, kTrialB units per thread and stride
+// iteration with every load issued before the first store --, one workgroup per 256 units up to kTabTrialGrid (the device's share:
+// 256 CUs x 8 workgroups of 256 threads); each segment's tail of bytes % 16 bytes goes bytewise.  No atomics, no LDS.
+static constexpr int32_t kTabTrialGrid = 2048;
+void launch_tab_trial_copy(const TrialTable& t, hipStream_t s);
 
 // ---- sparse LU engine ------------------------------------------------------------------------------
 // PRICE over CSC columns (thread per column), partial argmin per 256 columns

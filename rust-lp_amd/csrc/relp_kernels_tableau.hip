@@ -1740,6 +1740,61 @@ __global__ __launch_bounds__(kThreads) void k_tab_gomory_structural(TableauView 
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// The snapshot of a trial (relp_trial_begin / relp_trial_end): up to kTrialMaxSegments copies src -> dst in ONE launch, the table
+// passed by value (relp_trial.hpp: the planner).  The grid strides over the 16-byte units of all segments together: unit u belongs
+// to the segment s with unit_end[s - 1] <= u < unit_end[s], found by a walk over the table that is the same for every lane (the
+// table is read through scalar loads, never indexed by a lane).  Per stride iteration a thread owns kTrialB units a grid stride
+// apart: their loads are all issued before the first store, as in k_tab_drop_rows.  The bytes % 16 bytes behind the last unit of
+// a segment are copied bytewise by the first lanes of workgroup 0.  Sources and destinations never overlap (live arrays against
+// the snapshot buffer).  Copies only: no atomics, no LDS, no communication between workgroups.
+// ------------------------------------------------------------------------------------------------
+static constexpr int kTrialB = 4;
+// unit u of the table: its source and destination, nullptr past the last unit (the walk is the same for every lane)
+__device__ __forceinline__ void trial_locate(const TrialTable& t, int64_t u, const uint4*& src, uint4*& dst) {
+    src = nullptr; dst = nullptr;
+    int64_t begin = 0;
+    for (int s = 0; s < t.count; ++s) {
+        const int64_t end = t.unit_end[s];
+        if (u >= begin && u < end) {
+            src = static_cast<const uint4*>(t.seg[s].src) + (u - begin);
+            dst = static_cast<uint4*>(t.seg[s].dst) + (u - begin);
+        }
+        begin = end;
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void k_tab_trial_copy(TrialTable t) {
+    static_assert(kTrialB == 4, "the four units of a stride iteration are written out below");
+    const int64_t total = t.count > 0 ? t.unit_end[t.count - 1] : 0;
+    const int64_t stride = (int64_t)gridDim.x * kThreads;
+    const int64_t first = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    for (int64_t base = first; base < total; base += stride * kTrialB) {
+        const uint4 *s0, *s1, *s2, *s3;
+        uint4 *d0, *d1, *d2, *d3;
+        trial_locate(t, base, s0, d0);
+        trial_locate(t, base + stride, s1, d1);
+        trial_locate(t, base + 2 * stride, s2, d2);
+        trial_locate(t, base + 3 * stride, s3, d3);
+        uint4 v0 = make_uint4(0, 0, 0, 0), v1 = v0, v2 = v0, v3 = v0;
+        if (s0) v0 = *s0;
+        if (s1) v1 = *s1;
+        if (s2) v2 = *s2;
+        if (s3) v3 = *s3;
+        if (s0) *d0 = v0;
+        if (s1) *d1 = v1;
+        if (s2) *d2 = v2;
+        if (s3) *d3 = v3;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < kTrialUnit) {
+        for (int s = 0; s < t.count; ++s) {
+            const int64_t bytes = t.seg[s].bytes, whole = bytes / kTrialUnit * kTrialUnit;
+            if (whole + (int64_t)threadIdx.x < bytes)
+                static_cast<uint8_t*>(t.seg[s].dst)[whole + threadIdx.x] = static_cast<const uint8_t*>(t.seg[s].src)[whole + threadIdx.x];
+        }
+    }
+}
+
 int32_t tab_scan_blocks(int32_t n_owned_columns) { return cdiv(n_owned_columns, kThreads); }
 
 // The batch sizes of for_pending the kernels are instantiated for (DeferredUpdate::batch, RELP_TAB_LOAD_BATCH).  1 is the
@@ -2076,6 +2131,14 @@ void launch_tab_gomory(const TableauView& tv, const DeferredUpdate& du, const Co
             hipLaunchKernelGGL((k_tab_gomory_structural<decltype(B)::value, kTabRatioChunk>), dim3(gc.nr_normal, chunks), dim3(kThreads), 0, s,
                                tv, ct, gc);
     });
+}
+
+void launch_tab_trial_copy(const TrialTable& t, hipStream_t s) {
+    if (t.count < 1 || t.count > kTrialMaxSegments) return;
+    const int64_t units = t.unit_end[t.count - 1];
+    // one workgroup per 256 units up to the device's share (kTabTrialGrid); a table of tails alone still needs workgroup 0
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((units + kThreads - 1) / kThreads, kTabTrialGrid));
+    hipLaunchKernelGGL(k_tab_trial_copy, dim3(grid), dim3(kThreads), 0, s, t);
 }
 
 }  // namespace relp

@@ -31,6 +31,8 @@ RUNNING, OPTIMAL, UNBOUNDED, INFEASIBLE, PHASE_ONE_DONE, NO_ROW_PHASE_ONE = rang
 # kind of relp_gomory_cuts, and its status per list entry
 GOMORY_FRACTIONAL, GOMORY_MIXED = 0, 1
 GOMORY_CUT, GOMORY_NOT_INTEGER, GOMORY_FRACTION, GOMORY_ARTIFICIAL, GOMORY_CONTINUOUS = range(5)
+# status of relp_strong_branch per list entry
+BRANCH_EVALUATED, BRANCH_NOT_STRUCTURAL, BRANCH_FRACTION = range(3)
 OUTCOME_NAMES = {RUNNING: "running", OPTIMAL: "optimal", UNBOUNDED: "unbounded", INFEASIBLE: "infeasible",
                  PHASE_ONE_DONE: "phase_one_done", NO_ROW_PHASE_ONE: "no_row_phase_one"}
 # relp_kernel_id_t
@@ -118,6 +120,11 @@ _SIGNATURES = {
     "relp_gomory_cuts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p]),
     "relp_gomory_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "relp_trial_begin": (C.c_int, [C.c_void_p]),
+    "relp_trial_end": (C.c_int, [C.c_void_p, C.c_int32]),
+    "relp_trial_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "relp_strong_branch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
     "relp_solve_relaxation": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]),
     "relp_from_basis": (C.c_int, [C.c_void_p, C.c_void_p]),
     "relp_flush": (C.c_int, [C.c_void_p]),
@@ -654,6 +661,47 @@ class Tableau:
         self._ck(self._lib.relp_gomory_stats(self._h, out))
         return tuple(int(x) for x in out)
 
+    # -- trials (tableau engine, phase 2; beyond the reference) ---------------------------------
+    def trial_begin(self) -> None:
+        """Opens a trial (relp_trial_begin): what ``change_right_hand_side``, ``set_upper_bound``, ``change_cost``, ``add_cuts``
+        within the reserved room and ``run_dual`` can change is saved -- no flush, no copy of the tableau -- and ``trial_end()``
+        puts it back to the bit.  Inside a trial ``run_dual`` pivots only while the update block has room and never flushes or
+        re-inverts; whatever flushes, rebuilds, re-allocates or compacts is refused.  Trials do not nest."""
+        self._ck(self._lib.relp_trial_begin(self._h))
+
+    def trial_end(self, keep: bool = False) -> None:
+        """Ends the open trial (relp_trial_end): ``keep=False`` restores every getter and every ``*_stats`` to the bit,
+        ``keep=True`` drops the snapshot and leaves the state as it is."""
+        self._ck(self._lib.relp_trial_end(self._h, 1 if keep else 0))
+
+    def trial_stats(self) -> Tuple[int, int, int, int]:
+        """(trials begun, trials rolled back, bytes the last snapshot held, pivots the last trial could still have made when it
+        ended); relp_trial_stats."""
+        out = (C.c_int64 * 4)()
+        self._ck(self._lib.relp_trial_stats(self._h, out))
+        return tuple(int(x) for x in out)
+
+    def trial(self) -> "Trial":
+        """``with t.trial() as scope: ...``: a trial that is rolled back on exit unless ``scope.keep()`` was called."""
+        return Trial(self)
+
+    def strong_branch(self, rows, max_pivots: int, away: float = 1e-6):
+        """(objective, outcome, pivots, status) of relp_strong_branch: per listed engine row r with a fractional structural basic
+        column x_j, ``objective[k]`` / ``outcome[k]`` / ``pivots[k]`` hold (down, up): the child LPs x_j <= floor(b_r) and
+        x_j >= ceil(b_r) after at most ``max_pivots`` dual pivots each, rolled back afterwards.  outcome OPTIMAL, INFEASIBLE
+        (objective inf) or RUNNING (the objective is still a valid bound: the dual objective is monotone).  ``status[k]``:
+        BRANCH_EVALUATED, BRANCH_NOT_STRUCTURAL or BRANCH_FRACTION (skipped: nan, -1, 0).  May grow the room for one cut and
+        flush the open block once before the first trial; read-only otherwise."""
+        r = np.ascontiguousarray(rows, dtype=np.int32)
+        if r.ndim != 1:
+            raise ValueError("rows must be one-dimensional")
+        n = r.shape[0]
+        objective, outcome = np.full((n, 2), np.nan), np.full((n, 2), -1, dtype=np.int32)
+        pivots, status = np.zeros((n, 2), dtype=np.int32), np.full(n, -1, dtype=np.int32)
+        self._ck(self._lib.relp_strong_branch(self._h, r.ctypes.data, n, int(max_pivots), float(away), objective.ctypes.data,
+                                              outcome.ctypes.data, pivots.ctypes.data, status.ctypes.data))
+        return objective, outcome, pivots, status
+
     def cost_ranging(self, columns):
         """(decrease, increase) per structural column j of ``columns``: the basis stays optimal while c_j stays within
         [c_j - decrease, c_j + increase].  A non-basic column gives (d_j, inf); a basic one the (down, up) of ``row_ratios`` on
@@ -920,6 +968,24 @@ def phase_two_dual(tableau: Tableau, max_iters: int = 1 << 40) -> int:
     if tableau.phase != 2:
         raise RelpError("tableau still has artificial variables")
     return tableau.run_dual(max_iters)[1]
+
+
+class Trial:
+    """The scope of ``Tableau.trial()``: begins a trial on entry and ends it on exit, rolled back unless ``keep()`` was called."""
+
+    def __init__(self, tableau: Tableau):
+        self._t, self._keep = tableau, False
+
+    def keep(self) -> None:
+        self._keep = True
+
+    def __enter__(self) -> "Trial":
+        self._t.trial_begin()
+        return self
+
+    def __exit__(self, *exc) -> bool:
+        self._t.trial_end(self._keep)
+        return False
 
 
 def gomory_rounds(tableau: Tableau, is_integer=None, max_rounds: int = 20, cuts_per_round: int = 3, kind: int = GOMORY_FRACTIONAL,
