@@ -465,6 +465,49 @@ class Tableau {
                               out.status.data()));
         return out;
     }
+    // A pool of candidate columns kept on the device (relp_pool_create .. relp_pool_stats): priced against the duals as they stand,
+    // the winners picked on the device, the chosen ones added as add_columns adds them without their coefficients going through the
+    // host again.  Freed with the Pool object; a Pool must not outlive its Tableau (the handle frees the pools still alive).
+    class Pool {
+      public:
+        Pool(Pool&& o) noexcept : h_(o.h_), p_(o.p_), count_(o.count_) { o.p_ = nullptr; }
+        Pool(const Pool&) = delete;
+        Pool& operator=(const Pool&) = delete;
+        ~Pool() { if (p_) (void)relp_pool_destroy(h_, p_); }
+        int32_t count() const { return count_; }
+        // relp_pool_reduced_costs: d_k = c_k + sum_i (-pi)_i a_k[i] of every pool column, the bits add_columns would give it now
+        std::vector<double> reduced_costs() { std::vector<double> out((size_t)count_); ck(relp_pool_reduced_costs(h_, p_, out.data())); return out; }
+        // relp_pool_price: per share of ceil(count / segments) pool indices the active column with the smallest d_k < -tol
+        struct Winners { std::vector<int32_t> ids; std::vector<double> d; };
+        Winners price(int32_t segments = 1, double tol = 1e-7) {
+            const size_t room = (size_t)(segments > 0 ? segments : 1);
+            Winners out{std::vector<int32_t>(room), std::vector<double>(room)};
+            int32_t found = 0;
+            ck(relp_pool_price(h_, p_, segments, tol, out.ids.data(), out.d.data(), &found));
+            out.ids.resize((size_t)found); out.d.resize((size_t)found);
+            return out;
+        }
+        // relp_pool_add: the listed pool columns become the columns nr_columns() + k of the tableau, non-basic; their flags are cleared
+        void add(const std::vector<int32_t>& ids) { ck(relp_pool_add(h_, p_, ids.data(), (int32_t)ids.size())); }
+        // relp_pool_set_active: an inactive column is priced but never wins
+        void set_active(const std::vector<int32_t>& ids, bool flag) { ck(relp_pool_set_active(h_, p_, ids.data(), (int32_t)ids.size(), flag ? 1 : 0)); }
+        // relp_pool_stats: {pool columns, nonzeros held, entries stored on the device with padding, price calls so far}
+        std::array<int64_t, 4> stats() const { std::array<int64_t, 4> out{}; ck(relp_pool_stats(h_, p_, out.data())); return out; }
+
+      private:
+        friend class Tableau;
+        Pool(relp_engine_t* h, relp_pool_t* p, int32_t count) : h_(h), p_(p), count_(count) {}
+        void ck(relp_status_t st) const { if (st != RELP_OK) throw Error(st, relp_last_error(h_)); }
+        relp_engine_t* h_; relp_pool_t* p_; int32_t count_;
+    };
+    Pool pool(const std::vector<int64_t>& col_ptr, const std::vector<int32_t>& row_idx, const std::vector<double>& values,
+              const std::vector<double>& cost) {
+        if (col_ptr.size() != cost.size() + 1) throw Error(RELP_E_ARG, "col_ptr has one entry more than there are columns");
+        if (row_idx.size() != values.size() || (int64_t)values.size() < col_ptr.back()) throw Error(RELP_E_ARG, "one value per row index, col_ptr within them");
+        relp_pool_t* p = nullptr;
+        ck(relp_pool_create(h_, (int32_t)cost.size(), col_ptr.data(), row_idx.data(), values.data(), cost.data(), &p));
+        return Pool(h_, p, (int32_t)cost.size());
+    }
     // ---- one LP on several GPUs (no counterpart in the reference, which is single-threaded) ---------------------
     // Options::shard(rank, count) at construction, the owned structural columns in `MatrixData` (relp_shard_plan);
     // rank 0 makes the RCCL id, the host program hands it to every rank, every rank attaches, then the loop runs

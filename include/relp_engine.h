@@ -569,6 +569,74 @@ relp_status_t relp_trial_stats(const relp_engine_t *h, int64_t *out4);
 relp_status_t relp_strong_branch(relp_engine_t *h, const int32_t *rows, int32_t count, int32_t max_pivots, double away,
                                  double *objective /* 2*count */, int32_t *outcome /* 2*count */,
                                  int32_t *pivots /* 2*count */, int32_t *status /* count */);
+/* A pool of candidate columns kept ON THE DEVICE, priced and added in place (no counterpart in the reference): the master problem
+ * of a column-generation scheme (cutting stock, crew pairing, Dantzig-Wolfe) holds many candidate columns, prices all of them
+ * every round and adds a handful.  The loop: relp_run, relp_pool_price, relp_pool_add of the winners, until nothing prices out.
+ * Pricing needs no download of d and no host loop, and the add does not send the coefficients through the host again.
+ * relp_pool_create: `count` columns x >= 0 in CSC over the engine rows in their current order, exactly the argument of
+ * relp_add_columns, with its checks and refusals (RELP_E_ARG, no pool: count < 0, a missing array, a col_ptr that does not ascend
+ * from 0, a row outside [0, relp_nr_rows()), a row named twice in one column, a coefficient or cost that is not finite).  Explicit
+ * zeros are dropped, a column without entries is accepted, count == 0 gives an empty pool.  The pool is copied to the device as
+ * sliced ELL -- 64 columns per slice, entry-major inside a slice, rows ascending inside a column, every slice padded to its longest
+ * column -- and a host copy is kept for the layout and the later rebuilds.  The pool belongs to the handle: relp_pool_destroy frees
+ * it, relp_engine_destroy frees the pools still alive; a handle may hold several.  A fresh pool has every column active.
+ * Rows: the pool remembers rows_at_create = relp_nr_rows().  Cut rows added later (relp_add_cuts) have coefficient 0 in every pool
+ * column, and removing such rows again (relp_remove_cuts of rows >= rows_at_create) leaves the pool valid.  A relp_remove_cuts that
+ * takes out an engine row below rows_at_create makes the pool STALE: relp_pool_price, relp_pool_reduced_costs and relp_pool_add
+ * then return RELP_E_STATE with nothing written (relp_last_error says why); destroy it and create a new one.  The rollback of a
+ * trial takes rows out too: relp_trial_end(h, 0) takes back the cut rows added inside the trial, so a pool created INSIDE that trial
+ * after such a cut (rows_at_create above the rows the rollback leaves) is stale from the rollback on, for good -- a cut added later
+ * in the same place is another row.  Pools created before the trial, or inside it before its cuts, and every pool of a trial that is
+ * kept (relp_trial_end(h, 1)) stay valid.  Pools are no part of a trial's snapshot: a pool created or destroyed inside a trial stays
+ * created or destroyed, and activity flags set inside a trial (relp_pool_set_active) survive the rollback.
+ * relp_pool_reduced_costs: out[k], for every pool column k, active or not,
+ *     d_k = c_k + sum_i (-pi)_i * a_k[i]        (i ascending over the column's nonzero entries, ONE fma chain from c_k,
+ *                                                (-pi)_i = d[idcol(i)] - cost_store[idcol(i)] rounded once: relp_get_minus_pi)
+ * which is the arithmetic relp_add_columns uses for d[new_k]: d_k has the bits the column's reduced cost would have after
+ * relp_add_columns at this moment.  Read-only in the sense of relp_row_ratios: nothing is flushed, and T0, R0, W, d, b, the basis,
+ * the flags, the PRICE partials, the record, the trace and every other *_stats keep their bits.  Neither dual nor primal
+ * feasibility is required; allowed inside a trial.  No atomics: the same call on the same state gives the same bits.
+ * relp_pool_price: multiple pricing.  The pool indices [0, count) are cut into `segments` equal shares of ceil(count / segments)
+ * columns (the last shares may be short or empty; 1 <= segments <= count).  The winner of a share is its ACTIVE column with the
+ * smallest d_k among those with d_k < -tol (tol >= 0, finite; d_k == -tol is no candidate), the lowest pool index among equal
+ * d_k.  ids_out and d_out (room for `segments` entries each) receive the winners in ascending share order, compacted; *found is
+ * their number.  segments = 1: the most negative column; segments = count: every candidate.  The d are the bits of
+ * relp_pool_reduced_costs.  The winners are picked on the device and come down in one copy (beyond 4,096 segments: their number
+ * first, then the winners alone); the d vector never crosses the bus.  Read-only as above, allowed inside a trial.  RELP_E_ARG with
+ * nothing written: segments out of range, a tol that is negative or not finite, a missing array.  A pool without columns gives
+ * *found = 0 for any segments >= 1.  Priced in chunks of 256 columns per workgroup and share: meant for shares of hundreds of
+ * columns or more (segments = count works and launches a workgroup per column).
+ * relp_pool_set_active: the activity flag (0 or 1) of the listed pool columns, on the device.  RELP_E_ARG: an index outside the
+ * pool, an index named twice, another flag value, count < 0, a missing list.  Works on a stale pool too.
+ * relp_pool_add: the pool columns ids[0 .. count) (each once, any order) join the tableau exactly as relp_add_columns would add the
+ * same columns in the same order: column k becomes provider column relp_nr_columns() + k, non-basic, with the growth rule, the
+ * flags, the relp_column_stats bookkeeping and the inclusion in later rebuilds of relp_add_columns, and RELP_E_STATE inside a
+ * trial.  The activity flags of the added columns are cleared.  The bit contract: after the call every getter and every *_stats
+ * but relp_pool_stats returns exactly what it returns on a twin handle that called relp_add_columns with the host data of the same
+ * columns.  The operands of the add -- the ascending union list of identity columns of the touched rows, coef[entry][column],
+ * d[new], the costs and the columns' rows of the re-tabulation block -- are formed on the device from the device copy; the
+ * coefficient values are not uploaded again.  RELP_POOL_HOST_ADD=1 at relp_engine_create routes the call through relp_add_columns
+ * with the host copy (the control: the same bits).  RELP_E_ARG with nothing changed: an index outside the pool or named twice,
+ * count < 0, a missing list, more than 524,280 columns in one call.  count == 0 is a no-op.  RELP_E_HIP from this call means, as
+ * after a failed launch of a pivot, that the device may hold columns the layout does not: the handle is unusable (this includes the
+ * call's own cross-check of the device's union list against the host's, which cannot fail while the device copy is intact).  relp_remove_columns does not know the
+ * pool: a caller who takes an added column out again re-activates it with relp_pool_set_active.
+ * relp_pool_stats: out4 = { pool columns, nonzeros held (explicit zeros dropped), entries stored on the device (padding included),
+ * relp_pool_price calls so far (calls that returned RELP_OK; refused and failed ones are not counted) }.
+ * All seven: RELP_ENGINE_TABLEAU, unsharded, phase 2 -- RELP_E_UNSUPPORTED on another or a sharded engine, RELP_E_STATE in
+ * phase 1 -- and RELP_E_ARG for a pool that is not one of this handle's.  Out of scope: pools on sharded or other engines, pricing
+ * in phase 1, pools whose row space follows row removals, automatic re-activation on relp_remove_columns, changing the cost of a
+ * pool column. */
+typedef struct relp_pool relp_pool_t;
+relp_status_t relp_pool_create(relp_engine_t *h, int32_t count, const int64_t *col_ptr, const int32_t *row_idx, const double *values,
+                               const double *cost, relp_pool_t **pool);
+relp_status_t relp_pool_destroy(relp_engine_t *h, relp_pool_t *pool);
+relp_status_t relp_pool_set_active(relp_engine_t *h, relp_pool_t *pool, const int32_t *ids, int32_t count, int32_t flag);
+relp_status_t relp_pool_reduced_costs(relp_engine_t *h, relp_pool_t *pool, double *out_count);
+relp_status_t relp_pool_price(relp_engine_t *h, relp_pool_t *pool, int32_t segments, double tol, int32_t *ids_out /* segments */,
+                              double *d_out /* segments */, int32_t *found);
+relp_status_t relp_pool_add(relp_engine_t *h, relp_pool_t *pool, const int32_t *ids, int32_t count);
+relp_status_t relp_pool_stats(const relp_engine_t *h, const relp_pool_t *pool, int64_t *out4);
 /* InverseMaintener::from_basis (carry/mod.rs:428-463): warm start from provider column indices,
  * one per row; switches to phase 2.  RELP_ENGINE_LU: any basis (factorise, b = FTRAN(rhs), -pi = BTRAN(-c_B));
  * RELP_ENGINE_REVISED: any basis (basis_inverse_rows.rs:103-129: LU - factorised on the host like every

@@ -132,6 +132,20 @@ relp_status_t relp_strong_branch(relp_engine_t* h, const int32_t* rows, int32_t 
                                  int32_t* outcome, int32_t* pivots, int32_t* status) {
     return h ? H(h).strong_branch(rows, count, max_pivots, away, objective, outcome, pivots, status) : RELP_E_ARG;
 }
+relp_status_t relp_pool_create(relp_engine_t* h, int32_t count, const int64_t* col_ptr, const int32_t* row_idx, const double* values,
+                               const double* cost, relp_pool_t** pool) {
+    return h ? H(h).pool_create(count, col_ptr, row_idx, values, cost, pool) : RELP_E_ARG;
+}
+relp_status_t relp_pool_destroy(relp_engine_t* h, relp_pool_t* pool) { return h ? H(h).pool_destroy(pool) : RELP_E_ARG; }
+relp_status_t relp_pool_set_active(relp_engine_t* h, relp_pool_t* pool, const int32_t* ids, int32_t count, int32_t flag) {
+    return h ? H(h).pool_set_active(pool, ids, count, flag) : RELP_E_ARG;
+}
+relp_status_t relp_pool_reduced_costs(relp_engine_t* h, relp_pool_t* pool, double* out_count) { return h ? H(h).pool_reduced_costs(pool, out_count) : RELP_E_ARG; }
+relp_status_t relp_pool_price(relp_engine_t* h, relp_pool_t* pool, int32_t segments, double tol, int32_t* ids_out, double* d_out, int32_t* found) {
+    return h ? H(h).pool_price(pool, segments, tol, ids_out, d_out, found) : RELP_E_ARG;
+}
+relp_status_t relp_pool_add(relp_engine_t* h, relp_pool_t* pool, const int32_t* ids, int32_t count) { return h ? H(h).pool_add(pool, ids, count) : RELP_E_ARG; }
+relp_status_t relp_pool_stats(const relp_engine_t* h, const relp_pool_t* pool, int64_t* out4) { return (h && out4) ? H(h).pool_stats(pool, out4) : RELP_E_ARG; }
 relp_status_t relp_solve_relaxation(relp_engine_t* h, int64_t max_iters, int32_t* outcome) {
     return h ? H(h).solve_relaxation(max_iters, outcome) : RELP_E_ARG;
 }

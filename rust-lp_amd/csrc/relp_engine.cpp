@@ -118,6 +118,7 @@ Switches Switches::read() {
     s.tab_rhs_splits = std::max(0, num("RELP_TAB_RHS_SPLITS", 0));
     s.tab_cost_splits = std::max(0, num("RELP_TAB_COST_SPLITS", 0));
     s.trial_memcpy = num("RELP_TRIAL_MEMCPY", 0) != 0;
+    s.pool_host_add = num("RELP_POOL_HOST_ADD", 0) != 0;
     return s;
 }
 
@@ -1492,11 +1493,7 @@ relp_status_t Engine::add_columns(int32_t count, const int64_t* col_ptr, const i
     if (count > kTabColTile * 65535) return fail(RELP_E_ARG, "relp_add_columns: more than 524,280 columns in one call");       // (the grid's second dimension)
     if ((st = lay_.check_columns(count, col_ptr, row_idx, values, cost, &err_))) return st;
     if (count == 0) return RELP_OK;
-    if ((int64_t)lay_.nr_added + count > col_room_) {
-        const int64_t want = std::max<int64_t>({(int64_t)lay_.nr_added + count, 2 * (int64_t)col_room_, 16});
-        if (want > INT32_MAX / 2) return fail(RELP_E_ARG, "relp_add_columns: too many columns");
-        if ((st = grow_tableau(cut_room_, (int32_t)want))) return st;
-    }
+    if ((st = room_for_columns("relp_add_columns", count))) return st;
     int32_t p;
     if ((st = settled_pending(&p))) return st;
     const int32_t m = lay_.m, n_old = n_store_, added_old = lay_.nr_added;
@@ -1542,8 +1539,21 @@ relp_status_t Engine::add_columns(int32_t count, const int64_t* col_ptr, const i
     if (e == hipSuccess) launch_tab_add_columns(tv, deferred(), ca, p, ct, stream_);
     HIP_TRY(first_error(e, hipStreamSynchronize(stream_)));
     if (hipGetLastError() != hipSuccess) return fail(RELP_E_HIP, "relp_add_columns: a kernel launch failed");
+    return columns_added(count, col_ptr, row_idx, values, cost, entries, p);
+}
 
-    // the layout and the host mirrors follow (check_columns passed: add_columns cannot fail)
+// room for `count` more added columns: grown to max(added columns then in the tableau, 2 x the room so far, 16) when it lacks
+relp_status_t Engine::room_for_columns(const char* what, int32_t count) {
+    if ((int64_t)lay_.nr_added + count <= col_room_) return RELP_OK;
+    const int64_t want = std::max<int64_t>({(int64_t)lay_.nr_added + count, 2 * (int64_t)col_room_, 16});
+    if (want > INT32_MAX / 2) return fail(RELP_E_ARG, std::string(what) + ": too many columns");
+    return grow_tableau(cut_room_, (int32_t)want);
+}
+
+// the layout and the host mirrors follow the device (check_columns passed: Layout::add_columns cannot fail), the record is re-armed
+relp_status_t Engine::columns_added(int32_t count, const int64_t* col_ptr, const int32_t* row_idx, const double* values, const double* cost,
+                                    int32_t entries, int32_t p) {
+    const int32_t n_old = n_store_;
     (void)lay_.add_columns(count, col_ptr, row_idx, values, cost, &err_);
     cost_store_h_.resize((size_t)n_old + count);
     std::copy(cost, cost + count, cost_store_h_.begin() + n_old);
@@ -1684,6 +1694,7 @@ relp_status_t Engine::remove_cuts(const int32_t* rows, int32_t count) {
     // the layout follows (check_remove_cuts passed: remove_cuts cannot fail), then its tables on the device
     (void)lay_.remove_cuts(rows, count, basis, &err_);
     rm_cuts_ += count;
+    pools_mark_stale(rows, count);                     // (relp_pool.hpp: a row below a pool's rows_at_create went)
     return finish_removal();
 }
 

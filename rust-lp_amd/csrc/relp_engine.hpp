@@ -17,6 +17,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -28,6 +29,19 @@
 #include "relp_layout.hpp"
 #include "relp_lu.hpp"
 #include "relp_pack.hpp"
+
+// A column pool of a handle (relp_pool_create .. relp_pool_stats; relp_engine_pool.cpp).  The host copy (relp_pool.hpp) is what
+// Layout::add_columns and the rebuilds are given; the device copy is what the price and the add read.  Owned by its Engine.
+struct relp_pool {
+    relp::PoolImage image;
+    relp::DeviceBuf<int64_t> d_slice_ptr;
+    relp::DeviceBuf<int32_t> d_row, d_part_k;
+    relp::DeviceBuf<double> d_val, d_cost, d_all, d_part_d;   // (d_all, d_part_*, d_out: scratch of a price, allocated at the first one)
+    relp::DeviceBuf<uint8_t> d_active;
+    relp::DeviceBuf<char> d_out;                          // what a price downloads: the winners' d, their pool indices, their number
+    bool stale = false;                                   // an engine row below image.rows_at_create went (relp_remove_cuts, the rollback of a trial)
+    int64_t price_calls = 0;
+};
 
 namespace relp {
 
@@ -88,6 +102,7 @@ struct Switches {
     int tab_rhs_splits = 0;                               // RELP_TAB_RHS_SPLITS (0: the rule of tab_rhs_splits)
     int tab_cost_splits = 0;                              // RELP_TAB_COST_SPLITS (0: the rule of tab_cost_splits)
     bool trial_memcpy = false;                            // RELP_TRIAL_MEMCPY
+    bool pool_host_add = false;                           // RELP_POOL_HOST_ADD
     static Switches read();
 };
 
@@ -170,6 +185,16 @@ class Engine : private EngineQueue {
     relp_status_t trial_stats(int64_t* out4) const;
     relp_status_t strong_branch(const int32_t* rows, int32_t count, int32_t max_pivots, double away, double* objective, int32_t* outcome,
                                 int32_t* pivots, int32_t* status);
+    // a pool of candidate columns kept on the device (relp_engine_pool.cpp): priced there against -pi as it stands (read-only), its
+    // winners picked there, the chosen columns added as add_columns adds them, their coefficients never uploaded again
+    relp_status_t pool_create(int32_t count, const int64_t* col_ptr, const int32_t* row_idx, const double* values, const double* cost,
+                              relp_pool** out);
+    relp_status_t pool_destroy(relp_pool* pool);
+    relp_status_t pool_set_active(relp_pool* pool, const int32_t* ids, int32_t count, int32_t flag);
+    relp_status_t pool_reduced_costs(relp_pool* pool, double* out_count);
+    relp_status_t pool_price(relp_pool* pool, int32_t segments, double tol, int32_t* ids_out, double* d_out, int32_t* found);
+    relp_status_t pool_add(relp_pool* pool, const int32_t* ids, int32_t count);
+    relp_status_t pool_stats(const relp_pool* pool, int64_t* out4) const;
     int32_t engine_kind() const { return lay_.engine; }
     relp_status_t robust_stats(int64_t* out4) const;
     relp_status_t solve_relaxation(int64_t max_iters, int32_t* outcome);
@@ -358,6 +383,20 @@ class Engine : private EngineQueue {
     DeviceBuf<int32_t> d_col_cols_;
     DeviceBuf<double> d_col_coef_, d_col_d_, d_col_cost_;
     int32_t col_last_cols_ = 0, col_last_p_ = 0;
+    relp_status_t room_for_columns(const char* what, int32_t count);      // the growth rule of relp_add_columns
+    // the layout, the host mirrors and the record after the launches of an add (the columns have passed Layout::check_columns)
+    relp_status_t columns_added(int32_t count, const int64_t* col_ptr, const int32_t* row_idx, const double* values, const double* cost,
+                                int32_t entries, int32_t p);
+    // relp_pool_*: the pools of this handle (freed with it), the chosen ids and the places of the rows of an add on the device
+    // (relp_kernels.h: launch_pool_add_operands), grown on demand
+    std::vector<std::unique_ptr<relp_pool>> pools_;
+    DeviceBuf<int32_t> d_pool_ids_, d_pool_rank_, d_pool_entries_;
+    DeviceBuf<double> d_pool_minus_pi_;                   // -pi as a vector: scratch of every price and add (relp_kernels.h: MinusPi)
+    relp_status_t pool_ready(const char* what, const relp_pool* pool, bool fresh);
+    void pools_mark_stale(const int32_t* rows, int32_t count);             // engine rows went: the listed ones, or (nullptr) those from lay_.m on
+    PoolView pool_view(const relp_pool& pool) const;
+    MinusPi minus_pi_view() const { return MinusPi{d_d_, d_cost_store_, d_idcol_, lay_.m, d_pool_minus_pi_}; }
+    relp_status_t pool_launch_price(relp_pool& pool, int32_t segments, double tol, bool all);
     // relp_remove_cuts / relp_remove_columns: the lists of a call on the device (relp_kernels.h: launch_tab_compact), grown on demand;
     // what relp_removal_stats reports.  The rooms stay: the next add reuses what a removal freed.
     DeviceBuf<int32_t> d_rm_lists_;

@@ -151,6 +151,7 @@ relp_status_t Engine::trial_end(int32_t keep) {
     }
     if ((st = trial_copy(false))) return st;
     trial_host_restore();
+    pools_mark_stale(nullptr, 0);                      // a pool created inside the trial over a cut row the rollback took back
     tab_partials_valid_ = false;
     trial_open_ = false;
     ++trials_rolled_back_;

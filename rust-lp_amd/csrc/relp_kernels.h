@@ -12,6 +12,7 @@
 #include <stdint.h>
 
 #include "relp_layout.hpp"   // kWrappedArtificialBase
+#include "relp_pool.hpp"     // kPoolSlice, kPoolChunk, pool_segment_size
 #include "relp_trial.hpp"    // TrialTable
 
 namespace relp {
@@ -651,6 +652,56 @@ void launch_tab_gomory(const TableauView& tv, const DeferredUpdate& du, const Co
 // 256 CUs x 8 workgroups of 256 threads); each segment's tail of bytes % 16 bytes goes bytewise.  No atomics, no LDS.
 static constexpr int32_t kTabTrialGrid = 2048;
 void launch_tab_trial_copy(const TrialTable& t, hipStream_t s);
+// A column pool on the device (relp_pool_create .. relp_pool_add), read-only to every launch below but for the activity flags.
+// Sliced ELL as relp_pool.hpp packs it: pool column k is lane k % 64 of slice k / 64, entry e of it stands at
+// slice_ptr[k / 64] + e * 64 + k % 64 and slice s is (slice_ptr[s + 1] - slice_ptr[s]) / 64 entries wide; rows ascend inside a
+// column, padding has row -1 and is skipped by its row (it reaches no fma).  cost, active: one per pool column.
+struct PoolView {
+    const int64_t* slice_ptr; const int32_t* row; const double* val; const double* cost; uint8_t* active;
+    int32_t count;
+};
+// -pi as relp_get_minus_pi reads it off the tableau: (-pi)_i = d[idcol[i]] - cost_store[idcol[i]], rounded once, over the m engine
+// rows.  vec: m doubles of scratch; every launch below first writes -pi there (k_pool_minus_pi, one row per thread) and its chains
+// read it from there.
+struct MinusPi { const double* d; const double* cost_store; const int32_t* idcol; int32_t m; double* vec; };
+// The reduced cost of pool column k:  d_k = cost[k], then d_k = fma((-pi)_row, value, d_k) over the column's entries in stored
+// (ascending row) order -- the chain Engine::add_columns forms for d_new, to the bit.  The loads of a chain are issued sixteen
+// entries at a time (kPoolBatch); the order of the chain does not depend on it.
+// Multiple pricing (relp_pool_price, relp_pool_reduced_costs).  The pool indices are cut into `segments` shares of
+// S = ceil(count / segments) columns and every share into chunks of kPoolChunk columns:
+// [k_pool_minus_pi] -> [k_pool_price, grid segments x chunks (one dimension), 256 threads: thread t of chunk (s, c) prices the column
+// s * S + c * kPoolChunk + t where that lies below the end of the share and of the pool -- consecutive lanes, consecutive columns,
+// so a wave reads consecutive entries of a slice; d_all[k] = d_k when d_all is given; a column is a candidate when it is active and
+// d_k < -tol; the chunk's minimum in the total order (d, pool index) by block_min_key -> part_d / part_k[s * chunks + c], (+inf, -1)
+// without a candidate] -> [k_pool_fold, only when chunks > 1, one workgroup per share: the share's chunks folded in the same order
+// into its first slot part_d / part_k[s * chunks]] -> [k_pool_winners, one workgroup of 256 threads, shares 256 at a time: an
+// ordered scan over the 256 flags "has a winner" gives every winner its place; out_k / out_d[0 .. *found) = the winners in
+// ascending share order].  No atomics; minima in a total order and one fma chain per column: the same launch on the same state
+// gives the same bits.  segments < 1: only d_all is written (no partials, no further launch).
+// part_d / part_k: segments * pool_segment_chunks(count, segments) entries; out_k / out_d: segments entries; found: one.
+void launch_pool_price(const PoolView& pv, const MinusPi& mp, int32_t segments, double tol, double* d_all, double* part_d, int32_t* part_k,
+                       int32_t* out_k, double* out_d, int32_t* found, hipStream_t s);
+// The operands of launch_tab_add_columns for the pool columns ids[0 .. count) (device list, distinct), formed on the device
+// (relp_pool_add).  m: the engine rows; longest: the longest chosen column (entries, the second grid dimension's reach).
+//   rank     m words of scratch: afterwards rank[i] = the place of row i in the union list, -1 for a row no chosen column touches
+//   cols     the union list: idcol[i] of the touched rows i, ascending; *entries = its length
+//   coef     coef[e * count + x] = the coefficient of column ids[x] in the row of list entry e, 0.0 elsewhere (`entries` x count;
+//            the caller knows `entries` from its host copy -- it sizes the buffer and the zero fill)
+//   col_a    the dense row-space block of added columns: column a0 + x at (a0 + x) * ld_c gets the m-vector of column ids[x]
+//   d_new, cost_new   the chain above and the cost of column ids[x];  the activity flags of the chosen columns are cleared
+// [rank = 0] -> [k_pool_entries<false>, one workgroup per 256 entries of a chosen column: rank[row] = 1; many writers, one value] ->
+// [k_pool_union, one workgroup, rows 256 at a time, an ordered scan over the marks: rank, cols, *entries] -> [k_pool_minus_pi] -> [coef = 0, the new
+// columns of col_a = 0] -> [k_pool_entries<true>, the same grid: one entry per thread into coef and col_a] -> [k_pool_chosen, one
+// workgroup per chosen column, the operands staged in LDS 256 entries at a time, thread 0 chains: d_new, cost_new, active = 0].  No atomics; every output word has one writer or one value.
+struct PoolAdd {
+    const int32_t* ids; int32_t count, m, longest, entries;
+    int32_t* rank; int32_t* cols; int32_t* entries_out; double* coef;
+    double* col_a; int64_t ld_c; int32_t a0;
+    double* d_new; double* cost_new;
+};
+void launch_pool_add_operands(const PoolView& pv, const MinusPi& mp, const PoolAdd& pa, hipStream_t s);
+// active[ids[x]] = flag for x < count (relp_pool_set_active); ids: device list
+void launch_pool_set_active(const PoolView& pv, const int32_t* ids, int32_t count, int32_t flag, hipStream_t s);
 
 // ---- sparse LU engine ------------------------------------------------------------------------------
 // PRICE over CSC columns (thread per column), partial argmin per 256 columns

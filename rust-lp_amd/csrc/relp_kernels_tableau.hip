@@ -2141,4 +2141,238 @@ void launch_tab_trial_copy(const TrialTable& t, hipStream_t s) {
     hipLaunchKernelGGL(k_tab_trial_copy, dim3(grid), dim3(kThreads), 0, s, t);
 }
 
+// ------------------------------------------------------------------------------------------------
+// The column pool (relp_pool_price, relp_pool_reduced_costs, relp_pool_add): sliced ELL, one pool column per lane (PoolView).  A
+// column's reduced cost is one sequential fma chain, so the parallelism is across columns, never inside one.
+// ------------------------------------------------------------------------------------------------
+// -pi as a vector of its own, once per launch sequence: vec[i] = d[idcol[i]] - cost_store[idcol[i]], one rounding, what
+// relp_get_minus_pi forms on the host.  The chains then make two dependent loads per entry (row, vec[row]) instead of three
+// (row, idcol[row], d and cost_store of it), and 8 m bytes that stay in cache instead of three scattered arrays.
+__global__ void k_pool_minus_pi(MinusPi mp) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < mp.m) { const int c = mp.idcol[i]; mp.vec[i] = mp.d[c] - mp.cost_store[c]; }
+}
+
+// d_k = cost[k] + sum (-pi)_row * value over the entries of pool column k in stored order: one chain from the cost.  The loads do
+// not depend on the chain, so they are issued kPoolBatch entries at a time before any is used, as in for_pending: rows and values
+// first (consecutive lanes, consecutive addresses), then the gathers of -pi; a thread makes two round trips per batch instead of two
+// per entry.  A padded entry (row < 0) gathers and adds nothing.  The order of the chain is the stored order whatever the batch is.
+static constexpr int kPoolBatch = 16;
+__device__ __forceinline__ double pool_chain(const PoolView& pv, const double* __restrict__ minus_pi, int k) {
+    const int s = k / kPoolSlice;
+    const int64_t base = pv.slice_ptr[s], width = (pv.slice_ptr[s + 1] - base) / kPoolSlice;
+    const int32_t* __restrict__ row = pv.row + base + k % kPoolSlice;
+    const double* __restrict__ val = pv.val + base + k % kPoolSlice;
+    double acc = pv.cost[k];
+    int64_t e = 0;
+    for (; e + kPoolBatch <= width; e += kPoolBatch) {
+        int r[kPoolBatch];
+        double v[kPoolBatch], p[kPoolBatch];
+#pragma unroll
+        for (int t = 0; t < kPoolBatch; ++t) { r[t] = row[(e + t) * kPoolSlice]; v[t] = val[(e + t) * kPoolSlice]; }
+#pragma unroll
+        for (int t = 0; t < kPoolBatch; ++t) p[t] = r[t] >= 0 ? minus_pi[r[t]] : 0.0;
+#pragma unroll
+        for (int t = 0; t < kPoolBatch; ++t)
+            if (r[t] >= 0) acc = fma(p[t], v[t], acc);
+    }
+    for (; e < width; ++e) {
+        const int r = row[e * kPoolSlice];
+        if (r >= 0) acc = fma(minus_pi[r], val[e * kPoolSlice], acc);
+    }
+    return acc;
+}
+
+// Chunk blockIdx.x % chunks of segment blockIdx.x / chunks (relp_kernels.h: launch_pool_price).  segments < 1: one share, no partials.
+__global__ __launch_bounds__(kThreads) void k_pool_price(PoolView pv, MinusPi mp, int seg_size, int chunks, double tol, double* d_all,
+                                                         double* part_d, int32_t* part_k) {
+    const int seg = blockIdx.x / chunks, chunk = blockIdx.x % chunks;
+    const int64_t lo = (int64_t)seg * seg_size + (int64_t)chunk * kPoolChunk;
+    const int hi = (int)min(min(lo + kPoolChunk, (int64_t)(seg + 1) * seg_size), (int64_t)pv.count);
+    double best = INFINITY;
+    int best_k = INT32_MAX;
+    for (int64_t k64 = lo + threadIdx.x; k64 < hi; k64 += kThreads) {
+        const int k = (int)k64;
+        const double d = pool_chain(pv, mp.vec, k);
+        if (d_all) d_all[k] = d;
+        if (pv.active[k] && d < -tol && d < best) { best = d; best_k = k; }     // (ascending k: the first of equal d stays)
+    }
+    if (!part_d) return;
+    block_min_key<kThreads>(best, best_k);
+    if (threadIdx.x == 0) {
+        part_d[blockIdx.x] = best_k == INT32_MAX ? INFINITY : best;
+        part_k[blockIdx.x] = best_k == INT32_MAX ? -1 : best_k;
+    }
+}
+
+// The exclusive prefix sum of one flag per thread over the workgroup's 256 threads, in thread order; *total = the sum.  Inside a
+// wave by ballot and population count, across the four waves through LDS: two barriers, callable in a loop (the first barrier
+// stands in front of the write: the previous call's words have been read).
+__device__ __forceinline__ int block_flag_scan(int flag, int* s_scan, int* total) {
+    const unsigned long long votes = __ballot(flag != 0);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int below = __popcll(votes & ((1ull << lane) - 1ull));
+    __syncthreads();
+    if (lane == 0) s_scan[wave] = __popcll(votes);
+    __syncthreads();
+    int before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < kThreads / 64; ++w) {
+        const int c = s_scan[w];
+        before += w < wave ? c : 0;
+        all += c;
+    }
+    *total = all;
+    return before + below;
+}
+
+// The chunks of share blockIdx.x folded into its first slot: thread t takes the chunks t, t + 256, ... in ascending order, then the
+// workgroup minimum in the same total order.  Every read of the share's partials precedes the barrier inside block_min_key, the
+// one write follows it.  Launched only when a share has more than one chunk.
+__global__ __launch_bounds__(kThreads) void k_pool_fold(int chunks, double* part_d, int32_t* part_k) {
+    const int64_t first = (int64_t)blockIdx.x * chunks;
+    double best = INFINITY;
+    int best_k = INT32_MAX;
+    for (int c = threadIdx.x; c < chunks; c += kThreads) {
+        const double d = part_d[first + c];
+        const int k = part_k[first + c];
+        if (k >= 0 && (d < best || (d == best && k < best_k))) { best = d; best_k = k; }
+    }
+    block_min_key<kThreads>(best, best_k);
+    if (threadIdx.x == 0) {
+        part_d[first] = best_k == INT32_MAX ? INFINITY : best;
+        part_k[first] = best_k == INT32_MAX ? -1 : best_k;
+    }
+}
+
+// One workgroup: the winners of the shares (the first slot of each share's partials), compacted in ascending share order.
+__global__ __launch_bounds__(kThreads) void k_pool_winners(int segments, int chunks, const double* __restrict__ part_d,
+                                                           const int32_t* __restrict__ part_k, int32_t* out_k, double* out_d, int32_t* found) {
+    __shared__ int s_scan[kThreads / 64];
+    int placed = 0;
+    for (int base = 0; base < segments; base += kThreads) {
+        const int seg = base + threadIdx.x;
+        const int best_k = seg < segments ? part_k[(int64_t)seg * chunks] : -1;
+        int total;
+        const int at = placed + block_flag_scan(best_k >= 0 ? 1 : 0, s_scan, &total);
+        if (best_k >= 0) { out_k[at] = best_k; out_d[at] = part_d[(int64_t)seg * chunks]; }
+        placed += total;
+    }
+    if (threadIdx.x == 0) *found = placed;
+}
+
+// Entries 256 at a time: with C = ceil(longest / 256), workgroup b has the entries (b % C) * 256 + threadIdx.x of the chosen column
+// b / C (relp_kernels.h: launch_pool_add_operands).  SCATTER == false: the row is marked.  true: the value goes to its place in
+// coef and in the column's row-space vector.
+template <bool SCATTER>
+__global__ __launch_bounds__(kThreads) void k_pool_entries(PoolView pv, PoolAdd pa) {
+    const int per_column = (pa.longest + kThreads - 1) / kThreads;
+    const int x = blockIdx.x / per_column, k = pa.ids[x], s = k / kPoolSlice;
+    const int64_t base = pv.slice_ptr[s], width = (pv.slice_ptr[s + 1] - base) / kPoolSlice;
+    const int64_t e = (int64_t)(blockIdx.x % per_column) * kThreads + threadIdx.x;
+    if (e >= width) return;
+    const int64_t at = base + e * kPoolSlice + k % kPoolSlice;
+    const int r = pv.row[at];
+    if (r < 0 || r >= pa.m) return;
+    if (!SCATTER) { pa.rank[r] = 1; return; }
+    const double v = pv.val[at];
+    if (pa.rank[r] < 0 || pa.rank[r] >= pa.entries) return;      // (a list longer than the caller sized coef for: reported through *entries_out)
+    pa.coef[(int64_t)pa.rank[r] * pa.count + x] = v;
+    pa.col_a[(int64_t)(pa.a0 + x) * pa.ld_c + r] = v;
+}
+
+// One workgroup: the marks become places, the marked rows' identity columns the union list, ascending.
+__global__ __launch_bounds__(kThreads) void k_pool_union(PoolAdd pa, const int32_t* __restrict__ idcol) {
+    __shared__ int s_scan[kThreads / 64];
+    int placed = 0;
+    for (int base = 0; base < pa.m; base += kThreads) {
+        const int i = base + threadIdx.x;
+        const int flag = i < pa.m && pa.rank[i] != 0 ? 1 : 0;
+        int total;
+        const int at = placed + block_flag_scan(flag, s_scan, &total);
+        if (i < pa.m) pa.rank[i] = flag ? at : -1;
+        if (flag && at < pa.entries) pa.cols[at] = idcol[i];
+        placed += total;
+    }
+    if (threadIdx.x == 0) *pa.entries_out = placed;
+}
+
+// d, cost of the chosen column blockIdx.x; its activity flag cleared.  One chain, so one thread adds; but its operands do not depend
+// on it, so the workgroup fetches them 256 entries at a time into LDS (row, value, -pi of the row: one entry per thread, three
+// round trips per 256 entries instead of two per batch of one thread) and thread 0 chains them from there in stored order.
+__global__ __launch_bounds__(kThreads) void k_pool_chosen(PoolView pv, MinusPi mp, PoolAdd pa) {
+    __shared__ double s_p[kThreads], s_v[kThreads];
+    __shared__ int s_r[kThreads];
+    const int x = blockIdx.x, k = pa.ids[x], s = k / kPoolSlice;
+    const int64_t base = pv.slice_ptr[s], width = (pv.slice_ptr[s + 1] - base) / kPoolSlice;
+    const int32_t* __restrict__ row = pv.row + base + k % kPoolSlice;
+    const double* __restrict__ val = pv.val + base + k % kPoolSlice;
+    double acc = pv.cost[k];
+    for (int64_t e0 = 0; e0 < width; e0 += kThreads) {
+        __syncthreads();                               // (thread 0 has read the previous 256)
+        const int64_t e = e0 + threadIdx.x;
+        int r = -1;
+        double v = 0.0, p = 0.0;
+        if (e < width) {
+            r = row[e * kPoolSlice];
+            if (r >= 0) { v = val[e * kPoolSlice]; p = mp.vec[r]; }
+        }
+        s_r[threadIdx.x] = r; s_v[threadIdx.x] = v; s_p[threadIdx.x] = p;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const int n = (int)min((int64_t)kThreads, width - e0);
+#pragma unroll 8
+            for (int j = 0; j < n; ++j) {              // (a select, not a branch: the LDS reads of the unrolled entries leave together)
+                const double next = fma(s_p[j], s_v[j], acc);
+                acc = s_r[j] >= 0 ? next : acc;
+            }
+        }
+    }
+    if (threadIdx.x == 0) {
+        pa.d_new[x] = acc;
+        pa.cost_new[x] = pv.cost[k];
+        pv.active[k] = 0;
+    }
+}
+
+__global__ void k_pool_set_active(PoolView pv, const int32_t* __restrict__ ids, int count, int flag) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    if (x < count) pv.active[ids[x]] = (uint8_t)flag;
+}
+
+void launch_pool_price(const PoolView& pv, const MinusPi& mp, int32_t segments, double tol, double* d_all, double* part_d, int32_t* part_k,
+                       int32_t* out_k, double* out_d, int32_t* found, hipStream_t s) {
+    if (pv.count > 0 && mp.m > 0) hipLaunchKernelGGL(k_pool_minus_pi, dim3(cdiv(mp.m, 256)), dim3(256), 0, s, mp);
+    if (segments < 1) {
+        if (pv.count > 0 && d_all)
+            hipLaunchKernelGGL(k_pool_price, dim3(cdiv(pv.count, kPoolChunk)), dim3(kThreads), 0, s, pv, mp, (int)pv.count, cdiv(pv.count, kPoolChunk),
+                               tol, d_all, (double*)nullptr, (int32_t*)nullptr);
+        return;
+    }
+    const int chunks = pool_segment_chunks(pv.count, segments);
+    if (pv.count > 0)
+        hipLaunchKernelGGL(k_pool_price, dim3((unsigned)((int64_t)segments * chunks)), dim3(kThreads), 0, s, pv, mp,
+                           (int)pool_segment_size(pv.count, segments), chunks, tol, d_all, part_d, part_k);
+    if (pv.count > 0 && chunks > 1) hipLaunchKernelGGL(k_pool_fold, dim3(segments), dim3(kThreads), 0, s, chunks, part_d, part_k);
+    hipLaunchKernelGGL(k_pool_winners, dim3(1), dim3(kThreads), 0, s, pv.count > 0 ? (int)segments : 0, chunks, part_d, part_k, out_k, out_d, found);
+}
+
+void launch_pool_add_operands(const PoolView& pv, const MinusPi& mp, const PoolAdd& pa, hipStream_t s) {
+    if (pa.count < 1 || pa.m < 1) return;
+    const dim3 grid((unsigned)((int64_t)cdiv(std::max(pa.longest, 1), kThreads) * pa.count));
+    (void)hipMemsetAsync(pa.rank, 0, sizeof(int32_t) * (size_t)pa.m, s);
+    if (pa.longest > 0) hipLaunchKernelGGL(k_pool_entries<false>, grid, dim3(kThreads), 0, s, pv, pa);
+    hipLaunchKernelGGL(k_pool_union, dim3(1), dim3(kThreads), 0, s, pa, mp.idcol);
+    hipLaunchKernelGGL(k_pool_minus_pi, dim3(cdiv(mp.m, 256)), dim3(256), 0, s, mp);
+    if (pa.entries > 0) (void)hipMemsetAsync(pa.coef, 0, sizeof(double) * (size_t)pa.entries * (size_t)pa.count, s);
+    (void)hipMemset2DAsync(pa.col_a + (int64_t)pa.a0 * pa.ld_c, sizeof(double) * (size_t)pa.ld_c, 0, sizeof(double) * (size_t)pa.m, (size_t)pa.count, s);
+    if (pa.longest > 0) hipLaunchKernelGGL(k_pool_entries<true>, grid, dim3(kThreads), 0, s, pv, pa);
+    hipLaunchKernelGGL(k_pool_chosen, dim3(pa.count), dim3(kThreads), 0, s, pv, mp, pa);
+}
+
+void launch_pool_set_active(const PoolView& pv, const int32_t* ids, int32_t count, int32_t flag, hipStream_t s) {
+    if (count < 1) return;
+    hipLaunchKernelGGL(k_pool_set_active, dim3(cdiv(count, 256)), dim3(256), 0, s, pv, ids, (int)count, (int)flag);
+}
+
 }  // namespace relp

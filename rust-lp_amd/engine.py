@@ -125,6 +125,13 @@ _SIGNATURES = {
     "relp_trial_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "relp_strong_branch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p]),
+    "relp_pool_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "relp_pool_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "relp_pool_set_active": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
+    "relp_pool_reduced_costs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "relp_pool_price": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
+    "relp_pool_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
+    "relp_pool_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
     "relp_solve_relaxation": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]),
     "relp_from_basis": (C.c_int, [C.c_void_p, C.c_void_p]),
     "relp_flush": (C.c_int, [C.c_void_p]),
@@ -538,6 +545,12 @@ class Tableau:
         every existing column, non-basic, on the current basis and without a flush or a re-tabulation (relp_add_columns); column k
         is column ``nr_columns() + k`` (read before the call).  ``A_new`` is a dense ``nr_rows() x count`` array, one vector with a
         scalar cost, or a CSC triple ``(col_ptr, row_idx, values)``; ``run`` re-solves from there."""
+        count, ptr, idx, val, c = self._csc_columns(A_new, cost)
+        self._ck(self._lib.relp_add_columns(self._h, count, ptr.ctypes.data, idx.ctypes.data, val.ctypes.data, c.ctypes.data))
+
+    def _csc_columns(self, A_new, cost):
+        """(count, col_ptr, row_idx, values, cost) of columns given as a dense ``nr_rows() x count`` array, one vector with a scalar
+        cost, or a CSC triple: what relp_add_columns and relp_pool_create take."""
         if isinstance(A_new, tuple):
             if len(A_new) != 3:
                 raise ValueError("a CSC triple is (col_ptr, row_idx, values)")
@@ -562,7 +575,16 @@ class Tableau:
         c = np.ascontiguousarray(np.atleast_1d(cost), dtype=np.float64)
         if c.shape != (count,):
             raise ValueError("cost must have one entry per column")
-        self._ck(self._lib.relp_add_columns(self._h, count, ptr.ctypes.data, idx.ctypes.data, val.ctypes.data, c.ctypes.data))
+        return count, ptr, idx, val, c
+
+    def pool(self, A, cost) -> "ColumnPool":
+        """A pool of candidate columns ``x >= 0`` kept on the device (relp_pool_create): ``A`` and ``cost`` as ``add_columns`` takes
+        them.  The pool is priced against the duals as they stand (``ColumnPool.price``) and its winners are added in place
+        (``ColumnPool.add``) without their coefficients going through the host again; it belongs to this tableau."""
+        count, ptr, idx, val, c = self._csc_columns(A, cost)
+        handle = C.c_void_p()
+        self._ck(self._lib.relp_pool_create(self._h, count, ptr.ctypes.data, idx.ctypes.data, val.ctypes.data, c.ctypes.data, C.byref(handle)))
+        return ColumnPool(self, handle, count)
 
     def reserve_columns(self, columns: int) -> None:
         """Room for ``columns`` added columns in all, without adding any (relp_reserve_columns): the tableau is re-allocated and
@@ -986,6 +1008,83 @@ class Trial:
     def __exit__(self, *exc) -> bool:
         self._t.trial_end(self._keep)
         return False
+
+
+class ColumnPool:
+    """A column pool of a ``Tableau`` (``Tableau.pool``): candidate columns resident on the device, priced and added in place.
+    Freed by ``close()``, or with the tableau."""
+
+    def __init__(self, tableau: Tableau, handle, count: int):
+        self._t, self._p, self.count = tableau, handle, int(count)
+
+    def _call(self, name, *args):
+        if self._p is None:
+            raise RelpError("the pool is closed")
+        if not self._t._h:
+            raise RelpError("the pool's tableau is closed")
+        self._t._ck(getattr(self._t._lib, name)(self._t._h, self._p, *args))
+
+    def close(self) -> None:
+        if self._p is not None and self._t._h:
+            self._t._lib.relp_pool_destroy(self._t._h, self._p)
+        self._p = None
+
+    def reduced_costs(self) -> np.ndarray:
+        """``d_k = c_k + sum_i (-pi)_i a_k[i]`` of every pool column, active or not, with the bits ``add_columns`` would give the
+        column's reduced cost at this moment (relp_pool_reduced_costs); read-only."""
+        out = np.zeros(self.count)
+        self._call("relp_pool_reduced_costs", out.ctypes.data)
+        return out
+
+    def price(self, segments: int = 1, tol: float = 1e-7):
+        """Multiple pricing (relp_pool_price): the pool indices cut into ``segments`` equal shares, per share the active column with
+        the smallest ``d_k < -tol`` (lowest index among equals).  Returns (ids, d) of the winners, ascending share order."""
+        ids = np.zeros(max(int(segments), 1), dtype=np.int32)
+        d = np.zeros(max(int(segments), 1))
+        found = C.c_int32(0)
+        self._call("relp_pool_price", int(segments), float(tol), ids.ctypes.data, d.ctypes.data, C.byref(found))
+        return ids[:found.value].copy(), d[:found.value].copy()
+
+    def add(self, ids) -> None:
+        """The pool columns ``ids`` join the tableau as ``add_columns`` would add them, in that order (relp_pool_add): column k of
+        the list is column ``nr_columns() + k`` (read before the call); their activity flags are cleared."""
+        i = np.ascontiguousarray(np.atleast_1d(ids), dtype=np.int32)
+        if i.ndim != 1:
+            raise ValueError("ids must be one-dimensional")
+        self._call("relp_pool_add", i.ctypes.data, i.shape[0])
+
+    def set_active(self, ids, flag: bool) -> None:
+        """The activity flag of the pool columns ``ids`` (relp_pool_set_active): an inactive column is priced but never wins."""
+        i = np.ascontiguousarray(np.atleast_1d(ids), dtype=np.int32)
+        if i.ndim != 1:
+            raise ValueError("ids must be one-dimensional")
+        self._call("relp_pool_set_active", i.ctypes.data, i.shape[0], 1 if flag else 0)
+
+    def stats(self) -> Tuple[int, int, int, int]:
+        """(pool columns, nonzeros held, entries stored on the device with padding, price calls so far); relp_pool_stats."""
+        out = (C.c_int64 * 4)()
+        self._call("relp_pool_stats", out)
+        return tuple(int(x) for x in out)
+
+
+def column_generation(tableau: Tableau, pool: ColumnPool, segments: int = 1, tol: float = 1e-7, max_rounds: int = 100,
+                      max_iters: int = 1 << 40):
+    """The column-generation loop on a phase-2 tableau: ``run`` -> ``pool.price(segments, tol)`` -> ``pool.add(winners)`` until
+    nothing prices out, the LP is not optimal or ``max_rounds`` rounds have added columns.  Returns (rounds that added columns,
+    columns added, last outcome); the outcome is OPTIMAL only if the last pricing found no candidate."""
+    rounds, added = 0, 0
+    while True:
+        outcome = tableau.run(max_iters)[1]
+        if outcome != OPTIMAL:
+            return rounds, added, outcome
+        ids, _ = pool.price(segments, tol)
+        if ids.shape[0] == 0:
+            return rounds, added, OPTIMAL
+        if rounds >= max_rounds:
+            return rounds, added, RUNNING
+        pool.add(ids)
+        rounds += 1
+        added += int(ids.shape[0])
 
 
 def gomory_rounds(tableau: Tableau, is_integer=None, max_rounds: int = 20, cuts_per_round: int = 3, kind: int = GOMORY_FRACTIONAL,
