@@ -508,6 +508,51 @@ class Tableau {
         ck(relp_pool_create(h_, (int32_t)cost.size(), col_ptr.data(), row_idx.data(), values.data(), cost.data(), &p));
         return Pool(h_, p, (int32_t)cost.size());
     }
+    // A pool of candidate cuts kept on the device (relp_cutpool_create .. relp_cutpool_stats), the mirror image of Pool: separated
+    // against the vertex as it stands, the winners picked on the device, the chosen ones added as add_cuts adds them without their
+    // coefficients going through the host again.  Freed with the CutPool object; a CutPool must not outlive its Tableau.
+    class CutPool {
+      public:
+        CutPool(CutPool&& o) noexcept : h_(o.h_), p_(o.p_), count_(o.count_) { o.p_ = nullptr; }
+        CutPool(const CutPool&) = delete;
+        CutPool& operator=(const CutPool&) = delete;
+        ~CutPool() { if (p_) (void)relp_cutpool_destroy(h_, p_); }
+        int32_t count() const { return count_; }
+        // relp_cutpool_slacks: s_k = rhs_k - sum_j g_kj x_j of every pool cut at the current vertex, one fma chain, columns ascending
+        std::vector<double> slacks() { std::vector<double> out((size_t)count_); ck(relp_cutpool_slacks(h_, p_, out.data())); return out; }
+        // relp_cutpool_separate: per share of ceil(count / segments) pool indices the active cut with the smallest key (s_k, or
+        // s_k / norm_k by efficacy) among those with s_k < -tol
+        struct Winners { std::vector<int32_t> ids; std::vector<double> slack; };
+        Winners separate(int32_t segments = 1, double tol = 1e-7, bool by_efficacy = false) {
+            const size_t room = (size_t)(segments > 0 ? segments : 1);
+            Winners out{std::vector<int32_t>(room), std::vector<double>(room)};
+            int32_t found = 0;
+            ck(relp_cutpool_separate(h_, p_, segments, tol, by_efficacy ? 1 : 0, out.ids.data(), out.slack.data(), &found));
+            out.ids.resize((size_t)found); out.slack.resize((size_t)found);
+            return out;
+        }
+        // relp_cutpool_add: the listed pool cuts become the rows nr_rows() + k of the tableau, their slacks basic; their flags are
+        // cleared (and stay cleared when a trial that added them is rolled back)
+        void add(const std::vector<int32_t>& ids) { ck(relp_cutpool_add(h_, p_, ids.data(), (int32_t)ids.size())); }
+        // relp_cutpool_set_active: an inactive cut has a slack but never wins
+        void set_active(const std::vector<int32_t>& ids, bool flag) { ck(relp_cutpool_set_active(h_, p_, ids.data(), (int32_t)ids.size(), flag ? 1 : 0)); }
+        // relp_cutpool_stats: {pool cuts, nonzeros held, entries stored on the device with padding, separate calls so far}
+        std::array<int64_t, 4> stats() const { std::array<int64_t, 4> out{}; ck(relp_cutpool_stats(h_, p_, out.data())); return out; }
+
+      private:
+        friend class Tableau;
+        CutPool(relp_engine_t* h, relp_cutpool_t* p, int32_t count) : h_(h), p_(p), count_(count) {}
+        void ck(relp_status_t st) const { if (st != RELP_OK) throw Error(st, relp_last_error(h_)); }
+        relp_engine_t* h_; relp_cutpool_t* p_; int32_t count_;
+    };
+    CutPool cut_pool(const std::vector<int64_t>& row_ptr, const std::vector<int32_t>& col_idx, const std::vector<double>& values,
+                     const std::vector<double>& rhs) {
+        if (row_ptr.size() != rhs.size() + 1) throw Error(RELP_E_ARG, "row_ptr has one entry more than there are cuts");
+        if (col_idx.size() != values.size() || (int64_t)values.size() < row_ptr.back()) throw Error(RELP_E_ARG, "one value per column index, row_ptr within them");
+        relp_cutpool_t* p = nullptr;
+        ck(relp_cutpool_create(h_, (int32_t)rhs.size(), row_ptr.data(), col_idx.data(), values.data(), rhs.data(), &p));
+        return CutPool(h_, p, (int32_t)rhs.size());
+    }
     // ---- one LP on several GPUs (no counterpart in the reference, which is single-threaded) ---------------------
     // Options::shard(rank, count) at construction, the owned structural columns in `MatrixData` (relp_shard_plan);
     // rank 0 makes the RCCL id, the host program hands it to every rank, every rank attaches, then the loop runs

@@ -637,6 +637,74 @@ relp_status_t relp_pool_price(relp_engine_t *h, relp_pool_t *pool, int32_t segme
                               double *d_out /* segments */, int32_t *found);
 relp_status_t relp_pool_add(relp_engine_t *h, relp_pool_t *pool, const int32_t *ids, int32_t count);
 relp_status_t relp_pool_stats(const relp_engine_t *h, const relp_pool_t *pool, int64_t *out4);
+/* A pool of candidate CUTS kept ON THE DEVICE, separated and added in place (no counterpart in the reference): the mirror image of
+ * the column pool above, for row generation -- lazy constraints, a model with far more rows than are ever binding, cuts kept from
+ * earlier rounds or nodes, Gomory cuts set aside.  The loop: relp_run_dual, relp_cutpool_separate, relp_cutpool_add of the winners,
+ * until nothing is violated.  Separation needs no download of b and the basis and no host loop, and the add does not send the
+ * coefficients through the host again.
+ * relp_cutpool_create: `count` cuts g_k' x <= rhs_k in CSR over the structural columns [0, nr_normal), exactly the argument of
+ * relp_add_cuts, with its checks and refusals (RELP_E_ARG, no pool: count < 0, a missing array, a row_ptr that does not ascend from
+ * 0, a column that is not structural, a column named twice in one cut, a coefficient or right-hand side that is not finite).
+ * Explicit zeros are dropped, a cut without entries is accepted, count == 0 gives an empty pool.  The pool is copied to the device
+ * as sliced ELL -- 64 cuts per slice, entry-major inside a slice, columns ascending inside a cut, every slice padded to its longest
+ * cut with (column -1, value 0.0), skipped by its column -- with rhs_k and norm_k per cut; norm_k is the square root of ONE fma chain
+ * of squares from 0.0 over the stored entries in ascending column order, computed on the host at the create.  A host copy is kept
+ * for the layout and the later rebuilds.  The pool belongs to the handle: relp_cutpool_destroy frees it, relp_engine_destroy frees
+ * the pools still alive; a handle may hold several, next to column pools.  A fresh pool has every cut active.  There is NO stale
+ * rule: the structural columns never move -- added columns (relp_add_columns) lie behind them, and cuts with coefficients on added
+ * columns are out of scope -- so a cut pool stays valid through every add and removal of rows and columns.
+ * relp_cutpool_slacks: out[k], for every pool cut k, active or not,
+ *     s_k = rhs_k - acc,   acc = fma(g_kj, x_j, acc) from 0.0 over the cut's stored entries, j ascending, every operand rounded once,
+ *     x_j = b[r] if structural column j is basic in row r, else +0.0:
+ * the slack the cut would have at the current vertex; s_k < 0 means the cut is violated.  This is the call's own fixed arithmetic.
+ * It equals the b of the new row that relp_add_cuts would produce at this moment UP TO SUMMATION ORDER -- relp_add_cuts walks the
+ * tableau rows ascending, this call the columns -- and equals it to the bit whenever ascending columns and ascending rows give the
+ * cut's entries the same order.  Read-only in the sense of relp_pool_reduced_costs: nothing is flushed or re-armed, the record is
+ * not downloaded, and T0, R0, W, d, b, the basis, the flags, the record, the trace and every other *_stats keep their bits.
+ * Neither primal nor dual feasibility is required; allowed inside a trial.  No atomics: the same call on the same state gives the
+ * same bits.
+ * relp_cutpool_separate: the pool indices [0, count) are cut into `segments` equal shares of ceil(count / segments) cuts (the last
+ * shares may be short or empty; 1 <= segments <= count).  The winner of a share is its ACTIVE cut with the smallest key among those
+ * with s_k < -tol (tol >= 0, finite; s_k == -tol is no candidate).  The key is s_k when by_efficacy is 0 and s_k / norm_k when it
+ * is 1 (a cut with norm_k == 0 ranks with norm 1); the lowest pool index wins among equal keys.  ids_out and slack_out (room for
+ * `segments` entries each) receive the winners in ascending share order, compacted; *found is their number; slack_out[i] has the
+ * bits of relp_cutpool_slacks()[ids_out[i]].  The winners are picked on the device and come down in one copy (beyond 4,096
+ * segments: their number first, then the winners alone).  Read-only as above, allowed inside a trial.  RELP_E_ARG with nothing
+ * written: segments out of range, a tol that is negative or not finite, by_efficacy outside {0, 1}, a missing array.  A pool
+ * without cuts gives *found = 0 for any segments >= 1.
+ * relp_cutpool_set_active: the activity flag (0 or 1) of the listed pool cuts, on the device.  RELP_E_ARG: an index outside the
+ * pool, an index named twice, another flag value, count < 0, a missing list.
+ * relp_cutpool_add: the pool cuts ids[0 .. count) (each once, any order) join the tableau exactly as relp_add_cuts would add the
+ * same cuts in the same order: cut k becomes row relp_nr_rows() + k with its slack basic in it, with the growth rule, the room
+ * rule inside a trial (allowed within the reserved room, RELP_E_STATE when the tableau would have to grow), the relp_cut_stats
+ * bookkeeping and the inclusion in later rebuilds of relp_add_cuts.  The activity flags of the added cuts are cleared.  The bit
+ * contract: after the call every getter and every *_stats but relp_cutpool_stats returns exactly what it returns on a twin handle
+ * that called relp_add_cuts with the host data of the same cuts.  The operands of the add -- the ascending union list of rows
+ * whose basic column is structural and touched by a chosen cut, coef[entry][cut], the cut rows of the engine's matrix and b of the
+ * new rows -- are formed on the device from the device copy; the coefficient values, b and the basis do not cross the bus.  Four
+ * bytes do: the length of the union list comes down between the operands and the row kernels, because which touched columns are
+ * basic only the device knows; it is checked there against the host's bound, before the tableau is written.
+ * RELP_CUTPOOL_HOST_ADD=1 at relp_engine_create routes the call through relp_add_cuts with the host copy (the control: the same
+ * bits).  RELP_E_ARG with nothing changed: an index outside the pool or named twice, count < 0, a missing list.  count == 0 is a
+ * no-op.  Pools are no part of a trial's snapshot: a pool created or destroyed inside a trial stays created or destroyed, and the
+ * flags cleared by an add inside a trial STAY cleared after relp_trial_end(h, 0), although the rows are gone -- the caller
+ * re-activates them with relp_cutpool_set_active.  relp_remove_cuts does not know the pool either.
+ * relp_cutpool_stats: out4 = { pool cuts, nonzeros held (explicit zeros dropped), entries stored on the device (padding included),
+ * relp_cutpool_separate calls so far (calls that returned RELP_OK; refused and failed ones are not counted) }.
+ * All seven: RELP_ENGINE_TABLEAU, unsharded, phase 2 -- RELP_E_UNSUPPORTED on another or a sharded engine, RELP_E_STATE in
+ * phase 1 -- and RELP_E_ARG for a pool that is not one of this handle's.  Out of scope: pools on sharded or other engines or in
+ * phase 1, cuts with coefficients on added or virtual columns, moving slack-basic pool cuts back into the pool, restoring the
+ * flags at a rollback, parallelism and orthogonality filtering between chosen cuts. */
+typedef struct relp_cutpool relp_cutpool_t;
+relp_status_t relp_cutpool_create(relp_engine_t *h, int32_t count, const int64_t *row_ptr, const int32_t *col_idx, const double *values,
+                                  const double *rhs, relp_cutpool_t **pool);
+relp_status_t relp_cutpool_destroy(relp_engine_t *h, relp_cutpool_t *pool);
+relp_status_t relp_cutpool_set_active(relp_engine_t *h, relp_cutpool_t *pool, const int32_t *ids, int32_t count, int32_t flag);
+relp_status_t relp_cutpool_slacks(relp_engine_t *h, relp_cutpool_t *pool, double *out_count);
+relp_status_t relp_cutpool_separate(relp_engine_t *h, relp_cutpool_t *pool, int32_t segments, double tol, int32_t by_efficacy,
+                                    int32_t *ids_out /* segments */, double *slack_out /* segments */, int32_t *found);
+relp_status_t relp_cutpool_add(relp_engine_t *h, relp_cutpool_t *pool, const int32_t *ids, int32_t count);
+relp_status_t relp_cutpool_stats(const relp_engine_t *h, const relp_cutpool_t *pool, int64_t *out4);
 /* InverseMaintener::from_basis (carry/mod.rs:428-463): warm start from provider column indices,
  * one per row; switches to phase 2.  RELP_ENGINE_LU: any basis (factorise, b = FTRAN(rhs), -pi = BTRAN(-c_B));
  * RELP_ENGINE_REVISED: any basis (basis_inverse_rows.rs:103-129: LU - factorised on the host like every

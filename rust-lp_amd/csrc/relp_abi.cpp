@@ -146,6 +146,21 @@ relp_status_t relp_pool_price(relp_engine_t* h, relp_pool_t* pool, int32_t segme
 }
 relp_status_t relp_pool_add(relp_engine_t* h, relp_pool_t* pool, const int32_t* ids, int32_t count) { return h ? H(h).pool_add(pool, ids, count) : RELP_E_ARG; }
 relp_status_t relp_pool_stats(const relp_engine_t* h, const relp_pool_t* pool, int64_t* out4) { return (h && out4) ? H(h).pool_stats(pool, out4) : RELP_E_ARG; }
+relp_status_t relp_cutpool_create(relp_engine_t* h, int32_t count, const int64_t* row_ptr, const int32_t* col_idx, const double* values,
+                                  const double* rhs, relp_cutpool_t** pool) {
+    return h ? H(h).cutpool_create(count, row_ptr, col_idx, values, rhs, pool) : RELP_E_ARG;
+}
+relp_status_t relp_cutpool_destroy(relp_engine_t* h, relp_cutpool_t* pool) { return h ? H(h).cutpool_destroy(pool) : RELP_E_ARG; }
+relp_status_t relp_cutpool_set_active(relp_engine_t* h, relp_cutpool_t* pool, const int32_t* ids, int32_t count, int32_t flag) {
+    return h ? H(h).cutpool_set_active(pool, ids, count, flag) : RELP_E_ARG;
+}
+relp_status_t relp_cutpool_slacks(relp_engine_t* h, relp_cutpool_t* pool, double* out_count) { return h ? H(h).cutpool_slacks(pool, out_count) : RELP_E_ARG; }
+relp_status_t relp_cutpool_separate(relp_engine_t* h, relp_cutpool_t* pool, int32_t segments, double tol, int32_t by_efficacy, int32_t* ids_out,
+                                    double* slack_out, int32_t* found) {
+    return h ? H(h).cutpool_separate(pool, segments, tol, by_efficacy, ids_out, slack_out, found) : RELP_E_ARG;
+}
+relp_status_t relp_cutpool_add(relp_engine_t* h, relp_cutpool_t* pool, const int32_t* ids, int32_t count) { return h ? H(h).cutpool_add(pool, ids, count) : RELP_E_ARG; }
+relp_status_t relp_cutpool_stats(const relp_engine_t* h, const relp_cutpool_t* pool, int64_t* out4) { return (h && out4) ? H(h).cutpool_stats(pool, out4) : RELP_E_ARG; }
 relp_status_t relp_solve_relaxation(relp_engine_t* h, int64_t max_iters, int32_t* outcome) {
     return h ? H(h).solve_relaxation(max_iters, outcome) : RELP_E_ARG;
 }

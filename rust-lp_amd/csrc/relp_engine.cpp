@@ -119,6 +119,7 @@ Switches Switches::read() {
     s.tab_cost_splits = std::max(0, num("RELP_TAB_COST_SPLITS", 0));
     s.trial_memcpy = num("RELP_TRIAL_MEMCPY", 0) != 0;
     s.pool_host_add = num("RELP_POOL_HOST_ADD", 0) != 0;
+    s.cutpool_host_add = num("RELP_CUTPOOL_HOST_ADD", 0) != 0;
     return s;
 }
 
@@ -1398,12 +1399,7 @@ relp_status_t Engine::add_cuts(int32_t count, const int64_t* row_ptr, const int3
     if (st) return st;
     if ((st = lay_.check_cuts(count, row_ptr, col_idx, values, rhs, &err_))) return st;
     if (count == 0) return RELP_OK;
-    if ((int64_t)lay_.nr_cuts + count > cut_room_) {
-        if ((st = in_trial("relp_add_cuts beyond the reserved room"))) return st;
-        const int64_t want = std::max<int64_t>({(int64_t)lay_.nr_cuts + count, 2 * (int64_t)cut_room_, 16});
-        if (want > INT32_MAX / 2) return fail(RELP_E_ARG, "relp_add_cuts: too many cuts");
-        if ((st = grow_for_cuts((int32_t)want))) return st;
-    }
+    if ((st = room_for_cuts("relp_add_cuts", count))) return st;
     int32_t p;
     if ((st = settled_pending(&p))) return st;
     const int32_t m_old = lay_.m, cuts_old = lay_.nr_cuts;
@@ -1455,8 +1451,22 @@ relp_status_t Engine::add_cuts(int32_t count, const int64_t* row_ptr, const int3
     if (e == hipSuccess) launch_tab_add_cuts(tv, deferred(), cr, d_in_basis_, p, d_cut_u_, ct, stream_);
     HIP_TRY(first_error(e, hipStreamSynchronize(stream_)));
     if (hipGetLastError() != hipSuccess) return fail(RELP_E_HIP, "relp_add_cuts: a kernel launch failed");
+    return cuts_added(count, row_ptr, col_idx, values, rhs, entries, p);
+}
 
-    // the layout and the host mirrors follow (check_cuts passed: add_cuts cannot fail)
+// room for `count` more cut rows: grown to max(cuts then in the tableau, 2 x the room so far, 16) when it lacks; inside a trial the
+// reserved room is all there is
+relp_status_t Engine::room_for_cuts(const char* what, int32_t count) {
+    if ((int64_t)lay_.nr_cuts + count <= cut_room_) return RELP_OK;
+    if (const relp_status_t st = in_trial((std::string(what) + " beyond the reserved room").c_str())) return st;
+    const int64_t want = std::max<int64_t>({(int64_t)lay_.nr_cuts + count, 2 * (int64_t)cut_room_, 16});
+    if (want > INT32_MAX / 2) return fail(RELP_E_ARG, std::string(what) + ": too many cuts");
+    return grow_for_cuts((int32_t)want);
+}
+
+// the layout and the host mirrors follow the device (check_cuts passed: Layout::add_cuts cannot fail), the record is re-armed
+relp_status_t Engine::cuts_added(int32_t count, const int64_t* row_ptr, const int32_t* col_idx, const double* values, const double* rhs,
+                                 int32_t entries, int32_t p) {
     const int32_t n_old = n_store_;
     (void)lay_.add_cuts(count, row_ptr, col_idx, values, rhs, &err_);
     for (int32_t k = 0; k < count; ++k) idcol_h_.push_back(n_old + k);

@@ -27,6 +27,7 @@
 #include "relp_buffers.hpp"
 #include "relp_kernels.h"
 #include "relp_layout.hpp"
+#include "relp_cutpool.hpp"
 #include "relp_lu.hpp"
 #include "relp_pack.hpp"
 
@@ -41,6 +42,18 @@ struct relp_pool {
     relp::DeviceBuf<char> d_out;                          // what a price downloads: the winners' d, their pool indices, their number
     bool stale = false;                                   // an engine row below image.rows_at_create went (relp_remove_cuts, the rollback of a trial)
     int64_t price_calls = 0;
+};
+
+// A cut pool of a handle (relp_cutpool_create .. relp_cutpool_stats; relp_engine_cutpool.cpp).  The host copy (relp_cutpool.hpp) is
+// what Layout::add_cuts and the rebuilds are given; the device copy is what the separation and the add read.  Owned by its Engine.
+struct relp_cutpool {
+    relp::CutPoolImage image;
+    relp::DeviceBuf<int64_t> d_slice_ptr;
+    relp::DeviceBuf<int32_t> d_col, d_part_k;
+    relp::DeviceBuf<double> d_val, d_rhs, d_norm, d_all, d_part_d;   // (d_all, d_part_*, d_out: scratch of a separation, allocated at the first one)
+    relp::DeviceBuf<uint8_t> d_active;
+    relp::DeviceBuf<char> d_out;                          // what a separation downloads: the winners' slacks, their pool indices, their number
+    int64_t separate_calls = 0;
 };
 
 namespace relp {
@@ -103,6 +116,7 @@ struct Switches {
     int tab_cost_splits = 0;                              // RELP_TAB_COST_SPLITS (0: the rule of tab_cost_splits)
     bool trial_memcpy = false;                            // RELP_TRIAL_MEMCPY
     bool pool_host_add = false;                           // RELP_POOL_HOST_ADD
+    bool cutpool_host_add = false;                        // RELP_CUTPOOL_HOST_ADD
     static Switches read();
 };
 
@@ -195,6 +209,18 @@ class Engine : private EngineQueue {
     relp_status_t pool_price(relp_pool* pool, int32_t segments, double tol, int32_t* ids_out, double* d_out, int32_t* found);
     relp_status_t pool_add(relp_pool* pool, const int32_t* ids, int32_t count);
     relp_status_t pool_stats(const relp_pool* pool, int64_t* out4) const;
+    // a pool of candidate cuts kept on the device (relp_engine_cutpool.cpp), the mirror image of the column pool: separated there
+    // against the vertex as it stands (read-only), its winners picked there, the chosen cuts added as add_cuts adds them, their
+    // coefficients, b and the basis never crossing the bus
+    relp_status_t cutpool_create(int32_t count, const int64_t* row_ptr, const int32_t* col_idx, const double* values, const double* rhs,
+                                 relp_cutpool** out);
+    relp_status_t cutpool_destroy(relp_cutpool* pool);
+    relp_status_t cutpool_set_active(relp_cutpool* pool, const int32_t* ids, int32_t count, int32_t flag);
+    relp_status_t cutpool_slacks(relp_cutpool* pool, double* out_count);
+    relp_status_t cutpool_separate(relp_cutpool* pool, int32_t segments, double tol, int32_t by_efficacy, int32_t* ids_out, double* slack_out,
+                                   int32_t* found);
+    relp_status_t cutpool_add(relp_cutpool* pool, const int32_t* ids, int32_t count);
+    relp_status_t cutpool_stats(const relp_cutpool* pool, int64_t* out4) const;
     int32_t engine_kind() const { return lay_.engine; }
     relp_status_t robust_stats(int64_t* out4) const;
     relp_status_t solve_relaxation(int64_t max_iters, int32_t* outcome);
@@ -397,6 +423,20 @@ class Engine : private EngineQueue {
     PoolView pool_view(const relp_pool& pool) const;
     MinusPi minus_pi_view() const { return MinusPi{d_d_, d_cost_store_, d_idcol_, lay_.m, d_pool_minus_pi_}; }
     relp_status_t pool_launch_price(relp_pool& pool, int32_t segments, double tol, bool all);
+    // relp_cutpool_*: the cut pools of this handle (freed with it), the vertex over the structural columns and the marks of an add on
+    // the device (relp_kernels.h: Vertex, launch_cutpool_add_operands), grown on demand; d_pool_ids_ and d_pool_entries_ are shared
+    // with the column pools
+    std::vector<std::unique_ptr<relp_cutpool>> cutpools_;
+    DeviceBuf<double> d_cutpool_x_;
+    DeviceBuf<int32_t> d_cutpool_mark_;
+    relp_status_t cutpool_ready(const char* what, const relp_cutpool* pool);
+    CutPoolView cutpool_view(const relp_cutpool& pool) const;
+    Vertex vertex_view() const { return Vertex{d_b_, d_basis_, lay_.m, lay_.nr_normal, d_cutpool_x_}; }
+    relp_status_t cutpool_launch_separate(relp_cutpool& pool, int32_t segments, double tol, int32_t by_efficacy);
+    relp_status_t room_for_cuts(const char* what, int32_t count);         // the growth rule of relp_add_cuts, its room rule inside a trial
+    // the layout, the host mirrors and the record after the launches of an add (the cuts have passed Layout::check_cuts)
+    relp_status_t cuts_added(int32_t count, const int64_t* row_ptr, const int32_t* col_idx, const double* values, const double* rhs,
+                             int32_t entries, int32_t p);
     // relp_remove_cuts / relp_remove_columns: the lists of a call on the device (relp_kernels.h: launch_tab_compact), grown on demand;
     // what relp_removal_stats reports.  The rooms stay: the next add reuses what a removal freed.
     DeviceBuf<int32_t> d_rm_lists_;

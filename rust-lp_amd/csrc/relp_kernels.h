@@ -702,6 +702,52 @@ struct PoolAdd {
 void launch_pool_add_operands(const PoolView& pv, const MinusPi& mp, const PoolAdd& pa, hipStream_t s);
 // active[ids[x]] = flag for x < count (relp_pool_set_active); ids: device list
 void launch_pool_set_active(const PoolView& pv, const int32_t* ids, int32_t count, int32_t flag, hipStream_t s);
+// A cut pool on the device (relp_cutpool_create .. relp_cutpool_add): the PoolView of the column pool with the roles transposed
+// (relp_cutpool.hpp) -- pv.row holds structural columns, ascending inside a cut, pv.cost the right-hand sides -- and the norms, one
+// per cut.  Read-only to every launch below but for the activity flags.
+struct CutPoolView { PoolView pv; const double* norm; };
+// The current vertex over the structural columns: x[j] = b[r] where structural column j is basic in row r (basis[r] == j), +0.0
+// elsewhere.  x: nr_normal doubles of scratch; every launch sequence below first writes it ([x = +0.0, a memset] -> [k_cutpool_x, one
+// row per thread; a column is basic in at most one row, so no two threads write one word]) and its chains read it from there.
+struct Vertex { const double* b; const int32_t* basis; int32_t m, nr_normal; double* x; };
+void launch_cutpool_x(const Vertex& vx, hipStream_t s);
+// The slack of cut k at the vertex:  acc = 0.0, then acc = fma(value, x[column], acc) over the cut's entries in stored (ascending
+// column) order, s_k = rhs_k - acc: every operand rounded once.  The loads of a chain are issued sixteen entries at a time
+// (kPoolBatch): columns and values first, then the gathers of x; the order of the chain does not depend on it.
+// Separation (relp_cutpool_separate, relp_cutpool_slacks), in the shape of launch_pool_price: the pool indices are cut into
+// `segments` shares of S = ceil(count / segments) cuts and every share into chunks of kPoolChunk cuts:
+// [x] -> [k_cutpool_separate, grid segments x chunks (one dimension), 256 threads, one cut per thread, consecutive lanes for
+// consecutive cuts: s_all[k] = s_k; the key is s_k, or with by_efficacy s_k / norm_k (norm 0 counts as 1); a cut is a candidate
+// when it is active and s_k < -tol; the chunk's minimum in the total order (key, pool index) -> part_d / part_k[s * chunks + c],
+// (+inf, -1) without a candidate] -> [k_pool_fold, only when chunks > 1] -> [k_cutpool_winners, one workgroup: the winners in
+// ascending share order, out_k[i] and out_s[i] = s_all[out_k[i]], *found their number].  No atomics; the same launch on the same
+// state gives the same bits.  segments < 1: only s_all is written.  s_all: count doubles (always needed); part_d / part_k:
+// segments * pool_segment_chunks(count, segments) entries; out_k / out_s: segments entries; found: one.
+void launch_cutpool_separate(const CutPoolView& cv, const Vertex& vx, int32_t segments, double tol, int32_t by_efficacy, double* s_all,
+                             double* part_d, int32_t* part_k, int32_t* out_k, double* out_s, int32_t* found, hipStream_t s);
+// The operands of launch_tab_add_cuts for the pool cuts ids[0 .. count) (device list, distinct), formed on the device
+// (relp_cutpool_add) as Engine::add_cuts forms them on the host.  longest: the longest chosen cut (entries); room: the entries the
+// caller sized rows and coef for (the structural columns the chosen cuts touch bound the list).
+//   mark     nr_normal words of scratch: 0 for a column no chosen cut touches, 1 for a touched one that is not basic, 2 + the place
+//            in the union list for a touched one that is
+//   rows     the union list: the rows r, ascending, whose basic column is structural and touched; *entries_out = its length
+//   coef     coef[e * count + x] = the coefficient of the basic column of list entry e in cut ids[x], 0.0 elsewhere (room x count)
+//   A        rows a_row0 + x of the structural columns of the engine's matrix = the coefficients of cut ids[x], 0.0 elsewhere
+//   b_new    b_new[x] = rhs - acc, acc = fma(coef[e][x], b[rows[e]], acc) from 0.0 over the WHOLE list in ascending e, zeros
+//            included: the loop of Engine::add_cuts.  (The caller points it at b[m_old].)  The chosen cuts' flags are cleared.
+// [mark = 0] -> [k_cutpool_entries<false>, one workgroup per 256 entries of a chosen cut: mark[column] = 1; many writers, one
+// value] -> [k_cutpool_union, one workgroup, rows 256 at a time, an ordered scan over the flags: mark, rows, *entries_out] ->
+// [coef = 0, the new rows of A = 0] -> [k_cutpool_entries<true>, the same grid: one entry per thread into A, and into coef where
+// its column is in the list] -> [k_cutpool_chosen, one workgroup per chosen cut, the operands staged in LDS 256 entries at a
+// time, thread 0 chains: b_new, active = 0].  No atomics; every output word has one writer or one value.
+struct CutPoolAdd {
+    const int32_t* ids; int32_t count, m, nr_normal, longest, room;
+    const int32_t* basis; const double* b;
+    int32_t* mark; int32_t* rows; int32_t* entries_out; double* coef;
+    double* A; int64_t ld_a; int32_t a_row0;
+    double* b_new;
+};
+void launch_cutpool_add_operands(const CutPoolView& cv, const CutPoolAdd& ca, hipStream_t s);
 
 // ---- sparse LU engine ------------------------------------------------------------------------------
 // PRICE over CSC columns (thread per column), partial argmin per 256 columns

@@ -2375,4 +2375,191 @@ void launch_pool_set_active(const PoolView& pv, const int32_t* ids, int32_t coun
     hipLaunchKernelGGL(k_pool_set_active, dim3(cdiv(count, 256)), dim3(256), 0, s, pv, ids, (int)count, (int)flag);
 }
 
+// ------------------------------------------------------------------------------------------------
+// The cut pool (relp_cutpool_slacks, relp_cutpool_separate, relp_cutpool_add): the column pool transposed -- sliced ELL, one cut per
+// lane, pv.row holding structural columns (CutPoolView).  A cut's slack is one sequential fma chain, so the parallelism is across
+// cuts, never inside one.
+// ------------------------------------------------------------------------------------------------
+// The vertex over the structural columns, after x was cleared to +0.0: row r hands b[r] to its basic column where that is structural.
+__global__ void k_cutpool_x(Vertex vx) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= vx.m) return;
+    const int j = vx.basis[r];
+    if (j >= 0 && j < vx.nr_normal) vx.x[j] = vx.b[r];
+}
+
+// s_k = rhs[k] - sum value * x[column] over the entries of cut k in stored order: one chain from 0.0, the loads issued kPoolBatch
+// entries at a time as in pool_chain (columns and values first, then the gathers of x).  A padded entry (column < 0) gathers and
+// adds nothing.
+__device__ __forceinline__ double cutpool_chain(const PoolView& pv, const double* __restrict__ x, int nr_normal, int k) {
+    const int s = k / kPoolSlice;
+    const int64_t base = pv.slice_ptr[s], width = (pv.slice_ptr[s + 1] - base) / kPoolSlice;
+    const int32_t* __restrict__ col = pv.row + base + k % kPoolSlice;
+    const double* __restrict__ val = pv.val + base + k % kPoolSlice;
+    double acc = 0.0;
+    int64_t e = 0;
+    for (; e + kPoolBatch <= width; e += kPoolBatch) {
+        int c[kPoolBatch];
+        double v[kPoolBatch], xs[kPoolBatch];
+#pragma unroll
+        for (int t = 0; t < kPoolBatch; ++t) { c[t] = col[(e + t) * kPoolSlice]; v[t] = val[(e + t) * kPoolSlice]; }
+#pragma unroll
+        for (int t = 0; t < kPoolBatch; ++t) xs[t] = (c[t] >= 0 && c[t] < nr_normal) ? x[c[t]] : 0.0;
+#pragma unroll
+        for (int t = 0; t < kPoolBatch; ++t)
+            if (c[t] >= 0 && c[t] < nr_normal) acc = fma(v[t], xs[t], acc);
+    }
+    for (; e < width; ++e) {
+        const int c = col[e * kPoolSlice];
+        if (c >= 0 && c < nr_normal) acc = fma(val[e * kPoolSlice], x[c], acc);
+    }
+    return pv.cost[k] - acc;
+}
+
+// Chunk blockIdx.x % chunks of segment blockIdx.x / chunks (relp_kernels.h: launch_cutpool_separate).  part_d == nullptr: no partials.
+__global__ __launch_bounds__(kThreads) void k_cutpool_separate(CutPoolView cv, Vertex vx, int seg_size, int chunks, double tol, int by_efficacy,
+                                                               double* s_all, double* part_d, int32_t* part_k) {
+    const PoolView& pv = cv.pv;
+    const int seg = blockIdx.x / chunks, chunk = blockIdx.x % chunks;
+    const int64_t lo = (int64_t)seg * seg_size + (int64_t)chunk * kPoolChunk;
+    const int hi = (int)min(min(lo + kPoolChunk, (int64_t)(seg + 1) * seg_size), (int64_t)pv.count);
+    double best = INFINITY;
+    int best_k = INT32_MAX;
+    for (int64_t k64 = lo + threadIdx.x; k64 < hi; k64 += kThreads) {
+        const int k = (int)k64;
+        const double sl = cutpool_chain(pv, vx.x, vx.nr_normal, k);
+        s_all[k] = sl;
+        double key = sl;
+        if (by_efficacy) { const double nk = cv.norm[k]; key = sl / (nk == 0.0 ? 1.0 : nk); }
+        if (pv.active[k] && sl < -tol && key < best) { best = key; best_k = k; }     // (ascending k: the first of equal keys stays)
+    }
+    if (!part_d) return;
+    block_min_key<kThreads>(best, best_k);
+    if (threadIdx.x == 0) {
+        part_d[blockIdx.x] = best_k == INT32_MAX ? INFINITY : best;
+        part_k[blockIdx.x] = best_k == INT32_MAX ? -1 : best_k;
+    }
+}
+
+// k_pool_winners with the slack gathered in place of the key: one workgroup, the winners of the shares compacted in ascending share
+// order, out_s[i] = s_all[out_k[i]].
+__global__ __launch_bounds__(kThreads) void k_cutpool_winners(int segments, int chunks, const int32_t* __restrict__ part_k,
+                                                              const double* __restrict__ s_all, int count, int32_t* out_k, double* out_s,
+                                                              int32_t* found) {
+    __shared__ int s_scan[kThreads / 64];
+    int placed = 0;
+    for (int base = 0; base < segments; base += kThreads) {
+        const int seg = base + threadIdx.x;
+        int best_k = seg < segments ? part_k[(int64_t)seg * chunks] : -1;
+        if (best_k >= count) best_k = -1;
+        int total;
+        const int at = placed + block_flag_scan(best_k >= 0 ? 1 : 0, s_scan, &total);
+        if (best_k >= 0) { out_k[at] = best_k; out_s[at] = s_all[best_k]; }
+        placed += total;
+    }
+    if (threadIdx.x == 0) *found = placed;
+}
+
+// Entries 256 at a time, as k_pool_entries: with C = ceil(longest / 256), workgroup b has the entries (b % C) * 256 + threadIdx.x
+// of the chosen cut b / C.  SCATTER == false: the column is marked.  true: the value goes to its place in the cut's row of A, and
+// into coef where the column is in the union list.
+template <bool SCATTER>
+__global__ __launch_bounds__(kThreads) void k_cutpool_entries(PoolView pv, CutPoolAdd ca) {
+    const int per_cut = (ca.longest + kThreads - 1) / kThreads;
+    const int x = blockIdx.x / per_cut, k = ca.ids[x], s = k / kPoolSlice;
+    const int64_t base = pv.slice_ptr[s], width = (pv.slice_ptr[s + 1] - base) / kPoolSlice;
+    const int64_t e = (int64_t)(blockIdx.x % per_cut) * kThreads + threadIdx.x;
+    if (e >= width) return;
+    const int64_t at = base + e * kPoolSlice + k % kPoolSlice;
+    const int j = pv.row[at];
+    if (j < 0 || j >= ca.nr_normal) return;
+    if (!SCATTER) { ca.mark[j] = 1; return; }
+    const double v = pv.val[at];
+    ca.A[(int64_t)j * ca.ld_a + ca.a_row0 + x] = v;
+    const int place = ca.mark[j] - 2;
+    if (place >= 0 && place < ca.room) ca.coef[(int64_t)place * ca.count + x] = v;
+}
+
+// One workgroup: row r joins the union list iff its basic column is structural and marked; the list ascends in r.
+__global__ __launch_bounds__(kThreads) void k_cutpool_union(CutPoolAdd ca) {
+    __shared__ int s_scan[kThreads / 64];
+    int placed = 0;
+    for (int base = 0; base < ca.m; base += kThreads) {
+        const int r = base + threadIdx.x;
+        int j = -1;
+        if (r < ca.m) { j = ca.basis[r]; if (j < 0 || j >= ca.nr_normal || ca.mark[j] == 0) j = -1; }
+        int total;
+        const int at = placed + block_flag_scan(j >= 0 ? 1 : 0, s_scan, &total);
+        if (j >= 0) {
+            ca.mark[j] = 2 + at;                       // (basic in this row alone: the word's one writer)
+            if (at < ca.room) ca.rows[at] = r;
+        }
+        placed += total;
+    }
+    if (threadIdx.x == 0) *ca.entries_out = placed;
+}
+
+// b of the new row of the chosen cut blockIdx.x; its activity flag cleared.  One chain over the whole union list, zeros included, so
+// one thread adds; the workgroup fetches its operands 256 entries at a time into LDS (coef[e][x] and b[rows[e]]) and thread 0 chains
+// them from there in ascending e, as k_pool_chosen does.
+__global__ __launch_bounds__(kThreads) void k_cutpool_chosen(PoolView pv, CutPoolAdd ca) {
+    __shared__ double s_g[kThreads], s_b[kThreads];
+    const int x = blockIdx.x, k = ca.ids[x];
+    const int entries = min(*ca.entries_out, ca.room);
+    double acc = 0.0;
+    for (int e0 = 0; e0 < entries; e0 += kThreads) {
+        __syncthreads();                               // (thread 0 has read the previous 256)
+        const int e = e0 + threadIdx.x;
+        double g = 0.0, bv = 0.0;
+        if (e < entries) { g = ca.coef[(int64_t)e * ca.count + x]; bv = ca.b[ca.rows[e]]; }
+        s_g[threadIdx.x] = g; s_b[threadIdx.x] = bv;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const int n = min((int)kThreads, entries - e0);
+#pragma unroll 8
+            for (int j = 0; j < n; ++j) acc = fma(s_g[j], s_b[j], acc);
+        }
+    }
+    if (threadIdx.x == 0) {
+        ca.b_new[x] = pv.cost[k] - acc;
+        pv.active[k] = 0;
+    }
+}
+
+void launch_cutpool_x(const Vertex& vx, hipStream_t s) {
+    if (vx.nr_normal > 0) (void)hipMemsetAsync(vx.x, 0, sizeof(double) * (size_t)vx.nr_normal, s);
+    if (vx.m > 0 && vx.nr_normal > 0) hipLaunchKernelGGL(k_cutpool_x, dim3(cdiv(vx.m, 256)), dim3(256), 0, s, vx);
+}
+
+void launch_cutpool_separate(const CutPoolView& cv, const Vertex& vx, int32_t segments, double tol, int32_t by_efficacy, double* s_all,
+                             double* part_d, int32_t* part_k, int32_t* out_k, double* out_s, int32_t* found, hipStream_t s) {
+    const int32_t count = cv.pv.count;
+    if (count > 0) launch_cutpool_x(vx, s);
+    if (segments < 1) {
+        if (count > 0)
+            hipLaunchKernelGGL(k_cutpool_separate, dim3(cdiv(count, kPoolChunk)), dim3(kThreads), 0, s, cv, vx, (int)count, cdiv(count, kPoolChunk),
+                               tol, (int)by_efficacy, s_all, (double*)nullptr, (int32_t*)nullptr);
+        return;
+    }
+    const int chunks = pool_segment_chunks(count, segments);
+    if (count > 0)
+        hipLaunchKernelGGL(k_cutpool_separate, dim3((unsigned)((int64_t)segments * chunks)), dim3(kThreads), 0, s, cv, vx,
+                           (int)pool_segment_size(count, segments), chunks, tol, (int)by_efficacy, s_all, part_d, part_k);
+    if (count > 0 && chunks > 1) hipLaunchKernelGGL(k_pool_fold, dim3(segments), dim3(kThreads), 0, s, chunks, part_d, part_k);
+    hipLaunchKernelGGL(k_cutpool_winners, dim3(1), dim3(kThreads), 0, s, count > 0 ? (int)segments : 0, chunks, part_k, s_all, (int)count, out_k,
+                       out_s, found);
+}
+
+void launch_cutpool_add_operands(const CutPoolView& cv, const CutPoolAdd& ca, hipStream_t s) {
+    if (ca.count < 1 || ca.nr_normal < 1) return;      // (an LP has structural columns: Layout)
+    const dim3 grid((unsigned)((int64_t)cdiv(std::max(ca.longest, 1), kThreads) * ca.count));
+    (void)hipMemsetAsync(ca.mark, 0, sizeof(int32_t) * (size_t)ca.nr_normal, s);
+    if (ca.longest > 0) hipLaunchKernelGGL(k_cutpool_entries<false>, grid, dim3(kThreads), 0, s, cv.pv, ca);
+    hipLaunchKernelGGL(k_cutpool_union, dim3(1), dim3(kThreads), 0, s, ca);
+    if (ca.room > 0) (void)hipMemsetAsync(ca.coef, 0, sizeof(double) * (size_t)ca.room * (size_t)ca.count, s);
+    (void)hipMemset2DAsync(ca.A + ca.a_row0, sizeof(double) * (size_t)ca.ld_a, 0, sizeof(double) * (size_t)ca.count, (size_t)ca.nr_normal, s);
+    if (ca.longest > 0) hipLaunchKernelGGL(k_cutpool_entries<true>, grid, dim3(kThreads), 0, s, cv.pv, ca);
+    hipLaunchKernelGGL(k_cutpool_chosen, dim3(ca.count), dim3(kThreads), 0, s, cv.pv, ca);
+}
+
 }  // namespace relp

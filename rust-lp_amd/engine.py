@@ -132,6 +132,14 @@ _SIGNATURES = {
     "relp_pool_price": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
     "relp_pool_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
     "relp_pool_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
+    "relp_cutpool_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "relp_cutpool_destroy": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "relp_cutpool_set_active": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]),
+    "relp_cutpool_slacks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "relp_cutpool_separate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_void_p,
+                                        C.POINTER(C.c_int32)]),
+    "relp_cutpool_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
+    "relp_cutpool_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
     "relp_solve_relaxation": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int32)]),
     "relp_from_basis": (C.c_int, [C.c_void_p, C.c_void_p]),
     "relp_flush": (C.c_int, [C.c_void_p]),
@@ -503,6 +511,12 @@ class Tableau:
         without a flush or a re-tabulation (relp_add_cuts); cut k is row ``nr_rows() + k`` and its slack, basic in that row,
         column ``nr_columns() + k`` (both read before the call).  ``G`` is a dense ``count x nr_normal`` array or a CSR triple
         ``(row_ptr, col_idx, values)``; ``run_dual`` re-solves from there."""
+        count, ptr, idx, val, beta = self._csr_cuts(G, rhs)
+        self._ck(self._lib.relp_add_cuts(self._h, count, ptr.ctypes.data, idx.ctypes.data, val.ctypes.data, beta.ctypes.data))
+
+    def _csr_cuts(self, G, rhs):
+        """(count, row_ptr, col_idx, values, rhs) of cuts given as a dense ``count x nr_normal`` array or a CSR triple: what
+        relp_add_cuts and relp_cutpool_create take."""
         n = self.provider.nr_normal
         if isinstance(G, tuple):
             if len(G) != 3:
@@ -526,7 +540,17 @@ class Tableau:
         beta = np.ascontiguousarray(np.atleast_1d(rhs), dtype=np.float64)
         if beta.shape != (count,):
             raise ValueError("rhs must have one entry per cut")
-        self._ck(self._lib.relp_add_cuts(self._h, count, ptr.ctypes.data, idx.ctypes.data, val.ctypes.data, beta.ctypes.data))
+        return count, ptr, idx, val, beta
+
+    def cut_pool(self, G, rhs) -> "CutPool":
+        """A pool of candidate cuts ``G x <= rhs`` kept on the device (relp_cutpool_create): ``G`` and ``rhs`` as ``add_cuts`` takes
+        them.  The pool is separated against the vertex as it stands (``CutPool.separate``) and its winners are added in place
+        (``CutPool.add``) without their coefficients going through the host again; it belongs to this tableau."""
+        count, ptr, idx, val, beta = self._csr_cuts(G, rhs)
+        handle = C.c_void_p()
+        self._ck(self._lib.relp_cutpool_create(self._h, count, ptr.ctypes.data, idx.ctypes.data, val.ctypes.data, beta.ctypes.data,
+                                               C.byref(handle)))
+        return CutPool(self, handle, count)
 
     def reserve_cuts(self, rows: int) -> None:
         """Room for ``rows`` cut rows in all, without adding any (relp_reserve_cuts): the tableau is re-allocated and copied
@@ -1082,6 +1106,89 @@ def column_generation(tableau: Tableau, pool: ColumnPool, segments: int = 1, tol
             return rounds, added, OPTIMAL
         if rounds >= max_rounds:
             return rounds, added, RUNNING
+        pool.add(ids)
+        rounds += 1
+        added += int(ids.shape[0])
+
+
+class CutPool:
+    """A cut pool of a ``Tableau`` (``Tableau.cut_pool``): candidate cuts resident on the device, separated and added in place.
+    Freed by ``close()``, or with the tableau."""
+
+    def __init__(self, tableau: Tableau, handle, count: int):
+        self._t, self._p, self.count = tableau, handle, int(count)
+
+    def _call(self, name, *args):
+        if self._p is None:
+            raise RelpError("the cut pool is closed")
+        if not self._t._h:
+            raise RelpError("the cut pool's tableau is closed")
+        self._t._ck(getattr(self._t._lib, name)(self._t._h, self._p, *args))
+
+    def close(self) -> None:
+        if self._p is not None and self._t._h:
+            self._t._lib.relp_cutpool_destroy(self._t._h, self._p)
+        self._p = None
+
+    def slacks(self) -> np.ndarray:
+        """``s_k = rhs_k - g_k' x`` of every pool cut, active or not, at the current vertex (relp_cutpool_slacks): one fma chain
+        per cut over its entries in ascending column order; ``s_k < 0`` is a violated cut.  Read-only."""
+        out = np.zeros(self.count)
+        self._call("relp_cutpool_slacks", out.ctypes.data)
+        return out
+
+    def separate(self, segments: int = 1, tol: float = 1e-7, by_efficacy: bool = False):
+        """Separation (relp_cutpool_separate): the pool indices cut into ``segments`` equal shares, per share the active cut with
+        the smallest key among those with ``s_k < -tol``; the key is ``s_k``, or ``s_k / norm_k`` with ``by_efficacy`` (lowest
+        index among equals).  Returns (ids, slacks) of the winners, ascending share order."""
+        ids = np.zeros(max(int(segments), 1), dtype=np.int32)
+        s = np.zeros(max(int(segments), 1))
+        found = C.c_int32(0)
+        self._call("relp_cutpool_separate", int(segments), float(tol), 1 if by_efficacy else 0, ids.ctypes.data, s.ctypes.data,
+                   C.byref(found))
+        return ids[:found.value].copy(), s[:found.value].copy()
+
+    def add(self, ids) -> None:
+        """The pool cuts ``ids`` join the tableau as ``add_cuts`` would add them, in that order (relp_cutpool_add): cut k of the
+        list is row ``nr_rows() + k`` (read before the call); their activity flags are cleared, and stay cleared when a trial
+        that added them is rolled back."""
+        i = np.ascontiguousarray(np.atleast_1d(ids), dtype=np.int32)
+        if i.ndim != 1:
+            raise ValueError("ids must be one-dimensional")
+        self._call("relp_cutpool_add", i.ctypes.data, i.shape[0])
+
+    def set_active(self, ids, flag: bool) -> None:
+        """The activity flag of the pool cuts ``ids`` (relp_cutpool_set_active): an inactive cut has a slack but never wins."""
+        i = np.ascontiguousarray(np.atleast_1d(ids), dtype=np.int32)
+        if i.ndim != 1:
+            raise ValueError("ids must be one-dimensional")
+        self._call("relp_cutpool_set_active", i.ctypes.data, i.shape[0], 1 if flag else 0)
+
+    def stats(self) -> Tuple[int, int, int, int]:
+        """(pool cuts, nonzeros held, entries stored on the device with padding, separate calls so far); relp_cutpool_stats."""
+        out = (C.c_int64 * 4)()
+        self._call("relp_cutpool_stats", out)
+        return tuple(int(x) for x in out)
+
+
+def row_generation(tableau: Tableau, pool: CutPool, tol: float = 1e-7, per_round: int = 1, max_rounds: int = 100,
+                   by_efficacy: bool = False, max_iters: int = 1 << 40):
+    """The row-generation loop on a phase-2 tableau at a dual feasible basis: ``run_dual`` -> ``pool.separate(per_round, tol,
+    by_efficacy)`` -> ``pool.add(winners)`` until no active pool cut is violated, the LP is not optimal or ``max_rounds`` rounds have
+    added cuts.  ``per_round`` is the number of shares of a separation (at most the pool's cuts): a round adds at most that many
+    cuts.  Returns (rounds that added cuts, cuts added, objective); the objective is None unless the last separation found no
+    violated cut on an optimal tableau."""
+    rounds, added = 0, 0
+    segments = max(1, min(int(per_round), pool.count))
+    while True:
+        outcome = tableau.run_dual(max_iters)[1]
+        if outcome != OPTIMAL:
+            return rounds, added, None
+        ids, _ = pool.separate(segments, tol, by_efficacy)
+        if ids.shape[0] == 0:
+            return rounds, added, tableau.objective_function_value()
+        if rounds >= max_rounds:
+            return rounds, added, None
         pool.add(ids)
         rounds += 1
         added += int(ids.shape[0])
