@@ -1704,7 +1704,7 @@ relp_status_t Engine::remove_cuts(const int32_t* rows, int32_t count) {
     // the layout follows (check_remove_cuts passed: remove_cuts cannot fail), then its tables on the device
     (void)lay_.remove_cuts(rows, count, basis, &err_);
     rm_cuts_ += count;
-    pools_mark_stale(rows, count);                     // (relp_pool.hpp: a row below a pool's rows_at_create went)
+    pools_mark_stale(rows, count);                     // (relp_pool.hpp: a row below a pool's bound went)
     return finish_removal();
 }
 

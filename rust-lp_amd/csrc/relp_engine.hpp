@@ -31,29 +31,29 @@
 #include "relp_lu.hpp"
 #include "relp_pack.hpp"
 
-// A column pool of a handle (relp_pool_create .. relp_pool_stats; relp_engine_pool.cpp).  The host copy (relp_pool.hpp) is what
-// Layout::add_columns and the rebuilds are given; the device copy is what the price and the add read.  Owned by its Engine.
-struct relp_pool {
-    relp::PoolImage image;
-    relp::DeviceBuf<int64_t> d_slice_ptr;
-    relp::DeviceBuf<int32_t> d_row, d_part_k;
-    relp::DeviceBuf<double> d_val, d_cost, d_all, d_part_d;   // (d_all, d_part_*, d_out: scratch of a price, allocated at the first one)
-    relp::DeviceBuf<uint8_t> d_active;
-    relp::DeviceBuf<char> d_out;                          // what a price downloads: the winners' d, their pool indices, their number
-    bool stale = false;                                   // an engine row below image.rows_at_create went (relp_remove_cuts, the rollback of a trial)
-    int64_t price_calls = 0;
+namespace relp {
+// What a column pool and a cut pool of a handle share (relp_engine_pool.cpp).  The host copy (relp_pool.hpp) is what
+// Layout::add_columns / add_cuts and the rebuilds are given; the device copy is what the sweep and the add read.
+struct DevicePool {
+    PoolImage image;
+    DeviceBuf<int64_t> d_slice_ptr;
+    DeviceBuf<int32_t> d_idx, d_part_k;
+    DeviceBuf<double> d_val, d_scalar, d_all, d_part_d;   // (d_all, d_part_*, d_out: scratch of a sweep, allocated at the first one)
+    DeviceBuf<uint8_t> d_active;
+    DeviceBuf<char> d_out;                                // what a sweep downloads: the winners' values, their pool indices, their number
+    int64_t sweep_calls = 0;                              // relp_pool_price / relp_cutpool_separate calls that succeeded
+};
+}  // namespace relp
+
+// A column pool of a handle (relp_pool_create .. relp_pool_stats).  Owned by its Engine.
+struct relp_pool : relp::DevicePool {
+    bool stale = false;                                   // an engine row below image.bound went (relp_remove_cuts, the rollback of a trial)
 };
 
-// A cut pool of a handle (relp_cutpool_create .. relp_cutpool_stats; relp_engine_cutpool.cpp).  The host copy (relp_cutpool.hpp) is
-// what Layout::add_cuts and the rebuilds are given; the device copy is what the separation and the add read.  Owned by its Engine.
-struct relp_cutpool {
-    relp::CutPoolImage image;
-    relp::DeviceBuf<int64_t> d_slice_ptr;
-    relp::DeviceBuf<int32_t> d_col, d_part_k;
-    relp::DeviceBuf<double> d_val, d_rhs, d_norm, d_all, d_part_d;   // (d_all, d_part_*, d_out: scratch of a separation, allocated at the first one)
-    relp::DeviceBuf<uint8_t> d_active;
-    relp::DeviceBuf<char> d_out;                          // what a separation downloads: the winners' slacks, their pool indices, their number
-    int64_t separate_calls = 0;
+// A cut pool of a handle (relp_cutpool_create .. relp_cutpool_stats).  Owned by its Engine.
+struct relp_cutpool : relp::DevicePool {
+    std::vector<double> norm;                             // relp_cutpool.hpp: CutPoolImage
+    relp::DeviceBuf<double> d_norm;
 };
 
 namespace relp {
@@ -209,7 +209,7 @@ class Engine : private EngineQueue {
     relp_status_t pool_price(relp_pool* pool, int32_t segments, double tol, int32_t* ids_out, double* d_out, int32_t* found);
     relp_status_t pool_add(relp_pool* pool, const int32_t* ids, int32_t count);
     relp_status_t pool_stats(const relp_pool* pool, int64_t* out4) const;
-    // a pool of candidate cuts kept on the device (relp_engine_cutpool.cpp), the mirror image of the column pool: separated there
+    // a pool of candidate cuts kept on the device (relp_engine_pool.cpp), the column pool with the roles transposed: separated there
     // against the vertex as it stands (read-only), its winners picked there, the chosen cuts added as add_cuts adds them, their
     // coefficients, b and the basis never crossing the bus
     relp_status_t cutpool_create(int32_t count, const int64_t* row_ptr, const int32_t* col_idx, const double* values, const double* rhs,
@@ -420,17 +420,28 @@ class Engine : private EngineQueue {
     DeviceBuf<double> d_pool_minus_pi_;                   // -pi as a vector: scratch of every price and add (relp_kernels.h: MinusPi)
     relp_status_t pool_ready(const char* what, const relp_pool* pool, bool fresh);
     void pools_mark_stale(const int32_t* rows, int32_t count);             // engine rows went: the listed ones, or (nullptr) those from lay_.m on
-    PoolView pool_view(const relp_pool& pool) const;
     MinusPi minus_pi_view() const { return MinusPi{d_d_, d_cost_store_, d_idcol_, lay_.m, d_pool_minus_pi_}; }
     relp_status_t pool_launch_price(relp_pool& pool, int32_t segments, double tol, bool all);
+    // what the column pools and the cut pools do alike, each written once (`list`: pools_ or cutpools_; `w`: the words of the kind).
+    // The three member templates are defined in relp_engine_pool.cpp and used there alone: a use from another translation unit
+    // would not link.
+    template <class List> relp_status_t pool_mine(const char* what, const PoolWords& w, const List& list, const DevicePool* pool);
+    template <class List> relp_status_t pool_drop(const char* what, const PoolWords& w, List& list, const DevicePool* pool);
+    template <class List> relp_status_t pool_stats_in(const List& list, const DevicePool* pool, int64_t* out4) const;
+    relp_status_t pool_upload(DevicePool& dp, const std::vector<double>* norm, DeviceBuf<double>* d_norm);
+    PoolView pool_view(const DevicePool& dp) const;
+    relp_status_t pool_flags(const DevicePool& dp, const int32_t* ids, int32_t count, int32_t flag);
+    relp_status_t pool_flags_checked(const char* what, const PoolWords& w, const DevicePool& dp, const int32_t* ids, int32_t count, int32_t flag);
+    relp_status_t pool_sweep_scratch(DevicePool& dp, int32_t segments, bool all);
+    relp_status_t pool_winners(const char* what, DevicePool& dp, int32_t segments, int32_t* ids_out, double* out, int32_t* found);
+    void rename_prefix(const char* from, const char* to);                  // err_ said `from`, the call the checks were borrowed from
     // relp_cutpool_*: the cut pools of this handle (freed with it), the vertex over the structural columns and the marks of an add on
     // the device (relp_kernels.h: Vertex, launch_cutpool_add_operands), grown on demand; d_pool_ids_ and d_pool_entries_ are shared
     // with the column pools
     std::vector<std::unique_ptr<relp_cutpool>> cutpools_;
     DeviceBuf<double> d_cutpool_x_;
     DeviceBuf<int32_t> d_cutpool_mark_;
-    relp_status_t cutpool_ready(const char* what, const relp_cutpool* pool);
-    CutPoolView cutpool_view(const relp_cutpool& pool) const;
+    CutPoolView cutpool_view(const relp_cutpool& pool) const { return CutPoolView{pool_view(pool), pool.d_norm}; }
     Vertex vertex_view() const { return Vertex{d_b_, d_basis_, lay_.m, lay_.nr_normal, d_cutpool_x_}; }
     relp_status_t cutpool_launch_separate(relp_cutpool& pool, int32_t segments, double tol, int32_t by_efficacy);
     relp_status_t room_for_cuts(const char* what, int32_t count);         // the growth rule of relp_add_cuts, its room rule inside a trial

@@ -652,33 +652,37 @@ void launch_tab_gomory(const TableauView& tv, const DeferredUpdate& du, const Co
 // 256 CUs x 8 workgroups of 256 threads); each segment's tail of bytes % 16 bytes goes bytewise.  No atomics, no LDS.
 static constexpr int32_t kTabTrialGrid = 2048;
 void launch_tab_trial_copy(const TrialTable& t, hipStream_t s);
-// A column pool on the device (relp_pool_create .. relp_pool_add), read-only to every launch below but for the activity flags.
-// Sliced ELL as relp_pool.hpp packs it: pool column k is lane k % 64 of slice k / 64, entry e of it stands at
-// slice_ptr[k / 64] + e * 64 + k % 64 and slice s is (slice_ptr[s + 1] - slice_ptr[s]) / 64 entries wide; rows ascend inside a
-// column, padding has row -1 and is skipped by its row (it reaches no fma).  cost, active: one per pool column.
+// A pool on the device, the column pool (relp_pool_create .. relp_pool_add) or, inside a CutPoolView, the cut pool: read-only to
+// every launch below but for the activity flags.  Sliced ELL as relp_pool.hpp packs it: item k (a pool column, or a cut) is lane
+// k % 64 of slice k / 64, entry e of it stands at slice_ptr[k / 64] + e * 64 + k % 64 and slice s is
+// (slice_ptr[s + 1] - slice_ptr[s]) / 64 entries wide; the indices (rows, or structural columns) ascend inside an item, padding has
+// index -1 and is skipped by its index (it reaches no fma).  scalar (the cost, or the right-hand side), active: one per item.
 struct PoolView {
-    const int64_t* slice_ptr; const int32_t* row; const double* val; const double* cost; uint8_t* active;
+    const int64_t* slice_ptr; const int32_t* idx; const double* val; const double* scalar; uint8_t* active;
     int32_t count;
 };
+// The sweep both pools share (k_pool_sweep).  An item's value is one fma chain over its entries in stored (ascending index) order,
+// acc = fma(vec[index], value, acc), every operand rounded once; the loads of a chain are issued sixteen entries at a time
+// (kPoolBatch: indices and values first, then the gathers from vec), and the order of the chain does not depend on it.  The pool
+// indices are cut into `segments` shares of S = ceil(count / segments) items and every share into chunks of kPoolChunk items:
+// [k_pool_sweep, grid segments x chunks (one dimension), 256 threads: thread t of chunk (s, c) has the item
+// s * S + c * kPoolChunk + t where that lies below the end of the share and of the pool -- consecutive lanes, consecutive items, so
+// a wave reads consecutive entries of a slice; all[k] = the value when `all` is given; an item is a candidate when it is active and
+// its value < -tol; the chunk's minimum in the total order (key, pool index) by block_min_key -> part_d / part_k[s * chunks + c],
+// (+inf, -1) without a candidate] -> [k_pool_fold, only when chunks > 1, one workgroup per share: the share's chunks folded in the
+// same order into its first slot part_d / part_k[s * chunks]] -> [k_pool_winners, one workgroup of 256 threads, shares 256 at a
+// time: an ordered scan over the 256 flags "has a winner" gives every winner its place; out_k / out[0 .. *found) = the winners in
+// ascending share order, out = the winner's key or, where the launch says so, its value].  No atomics; minima in a total order and
+// one fma chain per item: the same launch on the same state gives the same bits.  segments < 1: only `all` is written (no partials,
+// no further launch).  part_d / part_k: segments * pool_segment_chunks(count, segments) entries; out_k / out: segments entries;
+// found: one.
+//
 // -pi as relp_get_minus_pi reads it off the tableau: (-pi)_i = d[idcol[i]] - cost_store[idcol[i]], rounded once, over the m engine
 // rows.  vec: m doubles of scratch; every launch below first writes -pi there (k_pool_minus_pi, one row per thread) and its chains
 // read it from there.
 struct MinusPi { const double* d; const double* cost_store; const int32_t* idcol; int32_t m; double* vec; };
-// The reduced cost of pool column k:  d_k = cost[k], then d_k = fma((-pi)_row, value, d_k) over the column's entries in stored
-// (ascending row) order -- the chain Engine::add_columns forms for d_new, to the bit.  The loads of a chain are issued sixteen
-// entries at a time (kPoolBatch); the order of the chain does not depend on it.
-// Multiple pricing (relp_pool_price, relp_pool_reduced_costs).  The pool indices are cut into `segments` shares of
-// S = ceil(count / segments) columns and every share into chunks of kPoolChunk columns:
-// [k_pool_minus_pi] -> [k_pool_price, grid segments x chunks (one dimension), 256 threads: thread t of chunk (s, c) prices the column
-// s * S + c * kPoolChunk + t where that lies below the end of the share and of the pool -- consecutive lanes, consecutive columns,
-// so a wave reads consecutive entries of a slice; d_all[k] = d_k when d_all is given; a column is a candidate when it is active and
-// d_k < -tol; the chunk's minimum in the total order (d, pool index) by block_min_key -> part_d / part_k[s * chunks + c], (+inf, -1)
-// without a candidate] -> [k_pool_fold, only when chunks > 1, one workgroup per share: the share's chunks folded in the same order
-// into its first slot part_d / part_k[s * chunks]] -> [k_pool_winners, one workgroup of 256 threads, shares 256 at a time: an
-// ordered scan over the 256 flags "has a winner" gives every winner its place; out_k / out_d[0 .. *found) = the winners in
-// ascending share order].  No atomics; minima in a total order and one fma chain per column: the same launch on the same state
-// gives the same bits.  segments < 1: only d_all is written (no partials, no further launch).
-// part_d / part_k: segments * pool_segment_chunks(count, segments) entries; out_k / out_d: segments entries; found: one.
+// Multiple pricing (relp_pool_price, relp_pool_reduced_costs): [k_pool_minus_pi] -> the sweep with the reduced cost as value and
+// as key -- the chain from cost[k] over -pi, the one Engine::add_columns forms for d_new, to the bit; out_d = the key.
 void launch_pool_price(const PoolView& pv, const MinusPi& mp, int32_t segments, double tol, double* d_all, double* part_d, int32_t* part_k,
                        int32_t* out_k, double* out_d, int32_t* found, hipStream_t s);
 // The operands of launch_tab_add_columns for the pool columns ids[0 .. count) (device list, distinct), formed on the device
@@ -702,27 +706,17 @@ struct PoolAdd {
 void launch_pool_add_operands(const PoolView& pv, const MinusPi& mp, const PoolAdd& pa, hipStream_t s);
 // active[ids[x]] = flag for x < count (relp_pool_set_active); ids: device list
 void launch_pool_set_active(const PoolView& pv, const int32_t* ids, int32_t count, int32_t flag, hipStream_t s);
-// A cut pool on the device (relp_cutpool_create .. relp_cutpool_add): the PoolView of the column pool with the roles transposed
-// (relp_cutpool.hpp) -- pv.row holds structural columns, ascending inside a cut, pv.cost the right-hand sides -- and the norms, one
-// per cut.  Read-only to every launch below but for the activity flags.
+// A cut pool on the device (relp_cutpool_create .. relp_cutpool_add): a PoolView whose items are cuts over the structural columns
+// with their right-hand sides (relp_cutpool.hpp), and the norms, one per cut.
 struct CutPoolView { PoolView pv; const double* norm; };
 // The current vertex over the structural columns: x[j] = b[r] where structural column j is basic in row r (basis[r] == j), +0.0
 // elsewhere.  x: nr_normal doubles of scratch; every launch sequence below first writes it ([x = +0.0, a memset] -> [k_cutpool_x, one
 // row per thread; a column is basic in at most one row, so no two threads write one word]) and its chains read it from there.
 struct Vertex { const double* b; const int32_t* basis; int32_t m, nr_normal; double* x; };
 void launch_cutpool_x(const Vertex& vx, hipStream_t s);
-// The slack of cut k at the vertex:  acc = 0.0, then acc = fma(value, x[column], acc) over the cut's entries in stored (ascending
-// column) order, s_k = rhs_k - acc: every operand rounded once.  The loads of a chain are issued sixteen entries at a time
-// (kPoolBatch): columns and values first, then the gathers of x; the order of the chain does not depend on it.
-// Separation (relp_cutpool_separate, relp_cutpool_slacks), in the shape of launch_pool_price: the pool indices are cut into
-// `segments` shares of S = ceil(count / segments) cuts and every share into chunks of kPoolChunk cuts:
-// [x] -> [k_cutpool_separate, grid segments x chunks (one dimension), 256 threads, one cut per thread, consecutive lanes for
-// consecutive cuts: s_all[k] = s_k; the key is s_k, or with by_efficacy s_k / norm_k (norm 0 counts as 1); a cut is a candidate
-// when it is active and s_k < -tol; the chunk's minimum in the total order (key, pool index) -> part_d / part_k[s * chunks + c],
-// (+inf, -1) without a candidate] -> [k_pool_fold, only when chunks > 1] -> [k_cutpool_winners, one workgroup: the winners in
-// ascending share order, out_k[i] and out_s[i] = s_all[out_k[i]], *found their number].  No atomics; the same launch on the same
-// state gives the same bits.  segments < 1: only s_all is written.  s_all: count doubles (always needed); part_d / part_k:
-// segments * pool_segment_chunks(count, segments) entries; out_k / out_s: segments entries; found: one.
+// Separation (relp_cutpool_separate, relp_cutpool_slacks): [x] -> the sweep with the slack as value -- s_k = rhs_k - acc, acc the
+// chain from 0.0 over x, an entry on a column >= nr_normal skipped like padding -- and as key s_k or, with by_efficacy,
+// s_k / norm_k (norm 0 counts as 1); out_s[i] = s_all[out_k[i]], the slack, not the key.  s_all: count doubles (always needed).
 void launch_cutpool_separate(const CutPoolView& cv, const Vertex& vx, int32_t segments, double tol, int32_t by_efficacy, double* s_all,
                              double* part_d, int32_t* part_k, int32_t* out_k, double* out_s, int32_t* found, hipStream_t s);
 // The operands of launch_tab_add_cuts for the pool cuts ids[0 .. count) (device list, distinct), formed on the device

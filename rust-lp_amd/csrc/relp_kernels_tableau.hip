@@ -2142,8 +2142,8 @@ void launch_tab_trial_copy(const TrialTable& t, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// The column pool (relp_pool_price, relp_pool_reduced_costs, relp_pool_add): sliced ELL, one pool column per lane (PoolView).  A
-// column's reduced cost is one sequential fma chain, so the parallelism is across columns, never inside one.
+// The pools (relp_pool_*, relp_cutpool_*): sliced ELL, one item -- a pool column, or a cut -- per lane (PoolView).  An item's value
+// (the reduced cost, or the slack) is one sequential fma chain, so the parallelism is across items, never inside one.
 // ------------------------------------------------------------------------------------------------
 // -pi as a vector of its own, once per launch sequence: vec[i] = d[idcol[i]] - cost_store[idcol[i]], one rounding, what
 // relp_get_minus_pi forms on the host.  The chains then make two dependent loads per entry (row, vec[row]) instead of three
@@ -2153,49 +2153,88 @@ __global__ void k_pool_minus_pi(MinusPi mp) {
     if (i < mp.m) { const int c = mp.idcol[i]; mp.vec[i] = mp.d[c] - mp.cost_store[c]; }
 }
 
-// d_k = cost[k] + sum (-pi)_row * value over the entries of pool column k in stored order: one chain from the cost.  The loads do
-// not depend on the chain, so they are issued kPoolBatch entries at a time before any is used, as in for_pending: rows and values
-// first (consecutive lanes, consecutive addresses), then the gathers of -pi; a thread makes two round trips per batch instead of two
-// per entry.  A padded entry (row < 0) gathers and adds nothing.  The order of the chain is the stored order whatever the batch is.
+// Where item k of a pool lives: its entry e has its index at idx[e * kPoolSlice] and its value at val[e * kPoolSlice], e < width.
+struct PoolLane {
+    const int32_t* __restrict__ idx;
+    const double* __restrict__ val;
+    int64_t width;
+    __device__ __forceinline__ PoolLane(const PoolView& pv, int k) {
+        const int s = k / kPoolSlice;
+        const int64_t base = pv.slice_ptr[s];
+        width = (pv.slice_ptr[s + 1] - base) / kPoolSlice;
+        idx = pv.idx + base + k % kPoolSlice;
+        val = pv.val + base + k % kPoolSlice;
+    }
+};
+
+// acc0 + sum vec[index] * value over the entries of a lane in stored order: one chain from acc0.  The loads do not depend on the
+// chain, so they are issued kPoolBatch entries at a time before any is used, as in for_pending: indices and values first
+// (consecutive lanes, consecutive addresses), then the gathers from vec; a thread makes two round trips per batch instead of two
+// per entry.  A padded entry (index < 0) gathers and adds nothing, and with BOUNDED neither does an entry whose index is not below
+// `bound`.  The order of the chain is the stored order whatever the batch is.
 static constexpr int kPoolBatch = 16;
-__device__ __forceinline__ double pool_chain(const PoolView& pv, const double* __restrict__ minus_pi, int k) {
-    const int s = k / kPoolSlice;
-    const int64_t base = pv.slice_ptr[s], width = (pv.slice_ptr[s + 1] - base) / kPoolSlice;
-    const int32_t* __restrict__ row = pv.row + base + k % kPoolSlice;
-    const double* __restrict__ val = pv.val + base + k % kPoolSlice;
-    double acc = pv.cost[k];
+template <bool BOUNDED>
+__device__ __forceinline__ double pool_chain(const PoolLane& ln, const double* __restrict__ vec, int bound, double acc0) {
+    const auto live = [&](int i) { return i >= 0 && (!BOUNDED || i < bound); };
+    double acc = acc0;
     int64_t e = 0;
-    for (; e + kPoolBatch <= width; e += kPoolBatch) {
-        int r[kPoolBatch];
-        double v[kPoolBatch], p[kPoolBatch];
+    for (; e + kPoolBatch <= ln.width; e += kPoolBatch) {
+        int i[kPoolBatch];
+        double v[kPoolBatch], g[kPoolBatch];
 #pragma unroll
-        for (int t = 0; t < kPoolBatch; ++t) { r[t] = row[(e + t) * kPoolSlice]; v[t] = val[(e + t) * kPoolSlice]; }
+        for (int t = 0; t < kPoolBatch; ++t) { i[t] = ln.idx[(e + t) * kPoolSlice]; v[t] = ln.val[(e + t) * kPoolSlice]; }
 #pragma unroll
-        for (int t = 0; t < kPoolBatch; ++t) p[t] = r[t] >= 0 ? minus_pi[r[t]] : 0.0;
+        for (int t = 0; t < kPoolBatch; ++t) g[t] = live(i[t]) ? vec[i[t]] : 0.0;
 #pragma unroll
         for (int t = 0; t < kPoolBatch; ++t)
-            if (r[t] >= 0) acc = fma(p[t], v[t], acc);
+            if (live(i[t])) acc = fma(g[t], v[t], acc);
     }
-    for (; e < width; ++e) {
-        const int r = row[e * kPoolSlice];
-        if (r >= 0) acc = fma(minus_pi[r], val[e * kPoolSlice], acc);
+    for (; e < ln.width; ++e) {
+        const int i = ln.idx[e * kPoolSlice];
+        if (live(i)) acc = fma(vec[i], ln.val[e * kPoolSlice], acc);
     }
     return acc;
 }
 
-// Chunk blockIdx.x % chunks of segment blockIdx.x / chunks (relp_kernels.h: launch_pool_price).  segments < 1: one share, no partials.
-__global__ __launch_bounds__(kThreads) void k_pool_price(PoolView pv, MinusPi mp, int seg_size, int chunks, double tol, double* d_all,
-                                                         double* part_d, int32_t* part_k) {
+// What a sweep asks of item k: its value and, from the value, the key its winners are ranked by; kAlwaysAll: the vector of every
+// item's value is always written (the kernel then does not test the pointer).
+// The reduced cost of a pool column: the chain from its cost over -pi; the key is the value.
+struct ReducedCost {
+    static constexpr bool kAlwaysAll = false;
+    PoolView pv; const double* minus_pi;
+    __device__ __forceinline__ double value(int k) const { return pool_chain<false>(PoolLane(pv, k), minus_pi, 0, pv.scalar[k]); }
+    __device__ __forceinline__ double key(int, double d) const { return d; }
+};
+// The slack of a cut at the vertex x: its right-hand side minus the chain from 0.0 over x; the key is the slack or the efficacy.
+struct Slack {
+    static constexpr bool kAlwaysAll = true;
+    PoolView pv; const double* norm; const double* x; int nr_normal, by_efficacy;
+    __device__ __forceinline__ double value(int k) const {
+        const double acc = pool_chain<true>(PoolLane(pv, k), x, nr_normal, 0.0);
+        return pv.scalar[k] - acc;
+    }
+    __device__ __forceinline__ double key(int k, double sl) const {
+        if (!by_efficacy) return sl;
+        const double nk = norm[k];
+        return sl / (nk == 0.0 ? 1.0 : nk);
+    }
+};
+
+// Chunk blockIdx.x % chunks of segment blockIdx.x / chunks (relp_kernels.h: the sweep).  segments < 1: one share, no partials.
+template <class Scorer>
+__global__ __launch_bounds__(kThreads) void k_pool_sweep(Scorer sc, int seg_size, int chunks, double tol, double* all, double* part_d,
+                                                         int32_t* part_k) {
     const int seg = blockIdx.x / chunks, chunk = blockIdx.x % chunks;
     const int64_t lo = (int64_t)seg * seg_size + (int64_t)chunk * kPoolChunk;
-    const int hi = (int)min(min(lo + kPoolChunk, (int64_t)(seg + 1) * seg_size), (int64_t)pv.count);
+    const int hi = (int)min(min(lo + kPoolChunk, (int64_t)(seg + 1) * seg_size), (int64_t)sc.pv.count);
     double best = INFINITY;
     int best_k = INT32_MAX;
     for (int64_t k64 = lo + threadIdx.x; k64 < hi; k64 += kThreads) {
         const int k = (int)k64;
-        const double d = pool_chain(pv, mp.vec, k);
-        if (d_all) d_all[k] = d;
-        if (pv.active[k] && d < -tol && d < best) { best = d; best_k = k; }     // (ascending k: the first of equal d stays)
+        const double v = sc.value(k);
+        if (Scorer::kAlwaysAll || all) all[k] = v;
+        const double key = sc.key(k, v);
+        if (sc.pv.active[k] && v < -tol && key < best) { best = key; best_k = k; }     // (ascending k: the first of equal keys stays)
     }
     if (!part_d) return;
     block_min_key<kThreads>(best, best_k);
@@ -2245,37 +2284,48 @@ __global__ __launch_bounds__(kThreads) void k_pool_fold(int chunks, double* part
     }
 }
 
-// One workgroup: the winners of the shares (the first slot of each share's partials), compacted in ascending share order.
+// One workgroup: the winners of the shares (the first slot of each share's partials), compacted in ascending share order with their
+// keys or, where `values` is given, with values[winner] (the cut pool: the slack, not the efficacy).
 __global__ __launch_bounds__(kThreads) void k_pool_winners(int segments, int chunks, const double* __restrict__ part_d,
-                                                           const int32_t* __restrict__ part_k, int32_t* out_k, double* out_d, int32_t* found) {
+                                                           const int32_t* __restrict__ part_k, const double* __restrict__ values, int count,
+                                                           int32_t* out_k, double* out, int32_t* found) {
     __shared__ int s_scan[kThreads / 64];
     int placed = 0;
     for (int base = 0; base < segments; base += kThreads) {
         const int seg = base + threadIdx.x;
-        const int best_k = seg < segments ? part_k[(int64_t)seg * chunks] : -1;
+        int best_k = seg < segments ? part_k[(int64_t)seg * chunks] : -1;
+        if (best_k >= count) best_k = -1;
         int total;
         const int at = placed + block_flag_scan(best_k >= 0 ? 1 : 0, s_scan, &total);
-        if (best_k >= 0) { out_k[at] = best_k; out_d[at] = part_d[(int64_t)seg * chunks]; }
+        if (best_k >= 0) { out_k[at] = best_k; out[at] = values ? values[best_k] : part_d[(int64_t)seg * chunks]; }
         placed += total;
     }
     if (threadIdx.x == 0) *found = placed;
 }
 
-// Entries 256 at a time: with C = ceil(longest / 256), workgroup b has the entries (b % C) * 256 + threadIdx.x of the chosen column
-// b / C (relp_kernels.h: launch_pool_add_operands).  SCATTER == false: the row is marked.  true: the value goes to its place in
-// coef and in the column's row-space vector.
+// The front of both entries kernels.  Entries 256 at a time: with C = ceil(longest / 256), workgroup b has the entries
+// (b % C) * 256 + threadIdx.x of the chosen item x = b / C.  i: the entry's index, -1 where the thread has nothing to do (behind the
+// item's slice width, padding, an index not below `bound`); v: where its value stands.
+struct PoolEntry { int x, i; const double* v; };
+__device__ __forceinline__ PoolEntry pool_entry(const PoolView& pv, const int32_t* __restrict__ ids, int longest, int bound) {
+    const int per_item = (longest + kThreads - 1) / kThreads;
+    const int x = blockIdx.x / per_item;
+    const PoolLane ln(pv, ids[x]);
+    const int64_t e = (int64_t)(blockIdx.x % per_item) * kThreads + threadIdx.x;
+    if (e >= ln.width) return PoolEntry{x, -1, nullptr};
+    const int i = ln.idx[e * kPoolSlice];
+    return PoolEntry{x, i < bound ? i : -1, ln.val + e * kPoolSlice};
+}
+
+// One entry of a chosen column per thread (pool_entry; relp_kernels.h: launch_pool_add_operands).  SCATTER == false: the row is
+// marked.  true: the value goes to its place in coef and in the column's row-space vector.
 template <bool SCATTER>
 __global__ __launch_bounds__(kThreads) void k_pool_entries(PoolView pv, PoolAdd pa) {
-    const int per_column = (pa.longest + kThreads - 1) / kThreads;
-    const int x = blockIdx.x / per_column, k = pa.ids[x], s = k / kPoolSlice;
-    const int64_t base = pv.slice_ptr[s], width = (pv.slice_ptr[s + 1] - base) / kPoolSlice;
-    const int64_t e = (int64_t)(blockIdx.x % per_column) * kThreads + threadIdx.x;
-    if (e >= width) return;
-    const int64_t at = base + e * kPoolSlice + k % kPoolSlice;
-    const int r = pv.row[at];
-    if (r < 0 || r >= pa.m) return;
+    const PoolEntry en = pool_entry(pv, pa.ids, pa.longest, pa.m);
+    const int x = en.x, r = en.i;
+    if (r < 0) return;
     if (!SCATTER) { pa.rank[r] = 1; return; }
-    const double v = pv.val[at];
+    const double v = *en.v;
     if (pa.rank[r] < 0 || pa.rank[r] >= pa.entries) return;      // (a list longer than the caller sized coef for: reported through *entries_out)
     pa.coef[(int64_t)pa.rank[r] * pa.count + x] = v;
     pa.col_a[(int64_t)(pa.a0 + x) * pa.ld_c + r] = v;
@@ -2303,19 +2353,18 @@ __global__ __launch_bounds__(kThreads) void k_pool_union(PoolAdd pa, const int32
 __global__ __launch_bounds__(kThreads) void k_pool_chosen(PoolView pv, MinusPi mp, PoolAdd pa) {
     __shared__ double s_p[kThreads], s_v[kThreads];
     __shared__ int s_r[kThreads];
-    const int x = blockIdx.x, k = pa.ids[x], s = k / kPoolSlice;
-    const int64_t base = pv.slice_ptr[s], width = (pv.slice_ptr[s + 1] - base) / kPoolSlice;
-    const int32_t* __restrict__ row = pv.row + base + k % kPoolSlice;
-    const double* __restrict__ val = pv.val + base + k % kPoolSlice;
-    double acc = pv.cost[k];
+    const int x = blockIdx.x, k = pa.ids[x];
+    const PoolLane ln(pv, k);
+    const int64_t width = ln.width;
+    double acc = pv.scalar[k];
     for (int64_t e0 = 0; e0 < width; e0 += kThreads) {
         __syncthreads();                               // (thread 0 has read the previous 256)
         const int64_t e = e0 + threadIdx.x;
         int r = -1;
         double v = 0.0, p = 0.0;
         if (e < width) {
-            r = row[e * kPoolSlice];
-            if (r >= 0) { v = val[e * kPoolSlice]; p = mp.vec[r]; }
+            r = ln.idx[e * kPoolSlice];
+            if (r >= 0) { v = ln.val[e * kPoolSlice]; p = mp.vec[r]; }
         }
         s_r[threadIdx.x] = r; s_v[threadIdx.x] = v; s_p[threadIdx.x] = p;
         __syncthreads();
@@ -2330,7 +2379,7 @@ __global__ __launch_bounds__(kThreads) void k_pool_chosen(PoolView pv, MinusPi m
     }
     if (threadIdx.x == 0) {
         pa.d_new[x] = acc;
-        pa.cost_new[x] = pv.cost[k];
+        pa.cost_new[x] = pv.scalar[k];
         pv.active[k] = 0;
     }
 }
@@ -2340,21 +2389,30 @@ __global__ void k_pool_set_active(PoolView pv, const int32_t* __restrict__ ids, 
     if (x < count) pv.active[ids[x]] = (uint8_t)flag;
 }
 
+// The launches of a sweep behind its prologue (relp_kernels.h).  values: what the winners come back with in place of their keys.
+template <class Scorer>
+static void launch_pool_sweep(const Scorer& sc, int32_t segments, double tol, double* all, double* part_d, int32_t* part_k,
+                              const double* values, int32_t* out_k, double* out, int32_t* found, hipStream_t s) {
+    const int32_t count = sc.pv.count;
+    if (segments < 1) {
+        if (count > 0 && all)
+            hipLaunchKernelGGL(k_pool_sweep<Scorer>, dim3(cdiv(count, kPoolChunk)), dim3(kThreads), 0, s, sc, (int)count, cdiv(count, kPoolChunk), tol,
+                               all, (double*)nullptr, (int32_t*)nullptr);
+        return;
+    }
+    const int chunks = pool_segment_chunks(count, segments);
+    if (count > 0)
+        hipLaunchKernelGGL(k_pool_sweep<Scorer>, dim3((unsigned)((int64_t)segments * chunks)), dim3(kThreads), 0, s, sc,
+                           (int)pool_segment_size(count, segments), chunks, tol, all, part_d, part_k);
+    if (count > 0 && chunks > 1) hipLaunchKernelGGL(k_pool_fold, dim3(segments), dim3(kThreads), 0, s, chunks, part_d, part_k);
+    hipLaunchKernelGGL(k_pool_winners, dim3(1), dim3(kThreads), 0, s, count > 0 ? (int)segments : 0, chunks, part_d, part_k, values, (int)count,
+                       out_k, out, found);
+}
+
 void launch_pool_price(const PoolView& pv, const MinusPi& mp, int32_t segments, double tol, double* d_all, double* part_d, int32_t* part_k,
                        int32_t* out_k, double* out_d, int32_t* found, hipStream_t s) {
     if (pv.count > 0 && mp.m > 0) hipLaunchKernelGGL(k_pool_minus_pi, dim3(cdiv(mp.m, 256)), dim3(256), 0, s, mp);
-    if (segments < 1) {
-        if (pv.count > 0 && d_all)
-            hipLaunchKernelGGL(k_pool_price, dim3(cdiv(pv.count, kPoolChunk)), dim3(kThreads), 0, s, pv, mp, (int)pv.count, cdiv(pv.count, kPoolChunk),
-                               tol, d_all, (double*)nullptr, (int32_t*)nullptr);
-        return;
-    }
-    const int chunks = pool_segment_chunks(pv.count, segments);
-    if (pv.count > 0)
-        hipLaunchKernelGGL(k_pool_price, dim3((unsigned)((int64_t)segments * chunks)), dim3(kThreads), 0, s, pv, mp,
-                           (int)pool_segment_size(pv.count, segments), chunks, tol, d_all, part_d, part_k);
-    if (pv.count > 0 && chunks > 1) hipLaunchKernelGGL(k_pool_fold, dim3(segments), dim3(kThreads), 0, s, chunks, part_d, part_k);
-    hipLaunchKernelGGL(k_pool_winners, dim3(1), dim3(kThreads), 0, s, pv.count > 0 ? (int)segments : 0, chunks, part_d, part_k, out_k, out_d, found);
+    launch_pool_sweep(ReducedCost{pv, mp.vec}, segments, tol, d_all, part_d, part_k, nullptr, out_k, out_d, found, s);
 }
 
 void launch_pool_add_operands(const PoolView& pv, const MinusPi& mp, const PoolAdd& pa, hipStream_t s) {
@@ -2376,9 +2434,8 @@ void launch_pool_set_active(const PoolView& pv, const int32_t* ids, int32_t coun
 }
 
 // ------------------------------------------------------------------------------------------------
-// The cut pool (relp_cutpool_slacks, relp_cutpool_separate, relp_cutpool_add): the column pool transposed -- sliced ELL, one cut per
-// lane, pv.row holding structural columns (CutPoolView).  A cut's slack is one sequential fma chain, so the parallelism is across
-// cuts, never inside one.
+// The cut pool's own (relp_cutpool_slacks, relp_cutpool_separate, relp_cutpool_add): the items are cuts, pv.idx holds structural
+// columns, pv.scalar the right-hand sides (CutPoolView).  The sweep is k_pool_sweep<Slack> above.
 // ------------------------------------------------------------------------------------------------
 // The vertex over the structural columns, after x was cleared to +0.0: row r hands b[r] to its basic column where that is structural.
 __global__ void k_cutpool_x(Vertex vx) {
@@ -2388,93 +2445,15 @@ __global__ void k_cutpool_x(Vertex vx) {
     if (j >= 0 && j < vx.nr_normal) vx.x[j] = vx.b[r];
 }
 
-// s_k = rhs[k] - sum value * x[column] over the entries of cut k in stored order: one chain from 0.0, the loads issued kPoolBatch
-// entries at a time as in pool_chain (columns and values first, then the gathers of x).  A padded entry (column < 0) gathers and
-// adds nothing.
-__device__ __forceinline__ double cutpool_chain(const PoolView& pv, const double* __restrict__ x, int nr_normal, int k) {
-    const int s = k / kPoolSlice;
-    const int64_t base = pv.slice_ptr[s], width = (pv.slice_ptr[s + 1] - base) / kPoolSlice;
-    const int32_t* __restrict__ col = pv.row + base + k % kPoolSlice;
-    const double* __restrict__ val = pv.val + base + k % kPoolSlice;
-    double acc = 0.0;
-    int64_t e = 0;
-    for (; e + kPoolBatch <= width; e += kPoolBatch) {
-        int c[kPoolBatch];
-        double v[kPoolBatch], xs[kPoolBatch];
-#pragma unroll
-        for (int t = 0; t < kPoolBatch; ++t) { c[t] = col[(e + t) * kPoolSlice]; v[t] = val[(e + t) * kPoolSlice]; }
-#pragma unroll
-        for (int t = 0; t < kPoolBatch; ++t) xs[t] = (c[t] >= 0 && c[t] < nr_normal) ? x[c[t]] : 0.0;
-#pragma unroll
-        for (int t = 0; t < kPoolBatch; ++t)
-            if (c[t] >= 0 && c[t] < nr_normal) acc = fma(v[t], xs[t], acc);
-    }
-    for (; e < width; ++e) {
-        const int c = col[e * kPoolSlice];
-        if (c >= 0 && c < nr_normal) acc = fma(val[e * kPoolSlice], x[c], acc);
-    }
-    return pv.cost[k] - acc;
-}
-
-// Chunk blockIdx.x % chunks of segment blockIdx.x / chunks (relp_kernels.h: launch_cutpool_separate).  part_d == nullptr: no partials.
-__global__ __launch_bounds__(kThreads) void k_cutpool_separate(CutPoolView cv, Vertex vx, int seg_size, int chunks, double tol, int by_efficacy,
-                                                               double* s_all, double* part_d, int32_t* part_k) {
-    const PoolView& pv = cv.pv;
-    const int seg = blockIdx.x / chunks, chunk = blockIdx.x % chunks;
-    const int64_t lo = (int64_t)seg * seg_size + (int64_t)chunk * kPoolChunk;
-    const int hi = (int)min(min(lo + kPoolChunk, (int64_t)(seg + 1) * seg_size), (int64_t)pv.count);
-    double best = INFINITY;
-    int best_k = INT32_MAX;
-    for (int64_t k64 = lo + threadIdx.x; k64 < hi; k64 += kThreads) {
-        const int k = (int)k64;
-        const double sl = cutpool_chain(pv, vx.x, vx.nr_normal, k);
-        s_all[k] = sl;
-        double key = sl;
-        if (by_efficacy) { const double nk = cv.norm[k]; key = sl / (nk == 0.0 ? 1.0 : nk); }
-        if (pv.active[k] && sl < -tol && key < best) { best = key; best_k = k; }     // (ascending k: the first of equal keys stays)
-    }
-    if (!part_d) return;
-    block_min_key<kThreads>(best, best_k);
-    if (threadIdx.x == 0) {
-        part_d[blockIdx.x] = best_k == INT32_MAX ? INFINITY : best;
-        part_k[blockIdx.x] = best_k == INT32_MAX ? -1 : best_k;
-    }
-}
-
-// k_pool_winners with the slack gathered in place of the key: one workgroup, the winners of the shares compacted in ascending share
-// order, out_s[i] = s_all[out_k[i]].
-__global__ __launch_bounds__(kThreads) void k_cutpool_winners(int segments, int chunks, const int32_t* __restrict__ part_k,
-                                                              const double* __restrict__ s_all, int count, int32_t* out_k, double* out_s,
-                                                              int32_t* found) {
-    __shared__ int s_scan[kThreads / 64];
-    int placed = 0;
-    for (int base = 0; base < segments; base += kThreads) {
-        const int seg = base + threadIdx.x;
-        int best_k = seg < segments ? part_k[(int64_t)seg * chunks] : -1;
-        if (best_k >= count) best_k = -1;
-        int total;
-        const int at = placed + block_flag_scan(best_k >= 0 ? 1 : 0, s_scan, &total);
-        if (best_k >= 0) { out_k[at] = best_k; out_s[at] = s_all[best_k]; }
-        placed += total;
-    }
-    if (threadIdx.x == 0) *found = placed;
-}
-
-// Entries 256 at a time, as k_pool_entries: with C = ceil(longest / 256), workgroup b has the entries (b % C) * 256 + threadIdx.x
-// of the chosen cut b / C.  SCATTER == false: the column is marked.  true: the value goes to its place in the cut's row of A, and
-// into coef where the column is in the union list.
+// One entry of a chosen cut per thread (pool_entry).  SCATTER == false: the column is marked.  true: the value goes to its place in
+// the cut's row of A, and into coef where the column is in the union list.
 template <bool SCATTER>
 __global__ __launch_bounds__(kThreads) void k_cutpool_entries(PoolView pv, CutPoolAdd ca) {
-    const int per_cut = (ca.longest + kThreads - 1) / kThreads;
-    const int x = blockIdx.x / per_cut, k = ca.ids[x], s = k / kPoolSlice;
-    const int64_t base = pv.slice_ptr[s], width = (pv.slice_ptr[s + 1] - base) / kPoolSlice;
-    const int64_t e = (int64_t)(blockIdx.x % per_cut) * kThreads + threadIdx.x;
-    if (e >= width) return;
-    const int64_t at = base + e * kPoolSlice + k % kPoolSlice;
-    const int j = pv.row[at];
-    if (j < 0 || j >= ca.nr_normal) return;
+    const PoolEntry en = pool_entry(pv, ca.ids, ca.longest, ca.nr_normal);
+    const int x = en.x, j = en.i;
+    if (j < 0) return;
     if (!SCATTER) { ca.mark[j] = 1; return; }
-    const double v = pv.val[at];
+    const double v = *en.v;
     ca.A[(int64_t)j * ca.ld_a + ca.a_row0 + x] = v;
     const int place = ca.mark[j] - 2;
     if (place >= 0 && place < ca.room) ca.coef[(int64_t)place * ca.count + x] = v;
@@ -2521,7 +2500,7 @@ __global__ __launch_bounds__(kThreads) void k_cutpool_chosen(PoolView pv, CutPoo
         }
     }
     if (threadIdx.x == 0) {
-        ca.b_new[x] = pv.cost[k] - acc;
+        ca.b_new[x] = pv.scalar[k] - acc;
         pv.active[k] = 0;
     }
 }
@@ -2533,21 +2512,9 @@ void launch_cutpool_x(const Vertex& vx, hipStream_t s) {
 
 void launch_cutpool_separate(const CutPoolView& cv, const Vertex& vx, int32_t segments, double tol, int32_t by_efficacy, double* s_all,
                              double* part_d, int32_t* part_k, int32_t* out_k, double* out_s, int32_t* found, hipStream_t s) {
-    const int32_t count = cv.pv.count;
-    if (count > 0) launch_cutpool_x(vx, s);
-    if (segments < 1) {
-        if (count > 0)
-            hipLaunchKernelGGL(k_cutpool_separate, dim3(cdiv(count, kPoolChunk)), dim3(kThreads), 0, s, cv, vx, (int)count, cdiv(count, kPoolChunk),
-                               tol, (int)by_efficacy, s_all, (double*)nullptr, (int32_t*)nullptr);
-        return;
-    }
-    const int chunks = pool_segment_chunks(count, segments);
-    if (count > 0)
-        hipLaunchKernelGGL(k_cutpool_separate, dim3((unsigned)((int64_t)segments * chunks)), dim3(kThreads), 0, s, cv, vx,
-                           (int)pool_segment_size(count, segments), chunks, tol, (int)by_efficacy, s_all, part_d, part_k);
-    if (count > 0 && chunks > 1) hipLaunchKernelGGL(k_pool_fold, dim3(segments), dim3(kThreads), 0, s, chunks, part_d, part_k);
-    hipLaunchKernelGGL(k_cutpool_winners, dim3(1), dim3(kThreads), 0, s, count > 0 ? (int)segments : 0, chunks, part_k, s_all, (int)count, out_k,
-                       out_s, found);
+    if (cv.pv.count > 0) launch_cutpool_x(vx, s);
+    launch_pool_sweep(Slack{cv.pv, cv.norm, vx.x, vx.nr_normal, (int)by_efficacy}, segments, tol, s_all, part_d, part_k, s_all, out_k, out_s,
+                      found, s);
 }
 
 void launch_cutpool_add_operands(const CutPoolView& cv, const CutPoolAdd& ca, hipStream_t s) {

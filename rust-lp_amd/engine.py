@@ -1034,24 +1034,49 @@ class Trial:
         return False
 
 
-class ColumnPool:
-    """A column pool of a ``Tableau`` (``Tableau.pool``): candidate columns resident on the device, priced and added in place.
-    Freed by ``close()``, or with the tableau."""
+class _DevicePool:
+    """What ``ColumnPool`` and ``CutPool`` share: the handle, the open/closed checks and the calls that differ in their C name alone
+    (``_PREFIX`` + ``_destroy`` / ``_add`` / ``_set_active`` / ``_stats``); the two classes keep ``add``, ``set_active`` and ``stats``
+    as one-line methods with their own docstrings.  ``_NOUN`` is the pool in the words of its errors."""
+    _PREFIX = _NOUN = ""
 
     def __init__(self, tableau: Tableau, handle, count: int):
         self._t, self._p, self.count = tableau, handle, int(count)
 
     def _call(self, name, *args):
         if self._p is None:
-            raise RelpError("the pool is closed")
+            raise RelpError(f"the {self._NOUN} is closed")
         if not self._t._h:
-            raise RelpError("the pool's tableau is closed")
+            raise RelpError(f"the {self._NOUN}'s tableau is closed")
         self._t._ck(getattr(self._t._lib, name)(self._t._h, self._p, *args))
+
+    def _call_ids(self, name, ids, *args):
+        i = np.ascontiguousarray(np.atleast_1d(ids), dtype=np.int32)
+        if i.ndim != 1:
+            raise ValueError("ids must be one-dimensional")
+        self._call(name, i.ctypes.data, i.shape[0], *args)
 
     def close(self) -> None:
         if self._p is not None and self._t._h:
-            self._t._lib.relp_pool_destroy(self._t._h, self._p)
+            getattr(self._t._lib, self._PREFIX + "_destroy")(self._t._h, self._p)
         self._p = None
+
+    def _add(self, ids) -> None:
+        self._call_ids(self._PREFIX + "_add", ids)
+
+    def _set_active(self, ids, flag: bool) -> None:
+        self._call_ids(self._PREFIX + "_set_active", ids, 1 if flag else 0)
+
+    def _stats(self) -> Tuple[int, int, int, int]:
+        out = (C.c_int64 * 4)()
+        self._call(self._PREFIX + "_stats", out)
+        return tuple(int(x) for x in out)
+
+
+class ColumnPool(_DevicePool):
+    """A column pool of a ``Tableau`` (``Tableau.pool``): candidate columns resident on the device, priced and added in place.
+    Freed by ``close()``, or with the tableau."""
+    _PREFIX, _NOUN = "relp_pool", "pool"
 
     def reduced_costs(self) -> np.ndarray:
         """``d_k = c_k + sum_i (-pi)_i a_k[i]`` of every pool column, active or not, with the bits ``add_columns`` would give the
@@ -1072,23 +1097,15 @@ class ColumnPool:
     def add(self, ids) -> None:
         """The pool columns ``ids`` join the tableau as ``add_columns`` would add them, in that order (relp_pool_add): column k of
         the list is column ``nr_columns() + k`` (read before the call); their activity flags are cleared."""
-        i = np.ascontiguousarray(np.atleast_1d(ids), dtype=np.int32)
-        if i.ndim != 1:
-            raise ValueError("ids must be one-dimensional")
-        self._call("relp_pool_add", i.ctypes.data, i.shape[0])
+        self._add(ids)
 
     def set_active(self, ids, flag: bool) -> None:
         """The activity flag of the pool columns ``ids`` (relp_pool_set_active): an inactive column is priced but never wins."""
-        i = np.ascontiguousarray(np.atleast_1d(ids), dtype=np.int32)
-        if i.ndim != 1:
-            raise ValueError("ids must be one-dimensional")
-        self._call("relp_pool_set_active", i.ctypes.data, i.shape[0], 1 if flag else 0)
+        self._set_active(ids, flag)
 
     def stats(self) -> Tuple[int, int, int, int]:
         """(pool columns, nonzeros held, entries stored on the device with padding, price calls so far); relp_pool_stats."""
-        out = (C.c_int64 * 4)()
-        self._call("relp_pool_stats", out)
-        return tuple(int(x) for x in out)
+        return self._stats()
 
 
 def column_generation(tableau: Tableau, pool: ColumnPool, segments: int = 1, tol: float = 1e-7, max_rounds: int = 100,
@@ -1111,24 +1128,10 @@ def column_generation(tableau: Tableau, pool: ColumnPool, segments: int = 1, tol
         added += int(ids.shape[0])
 
 
-class CutPool:
+class CutPool(_DevicePool):
     """A cut pool of a ``Tableau`` (``Tableau.cut_pool``): candidate cuts resident on the device, separated and added in place.
     Freed by ``close()``, or with the tableau."""
-
-    def __init__(self, tableau: Tableau, handle, count: int):
-        self._t, self._p, self.count = tableau, handle, int(count)
-
-    def _call(self, name, *args):
-        if self._p is None:
-            raise RelpError("the cut pool is closed")
-        if not self._t._h:
-            raise RelpError("the cut pool's tableau is closed")
-        self._t._ck(getattr(self._t._lib, name)(self._t._h, self._p, *args))
-
-    def close(self) -> None:
-        if self._p is not None and self._t._h:
-            self._t._lib.relp_cutpool_destroy(self._t._h, self._p)
-        self._p = None
+    _PREFIX, _NOUN = "relp_cutpool", "cut pool"
 
     def slacks(self) -> np.ndarray:
         """``s_k = rhs_k - g_k' x`` of every pool cut, active or not, at the current vertex (relp_cutpool_slacks): one fma chain
@@ -1152,23 +1155,15 @@ class CutPool:
         """The pool cuts ``ids`` join the tableau as ``add_cuts`` would add them, in that order (relp_cutpool_add): cut k of the
         list is row ``nr_rows() + k`` (read before the call); their activity flags are cleared, and stay cleared when a trial
         that added them is rolled back."""
-        i = np.ascontiguousarray(np.atleast_1d(ids), dtype=np.int32)
-        if i.ndim != 1:
-            raise ValueError("ids must be one-dimensional")
-        self._call("relp_cutpool_add", i.ctypes.data, i.shape[0])
+        self._add(ids)
 
     def set_active(self, ids, flag: bool) -> None:
         """The activity flag of the pool cuts ``ids`` (relp_cutpool_set_active): an inactive cut has a slack but never wins."""
-        i = np.ascontiguousarray(np.atleast_1d(ids), dtype=np.int32)
-        if i.ndim != 1:
-            raise ValueError("ids must be one-dimensional")
-        self._call("relp_cutpool_set_active", i.ctypes.data, i.shape[0], 1 if flag else 0)
+        self._set_active(ids, flag)
 
     def stats(self) -> Tuple[int, int, int, int]:
         """(pool cuts, nonzeros held, entries stored on the device with padding, separate calls so far); relp_cutpool_stats."""
-        out = (C.c_int64 * 4)()
-        self._call("relp_cutpool_stats", out)
-        return tuple(int(x) for x in out)
+        return self._stats()
 
 
 def row_generation(tableau: Tableau, pool: CutPool, tol: float = 1e-7, per_round: int = 1, max_rounds: int = 100,

@@ -35,9 +35,9 @@ struct Csr {
 static void check_image(const CutPoolImage& cim, int32_t nr_normal) {
     const PoolImage& im = cim.ell;
     const int32_t slices = (im.count + kPoolSlice - 1) / kPoolSlice;
-    CHECK(cim.count() == im.count && im.slices() == slices && (int32_t)cim.norm.size() == im.count && (int32_t)cim.rhs().size() == im.count);
-    CHECK((int32_t)cim.row_ptr().size() == im.count + 1 && cim.row_ptr()[0] == 0 && im.slice_ptr[0] == 0);
-    CHECK((int64_t)im.ell_row.size() == im.stored() && (int64_t)im.ell_val.size() == im.stored());
+    CHECK(cim.ell.count == im.count && im.slices() == slices && (int32_t)cim.norm.size() == im.count && (int32_t)im.scalar.size() == im.count);
+    CHECK((int32_t)im.ptr.size() == im.count + 1 && im.ptr[0] == 0 && im.slice_ptr[0] == 0);
+    CHECK((int64_t)im.ell_idx.size() == im.stored() && (int64_t)im.ell_val.size() == im.stored());
     int64_t held = 0;
     for (int32_t s = 0; s < slices; ++s) {
         int32_t longest = 0;
@@ -49,12 +49,12 @@ static void check_image(const CutPoolImage& cim, int32_t nr_normal) {
             for (int32_t e = 0; e < im.width(s); ++e) {
                 const int64_t at = im.slice_ptr[s] + (int64_t)e * kPoolSlice + lane;
                 if (e < len) {
-                    CHECK(im.ell_row[at] == cim.col_idx()[cim.row_ptr()[k] + e] && im.ell_val[at] == cim.values()[cim.row_ptr()[k] + e]);
-                    CHECK(im.ell_val[at] != 0.0 && im.ell_row[at] >= 0 && im.ell_row[at] < nr_normal);
-                    if (e > 0) CHECK(im.ell_row[at] > im.ell_row[at - kPoolSlice]);
+                    CHECK(im.ell_idx[at] == im.idx[im.ptr[k] + e] && im.ell_val[at] == im.values[im.ptr[k] + e]);
+                    CHECK(im.ell_val[at] != 0.0 && im.ell_idx[at] >= 0 && im.ell_idx[at] < nr_normal);
+                    if (e > 0) CHECK(im.ell_idx[at] > im.ell_idx[at - kPoolSlice]);
                     ++held;
                 } else {
-                    CHECK(im.ell_row[at] == -1 && im.ell_val[at] == 0.0 && !std::signbit(im.ell_val[at]));
+                    CHECK(im.ell_idx[at] == -1 && im.ell_val[at] == 0.0 && !std::signbit(im.ell_val[at]));
                 }
             }
         }
@@ -62,7 +62,7 @@ static void check_image(const CutPoolImage& cim, int32_t nr_normal) {
     CHECK(held == im.nonzeros());
     for (int32_t k = 0; k < im.count; ++k) {
         double acc = 0.0;
-        for (int64_t e = cim.row_ptr()[k]; e < cim.row_ptr()[k + 1]; ++e) acc = std::fma(cim.values()[e], cim.values()[e], acc);
+        for (int64_t e = im.ptr[k]; e < im.ptr[k + 1]; ++e) acc = std::fma(im.values[e], im.values[e], acc);
         CHECK(cim.norm[k] == std::sqrt(acc));
     }
 }
@@ -71,9 +71,9 @@ static void test_packer_and_norms() {
     {   // an empty pool
         Csr c;
         const CutPoolImage im = c.pack(5);
-        CHECK(im.count() == 0 && im.ell.slices() == 0 && im.ell.stored() == 0 && im.ell.nonzeros() == 0 && im.norm.empty());
+        CHECK(im.ell.count == 0 && im.ell.slices() == 0 && im.ell.stored() == 0 && im.ell.nonzeros() == 0 && im.norm.empty());
         check_image(im, 5);
-        CHECK(cutpool_pack(0, nullptr, nullptr, nullptr, nullptr, 5).count() == 0);
+        CHECK(cutpool_pack(0, nullptr, nullptr, nullptr, nullptr, 5).ell.count == 0);
     }
     {   // one cut, the caller's columns descending, an explicit zero and a negative zero dropped; a cut without entries
         Csr c;
@@ -81,11 +81,11 @@ static void test_packer_and_norms() {
         c.cut({}, -2.0);
         c.cut({{2, 0.0}}, 1.0);
         const CutPoolImage im = c.pack(7);
-        CHECK(im.count() == 3 && im.ell.slices() == 1 && im.ell.width(0) == 3 && im.ell.stored() == 3 * kPoolSlice && im.ell.nonzeros() == 3);
-        CHECK(im.col_idx() == (std::vector<int32_t>{0, 3, 6}) && im.values() == (std::vector<double>{12.0, -4.0, 3.0}));
-        CHECK(im.rhs() == (std::vector<double>{7.0, -2.0, 1.0}));
+        CHECK(im.ell.count == 3 && im.ell.slices() == 1 && im.ell.width(0) == 3 && im.ell.stored() == 3 * kPoolSlice && im.ell.nonzeros() == 3);
+        CHECK(im.ell.idx == (std::vector<int32_t>{0, 3, 6}) && im.ell.values == (std::vector<double>{12.0, -4.0, 3.0}));
+        CHECK(im.ell.scalar == (std::vector<double>{7.0, -2.0, 1.0}));
         CHECK(im.norm[0] == 13.0 && im.norm[1] == 0.0 && !std::signbit(im.norm[1]) && im.norm[2] == 0.0);
-        CHECK(im.ell.ell_row[0] == 0 && im.ell.ell_row[kPoolSlice] == 3 && im.ell.ell_row[2 * kPoolSlice] == 6 && im.ell.ell_row[1] == -1);
+        CHECK(im.ell.ell_idx[0] == 0 && im.ell.ell_idx[kPoolSlice] == 3 && im.ell.ell_idx[2 * kPoolSlice] == 6 && im.ell.ell_idx[1] == -1);
         check_image(im, 7);
     }
     {   // the norm is one fma chain in ascending column order, not a sum of rounded squares
@@ -120,15 +120,15 @@ static void test_packer_and_norms() {
         check_image(im, 320);
         // the chosen cuts of an add: ids in any order, the columns they touch, the longest
         const int32_t ids[3] = {129, 17, 0};
-        const CutPoolChoice ch = cutpool_choose(im, ids, 3, 320);
-        CHECK(ch.row_ptr == (std::vector<int64_t>{0, 1, 301, 302}) && ch.longest == 300);
-        CHECK(ch.rhs == (std::vector<double>{130.0, 18.0, 1.0}));
-        CHECK(ch.col_idx[0] == 129 && ch.col_idx[1] == 10 && ch.col_idx[300] == 309 && ch.col_idx[301] == 0);
+        const PoolChoice ch = pool_choose(im.ell, ids, 3);
+        CHECK(ch.ptr == (std::vector<int64_t>{0, 1, 301, 302}) && ch.longest == 300);
+        CHECK(ch.scalar == (std::vector<double>{130.0, 18.0, 1.0}));
+        CHECK(ch.idx[0] == 129 && ch.idx[1] == 10 && ch.idx[300] == 309 && ch.idx[301] == 0);
         CHECK(ch.touched == 301);                       // columns 10 .. 309 (column 129 is among them) and column 0
         const int32_t one[1] = {5};
-        const CutPoolChoice c1 = cutpool_choose(im, one, 1, 320);
+        const PoolChoice c1 = pool_choose(im.ell, one, 1);
         CHECK(c1.touched == 3 && c1.longest == 3 && c1.values == (std::vector<double>{0.5, 1.0, 1.5}));
-        CHECK(cutpool_choose(im, nullptr, 0, 320).touched == 0);
+        CHECK(pool_choose(im.ell, nullptr, 0).touched == 0);
     }
 }
 
@@ -149,28 +149,28 @@ static void test_segments_key_and_checks() {
     // the argument checks of relp_cutpool_separate
     int dummy = 0;
     const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
-    CHECK(cutpool_check_separate_args(10, 1, 0.0, 0, &dummy, &dummy, &dummy) == nullptr);
-    CHECK(cutpool_check_separate_args(10, 10, 1e-7, 1, &dummy, &dummy, &dummy) == nullptr);
-    CHECK(cutpool_check_separate_args(10, 0, 0.0, 0, &dummy, &dummy, &dummy) != nullptr);
-    CHECK(cutpool_check_separate_args(10, 11, 0.0, 0, &dummy, &dummy, &dummy) != nullptr);
-    CHECK(cutpool_check_separate_args(10, -1, 0.0, 0, &dummy, &dummy, &dummy) != nullptr);
-    CHECK(cutpool_check_separate_args(10, 1, -1e-9, 0, &dummy, &dummy, &dummy) != nullptr);
-    CHECK(cutpool_check_separate_args(10, 1, inf, 0, &dummy, &dummy, &dummy) != nullptr);
-    CHECK(cutpool_check_separate_args(10, 1, nan, 0, &dummy, &dummy, &dummy) != nullptr);
-    CHECK(std::string(cutpool_check_separate_args(10, 1, 0.0, 2, &dummy, &dummy, &dummy)).find("by_efficacy") != std::string::npos);
-    CHECK(cutpool_check_separate_args(10, 1, 0.0, -1, &dummy, &dummy, &dummy) != nullptr);
-    CHECK(cutpool_check_separate_args(10, 1, 0.0, 0, nullptr, &dummy, &dummy) != nullptr);
-    CHECK(cutpool_check_separate_args(10, 1, 0.0, 0, &dummy, nullptr, &dummy) != nullptr);
-    CHECK(cutpool_check_separate_args(10, 1, 0.0, 0, &dummy, &dummy, nullptr) != nullptr);
-    CHECK(cutpool_check_separate_args(0, 3, 0.0, 0, &dummy, &dummy, &dummy) == nullptr);      // an empty pool: any segments >= 1
-    CHECK(cutpool_check_separate_args(0, 0, 0.0, 0, &dummy, &dummy, &dummy) != nullptr);
+    CHECK(cutpool_check_separate_args(10, 1, 0.0, 0, &dummy, &dummy, &dummy).empty());
+    CHECK(cutpool_check_separate_args(10, 10, 1e-7, 1, &dummy, &dummy, &dummy).empty());
+    CHECK(!cutpool_check_separate_args(10, 0, 0.0, 0, &dummy, &dummy, &dummy).empty());
+    CHECK(!cutpool_check_separate_args(10, 11, 0.0, 0, &dummy, &dummy, &dummy).empty());
+    CHECK(!cutpool_check_separate_args(10, -1, 0.0, 0, &dummy, &dummy, &dummy).empty());
+    CHECK(!cutpool_check_separate_args(10, 1, -1e-9, 0, &dummy, &dummy, &dummy).empty());
+    CHECK(!cutpool_check_separate_args(10, 1, inf, 0, &dummy, &dummy, &dummy).empty());
+    CHECK(!cutpool_check_separate_args(10, 1, nan, 0, &dummy, &dummy, &dummy).empty());
+    CHECK(cutpool_check_separate_args(10, 1, 0.0, 2, &dummy, &dummy, &dummy).find("by_efficacy") != std::string::npos);
+    CHECK(!cutpool_check_separate_args(10, 1, 0.0, -1, &dummy, &dummy, &dummy).empty());
+    CHECK(!cutpool_check_separate_args(10, 1, 0.0, 0, nullptr, &dummy, &dummy).empty());
+    CHECK(!cutpool_check_separate_args(10, 1, 0.0, 0, &dummy, nullptr, &dummy).empty());
+    CHECK(!cutpool_check_separate_args(10, 1, 0.0, 0, &dummy, &dummy, nullptr).empty());
+    CHECK(cutpool_check_separate_args(0, 3, 0.0, 0, &dummy, &dummy, &dummy).empty());      // an empty pool: any segments >= 1
+    CHECK(!cutpool_check_separate_args(0, 0, 0.0, 0, &dummy, &dummy, &dummy).empty());
     // the lists
     const int32_t fine[3] = {4, 0, 2}, twice[3] = {4, 0, 4}, outside[2] = {1, 5}, negative[1] = {-1};
-    CHECK(cutpool_check_ids(fine, 3, 5) == nullptr && cutpool_check_ids(nullptr, 0, 5) == nullptr && cutpool_check_ids(fine, 0, 0) == nullptr);
-    CHECK(std::string(cutpool_check_ids(twice, 3, 5)).find("twice") != std::string::npos);
-    CHECK(std::string(cutpool_check_ids(outside, 2, 5)).find("range") != std::string::npos);
-    CHECK(cutpool_check_ids(negative, 1, 5) != nullptr && cutpool_check_ids(nullptr, 2, 5) != nullptr && cutpool_check_ids(fine, -1, 5) != nullptr);
-    CHECK(cutpool_check_ids(fine, 3, 4) != nullptr);
+    CHECK(pool_check_ids(kCutPoolWords, fine, 3, 5).empty() && pool_check_ids(kCutPoolWords, nullptr, 0, 5).empty() && pool_check_ids(kCutPoolWords, fine, 0, 0).empty());
+    CHECK(pool_check_ids(kCutPoolWords, twice, 3, 5).find("twice") != std::string::npos);
+    CHECK(pool_check_ids(kCutPoolWords, outside, 2, 5).find("range") != std::string::npos);
+    CHECK(!pool_check_ids(kCutPoolWords, negative, 1, 5).empty() && !pool_check_ids(kCutPoolWords, nullptr, 2, 5).empty() && !pool_check_ids(kCutPoolWords, fine, -1, 5).empty());
+    CHECK(!pool_check_ids(kCutPoolWords, fine, 3, 4).empty());
 }
 
 int main() {

@@ -35,8 +35,8 @@ struct Csc {
 static void check_image(const PoolImage& im) {
     const int32_t slices = (im.count + kPoolSlice - 1) / kPoolSlice;
     CHECK(im.slices() == slices);
-    CHECK((int32_t)im.col_ptr.size() == im.count + 1 && im.col_ptr[0] == 0);
-    CHECK(im.slice_ptr[0] == 0 && (int64_t)im.ell_row.size() == im.stored() && (int64_t)im.ell_val.size() == im.stored());
+    CHECK((int32_t)im.ptr.size() == im.count + 1 && im.ptr[0] == 0);
+    CHECK(im.slice_ptr[0] == 0 && (int64_t)im.ell_idx.size() == im.stored() && (int64_t)im.ell_val.size() == im.stored());
     int64_t held = 0;
     for (int32_t s = 0; s < slices; ++s) {
         int32_t longest = 0;
@@ -50,12 +50,12 @@ static void check_image(const PoolImage& im) {
                 const int64_t at = im.slice_ptr[s] + (int64_t)e * kPoolSlice + lane;
                 if (k < im.count) CHECK(at == im.at(k, e));
                 if (e < len) {
-                    CHECK(im.ell_row[at] == im.row_idx[im.col_ptr[k] + e] && im.ell_val[at] == im.values[im.col_ptr[k] + e]);
-                    CHECK(im.ell_val[at] != 0.0 && im.ell_row[at] >= 0 && im.ell_row[at] < im.rows_at_create);
-                    if (e > 0) CHECK(im.ell_row[at] > im.ell_row[at - kPoolSlice]);
+                    CHECK(im.ell_idx[at] == im.idx[im.ptr[k] + e] && im.ell_val[at] == im.values[im.ptr[k] + e]);
+                    CHECK(im.ell_val[at] != 0.0 && im.ell_idx[at] >= 0 && im.ell_idx[at] < im.bound);
+                    if (e > 0) CHECK(im.ell_idx[at] > im.ell_idx[at - kPoolSlice]);
                     ++held;
                 } else {
-                    CHECK(im.ell_row[at] == -1 && im.ell_val[at] == 0.0 && !std::signbit(im.ell_val[at]));
+                    CHECK(im.ell_idx[at] == -1 && im.ell_val[at] == 0.0 && !std::signbit(im.ell_val[at]));
                 }
             }
         }
@@ -77,9 +77,9 @@ static void test_packer() {
         c.column({{6, 2.5}, {4, 0.0}, {3, -1.0}, {1, -0.0}, {0, 4.0}}, 7.0);
         const PoolImage im = c.pack(7);
         CHECK(im.count == 1 && im.slices() == 1 && im.width(0) == 3 && im.stored() == 3 * kPoolSlice && im.nonzeros() == 3);
-        CHECK(im.row_idx == (std::vector<int32_t>{0, 3, 6}) && im.values == (std::vector<double>{4.0, -1.0, 2.5}));
-        CHECK(im.ell_row[0] == 0 && im.ell_row[kPoolSlice] == 3 && im.ell_row[2 * kPoolSlice] == 6 && im.ell_row[1] == -1);
-        CHECK(im.cost == std::vector<double>{7.0} && im.rows_at_create == 7);
+        CHECK(im.idx == (std::vector<int32_t>{0, 3, 6}) && im.values == (std::vector<double>{4.0, -1.0, 2.5}));
+        CHECK(im.ell_idx[0] == 0 && im.ell_idx[kPoolSlice] == 3 && im.ell_idx[2 * kPoolSlice] == 6 && im.ell_idx[1] == -1);
+        CHECK(im.scalar == std::vector<double>{7.0} && im.bound == 7);
         check_image(im);
     }
     for (int32_t count : {64, 65}) {   // exactly one slice; a second slice of one column
@@ -110,14 +110,14 @@ static void test_packer() {
         check_image(im);
         // the chosen columns of an add: ids in any order, the union of their rows, the longest
         const int32_t ids[3] = {129, 17, 0};
-        const PoolChoice ch = pool_choose(im, ids, 3, 320);
-        CHECK(ch.col_ptr == (std::vector<int64_t>{0, 1, 301, 302}) && ch.longest == 300 && ch.cost.size() == 3);
-        CHECK(ch.row_idx[0] == 129 && ch.row_idx[1] == 10 && ch.row_idx[300] == 309 && ch.row_idx[301] == 0);
-        CHECK(ch.entries == 301);                       // rows 10 .. 309 (row 129 is among them) and row 0
+        const PoolChoice ch = pool_choose(im, ids, 3);
+        CHECK(ch.ptr == (std::vector<int64_t>{0, 1, 301, 302}) && ch.longest == 300 && ch.scalar.size() == 3);
+        CHECK(ch.idx[0] == 129 && ch.idx[1] == 10 && ch.idx[300] == 309 && ch.idx[301] == 0);
+        CHECK(ch.touched == 301);                       // rows 10 .. 309 (row 129 is among them) and row 0
         const int32_t one[1] = {5};
-        const PoolChoice c1 = pool_choose(im, one, 1, 320);
-        CHECK(c1.entries == 3 && c1.longest == 3 && c1.values == (std::vector<double>{0.5, 1.0, 1.5}));
-        CHECK(pool_choose(im, nullptr, 0, 320).entries == 0);
+        const PoolChoice c1 = pool_choose(im, one, 1);
+        CHECK(c1.touched == 3 && c1.longest == 3 && c1.values == (std::vector<double>{0.5, 1.0, 1.5}));
+        CHECK(pool_choose(im, nullptr, 0).touched == 0);
     }
 }
 
@@ -146,28 +146,28 @@ static void test_segments() {
     // the argument checks of relp_pool_price
     int dummy = 0;
     const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
-    CHECK(pool_check_price_args(10, 1, 0.0, &dummy, &dummy, &dummy) == nullptr);
-    CHECK(pool_check_price_args(10, 10, 1e-7, &dummy, &dummy, &dummy) == nullptr);
-    CHECK(pool_check_price_args(10, 0, 0.0, &dummy, &dummy, &dummy) != nullptr);
-    CHECK(pool_check_price_args(10, 11, 0.0, &dummy, &dummy, &dummy) != nullptr);
-    CHECK(pool_check_price_args(10, -1, 0.0, &dummy, &dummy, &dummy) != nullptr);
-    CHECK(pool_check_price_args(10, 1, -1e-9, &dummy, &dummy, &dummy) != nullptr);
-    CHECK(pool_check_price_args(10, 1, inf, &dummy, &dummy, &dummy) != nullptr);
-    CHECK(pool_check_price_args(10, 1, nan, &dummy, &dummy, &dummy) != nullptr);
-    CHECK(pool_check_price_args(10, 1, 0.0, nullptr, &dummy, &dummy) != nullptr);
-    CHECK(pool_check_price_args(10, 1, 0.0, &dummy, nullptr, &dummy) != nullptr);
-    CHECK(pool_check_price_args(10, 1, 0.0, &dummy, &dummy, nullptr) != nullptr);
-    CHECK(pool_check_price_args(0, 3, 0.0, &dummy, &dummy, &dummy) == nullptr);      // an empty pool: any segments >= 1
-    CHECK(pool_check_price_args(0, 0, 0.0, &dummy, &dummy, &dummy) != nullptr);
+    CHECK(pool_check_sweep_args(kColumnPoolWords, 10, 1, 0.0, &dummy, &dummy, &dummy).empty());
+    CHECK(pool_check_sweep_args(kColumnPoolWords, 10, 10, 1e-7, &dummy, &dummy, &dummy).empty());
+    CHECK(!pool_check_sweep_args(kColumnPoolWords, 10, 0, 0.0, &dummy, &dummy, &dummy).empty());
+    CHECK(!pool_check_sweep_args(kColumnPoolWords, 10, 11, 0.0, &dummy, &dummy, &dummy).empty());
+    CHECK(!pool_check_sweep_args(kColumnPoolWords, 10, -1, 0.0, &dummy, &dummy, &dummy).empty());
+    CHECK(!pool_check_sweep_args(kColumnPoolWords, 10, 1, -1e-9, &dummy, &dummy, &dummy).empty());
+    CHECK(!pool_check_sweep_args(kColumnPoolWords, 10, 1, inf, &dummy, &dummy, &dummy).empty());
+    CHECK(!pool_check_sweep_args(kColumnPoolWords, 10, 1, nan, &dummy, &dummy, &dummy).empty());
+    CHECK(!pool_check_sweep_args(kColumnPoolWords, 10, 1, 0.0, nullptr, &dummy, &dummy).empty());
+    CHECK(!pool_check_sweep_args(kColumnPoolWords, 10, 1, 0.0, &dummy, nullptr, &dummy).empty());
+    CHECK(!pool_check_sweep_args(kColumnPoolWords, 10, 1, 0.0, &dummy, &dummy, nullptr).empty());
+    CHECK(pool_check_sweep_args(kColumnPoolWords, 0, 3, 0.0, &dummy, &dummy, &dummy).empty());      // an empty pool: any segments >= 1
+    CHECK(!pool_check_sweep_args(kColumnPoolWords, 0, 0, 0.0, &dummy, &dummy, &dummy).empty());
 }
 
 static void test_lists_and_stale_rule() {
     const int32_t fine[3] = {4, 0, 2}, twice[3] = {4, 0, 4}, outside[2] = {1, 5}, negative[1] = {-1};
-    CHECK(pool_check_ids(fine, 3, 5) == nullptr && pool_check_ids(nullptr, 0, 5) == nullptr && pool_check_ids(fine, 0, 0) == nullptr);
-    CHECK(std::string(pool_check_ids(twice, 3, 5)).find("twice") != std::string::npos);
-    CHECK(std::string(pool_check_ids(outside, 2, 5)).find("range") != std::string::npos);
-    CHECK(pool_check_ids(negative, 1, 5) != nullptr && pool_check_ids(nullptr, 2, 5) != nullptr && pool_check_ids(fine, -1, 5) != nullptr);
-    CHECK(pool_check_ids(fine, 3, 4) != nullptr);
+    CHECK(pool_check_ids(kColumnPoolWords, fine, 3, 5).empty() && pool_check_ids(kColumnPoolWords, nullptr, 0, 5).empty() && pool_check_ids(kColumnPoolWords, fine, 0, 0).empty());
+    CHECK(pool_check_ids(kColumnPoolWords, twice, 3, 5).find("twice") != std::string::npos);
+    CHECK(pool_check_ids(kColumnPoolWords, outside, 2, 5).find("range") != std::string::npos);
+    CHECK(!pool_check_ids(kColumnPoolWords, negative, 1, 5).empty() && !pool_check_ids(kColumnPoolWords, nullptr, 2, 5).empty() && !pool_check_ids(kColumnPoolWords, fine, -1, 5).empty());
+    CHECK(!pool_check_ids(kColumnPoolWords, fine, 3, 4).empty());
     // a pool created over 30 rows; cuts came later as rows 30, 31, 32
     const int32_t later[2] = {32, 30}, mixed[2] = {31, 29}, first[1] = {0};
     CHECK(!pool_stale_after_removal(30, later, 2));

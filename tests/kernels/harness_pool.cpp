@@ -6,36 +6,11 @@
 // not write).  This file only checks that nothing the launch may touch lies outside an image -- a refused call (negative code)
 // launches nothing -- uploads, launches, synchronises and downloads.  A HIP error is returned as 1000 + code and is sticky: nothing
 // is launched any more in this process.
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-#include <vector>
-
-#include "relp_kernels.h"
+#include "harness_pool_common.hpp"
 
 using namespace relp;
 
 namespace {
-
-constexpr int kRefusedShape = -1, kRefusedIndex = -2, kRefusedLength = -4;
-constexpr int kHipErrorBase = 1000;
-int g_sticky = 0;
-
-#define REFUSE_IF(cond, code) do { if (cond) return (code); } while (0)
-#define HIP_OK(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) { g_sticky = kHipErrorBase + (int)e_; return g_sticky; } } while (0)
-
-// a device copy of a host image; freed on every way out
-template <class T>
-struct Image {
-    T* d = nullptr; T* h; int64_t n;
-    Image(T* host, int64_t len) : h(host), n(len) {}
-    ~Image() { if (d) (void)hipFree(d); }
-    hipError_t up() {
-        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), sizeof(T) * (size_t)(n > 0 ? n : 1));
-        return (e != hipSuccess || n == 0) ? e : hipMemcpy(d, h, sizeof(T) * (size_t)n, hipMemcpyHostToDevice);
-    }
-    hipError_t back() { return n == 0 ? hipSuccess : hipMemcpy(h, d, sizeof(T) * (size_t)n, hipMemcpyDeviceToHost); }
-};
 
 // the pool and -pi as images: what both launches read
 struct PoolArgs {
@@ -44,16 +19,9 @@ struct PoolArgs {
     uint8_t* active; int64_t active_len; double* d; int64_t d_len; double* cost_store; int64_t cost_store_len; int32_t* idcol; int64_t idcol_len;
 };
 int check_pool(const PoolArgs& a) {
-    const int64_t cap = 1 << 22;
-    REFUSE_IF(a.count < 0 || a.count > cap || a.m < 1 || a.m > cap || a.n_store < 1 || a.n_store > cap, kRefusedShape);
-    const int64_t slices = (a.count + kPoolSlice - 1) / kPoolSlice;
-    REFUSE_IF(a.slice_ptr_len != slices + 1 || a.cost_len != a.count || a.active_len != a.count, kRefusedLength);
+    REFUSE_IF(a.count < 0 || a.count > kPoolCap || a.m < 1 || a.m > kPoolCap || a.n_store < 1 || a.n_store > kPoolCap, kRefusedShape);
     REFUSE_IF(a.d_len != a.n_store || a.cost_store_len != a.n_store || a.idcol_len != a.m, kRefusedLength);
-    REFUSE_IF(a.slice_ptr[0] != 0, kRefusedIndex);
-    for (int64_t s = 0; s < slices; ++s)
-        REFUSE_IF(a.slice_ptr[s + 1] < a.slice_ptr[s] || (a.slice_ptr[s + 1] - a.slice_ptr[s]) % kPoolSlice != 0, kRefusedIndex);
-    REFUSE_IF(a.row_len != a.slice_ptr[slices] || a.val_len != a.row_len || a.row_len > 16 * cap, kRefusedLength);
-    for (int64_t x = 0; x < a.row_len; ++x) REFUSE_IF(a.row[x] < -1 || a.row[x] >= a.m, kRefusedIndex);
+    if (const int rc = check_sliced_ell(a.count, a.m, a.slice_ptr, a.slice_ptr_len, a.row, a.row_len, a.val_len, a.cost_len, a.active_len)) return rc;
     for (int64_t i = 0; i < a.m; ++i) REFUSE_IF(a.idcol[i] < 0 || a.idcol[i] >= a.n_store, kRefusedIndex);
     return 0;
 }

@@ -9,7 +9,7 @@ CSRC := $(ROOT)/rust-lp_amd/csrc
 
 all: librelp_kernel_harness_pool.so
 
-librelp_kernel_harness_pool.so: harness_pool.cpp $(CSRC)/relp_kernels.h $(CSRC)/relp_pool.hpp $(CSRC)/relp_layout.hpp $(ROOT)/rust-lp_amd/librelp_engine.so
+librelp_kernel_harness_pool.so: harness_pool.cpp harness_pool_common.hpp $(CSRC)/relp_kernels.h $(CSRC)/relp_pool.hpp $(CSRC)/relp_layout.hpp $(ROOT)/rust-lp_amd/librelp_engine.so
 	$(HIPCC) --offload-arch=$(ARCH) -O2 -std=c++17 -fPIC -Wall -Wextra -x hip -shared -I$(CSRC) -I$(ROOT)/include $< -o $@ \
 	    -L$(ROOT)/rust-lp_amd -lrelp_engine -Wl,-rpath,'$$ORIGIN/../../rust-lp_amd'
 

@@ -59,6 +59,25 @@ def test_slacks_alone(name):
     check(case.separate(0, 0.0), case.separate_expected(0, 0.0))                    # relp_cutpool_slacks: x and s_all only
 
 
+@pytest.mark.parametrize("by_efficacy", [0, 1])
+@pytest.mark.parametrize("longest", [15, 16, 17, 32])
+def test_a_chain_of_one_load_batch_one_short_one_over_and_two(longest, by_efficacy):
+    """65 cuts over 40 structural columns in three shares: cut 17 has `longest` entries -- one short of a batch of sixteen loads, one
+    batch, one over, two batches -- and its last entry stands on the highest structural column, basic with a non-zero value; the
+    others have 1 to 5."""
+    m, n = 20, 40
+    rng = np.random.default_rng(longest)
+    cuts = khc.random_cuts(rng, n, 65, longest, long_cut=17)
+    cuts[17][-1] = (n - 1, cuts[17][-1][1])
+    basis = khc.random_basis(rng, m, n, 10)
+    if n - 1 not in basis:
+        basis[np.flatnonzero(basis >= n)[0]] = n - 1
+    case = khc.Case(m, n, cuts, seed=longest + 1, basis=basis)
+    assert len(cuts[17]) == longest and max(len(c) for k, c in enumerate(cuts) if k != 17) <= 5
+    assert case.x()[n - 1] != 0.0 and cuts[17][-1][1] != 0.0
+    check(case.separate(3, TOL, by_efficacy), case.separate_expected(3, TOL, by_efficacy))
+
+
 def test_a_cut_without_entries_has_its_rhs_and_padding_adds_nothing():
     rng = np.random.default_rng(3)
     cuts = khc.random_cuts(rng, 30, 70, 5, empty=(0, 7, 64, 69))

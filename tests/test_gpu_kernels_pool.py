@@ -56,6 +56,20 @@ def test_reduced_costs_alone_and_price_without_the_vector(name):
     check(case.price(segments, TOL, write_d=False), case.price_expected(segments, TOL, write_d=False))     # relp_pool_price: no d_all
 
 
+@pytest.mark.parametrize("longest", [15, 16, 17, 32])
+def test_a_chain_of_one_load_batch_one_short_one_over_and_two(longest):
+    """65 columns over 40 rows in three shares: column 17 has `longest` entries -- one short of a batch of sixteen loads, one batch,
+    one over, two batches -- and its last entry stands in the highest row with a non-zero multiplier there; the others have 1 to 5."""
+    m = 40
+    rng = np.random.default_rng(longest)
+    columns = khp.random_columns(rng, m, 65, longest, long_column=17)
+    columns[17][-1] = (m - 1, columns[17][-1][1])
+    case = khp.Case(m, columns, seed=longest + 1)
+    assert len(columns[17]) == longest and max(len(c) for k, c in enumerate(columns) if k != 17) <= 5
+    assert case.mpi[m - 1] != 0.0 and columns[17][-1][1] != 0.0
+    check(case.price(3, TOL), case.price_expected(3, TOL))
+
+
 def test_an_empty_column_prices_at_its_cost_and_padding_adds_nothing():
     rng = np.random.default_rng(3)
     columns = khp.random_columns(rng, 30, 70, 5, empty=(0, 7, 64, 69))
