@@ -9,19 +9,14 @@
 #include <map>
 #include <string>
 
+#include "check.hpp"
+
 namespace {
 struct Call { std::string name; hipStream_t stream; size_t bytes; };
 std::vector<Call> calls;
 std::map<void*, bool> device_live, pinned_live;         // allocation -> not freed yet (freeing anything else is an error)
 int allocations = 0, frees = 0;
 int refuse_malloc = 0;                                  // the next hipMalloc calls fail
-int checks = 0, failed = 0;
-
-#define CHECK(cond)                                                                     \
-    do {                                                                                \
-        ++checks;                                                                       \
-        if (!(cond)) { ++failed; std::printf("%s:%d: CHECK(%s) failed\n", __FILE__, __LINE__, #cond); } \
-    } while (0)
 
 hipStream_t const S1 = reinterpret_cast<hipStream_t>(0x1000), S2 = reinterpret_cast<hipStream_t>(0x2000);
 
@@ -48,7 +43,7 @@ hipError_t hipMalloc(void** p, size_t bytes) {
 }
 hipError_t hipFree(void* p) {
     calls.push_back({"hipFree", nullptr, 0});
-    if (!device_live.count(p) || !device_live[p]) { ++failed; std::printf("hipFree of memory that is not allocated\n"); return hipErrorInvalidValue; }
+    if (!device_live.count(p) || !device_live[p]) { ++g_failed; std::printf("hipFree of memory that is not allocated\n"); return hipErrorInvalidValue; }
     device_live[p] = false; ++frees;
     std::free(p);
     return hipSuccess;
@@ -76,7 +71,7 @@ hipError_t hipHostMalloc(void** p, size_t bytes, unsigned int) {
 }
 hipError_t hipHostFree(void* p) {
     calls.push_back({"hipHostFree", nullptr, 0});
-    if (!pinned_live.count(p) || !pinned_live[p]) { ++failed; std::printf("hipHostFree of memory that is not allocated\n"); return hipErrorInvalidValue; }
+    if (!pinned_live.count(p) || !pinned_live[p]) { ++g_failed; std::printf("hipHostFree of memory that is not allocated\n"); return hipErrorInvalidValue; }
     pinned_live[p] = false; ++frees;
     std::free(p);
     return hipSuccess;
@@ -261,6 +256,5 @@ int main() {
     for (const auto& a : device_live) CHECK(!a.second);
     for (const auto& a : pinned_live) CHECK(!a.second);
     CHECK(allocations > 10 && frees == allocations);
-    std::printf("relp_buffers.hpp: %d checks, %d failed\n", checks, failed);
-    return failed ? 1 : 0;
+    return finish("test_buffers");
 }

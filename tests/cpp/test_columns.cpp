@@ -1,7 +1,7 @@
 // C++ host-side test of columns added in place over include/relp.hpp (no counterpart in the reference, whose provider is immutable):
 // add_columns, reserve_columns, column_stats, run, objective on the dense 24 x 32 LP of rust-lp_amd/synthetic.py (seed 1), whose last
 // three columns are held back and added on the optimal basis of the first 29.  Runs on the GPU box: `tests/cpp/test_columns` (built by
-// tests/cpp/columns.mk, `__graft_entry__.build()`); exit code 0 = all checks passed.  tests/test_cpp_columns.py runs it under pytest
+// tests/cpp/Makefile, `__graft_entry__.build()`); exit code 0 = all checks passed.  tests/test_cpp_columns.py runs it under pytest
 // (-m gpu).
 #include <array>
 #include <cmath>
@@ -11,24 +11,12 @@
 #include <vector>
 
 #include "relp.hpp"
+#include "check.hpp"
 
 using namespace relp_host;
 
-static int g_checks = 0, g_failed = 0;
-#define CHECK(cond)                                                                                   \
-    do {                                                                                              \
-        ++g_checks;                                                                                   \
-        if (!(cond)) { ++g_failed; std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); }    \
-    } while (0)
-#define CHECK_THROWS(expr, code)                                                                      \
-    do {                                                                                              \
-        ++g_checks;                                                                                   \
-        bool thrown_ = false;                                                                         \
-        try { (void)(expr); } catch (const Error& e) { thrown_ = e.status() == (code); }              \
-        if (!thrown_) { ++g_failed; std::printf("FAILED %s:%d: %s did not throw %s\n", __FILE__, __LINE__, #expr, #code); } \
-    } while (0)
 
-static bool near(double a, double b, double tol = 1e-9) { return std::fabs(a - b) <= tol * std::fmax(1.0, std::fabs(b)); }
+static bool near(double a, double b) { return near(a, b, 1e-9); }
 
 // synthetic.splitmix64(seed, stream, idx)
 static uint64_t splitmix64(uint64_t seed, uint64_t stream, uint64_t idx) {
@@ -137,6 +125,5 @@ int main() {
         std::printf("unexpected exception: %s\n", e.what());
         return 2;
     }
-    std::printf("%d checks, %d failed\n", g_checks, g_failed);
-    return g_failed == 0 ? 0 : 1;
+    return finish("test_columns");
 }

@@ -1,6 +1,6 @@
 // The host side of a cut pool (rust-lp_amd/csrc/relp_cutpool.hpp: the adapter onto the sliced-ELL packer of the column pool, the
 // norms, the segment arithmetic of relp_cutpool_separate, the key, the argument checks, the chosen cuts of an add) on hand-made
-// pools.  Plain C++17, no library, no GPU; built by tests/cpp/cutpool.mk once as it is and once with -fsanitize=address,undefined.
+// pools.  Plain C++17, no library, no GPU; built by tests/cpp/Makefile once as it is and once with -fsanitize=address,undefined.
 #include <cmath>
 #include <cstdio>
 #include <limits>
@@ -8,15 +8,10 @@
 #include <vector>
 
 #include "relp_cutpool.hpp"
+#include "check.hpp"
 
 using namespace relp;
 
-static int g_checks = 0, g_failed = 0;
-#define CHECK(cond)                                                                 \
-    do {                                                                            \
-        ++g_checks;                                                                 \
-        if (!(cond)) { ++g_failed; std::printf("FAILED %s:%d  %s\n", __FILE__, __LINE__, #cond); } \
-    } while (0)
 
 struct Csr {
     std::vector<int64_t> ptr{0};
@@ -176,6 +171,5 @@ static void test_segments_key_and_checks() {
 int main() {
     test_packer_and_norms();
     test_segments_key_and_checks();
-    std::printf("test_cutpool: %d checks, %d failed\n", g_checks, g_failed);
-    return g_failed ? 1 : 0;
+    return finish("test_cutpool");
 }

@@ -1,5 +1,5 @@
 // test_gomory.cpp -- the host side of relp_gomory_cuts without a GPU (rust-lp_amd/csrc/relp_gomory.hpp over relp_layout.{hpp,cpp}).
-// `make -C tests/cpp -f gomory.mk`; exit code 0 = all checks passed.  gomory.mk builds it a second time with
+// `make -C tests/cpp`; exit code 0 = all checks passed.  The Makefile builds it a second time with
 // -fsanitize=address,undefined (test_gomory_asan): it has its own main and needs no preload.
 //
 // Pins, on a layout with an ==, a <= and a >= row, two bounded columns and two cut rows (in phase 2):
@@ -17,10 +17,10 @@
 #include <string>
 #include <vector>
 
+#include "check.hpp"
+
 using namespace relp;
 
-static int g_failed = 0, g_checks = 0;
-#define CHECK(cond) do { ++g_checks; if (!(cond)) { ++g_failed; std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); } } while (0)
 
 static const double kInf = std::numeric_limits<double>::infinity();
 
@@ -120,6 +120,5 @@ int main() {
         const double y2[3] = {1.0, -1.0, 1.0}, rhs2[3] = {1e16, 1e16, 1.0};
         CHECK(gomory_beta(0.5, y2, rhs2, 3) == 1.0);                                                 // ((-0.5 + 1e16) - 1e16) + 1 = 0 + 1
     }
-    std::printf("%d checks, %d failed\n", g_checks, g_failed);
-    return g_failed ? 1 : 0;
+    return finish("test_gomory");
 }

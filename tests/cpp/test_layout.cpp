@@ -24,11 +24,11 @@ extern "C" {
 #include <utility>
 #include <vector>
 
+#include "check.hpp"
+
 using namespace relp;
 using Entries = std::vector<std::pair<int32_t, double>>;
 
-static int g_failed = 0, g_checks = 0;
-#define CHECK(cond, ...) do { ++g_checks; if (!(cond)) { ++g_failed; std::printf("FAILED %s:%d: ", __FILE__, __LINE__); std::printf(__VA_ARGS__); std::printf("\n"); } } while (0)
 
 static const double kInf = std::numeric_limits<double>::infinity();
 
@@ -79,30 +79,30 @@ static void test_problem_1() {
     const Lp lp = problem_1();
     Layout L;
     std::string err;
-    CHECK(L.build(lp.md(), config(RELP_ENGINE_REVISED), &err) == RELP_OK, "build: %s", err.c_str());
+    CHECKF(L.build(lp.md(), config(RELP_ENGINE_REVISED), &err) == RELP_OK, "build: %s", err.c_str());
     // matrix_data.rs:680-755 (provider columns: no artificial columns in front)
     auto prov = [&](int32_t p) { return column(L, lp, L.nr_artificial + p); };
-    CHECK(L.nr_normal == 3, "nr_normal %d", L.nr_normal);
-    CHECK(prov(0) == (Entries{{1, 1.0}, {2, 1.0}}), "column 0");
-    CHECK(prov(1) == (Entries{{0, -1.0}, {3, 1.0}}), "column 1");
-    CHECK(prov(2) == (Entries{{0, 1.0}, {1, 1.0}}), "column 2");
-    CHECK(prov(3) == (Entries{{1, -1.0}}), "column 3");
-    CHECK(prov(4) == (Entries{{2, 1.0}}), "column 4");
-    CHECK(prov(5) == (Entries{{3, 1.0}}), "column 5");
-    CHECK(L.rhs == (std::vector<double>{6, 10, 4, 2}), "right-hand side");
-    CHECK(L.bound_row == (std::vector<int32_t>{2, 3, -1}), "bound rows");
-    CHECK(L.mc == 2 && L.nr_bounds == 2 && L.m == 4 && L.n_provider == 6, "mc %d bounds %d m %d n %d", L.mc, L.nr_bounds, L.m, L.n_provider);
+    CHECKF(L.nr_normal == 3, "nr_normal %d", L.nr_normal);
+    CHECKF(prov(0) == (Entries{{1, 1.0}, {2, 1.0}}), "column 0");
+    CHECKF(prov(1) == (Entries{{0, -1.0}, {3, 1.0}}), "column 1");
+    CHECKF(prov(2) == (Entries{{0, 1.0}, {1, 1.0}}), "column 2");
+    CHECKF(prov(3) == (Entries{{1, -1.0}}), "column 3");
+    CHECKF(prov(4) == (Entries{{2, 1.0}}), "column 4");
+    CHECKF(prov(5) == (Entries{{3, 1.0}}), "column 5");
+    CHECKF(L.rhs == (std::vector<double>{6, 10, 4, 2}), "right-hand side");
+    CHECKF(L.bound_row == (std::vector<int32_t>{2, 3, -1}), "bound rows");
+    CHECKF(L.mc == 2 && L.nr_bounds == 2 && L.m == 4 && L.n_provider == 6, "mc %d bounds %d m %d n %d", L.mc, L.nr_bounds, L.m, L.n_provider);
     // src/tests/problem_1.rs:376-399: artificials for rows 0 and 1, basis [0, 1, 2 + 4, 2 + 5], -pi (-1, -1, 0, 0), -obj -16
-    CHECK(L.nr_artificial == 2 && L.column_to_row == (std::vector<int32_t>{0, 1}), "artificial columns");
-    CHECK(L.basis == (std::vector<int32_t>{0, 1, 6, 7}), "initial basis");
-    CHECK(L.minus_pi == (std::vector<double>{-1, -1, 0, 0}), "-pi");
-    CHECK(L.phase1_objective == 16.0, "phase-1 objective %g", L.phase1_objective);
-    CHECK(column(L, lp, 0) == (Entries{{0, 1.0}}) && column(L, lp, 1) == (Entries{{1, 1.0}}), "artificial columns are unit columns");
-    CHECK(column(L, lp, L.nr_columns()) == (Entries{{-99, 0.0}}), "no column beyond the last");
+    CHECKF(L.nr_artificial == 2 && L.column_to_row == (std::vector<int32_t>{0, 1}), "artificial columns");
+    CHECKF(L.basis == (std::vector<int32_t>{0, 1, 6, 7}), "initial basis");
+    CHECKF(L.minus_pi == (std::vector<double>{-1, -1, 0, 0}), "-pi");
+    CHECKF(L.phase1_objective == 16.0, "phase-1 objective %g", L.phase1_objective);
+    CHECKF(column(L, lp, 0) == (Entries{{0, 1.0}}) && column(L, lp, 1) == (Entries{{1, 1.0}}), "artificial columns are unit columns");
+    CHECKF(column(L, lp, L.nr_columns()) == (Entries{{-99, 0.0}}), "no column beyond the last");
     // after the phase switch (Engine::switch_to_phase_two) an artificial that stayed basic has a wrapped index
     L.wrapped_na = L.nr_artificial; L.nr_artificial = 0;
-    CHECK(L.artificial_row(INT32_MAX - (2 - 1 - 1)) == 1 && L.artificial_row(INT32_MAX - (2 - 1 - 0)) == 0, "wrapped decode");
-    CHECK(column(L, lp, INT32_MAX) == (Entries{{1, 1.0}}) && column(L, lp, 0) == (Entries{{1, 1.0}, {2, 1.0}}), "phase-2 columns");
+    CHECKF(L.artificial_row(INT32_MAX - (2 - 1 - 1)) == 1 && L.artificial_row(INT32_MAX - (2 - 1 - 0)) == 0, "wrapped decode");
+    CHECKF(column(L, lp, INT32_MAX) == (Entries{{1, 1.0}}) && column(L, lp, 0) == (Entries{{1, 1.0}, {2, 1.0}}), "phase-2 columns");
 }
 
 // seeded LP with every row kind; columns sorted by row, some variables bounded
@@ -132,8 +132,8 @@ static void test_against_oracle() {
         Layout L;
         std::string err;
         const relp_status_t st = L.build(lp.md(), config(RELP_ENGINE_REVISED), &err);
-        if (lp.mc() == 0 && L.nr_bounds == 0) { CHECK(st == RELP_E_ARG && err == "empty problem", "seed %llu: %s", (unsigned long long)seed, err.c_str()); continue; }
-        CHECK(st == RELP_OK, "seed %llu: %s", (unsigned long long)seed, err.c_str());
+        if (lp.mc() == 0 && L.nr_bounds == 0) { CHECKF(st == RELP_E_ARG && err == "empty problem", "seed %llu: %s", (unsigned long long)seed, err.c_str()); continue; }
+        CHECKF(st == RELP_OK, "seed %llu: %s", (unsigned long long)seed, err.c_str());
         if (st) continue;
         oracle_matrix_data_t omd{};
         omd.nr_normal = lp.nr_normal; omd.nr_eq = lp.nr_eq; omd.nr_range = lp.nr_range; omd.nr_le = lp.nr_le; omd.nr_ge = lp.nr_ge;
@@ -142,7 +142,7 @@ static void test_against_oracle() {
         oracle_config_t ocfg{};
         oracle_engine_t* o = oracle_create(&omd, &ocfg);
         const int32_t m = oracle_m(o);
-        CHECK(m == L.m && oracle_n(o) == L.nr_columns() && oracle_nr_artificial(o) == L.nr_artificial,
+        CHECKF(m == L.m && oracle_n(o) == L.nr_columns() && oracle_nr_artificial(o) == L.nr_artificial,
               "seed %llu: sizes m %d/%d n %d/%d", (unsigned long long)seed, m, L.m, oracle_n(o), L.nr_columns());
         if (m == L.m) {
             std::vector<int32_t> basis(m);
@@ -150,14 +150,14 @@ static void test_against_oracle() {
             oracle_get_basis(o, basis.data());
             oracle_get_b(o, b.data());
             oracle_get_minus_pi(o, mpi.data());
-            CHECK(basis == L.basis, "seed %llu: initial basis", (unsigned long long)seed);
-            CHECK(b == L.rhs, "seed %llu: rhs", (unsigned long long)seed);
-            CHECK(mpi == L.minus_pi, "seed %llu: -pi", (unsigned long long)seed);
-            CHECK(oracle_objective(o) == L.phase1_objective, "seed %llu: objective %g / %g", (unsigned long long)seed,
+            CHECKF(basis == L.basis, "seed %llu: initial basis", (unsigned long long)seed);
+            CHECKF(b == L.rhs, "seed %llu: rhs", (unsigned long long)seed);
+            CHECKF(mpi == L.minus_pi, "seed %llu: -pi", (unsigned long long)seed);
+            CHECKF(oracle_objective(o) == L.phase1_objective, "seed %llu: objective %g / %g", (unsigned long long)seed,
                   oracle_objective(o), L.phase1_objective);
             // the initial basis is the identity: column basis[r] is e_r
             for (int32_t r = 0; r < m; ++r)
-                CHECK(column(L, lp, L.basis[r]) == (Entries{{r, 1.0}}), "seed %llu: basis column of row %d", (unsigned long long)seed, r);
+                CHECKF(column(L, lp, L.basis[r]) == (Entries{{r, 1.0}}), "seed %llu: basis column of row %d", (unsigned long long)seed, r);
         }
         oracle_destroy(o);
     }
@@ -190,24 +190,24 @@ static void test_remove_rows() {
         for (int32_t i = 0; i < lp.nr_eq; ++i) if ((seed >> i) & 1) drop.push_back(i);
         Layout L, F;
         std::string err;
-        CHECK(L.build(lp.md(), config(RELP_ENGINE_TABLEAU), &err) == RELP_OK, "build: %s", err.c_str());
+        CHECKF(L.build(lp.md(), config(RELP_ENGINE_TABLEAU), &err) == RELP_OK, "build: %s", err.c_str());
         const Lp lp_f = without_rows(lp, drop);
-        CHECK(F.build(lp_f.md(), config(RELP_ENGINE_TABLEAU), &err) == RELP_OK, "build: %s", err.c_str());
+        CHECKF(F.build(lp_f.md(), config(RELP_ENGINE_TABLEAU), &err) == RELP_OK, "build: %s", err.c_str());
         std::vector<int32_t> map(L.m);
         for (int32_t i = 0, f = 0, out = 0; i < L.m; ++i) map[i] = (f < (int32_t)drop.size() && drop[f] == i) ? (++f, -1) : out++;
         L.remove_rows(map);
         // (== rows have no slack: the provider columns are the same columns)
-        CHECK(L.m == F.m && L.mc == F.mc && L.n_provider == F.n_provider, "seed %llu: sizes", (unsigned long long)seed);
-        CHECK(L.rhs == F.rhs && L.bound_row == F.bound_row, "seed %llu: rhs / bound rows", (unsigned long long)seed);
-        CHECK(L.vrow0 == F.vrow0 && L.vrow1 == F.vrow1 && L.vsign == F.vsign, "seed %llu: virtual columns", (unsigned long long)seed);
-        CHECK(L.row_lo == 0 && L.row_hi == F.m && L.row_stride == F.row_stride && L.candidate_len == F.candidate_len,
+        CHECKF(L.m == F.m && L.mc == F.mc && L.n_provider == F.n_provider, "seed %llu: sizes", (unsigned long long)seed);
+        CHECKF(L.rhs == F.rhs && L.bound_row == F.bound_row, "seed %llu: rhs / bound rows", (unsigned long long)seed);
+        CHECKF(L.vrow0 == F.vrow0 && L.vrow1 == F.vrow1 && L.vsign == F.vsign, "seed %llu: virtual columns", (unsigned long long)seed);
+        CHECKF(L.row_lo == 0 && L.row_hi == F.m && L.row_stride == F.row_stride && L.candidate_len == F.candidate_len,
               "seed %llu: shard fields", (unsigned long long)seed);
         for (int32_t p = 0; p < L.n_provider; ++p)
-            CHECK(column(L, lp_f, L.nr_artificial + p) == column(F, lp_f, F.nr_artificial + p), "seed %llu: column %d", (unsigned long long)seed, p);
+            CHECKF(column(L, lp_f, L.nr_artificial + p) == column(F, lp_f, F.nr_artificial + p), "seed %llu: column %d", (unsigned long long)seed, p);
         // the artificial columns of the rows that stay keep their (shifted) rows
         for (int32_t a = 0, fa = 0; a < L.nr_artificial; ++a) {
             if (std::find(drop.begin(), drop.end(), a) != drop.end()) continue;      // (artificial a < nr_eq started in == row a)
-            CHECK(fa < F.nr_artificial && L.column_to_row[a] == F.column_to_row[fa], "seed %llu: artificial %d", (unsigned long long)seed, a);
+            CHECKF(fa < F.nr_artificial && L.column_to_row[a] == F.column_to_row[fa], "seed %llu: artificial %d", (unsigned long long)seed, a);
             ++fa;
         }
     }
@@ -215,14 +215,14 @@ static void test_remove_rows() {
     const Lp lp = random_lp(7, 5, 1, 1, 1, 2);
     Layout L;
     std::string err;
-    CHECK(L.build(lp.md(), config(RELP_ENGINE_TABLEAU), &err) == RELP_OK, "build: %s", err.c_str());
+    CHECKF(L.build(lp.md(), config(RELP_ENGINE_TABLEAU), &err) == RELP_OK, "build: %s", err.c_str());
     std::vector<int32_t> map(L.m);
     const int32_t gone = lp.nr_eq + lp.nr_range + lp.nr_le;            // the first >= row
     for (int32_t i = 0, out = 0; i < L.m; ++i) map[i] = i == gone ? -1 : out++;
     const int32_t slack = L.nr_normal + lp.nr_range + lp.nr_le;         // its slack column
     L.remove_rows(map);
-    CHECK(column(L, lp, L.nr_artificial + slack).empty(), "the slack of a removed row is an empty column");
-    CHECK(column(L, lp, L.nr_artificial + slack + 1) == (Entries{{gone, -1.0}}), "the next >= slack moves up a row");
+    CHECKF(column(L, lp, L.nr_artificial + slack).empty(), "the slack of a removed row is an empty column");
+    CHECKF(column(L, lp, L.nr_artificial + slack + 1) == (Entries{{gone, -1.0}}), "the next >= slack moves up a row");
 }
 
 static void test_shard_plans() {
@@ -238,32 +238,32 @@ static void test_shard_plans() {
                     std::string err;
                     const relp_status_t st = L.plan(lp->md(), config(kind, G, g), &err);
                     if ((kind == RELP_ENGINE_REVISED || kind == RELP_ENGINE_LU) && G > 1 && lp == &general) {
-                        CHECK(st == RELP_E_UNSUPPORTED, "a sharded engine other than the tableau needs a slack basis");
+                        CHECKF(st == RELP_E_UNSUPPORTED, "a sharded engine other than the tableau needs a slack basis");
                         break;
                     }
-                    CHECK(st == RELP_OK, "G %d kind %d rank %d: %s", G, kind, g, err.c_str());
+                    CHECKF(st == RELP_OK, "G %d kind %d rank %d: %s", G, kind, g, err.c_str());
                     const int32_t resolved = L.engine;
-                    CHECK(kind != RELP_ENGINE_AUTO || resolved == RELP_ENGINE_TABLEAU, "AUTO on a small LP is the tableau engine");
-                    CHECK(L.col_lo == next_col && L.col_hi >= L.col_lo, "G %d kind %d rank %d: columns [%d, %d) after %d", G, kind, g,
+                    CHECKF(kind != RELP_ENGINE_AUTO || resolved == RELP_ENGINE_TABLEAU, "AUTO on a small LP is the tableau engine");
+                    CHECKF(L.col_lo == next_col && L.col_hi >= L.col_lo, "G %d kind %d rank %d: columns [%d, %d) after %d", G, kind, g,
                           L.col_lo, L.col_hi, next_col);
                     next_col = L.col_hi;
                     if (resolved == RELP_ENGINE_TABLEAU) {
-                        CHECK(L.sc_lo == next_store && L.sc_hi >= L.sc_lo, "stored columns");
+                        CHECKF(L.sc_lo == next_store && L.sc_hi >= L.sc_lo, "stored columns");
                         next_store = L.sc_hi;
                     } else {
-                        CHECK(L.row_lo == next_row && L.row_hi >= L.row_lo && L.row_hi - L.row_lo <= L.row_stride, "rows of B^-1");
+                        CHECKF(L.row_lo == next_row && L.row_hi >= L.row_lo && L.row_hi - L.row_lo <= L.row_stride, "rows of B^-1");
                         next_row = L.row_hi;
                     }
                     if (kind == RELP_ENGINE_AUTO) {
                         Layout T;
-                        CHECK(T.plan(lp->md(), config(RELP_ENGINE_TABLEAU, G, g), &err) == RELP_OK, "tableau plan");
-                        CHECK(T.col_lo == L.col_lo && T.col_hi == L.col_hi && T.sc_lo == L.sc_lo && T.sc_hi == L.sc_hi &&
+                        CHECKF(T.plan(lp->md(), config(RELP_ENGINE_TABLEAU, G, g), &err) == RELP_OK, "tableau plan");
+                        CHECKF(T.col_lo == L.col_lo && T.col_hi == L.col_hi && T.sc_lo == L.sc_lo && T.sc_hi == L.sc_hi &&
                               T.candidate_len == L.candidate_len, "AUTO plans the tableau engine (G %d rank %d)", G, g);
                     }
                     if (g == G - 1) {
-                        CHECK(next_col == L.nr_normal, "G %d kind %d: the columns end at %d of %d", G, kind, next_col, L.nr_normal);
-                        if (resolved == RELP_ENGINE_TABLEAU) CHECK(next_store == L.nr_columns(), "the stored columns are covered");
-                        else CHECK(next_row == L.m, "the rows are covered");
+                        CHECKF(next_col == L.nr_normal, "G %d kind %d: the columns end at %d of %d", G, kind, next_col, L.nr_normal);
+                        if (resolved == RELP_ENGINE_TABLEAU) CHECKF(next_store == L.nr_columns(), "the stored columns are covered");
+                        else CHECKF(next_row == L.m, "the rows are covered");
                     }
                 }
             }
@@ -274,16 +274,16 @@ static void test_shard_plans() {
     big.upper[2] = 1e301;
     Layout L;
     std::string err;
-    CHECK(L.plan(big.md(), config(RELP_ENGINE_TABLEAU), &err) == RELP_OK && L.bound_row[2] >= 0, "1e301 is a bound");
+    CHECKF(L.plan(big.md(), config(RELP_ENGINE_TABLEAU), &err) == RELP_OK && L.bound_row[2] >= 0, "1e301 is a bound");
     // the argument checks of relp_create
     relp_matrix_data_t md = big.md();
     md.nr_ge = -1;
-    CHECK(L.build(md, config(RELP_ENGINE_TABLEAU), &err) == RELP_E_ARG && err == "negative size", "negative size");
-    CHECK(L.build(big.md(), config(RELP_ENGINE_TABLEAU, 2, 2), &err) == RELP_E_ARG && err == "bad shard rank", "bad shard rank");
+    CHECKF(L.build(md, config(RELP_ENGINE_TABLEAU), &err) == RELP_E_ARG && err == "negative size", "negative size");
+    CHECKF(L.build(big.md(), config(RELP_ENGINE_TABLEAU, 2, 2), &err) == RELP_E_ARG && err == "bad shard rank", "bad shard rank");
     md = big.md();
     md.b = nullptr;
-    CHECK(L.build(md, config(RELP_ENGINE_TABLEAU), &err) == RELP_E_ARG && err == "missing b / cost / upper_bound / ranges", "missing b");
-    CHECK(L.plan(md, config(RELP_ENGINE_TABLEAU), &err) == RELP_OK, "the plan reads no b");
+    CHECKF(L.build(md, config(RELP_ENGINE_TABLEAU), &err) == RELP_E_ARG && err == "missing b / cost / upper_bound / ranges", "missing b");
+    CHECKF(L.plan(md, config(RELP_ENGINE_TABLEAU), &err) == RELP_OK, "the plan reads no b");
 }
 
 int main() {
@@ -291,6 +291,5 @@ int main() {
     test_against_oracle();
     test_remove_rows();
     test_shard_plans();
-    std::printf("test_layout: %d checks, %d failed\n", g_checks, g_failed);
-    return g_failed ? 1 : 0;
+    return finish("test_layout");
 }

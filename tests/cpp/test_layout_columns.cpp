@@ -1,5 +1,5 @@
 // test_layout_columns.cpp -- Layout::add_columns without a GPU (rust-lp_amd/csrc/relp_layout.{hpp,cpp}): columns from outside behind
-// every column.  `make -C tests/cpp -f columns.mk test_layout_columns`; exit code 0 = all checks passed.
+// every column.  `make -C tests/cpp test_layout_columns`; exit code 0 = all checks passed.
 //
 // Pins, on a layout with an ==, a <= and a >= row and two bounded columns (in phase 2: no artificial columns in front):
 //   * the indices of the new columns, and that m, rhs, the row classes, bound_row and every old descriptor stay;
@@ -17,11 +17,11 @@
 #include <utility>
 #include <vector>
 
+#include "check.hpp"
+
 using namespace relp;
 using Entries = std::vector<std::pair<int32_t, double>>;
 
-static int g_failed = 0, g_checks = 0;
-#define CHECK(cond) do { ++g_checks; if (!(cond)) { ++g_failed; std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); } } while (0)
 
 static const double kInf = std::numeric_limits<double>::infinity();
 
@@ -179,6 +179,5 @@ int main() {
         CHECK(L.add_columns(2, ptr.data(), idx.data(), val.data(), cost.data(), &err) == RELP_OK);
         CHECK(L.nr_added == 6 && column(L, lp, 12) == Entries({{2, 1.0}}) && column(L, lp, 13) == Entries({{2, 2.0}}));
     }
-    std::printf("%d checks, %d failed\n", g_checks, g_failed);
-    return g_failed == 0 ? 0 : 1;
+    return finish("test_layout_columns");
 }

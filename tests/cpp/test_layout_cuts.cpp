@@ -1,5 +1,5 @@
 // test_layout_cuts.cpp -- Layout::add_cuts without a GPU (rust-lp_amd/csrc/relp_layout.{hpp,cpp}): cut rows behind every row, their
-// slacks behind every column.  `make -C tests/cpp -f cuts.mk test_layout_cuts`; exit code 0 = all checks passed.
+// slacks behind every column.  `make -C tests/cpp test_layout_cuts`; exit code 0 = all checks passed.
 //
 // Pins, on a layout with an ==, a <= and a >= row and two bounded columns (in phase 2: no artificial columns in front):
 //   * the indices of the new rows and columns, and that mc, the row classes, bound_row and every old descriptor stay;
@@ -16,11 +16,11 @@
 #include <utility>
 #include <vector>
 
+#include "check.hpp"
+
 using namespace relp;
 using Entries = std::vector<std::pair<int32_t, double>>;
 
-static int g_failed = 0, g_checks = 0;
-#define CHECK(cond) do { ++g_checks; if (!(cond)) { ++g_failed; std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); } } while (0)
 
 static const double kInf = std::numeric_limits<double>::infinity();
 
@@ -153,6 +153,5 @@ int main() {
         CHECK(column(L, lp, 2) == Entries({{1, 1.0}, {2, 3.0}, {4, 1.0}, {5, -2.0}, {6, 4.0}, {8, 1.0}, {9, 2.0}}));
         CHECK(column(L, lp, 12) == Entries({{10, 1.0}}));
     }
-    std::printf("%d checks, %d failed\n", g_checks, g_failed);
-    return g_failed == 0 ? 0 : 1;
+    return finish("test_layout_cuts");
 }

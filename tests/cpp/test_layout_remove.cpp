@@ -1,5 +1,5 @@
 // test_layout_remove.cpp -- Layout::remove_cuts / remove_columns without a GPU (rust-lp_amd/csrc/relp_layout.{hpp,cpp}): cut rows and
-// added columns taken back.  `make -C tests/cpp -f remove.mk test_layout_remove`; exit code 0 = all checks passed.
+// added columns taken back.  `make -C tests/cpp test_layout_remove`; exit code 0 = all checks passed.
 //
 // Pins, on the layout of test_layout_columns.cpp (an ==, a <= and a >= row, two bounded columns, phase 2):
 //   * a layout that added cuts and columns interleaved (both orders) and then removed some of them EQUALS, member by member, the
@@ -16,11 +16,11 @@
 #include <utility>
 #include <vector>
 
+#include "check.hpp"
+
 using namespace relp;
 using Entries = std::vector<std::pair<int32_t, double>>;
 
-static int g_failed = 0, g_checks = 0;
-#define CHECK(cond) do { ++g_checks; if (!(cond)) { ++g_failed; std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); } } while (0)
 
 static const double kInf = std::numeric_limits<double>::infinity();
 
@@ -224,6 +224,5 @@ int main() {
         const Layout keep_f = F;
         CHECK(F.remove_cuts(rows, 1, {0, 1, 2, 3, 4}, &err) == RELP_E_ARG && F.remove_columns(cs, 1, {0, 1, 2, 3, 4}, &err) == RELP_E_ARG && same(F, keep_f));
     }
-    std::printf("%d checks, %d failed\n", g_checks, g_failed);
-    return g_failed == 0 ? 0 : 1;
+    return finish("test_layout_remove");
 }

@@ -15,12 +15,11 @@
 #include "relp_lu_factor_core.h"
 #include "relp_lu_image.hpp"
 #include "relp_lu_schedule_core.h"
+#include "check.hpp"
 
 using namespace relp;
 using Cols = std::vector<std::vector<std::pair<int32_t, double>>>;
 
-static int g_checks = 0, g_failed = 0;
-#define CHECK(cond, ...) do { ++g_checks; if (!(cond)) { ++g_failed; std::printf("FAILED %s:%d: ", __FILE__, __LINE__); std::printf(__VA_ARGS__); std::printf("\n"); } } while (0)
 
 // A provider in the engine's terms: structural columns (CSC over the constraint rows) with optional bound rows, virtual
 // (slack) columns, artificial columns; and a basis = m column ids.
@@ -166,22 +165,22 @@ static void check(const char* name, const Provider& P, const std::vector<int32_t
     for (int32_t c = 0; c < m; ++c) { cols[c] = P.column_of(basis[c]); std::sort(cols[c].begin(), cols[c].end()); }
     LUFactors hf; std::string err;
     const bool host_ok = lu_factor(m, cols, &hf, &err);
-    if (expect_singular) { CHECK(B.O.status[0] == LUF_SINGULAR && !host_ok, "%s: a singular basis passed (status %d)", name, B.O.status[0]); return; }
+    if (expect_singular) { CHECKF(B.O.status[0] == LUF_SINGULAR && !host_ok, "%s: a singular basis passed (status %d)", name, B.O.status[0]); return; }
     if (!host_ok) return;                                 // (a random basis may be singular: nothing to compare with)
-    CHECK(B.O.status[0] == LUF_OK, "%s: status %d (bump %d, peeled %d)", name, B.O.status[0], B.O.status[1], B.O.status[2]);
+    CHECKF(B.O.status[0] == LUF_OK, "%s: status %d (bump %d, peeled %d)", name, B.O.status[0], B.O.status[1], B.O.status[2]);
     if (B.O.status[0] != LUF_OK) return;
     const LufOut& O = B.O;
     // permutations are permutations, the inverses agree
     std::vector<int> seen_r(m, 0), seen_c(m, 0);
-    for (int32_t k = 0; k < m; ++k) { ++seen_r[O.rowperm[k]]; ++seen_c[O.colperm[k]]; CHECK(O.row_step[O.rowperm[k]] == k && O.col_step[O.colperm[k]] == k, "%s: step %d", name, k); }
-    for (int32_t i = 0; i < m; ++i) CHECK(seen_r[i] == 1 && seen_c[i] == 1, "%s: not a permutation at %d", name, i);
+    for (int32_t k = 0; k < m; ++k) { ++seen_r[O.rowperm[k]]; ++seen_c[O.colperm[k]]; CHECKF(O.row_step[O.rowperm[k]] == k && O.col_step[O.colperm[k]] == k, "%s: step %d", name, k); }
+    for (int32_t i = 0; i < m; ++i) CHECKF(seen_r[i] == 1 && seen_c[i] == 1, "%s: not a permutation at %d", name, i);
     // P B Q = L U, entry by entry
     const std::vector<double> a = dense_basis(P, basis);
     std::vector<double> L((size_t)m * m, 0.0), U((size_t)m * m, 0.0);
     for (int32_t k = 0; k < m; ++k) {
         L[(size_t)k * m + k] = 1.0; U[(size_t)k * m + k] = O.diag[k];
-        for (int32_t e = O.Lf.ptr[k]; e < O.Lf.ptr[k + 1]; ++e) { CHECK(O.Lf.idx[e] < k, "%s: L entry above the diagonal", name); L[(size_t)k * m + O.Lf.idx[e]] = O.Lf.val[e]; }
-        for (int32_t e = O.Uf.ptr[k]; e < O.Uf.ptr[k + 1]; ++e) { CHECK(O.Uf.idx[e] > k, "%s: U entry below the diagonal", name); U[(size_t)k * m + O.Uf.idx[e]] = O.Uf.val[e]; }
+        for (int32_t e = O.Lf.ptr[k]; e < O.Lf.ptr[k + 1]; ++e) { CHECKF(O.Lf.idx[e] < k, "%s: L entry above the diagonal", name); L[(size_t)k * m + O.Lf.idx[e]] = O.Lf.val[e]; }
+        for (int32_t e = O.Uf.ptr[k]; e < O.Uf.ptr[k + 1]; ++e) { CHECKF(O.Uf.idx[e] > k, "%s: U entry below the diagonal", name); U[(size_t)k * m + O.Uf.idx[e]] = O.Uf.val[e]; }
     }
     double worst = 0.0, scale = 1.0;
     for (int32_t k = 0; k < m; ++k)
@@ -191,7 +190,7 @@ static void check(const char* name, const Provider& P, const std::vector<int32_t
             const double want = a[(size_t)O.rowperm[k] * m + O.colperm[l]];
             worst = std::max(worst, std::fabs(s - want)); scale = std::max(scale, std::fabs(want));
         }
-    CHECK(worst <= 1e-12 * scale * std::max(1, m), "%s: |P B Q - L U| = %.3e", name, worst);
+    CHECKF(worst <= 1e-12 * scale * std::max(1, m), "%s: |P B Q - L U| = %.3e", name, worst);
     // the column views hold the same entries as the row views
     {
         std::vector<double> Lc((size_t)m * m, 0.0), Uc((size_t)m * m, 0.0);
@@ -205,20 +204,20 @@ static void check(const char* name, const Provider& P, const std::vector<int32_t
                 if (k > l && Lc[(size_t)k * m + l] != L[(size_t)k * m + l]) same = false;
                 if (k < l && Uc[(size_t)k * m + l] != U[(size_t)k * m + l]) same = false;
             }
-        CHECK(same, "%s: row and column views differ", name);
-        CHECK(O.Lf.ptr[m] == O.Lb.ptr[m] && O.Uf.ptr[m] == O.Ub.ptr[m] && O.status[3] == O.Lf.ptr[m] && O.status[4] == O.Uf.ptr[m], "%s: entry counts", name);
+        CHECKF(same, "%s: row and column views differ", name);
+        CHECKF(O.Lf.ptr[m] == O.Lb.ptr[m] && O.Uf.ptr[m] == O.Ub.ptr[m] && O.status[3] == O.Lf.ptr[m] && O.status[4] == O.Uf.ptr[m], "%s: entry counts", name);
     }
     // FTRAN / BTRAN: against dense elimination and against the host factorisation
     std::vector<double> rhs(m), xh, zh;
     for (auto& v : rhs) v = (double)((int)(rng() % 19) - 9);
     const std::vector<double> x = ftran(O, m, rhs), z = btran(O, m, rhs);
-    CHECK(max_rel(x, dense_solve(m, a, rhs, false)) <= 1e-9, "%s: FTRAN differs from the dense solve by %.3e", name, max_rel(x, dense_solve(m, a, rhs, false)));
-    CHECK(max_rel(z, dense_solve(m, a, rhs, true)) <= 1e-9, "%s: BTRAN differs from the dense solve by %.3e", name, max_rel(z, dense_solve(m, a, rhs, true)));
+    CHECKF(max_rel(x, dense_solve(m, a, rhs, false)) <= 1e-9, "%s: FTRAN differs from the dense solve by %.3e", name, max_rel(x, dense_solve(m, a, rhs, false)));
+    CHECKF(max_rel(z, dense_solve(m, a, rhs, true)) <= 1e-9, "%s: BTRAN differs from the dense solve by %.3e", name, max_rel(z, dense_solve(m, a, rhs, true)));
     lu_ftran_host(hf, rhs, &xh); lu_btran_host(hf, rhs, &zh);
-    CHECK(max_rel(x, xh) <= 1e-9 && max_rel(z, zh) <= 1e-9, "%s: solves differ from lu_factor's by %.3e / %.3e", name, max_rel(x, xh), max_rel(z, zh));
+    CHECKF(max_rel(x, xh) <= 1e-9 && max_rel(z, zh) <= 1e-9, "%s: solves differ from lu_factor's by %.3e / %.3e", name, max_rel(x, xh), max_rel(z, zh));
     check_schedules(name, O, B.W, m, rng);
     // no more fill than the host factorisation by a wide margin (both pivot for sparsity)
-    CHECK(O.Lf.ptr[m] + O.Uf.ptr[m] <= 3 * (hf.nnz_l + hf.nnz_u) + 4 * m, "%s: %d + %d entries against the host's %lld + %lld", name, O.Lf.ptr[m], O.Uf.ptr[m],
+    CHECKF(O.Lf.ptr[m] + O.Uf.ptr[m] <= 3 * (hf.nnz_l + hf.nnz_u) + 4 * m, "%s: %d + %d entries against the host's %lld + %lld", name, O.Lf.ptr[m], O.Uf.ptr[m],
           (long long)hf.nnz_l, (long long)hf.nnz_u);
 }
 
@@ -298,32 +297,32 @@ static void check_host_image(const char* name, const char* which, const LufTrian
             int64_t sum = 0;
             for (int i = 0; i < 8; ++i) {
                 const int64_t bytes = pieces[i].bytes + (i == 0 ? 16 * kEllPadHeaders : 0);
-                CHECK(pieces[i].at == sum, "%s %s wide %d cap %d: %s at %lld, not at %lld", name, which, wide, cap, pieces[i].what, (long long)pieces[i].at, (long long)sum);
+                CHECKF(pieces[i].at == sum, "%s %s wide %d cap %d: %s at %lld, not at %lld", name, which, wide, cap, pieces[i].what, (long long)pieces[i].at, (long long)sum);
                 sum += (bytes + 15) / 16 * 16;
             }
-            CHECK(L.total == sum, "%s %s wide %d cap %d: image of %lld bytes, arrays of %lld", name, which, wide, cap, (long long)L.total, (long long)sum);
+            CHECKF(L.total == sum, "%s %s wide %d cap %d: image of %lld bytes, arrays of %lld", name, which, wide, cap, (long long)L.total, (long long)sum);
             if (L.total != sum) continue;
             if (cap == 0 && expect_overflow >= 0) {
-                CHECK((e.overflow() > 0) == (expect_overflow == 1), "%s %s wide %d: %zu overflow entries", name, which, wide, e.overflow());
-                if (expect_overflow == 1) CHECK(e.rovf.size() == 2 * (size_t)m && L.sidx - L.rovf == (8 * (int64_t)m + 15) / 16 * 16, "%s %s wide %d: rovf is not 2 m words", name, which, wide);
-                else CHECK(e.rovf.empty() && L.sidx == L.oval, "%s %s wide %d: sidx does not follow oval directly", name, which, wide);
+                CHECKF((e.overflow() > 0) == (expect_overflow == 1), "%s %s wide %d: %zu overflow entries", name, which, wide, e.overflow());
+                if (expect_overflow == 1) CHECKF(e.rovf.size() == 2 * (size_t)m && L.sidx - L.rovf == (8 * (int64_t)m + 15) / 16 * 16, "%s %s wide %d: rovf is not 2 m words", name, which, wide);
+                else CHECKF(e.rovf.empty() && L.sidx == L.oval, "%s %s wide %d: sidx does not follow oval directly", name, which, wide);
             }
             std::vector<char> image((size_t)L.total, (char)0x5a);          // (the writer must not rely on a cleared buffer)
             const bool written = ell_image_write(e, shape, image.data());
-            CHECK(written, "%s %s wide %d cap %d: ell_image_write refused the packing", name, which, wide, cap);
+            CHECKF(written, "%s %s wide %d cap %d: ell_image_write refused the packing", name, which, wide, cap);
             if (!written) continue;
             std::vector<char> is_data((size_t)L.total, 0);
             for (const Piece& pc : pieces) {
-                CHECK(pc.bytes == 0 || std::memcmp(image.data() + pc.at, pc.src, (size_t)pc.bytes) == 0, "%s %s wide %d cap %d: %s is not at its offset", name, which, wide, cap, pc.what);
+                CHECKF(pc.bytes == 0 || std::memcmp(image.data() + pc.at, pc.src, (size_t)pc.bytes) == 0, "%s %s wide %d cap %d: %s is not at its offset", name, which, wide, cap, pc.what);
                 std::fill(is_data.begin() + pc.at, is_data.begin() + pc.at + pc.bytes, 1);
             }
             bool pad_zero = true;
             for (int64_t i = 0; i < L.total; ++i) if (!is_data[(size_t)i] && image[(size_t)i] != 0) pad_zero = false;
-            CHECK(pad_zero, "%s %s wide %d cap %d: padding (or an empty header) is not zero", name, which, wide, cap);
+            CHECKF(pad_zero, "%s %s wide %d cap %d: padding (or an empty header) is not zero", name, which, wide, cap);
             // the view addresses the same arrays
             EllSchedule d{};
             ell_image_view(image.data(), shape, &d);
-            CHECK((const char*)d.passes == image.data() + L.passes && (const char*)d.lvl_pass == image.data() + L.lvl_pass && (const char*)d.rdiag == image.data() + L.rdiag &&
+            CHECKF((const char*)d.passes == image.data() + L.passes && (const char*)d.lvl_pass == image.data() + L.lvl_pass && (const char*)d.rdiag == image.data() + L.rdiag &&
                   (const char*)d.sval == image.data() + L.sval && (const char*)d.oval == image.data() + L.oval && (const char*)d.rovf == image.data() + L.rovf &&
                   (const char*)d.sidx == image.data() + L.sidx && (const char*)d.oidx == image.data() + L.oidx && d.bytes == L.total && d.m == m &&
                   d.n_passes == (int32_t)e.passes.size() && d.n_levels == (int32_t)e.lvl_pass.size() - 1 && d.n_lanes == (int32_t)e.lanes() && d.n_ovf == (int32_t)e.overflow(),
@@ -333,14 +332,14 @@ static void check_host_image(const char* name, const char* which, const LufTrian
             desc[LUF_D_PASSES] = shape.n_passes; desc[LUF_D_LEVELS] = shape.n_levels; desc[LUF_D_LANES] = shape.n_lanes; desc[LUF_D_OVF] = shape.n_ovf;
             desc[LUF_D_BYTES] = (int32_t)L.total; desc[LUF_D_TRIV] = (int32_t)e.triv.size(); desc[LUF_D_NRHS] = wide ? (int32_t)e.rhs_src.size() : -1;
             for (int32_t v : fs.s.idx) if (v >= fs.rhs_base) desc[LUF_D_USES_RHS] = 1;
-            CHECK(fs.rhs_base == m + 1, "%s %s: right-hand-side copies from %d on", name, which, fs.rhs_base);
+            CHECKF(fs.rhs_base == m + 1, "%s %s: right-hand-side copies from %d on", name, which, fs.rhs_base);
             std::vector<double> b(m), want, got;
             for (auto& v : b) v = (rng() % 3 == 0) ? (double)((int)(rng() % 13) - 6) : 0.0;
             if (m <= 5) for (auto& v : b) v = (double)((int)(rng() % 13) + 1);
             want = b; got = b;
             plain_solve(T, diag, ascending, m, want);
             image_solve(image.data(), desc, m, wide != 0, e.triv.data(), e.rhs_src.data(), got, 0);
-            CHECK(max_rel(got, want) <= 1e-9, "%s %s wide %d cap %d: host image solve differs by %.3e", name, which, wide, cap, max_rel(got, want));
+            CHECKF(max_rel(got, want) <= 1e-9, "%s %s wide %d cap %d: host image solve differs by %.3e", name, which, wide, cap, max_rel(got, want));
         }
 }
 
@@ -412,15 +411,15 @@ static void check_schedules(const char* name, const LufOut& O, const LufWork& W,
             SB.setup(m, tri[q]->ptr[m]);
             luf_build_schedule(T, SB.S, SB.SO);
             const LufSchedOut& SO = SB.SO;
-            CHECK(SO.desc[LUF_D_STATUS] == LUF_OK, "%s %s variant %d: schedule status %d", name, nm[q], variant, SO.desc[LUF_D_STATUS]);
+            CHECKF(SO.desc[LUF_D_STATUS] == LUF_OK, "%s %s variant %d: schedule status %d", name, nm[q], variant, SO.desc[LUF_D_STATUS]);
             if (SO.desc[LUF_D_STATUS] != LUF_OK) continue;
             std::vector<double> b(m), want, got;
             for (auto& v : b) v = (rng() % 3 == 0) ? (double)((int)(rng() % 13) - 6) : 0.0;
             want = b; got = b;
             plain_solve(*tri[q], T.diag, asc[q], m, want);
             image_solve(SB.image.data(), SO.desc, m, wide, SO.triv, SO.rhs_src, got, 0);
-            CHECK(max_rel(got, want) <= 1e-9, "%s %s variant %d: image solve differs by %.3e", name, nm[q], variant, max_rel(got, want));
-            CHECK(SO.desc[LUF_D_LEVELS] <= SO.desc[LUF_D_KAHN_LEVELS], "%s %s variant %d: more groups than levels", name, nm[q], variant);
+            CHECKF(max_rel(got, want) <= 1e-9, "%s %s variant %d: image solve differs by %.3e", name, nm[q], variant, max_rel(got, want));
+            CHECKF(SO.desc[LUF_D_LEVELS] <= SO.desc[LUF_D_KAHN_LEVELS], "%s %s variant %d: more groups than levels", name, nm[q], variant);
             // hyper-sparse start from the reach array
             std::vector<double> bs(m, 0.0);
             for (int t = 0; t < 3; ++t) bs[rng() % m] = (double)((int)(rng() % 9) + 1);
@@ -429,7 +428,7 @@ static void check_schedules(const char* name, const LufOut& O, const LufWork& W,
             want = bs; got = bs;
             plain_solve(*tri[q], T.diag, asc[q], m, want);
             image_solve(SB.image.data(), SO.desc, m, wide, SO.triv, SO.rhs_src, got, g0);
-            CHECK(max_rel(got, want) <= 1e-9, "%s %s variant %d: sweep from group %d differs by %.3e", name, nm[q], variant, g0, max_rel(got, want));
+            CHECKF(max_rel(got, want) <= 1e-9, "%s %s variant %d: sweep from group %d differs by %.3e", name, nm[q], variant, g0, max_rel(got, want));
             // level_of (start_after of fuse_levels): a right-hand side that is zero on p and on everything solved no later than p lets
             // the sweep start at group level_of[p] + 1
             {
@@ -446,7 +445,7 @@ static void check_schedules(const char* name, const LufOut& O, const LufWork& W,
                 want = bz; got = bz;
                 plain_solve(*tri[q], T.diag, asc[q], m, want);
                 image_solve(SB.image.data(), SO.desc, m, wide, SO.triv, SO.rhs_src, got, SO.level_of[p] + 1);
-                CHECK(max_rel(got, want) <= 1e-9, "%s %s variant %d: sweep behind pivot %d (group %d) differs by %.3e", name, nm[q], variant, p, SO.level_of[p] + 1,
+                CHECKF(max_rel(got, want) <= 1e-9, "%s %s variant %d: sweep behind pivot %d (group %d) differs by %.3e", name, nm[q], variant, p, SO.level_of[p] + 1,
                       max_rel(got, want));
             }
             if (variant == 0) check_host_image(name, nm[q], *tri[q], T.diag, asc[q], m, rng);
@@ -473,7 +472,7 @@ static void check_schedules(const char* name, const LufOut& O, const LufWork& W,
                     want[k] = masked[k] ? 0.0 : s2 / T.diag[k];
                 }
                 image_solve(SB.image.data(), SO.desc, m, wide, SO.triv, SO.rhs_src, got, 0);
-                CHECK(max_rel(got, want) <= 1e-9, "%s %s variant %d: image solve with %d masked pivots differs by %.3e", name, nm[q], variant, t + 1, max_rel(got, want));
+                CHECKF(max_rel(got, want) <= 1e-9, "%s %s variant %d: image solve with %d masked pivots differs by %.3e", name, nm[q], variant, t + 1, max_rel(got, want));
             }
         }
 }
@@ -647,6 +646,5 @@ int main(int argc, char** argv) {
     if (argc > 2) Buffers::dense_cap() = std::atoi(argv[2]);
     if (argc > 1) return probe(argv[1]);
     for (int dc : {64, 0, 7}) { Buffers::dense_cap() = dc; all_checks(); }     // the dense finish at the kernel's size, off, tiny
-    std::printf("test_lu_device_model: %d checks, %d failed\n", g_checks, g_failed);
-    return g_failed ? 1 : 0;
+    return finish("test_lu_device_model");
 }

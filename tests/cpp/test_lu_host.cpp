@@ -18,11 +18,11 @@
 #include <string>
 #include <vector>
 
+#include "check.hpp"
+
 using namespace relp;
 using Cols = std::vector<std::vector<std::pair<int32_t, double>>>;
 
-static int g_failed = 0, g_checks = 0;
-#define CHECK(cond, ...) do { ++g_checks; if (!(cond)) { ++g_failed; std::printf("FAILED %s:%d: ", __FILE__, __LINE__); std::printf(__VA_ARGS__); std::printf("\n"); } } while (0)
 
 static std::vector<double> dense_of(int m, const Cols& cols) {
     std::vector<double> a((size_t)m * m, 0.0);
@@ -128,19 +128,19 @@ static void check_matrix(const char* name, int m, const Cols& cols_in, std::mt19
     for (auto& c : cols) std::sort(c.begin(), c.end());
     LUFactors f; std::string err;
     const bool ok = lu_factor(m, cols, &f, &err);
-    CHECK(ok, "%s: lu_factor failed: %s", name, err.c_str());
+    CHECKF(ok, "%s: lu_factor failed: %s", name, err.c_str());
     if (!ok) return;
     const double res = residual(m, cols, f);
-    CHECK(res <= 1e-12 * std::max(1.0, (double)m), "%s: |P B Q - L U| = %.3e", name, res);
+    CHECKF(res <= 1e-12 * std::max(1.0, (double)m), "%s: |P B Q - L U| = %.3e", name, res);
     // FTRAN / BTRAN against the dense solve
     const std::vector<double> a = dense_of(m, cols);
     std::vector<double> rhs(m), x, z;
     for (auto& v : rhs) v = (double)((int)(rng() % 19) - 9);
     lu_ftran_host(f, rhs, &x);
-    CHECK(max_diff(x, dense_solve(m, a, rhs, false)) <= 1e-9, "%s: FTRAN differs from the dense solve by %.3e", name,
+    CHECKF(max_diff(x, dense_solve(m, a, rhs, false)) <= 1e-9, "%s: FTRAN differs from the dense solve by %.3e", name,
           max_diff(x, dense_solve(m, a, rhs, false)));
     lu_btran_host(f, rhs, &z);
-    CHECK(max_diff(z, dense_solve(m, a, rhs, true)) <= 1e-9, "%s: BTRAN differs from the dense solve by %.3e", name,
+    CHECKF(max_diff(z, dense_solve(m, a, rhs, true)) <= 1e-9, "%s: BTRAN differs from the dense solve by %.3e", name,
           max_diff(z, dense_solve(m, a, rhs, true)));
     // the four schedules: fused and packed, executed like the device does, against the plain solve
     const TriangularSchedule* sch[4] = {&f.Lf, &f.Uf, &f.Ub, &f.Lb};
@@ -157,7 +157,7 @@ static void check_matrix(const char* name, int m, const Cols& cols_in, std::mt19
             want = b;
             solve_plain(*sch[k], want);
             solve_ell(e, m, fs.rhs_base, b, &got);
-            CHECK(max_diff(got, want) <= 1e-9, "%s %s cap %d: packed solve differs by %.3e", name, nm[k], cap, max_diff(got, want));
+            CHECKF(max_diff(got, want) <= 1e-9, "%s %s cap %d: packed solve differs by %.3e", name, nm[k], cap, max_diff(got, want));
             {   // hyper-sparse start: a right-hand side with a few entries, the sweep begins at the first group they reach
                 std::vector<double> bs(m, 0.0), want_s, got_s;
                 for (int t = 0; t < 3; ++t) bs[rng() % m] = (double)((int)(rng() % 9) + 1);
@@ -166,18 +166,18 @@ static void check_matrix(const char* name, int m, const Cols& cols_in, std::mt19
                 want_s = bs;
                 solve_plain(*sch[k], want_s);
                 solve_ell(e, m, fs.rhs_base, bs, &got_s, g0);
-                CHECK(max_diff(got_s, want_s) <= 1e-9, "%s %s cap %d: sweep started at group %d differs by %.3e", name, nm[k], cap, g0,
+                CHECKF(max_diff(got_s, want_s) <= 1e-9, "%s %s cap %d: sweep started at group %d differs by %.3e", name, nm[k], cap, g0,
                       max_diff(got_s, want_s));
-                for (int kk : e.triv) CHECK(sch[k]->ptr[kk + 1] == sch[k]->ptr[kk], "%s %s: row %d in the trivial list has entries", name, nm[k], kk);
+                for (int kk : e.triv) CHECKF(sch[k]->ptr[kk + 1] == sch[k]->ptr[kk], "%s %s: row %d in the trivial list has entries", name, nm[k], kk);
             }
             {   // the 32-bit packing of large bases: same passes, same slots, same result bit for bit
                 EllPacked w;
                 ell_pack(fs, maskable, &w, true, true, 4);     // (+ compacted right-hand-side copies, rows without entries listed)
                 std::vector<double> got_w;
                 solve_ell(w, m, fs.rhs_base, b, &got_w);
-                CHECK(w.sidx.empty() && w.overflow() == e.overflow() && w.passes.size() <= e.passes.size(),
+                CHECKF(w.sidx.empty() && w.overflow() == e.overflow() && w.passes.size() <= e.passes.size(),
                       "%s %s cap %d: wide packing has another shape", name, nm[k], cap);
-                CHECK(max_diff(got_w, got) <= 1e-12, "%s %s cap %d: wide packing solves differently", name, nm[k], cap);
+                CHECKF(max_diff(got_w, got) <= 1e-12, "%s %s cap %d: wide packing solves differently", name, nm[k], cap);
                 std::vector<double> bs(m, 0.0), want_s, got_s;      // hyper-sparse start on the list / compact variant
                 for (int t = 0; t < 3; ++t) bs[rng() % m] = (double)((int)(rng() % 9) + 1);
                 int g0 = 0x7fffffff;
@@ -185,11 +185,11 @@ static void check_matrix(const char* name, int m, const Cols& cols_in, std::mt19
                 want_s = bs;
                 solve_plain(*sch[k], want_s);
                 solve_ell(w, m, fs.rhs_base, bs, &got_s, g0);
-                CHECK(max_diff(got_s, want_s) <= 1e-9, "%s %s cap %d: wide sweep started at group %d differs by %.3e", name, nm[k], cap, g0,
+                CHECKF(max_diff(got_s, want_s) <= 1e-9, "%s %s cap %d: wide sweep started at group %d differs by %.3e", name, nm[k], cap, g0,
                       max_diff(got_s, want_s));
             }
-            CHECK(fs.s.level_ptr.size() <= sch[k]->level_ptr.size(), "%s %s: more groups than levels", name, nm[k]);
-            for (const EllPassHost& ps : e.passes) CHECK(ps.lanes <= 256 && ps.lanes > 0, "%s %s: pass of %d lanes", name, nm[k], ps.lanes);
+            CHECKF(fs.s.level_ptr.size() <= sch[k]->level_ptr.size(), "%s %s: more groups than levels", name, nm[k]);
+            for (const EllPassHost& ps : e.passes) CHECKF(ps.lanes <= 256 && ps.lanes > 0, "%s %s: pass of %d lanes", name, nm[k], ps.lanes);
             if (!maskable || m < 2) continue;
             // mask a few pivots the way ft_update does: 1 / diagonal := 0, the listed entries := 0, x[p] := 0 on entry
             std::vector<char> masked(m, 0);
@@ -198,13 +198,13 @@ static void check_matrix(const char* name, int m, const Cols& cols_in, std::mt19
                 if (masked[p]) continue;
                 masked[p] = 1;
                 e.rdiag[p] = 0.0;
-                for (int v = e.via_ptr[p]; v < e.via_ptr[p + 1]; ++v) { CHECK(e.via_pos[v] >= 0, "%s %s: via entry in an overflow list", name, nm[k]); if (e.via_pos[v] >= 0) e.sval[e.via_pos[v]] = 0.0; }
+                for (int v = e.via_ptr[p]; v < e.via_ptr[p + 1]; ++v) { CHECKF(e.via_pos[v] >= 0, "%s %s: via entry in an overflow list", name, nm[k]); if (e.via_pos[v] >= 0) e.sval[e.via_pos[v]] = 0.0; }
                 std::vector<double> bm = b;
                 for (int i = 0; i < m; ++i) if (masked[i]) bm[i] = 0.0;
                 want = bm;
                 solve_plain(*sch[k], want, &masked);
                 solve_ell(e, m, fs.rhs_base, bm, &got);
-                CHECK(max_diff(got, want) <= 1e-9, "%s %s cap %d: packed solve with %d masked pivots differs by %.3e", name, nm[k], cap,
+                CHECKF(max_diff(got, want) <= 1e-9, "%s %s cap %d: packed solve with %d masked pivots differs by %.3e", name, nm[k], cap,
                       t + 1, max_diff(got, want));
             }
         }
@@ -218,7 +218,7 @@ static void check_level_runs(const char* name, const std::vector<int>& sizes, co
     const std::vector<int32_t> got = lu_level_runs(level_ptr);
     std::string text;
     for (int32_t v : got) text += std::to_string(v) + " ";
-    CHECK(got == want, "level runs, %s: got ( %s)", name, text.c_str());
+    CHECKF(got == want, "level runs, %s: got ( %s)", name, text.c_str());
 }
 
 int main() {
@@ -246,12 +246,12 @@ int main() {
     {   // wikipedia 2's known answers (decomposition/mod.rs:470-489): B^-1 e_0 = (2, 2), B^-1 e_1 = (3, 2)
         Cols c = {{{0, -1.0}, {1, 1.0}}, {{0, 1.5}, {1, -1.0}}};
         LUFactors f; std::string err;
-        CHECK(lu_factor(2, c, &f, &err), "wikipedia 2: %s", err.c_str());
+        CHECKF(lu_factor(2, c, &f, &err), "wikipedia 2: %s", err.c_str());
         std::vector<double> x;
         lu_ftran_host(f, {1.0, 0.0}, &x);
-        CHECK(std::fabs(x[0] - 2.0) < 1e-14 && std::fabs(x[1] - 2.0) < 1e-14, "wikipedia 2: B^-1 e_0 = (%g, %g)", x[0], x[1]);
+        CHECKF(std::fabs(x[0] - 2.0) < 1e-14 && std::fabs(x[1] - 2.0) < 1e-14, "wikipedia 2: B^-1 e_0 = (%g, %g)", x[0], x[1]);
         lu_ftran_host(f, {0.0, 1.0}, &x);
-        CHECK(std::fabs(x[0] - 3.0) < 1e-14 && std::fabs(x[1] - 2.0) < 1e-14, "wikipedia 2: B^-1 e_1 = (%g, %g)", x[0], x[1]);
+        CHECKF(std::fabs(x[0] - 3.0) < 1e-14 && std::fabs(x[1] - 2.0) < 1e-14, "wikipedia 2: B^-1 e_1 = (%g, %g)", x[0], x[1]);
     }
     // the 5 x 5 upper factor of lower_upper/mod.rs:779-867 (Elble & Sahinidis) as a basis of its own
     check_matrix("elble-sahinidis U", 5, {{{0, 11.0}}, {{0, 12.0}, {1, 22.0}}, {{0, 13.0}, {1, 23.0}, {2, 33.0}},
@@ -260,7 +260,7 @@ int main() {
     {
         LUFactors f; std::string err;
         Cols c = {{{0, 1.0}, {1, 2.0}}, {{0, 2.0}, {1, 4.0}}};
-        CHECK(!lu_factor(2, c, &f, &err) && !err.empty(), "a singular matrix passed");
+        CHECKF(!lu_factor(2, c, &f, &err) && !err.empty(), "a singular matrix passed");
     }
     // LP-like random bases: a permuted diagonal, a sparse bump, a few dense columns, long dependency chains
     for (int trial = 0; trial < 60; ++trial) {
@@ -283,6 +283,5 @@ int main() {
         std::snprintf(nm, sizeof nm, "random %d (m = %d)", trial, m);
         check_matrix(nm, m, cols, rng);
     }
-    std::printf("test_lu_host: %d checks, %d failed\n", g_checks, g_failed);
-    return g_failed ? 1 : 0;
+    return finish("test_lu_host");
 }

@@ -1,6 +1,6 @@
 // The host side of a column pool (rust-lp_amd/csrc/relp_pool.hpp: the sliced-ELL packer, the segment arithmetic of relp_pool_price,
 // the stale rule, the argument checks, the chosen columns of an add) on hand-made pools.  Plain C++17, no library, no GPU; built by
-// tests/cpp/pool.mk once as it is and once with -fsanitize=address,undefined.
+// tests/cpp/Makefile once as it is and once with -fsanitize=address,undefined.
 #include <cmath>
 #include <cstdio>
 #include <limits>
@@ -8,15 +8,10 @@
 #include <vector>
 
 #include "relp_pool.hpp"
+#include "check.hpp"
 
 using namespace relp;
 
-static int g_checks = 0, g_failed = 0;
-#define CHECK(cond)                                                                 \
-    do {                                                                            \
-        ++g_checks;                                                                 \
-        if (!(cond)) { ++g_failed; std::printf("FAILED %s:%d  %s\n", __FILE__, __LINE__, #cond); } \
-    } while (0)
 
 struct Csc {
     std::vector<int64_t> ptr{0};
@@ -183,6 +178,5 @@ int main() {
     test_packer();
     test_segments();
     test_lists_and_stale_rule();
-    std::printf("test_pool: %d checks, %d failed\n", g_checks, g_failed);
-    return g_failed ? 1 : 0;
+    return finish("test_pool");
 }

@@ -1,30 +1,18 @@
 // C++ host-side test of the batched ratio queries over include/relp.hpp (no counterpart in the reference): row_ratios, rhs_ranging,
 // ranging_stats on one LP solved by hand, and the refusals.  Runs on the GPU box: `tests/cpp/test_ranging` (built by
-// tests/cpp/ranging.mk, `__graft_entry__.build()`); exit code 0 = all checks passed.  tests/test_cpp_ranging.py runs it under pytest
+// tests/cpp/Makefile, `__graft_entry__.build()`); exit code 0 = all checks passed.  tests/test_cpp_ranging.py runs it under pytest
 // (-m gpu).
 #include <cmath>
 #include <cstdio>
 #include <limits>
 
 #include "relp.hpp"
+#include "check.hpp"
 
 using namespace relp_host;
 
-static int g_checks = 0, g_failed = 0;
-#define CHECK(cond)                                                                                   \
-    do {                                                                                              \
-        ++g_checks;                                                                                   \
-        if (!(cond)) { ++g_failed; std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); }    \
-    } while (0)
-#define CHECK_THROWS(expr, code)                                                                      \
-    do {                                                                                              \
-        ++g_checks;                                                                                   \
-        bool thrown_ = false;                                                                         \
-        try { (void)(expr); } catch (const Error& e) { thrown_ = e.status() == (code); }              \
-        if (!thrown_) { ++g_failed; std::printf("FAILED %s:%d: %s did not throw %s\n", __FILE__, __LINE__, #expr, #code); } \
-    } while (0)
 
-static bool near(double a, double b, double tol = 1e-12) { return std::fabs(a - b) <= tol * std::fmax(1.0, std::fabs(b)); }
+static bool near(double a, double b) { return near(a, b, 1e-12); }
 
 int main() {
     try {
@@ -82,6 +70,5 @@ int main() {
         std::printf("unexpected exception: %s\n", e.what());
         return 2;
     }
-    std::printf("%d checks, %d failed\n", g_checks, g_failed);
-    return g_failed == 0 ? 0 : 1;
+    return finish("test_ranging");
 }

@@ -1,6 +1,6 @@
 // C++ host-side test of cut rows and added columns removed in place over include/relp.hpp (no counterpart in the reference, whose
 // provider is immutable): remove_cuts, remove_columns, removal_stats on the dense 24 x 32 LP of rust-lp_amd/synthetic.py (seed 1),
-// whose last three columns are held back.  Runs on the GPU box: `tests/cpp/test_remove` (built by tests/cpp/remove.mk,
+// whose last three columns are held back.  Runs on the GPU box: `tests/cpp/test_remove` (built by tests/cpp/Makefile,
 // `__graft_entry__.build()`); exit code 0 = all checks passed.  tests/test_cpp_remove.py runs it under pytest (-m gpu).
 #include <array>
 #include <cmath>
@@ -9,24 +9,12 @@
 #include <vector>
 
 #include "relp.hpp"
+#include "check.hpp"
 
 using namespace relp_host;
 
-static int g_checks = 0, g_failed = 0;
-#define CHECK(cond)                                                                                   \
-    do {                                                                                              \
-        ++g_checks;                                                                                   \
-        if (!(cond)) { ++g_failed; std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); }    \
-    } while (0)
-#define CHECK_THROWS(expr, code)                                                                      \
-    do {                                                                                              \
-        ++g_checks;                                                                                   \
-        bool thrown_ = false;                                                                         \
-        try { (void)(expr); } catch (const Error& e) { thrown_ = e.status() == (code); }              \
-        if (!thrown_) { ++g_failed; std::printf("FAILED %s:%d: %s did not throw %s\n", __FILE__, __LINE__, #expr, #code); } \
-    } while (0)
 
-static bool near(double a, double b, double tol = 1e-9) { return std::fabs(a - b) <= tol * std::fmax(1.0, std::fabs(b)); }
+static bool near(double a, double b) { return near(a, b, 1e-9); }
 
 // synthetic.splitmix64(seed, stream, idx)
 static uint64_t splitmix64(uint64_t seed, uint64_t stream, uint64_t idx) {
@@ -172,6 +160,5 @@ int main() {
         std::printf("unexpected exception: %s\n", e.what());
         return 2;
     }
-    std::printf("%d checks, %d failed\n", g_checks, g_failed);
-    return g_failed == 0 ? 0 : 1;
+    return finish("test_remove");
 }

@@ -8,24 +8,12 @@
 #include <string>
 
 #include "relp.hpp"
+#include "check.hpp"
 
 using namespace relp_host;
 
-static int g_checks = 0, g_failed = 0;
-#define CHECK(cond)                                                                                   \
-    do {                                                                                              \
-        ++g_checks;                                                                                   \
-        if (!(cond)) { ++g_failed; std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); }    \
-    } while (0)
-#define CHECK_THROWS(expr, code)                                                                      \
-    do {                                                                                              \
-        ++g_checks;                                                                                   \
-        bool thrown_ = false;                                                                         \
-        try { (void)(expr); } catch (const Error& e) { thrown_ = e.status() == (code); }              \
-        if (!thrown_) { ++g_failed; std::printf("FAILED %s:%d: %s did not throw %s\n", __FILE__, __LINE__, #expr, #code); } \
-    } while (0)
 
-static bool near(double a, double b, double tol = 1e-12) { return std::fabs(a - b) <= tol * std::fmax(1.0, std::fabs(b)); }
+static bool near(double a, double b) { return near(a, b, 1e-12); }
 static bool near(const std::vector<double>& a, const std::vector<double>& b, double tol = 1e-12) {
     if (a.size() != b.size()) return false;
     for (size_t i = 0; i < a.size(); ++i) if (!near(a[i], b[i], tol)) return false;
@@ -269,6 +257,5 @@ int main() {
         std::printf("unexpected exception: %s\n", e.what());
         return 2;
     }
-    std::printf("%d checks, %d failed\n", g_checks, g_failed);
-    return g_failed == 0 ? 0 : 1;
+    return finish("test_tableau");
 }

@@ -1,5 +1,5 @@
 // test_trial.cpp -- the planner of the trial snapshot without a GPU (rust-lp_amd/csrc/relp_trial.hpp: plain C++17, no HIP).
-// `make -C tests/cpp -f trial.mk`; exit code 0 = all checks passed.  trial.mk builds it a second time with
+// `make -C tests/cpp`; exit code 0 = all checks passed.  The Makefile builds it a second time with
 // -fsanitize=address,undefined (test_trial_asan): it has its own main and needs no preload.
 //
 // Pins, for 0, 1 and 32 segments with the byte counts 0, 1, 15, 16 and 17 (and 4,099):
@@ -15,10 +15,10 @@
 #include <cstring>
 #include <vector>
 
+#include "check.hpp"
+
 using namespace relp;
 
-static int g_failed = 0, g_checks = 0;
-#define CHECK(cond) do { ++g_checks; if (!(cond)) { ++g_failed; std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); } } while (0)
 
 // what k_tab_trial_copy does with a table: the whole units of every segment, then each tail
 static void model_copy(const TrialTable& t) {
@@ -112,6 +112,5 @@ int main() {
         TrialPlan empty;
         CHECK(empty.add(nullptr, 0) && empty.count() == 1 && empty.buffer_bytes() == 0);   // an array this engine does not have
     }
-    std::printf("%d checks, %d failed\n", g_checks, g_failed);
-    return g_failed ? 1 : 0;
+    return finish("test_trial");
 }

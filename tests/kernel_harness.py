@@ -83,16 +83,13 @@ def load():
     return _lib
 
 
-def _call(name, scalars, arrays):
-    """lib.name(*scalars, *(pointer, length of every array)).  Input arrays must already have their dtype."""
+def invoke(name, *args):
+    """Every call of the library that may launch goes through here: nothing is called once the library's sticky HIP error is set
+    (one for all families), a negative return code is a refusal, any other a HIP error.  `args` are ctypes values."""
     lib = load()
     sticky = lib.rkh_sticky_error()
     if sticky:
         raise HarnessFault(f"an earlier harness call failed with HIP error {sticky - HIP_ERROR_BASE}; nothing is launched any more")
-    args = [C.c_int64(int(s)) if wide else C.c_int(int(s)) for s, wide in scalars]
-    for a in arrays:
-        assert a.flags["C_CONTIGUOUS"]
-        args += [C.c_void_p(a.ctypes.data), C.c_int64(a.size)]
     fn = getattr(lib, name)
     fn.restype = C.c_int
     rc = fn(*args)
@@ -100,6 +97,22 @@ def _call(name, scalars, arrays):
         raise HarnessRefused(rc)
     if rc:
         raise HarnessFault(f"{name}: HIP error {rc - HIP_ERROR_BASE}")
+
+
+def _call(name, scalars, arrays, reals=(), lengths=None):
+    """lib.name(*scalars, *reals, *(pointer, length of every array)); the family modules tests/kernel_harness_*.py call through
+    here too.  A scalar is an int (passed as int64) or (value, wide); the reals are passed as doubles.  `arrays` is a list of arrays
+    or a dict of named images; `lengths` overrides the length passed for a named image (the refusal tests).  Input arrays must
+    already have their dtype."""
+    args = []
+    for s in scalars:
+        value, wide = s if isinstance(s, tuple) else (s, True)
+        args.append(C.c_int64(int(value)) if wide else C.c_int(int(value)))
+    args += [C.c_double(r) for r in reals]
+    for key, a in (arrays.items() if isinstance(arrays, dict) else enumerate(arrays)):
+        assert a.flags["C_CONTIGUOUS"]
+        args += [C.c_void_p(a.ctypes.data), C.c_int64((lengths or {}).get(key, a.size))]
+    invoke(name, *args)
 
 
 def _f64(a): return np.ascontiguousarray(a, dtype=np.float64)
@@ -843,6 +856,27 @@ def diff_image(got, want, what, limit=5):
     idx = np.argwhere(bad)
     return [f"{what}{tuple(i)}: got {got[tuple(i)]!r} ({bg[tuple(i)]:#x}), want {want[tuple(i)]!r} ({bw[tuple(i)]:#x})"
             for i in idx[:limit]] + ([f"{what}: {len(idx)} words differ"] if len(idx) > limit else [])
+
+
+def image_bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view(np.uint64) if a.dtype == np.float64 else a
+
+
+def diff_images(got, want, limit=5):
+    """Every returned image (a dict) against the expected one, bit for bit (the sentinels included: what the launch must not
+    write)."""
+    problems = []
+    for name in want:
+        g, w = image_bits(got[name]), image_bits(want[name])
+        if g.shape != w.shape:
+            problems.append(f"{name}: {g.shape} words returned, {w.shape} expected")
+            continue
+        bad = np.flatnonzero(g != w)
+        if bad.size:
+            shown = ", ".join(f"[{int(x)}] {got[name].reshape(-1)[x]!r} != {want[name].reshape(-1)[x]!r}" for x in bad[:limit])
+            problems.append(f"{name}: {bad.size} words differ: {shown}")
+    return problems
 
 
 RHS_IMAGES = ("b", "v", "partial", "T0", "W", "R0", "cols", "delta")

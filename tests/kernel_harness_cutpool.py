@@ -1,5 +1,5 @@
-"""Helper module of the kernel tests of the cut pool (not collected by pytest): the ctypes binding of
-tests/kernels/librelp_kernel_harness_cutpool.so, the reference model of launch_cutpool_separate and launch_cutpool_add_operands in
+"""Helper module of the kernel tests of the cut pool (not collected by pytest): the calls of
+tests/kernels/harness_cutpool.cpp (through tests/kernel_harness.py), the reference model of launch_cutpool_separate and launch_cutpool_add_operands in
 the orders relp_kernels.h states, and the construction of the device images a case starts from and must end with.
 
 Reference arithmetic: `kernel_harness.fma_exact` (the Fraction fma) chains.
@@ -17,33 +17,19 @@ The sliced-ELL image is packed by kernel_harness_pool.pack_ell, independently of
 a test may store a hole (column -1, any value) anywhere."""
 from __future__ import annotations
 
-import ctypes as C
-import os
-import subprocess
-
 import numpy as np
 
 import kernel_harness as kh
 import kernel_harness_pool as khp
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "kernels", "librelp_kernel_harness_cutpool.so")
 SLICE, CHUNK = khp.SLICE, khp.CHUNK
-_lib = None
-diff_images = khp.diff_images
+diff_images = kh.diff_images
 segment_size, segment_chunks = khp.segment_size, khp.segment_chunks
 
 
-def load():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            made = subprocess.run(["make", "-C", os.path.dirname(LIB_PATH), "-f", "cutpool.mk", "ARCH=gfx950"], capture_output=True, text=True)
-            if made.returncode or not os.path.exists(LIB_PATH):
-                raise FileNotFoundError(f"{LIB_PATH} is missing and make -C tests/kernels -f cutpool.mk failed: run build()\n{made.stderr[-2000:]}")
-        _lib = C.CDLL(LIB_PATH)
-        assert (_lib.rkcutpool_slice(), _lib.rkcutpool_chunk()) == (SLICE, CHUNK)
-    return _lib
+def _check_constants():
+    lib = kh.load()
+    assert (lib.rkcutpool_slice(), lib.rkcutpool_chunk()) == (SLICE, CHUNK)
 
 
 def norm_of(cut):
@@ -158,7 +144,7 @@ class Case:
 
     def separate(self, segments, tol, by_efficacy=0, lengths=None):
         img = self.separate_images(segments)
-        _launch("rkcutpool_separate", [self.count, self.m, self.nr_normal, segments, by_efficacy], [C.c_double(tol)], img,
+        _launch("rkcutpool_separate", [self.count, self.m, self.nr_normal, segments, by_efficacy], [tol], img,
                 ("slice_ptr", "col", "val", "rhs", "norm", "active", "basis", "b", "x", "s_all", "part_d", "part_k", "out_k", "out_s", "found"),
                 lengths)
         return img
@@ -217,19 +203,5 @@ class Case:
 
 def _launch(name, scalars, reals, img, names, lengths):
     """One harness call on the images; `lengths` overrides the length passed for an image (the refusal tests)."""
-    lib = load()
-    sticky = lib.rkcutpool_sticky_error()
-    if sticky:
-        raise kh.HarnessFault(f"an earlier harness call failed with HIP error {sticky - kh.HIP_ERROR_BASE}; nothing is launched any more")
-    args = [C.c_int64(int(s)) for s in scalars] + list(reals)
-    for n in names:
-        a = img[n]
-        assert a.flags["C_CONTIGUOUS"]
-        args += [C.c_void_p(a.ctypes.data), C.c_int64((lengths or {}).get(n, a.size))]
-    fn = getattr(lib, name)
-    fn.restype = C.c_int
-    rc = fn(*args)
-    if rc < 0:
-        raise kh.HarnessRefused(rc)
-    if rc:
-        raise kh.HarnessFault(f"{name}: HIP error {rc - kh.HIP_ERROR_BASE}")
+    _check_constants()
+    kh._call(name, scalars, {n: img[n] for n in names}, reals, lengths)

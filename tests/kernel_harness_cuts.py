@@ -1,5 +1,5 @@
-"""Helper module of the kernel tests of the in-place cut rows (not collected by pytest): the ctypes binding of
-tests/kernels/librelp_kernel_harness_cuts.so, the reference model of launch_tab_add_cuts in the summation order relp_kernels.h
+"""Helper module of the kernel tests of the in-place cut rows (not collected by pytest): the calls of
+tests/kernels/harness_cuts.cpp (through tests/kernel_harness.py), the reference model of launch_tab_add_cuts in the summation order relp_kernels.h
 states, and the construction of the device images a case starts from and must end with.
 
 Reference arithmetic: `kernel_harness.fma_vec` (held to `fma_exact`, the Fraction fma, by tests/test_kernel_models.py) over vectors,
@@ -14,30 +14,12 @@ coef[e][k], g[sp][k] (structural column sp, cut k).  `Case.images()` lays them i
 the sentinels of kernel_harness everywhere else; `Case.expected()` is every image after the launch."""
 from __future__ import annotations
 
-import ctypes as C
-import os
-import subprocess
-
 import numpy as np
 
 import kernel_harness as kh
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "kernels", "librelp_kernel_harness_cuts.so")
 CUT_TILE = 8
-_lib = None
-
-
-def load():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            made = subprocess.run(["make", "-C", os.path.dirname(LIB_PATH), "-f", "cuts.mk", "ARCH=gfx950"], capture_output=True, text=True)
-            if made.returncode or not os.path.exists(LIB_PATH):
-                raise FileNotFoundError(f"{LIB_PATH} is missing and make -C tests/kernels -f cuts.mk failed: run build()\n{made.stderr[-2000:]}")
-        _lib = C.CDLL(LIB_PATH)
-        assert _lib.rkc_cut_tile() == CUT_TILE
-    return _lib
+image_bits, diff_images = kh.image_bits, kh.diff_images
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -174,43 +156,11 @@ class Case:
 
     def launch(self):
         """The images after rkc_tab_add_cuts."""
-        lib = load()
-        sticky = lib.rkc_sticky_error()
-        if sticky:
-            raise kh.HarnessFault(f"an earlier harness call failed with HIP error {sticky - kh.HIP_ERROR_BASE}; nothing is launched any more")
+        assert kh.load().rkc_cut_tile() == CUT_TILE
         img = self.images()
         scalars = [self.m, self.n_owned, self.c_lo, self.col_off, self.p, self.kmax, self.batch, self.count, self.entries, self.ld_t, self.ld_b,
                    self.ld_r, self.ld_a, self.a_row0, self.struct_c0, self.nr_normal, self.first_virtual]
-        args = [C.c_int64(int(s)) for s in scalars]
-        for name in ("T0", "W", "R0", "d", "cost_store", "in_basis", "idcol", "basis", "pos_of_row", "vrow0", "vrow1", "vsign", "A", "rows",
-                     "coef", "u"):
-            a = img[name]
-            assert a.flags["C_CONTIGUOUS"]
-            args += [C.c_void_p(a.ctypes.data), C.c_int64(a.size)]
-        lib.rkc_tab_add_cuts.restype = C.c_int
-        rc = lib.rkc_tab_add_cuts(*args)
-        if rc < 0:
-            raise kh.HarnessRefused(rc)
-        if rc:
-            raise kh.HarnessFault(f"rkc_tab_add_cuts: HIP error {rc - kh.HIP_ERROR_BASE}")
+        names = ("T0", "W", "R0", "d", "cost_store", "in_basis", "idcol", "basis", "pos_of_row", "vrow0", "vrow1", "vsign", "A",
+                 "rows", "coef", "u")
+        kh._call("rkc_tab_add_cuts", scalars, {name: img[name] for name in names})
         return img
-
-
-def image_bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64) if a.dtype == np.float64 else a
-
-
-def diff_images(got, want, limit=5):
-    """Every returned image against the expected one, bit for bit (the sentinels included: what the launch must not write)."""
-    problems = []
-    for name in want:
-        g, w = image_bits(got[name]), image_bits(want[name])
-        if g.shape != w.shape:
-            problems.append(f"{name}: {g.shape} words returned, {w.shape} expected")
-            continue
-        bad = np.flatnonzero(g != w)
-        if bad.size:
-            shown = ", ".join(f"[{int(x)}] {got[name].reshape(-1)[x]!r} != {want[name].reshape(-1)[x]!r}" for x in bad[:limit])
-            problems.append(f"{name}: {bad.size} words differ: {shown}")
-    return problems

@@ -1,5 +1,5 @@
-"""Helper module of the kernel tests of the Gomory cuts (not collected by pytest): the ctypes binding of
-tests/kernels/librelp_kernel_harness_gomory.so, the cases of launch_tab_gomory, the f64 model in the order relp_kernels.h states
+"""Helper module of the kernel tests of the Gomory cuts (not collected by pytest): the calls of
+tests/kernels/harness_gomory.cpp (through tests/kernel_harness.py), the cases of launch_tab_gomory, the f64 model in the order relp_kernels.h states
 (tests/gomory_reference.py: pi_f64, structural_f64 over kernel_harness.model_rows_of_T / model_pending(order="tree")) and the same
 over Fractions.
 
@@ -9,10 +9,7 @@ j = c - col_off; structural sp = j < nr_normal; virtual v = j - nr_normal.  `Cas
 case's pitches and the sentinels of kernel_harness everywhere else and behind every output."""
 from __future__ import annotations
 
-import ctypes as C
 import math
-import os
-import subprocess
 from fractions import Fraction
 
 import numpy as np
@@ -20,23 +17,8 @@ import numpy as np
 import gomory_reference as gr
 import kernel_harness as kh
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "kernels", "librelp_kernel_harness_gomory.so")
 TAIL = 64                                # sentinel words behind every output
 TOL_ZERO = 1e-11
-_lib = None
-
-
-def load():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            made = subprocess.run(["make", "-C", os.path.dirname(LIB_PATH), "-f", "gomory.mk", "ARCH=gfx950"], capture_output=True, text=True)
-            if made.returncode or not os.path.exists(LIB_PATH):
-                raise FileNotFoundError(f"{LIB_PATH} is missing and make -C tests/kernels -f gomory.mk failed: run build()\n{made.stderr[-2000:]}")
-        _lib = C.CDLL(LIB_PATH)
-        assert _lib.rkg_chunk() == kh.RATIO_CHUNK
-    return _lib
 
 
 class Case:
@@ -187,24 +169,13 @@ class Case:
 
     def launch(self):
         """The images after rkg_tab_gomory."""
-        lib = load()
-        sticky = lib.rkg_sticky_error()
-        if sticky:
-            raise kh.HarnessFault(f"an earlier harness call failed with HIP error {sticky - kh.HIP_ERROR_BASE}; nothing is launched any more")
+        assert kh.load().rkg_chunk() == kh.RATIO_CHUNK
         img = self.images()
         scalars = [self.m, self.n_owned, self.c_lo, self.col_off, self.p, self.kmax, self.batch, self.count, self.kind, self.ld_t, self.ld_b,
                    self.ld_r, self.ld_a, self.mc, self.cuts, self.cut_row0, self.nn, self.nv, 0 if self.is_integer is None else 1]
-        args = [C.c_int64(int(s)) for s in scalars] + [C.c_double(self.tol_zero)]
-        for name in ("T0", "W", "R0", "in_basis", "is_integer", "vrow0", "vsign", "bound_row", "A", "rows", "f0", "pi", "y", "bad", "g"):
-            a = img[name]
-            assert a.flags["C_CONTIGUOUS"]
-            args += [C.c_void_p(a.ctypes.data), C.c_int64(a.size)]
-        lib.rkg_tab_gomory.restype = C.c_int
-        rc = lib.rkg_tab_gomory(*args)
-        if rc < 0:
-            raise kh.HarnessRefused(rc)
-        if rc:
-            raise kh.HarnessFault(f"rkg_tab_gomory: HIP error {rc - kh.HIP_ERROR_BASE}")
+        names = ("T0", "W", "R0", "in_basis", "is_integer", "vrow0", "vsign", "bound_row", "A", "rows", "f0", "pi", "y", "bad",
+                 "g")
+        kh._call("rkg_tab_gomory", scalars, {name: img[name] for name in names}, reals=[self.tol_zero])
         return img
 
     def compare(self, img):

@@ -1,5 +1,5 @@
-"""Helper module of the kernel tests of the column pool (not collected by pytest): the ctypes binding of
-tests/kernels/librelp_kernel_harness_pool.so, the reference model of launch_pool_price and launch_pool_add_operands in the orders
+"""Helper module of the kernel tests of the column pool (not collected by pytest): the calls of
+tests/kernels/harness_pool.cpp (through tests/kernel_harness.py), the reference model of launch_pool_price and launch_pool_add_operands in the orders
 relp_kernels.h states, and the construction of the device images a case starts from and must end with.
 
 Reference arithmetic: `kernel_harness.fma_exact` (the Fraction fma) chains.
@@ -14,30 +14,17 @@ The sliced-ELL image is packed here independently of relp_pool.hpp: column k is 
 slice_ptr[k // 64] + e * 64 + k % 64.  A column is a list of (row, value); a test may store a hole (row -1, any value) anywhere."""
 from __future__ import annotations
 
-import ctypes as C
-import os
-import subprocess
-
 import numpy as np
 
 import kernel_harness as kh
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "kernels", "librelp_kernel_harness_pool.so")
 SLICE, CHUNK = 64, 256
-_lib = None
+diff_images = kh.diff_images
 
 
-def load():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            made = subprocess.run(["make", "-C", os.path.dirname(LIB_PATH), "-f", "pool.mk", "ARCH=gfx950"], capture_output=True, text=True)
-            if made.returncode or not os.path.exists(LIB_PATH):
-                raise FileNotFoundError(f"{LIB_PATH} is missing and make -C tests/kernels -f pool.mk failed: run build()\n{made.stderr[-2000:]}")
-        _lib = C.CDLL(LIB_PATH)
-        assert (_lib.rkpool_slice(), _lib.rkpool_chunk()) == (SLICE, CHUNK)
-    return _lib
+def _check_constants():
+    lib = kh.load()
+    assert (lib.rkpool_slice(), lib.rkpool_chunk()) == (SLICE, CHUNK)
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -163,7 +150,7 @@ class Case:
 
     def price(self, segments, tol, write_d=True, lengths=None):
         img = self.price_images(segments, write_d)
-        _launch("rkpool_price", [self.count, self.m, self.n_store, segments], [C.c_double(tol)], img,
+        _launch("rkpool_price", [self.count, self.m, self.n_store, segments], [tol], img,
                 ("slice_ptr", "row", "val", "cost", "active", "d", "cost_store", "idcol", "minus_pi", "d_all", "part_d", "part_k", "out_k", "out_d", "found"),
                 lengths)
         return img
@@ -225,39 +212,5 @@ def set_active(active, ids, flag):
 
 def _launch(name, scalars, reals, img, names, lengths):
     """One harness call on the images; `lengths` overrides the length passed for an image (the refusal tests)."""
-    lib = load()
-    sticky = lib.rkpool_sticky_error()
-    if sticky:
-        raise kh.HarnessFault(f"an earlier harness call failed with HIP error {sticky - kh.HIP_ERROR_BASE}; nothing is launched any more")
-    args = [C.c_int64(int(s)) for s in scalars] + list(reals)
-    for n in names:
-        a = img[n]
-        assert a.flags["C_CONTIGUOUS"]
-        args += [C.c_void_p(a.ctypes.data), C.c_int64((lengths or {}).get(n, a.size))]
-    fn = getattr(lib, name)
-    fn.restype = C.c_int
-    rc = fn(*args)
-    if rc < 0:
-        raise kh.HarnessRefused(rc)
-    if rc:
-        raise kh.HarnessFault(f"{name}: HIP error {rc - kh.HIP_ERROR_BASE}")
-
-
-def image_bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64) if a.dtype == np.float64 else a
-
-
-def diff_images(got, want, limit=5):
-    """Every returned image against the expected one, bit for bit (the sentinels included: what the launch must not write)."""
-    problems = []
-    for name in want:
-        g, w = image_bits(got[name]), image_bits(want[name])
-        if g.shape != w.shape:
-            problems.append(f"{name}: {g.shape} words returned, {w.shape} expected")
-            continue
-        bad = np.flatnonzero(g != w)
-        if bad.size:
-            shown = ", ".join(f"[{int(x)}] {got[name].reshape(-1)[x]!r} != {want[name].reshape(-1)[x]!r}" for x in bad[:limit])
-            problems.append(f"{name}: {bad.size} words differ: {shown}")
-    return problems
+    _check_constants()
+    kh._call(name, scalars, {n: img[n] for n in names}, reals, lengths)

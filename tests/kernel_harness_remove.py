@@ -1,5 +1,5 @@
-"""Helper module of the kernel tests of the rows and columns removed in place (not collected by pytest): the ctypes binding of
-tests/kernels/librelp_kernel_harness_remove.so (one launch_tab_compact on an image the test constructs) and the list of cases the
+"""Helper module of the kernel tests of the rows and columns removed in place (not collected by pytest): the calls of
+tests/kernels/harness_remove.cpp (through tests/kernel_harness.py) (one launch_tab_compact on an image the test constructs) and the list of cases the
 CPU model test and the GPU test share.  The reference and the in-place model are in tests/remove_reference.py.
 
 A case is (m, n, rows, cols): m x n live entries in an image with 3 room rows (pitch rounded up to even) and 2 room columns, all
@@ -7,31 +7,12 @@ sentinels.  "moved" below = the surviving rows below the first removed one, the 
 is 256 B of them, B = 4 as shipped or 1."""
 from __future__ import annotations
 
-import ctypes as C
-import os
-import subprocess
-
 import numpy as np
 
 import kernel_harness as kh
 import remove_reference as rr
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "kernels", "librelp_kernel_harness_remove.so")
 BATCHES = (rr.SHIPPED_B, 1)
-_lib = None
-
-
-def load():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            made = subprocess.run(["make", "-C", os.path.dirname(LIB_PATH), "-f", "remove.mk", "ARCH=gfx950"], capture_output=True, text=True)
-            if made.returncode or not os.path.exists(LIB_PATH):
-                raise FileNotFoundError(f"{LIB_PATH} is missing and make -C tests/kernels -f remove.mk failed: run build()\n{made.stderr[-2000:]}")
-        _lib = C.CDLL(LIB_PATH)
-        assert _lib.rkrm_batch() == rr.SHIPPED_B
-    return _lib
 
 
 def _one_row(moved, above=3):
@@ -68,19 +49,10 @@ def image_of(case, seed=0):
 
 def launch(img, m, n, rows, cols, batch=rr.SHIPPED_B):
     """The image after rkrm_tab_compact (a copy; img stays)."""
-    lib = load()
-    sticky = lib.rkrm_sticky_error()
-    if sticky:
-        raise kh.HarnessFault(f"an earlier harness call failed with HIP error {sticky - kh.HIP_ERROR_BASE}; nothing is launched any more")
+    assert kh.load().rkrm_batch() == rr.SHIPPED_B
     out = np.ascontiguousarray(np.array(img, dtype=np.float64, copy=True))
     r, c = np.ascontiguousarray(rows, dtype=np.int32), np.ascontiguousarray(cols, dtype=np.int32)
-    lib.rkrm_tab_compact.restype = C.c_int
-    rc = lib.rkrm_tab_compact(C.c_int64(m), C.c_int64(n), C.c_int64(out.shape[1]), C.c_int64(batch), C.c_void_p(out.ctypes.data), C.c_int64(out.size),
-                              C.c_void_p(r.ctypes.data), C.c_int64(r.size), C.c_void_p(c.ctypes.data), C.c_int64(c.size))
-    if rc < 0:
-        raise kh.HarnessRefused(rc)
-    if rc:
-        raise kh.HarnessFault(f"rkrm_tab_compact: HIP error {rc - kh.HIP_ERROR_BASE}")
+    kh._call("rkrm_tab_compact", [m, n, out.shape[1], batch], [out, r, c])
     return out
 
 

@@ -1,5 +1,5 @@
-"""Helper module of the kernel test of the trial snapshot (not collected by pytest): the ctypes binding of
-tests/kernels/librelp_kernel_harness_trial.so and the image a case is laid out in.
+"""Helper module of the kernel test of the trial snapshot (not collected by pytest): the call of
+tests/kernels/harness_trial.cpp (through tests/kernel_harness.py) and the image a case is laid out in.
 
 One image of bytes holds every source and every destination of a table.  A region starts at a 16-byte-aligned offset; the 8 bytes
 before it and the 8 bytes right behind its last byte (not behind its last 16-byte unit: a store that rounds a tail up would hit
@@ -9,34 +9,19 @@ the canaries, the sources and the gaps are all covered by one comparison."""
 from __future__ import annotations
 
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "kernels", "librelp_kernel_harness_trial.so")
+import kernel_harness as kh
+
 UNIT = 16
 CANARY = 8
-_lib = None
-
-
-def load():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            made = subprocess.run(["make", "-C", os.path.dirname(LIB_PATH), "-f", "trial.mk", "ARCH=gfx950"], capture_output=True, text=True)
-            if made.returncode or not os.path.exists(LIB_PATH):
-                raise FileNotFoundError(f"{LIB_PATH} is missing and make -C tests/kernels -f trial.mk failed: run build()\n{made.stderr[-2000:]}")
-        _lib = C.CDLL(LIB_PATH)
-        _lib.rkt_trial_copy.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
-        assert _lib.rkt_max_segments() == 32
-    return _lib
+MAX_SEGMENTS = 32                        # kTrialMaxSegments
 
 
 def grid_units():
     """16-byte units one workgroup per 256 covers before the grid is capped."""
-    return load().rkt_grid() * 256
+    return kh.load().rkt_grid() * 256
 
 
 class Case:
@@ -65,8 +50,9 @@ class Case:
         for s, d, n in zip(src, dst, self.lengths):
             want[d:d + n] = image[s:s + n]
         got = np.ascontiguousarray(image.copy())
-        code = load().rkt_trial_copy(got.ctypes.data, got.size, len(self.lengths), src.ctypes.data, dst.ctypes.data, self.lengths.ctypes.data)
-        assert code == 0, f"rkt_trial_copy returned {code}"
+        assert kh.load().rkt_max_segments() == MAX_SEGMENTS
+        kh.invoke("rkt_trial_copy", C.c_void_p(got.ctypes.data), C.c_int64(got.size), C.c_int64(len(self.lengths)),
+                  *(C.c_void_p(a.ctypes.data) for a in (src, dst, self.lengths)))
         return got, want
 
 

@@ -12,49 +12,30 @@
 //     R0's scratch row, R0c and cols) are filled with the quiet NaN kSentinel before the upload; the WHOLE of every buffer
 //     comes back so that the test sees what was written;
 //   * refusals (negative return codes) happen before any HIP call; every list index an entry accepts is in range;
-//   * the first HIP error is sticky: every later entry returns kHipErrorBase + that error without touching the GPU.
+//   * the first HIP error is sticky for the whole library (harness_common.hpp): every later entry of every family returns
+//     kHipErrorBase + that error without touching the GPU.
 //
 // Layouts of the logical arrays (C order): T0[c][i] (n_owned x m), W[j][i] (p x m), R0[j][c] (p x n_owned),
 // Binv[i][j] (m x m).  Returned device images: T0 n_owned x ld_t, W kmax x ld_b, R0 (kmax + 1) x ld_r, Binv m x ld_b.
 //
-// Adding a launcher: write one entry that checks its arguments with the REFUSE_* macros first, builds the device images with
-// Dev<T> (pad_rows / fill), calls the launcher with stream 0, and downloads every buffer with `back`.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+// A new kernel family gets a harness as one source file harness_<family>.cpp beside this one that includes harness_common.hpp
+// (every entry: `if (g_sticky) return g_sticky;`, the REFUSE_* checks, then Image<T> / Dev<T>, the launcher on stream 0, and every
+// buffer back), its name in SRCS of the Makefile, and one Python module tests/kernel_harness_<family>.py over tests/kernel_harness.py.
 #include <string.h>
 
 #include <algorithm>
-#include <vector>
 
-#include "relp_kernels.h"
+#include "harness_common.hpp"
 
 using namespace relp;
 
 namespace {
 
-constexpr int kRefusedShape = -1;    // m < 1, n_owned < 1, p < 0, p > kmax, kmax > 128
-constexpr int kRefusedIndex = -2;    // a row or column index out of range
-constexpr int kRefusedBatch = -3;    // a batch tab_load_batch would remap
-constexpr int kRefusedLength = -4;   // a wrong array length
-constexpr int kRefusedSplits = -5;   // splits < 1 or beyond min(count, the launcher's maximum)
-constexpr int kRefusedOrder = -6;    // a list that is not strictly ascending, a repeated basis entry, a direct term on a basic column
-constexpr int kHipErrorBase = 1000;  // + hipError_t of the first failed HIP call (sticky)
-
 constexpr uint64_t kSentinelBits = 0x7ff80000c0ffee01ull;
 constexpr int32_t kSentinelInt = -0x5a5a5a5b;
 
-int g_sticky = 0;
-
 inline int64_t round_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 inline double sentinel() { double d; memcpy(&d, &kSentinelBits, 8); return d; }
-
-#define HIP_OK(call)                                                                 \
-    do {                                                                             \
-        hipError_t e_ = (call);                                                      \
-        if (e_ != hipSuccess) { g_sticky = kHipErrorBase + (int)e_; return g_sticky; } \
-    } while (0)
-#define REFUSE_IF(cond, code) do { if (cond) return (code); } while (0)
-#define REFUSE_LEN(len, want) do { if ((int64_t)(len) != (int64_t)(want)) return kRefusedLength; } while (0)
 
 // a device buffer with its host image; freed on scope exit
 template <class T>
@@ -78,7 +59,6 @@ struct Dev {
         return 0;
     }
 };
-#define TRY(expr) do { int rc_ = (expr); if (rc_) return rc_; } while (0)
 
 // rows x cols logical (row-major, `cols` contiguous) into an image of total_rows x ld, the rest = fill
 void pad_rows(std::vector<double>& img, const double* src, int64_t rows, int64_t cols, int64_t ld, int64_t total_rows, double fill) {

@@ -1,12 +1,12 @@
 // The kernel harness of the cut pool (test infrastructure): extern "C" entries that run relp::launch_cutpool_separate and
 // relp::launch_cutpool_add_operands of the shipped librelp_engine.so once on whole device IMAGES a test constructs
-// (tests/kernel_harness_cutpool.py) and hand every image back.  `make -C tests/kernels -f cutpool.mk`
+// (tests/kernel_harness_cutpool.py) and hand every image back.  `make -C tests/kernels`
 //
 // The caller owns the layout: every buffer is passed as the image the device shall hold (its own sentinels where the launch must
 // not write).  This file only checks that nothing the launch may touch lies outside an image -- a refused call (negative code)
-// launches nothing -- uploads, launches, synchronises and downloads.  A HIP error is returned as 1000 + code and is sticky: nothing
-// is launched any more in this process.
-#include "harness_pool_common.hpp"
+// launches nothing -- uploads, launches, synchronises and downloads.  A HIP error is returned as 1000 + code and is sticky for the
+// whole library (harness_common.hpp): nothing is launched any more in this process.
+#include "harness_common.hpp"
 
 using namespace relp;
 
@@ -37,7 +37,6 @@ int check_pool(const CutPoolArgs& a) {
 
 extern "C" {
 
-int rkcutpool_sticky_error() { return g_sticky; }
 int rkcutpool_slice() { return kPoolSlice; }
 int rkcutpool_chunk() { return kPoolChunk; }
 

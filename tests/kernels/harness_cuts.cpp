@@ -1,47 +1,18 @@
 // The kernel harness of the in-place cut rows (test infrastructure): one extern "C" entry that runs relp::launch_tab_add_cuts of the
 // shipped librelp_engine.so once on whole device IMAGES a test constructs (tests/kernel_harness_cuts.py) and hands every image
-// back.  `make -C tests/kernels -f cuts.mk`
+// back.  `make -C tests/kernels`
 //
 // The caller owns the layout: it passes the pitches and every buffer as the image the device shall hold (its own sentinels where
 // the launch must not write).  This file only checks that nothing the launch may touch lies outside an image -- a refused call
 // (negative code) launches nothing -- uploads, launches, synchronises and downloads.  A HIP error is returned as 1000 + code and is
-// sticky: nothing is launched any more in this process.
-#include <hip/hip_runtime.h>
+// sticky for the whole library (harness_common.hpp): nothing is launched any more in this process.
 
-#include <cstdint>
-#include <vector>
-
-#include "relp_kernels.h"
+#include "harness_common.hpp"
 
 using namespace relp;
 
-namespace {
-
-constexpr int kRefusedShape = -1, kRefusedIndex = -2, kRefusedBatch = -3, kRefusedLength = -4;
-constexpr int kHipErrorBase = 1000;
-int g_sticky = 0;
-
-#define REFUSE_IF(cond, code) do { if (cond) return (code); } while (0)
-#define HIP_OK(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) { g_sticky = kHipErrorBase + (int)e_; return g_sticky; } } while (0)
-
-// a device copy of a host image; freed on every way out
-template <class T>
-struct Image {
-    T* d = nullptr; T* h; int64_t n;
-    Image(T* host, int64_t len) : h(host), n(len) {}
-    ~Image() { if (d) (void)hipFree(d); }
-    hipError_t up() {
-        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), sizeof(T) * (size_t)(n > 0 ? n : 1));
-        return (e != hipSuccess || n == 0) ? e : hipMemcpy(d, h, sizeof(T) * (size_t)n, hipMemcpyHostToDevice);
-    }
-    hipError_t back() { return n == 0 ? hipSuccess : hipMemcpy(h, d, sizeof(T) * (size_t)n, hipMemcpyDeviceToHost); }
-};
-
-}  // namespace
-
 extern "C" {
 
-int rkc_sticky_error() { return g_sticky; }
 int rkc_cut_tile() { return kTabCutTile; }
 
 // launch_tab_add_cuts on the view (m rows, owned stored columns [c_lo, c_lo + n_owned) = all up to n_store, tableau columns from

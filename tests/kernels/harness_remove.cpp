@@ -1,46 +1,18 @@
 // The kernel harness of the rows and columns removed in place (test infrastructure): one extern "C" entry that runs
 // relp::launch_tab_compact of the shipped librelp_engine.so once on a whole device IMAGE a test constructs
-// (tests/kernel_harness_remove.py) and hands the image back.  `make -C tests/kernels -f remove.mk`
+// (tests/kernel_harness_remove.py) and hands the image back.  `make -C tests/kernels`
 //
 // The caller owns the layout: it passes the pitch and the image as the device shall hold it (its own sentinels where the launch must
 // not write).  This file only checks that nothing the launch may touch lies outside the image -- a refused call (negative code)
-// launches nothing -- uploads, launches, synchronises and downloads.  A HIP error is returned as 1000 + code and is sticky: nothing
-// is launched any more in this process.
-#include <hip/hip_runtime.h>
+// launches nothing -- uploads, launches, synchronises and downloads.  A HIP error is returned as 1000 + code and is sticky for the
+// whole library (harness_common.hpp): nothing is launched any more in this process.
 
-#include <cstdint>
-
-#include "relp_kernels.h"
+#include "harness_common.hpp"
 
 using namespace relp;
 
-namespace {
-
-constexpr int kRefusedShape = -1, kRefusedIndex = -2, kRefusedBatch = -3, kRefusedLength = -4;
-constexpr int kHipErrorBase = 1000;
-int g_sticky = 0;
-
-#define REFUSE_IF(cond, code) do { if (cond) return (code); } while (0)
-#define HIP_OK(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) { g_sticky = kHipErrorBase + (int)e_; return g_sticky; } } while (0)
-
-// a device copy of a host image; freed on every way out
-template <class T>
-struct Image {
-    T* d = nullptr; T* h; int64_t n;
-    Image(T* host, int64_t len) : h(host), n(len) {}
-    ~Image() { if (d) (void)hipFree(d); }
-    hipError_t up() {
-        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), sizeof(T) * (size_t)(n > 0 ? n : 1));
-        return (e != hipSuccess || n == 0) ? e : hipMemcpy(d, h, sizeof(T) * (size_t)n, hipMemcpyHostToDevice);
-    }
-    hipError_t back() { return n == 0 ? hipSuccess : hipMemcpy(h, d, sizeof(T) * (size_t)n, hipMemcpyDeviceToHost); }
-};
-
-}  // namespace
-
 extern "C" {
 
-int rkrm_sticky_error() { return g_sticky; }
 int rkrm_batch() { return kTabCompactB; }
 
 // launch_tab_compact on the image img (img_len = ld x the columns the image has, at least n): m rows and n columns are live, the

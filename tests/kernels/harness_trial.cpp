@@ -1,33 +1,17 @@
 // The kernel harness of the trial snapshot (test infrastructure): one extern "C" entry that runs relp::launch_tab_trial_copy of the
 // shipped librelp_engine.so once on ONE device image a test constructs (tests/kernel_harness_trial.py) and hands the image back.
-// `make -C tests/kernels -f trial.mk`
+// `make -C tests/kernels`
 //
 // The caller owns the layout: the segments are (source offset, destination offset, bytes) inside the image, and whatever lies
 // between them is the caller's canaries.  This file only checks that nothing the launch may touch lies outside the image, that
 // every offset is 16-byte aligned and that no destination overlaps another segment's bytes -- a refused call (negative code)
-// launches nothing --, uploads, launches, synchronises and downloads.  A HIP error is returned as 1000 + code and is sticky:
-// nothing is launched any more in this process.
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
-
-#include "relp_kernels.h"
+// launches nothing --, uploads, launches, synchronises and downloads.  A HIP error is returned as 1000 + code and is sticky
+// for the whole library (harness_common.hpp): nothing is launched any more in this process.
+#include "harness_common.hpp"
 
 using namespace relp;
 
 namespace {
-
-constexpr int kRefusedShape = -1, kRefusedIndex = -2, kRefusedOverlap = -3;
-constexpr int kHipErrorBase = 1000;
-int g_sticky = 0;
-
-#define REFUSE_IF(cond, code) do { if (cond) return (code); } while (0)
-#define HIP_OK(expr) do { const hipError_t e_ = (expr); if (e_ != hipSuccess) { g_sticky = kHipErrorBase + (int)e_; return g_sticky; } } while (0)
-
-struct Image {
-    uint8_t* d = nullptr;
-    ~Image() { if (d) (void)hipFree(d); }
-};
 
 bool overlap(int64_t a, int64_t a_len, int64_t b, int64_t b_len) { return a_len > 0 && b_len > 0 && a < b + b_len && b < a + a_len; }
 
@@ -35,7 +19,6 @@ bool overlap(int64_t a, int64_t a_len, int64_t b, int64_t b_len) { return a_len 
 
 extern "C" {
 
-int rkt_sticky_error() { return g_sticky; }
 int rkt_max_segments() { return kTrialMaxSegments; }
 int rkt_grid() { return kTabTrialGrid; }
 
@@ -53,10 +36,9 @@ int rkt_trial_copy(uint8_t* img, int64_t img_len, int64_t count, const int64_t* 
             REFUSE_IF(overlap(dst_off[s], bytes[s], dst_off[o], bytes[o]) || overlap(dst_off[s], bytes[s], src_off[o], bytes[o]), kRefusedOverlap);
         }
     }
-    Image image;
-    HIP_OK(hipMalloc(reinterpret_cast<void**>(&image.d), (size_t)img_len));
+    Image<uint8_t> image(img, img_len);
+    HIP_OK(image.up());
     REFUSE_IF(reinterpret_cast<uintptr_t>(image.d) % kTrialUnit != 0, kRefusedIndex);
-    HIP_OK(hipMemcpy(image.d, img, (size_t)img_len, hipMemcpyHostToDevice));
     TrialTable t;
     t.count = (int32_t)count;
     int64_t units = 0;
@@ -72,7 +54,7 @@ int rkt_trial_copy(uint8_t* img, int64_t img_len, int64_t count, const int64_t* 
     launch_tab_trial_copy(t, 0);
     HIP_OK(hipGetLastError());
     HIP_OK(hipDeviceSynchronize());
-    HIP_OK(hipMemcpy(img, image.d, (size_t)img_len, hipMemcpyDeviceToHost));
+    HIP_OK(image.back());
     return 0;
 }
 

@@ -1,39 +1,22 @@
 """tests/cpp/test_layout_cuts.cpp: Layout::add_cuts on the host (plain g++, no library) -- CPU tier, it runs here.
 tests/cpp/test_cuts.cpp: cut rows added in place through include/relp.hpp (add_cuts, reserve_cuts, run_dual, objective; the
-refusals) -- CPU tier: the program compiles and links against the library; GPU tier: it runs.  Both are built by tests/cpp/cuts.mk,
-a line of `__graft_entry__.build()`."""
-import os
-import subprocess
-
+refusals) -- CPU tier: the program compiles and links against the library; GPU tier: it runs.
+Both are built by tests/cpp/Makefile (`__graft_entry__.build()`)."""
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CPP = os.path.join(ROOT, "tests", "cpp")
-LAYOUT_BINARY = os.path.join(CPP, "test_layout_cuts")
-LAYOUT_MAKE = ["make", "-C", CPP, "-f", "cuts.mk", "test_layout_cuts"]
-BINARY = os.path.join(CPP, "test_cuts")
-MAKE = ["make", "-C", CPP, "-f", "cuts.mk"]
+import cpp_programs
 
 
 def test_layout_add_cuts_on_the_host():
-    subprocess.check_call(LAYOUT_MAKE, stdout=subprocess.DEVNULL)
-    res = subprocess.run([LAYOUT_BINARY], capture_output=True, text=True, timeout=60)
-    assert res.returncode == 0, res.stdout + res.stderr
-    assert " 0 failed" in res.stdout
+    cpp_programs.make_target("test_layout_cuts")
+    cpp_programs.run("test_layout_cuts", timeout=60)
 
 
 def test_cpp_cuts_test_compiles_and_links():
-    import rust_lp_amd  # noqa: F401  (builds the library when it is missing)
-    from rust_lp_amd import engine
-    engine.load_library()
-    subprocess.check_call(MAKE, stdout=subprocess.DEVNULL)
-    assert os.access(BINARY, os.X_OK)
+    cpp_programs.links_against_the_library("test_cuts")
 
 
 @pytest.mark.gpu
 def test_cpp_cuts_test_passes_on_the_gpu():
-    if not os.access(BINARY, os.X_OK):
-        subprocess.check_call(MAKE, stdout=subprocess.DEVNULL)
-    res = subprocess.run([BINARY], capture_output=True, text=True, timeout=300)
-    assert res.returncode == 0, res.stdout + res.stderr
-    assert " 0 failed" in res.stdout
+    cpp_programs.make_target("test_cuts", only_if_missing=True)
+    cpp_programs.run("test_cuts", timeout=300)

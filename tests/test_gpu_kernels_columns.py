@@ -1,4 +1,4 @@
-"""launch_tab_add_columns alone, through tests/kernels/librelp_kernel_harness_columns.so: single launches on constructed operands
+"""launch_tab_add_columns alone, through tests/kernels/harness_columns.cpp: single launches on constructed operands
 with sentinel-filled images, every returned image compared bit for bit with the model of tests/kernel_harness_columns.py -- the
 written columns, and everything outside them, behind m, n and the pitches, unchanged.
 

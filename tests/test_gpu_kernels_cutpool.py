@@ -1,4 +1,4 @@
-"""launch_cutpool_separate and launch_cutpool_add_operands alone, through tests/kernels/librelp_kernel_harness_cutpool.so: single
+"""launch_cutpool_separate and launch_cutpool_add_operands alone, through tests/kernels/harness_cutpool.cpp: single
 launches on constructed sliced-ELL pools with sentinel-filled images, every returned image compared bit for bit with the model of
 tests/kernel_harness_cutpool.py (Fraction fma chains, winners in the total order (key, index)) -- what is written, and everything
 outside it, unchanged.

@@ -1,4 +1,4 @@
-"""launch_tab_add_cuts alone, through tests/kernels/librelp_kernel_harness_cuts.so: single launches on constructed operands with
+"""launch_tab_add_cuts alone, through tests/kernels/harness_cuts.cpp: single launches on constructed operands with
 sentinel-filled images, every returned image compared bit for bit with the model of tests/kernel_harness_cuts.py -- the written rows
 and columns, and everything outside them, behind m, n and the pitches, unchanged.
 

@@ -1,4 +1,4 @@
-"""launch_pool_price, launch_pool_add_operands and launch_pool_set_active alone, through tests/kernels/librelp_kernel_harness_pool.so:
+"""launch_pool_price, launch_pool_add_operands and launch_pool_set_active alone, through tests/kernels/harness_pool.cpp:
 single launches on constructed sliced-ELL pools with sentinel-filled images, every returned image compared bit for bit with the
 model of tests/kernel_harness_pool.py (Fraction fma chains, winners in the total order (d, index)) -- what is written, and everything
 outside it, unchanged.

@@ -1,4 +1,4 @@
-"""launch_tab_compact alone, through tests/kernels/librelp_kernel_harness_remove.so: single launches on sentinel-filled images, the
+"""launch_tab_compact alone, through tests/kernels/harness_remove.cpp: single launches on sentinel-filled images, the
 returned image compared bit for bit with np.delete on its live part (tests/remove_reference.py: expected) -- the survivors in order
 with their bits, 0.0 in the vacated rows and columns, and the pitch padding, the room rows and the room columns untouched.
 
