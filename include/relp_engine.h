@@ -742,6 +742,13 @@ relp_status_t relp_retab_stats(const relp_engine_t *h, int64_t *out4);
 /* Tableau engine: how many of the p pending rows of an update block the per-pivot kernels load per memory round trip:
  * RELP_TAB_LOAD_BATCH at create if it was 1 (one by one), 8, 16 or 32, else the default.  Other engines: 0. */
 int32_t       relp_tab_load_batch(const relp_engine_t *h);
+/* Tableau engine: the rows one workgroup of the column kernel walks in the fused single-GPU loop (every other path: 256):
+ * RELP_TAB_COLUMN_ROWS at create if it was 256 (the control), 128 or 64; else 256 when the update block is above 64 pivots, and
+ * relp_tab_column_rows_for(0, m) for the m rows the tableau has at the call.  Other engines: 0. */
+int32_t       relp_tab_column_rows(const relp_engine_t *h);
+/* The choice itself (host code, no device): `wanted` if it is 256, 128 or 64, else the smallest of them with at most 256
+ * workgroups over m rows. */
+int32_t       relp_tab_column_rows_for(int32_t wanted, int32_t m);
 /* The block size K in effect (0 = explicit rank-1 updates; LU engine: pivots between refactorisations). */
 int32_t       relp_update_block(const relp_engine_t *h);
 /* RELP_ENGINE_LU only: statistics of the current factorisation, out[8] = { refactorisations so far, m,

@@ -171,6 +171,8 @@ relp_status_t relp_set_reinversion_interval(relp_engine_t* h, int64_t pivots) { 
 int64_t relp_reinversions(const relp_engine_t* h) { return h ? H(h).reinversions() : -1; }
 int32_t relp_update_block(const relp_engine_t* h) { return h ? H(h).update_block() : -1; }
 int32_t relp_tab_load_batch(const relp_engine_t* h) { return h ? H(h).tab_load_batch_size() : -1; }
+int32_t relp_tab_column_rows(const relp_engine_t* h) { return h ? H(h).tab_column_rows_size() : -1; }
+int32_t relp_tab_column_rows_for(int32_t wanted, int32_t m) { return relp::tab_column_rows(wanted, m); }
 relp_status_t relp_lu_stats(const relp_engine_t* h, int64_t* out8) { return (h && out8) ? H(h).lu_stats(out8) : RELP_E_ARG; }
 relp_status_t relp_lu_lookahead_stats(const relp_engine_t* h, int64_t* out4) { return (h && out4) ? H(h).lu_lookahead_stats(out4) : RELP_E_ARG; }
 relp_status_t relp_lu_kernel_layout(const relp_engine_t* h, int32_t* out4) { return (h && out4) ? H(h).lu_kernel_layout(out4) : RELP_E_ARG; }

@@ -97,6 +97,7 @@ Switches Switches::read() {
     s.tab_flush_all = num("RELP_TAB_FLUSH_ALL", 0) != 0;
     s.tab_load_batch = num("RELP_TAB_LOAD_BATCH", 0);
     s.tab_w_split = num("RELP_TAB_W_SPLIT", 0);
+    s.tab_column_rows = num("RELP_TAB_COLUMN_ROWS", 0);
     s.fused_update = num("RELP_FUSED_UPDATE", 1) != 0;
     s.lu_lookahead_set = given("RELP_LU_LOOKAHEAD");
     s.lu_lookahead = num("RELP_LU_LOOKAHEAD", 8);
@@ -258,6 +259,8 @@ relp_status_t Engine::create(const relp_matrix_data_t& md, const relp_config_t& 
             // rows that share W <- E W in the fused update: RELP_TAB_LOAD_BATCH, RELP_TAB_W_SPLIT
             load_batch_ = tab_load_batch(sw_.tab_load_batch);
             w_split_ = sw_.tab_w_split >= 1 ? std::min(sw_.tab_w_split, 16) : kTabSplitDefault;
+            // rows per workgroup of the column kernel in the fused single-GPU loop: RELP_TAB_COLUMN_ROWS (256 = the control)
+            col_rows_wanted_ = sw_.tab_column_rows;
         }
         {   // two launches per pivot instead of three in the single-GPU loop (RELP_FUSED_UPDATE=0: k_ratio_blocks + k_tab_update_all)
             fused_update_ = sw_.fused_update;               // (also the native sharded loop, relp_shard_run)
@@ -295,7 +298,7 @@ relp_status_t Engine::create(const relp_matrix_data_t& md, const relp_config_t& 
         HIP_TRY(d_pos_of_row_.alloc(lay_.m));
         HIP_TRY(d_pos_of_row_.fill_bytes(0xFF, lay_.m, stream_));               // -1 everywhere
     }
-    HIP_TRY(d_rmin_.alloc(lay_.m / 8 + 2));          // block minima of the ratio test (8 or 256 rows per block)
+    HIP_TRY(d_rmin_.alloc(lay_.m / 8 + 2));          // block minima of the ratio test (8, 64, 128 or 256 rows per block)
     HIP_TRY(h_rec_.alloc(sizeof(PivotRecord)));
     trace_cap_ = std::max(cfg_.trace_capacity, 0);
     if (trace_cap_ > 0) HIP_TRY(d_trace_.alloc(4 * trace_cap_));
@@ -418,13 +421,14 @@ void Engine::enqueue_price(int cost_mode, const double* vec, const PivotRecord* 
 // One pivot of the dense-tableau engine: 5 launches, O(K (m + n)) bytes.
 void Engine::enqueue_iteration_tableau(int rule) {
     const TableauView tv = tview();
-    const DeferredUpdate du = deferred();
+    DeferredUpdate du = deferred();
     const SelectPartials sp = tab_partials(rule);
     // 3 launches: [PRICE's final reduction + tableau column] -> [ratio test + block bookkeeping] ->
     // [tableau row / reduced costs / next PRICE partials  ||  W, b, basis]
     if (fused_update_ && in_loop_) {
         // 2 launches: [PRICE's final reduction + tableau column + block minima of the ratios] -> [ratio test in every
         // workgroup + tableau row / reduced costs / next PRICE partials || W, b, basis]
+        du.col_rows = tab_column_rows_size();              // this loop alone: every other caller of the two launches keeps 256
         prof_begin(RELP_K_FTRAN);
         launch_tab_select_column_rmin(tv, du, sp, tab_scan_blocks(lay_.sc_hi - lay_.sc_lo), d_alpha_, d_b_, tolerances(), d_rmin_,
                                       d_rec_, stream_, d_shadow_, d_shadow_meta_);

@@ -97,6 +97,7 @@ struct Switches {
     bool pivot_guard_set = false; double pivot_guard = 0.0;   // RELP_PIVOT_GUARD
     bool tab_flush_all = false;                           // RELP_TAB_FLUSH_ALL
     int tab_load_batch = 0, tab_w_split = 0;              // RELP_TAB_LOAD_BATCH, RELP_TAB_W_SPLIT (0: the default)
+    int tab_column_rows = 0;                              // RELP_TAB_COLUMN_ROWS (0: the default)
     bool fused_update = true;                             // RELP_FUSED_UPDATE
     bool lu_lookahead_set = false; int lu_lookahead = 8;  // RELP_LU_LOOKAHEAD
     int fuse_lanes = 256;                                 // RELP_FUSE_LANES
@@ -273,6 +274,13 @@ class Engine : private EngineQueue {
     relp_status_t tab_flush_stats(int64_t* out2);
     relp_status_t retab_stats(int64_t* out4) const;
     int32_t tab_load_batch_size() const { return tableau_ ? load_batch_ : 0; }
+    // for the rows the tableau has now (cut rows come and go); blocks above 64 pivots keep 256 unless a value was asked for:
+    // their shares need the larger register arrays, which nobody has measured
+    int32_t tab_column_rows_size() const {
+        if (!tableau_) return 0;
+        const bool asked = col_rows_wanted_ == 64 || col_rows_wanted_ == 128 || col_rows_wanted_ == 256;
+        return !asked && block_ > 64 ? 256 : tab_column_rows(col_rows_wanted_, lay_.m);
+    }
     relp_status_t get_trace(int32_t* phase, int32_t* entering, int32_t* row, int32_t* leaving, int64_t cap,
                             int64_t* count);
     relp_status_t check_basis(double* max_identity_error, double* max_basic_cost, double* min_b);
@@ -334,6 +342,7 @@ class Engine : private EngineQueue {
     FlushList flush_list() const;
     // RELP_TAB_LOAD_BATCH / RELP_TAB_W_SPLIT (relp_kernels.h: tab_load_batch, launch_tab_ratio_update_all)
     int32_t load_batch_ = 0, w_split_ = 0;
+    int32_t col_rows_wanted_ = 0;        // RELP_TAB_COLUMN_ROWS (tab_column_rows): the fused single-GPU loop's column kernel
     DeviceBuf<double> d_cost_store_;     // cost per stored column in the current phase
     DeviceBuf<int32_t> d_idcol_;         // stored column that was e_k originally, per row k
     // Ratio test + update in one launch (single-GPU loop, relp_kernels.h: launch_tab_ratio_update_all): the second copies of b
@@ -341,7 +350,7 @@ class Engine : private EngineQueue {
     bool fused_update_ = false, shadow_pending_ = false;
     DeviceBuf<double> d_b_alt_, d_shadow_;
     DeviceBuf<int32_t> d_basis_alt_, d_shadow_meta_;
-    DeviceBuf<double> d_rmin_;           // minimum ratio per block of 256 rows (k_tab_select_column -> k_ratio_blocks)
+    DeviceBuf<double> d_rmin_;           // minimum ratio per block of 256 (128, 64) rows (k_tab_select_column -> k_ratio_blocks)
     int32_t n_store_ = 0;                // stored columns = original artificials + provider columns
     int32_t tab_na_ = 0;                 // original number of artificial columns (their block is kept)
     bool tab_partials_valid_ = false;    // the PRICE partials describe the current d

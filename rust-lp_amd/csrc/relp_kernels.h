@@ -58,6 +58,7 @@ struct DeferredUpdate {
     double*  R;             // flush snapshot S' B0inv, kmax x ld (row j contiguous)
     int32_t  batch;         // tableau kernels: pending rows loaded per round trip (tab_load_batch; 0 = the default)
     int32_t  w_split;       // tableau fused update: workgroups per 256 rows of W <- E W, at most (0 or 1 = one)
+    int32_t  col_rows = 0;  // tableau column kernel with block minima: rows per workgroup and per minimum, 128 or 64 (else 256)
 };
 
 // Read-only description of the tableau's columns (Kind + MatrixData, partially.rs:72-80,
@@ -450,6 +451,10 @@ static constexpr int32_t kTabLoadBatchDefault = 8;
 static constexpr int32_t kTabSplitDefault = 2;
 static constexpr int32_t kTabSplitCUs = 256;
 int32_t tab_load_batch(int32_t wanted);
+// RELP_TAB_COLUMN_ROWS: the rows a workgroup of the column kernel walks in the fused single-GPU loop (DeferredUpdate::col_rows;
+// launch_tab_select_column_rmin and launch_tab_ratio_update_all read it, every other launch keeps 256).  256 (the control), 128
+// and 64 are themselves; anything else is the default for m rows.
+int32_t tab_column_rows(int32_t wanted, int32_t m);
 // flush: T0 += W R0 with v_mfma_f64_16x16x4_f64 tiles
 void launch_tab_flush(const TableauView& tv, const DeferredUpdate& du, const PivotRecord* rec, const FlushList& fl,
                       hipStream_t s);

@@ -347,25 +347,28 @@ __global__ __launch_bounds__(kThreads) void k_tab_update_all(TableauView tv, Def
 // the new row r of W goes to `shadow`, n_eta is read as p_now; the basis flags are read through the expression that is
 // the same for old and new flags; pos_of_row[r] reads as -1 or as the value it is about to get.  Same arithmetic as
 // k_ratio_blocks + k_tab_update_all, bit for bit.
-// `split` > 1: the W half has split * nblk workgroups, and workgroup part * nblk + wblock updates the rows of block wblock in
+// `rmin` holds nblk minima, one per RPB rows (what the column kernel walked per workgroup); the W half keeps blocks of 256 rows,
+// nb_w of them (RPB = 256: nblk of them).
+// `split` > 1: the W half has split * nb_w workgroups, and workgroup part * nb_w + wblock updates the rows of block wblock in
 // its share of the pending columns of W (the m x p entries are independent of each other).  Part 0 alone keeps b, the
 // basis array, the shadow row and the record; column jt gets its u from the part that holds it.
-template <int B>
+template <int B, int RPB>
 __global__ __launch_bounds__(kThreads) void k_tab_ratio_update_all(TableauView tv, DeferredUpdate du, SelectPartials sp, int nb_row,
                                                                    int m, const double* alpha,
                                                                    const double* __restrict__ b_in, double* __restrict__ b_out,
                                                                    const int32_t* __restrict__ basis_in,
                                                                    int32_t* __restrict__ basis_out, uint8_t* in_basis,
                                                                    int32_t* __restrict__ trace, int64_t trace_cap, Tolerances tol,
-                                                                   const double* rmin, int nblk,
+                                                                   const double* rmin, int nblk, int nb_w_other,
                                                                    double* __restrict__ shadow, int32_t* __restrict__ shadow_meta,
                                                                    PivotRecord* rec, const double* __restrict__ msgs, int count,
                                                                    int64_t msg_len, int rule, int split) {
     const double first = (!msgs && (int)threadIdx.x < nblk) ? rmin[threadIdx.x] : INFINITY;      // in flight with the record
     PivotRecord R = *rec;
     const bool w_half = (int)blockIdx.x >= nb_row;
-    const int part = w_half ? ((int)blockIdx.x - nb_row) / nblk : 0;
-    const int wblock = (int)blockIdx.x - nb_row - part * nblk;
+    const int nb_w = RPB == kThreads ? nblk : nb_w_other;
+    const int part = w_half ? ((int)blockIdx.x - nb_row) / nb_w : 0;
+    const int wblock = (int)blockIdx.x - nb_row - part * nb_w;
     const int i = wblock * kThreads + threadIdx.x;
     // the loop has ended (or ends here): the double buffers still advance, because the host keeps swapping them
     const bool lead = w_half && part == 0;
@@ -392,7 +395,7 @@ __global__ __launch_bounds__(kThreads) void k_tab_ratio_update_all(TableauView t
         rmin = alpha + m;
     }
     int r, leaving;
-    ratio_blocks_pick<kThreads>(alpha, b_in, basis_in, m, tol, rmin, nblk, &r, &leaving, first, !msgs);
+    ratio_blocks_pick<kThreads>(alpha, b_in, basis_in, m, tol, rmin, nblk, &r, &leaving, first, !msgs, RPB);
     if (r < 0) {
         if (mine) { b_out[i] = b_in[i]; basis_out[i] = basis_in[i]; }
         if (lead && wblock == 0 && threadIdx.x == 0) rec->outcome = DEV_NO_ROW;
@@ -472,18 +475,29 @@ __global__ void k_tab_apply_shadow(DeferredUpdate du, double* __restrict__ shado
 // of the record; a rank without a candidate sends key = +inf and stays RUNNING (another rank may have one).
 // `rmin` (single-GPU loop): the minimum ratio b_i / alpha_i over this workgroup's 256 rows, for
 // k_ratio_blocks.
-template <int B>
+// R = rows per workgroup (256, 128 or 64; tab_column_rows), always 256 threads.  R = 256 is one thread per row walking all p
+// pending rows B at a time (tab_column_entry).  R < 256: S = 256 / R slices of R threads stand on the same R rows, thread t on
+// row blockIdx.x * R + t % R in slice t / R, and slice s owns the pending rows j in [s * ceil(p / S), (s + 1) * ceil(p / S)),
+// cut at p.  Every slice loads its whole share of W into NW registers at once (NW >= ceil(kmax / S), masked by p: nothing at
+// or past row p is read), so a row block has S times the loads in flight and a CU pulls 1 / S of the bytes.  The fma chain of a
+// row is then handed from slice to slice through s_acc: slice 0 starts from T0[i, q], each slice continues from the value its
+// predecessor left, in ascending j -- the operations and the order of tab_column_entry -- and an empty share passes the value
+// on untouched.  The last slice writes alpha and forms the ratios; rmin[blockIdx.x] is the minimum over the R rows (exact in
+// any order).  B is not used when R < 256.
+template <int B, int R, int NW>
 __global__ __launch_bounds__(kThreads) void k_tab_select_column(TableauView tv, DeferredUpdate du, SelectPartials sp,
                                                                 int count, double* alpha, double* msg,
                                                                 const double* b, Tolerances tol,
                                                                 double* rmin, PivotRecord* rec,
                                                                 const double* shadow, int32_t* shadow_meta) {
+    static_assert(R == 64 || R == 128 || R == kThreads, "whole wavefronts per slice");
+    constexpr int S = kThreads / R;
     const int outcome = rec->outcome, p = rec->n_eta;          // one round trip for both ...
     // ... and for the shadow row of the previous pivot's fused update: the workgroup that owns the row folds it into W before
     // it reads the row (no other workgroup reads it)
     if (shadow_meta) {
         const int srow = shadow_meta[0], slen = shadow_meta[1];
-        if (srow >= 0 && srow / kThreads == (int)blockIdx.x) {
+        if (srow >= 0 && srow / R == (int)blockIdx.x) {
             if ((int)threadIdx.x < slen) du.W[(int64_t)threadIdx.x * du.ld + srow] = shadow[threadIdx.x];
             __syncthreads();
             if (threadIdx.x == 0) shadow_meta[0] = -1;
@@ -494,8 +508,9 @@ __global__ __launch_bounds__(kThreads) void k_tab_select_column(TableauView tv, 
     double k1 = INFINITY;
     int bj = 0x7fffffff;
     if ((int)threadIdx.x < count) { k1 = sp.k1[threadIdx.x]; bj = sp.j[threadIdx.x]; }
-    const int i = blockIdx.x * kThreads + threadIdx.x;
-    const double b_i = (rmin && i < tv.m) ? b[i] : 0.0;
+    const int slice = R == kThreads ? 0 : (int)threadIdx.x / R;
+    const int i = blockIdx.x * R + (R == kThreads ? (int)threadIdx.x : (int)threadIdx.x % R);
+    const double b_i = (rmin && i < tv.m && slice == S - 1) ? b[i] : 0.0;
     if (outcome != DEV_RUNNING) return;
     __shared__ double s_vs[kMaxEta];
     tab_select_entering<kThreads>(tv, sp, count, k1, bj);
@@ -519,17 +534,55 @@ __global__ __launch_bounds__(kThreads) void k_tab_select_column(TableauView tv, 
             if (sp.rule == 1) rec->last_selected = bj;
         }
     }
-    if ((int)threadIdx.x < p) s_vs[threadIdx.x] = tv.R0[(int64_t)threadIdx.x * tv.ld_r + cq];
-    const double t0 = i < tv.m ? tv.T0[(int64_t)cq * tv.ld_t + i] : 0.0;     // in flight together with the R0 column
-    __syncthreads();
     double ratio = INFINITY;
-    if (i < tv.m) {
-        const double a = tab_column_entry<B>(du, i, p, s_vs, t0);
-        alpha[i] = a;
-        // the same expression as the ratio test's first pass (ratio_body), so min over the block minima is
-        // bit for bit the minimum over all rows
-        const double bz = b_i <= tol.zero ? 0.0 : b_i;
-        if (a > tol.pivot) ratio = bz / a;
+    if constexpr (R == kThreads) {
+        if ((int)threadIdx.x < p) s_vs[threadIdx.x] = tv.R0[(int64_t)threadIdx.x * tv.ld_r + cq];
+        const double t0 = i < tv.m ? tv.T0[(int64_t)cq * tv.ld_t + i] : 0.0;     // in flight together with the R0 column
+        __syncthreads();
+        if (i < tv.m) {
+            const double a = tab_column_entry<B>(du, i, p, s_vs, t0);
+            alpha[i] = a;
+            // the same expression as the ratio test's first pass (ratio_body), so min over the block minima is
+            // bit for bit the minimum over all rows
+            const double bz = b_i <= tol.zero ? 0.0 : b_i;
+            if (a > tol.pivot) ratio = bz / a;
+        }
+    } else {
+        // One round trip for the R0 column, T0[i, q] and this slice's whole share of the pending rows: the R0 entry goes to
+        // s_vs only after the loads of W have left, so no slice waits for anything before its own loads are on their way.
+        const double vq = (int)threadIdx.x < p ? tv.R0[(int64_t)threadIdx.x * tv.ld_r + cq] : 0.0;
+        double a = (i < tv.m && slice == 0) ? tv.T0[(int64_t)cq * tv.ld_t + i] : 0.0;
+        const int share = (p + S - 1) / S;
+        const int j_lo = min(slice * share, p);
+        const int cnt = i < tv.m ? min(share, p - j_lo) : 0;
+        const double* col = du.W + (int64_t)j_lo * du.ld + i;
+        double w[NW];
+#pragma unroll
+        for (int t = 0; t < NW; ++t) w[t] = t < cnt ? col[(int64_t)t * du.ld] : 0.0;
+        if ((int)threadIdx.x < p) s_vs[threadIdx.x] = vq;
+        __syncthreads();
+        // the share's entries of the R0 column into registers too, ahead of the hand-offs (an entry past the share is read
+        // inside s_vs and not used)
+        double v[NW];
+#pragma unroll
+        for (int t = 0; t < NW; ++t) v[t] = s_vs[min(j_lo + t, kMaxEta - 1)];
+        __shared__ double s_acc[R];
+        const int x = (int)threadIdx.x % R;
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            if (s > 0) __syncthreads();                // the value slice s - 1 left in s_acc
+            if (slice == s) {
+                if (s > 0) a = s_acc[x];
+#pragma unroll
+                for (int t = 0; t < NW; ++t) a = t < cnt ? fma(w[t], v[t], a) : a;
+                if (s < S - 1) s_acc[x] = a;
+            }
+        }
+        if (slice == S - 1 && i < tv.m) {
+            alpha[i] = a;
+            const double bz = b_i <= tol.zero ? 0.0 : b_i;     // (as above)
+            if (a > tol.pivot) ratio = bz / a;
+        }
     }
     if (!rmin) return;
     ratio = block_min_value<kThreads>(ratio);
@@ -1803,6 +1856,19 @@ int32_t tab_load_batch(int32_t wanted) {
     return (wanted == 1 || wanted == 8 || wanted == 16 || wanted == 32) ? wanted : kTabLoadBatchDefault;
 }
 
+// RELP_TAB_COLUMN_ROWS / DeferredUpdate::col_rows: 256, 128 and 64 are themselves; anything else is the smallest of them that
+// keeps the column kernel within one workgroup per CU (kTabSplitCUs).
+int32_t tab_column_rows(int32_t wanted, int32_t m) {
+    if (wanted == 64 || wanted == 128 || wanted == kThreads) return wanted;
+    for (int32_t rows : {64, 128})
+        if (cdiv(m, rows) <= kTabSplitCUs) return rows;
+    return kThreads;
+}
+
+// Rows per workgroup of k_tab_select_column and per minimum in rmin for this DeferredUpdate: 256 unless the caller asked for
+// 128 or 64.
+static int column_rows_of(const DeferredUpdate& du) { return du.col_rows == 64 || du.col_rows == 128 ? du.col_rows : kThreads; }
+
 // launch(std::integral_constant<int, B>) for B = tab_load_batch(batch)
 template <class Launch>
 static void with_load_batch(int32_t batch, Launch&& launch) {
@@ -1867,10 +1933,31 @@ void launch_tab_update_vectors(int32_t m, const double* alpha, double* b, int32_
 void launch_tab_select_column_rmin(const TableauView& tv, const DeferredUpdate& du, SelectPartials sp, int32_t count,
                                    double* alpha, const double* b, Tolerances tol, double* rmin, PivotRecord* rec,
                                    hipStream_t s, const double* shadow, int32_t* shadow_meta) {
-    with_load_batch(du.batch, [&](auto B) {
-        hipLaunchKernelGGL((k_tab_select_column<decltype(B)::value>), dim3(cdiv(tv.m, kThreads)), dim3(kThreads), 0, s, tv, du, sp, count, alpha,
-                           (double*)nullptr, b, tol, rmin, rec, shadow, shadow_meta);
-    });
+    const int rows = column_rows_of(du);
+    if (rows == kThreads) {
+        with_load_batch(du.batch, [&](auto B) {
+            hipLaunchKernelGGL((k_tab_select_column<decltype(B)::value, kThreads, 1>), dim3(cdiv(tv.m, kThreads)), dim3(kThreads), 0, s, tv, du, sp,
+                               count, alpha, (double*)nullptr, b, tol, rmin, rec, shadow, shadow_meta);
+        });
+        return;
+    }
+    // the registers of a slice hold its whole share of the pending rows: the smallest array that takes ceil(kmax / S)
+    const int need = cdiv(du.kmax, kThreads / rows);
+    static_assert(kMaxEta <= 2 * 64, "the largest array takes half of the pending rows");
+    auto launch = [&](auto R, auto NW) {
+        hipLaunchKernelGGL((k_tab_select_column<kTabLoadBatchDefault, decltype(R)::value, decltype(NW)::value>), dim3(cdiv(tv.m, rows)),
+                           dim3(kThreads), 0, s, tv, du, sp, count, alpha, (double*)nullptr, b, tol, rmin, rec, shadow, shadow_meta);
+    };
+    static_assert(kMaxEta <= 4 * 32, "32 registers take a quarter of the pending rows");
+    if (need <= 16) {
+        if (rows == 128) launch(std::integral_constant<int, 128>{}, std::integral_constant<int, 16>{});
+        else launch(std::integral_constant<int, 64>{}, std::integral_constant<int, 16>{});
+    } else if (need <= 32) {
+        if (rows == 128) launch(std::integral_constant<int, 128>{}, std::integral_constant<int, 32>{});
+        else launch(std::integral_constant<int, 64>{}, std::integral_constant<int, 32>{});
+    } else {
+        launch(std::integral_constant<int, 128>{}, std::integral_constant<int, 64>{});       // (two slices only)
+    }
 }
 
 void launch_tab_ratio_update_all(const TableauView& tv, const DeferredUpdate& du, SelectPartials sp, int32_t m,
@@ -1880,13 +1967,20 @@ void launch_tab_ratio_update_all(const TableauView& tv, const DeferredUpdate& du
                                  const double* msgs, int32_t count, int64_t msg_len, int32_t rule) {
     const int nb_row = tv.c_hi > tv.c_lo ? tab_scan_blocks(tv.c_hi - tv.c_lo) : 0;
     const int nb_w = cdiv(m, kThreads);
+    // the minima the column kernel left: one per 256 rows in a message, else one per column_rows_of(du) rows
+    const int rpb = msgs ? kThreads : column_rows_of(du);
     // the W half over `split` workgroups per 256 rows, as far as the whole grid still fits one workgroup per CU (past that
     // the extra workgroups queue behind the others and only repeat the ratio test); never under batch 1, the control
     int split = tab_load_batch(du.batch) == 1 ? 1 : std::max(1, std::min({(int)du.w_split, (int)du.kmax, (kTabSplitCUs - nb_row) / nb_w}));
+    auto launch = [&](auto B, auto RPB) {
+        hipLaunchKernelGGL((k_tab_ratio_update_all<decltype(B)::value, decltype(RPB)::value>), dim3(nb_row + split * nb_w), dim3(kThreads), 0, s,
+                           tv, du, sp, nb_row, m, alpha, b_in, b_out, basis_in, basis_out, in_basis, trace, trace_cap, tol, rmin,
+                           cdiv(m, rpb), nb_w, shadow, shadow_meta, rec, msgs, (int)count, msg_len, (int)rule, split);
+    };
     with_load_batch(du.batch, [&](auto B) {
-        hipLaunchKernelGGL((k_tab_ratio_update_all<decltype(B)::value>), dim3(nb_row + split * nb_w), dim3(kThreads), 0, s, tv, du, sp, nb_row, m,
-                           alpha, b_in, b_out, basis_in, basis_out, in_basis, trace, trace_cap, tol, rmin, nb_w, shadow,
-                           shadow_meta, rec, msgs, (int)count, msg_len, (int)rule, split);
+        if (rpb == 64) launch(B, std::integral_constant<int, 64>{});
+        else if (rpb == 128) launch(B, std::integral_constant<int, 128>{});
+        else launch(B, std::integral_constant<int, kThreads>{});
     });
 }
 
@@ -1904,7 +1998,7 @@ void launch_tab_select_column_msg(const TableauView& tv, const DeferredUpdate& d
                                   double* msg, const double* b, Tolerances tol, PivotRecord* rec, hipStream_t s,
                                   const double* shadow, int32_t* shadow_meta) {
     with_load_batch(du.batch, [&](auto B) {
-        hipLaunchKernelGGL((k_tab_select_column<decltype(B)::value>), dim3(cdiv(tv.m, kThreads)), dim3(kThreads), 0, s, tv, du, sp, count, msg + 3,
+        hipLaunchKernelGGL((k_tab_select_column<decltype(B)::value, kThreads, 1>), dim3(cdiv(tv.m, kThreads)), dim3(kThreads), 0, s, tv, du, sp, count, msg + 3,
                            msg, b, tol, msg + 3 + tv.m, rec, shadow, shadow_meta);
     });
 }

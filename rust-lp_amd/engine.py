@@ -145,6 +145,8 @@ _SIGNATURES = {
     "relp_flush": (C.c_int, [C.c_void_p]),
     "relp_update_block": (C.c_int32, [C.c_void_p]),
     "relp_tab_load_batch": (C.c_int32, [C.c_void_p]),
+    "relp_tab_column_rows": (C.c_int32, [C.c_void_p]),
+    "relp_tab_column_rows_for": (C.c_int32, [C.c_int32, C.c_int32]),
     "relp_tab_flush_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "relp_retab_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "relp_lu_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
@@ -783,6 +785,10 @@ class Tableau:
     def load_batch(self) -> int:
         """Tableau engine: pending rows the per-pivot kernels load per round trip (RELP_TAB_LOAD_BATCH at create)."""
         return self._lib.relp_tab_load_batch(self._h)
+
+    def column_rows(self) -> int:
+        """Tableau engine: rows per workgroup of the column kernel in the fused loop (RELP_TAB_COLUMN_ROWS at create)."""
+        return self._lib.relp_tab_column_rows(self._h)
 
     def flush_stats(self) -> Tuple[int, int]:
         """Tableau engine: (flushes, columns those flushes rewrote) since create."""
